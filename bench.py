@@ -22,6 +22,7 @@ mode of the N = 1 line (no data-path collective) and BASELINE config C4 (ellipti
 sharded over the ranks).
 
     python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 --dump-outputs DIR     # + what the last timed step returned, as .npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 """
@@ -148,7 +149,7 @@ def cpu_baseline(w, k_samples: int, sample_blocks: int = 8):
     then 1 warm-up + median of 5 at the best count."""
     import numpy as np
     from oracle import bt_oracle as O
-    from threadpoolctl import threadpool_limits
+    from threadpoolctl import threadpool_info, threadpool_limits
     nb = min(sample_blocks, w.n_blocks)
     ns = nb * w.block_size
     Qs = w.Q.tocsr()[:ns, :ns].tocsc()
@@ -163,7 +164,10 @@ def cpu_baseline(w, k_samples: int, sample_blocks: int = 8):
         X = O.sample(F, mu, Z)
         return time.perf_counter() - t0, t1 - t0, (mu, X)
 
-    ncpu = os.cpu_count() or 1
+    # the sweep stays within the cores this process may run on and within the BLAS thread pools as they were sized at load time
+    # (OMP_NUM_THREADS / OPENBLAS_NUM_THREADS, else every core): OpenBLAS crashes when it is asked for more threads than that
+    ncpu = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    ncpu = min([ncpu] + [p["num_threads"] for p in threadpool_info() if p.get("user_api") == "blas"])
     counts = sorted({c for c in (4, 8, 16, 32, 64, 128, ncpu) if c <= ncpu})
     sweep = {}
     for c in counts:
@@ -394,6 +398,10 @@ class ProblemsJob:
                 j_t.step(1 << 20)     # set-up, untimed: captures the sweep / sample graphs too, whatever --warmup is
             self.jobs.append((st_t, e_t, j_t))
         self.eng, self.job = self.jobs[0][1], self.jobs[0][2]
+        # keep_last: run() keeps what the LAST step of each handle returned, (means, samples), in self.last[t] (--dump-outputs);
+        # the other steps' outputs are dropped as they come, as without it
+        self.keep_last = False
+        self.last = [None] * n_streams
 
     def solves_per_step(self):
         return self.n_streams * self.batch * (1 + self.samples)
@@ -401,15 +409,18 @@ class ProblemsJob:
     def run(self, first, count):
         torch = self.torch
 
-        def worker(st_t, j_t):
+        def worker(t, st_t, j_t):
             with torch.cuda.stream(st_t):
                 for s in range(count):
-                    j_t.step(first + s)
+                    if self.keep_last and s == count - 1:
+                        self.last[t] = j_t.step(first + s)
+                    else:
+                        j_t.step(first + s)
                 st_t.synchronize()
         if len(self.jobs) == 1:
-            worker(self.jobs[0][0], self.jobs[0][2])
+            worker(0, self.jobs[0][0], self.jobs[0][2])
             return
-        ths = [threading.Thread(target=worker, args=(st_t, j_t)) for st_t, _, j_t in self.jobs]
+        ths = [threading.Thread(target=worker, args=(t, st_t, j_t)) for t, (st_t, _, j_t) in enumerate(self.jobs)]
         for th in ths:
             th.start()
         for th in ths:
@@ -425,6 +436,7 @@ class ProblemsJob:
                 "persist_refused": int(sum(x["persist_refused"] for x in st))}
 
     def close(self):
+        self.last = [None] * len(self.jobs)
         for _, e, _ in self.jobs:
             e.F.close()
         self.jobs = []
@@ -446,6 +458,43 @@ def timed(run, sync, dist, torch, first, steps):
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
     return elapsed
+
+
+DUMP_BYTES = {"mean": 16_000_000, "samples": 48_000_000}      # --dump-outputs: float64 bytes per array, 64 MB in all
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: write what the timed path returned in its last step as path/<name>.npy, float64.  `arrays` maps a name
+    to the per-handle device tensors whose concatenation along dimension 0 is the array (handle t's problems follow handle
+    t - 1's).  An array that fits its share of DUMP_BYTES is written whole, in its shape; a larger one as a fixed sample of its
+    entries in row-major order: the flat range is cut into m equal strata and stratum i gives the entry at a uniform offset
+    drawn by numpy.random.default_rng(<array's position in DUMP_BYTES>) -- the same entries for the same shape in every run.
+    Returns what the result line says about the files."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    rec = {}
+    for pos, (name, parts) in enumerate(arrays.items()):
+        shape = [sum(int(p.shape[0]) for p in parts)] + [int(d) for d in parts[0].shape[1:]]
+        total = int(np.prod(shape))
+        m = DUMP_BYTES[name] // 8
+        if total <= m:
+            vals = torch.cat([p.reshape(p.shape[0], -1) for p in parts]).cpu().numpy().reshape(shape)
+            rec[name] = {"shape": shape, "written": "whole"}
+        else:
+            i = np.arange(m, dtype=np.int64)
+            lo, hi = i * total // m, (i + 1) * total // m
+            idx = lo + (np.random.default_rng(pos).random(m) * (hi - lo)).astype(np.int64)
+            vals, off = np.empty(m, dtype=np.float64), 0
+            for p in parts:                      # each handle's tensor gives the entries of its flat range
+                sel = (idx >= off) & (idx < off + p.numel())
+                if sel.any():
+                    vals[sel] = torch.take(p.contiguous(), torch.from_numpy(idx[sel] - off).to(p.device)).cpu().numpy()
+                off += p.numel()
+            rec[name] = {"shape": shape, "written": f"sample of {m} entries (row-major order, one per stratum of {total // m}+ entries, "
+                                                    f"offsets from numpy.random.default_rng({pos}).random)"}
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(vals, dtype=np.float64))
+    return rec
 
 
 def spmm_roofline(pkg, torch):
@@ -522,7 +571,14 @@ def main():
                     help="rehearsal: run the shared-factor code (process group, communicator, broadcasts) with a world of one rank")
     ap.add_argument("--regimes", default="256,1024",
                     help="N > 1: further samples-per-rank-and-posterior regimes of the shared-factor job (side leg)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (means, samples of the independent-problems "
+                         "headline; rank 0) as DIR/mean.npy and DIR/samples.npy, float64, 64 MB at most (dump_outputs())")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.dump_outputs and (args.mode == "shared-factor" or args.force_shared):
+        ap.error("--dump-outputs writes the outputs of the independent-problems headline (not of --mode shared-factor / --force-shared)")
 
     # `python bench.py --gpus N` without a launcher: start the N ranks here (a torch.distributed.run child, spawned
     # before this process makes any GPU call) and relay their output and exit code.
@@ -698,7 +754,13 @@ def main():
                          args.eager_flags)
         eng, job = pj.eng, pj.job
         pj.run(0, args.warmup)
+        pj.keep_last = bool(args.dump_outputs)
         elapsed = timed(pj.run, sync, dist, torch, args.warmup, args.steps)
+        pj.keep_last = False
+        if args.dump_outputs and rank == 0:
+            extra["dump_outputs"] = dict(dir=args.dump_outputs, step=args.warmup + args.steps - 1, arrays=dump_outputs(
+                args.dump_outputs, {"mean": [r[0] for r in pj.last], "samples": [r[1] for r in pj.last]}))
+        pj.last = [None] * len(pj.jobs)
         per_step = world * pj.solves_per_step()
         workload = (f"{w.name}: n={w.n}, {w.n_blocks} blocks x {w.block_size}, nnz={w.Q.nnz}; {pj.n_streams * pj.batch} independent "
                     f"posterior(s) per GPU and step ({pj.n_streams} stream(s) x batch {pj.batch}), each factor + mean + {args.samples} samples")

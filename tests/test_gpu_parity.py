@@ -1165,17 +1165,14 @@ def test_schur_block_assembled_inside_the_coupling_launch(pkg):
         import gc; gc.collect()
 
 
-_ref16_cache = {}
-
-
 def F_ref16(F, res, rhs):
-    """16 samples with seed 6 by the launch-per-product form (computed once per handle)."""
-    key = id(F)
-    if key not in _ref16_cache:
+    """16 samples with seed 6 by the launch-per-product form (computed once per handle and kept in that handle's `res`:
+    a cache keyed by id(F) handed a freed handle's samples to the next handle allocated at the same address)."""
+    if "ref16" not in res:
         F.set_eager(65536)
-        _ref16_cache[key] = F.sample(16, mean=res["per_product"][0], seed=6, like=rhs)
+        res["ref16"] = F.sample(16, mean=res["per_product"][0], seed=6, like=rhs)
         F.set_eager(0)
-    return _ref16_cache[key]
+    return res["ref16"]
 
 
 def test_persistent_sweeps_of_one_problem_are_the_per_product_sweeps_bitwise(pkg):

@@ -75,6 +75,18 @@ static bool is_device_ptr(const void* p) {
     return attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged;
 }
 
+// Do the byte ranges [p, p + pb) and [q, q + qb) meet?  Addresses only: host and device pointers alike.
+static bool ranges_overlap(const void* p, int64_t pb, const void* q, int64_t qb) {
+    if (!p || !q || pb <= 0 || qb <= 0) return false;
+    const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
+    return a < b + (uintptr_t)qb && b < a + (uintptr_t)pb;
+}
+
+// bytes spanned by `cols` column-major columns of n doubles with leading dimension ld
+static int64_t cols_bytes(int64_t n, int64_t cols, int64_t ld) {
+    return cols <= 0 ? 0 : ((cols - 1) * ld + n) * (int64_t)sizeof(double);
+}
+
 static int64_t next_pow2(int64_t v) {
     int64_t p = 1;
     while (p < v) p <<= 1;
@@ -226,7 +238,7 @@ struct gmrf_handle {
     int sweep_nw = 0;
     double *d_P2 = nullptr, *d_Y2 = nullptr, *d_T2 = nullptr;     // gmrf_bt_posterior: the samples' panels (their sweep runs beside the mean's)
     int64_t p2_elems = 0;
-    bool sweep_persist_hold = false;      // this call must not use it (its input would be lost if the launch gave up: in-place solve)
+    bool sweep_persist_hold = false;      // this call must not use it (an input overlaps an output: a launch that gave up could not be repeated)
     bool no_persist_panels = false;    // batches small enough for it keep potrf_diag128 + the 128^3 products instead of one persistent launch per panel (set_eager bit 15)
     // second branch of the captured factor graph: the inverse assembly of a block's first half runs
     // beside the panel chain of its second half (see potrf_block)
@@ -2688,7 +2700,8 @@ gmrf_status gmrf_bt_solve(gmrf_handle* h, const double* b, double* y, int64_t k,
     const bool b_dev = is_device_ptr(b), y_dev = is_device_ptr(y);
     h->stats.solve_ms = 0.0;
     const int64_t nb = h->B;            // b / y hold nb consecutive groups of k columns (problem-major)
-    h->sweep_persist_hold = (b == y);   // (in place: a persistent sweep that gave up could not be repeated)
+    // b and y overlap (in place, or y a column further on): a persistent sweep that gave up could not be repeated from b
+    h->sweep_persist_hold = ranges_overlap(b, cols_bytes(h->n, k * nb, ldb), y, cols_bytes(h->n, k * nb, ldy));
     h->stats.sweep_persist = 0;
     for (int64_t c0 = 0; c0 < k; c0 += KP_CHUNK) {
         const int kc = (int)std::min<int64_t>(KP_CHUNK, k - c0);
@@ -2776,7 +2789,10 @@ gmrf_status gmrf_bt_sample(gmrf_handle* h, uint64_t seed, int64_t first_id, int6
     const double* d_mean = nullptr;
     GCHK(stage_vector(h, mean, &h->d_mean, &d_mean));
     const bool out_dev = is_device_ptr(out);
-    h->sweep_persist_hold = (z == out);
+    // z or the mean overlaps the output: the repeat after a persistent sweep that gave up would read what the first pass wrote
+    const int64_t out_bytes = cols_bytes(h->n, k * h->B, ld);
+    h->sweep_persist_hold = ranges_overlap(z, cols_bytes(h->n, k * h->B, ld), out, out_bytes) ||
+                            ranges_overlap(mean, h->n * h->B * (int64_t)sizeof(double), out, out_bytes);
     h->stats.sweep_persist = 0;
     HIPCHK(hipEventRecord(h->ev0, h->stream));
     for (int64_t c0 = 0; c0 < k; c0 += KP_CHUNK) {
@@ -2818,7 +2834,12 @@ gmrf_status gmrf_bt_posterior(gmrf_handle* h, const double* b, uint64_t seed, in
     HIPCHK(hipSetDevice(h->device));
     const int kp = pad_k(k);
     const bool dev_all = is_device_ptr(b) && is_device_ptr(mean) && is_device_ptr(samples);
-    const bool beside = h->B == 1 && k <= KP_CHUNK && k >= 2 && dev_all && b != mean && !h->profiling && sweep_persist_ok(h, 1) && sweep_persist_ok(h, kp);
+    // beside only when no two of b, mean, samples overlap (else the two calls, each with its own guard)
+    const int64_t vec_bytes = h->n * h->B * (int64_t)sizeof(double), smp_bytes = cols_bytes(h->n, k * h->B, ld);
+    h->sweep_persist_hold = ranges_overlap(b, vec_bytes, mean, vec_bytes) || ranges_overlap(b, vec_bytes, samples, smp_bytes) ||
+                            ranges_overlap(mean, vec_bytes, samples, smp_bytes);
+    h->stats.sweep_persist = 0;
+    const bool beside = h->B == 1 && k <= KP_CHUNK && k >= 2 && dev_all && !h->profiling && sweep_persist_ok(h, 1) && sweep_persist_ok(h, kp);
     if (!beside) {
         GCHK(gmrf_bt_solve(h, b, mean, 1, h->n, h->n, GMRF_SOLVE_FULL));
         return gmrf_bt_sample(h, seed, first_id, k, mean, nullptr, samples, ld);
@@ -4095,6 +4116,15 @@ static gmrf_status var_chunk(gmrf_handle* h, int method, int64_t p, int kc, cons
     return GMRF_OK;
 }
 
+// The sampled estimators' sweeps may be persistent launches (one problem, blocks of 512 .. 1024).  Their callers check for one
+// that gave up behind the synchronisation that ends the call and then repeat the whole call from its inputs, which they keep (the
+// accumulator as it came in): no synchronisation per chunk.  The first chunk that gave up leaves garbage in d_Y and raises the
+// abort words; the chunks after it drain at once and add more garbage, which the repeat discards.
+static void var_entry(gmrf_handle* h) {
+    h->sweep_persist_hold = false;
+    h->stats.sweep_persist = 0;
+}
+
 static gmrf_status var_accumulate_dev(gmrf_handle* h, int method, int64_t first_id, int64_t k, uint64_t seed,
                                       const gmrf_csr* Q, double* d_acc) {
     for (int64_t c0 = 0; c0 < k; c0 += 64) {
@@ -4114,16 +4144,27 @@ gmrf_status gmrf_bt_var_accumulate(gmrf_handle* h, int32_t method, int64_t first
     if (k <= 0) return bad_shape("k <= 0");
     GCHK(need_single(h));
     HIPCHK(hipSetDevice(h->device));
+    var_entry(h);
     const bool dev = is_device_ptr(acc);
-    double* d_acc = acc;
-    if (!dev) {
-        if (!h->d_acc) { HIPCHK(hipMalloc(&h->d_acc, sizeof(double) * h->n)); h->acc_B = 1; }
-        HIPCHK(hipMemcpyAsync(h->d_acc, acc, sizeof(double) * h->n, hipMemcpyHostToDevice, h->stream));
-        d_acc = h->d_acc;
-    }
+    if (!h->d_acc) { HIPCHK(hipMalloc(&h->d_acc, sizeof(double) * h->n)); h->acc_B = 1; }
+    // h->d_acc: the accumulator a host acc is summed in, or the copy of a device acc as it came in (for the repeat)
+    HIPCHK(hipMemcpyAsync(h->d_acc, acc, sizeof(double) * h->n, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
+    double* d_acc = dev ? acc : h->d_acc;
     GCHK(var_accumulate_dev(h, method, first_id, k, seed, Q, d_acc));
-    if (!dev) HIPCHK(hipMemcpyAsync(acc, d_acc, sizeof(double) * h->n, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
+    bool repeat = false;
+    GCHK(sweep_persist_check(h, &repeat));
+    if (repeat) {                                      // (once: the handle has left the persistent form)
+        if (dev) {
+            HIPCHK(hipMemcpyAsync(acc, h->d_acc, sizeof(double) * h->n, hipMemcpyDeviceToDevice, h->stream));
+            HIPCHK(hipStreamSynchronize(h->stream));
+        }
+        return gmrf_bt_var_accumulate(h, method, first_id, k, seed, Q, acc);
+    }
+    if (!dev) {
+        HIPCHK(hipMemcpyAsync(acc, d_acc, sizeof(double) * h->n, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+    }
     return GMRF_OK;
 }
 
@@ -4133,6 +4174,7 @@ gmrf_status gmrf_bt_marginal_var(gmrf_handle* h, int32_t method, int64_t k, uint
     if (!h->factored) { g_last_error = "variance before factor"; return GMRF_ERR_NO_FACTOR; }
     if (method != GMRF_VAR_EXACT) GCHK(need_single(h));    // sampled estimators: one problem per handle
     HIPCHK(hipSetDevice(h->device));
+    var_entry(h);
     if (!h->d_acc || h->acc_B < h->B) {
         free_dev(h->d_acc); h->d_acc = nullptr;
         HIPCHK(hipMalloc(&h->d_acc, sizeof(double) * h->n * h->B));
@@ -4164,6 +4206,9 @@ gmrf_status gmrf_bt_marginal_var(gmrf_handle* h, int32_t method, int64_t k, uint
     if (dev) HIPCHK(hipMemcpyAsync(d_out, d_fin, sizeof(double) * h->n, hipMemcpyDeviceToDevice, h->stream));
     else HIPCHK(hipMemcpyAsync(var_out, d_fin, sizeof(double) * h->n, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
+    bool repeat = false;
+    GCHK(sweep_persist_check(h, &repeat));
+    if (repeat) return gmrf_bt_marginal_var(h, method, k, seed, Q, var_out);      // (once: the handle has left the persistent form)
     if (h->profiling) prof_collect(h);
     return GMRF_OK;
 }
@@ -4181,6 +4226,7 @@ gmrf_status gmrf_bt_marginal_var_batch(gmrf_handle* h, int32_t method, int64_t k
     if (method == GMRF_VAR_RBMC && (!Q || Q->n_rows != h->n || Q->n_cols != h->n || !q_vals)) return bad_shape("RBMC needs the pattern of Q and its values per problem");
     if (k <= 0) return bad_shape("k <= 0");
     HIPCHK(hipSetDevice(h->device));
+    var_entry(h);
     const int64_t n = h->n, B = h->B;
     if (!h->d_acc || h->acc_B < B) {
         free_dev(h->d_acc); h->d_acc = nullptr;
@@ -4223,6 +4269,10 @@ gmrf_status gmrf_bt_marginal_var_batch(gmrf_handle* h, int32_t method, int64_t k
     }
     (void)hipStreamSynchronize(h->stream);
     free_dev(d_qv); free_dev(d_diag);
+    bool repeat = false;                               // (a batch of one: its sweeps may be persistent launches)
+    const gmrf_status cs = sweep_persist_check(h, &repeat);
+    if (st == GMRF_OK) st = cs;
+    if (st == GMRF_OK && repeat) return gmrf_bt_marginal_var_batch(h, method, k, seed, Q, q_vals, var_out);      // (once)
     return st;
 }
 

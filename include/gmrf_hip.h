@@ -104,8 +104,11 @@ typedef struct {
     int32_t persist_cus;          /* CUs this handle holds of its device's budget for persistent launches (every workgroup of such a
                                    * launch must be resident; the claims of all handles of a device never exceed its CU count) */
     int32_t persist_refused;      /* 1: the budget refused this handle's claim (other handles hold the CUs): no persistent launches */
-    int32_t sweep_persist;        /* 1: the last gmrf_bt_solve / gmrf_bt_sample ran its sweeps as ONE persistent launch each (one problem,
-                                   * blocks of 512 .. 1024, the handle holds the whole chip); a launch that gives up counts in persist_aborts */
+    int32_t sweep_persist;        /* 1: the last call that runs sweeps (gmrf_bt_solve, gmrf_bt_sample, gmrf_bt_posterior, the sampled
+                                   * gmrf_bt_marginal_var, gmrf_bt_var_accumulate, gmrf_bt_marginal_var_batch) ran them as ONE persistent
+                                   * launch each (one problem, blocks of 512 .. 1024, the handle holds the whole chip); a call whose inputs
+                                   * overlap its outputs keeps a launch per product (0); a launch that gives up counts in persist_aborts
+                                   * and the call is repeated with a launch per product */
     int32_t sweep_persist_launches;   /* such launches since the handle was created */
 } gmrf_stats;
 
@@ -146,14 +149,16 @@ gmrf_status gmrf_bt_refactor_values(gmrf_handle* h, const double* nzval, int32_t
  * mode FORWARD:  y = L^-1 b           forward_solve   (:43-52)
  * mode BACKWARD: y = L^-T b           backward_solve  (:24-33)
  * b, y: n x k column-major with leading dimensions ldb, ldy (a strided Julia view and a dense
- * result may differ); b == y (in place, as ldiv! allows) needs ldb == ldy. */
+ * result may differ); b == y (in place, as ldiv! allows) needs ldb == ldy.  Overlapping b and y (in place included) are
+ * well defined for k <= 128 and take the launch-per-product sweeps (stats.sweep_persist). */
 gmrf_status gmrf_bt_solve(gmrf_handle* h, const double* b, double* y, int64_t k,
                           int64_t ldb, int64_t ldy, int32_t mode);
 
 /* k samples  x_s = mean + L^-T z_s  (rand(rng, x_cond), solve_darcy_gmrf-fem.jl:191).
  * z == NULL: z_s[dof] is Philox4x32-10(key = seed, counter = (dof, first_id + s)) through
  * Box-Muller, independent of GPU count and launch geometry.  z != NULL: n x k column-major
- * standard normals supplied by the caller (parity mode).  mean may be NULL (zero). */
+ * standard normals supplied by the caller (parity mode).  mean may be NULL (zero).  z overlapping out (k <= 128), or
+ * mean == out with k = 1, is well defined and takes the launch-per-product sweeps. */
 gmrf_status gmrf_bt_sample(gmrf_handle* h, uint64_t seed, int64_t first_id, int64_t k,
                            const double* mean, const double* z, double* out, int64_t ld);
 
@@ -161,7 +166,8 @@ gmrf_status gmrf_bt_sample(gmrf_handle* h, uint64_t seed, int64_t first_id, int6
  * scripts/darcy/solve_darcy_gmrf-fem.jl:190-191 asks of one factor (`mean`, then `rand`).  Results bitwise those of
  * gmrf_bt_solve(mode 0) followed by gmrf_bt_sample(mean = that mean, z = NULL); where the sweeps of a handle are persistent
  * launches (one problem, blocks of 512 .. 1024, device pointers, 2 <= k <= 128) the samples' sweep runs BESIDE the mean's two on a
- * second stream.  b, mean: n doubles; samples: n x k column-major, leading dimension ld.  stats.solve_ms = the whole call. */
+ * second stream.  b, mean: n doubles; samples: n x k column-major, leading dimension ld.  stats.solve_ms = the whole call.
+ * If two of b, mean, samples overlap the call IS the two calls (each with its own guard against overlap). */
 gmrf_status gmrf_bt_posterior(gmrf_handle* h, const double* b, uint64_t seed, int64_t first_id, int64_t k,
                               double* mean, double* samples, int64_t ld);
 

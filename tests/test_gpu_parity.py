@@ -1322,9 +1322,10 @@ def test_persistent_sweeps_under_uneven_load(pkg):
 
 def test_persistent_sweep_abort_falls_back(pkg):
     """The safety net of the persistent sweeps: every wait for an input panel is bounded; a wave that gives up raises the abort
-    words, every other wait ends on them, the launch drains; gmrf_bt_solve / gmrf_bt_sample see the (mapped host) word behind
-    their own synchronisation and repeat the call with a launch per product, which the handle keeps (stats.persist_aborts, claim
-    released).  Forced in a child process with GMRF_SWEEP_SPIN_MS=0: results bitwise those of the launch-per-product form."""
+    words, every other wait ends on them, the launch drains; gmrf_bt_solve / gmrf_bt_sample / gmrf_bt_posterior and the sampled
+    variances see the (mapped host) word behind their own synchronisation and repeat the call with a launch per product, which the
+    handle keeps (stats.persist_aborts, claim released); aliased calls keep that form from the start.  Forced in a child process
+    with GMRF_SWEEP_SPIN_MS=0: results bitwise those of the launch-per-product form."""
     import json
     import subprocess
     import sys
@@ -1339,6 +1340,271 @@ def test_persistent_sweep_abort_falls_back(pkg):
     assert out["route_after_refactor"] == 0 and out["aborts_of_the_per_product_form"] == 0, out
     assert out["solve_equal"] and out["sample_equal"], out
     assert out["sample_first"] == {"persist_aborts": 1, "persist_cus": 0, "sweep_persist": 0} and out["sample_first_equal"], out
+    # the sampled variances (gmrf_bt_marginal_var, gmrf_bt_var_accumulate, gmrf_bt_marginal_var_batch on a batch of one) and two
+    # aliased calls, each the first persistent sweep of a fresh handle: bitwise the per-product handle's results; where a persistent
+    # launch ran it gave up once and the handle let go of the chip (the aliased sample keeps the per-product form from the start)
+    for name in ("var_mc_65", "var_rbmc_50", "var_accumulate_mc_dev", "var_accumulate_rbmc_host", "var_batch_rbmc_65",
+                 "sample_mean_is_out", "posterior_b_in_samples"):
+        r = out[name]
+        assert r["equal"] and r["persist_cus_before"] == 256 and r["persist_aborts"] <= 1, (name, r)
+        assert r["launches"] == 0 or (r["persist_aborts"] == 1 and r["persist_cus"] == 0), (name, r)
+        if not name.startswith("sample"):
+            assert r["launches"] > 0, (name, r)
+
+
+# ---- the persistent sweeps (one problem, blocks of 512 .. 1024) against a float64 reference, and with aliased arguments
+_PERSIST_REF = {}
+
+
+def _persist_case(pkg, name):
+    """(w, Fo, tol, F): the oracle factor (kept per workload: plain NumPy) and a FRESH one-problem handle that holds the whole chip,
+    so that its sweeps are persistent launches (the caller closes it: the next fresh handle needs the chip)."""
+    if name not in _PERSIST_REF:
+        w = pkg.workloads.make(name)
+        if name == "darcy256":
+            w.meta.setdefault("cond", 3.4e9)       # (as in test_config_darcy256_against_oracle: eigsh at n = 65536 takes minutes)
+        _PERSIST_REF[name] = (w, O.tridiagonal_cholesky(w.Q, w.n_blocks), solve_tol(w))
+    w, Fo, tol = _PERSIST_REF[name]
+    F = pkg.tridiagonal_cholesky(w.Q, w.n_blocks)
+    st = F.stats()
+    assert st["persist_cus"] == 256 and st["persist_refused"] == 0, (name, st)
+    return w, Fo, tol, F
+
+
+def _release(F):
+    import gc
+    F.close()
+    gc.collect()
+
+
+@pytest.mark.parametrize("name", ["burgers512x64", "darcy256"])
+def test_persistent_sampled_variances_against_float64_reference(pkg, name):
+    """RBMCStrategy(k) and plain MC variances (`std(x_cond)`, scripts/darcy/solve_darcy_gmrf-fem.jl:192) where the samples' sweeps
+    are persistent launches: against the float64 oracle on the same Philox draws, for k = 1 (the k = 1 body), 17 (a padded 32-wide
+    panel), 50 (the padded 64-wide panel of RBMCStrategy(50)), 64, 65 (64 + a k = 1 tail chunk) and 130 (three chunks); bitwise the
+    launch-per-product form; the statistics say which form ran and count one launch per chunk of 64.  Then into a device tensor, and
+    sharded over two calls of var_accumulate (host and device accumulators) against the one-shot estimator."""
+    import torch
+    w, Fo, tol, F = _persist_case(pkg, name)
+    try:
+        Q = pkg.CsrMatrix(w.Q)
+        seed = 41
+        X130 = O.backward_solve(Fo, F.normals(130, seed=seed))      # (Philox draws: the first k columns are the draws of k samples)
+        # MC at k = 1 is x^2, arbitrarily close to zero at some node: its error is taken against the node's variance (130 samples)
+        scale = O.marginal_variances_mc(X130)
+        one_shot = {}
+        for k in (1, 17, 50, 64, 65, 130):
+            X = X130[:, :k]
+            for method in ("rbmc", "mc"):
+                kw = dict(k=k, seed=seed, Q=Q) if method == "rbmc" else dict(k=k, seed=seed)
+                ref = O.marginal_variances_rbmc(w.Q, X) if method == "rbmc" else O.marginal_variances_mc(X)
+                n0 = F.stats()["sweep_persist_launches"]
+                v = F.marginal_var(method, **kw)
+                st = F.stats()
+                assert st["sweep_persist"] == 1 and st["sweep_persist_launches"] - n0 == -(-k // 64), (name, method, k, st)
+                den = ref if method == "rbmc" else np.maximum(ref, scale)
+                err = float(np.max(np.abs(v - ref) / den))
+                assert err < 4.0 * tol, (name, method, k, err, tol)             # squares of samples that agree to tol
+                F.set_eager(65536)
+                v_pp = F.marginal_var(method, **kw)
+                st_pp = F.stats()
+                F.set_eager(0)
+                assert st_pp["sweep_persist"] == 0 and st_pp["sweep_persist_launches"] == st["sweep_persist_launches"], (name, method, k)
+                assert np.array_equal(v, v_pp), (name, method, k)
+                one_shot[(method, k)] = v
+        out = torch.full((w.n,), float("nan"), dtype=torch.float64, device="cuda")
+        F.marginal_var("rbmc", k=50, seed=seed, Q=Q, out=out)
+        assert F.stats()["sweep_persist"] == 1
+        assert np.array_equal(out.cpu().numpy(), one_shot[("rbmc", 50)]), name
+        # sharded: samples [0, 70) then [70, 130) into one accumulator
+        inv_d = 1.0 / sp.csr_matrix(w.Q).diagonal()
+        for method in ("mc", "rbmc"):
+            for on_dev in (False, True):
+                acc = torch.zeros(w.n, dtype=torch.float64, device="cuda") if on_dev else np.zeros(w.n)
+                F.var_accumulate(acc, method, 0, 70, seed=seed, Q=Q if method == "rbmc" else None)
+                assert F.stats()["sweep_persist"] == 1
+                F.var_accumulate(acc, method, 70, 60, seed=seed, Q=Q if method == "rbmc" else None)
+                a = acc.cpu().numpy() if on_dev else acc
+                v = a / 130.0 + (inv_d if method == "rbmc" else 0.0)
+                ref = one_shot[(method, 130)]
+                assert float(np.max(np.abs(v - ref) / ref)) < 1e-12, (name, method, on_dev)
+        assert F.stats()["persist_aborts"] == 0
+    finally:
+        _release(F)
+
+
+@pytest.mark.parametrize("name", ["burgers512x64", "darcy256"])
+def test_persistent_sweeps_c_abi_leading_dimensions_and_mixed_k(pkg, lib, name):
+    """Straight through the C ABI on the persistent sweeps: n x k right-hand sides with ld = n + 7 (host and device memory), the
+    three solve modes and samples with a given z, k changing from call to call on one handle (1, 2, 16, 17, 64, 128, 129: the
+    k = 1 body, padded panels, one chunk of 128, 128 + 1).  Against the oracle; bitwise the same calls with a launch per product;
+    the NaN padding of the leading dimension is neither read into the result nor written."""
+    import torch
+    w, Fo, tol, F = _persist_case(pkg, name)
+    cabi = pkg._cabi
+    try:
+        n, ld = w.n, w.n + 7
+        rng = np.random.default_rng(5)
+        mu = O.ldiv(Fo, w.rhs)
+        mu_dev = torch.from_numpy(mu).cuda()
+        oracle = {cabi.SOLVE_FULL: O.ldiv, cabi.SOLVE_FORWARD: O.forward_solve, cabi.SOLVE_BACKWARD: O.backward_solve}
+
+        def padded(M, dev):
+            buf = np.full((M.shape[1], ld), np.nan)
+            buf[:, :n] = M.T
+            return torch.from_numpy(buf).cuda() if dev else buf
+
+        def fetch(buf):
+            return buf.cpu().numpy() if isinstance(buf, torch.Tensor) else buf
+
+        def both_forms(call, dev, k):
+            """call(out) on the persistent form and on the launch-per-product form; the first result (host array)"""
+            res = []
+            for bits in (0, 65536):
+                F.set_eager(bits)
+                out = padded(np.full((n, k), np.nan), dev)
+                n0 = F.stats()["sweep_persist_launches"]
+                cabi.check(call(out))
+                st = F.stats()
+                assert st["sweep_persist"] == (1 if bits == 0 else 0), (name, k, bits, st["sweep_persist"])
+                assert (st["sweep_persist_launches"] > n0) == (bits == 0), (name, k, bits)
+                res.append(fetch(out))
+            F.set_eager(0)
+            a, b = res
+            assert np.array_equal(a[:, :n], b[:, :n]), (name, k, dev)
+            assert np.all(np.isnan(a[:, n:])) and np.all(np.isnan(b[:, n:])), (name, k, dev)
+            return a[:, :n].T
+
+        for k in (1, 2, 16, 17, 64, 128, 129, 1):
+            B = rng.standard_normal((n, k))
+            for dev in (False, True):
+                b = padded(B, dev)
+                b0 = fetch(b).copy()
+                for mode in (cabi.SOLVE_FULL, cabi.SOLVE_FORWARD, cabi.SOLVE_BACKWARD):
+                    y = both_forms(lambda out: lib.gmrf_bt_solve(F._h, cabi.ptr(b), cabi.ptr(out), k, ld, ld, mode), dev, k)
+                    assert rel(y, oracle[mode](Fo, B)) < tol, (name, k, dev, mode)
+                # samples mean + L^-T z with the caller's z (ld > n) and the oracle's mean
+                m = mu_dev if dev else mu
+                x = both_forms(lambda out: lib.gmrf_bt_sample(F._h, 0, 0, k, cabi.ptr(m), cabi.ptr(b), cabi.ptr(out), ld), dev, k)
+                assert rel(x, O.sample(Fo, mu, B)) < tol, (name, k, dev)
+                assert np.array_equal(fetch(b), b0, equal_nan=True), (name, k, dev)       # the inputs are not written
+        assert F.stats()["persist_aborts"] == 0
+    finally:
+        _release(F)
+
+
+@pytest.mark.parametrize("name", ["burgers512x64", "darcy256"])
+def test_persistent_sweeps_with_aliased_arguments(pkg, lib, name):
+    """Arguments that overlap (well defined with a launch per product for k <= 128: every input is packed whole into the panels
+    before any output is written): a sample whose mean IS its output (k = 1), a sample whose z lies one column before its output,
+    a solve whose y lies one column after b, a posterior whose b is column 0 of its samples.  Each is bitwise the same aliased call
+    with a launch per product (these calls keep that form: a persistent launch that gave up could not be repeated from inputs it
+    has overwritten); the samples agree with the oracle."""
+    import torch
+    w, Fo, tol, F = _persist_case(pkg, name)
+    cabi = pkg._cabi
+    try:
+        n, ld, k, seed = w.n, w.n + 5, 16, 23
+        mu_o = O.ldiv(Fo, w.rhs)
+        rhs = torch.from_numpy(w.rhs).cuda()
+        mu = pkg.ldiv(F, rhs).cpu().numpy()
+        z1 = F.normals(1, seed=seed)
+        Z = np.random.default_rng(8).standard_normal((n, k))
+
+        def fetch(buf):
+            return buf.cpu().numpy() if isinstance(buf, torch.Tensor) else buf.copy()
+
+        def both_forms(run):
+            res = [None, None]
+            for i, bits in enumerate((0, 65536)):
+                F.set_eager(bits)
+                res[i] = run()
+            F.set_eager(0)
+            return res
+
+        for dev in (False, True):
+            wrap = (lambda a: torch.from_numpy(a).cuda()) if dev else (lambda a: a)
+
+            def mean_is_out():
+                buf = wrap(mu.copy())
+                cabi.check(lib.gmrf_bt_sample(F._h, seed, 0, 1, cabi.ptr(buf), None, cabi.ptr(buf), n))
+                return fetch(buf)
+            a, b = both_forms(mean_is_out)
+            assert np.array_equal(a, b), (name, dev)
+            assert rel(a, mu_o + O.backward_solve(Fo, z1)[:, 0]) < tol, (name, dev)
+
+            def z_before_out():
+                buf = np.full((k + 1, ld), np.nan)
+                buf[:k, :n] = Z.T
+                buf = wrap(buf)
+                base = buf.data_ptr() if dev else buf.ctypes.data
+                mean = wrap(mu.copy())
+                cabi.check(lib.gmrf_bt_sample(F._h, 0, 0, k, cabi.ptr(mean), cabi.ptr(base), cabi.ptr(base + 8 * ld), ld))
+                return fetch(buf)
+            a, b = both_forms(z_before_out)
+            assert np.array_equal(a, b, equal_nan=True), (name, dev)
+            assert np.all(np.isnan(a[:, n:])), (name, dev)
+            assert rel(a[1:, :n].T, O.sample(Fo, mu_o, Z)) < tol, (name, dev)
+
+            def y_after_b():
+                buf = np.full((k + 1, ld), np.nan)
+                buf[:k, :n] = Z.T
+                buf = wrap(buf)
+                base = buf.data_ptr() if dev else buf.ctypes.data
+                cabi.check(lib.gmrf_bt_solve(F._h, cabi.ptr(base), cabi.ptr(base + 8 * ld), k, ld, ld, cabi.SOLVE_FULL))
+                return fetch(buf)
+            a, b = both_forms(y_after_b)
+            assert np.array_equal(a, b, equal_nan=True), (name, dev)
+            assert rel(a[1:, :n].T, O.ldiv(Fo, Z)) < tol, (name, dev)
+
+        # posterior, b = column 0 of the samples (device memory: where the samples' sweep may run beside the mean's)
+        mu_ref = pkg.ldiv(F, rhs)
+        X_ref = F.sample(k, mean=mu_ref, seed=seed, like=rhs)
+
+        def b_in_samples():
+            samples = torch.full((k, n), float("nan"), dtype=torch.float64, device="cuda")
+            samples[0] = rhs
+            mean = torch.empty(n, dtype=torch.float64, device="cuda")
+            cabi.check(lib.gmrf_bt_posterior(F._h, cabi.ptr(samples[0]), seed, 0, k, cabi.ptr(mean), cabi.ptr(samples), n))
+            return mean, samples
+        (ma, sa), (mb, sb) = both_forms(b_in_samples)
+        assert torch.equal(ma, mb) and torch.equal(sa, sb), name
+        assert torch.equal(ma, mu_ref) and torch.equal(sa, X_ref.t()), name
+        assert F.stats()["persist_aborts"] == 0
+    finally:
+        _release(F)
+
+
+@pytest.mark.parametrize("name", ["burgers512x64", "darcy256"])
+def test_persistent_route_does_not_depend_on_the_previous_call(pkg, name):
+    """An in-place solve keeps the launch-per-product form for ITSELF only: the variances and the one-call posterior that follow
+    run their sweeps as persistent launches again (sweep_persist says so), with results bitwise those of the per-product form; the
+    posterior runs the samples' sweep beside the mean's (its sample_ms is 0: the call is not solve + sample)."""
+    import torch
+    w, Fo, tol, F = _persist_case(pkg, name)
+    try:
+        rhs = torch.from_numpy(w.rhs).cuda()
+        F.set_eager(65536)
+        mu_ref = pkg.ldiv(F, rhs)
+        X_ref = F.sample(16, mean=mu_ref, seed=7, like=rhs)
+        v_ref = F.marginal_var("mc", k=64, seed=5)
+        F.set_eager(0)
+        buf = rhs.clone()
+        F._solve(buf, pkg._cabi.SOLVE_FULL, out=buf)                               # in place
+        assert F.stats()["sweep_persist"] == 0 and torch.equal(buf, mu_ref)
+        v = F.marginal_var("mc", k=64, seed=5)
+        assert F.stats()["sweep_persist"] == 1, name
+        assert np.array_equal(v, v_ref), name
+        buf = rhs.clone()
+        F._solve(buf, pkg._cabi.SOLVE_FULL, out=buf)
+        assert F.stats()["sweep_persist"] == 0
+        mu, X = F.posterior(rhs, 16, seed=7)
+        st = F.stats()
+        assert st["sweep_persist"] == 1 and st["sample_ms"] == 0.0, (name, st["sweep_persist"], st["sample_ms"])
+        assert torch.equal(mu, mu_ref) and torch.equal(X, X_ref), name
+        assert st["persist_aborts"] == 0
+    finally:
+        _release(F)
 
 
 def test_inverse_rows_inside_the_fused_steps(pkg):

@@ -17,12 +17,20 @@ every finished range of Linv / C blocks is broadcast over RCCL (the library's ow
 gmrf_comm_*; torch.distributed if that cannot be set up) while the next range is being factored --
 and the samples sharded: every rank takes the means and draws ITS OWN 64 samples per posterior.
 value = B_shared * (1 + 64 N) * steps / time (B_shared = 32 posteriors per step: the root factors them as one
-batch, 2.6 ms per posterior, and 0.83 GB per posterior cross xGMI).  Beside it, in the same run: the independent-problems
-mode of the N = 1 line (no data-path collective) and BASELINE config C4 (elliptic 512^2, 256 samples
+batch, 2.6 ms per posterior, and 0.83 GB per posterior cross xGMI).  With --full, beside it in the same run: the
+independent-problems mode of the N = 1 line (no data-path collective) and BASELINE config C4 (elliptic 512^2, 256 samples
 sharded over the ranks).
+
+A plain run does what the headline needs and nothing more: set-up, --warmup steps, --steps timed steps, the outputs of
+the last one if --dump-outputs is given, the result line.  --full adds everything else the benchmark measures and checks,
+after the timed steps: at N = 1 one instrumented step (per-kernel times, roofline figures, GEMM launches by shape), the
+phase times, the batch-1 latency, the reference's whole per-problem loop, the K6 SpMM roofline, the CPU baselines and the
+oracle parity of the timed route (--no-single-problem, --no-full-loop, --no-spmm and --no-cpu-baseline leave legs out);
+at N > 1 the side legs (--no-side-legs).
 
     python bench.py --gpus 1 --steps 20 --warmup 3
     python bench.py --gpus 1 --steps 20 --warmup 3 --dump-outputs DIR     # + what the last timed step returned, as .npy
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full                 # + every other leg
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 """
@@ -551,7 +559,7 @@ def main():
                     help="independent batched handles per GPU, each on its own HIP stream and host thread")
     ap.add_argument("--mode", choices=["auto", "problems", "shared-factor"], default="auto",
                     help="headline workload.  auto = problems: independent posteriors per rank at every N (the shared-factor job "
-                         "then runs as side legs at N > 1); shared-factor: rank 0 factors, broadcast, samples sharded")
+                         "then runs as side legs at N > 1 with --full); shared-factor: rank 0 factors, broadcast, samples sharded")
     ap.add_argument("--shared-batch", type=int, default=32, help="posteriors per step whose factor is shared (N > 1)")
     ap.add_argument("--group", type=int, default=8, help="blocks per broadcast range (shared-factor)")
     ap.add_argument("--share", choices=["broadcast", "allgather"], default="allgather",
@@ -559,12 +567,16 @@ def main():
                          "the block ranges are all-gathered (round 4; both run as side legs at N > 1)")
     ap.add_argument("--keep-l", action="store_true", help="retain the L blocks (F.chos); default: only Linv and C are stored")
     ap.add_argument("--transport", choices=["auto", "cabi", "torch"], default="auto")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, every other leg of the benchmark (N = 1: instrumented step, roofline, phase times, "
+                         "batch-1 latency, whole-loop, K6 SpMM, CPU baselines, oracle parity; N > 1: the side legs).  Off: the "
+                         "headline alone")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines and the oracle parity leg")
     ap.add_argument("--no-single-problem", action="store_true",
-                    help="skip the batch-1 latency probe (profile runs: keeps one launch shape per kernel)")
-    ap.add_argument("--no-spmm", action="store_true", help="skip the K6 roofline leg (burgers4096x512 matrix)")
-    ap.add_argument("--no-full-loop", action="store_true", help="skip the leg that times the reference's whole per-problem loop")
-    ap.add_argument("--no-side-legs", action="store_true", help="N > 1: skip the problems-mode and C4 legs")
+                    help="--full: skip the batch-1 latency probe (profile runs: keeps one launch shape per kernel)")
+    ap.add_argument("--no-spmm", action="store_true", help="--full: skip the K6 roofline leg (burgers4096x512 matrix)")
+    ap.add_argument("--no-full-loop", action="store_true", help="--full: skip the leg that times the reference's whole per-problem loop")
+    ap.add_argument("--no-side-legs", action="store_true", help="--full, N > 1: skip the side legs")
     ap.add_argument("--side-leg-limit", type=float, default=360.0, help="N > 1: seconds after which the side legs are abandoned")
     ap.add_argument("--eager-flags", type=int, default=0, help="gmrf_bt_set_eager bits for every handle (experiments)")
     ap.add_argument("--force-shared", action="store_true",
@@ -625,10 +637,10 @@ def main():
     torch.cuda.set_device(local)
     # Headline at every N: independent posteriors per rank (the BASELINE single-GPU config on every GPU, no data-path
     # collective: ONE weak-scaling series).  The shared-factor job of north_star (rank 0 factors, the factor crosses xGMI,
-    # samples sharded) runs in the same invocation as side legs at N > 1; --mode shared-factor makes it the headline.
+    # samples sharded) runs in the same invocation as side legs at N > 1 with --full; --mode shared-factor makes it the headline.
     mode = args.mode if args.mode != "auto" else ("shared-factor" if args.force_shared else "problems")
     shared = mode == "shared-factor" and (world > 1 or args.force_shared)
-    shared_legs = (world > 1 or args.force_shared) and not args.no_side_legs       # the shared-factor job runs somewhere
+    shared_legs = (world > 1 or args.force_shared) and args.full and not args.no_side_legs       # the shared-factor job runs somewhere
     keep_l = bool(args.keep_l)
 
     def sync():
@@ -946,8 +958,17 @@ def main():
         pj.close()
         pj = None
 
-    # ------------------------------------------------------------------ N = 1: per-kernel roofline + parity + CPU baseline
-    if rank == 0 and world == 1 and not shared:
+    # ------------------------------------------------------------------ N = 1, plain run: what the timed handles' persistent
+    # launches did (a counter read, no further launch), then their HBM back
+    if rank == 0 and world == 1 and not shared and not args.full:
+        ps = pj.persist_state()
+        out["persist_aborts"] = ps["persist_aborts"]
+        out["persist"] = ps
+        pj.close()
+        pj = None
+
+    # ------------------------------------------------------------------ N = 1, --full: per-kernel roofline + parity + CPU baseline
+    if rank == 0 and world == 1 and not shared and args.full:
         eng.F.set_profiling(1)
         with torch.cuda.stream(pj.jobs[0][0]):
             job.step(10_000)

@@ -1810,6 +1810,40 @@ def test_measured_path_elliptic512_batch8_against_oracle(pkg):
     assert r["var_rbmc_max_rel"] < 4.0 * tol, r
 
 
+def test_bench_plain_line_and_full_legs(tmp_path):
+    """bench.py as a child on a small job (darcy64, one stream x batch 8): a plain run is the headline alone -- its line says
+    what the timed steps did (value x ms_per_step = the solves of one step), --dump-outputs writes the last step's means and
+    samples, and none of the legs --full adds has run; --full adds them after the timed steps (here the instrumented step,
+    its roofline and the phase times: the costlier legs are left out by their --no-* options)."""
+    import json
+    import subprocess
+    import sys
+    bench = _os.path.join(_os.path.dirname(_os.path.dirname(_os.path.abspath(__file__))), "bench.py")
+    job = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--config", "darcy64", "--streams", "1", "--batch", "8"]
+    added = ("roofline", "kernels", "phases_ms", "gemm_by_shape", "single_problem", "full_loop", "roofline_spmm", "cpu_baseline", "parity")
+
+    def run(*extra):
+        r = subprocess.run([sys.executable, bench] + job + list(extra), capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+        return json.loads(r.stdout.strip().splitlines()[-1])
+
+    plain = run("--dump-outputs", str(tmp_path))
+    assert plain["unit"] == "solves/s" and plain["higher_is_better"] is True and plain["dtype"] == "f64"
+    assert plain["steps"] == 2 and plain["warmup"] == 1 and plain["value"] > 0
+    assert abs(plain["value"] * plain["ms_per_step"] * 1e-3 - 8 * 65) < 1e-6 * 8 * 65
+    assert plain["persist_aborts"] == 0
+    assert not [k for k in added if k in plain], sorted(plain)
+    mean, samples = np.load(tmp_path / "mean.npy"), np.load(tmp_path / "samples.npy")
+    assert mean.shape == (8, 64 * 64) and samples.shape == (8, 64, 64 * 64)
+    assert np.isfinite(mean).all() and np.isfinite(samples).all()
+    full = run("--full", "--no-single-problem", "--no-full-loop", "--no-spmm", "--no-cpu-baseline")
+    assert full["unit"] == "solves/s" and full["value"] > 0
+    for k in ("roofline", "kernels", "phases_ms", "gemm_by_shape"):
+        assert k in full, sorted(full)
+    for k in ("single_problem", "full_loop", "roofline_spmm", "cpu_baseline", "parity"):
+        assert k not in full, sorted(full)
+
+
 def test_exact_variance_error_not_worse_than_lapack(pkg):
     """Why the exact-variance gate at darcy256 is cond-aware (7.5e-9 instead of BASELINE.md's flat 1e-9): entries of
     diag(Q^-1) in extended precision (columns Q^-1 e_i refined with long-double residuals, 24 interior nodes of the

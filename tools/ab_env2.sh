@@ -2,7 +2,7 @@
 # A/B of environment settings on the bench job within ONE gpurun call: tools/ab_env2.sh <outdir> "VAR=v,VAR2=w" "VAR=x" ...
 OUT=gpurun_out/$1; mkdir -p $OUT; shift
 for cfg in "$@"; do
-  env $(echo $cfg | tr ',' ' ') timeout -k 10 300 python bench.py --steps 8 --warmup 2 --no-cpu-baseline --no-spmm --no-single-problem --no-full-loop 2>$OUT/err.log | python3 -c "
+  env $(echo $cfg | tr ',' ' ') timeout -k 10 300 python bench.py --full --steps 8 --warmup 2 --no-cpu-baseline --no-spmm --no-single-problem --no-full-loop 2>$OUT/err.log | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 k=d['kernels']

@@ -10,7 +10,7 @@ if [ -n "$2" ]; then KEXPR=(-k "$2"); else KEXPR=(); fi
 timeout -k 10 1100 python -m pytest tests -x -q -m gpu "${KEXPR[@]}" > $OUT/pytest.log 2>&1 || { tail -60 $OUT/pytest.log | cut -c1-400; exit 1; }
 tail -3 $OUT/pytest.log
 if [ "$3" = "bench" ]; then
-  timeout -k 10 500 python bench.py > $OUT/bench_line_default.json 2> $OUT/bench.err || { tail -20 $OUT/bench.err; exit 1; }
+  timeout -k 10 500 python bench.py --full > $OUT/bench_line_default.json 2> $OUT/bench.err || { tail -20 $OUT/bench.err; exit 1; }
   python - <<PY
 import json
 d = json.loads(open("$OUT/bench_line_default.json").read().strip().splitlines()[-1])

@@ -4,11 +4,11 @@
 set -o pipefail
 R=$GRAFT_REPO_ROOT; P=$R/gpurun_out/${1:-r5traces}; mkdir -p $P
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $P/trace_c4 -- python3 $R/bench.py --config elliptic512 --batch 8 --streams 1 --steps 2 --warmup 1 --no-cpu-baseline --no-spmm --no-full-loop --no-single-problem > $P/c4_1stream_under_rocprof.json 2> $P/trace_c4.err || { echo "c4 trace failed"; tail -5 $P/trace_c4.err; exit 1; }
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $P/trace_c4 -- python3 $R/bench.py --full --config elliptic512 --batch 8 --streams 1 --steps 2 --warmup 1 --no-cpu-baseline --no-spmm --no-full-loop --no-single-problem > $P/c4_1stream_under_rocprof.json 2> $P/trace_c4.err || { echo "c4 trace failed"; tail -5 $P/trace_c4.err; exit 1; }
 python3 $R/tools/trace_summary.py $(ls $P/trace_c4/*/*kernel_trace.csv | head -1) 1 40 > $P/c4_trace_by_grid.txt
 cp $(ls $P/trace_c4/*/*kernel_stats.csv | head -1) $P/c4_kernel_stats_1stream.csv
 rm -rf $P/trace_c4
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $P/trace_c5 -- python3 $R/bench.py --config burgers4096x512 --batch 1 --streams 1 --steps 1 --warmup 1 --no-cpu-baseline --no-spmm --no-full-loop --no-single-problem > $P/c5_under_rocprof.json 2> $P/trace_c5.err || { echo "c5 trace failed"; tail -5 $P/trace_c5.err; exit 1; }
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $P/trace_c5 -- python3 $R/bench.py --full --config burgers4096x512 --batch 1 --streams 1 --steps 1 --warmup 1 --no-cpu-baseline --no-spmm --no-full-loop --no-single-problem > $P/c5_under_rocprof.json 2> $P/trace_c5.err || { echo "c5 trace failed"; tail -5 $P/trace_c5.err; exit 1; }
 python3 $R/tools/trace_summary.py $(ls $P/trace_c5/*/*kernel_trace.csv | head -1) 1 40 > $P/c5_trace_by_grid.txt
 cp $(ls $P/trace_c5/*/*kernel_stats.csv | head -1) $P/c5_kernel_stats.csv
 rm -rf $P/trace_c5

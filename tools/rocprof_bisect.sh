@@ -4,7 +4,7 @@ R=$GRAFT_REPO_ROOT; OUT=$R/gpurun_out/bisect; rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 run() {
   name=$1; shift
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/$name -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-spmm "$@" > $OUT/$name.json 2> $OUT/$name.err
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/$name -- python3 $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-spmm "$@" > $OUT/$name.json 2> $OUT/$name.err
   echo "$name rc=$? $(grep -c SIGSEGV $OUT/$name.err)"
   rm -rf $OUT/$name
 }

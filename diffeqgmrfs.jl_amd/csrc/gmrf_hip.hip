@@ -17,7 +17,10 @@
 #include <iterator>
 #include <cmath>
 #include <map>
+#include <memory>
 #include <chrono>
+#include <functional>
+#include <initializer_list>
 #include <mutex>
 #include <string>
 #include <type_traits>
@@ -981,6 +984,15 @@ static void persist_release(gmrf_handle* h) {
     h->sweep_persist_planned = false;
 }
 
+// A bounded wait inside a persistent launch gave up: this handle keeps the launch-per-step / per-product forms for good, lets go
+// of its claim and drops the captured graphs that hold such launches.  (The caller resets its abort word and repeats its work.)
+static void persist_give_up(gmrf_handle* h) {
+    h->persist_gave_up = true; h->persist_aborts++;
+    h->stats.persist_aborts = h->persist_aborts;
+    persist_release(h);
+    destroy_graphs(h);
+}
+
 // One persistent launch (potrf_persist.hpp) over the column tiles [j0, j1) of a block of nt tiles (its flag words are zero
 // between launches: the last workgroup out of a launch leaves them so).  false: the handle holds no claim that covers this
 // shape (it does not fit the chip beside the other handles' launches, or the form is switched off).
@@ -1478,10 +1490,7 @@ static gmrf_status persist_check_range(gmrf_handle* h, int64_t i0, int64_t i1, i
     HIPCHK(hipStreamSynchronize(h->stream));
     h->persist_launched = false;
     if (hinfo2[1] != 0) {
-        h->persist_gave_up = true; h->persist_aborts++;
-        h->stats.persist_aborts = h->persist_aborts;
-        persist_release(h);
-        destroy_graphs(h);
+        persist_give_up(h);
         const int restore[4] = {h->info_checked, 0, 0, 0};     // (what the aborted range wrote into the info word means nothing)
         HIPCHK(hipMemcpyAsync(h->d_info, restore, 4 * sizeof(int), hipMemcpyHostToDevice, h->stream));
         if (h->d_pflags) HIPCHK(hipMemsetAsync(h->d_pflags, 0, sizeof(unsigned) * (size_t)h->pflags_words, h->stream));   // (belt and braces: the drained launches cleaned up themselves)
@@ -1646,6 +1655,7 @@ static gmrf_status launch_sweep_persist(gmrf_handle* h, bool backward, int kp, d
     double* Tp = T_over ? T_over : h->d_Tsw;
     if (!h->d_sweep_flags || !h->h_sweep_abort || nw <= 0 || !Tp || (!T_over && h->t_elems < elems))
         return bad_shape("internal: words / panel of the persistent sweeps not allocated");
+    if (elems % 2 != 0) return bad_shape("internal: the persistent sweeps' panels need an even element count (sweep_fill_sentinel)");
     SweepPersistArgs a;
     a.C = h->d_C; a.Linv = h->d_Linv; a.Pin = Pin; a.T = Tp; a.Yout = Yout;
     a.N = (int)h->N; a.bsp = (int)h->bsp; a.cm = (int)h->cmin; a.rm = (int)h->rmax; a.kp = kp; a.backward = backward ? 1 : 0; a.nw = nw;
@@ -1673,7 +1683,7 @@ static gmrf_status launch_sweep_persist(gmrf_handle* h, bool backward, int kp, d
     const double work = (kp == 1) ? 8.0 * ((N - 1) * h->c_streamed + N * 0.5 * bsp * (bsp + 1))
                                   : kp * (2.0 * (N - 1) * h->c_streamed + N * bsp * (bsp + 1));
     {
-        // the panels the products read from each other: sentinel everywhere (elems is even: n_pad is a multiple of 64)
+        // the panels the products read from each other: sentinel everywhere (two elements per thread: elems is even, checked above)
         ProfScope ps(h, 5, 16.0 * (double)elems);
         hipLaunchKernelGGL(sweep_fill_sentinel, dim3((unsigned)((elems / 2 + 255) / 256)), dim3(256), 0, st, Tp, Yout, elems);
         HIPCHK(hipGetLastError());
@@ -1693,14 +1703,32 @@ static gmrf_status sweep_persist_check(gmrf_handle* h, bool* repeat) {
     h->sweep_persist_launched = false;
     if (!h->h_sweep_abort || *reinterpret_cast<volatile unsigned*>(h->h_sweep_abort) == 0u) return GMRF_OK;
     *h->h_sweep_abort = 0u;
-    h->persist_gave_up = true; h->persist_aborts++;
-    h->stats.persist_aborts = h->persist_aborts;
-    persist_release(h);
-    destroy_graphs(h);
+    persist_give_up(h);
     HIPCHK(hipMemsetAsync(h->d_sweep_flags, 0, sizeof(unsigned) * 16, h->stream));
     h->stats.sweep_persist = 0;
     *repeat = true;
     return GMRF_OK;
+}
+
+// (input, output) byte ranges of a call that runs sweeps
+struct SweepIo { const void* in; int64_t in_bytes; const void* out; int64_t out_bytes; };
+
+// Every public call that runs sweeps goes through here.  A persistent sweep whose wait gave up leaves garbage in its panels and
+// raises the abort words (the call's later persistent launches drain at once and add more garbage); the call sees the word behind
+// the synchronisation that ends it -- none per chunk -- and is repeated from its inputs with a launch per product (the handle has
+// left the persistent form for good).  So the persistent form is held off for a call whose inputs overlap its outputs (`io`: the
+// repeat would read what the first pass wrote).  `body` enqueues the call and ends in its synchronisation; `restore`, if given,
+// puts back before the repeat an input that the body changes in place.
+static gmrf_status sweep_guarded(gmrf_handle* h, std::initializer_list<SweepIo> io, const std::function<gmrf_status()>& body,
+                                 const std::function<gmrf_status()>& restore = nullptr) {
+    h->stats.sweep_persist = 0;
+    h->sweep_persist_hold = std::any_of(io.begin(), io.end(), [](const SweepIo& r) { return ranges_overlap(r.in, r.in_bytes, r.out, r.out_bytes); });
+    GCHK(body());
+    bool repeat = false;
+    GCHK(sweep_persist_check(h, &repeat));
+    if (!repeat) return GMRF_OK;
+    if (restore) GCHK(restore());
+    return body();
 }
 
 static gmrf_status sweep_launches(gmrf_handle* h, bool backward, int kp, double* Pin, double* Yout) {
@@ -1853,6 +1881,29 @@ static gmrf_status launch_unpack(gmrf_handle* h, const double* panel, double* d_
     hipLaunchKernelGGL(unpack_panel, dim3((unsigned)((total + 255) / 256), (unsigned)h->B), dim3(256), 0, h->stream, panel,
                        h->n_pad, d_dst, ld, (int)h->bs, (int)h->bsp, h->n, k, pad_k(k), d_mean);
     HIPCHK(hipGetLastError());
+    return GMRF_OK;
+}
+
+// k columns per problem of the caller's (src, ld) as the pack reads them: where they lie in device memory, else copied into
+// d_stage (leading dimension n)
+static gmrf_status cols_in(gmrf_handle* h, const double* src, int64_t ld, bool src_dev, int k, const double** d_src, int64_t* d_ld) {
+    *d_src = src; *d_ld = ld;
+    if (src_dev) return GMRF_OK;
+    GCHK(ensure_stage(h, (int64_t)k * h->n * h->B));
+    HIPCHK(hipMemcpy2DAsync(h->d_stage, h->n * sizeof(double), src, ld * sizeof(double),
+                            h->n * sizeof(double), k * h->B, hipMemcpyHostToDevice, h->stream));
+    *d_src = h->d_stage; *d_ld = h->n;
+    return GMRF_OK;
+}
+
+// k columns per problem of a panel (plus d_mean, if given) out to the caller's (dst, ld): unpacked there if it is device memory,
+// else into d_stage and copied to the host from there (the caller synchronises)
+static gmrf_status cols_out(gmrf_handle* h, const double* panel, int k, const double* d_mean, double* dst, int64_t ld, bool dst_dev) {
+    if (dst_dev) return launch_unpack(h, panel, dst, ld, k, d_mean);
+    GCHK(ensure_stage(h, (int64_t)k * h->n * h->B));
+    GCHK(launch_unpack(h, panel, h->d_stage, h->n, k, d_mean));
+    HIPCHK(hipMemcpy2DAsync(dst, ld * sizeof(double), h->d_stage, h->n * sizeof(double),
+                            h->n * sizeof(double), k * h->B, hipMemcpyDeviceToHost, h->stream));
     return GMRF_OK;
 }
 
@@ -2698,52 +2749,35 @@ gmrf_status gmrf_bt_solve(gmrf_handle* h, const double* b, double* y, int64_t k,
     HIPCHK(hipSetDevice(h->device));
     if (h->B > 1 && k > KP_CHUNK) return bad_shape("with a batch of problems k is limited to 128 per call");
     const bool b_dev = is_device_ptr(b), y_dev = is_device_ptr(y);
-    h->stats.solve_ms = 0.0;
     const int64_t nb = h->B;            // b / y hold nb consecutive groups of k columns (problem-major)
     // b and y overlap (in place, or y a column further on): a persistent sweep that gave up could not be repeated from b
-    h->sweep_persist_hold = ranges_overlap(b, cols_bytes(h->n, k * nb, ldb), y, cols_bytes(h->n, k * nb, ldy));
-    h->stats.sweep_persist = 0;
-    for (int64_t c0 = 0; c0 < k; c0 += KP_CHUNK) {
-        const int kc = (int)std::min<int64_t>(KP_CHUNK, k - c0);
-        const int kp = pad_k(kc);
-        GCHK(ensure_panels(h, kp));
-        const double* bsrc = b + c0 * ldb;
-        double* ydst = y + c0 * ldy;
-        const double* d_b = bsrc;
-        if (!b_dev || !y_dev) GCHK(ensure_stage(h, (int64_t)kc * h->n * nb));
-        if (!b_dev) {
-            HIPCHK(hipMemcpy2DAsync(h->d_stage, h->n * sizeof(double), bsrc, ldb * sizeof(double),
-                                    h->n * sizeof(double), kc * nb, hipMemcpyHostToDevice, h->stream));
-            d_b = h->d_stage;
-        }
-        GCHK(launch_pack(h, d_b, b_dev ? ldb : h->n, kc, kp));
-        HIPCHK(hipEventRecord(h->ev0, h->stream));
-        GCHK(run_sweeps(h, mode, kp));
-        HIPCHK(hipEventRecord(h->ev1, h->stream));
-        const double* result = (mode == GMRF_SOLVE_FULL) ? h->d_P : h->d_Y;
-        if (y_dev) {
-            GCHK(launch_unpack(h, result, ydst, ldy, kc, nullptr));
+    return sweep_guarded(h, {{b, cols_bytes(h->n, k * nb, ldb), y, cols_bytes(h->n, k * nb, ldy)}}, [&]() -> gmrf_status {
+        h->stats.solve_ms = 0.0;
+        for (int64_t c0 = 0; c0 < k; c0 += KP_CHUNK) {
+            const int kc = (int)std::min<int64_t>(KP_CHUNK, k - c0);
+            const int kp = pad_k(kc);
+            GCHK(ensure_panels(h, kp));
+            const double* d_b = nullptr;
+            int64_t ld_b = 0;
+            GCHK(cols_in(h, b + c0 * ldb, ldb, b_dev, kc, &d_b, &ld_b));
+            GCHK(launch_pack(h, d_b, ld_b, kc, kp));
+            HIPCHK(hipEventRecord(h->ev0, h->stream));
+            GCHK(run_sweeps(h, mode, kp));
+            HIPCHK(hipEventRecord(h->ev1, h->stream));
+            GCHK(cols_out(h, (mode == GMRF_SOLVE_FULL) ? h->d_P : h->d_Y, kc, nullptr, y + c0 * ldy, ldy, y_dev));
             HIPCHK(hipStreamSynchronize(h->stream));
-        } else {
-            GCHK(launch_unpack(h, result, h->d_stage, h->n, kc, nullptr));
-            HIPCHK(hipMemcpy2DAsync(ydst, ldy * sizeof(double), h->d_stage, h->n * sizeof(double),
-                                    h->n * sizeof(double), kc * nb, hipMemcpyDeviceToHost, h->stream));
-            HIPCHK(hipStreamSynchronize(h->stream));
+            float ms = 0.f;
+            (void)hipEventElapsedTime(&ms, h->ev0, h->ev1);
+            h->stats.solve_ms += ms;
+            const int nsweeps = (mode == GMRF_SOLVE_FULL) ? 2 : 1;
+            h->stats.sweep_ms = ms / nsweeps;
+            h->stats.sweep_bytes = sweep_bytes(h, kc) * (double)nb;
+            h->stats.sweep_bytes_streamed = (8.0 * ((double)h->N * 0.5 * (double)h->bsp * (double)(h->bsp + 1) +
+                                                    (double)(h->N - 1) * h->c_streamed) + 16.0 * (double)h->n_pad * kc) * (double)nb;
+            if (h->profiling) prof_collect(h);
         }
-        bool repeat = false;
-        GCHK(sweep_persist_check(h, &repeat));
-        if (repeat) { c0 -= KP_CHUNK; continue; }           // (this chunk again, with a launch per product: b is untouched)
-        float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, h->ev0, h->ev1);
-        h->stats.solve_ms += ms;
-        const int nsweeps = (mode == GMRF_SOLVE_FULL) ? 2 : 1;
-        h->stats.sweep_ms = ms / nsweeps;
-        h->stats.sweep_bytes = sweep_bytes(h, kc) * (double)nb;
-        h->stats.sweep_bytes_streamed = (8.0 * ((double)h->N * 0.5 * (double)h->bsp * (double)(h->bsp + 1) +
-                                                (double)(h->N - 1) * h->c_streamed) + 16.0 * (double)h->n_pad * kc) * (double)nb;
-        if (h->profiling) prof_collect(h);
-    }
-    return GMRF_OK;
+        return GMRF_OK;
+    });
 }
 
 static gmrf_status stage_vector(gmrf_handle* h, const double* v, double** d_buf, const double** d_out) {
@@ -2761,14 +2795,9 @@ static gmrf_status sample_chunk(gmrf_handle* h, uint64_t seed, int64_t first_id,
     const int kp = pad_k(kc);
     GCHK(ensure_panels(h, kp));
     if (z) {
-        const double* d_z = z;
-        int64_t ldd = ldz;
-        if (!is_device_ptr(z)) {
-            GCHK(ensure_stage(h, (int64_t)kc * h->n * h->B));
-            HIPCHK(hipMemcpy2DAsync(h->d_stage, h->n * sizeof(double), z, ldz * sizeof(double),
-                                    h->n * sizeof(double), kc * h->B, hipMemcpyHostToDevice, h->stream));
-            d_z = h->d_stage; ldd = h->n;
-        }
+        const double* d_z = nullptr;
+        int64_t ldd = 0;
+        GCHK(cols_in(h, z, ldz, is_device_ptr(z), kc, &d_z, &ldd));
         GCHK(launch_pack(h, d_z, ldd, kc, kp));
     } else {
         const int64_t total = (int64_t)kp * h->n_pad;
@@ -2790,29 +2819,20 @@ gmrf_status gmrf_bt_sample(gmrf_handle* h, uint64_t seed, int64_t first_id, int6
     GCHK(stage_vector(h, mean, &h->d_mean, &d_mean));
     const bool out_dev = is_device_ptr(out);
     // z or the mean overlaps the output: the repeat after a persistent sweep that gave up would read what the first pass wrote
-    const int64_t out_bytes = cols_bytes(h->n, k * h->B, ld);
-    h->sweep_persist_hold = ranges_overlap(z, cols_bytes(h->n, k * h->B, ld), out, out_bytes) ||
-                            ranges_overlap(mean, h->n * h->B * (int64_t)sizeof(double), out, out_bytes);
-    h->stats.sweep_persist = 0;
-    HIPCHK(hipEventRecord(h->ev0, h->stream));
-    for (int64_t c0 = 0; c0 < k; c0 += KP_CHUNK) {
-        const int kc = (int)std::min<int64_t>(KP_CHUNK, k - c0);
-        GCHK(sample_chunk(h, seed, first_id + c0, kc, z ? z + c0 * ld : nullptr, ld, k));
-        if (out_dev) {
-            GCHK(launch_unpack(h, h->d_Y, out + c0 * ld, ld, kc, d_mean));
-        } else {
-            GCHK(ensure_stage(h, (int64_t)kc * h->n * h->B));
-            GCHK(launch_unpack(h, h->d_Y, h->d_stage, h->n, kc, d_mean));
-            HIPCHK(hipMemcpy2DAsync(out + c0 * ld, ld * sizeof(double), h->d_stage, h->n * sizeof(double),
-                                    h->n * sizeof(double), kc * h->B, hipMemcpyDeviceToHost, h->stream));
-            HIPCHK(hipStreamSynchronize(h->stream));
+    const int64_t smp_bytes = cols_bytes(h->n, k * h->B, ld);      // z and out alike
+    GCHK(sweep_guarded(h, {{z, smp_bytes, out, smp_bytes}, {mean, h->n * h->B * (int64_t)sizeof(double), out, smp_bytes}},
+                       [&]() -> gmrf_status {
+        HIPCHK(hipEventRecord(h->ev0, h->stream));
+        for (int64_t c0 = 0; c0 < k; c0 += KP_CHUNK) {
+            const int kc = (int)std::min<int64_t>(KP_CHUNK, k - c0);
+            GCHK(sample_chunk(h, seed, first_id + c0, kc, z ? z + c0 * ld : nullptr, ld, k));
+            GCHK(cols_out(h, h->d_Y, kc, d_mean, out + c0 * ld, ld, out_dev));
+            if (!out_dev) HIPCHK(hipStreamSynchronize(h->stream));
         }
-    }
-    HIPCHK(hipEventRecord(h->ev1, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    bool repeat = false;
-    GCHK(sweep_persist_check(h, &repeat));
-    if (repeat) return gmrf_bt_sample(h, seed, first_id, k, mean, z, out, ld);     // (once: the handle has left the persistent form)
+        HIPCHK(hipEventRecord(h->ev1, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        return GMRF_OK;
+    }));
     float ms = 0.f;
     (void)hipEventElapsedTime(&ms, h->ev0, h->ev1);
     h->stats.sample_ms = ms;
@@ -2820,30 +2840,11 @@ gmrf_status gmrf_bt_sample(gmrf_handle* h, uint64_t seed, int64_t first_id, int6
     return GMRF_OK;
 }
 
-// mean = A^-1 b and k samples mean + L^-T z in ONE call (scripts/darcy/solve_darcy_gmrf-fem.jl:190-191 calls `mean` and `rand` on one
-// factor, one after the other).  The samples' backward sweep needs nothing of the mean -- only their last step, adding it, does --
-// so where the sweeps are persistent launches (one problem, blocks of 512 .. 1024) it runs BESIDE the mean's two sweeps, on a second
-// stream with panels of its own: both are bound by their chains of hand-offs, not by the chip, and two resident workgroups per
-// CU (97 + 189 VGPRs, 13 + 33 KB of LDS) take turns in the same time one takes alone.  The same kernels and the same sums as
-// gmrf_bt_solve + gmrf_bt_sample: bitwise their results.  Anywhere else the call IS those two calls.
-gmrf_status gmrf_bt_posterior(gmrf_handle* h, const double* b, uint64_t seed, int64_t first_id, int64_t k, double* mean,
-                              double* samples, int64_t ld) {
-    if (!h || !b || !mean || !samples) return bad_shape("null pointer");
-    if (!h->factored) { g_last_error = "posterior before factor"; return GMRF_ERR_NO_FACTOR; }
-    if (k <= 0 || ld < h->n) return bad_shape("bad k / ld");
-    HIPCHK(hipSetDevice(h->device));
+// The samples' backward sweep of gmrf_bt_posterior beside the mean's two (persistent launches, device pointers, no two of b, mean,
+// samples overlapping); ends in the synchronisation of the handle's stream.
+static gmrf_status posterior_beside(gmrf_handle* h, const double* b, uint64_t seed, int64_t first_id, int64_t k, double* mean,
+                                    double* samples, int64_t ld) {
     const int kp = pad_k(k);
-    const bool dev_all = is_device_ptr(b) && is_device_ptr(mean) && is_device_ptr(samples);
-    // beside only when no two of b, mean, samples overlap (else the two calls, each with its own guard)
-    const int64_t vec_bytes = h->n * h->B * (int64_t)sizeof(double), smp_bytes = cols_bytes(h->n, k * h->B, ld);
-    h->sweep_persist_hold = ranges_overlap(b, vec_bytes, mean, vec_bytes) || ranges_overlap(b, vec_bytes, samples, smp_bytes) ||
-                            ranges_overlap(mean, vec_bytes, samples, smp_bytes);
-    h->stats.sweep_persist = 0;
-    const bool beside = h->B == 1 && k <= KP_CHUNK && k >= 2 && dev_all && !h->profiling && sweep_persist_ok(h, 1) && sweep_persist_ok(h, kp);
-    if (!beside) {
-        GCHK(gmrf_bt_solve(h, b, mean, 1, h->n, h->n, GMRF_SOLVE_FULL));
-        return gmrf_bt_sample(h, seed, first_id, k, mean, nullptr, samples, ld);
-    }
     GCHK(ensure_panels(h, 1));
     GCHK(sweep_persist_prepare(h, 1));
     const int64_t elems = (int64_t)kp * h->n_pad;
@@ -2905,10 +2906,35 @@ gmrf_status gmrf_bt_posterior(gmrf_handle* h, const double* b, uint64_t seed, in
     GCHK(launch_unpack(h, h->d_Y2, samples, ld, (int)k, mean));
     HIPCHK(hipEventRecord(h->ev1, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
-    bool repeat = false;
-    GCHK(sweep_persist_check(h, &repeat));
-    if (repeat) {                                      // (a persistent sweep gave up: the two calls, with a launch per product)
+    return GMRF_OK;
+}
+
+// mean = A^-1 b and k samples mean + L^-T z in ONE call (scripts/darcy/solve_darcy_gmrf-fem.jl:190-191 calls `mean` and `rand` on one
+// factor, one after the other).  The samples' backward sweep needs nothing of the mean -- only their last step, adding it, does --
+// so where the sweeps are persistent launches (one problem, blocks of 512 .. 1024) it runs BESIDE the mean's two sweeps, on a second
+// stream with panels of its own: both are bound by their chains of hand-offs, not by the chip, and two resident workgroups per
+// CU (97 + 189 VGPRs, 13 + 33 KB of LDS) take turns in the same time one takes alone.  The same kernels and the same sums as
+// gmrf_bt_solve + gmrf_bt_sample: bitwise their results.  Anywhere else the call IS those two calls.
+gmrf_status gmrf_bt_posterior(gmrf_handle* h, const double* b, uint64_t seed, int64_t first_id, int64_t k, double* mean,
+                              double* samples, int64_t ld) {
+    if (!h || !b || !mean || !samples) return bad_shape("null pointer");
+    if (!h->factored) { g_last_error = "posterior before factor"; return GMRF_ERR_NO_FACTOR; }
+    if (k <= 0 || ld < h->n) return bad_shape("bad k / ld");
+    HIPCHK(hipSetDevice(h->device));
+    const bool dev_all = is_device_ptr(b) && is_device_ptr(mean) && is_device_ptr(samples);
+    // beside only when no two of b, mean, samples overlap (else the two calls, each with its own guard)
+    const int64_t vec_bytes = h->n * h->B * (int64_t)sizeof(double), smp_bytes = cols_bytes(h->n, k * h->B, ld);
+    bool beside = false;
+    GCHK(sweep_guarded(h, {{b, vec_bytes, mean, vec_bytes}, {b, vec_bytes, samples, smp_bytes}, {mean, vec_bytes, samples, smp_bytes}},
+                       [&]() -> gmrf_status {
+        // (decided behind the hold, which sweep_persist_ok reads; the repeat after an abort finds the handle off the persistent form)
+        beside = h->B == 1 && k <= KP_CHUNK && k >= 2 && dev_all && !h->profiling && sweep_persist_ok(h, 1) && sweep_persist_ok(h, pad_k(k));
+        return beside ? posterior_beside(h, b, seed, first_id, k, mean, samples, ld) : GMRF_OK;
+    }, [&]() -> gmrf_status {
         HIPCHK(hipStreamSynchronize(h->aux));
+        return GMRF_OK;
+    }));
+    if (!beside) {
         GCHK(gmrf_bt_solve(h, b, mean, 1, h->n, h->n, GMRF_SOLVE_FULL));
         return gmrf_bt_sample(h, seed, first_id, k, mean, nullptr, samples, ld);
     }
@@ -2934,14 +2960,7 @@ gmrf_status gmrf_bt_normals(gmrf_handle* h, uint64_t seed, int64_t first_id, int
         hipLaunchKernelGGL(fill_normals_panel, dim3((unsigned)((total + 255) / 256), (unsigned)h->B), dim3(256), 0,
                            h->stream, h->d_P, h->n_pad, (int)h->bs, (int)h->bsp, kc, kp, seed, first_id + c0, k);
         HIPCHK(hipGetLastError());
-        if (z_dev) {
-            GCHK(launch_unpack(h, h->d_P, z + c0 * ld, ld, kc, nullptr));
-        } else {
-            GCHK(ensure_stage(h, (int64_t)kc * h->n * h->B));
-            GCHK(launch_unpack(h, h->d_P, h->d_stage, h->n, kc, nullptr));
-            HIPCHK(hipMemcpy2DAsync(z + c0 * ld, ld * sizeof(double), h->d_stage, h->n * sizeof(double),
-                                    h->n * sizeof(double), kc * h->B, hipMemcpyDeviceToHost, h->stream));
-        }
+        GCHK(cols_out(h, h->d_P, kc, nullptr, z + c0 * ld, ld, z_dev));
         HIPCHK(hipStreamSynchronize(h->stream));
     }
     return GMRF_OK;
@@ -4116,15 +4135,6 @@ static gmrf_status var_chunk(gmrf_handle* h, int method, int64_t p, int kc, cons
     return GMRF_OK;
 }
 
-// The sampled estimators' sweeps may be persistent launches (one problem, blocks of 512 .. 1024).  Their callers check for one
-// that gave up behind the synchronisation that ends the call and then repeat the whole call from its inputs, which they keep (the
-// accumulator as it came in): no synchronisation per chunk.  The first chunk that gave up leaves garbage in d_Y and raises the
-// abort words; the chunks after it drain at once and add more garbage, which the repeat discards.
-static void var_entry(gmrf_handle* h) {
-    h->sweep_persist_hold = false;
-    h->stats.sweep_persist = 0;
-}
-
 static gmrf_status var_accumulate_dev(gmrf_handle* h, int method, int64_t first_id, int64_t k, uint64_t seed,
                                       const gmrf_csr* Q, double* d_acc) {
     for (int64_t c0 = 0; c0 < k; c0 += 64) {
@@ -4132,6 +4142,15 @@ static gmrf_status var_accumulate_dev(gmrf_handle* h, int method, int64_t first_
         GCHK(sample_chunk(h, seed, first_id + c0, kc, nullptr, 0, 0));
         GCHK(var_chunk(h, method, 0, kc, Q, nullptr, Q ? Q->d_diag : nullptr, d_acc));
     }
+    return GMRF_OK;
+}
+
+// h->d_acc: room for the variances of B problems
+static gmrf_status ensure_acc(gmrf_handle* h, int64_t B) {
+    if (h->d_acc && h->acc_B >= B) return GMRF_OK;
+    free_dev(h->d_acc); h->d_acc = nullptr;
+    HIPCHK(hipMalloc(&h->d_acc, sizeof(double) * h->n * B));
+    h->acc_B = B;
     return GMRF_OK;
 }
 
@@ -4144,23 +4163,19 @@ gmrf_status gmrf_bt_var_accumulate(gmrf_handle* h, int32_t method, int64_t first
     if (k <= 0) return bad_shape("k <= 0");
     GCHK(need_single(h));
     HIPCHK(hipSetDevice(h->device));
-    var_entry(h);
     const bool dev = is_device_ptr(acc);
-    if (!h->d_acc) { HIPCHK(hipMalloc(&h->d_acc, sizeof(double) * h->n)); h->acc_B = 1; }
+    GCHK(ensure_acc(h, 1));
     // h->d_acc: the accumulator a host acc is summed in, or the copy of a device acc as it came in (for the repeat)
-    HIPCHK(hipMemcpyAsync(h->d_acc, acc, sizeof(double) * h->n, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
     double* d_acc = dev ? acc : h->d_acc;
-    GCHK(var_accumulate_dev(h, method, first_id, k, seed, Q, d_acc));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    bool repeat = false;
-    GCHK(sweep_persist_check(h, &repeat));
-    if (repeat) {                                      // (once: the handle has left the persistent form)
-        if (dev) {
-            HIPCHK(hipMemcpyAsync(acc, h->d_acc, sizeof(double) * h->n, hipMemcpyDeviceToDevice, h->stream));
-            HIPCHK(hipStreamSynchronize(h->stream));
-        }
-        return gmrf_bt_var_accumulate(h, method, first_id, k, seed, Q, acc);
-    }
+    GCHK(sweep_guarded(h, {}, [&]() -> gmrf_status {
+        HIPCHK(hipMemcpyAsync(h->d_acc, acc, sizeof(double) * h->n, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
+        GCHK(var_accumulate_dev(h, method, first_id, k, seed, Q, d_acc));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        return GMRF_OK;
+    }, [&]() -> gmrf_status {
+        if (dev) HIPCHK(hipMemcpyAsync(acc, h->d_acc, sizeof(double) * h->n, hipMemcpyDeviceToDevice, h->stream));
+        return GMRF_OK;
+    }));
     if (!dev) {
         HIPCHK(hipMemcpyAsync(acc, d_acc, sizeof(double) * h->n, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));
@@ -4172,43 +4187,30 @@ gmrf_status gmrf_bt_marginal_var(gmrf_handle* h, int32_t method, int64_t k, uint
                                  double* var_out) {
     if (!h || !var_out) return bad_shape("null pointer");
     if (!h->factored) { g_last_error = "variance before factor"; return GMRF_ERR_NO_FACTOR; }
-    if (method != GMRF_VAR_EXACT) GCHK(need_single(h));    // sampled estimators: one problem per handle
+    if (method != GMRF_VAR_EXACT) {
+        GCHK(need_single(h));                          // sampled estimators: one problem per handle
+        if (method != GMRF_VAR_RBMC && method != GMRF_VAR_MC) return bad_shape("bad variance method");
+        if (method == GMRF_VAR_RBMC && (!Q || Q->n_rows != h->n || !Q->d_diag)) return bad_shape("RBMC needs the square matrix Q");
+        if (k <= 0) return bad_shape("k <= 0");
+    }
     HIPCHK(hipSetDevice(h->device));
-    var_entry(h);
-    if (!h->d_acc || h->acc_B < h->B) {
-        free_dev(h->d_acc); h->d_acc = nullptr;
-        HIPCHK(hipMalloc(&h->d_acc, sizeof(double) * h->n * h->B));
-        h->acc_B = h->B;
-    }
-    const bool dev = is_device_ptr(var_out);
-    double* d_out = var_out;
-    if (!dev) { GCHK(ensure_stage(h, std::max<int64_t>(h->n, 1))); }
-    if (method == GMRF_VAR_EXACT) {
-        // selected inversion; var_out is [batch][n]
-        GCHK(var_exact(h, h->d_acc));
-        const size_t bytes = sizeof(double) * h->n * h->B;
-        if (dev) HIPCHK(hipMemcpyAsync(d_out, h->d_acc, bytes, hipMemcpyDeviceToDevice, h->stream));
-        else HIPCHK(hipMemcpyAsync(var_out, h->d_acc, bytes, hipMemcpyDeviceToHost, h->stream));
+    GCHK(ensure_acc(h, h->B));
+    const hipMemcpyKind kind = is_device_ptr(var_out) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    GCHK(sweep_guarded(h, {}, [&]() -> gmrf_status {
+        if (method == GMRF_VAR_EXACT) {
+            GCHK(var_exact(h, h->d_acc));              // selected inversion; var_out is [batch][n]
+        } else {
+            HIPCHK(hipMemsetAsync(h->d_acc, 0, sizeof(double) * h->n, h->stream));
+            GCHK(var_accumulate_dev(h, method, 0, k, seed, Q, h->d_acc));
+            // finish in place: var = base + acc / k
+            hipLaunchKernelGGL(var_finish, dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, h->stream, h->d_acc,
+                               method == GMRF_VAR_RBMC ? Q->d_diag : (const double*)nullptr, 1.0 / (double)k, h->n, h->d_acc);
+            HIPCHK(hipGetLastError());
+        }
+        HIPCHK(hipMemcpyAsync(var_out, h->d_acc, sizeof(double) * h->n * h->B, kind, h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));
-        if (h->profiling) prof_collect(h);
         return GMRF_OK;
-    }
-    if (method != GMRF_VAR_RBMC && method != GMRF_VAR_MC) return bad_shape("bad variance method");
-    if (method == GMRF_VAR_RBMC && (!Q || Q->n_rows != h->n || !Q->d_diag)) return bad_shape("RBMC needs the square matrix Q");
-    if (k <= 0) return bad_shape("k <= 0");
-    HIPCHK(hipMemsetAsync(h->d_acc, 0, sizeof(double) * h->n, h->stream));
-    GCHK(var_accumulate_dev(h, method, 0, k, seed, Q, h->d_acc));
-    // finish in place: var = base + acc / k
-    double* d_fin = h->d_acc;
-    hipLaunchKernelGGL(var_finish, dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, h->stream, h->d_acc,
-                       method == GMRF_VAR_RBMC ? Q->d_diag : (const double*)nullptr, 1.0 / (double)k, h->n, d_fin);
-    HIPCHK(hipGetLastError());
-    if (dev) HIPCHK(hipMemcpyAsync(d_out, d_fin, sizeof(double) * h->n, hipMemcpyDeviceToDevice, h->stream));
-    else HIPCHK(hipMemcpyAsync(var_out, d_fin, sizeof(double) * h->n, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    bool repeat = false;
-    GCHK(sweep_persist_check(h, &repeat));
-    if (repeat) return gmrf_bt_marginal_var(h, method, k, seed, Q, var_out);      // (once: the handle has left the persistent form)
+    }));
     if (h->profiling) prof_collect(h);
     return GMRF_OK;
 }
@@ -4226,54 +4228,45 @@ gmrf_status gmrf_bt_marginal_var_batch(gmrf_handle* h, int32_t method, int64_t k
     if (method == GMRF_VAR_RBMC && (!Q || Q->n_rows != h->n || Q->n_cols != h->n || !q_vals)) return bad_shape("RBMC needs the pattern of Q and its values per problem");
     if (k <= 0) return bad_shape("k <= 0");
     HIPCHK(hipSetDevice(h->device));
-    var_entry(h);
     const int64_t n = h->n, B = h->B;
-    if (!h->d_acc || h->acc_B < B) {
-        free_dev(h->d_acc); h->d_acc = nullptr;
-        HIPCHK(hipMalloc(&h->d_acc, sizeof(double) * n * B));
-        h->acc_B = B;
-    }
-    HIPCHK(hipMemsetAsync(h->d_acc, 0, sizeof(double) * n * B, h->stream));
-    double *d_qv = nullptr, *d_diag = nullptr;
-    const double* qv = q_vals;
-    if (method == GMRF_VAR_RBMC) {
-        if (!is_device_ptr(q_vals)) {
-            HIPCHK(hipMalloc(&d_qv, sizeof(double) * Q->nnz * B));
-            if (hipMemcpyAsync(d_qv, q_vals, sizeof(double) * Q->nnz * B, hipMemcpyHostToDevice, h->stream) != hipSuccess) {
-                free_dev(d_qv); g_last_error = "hipMemcpyAsync(q_vals) failed"; return GMRF_ERR_HIP;
+    GCHK(ensure_acc(h, B));
+    GCHK(sweep_guarded(h, {}, [&]() -> gmrf_status {     // (a batch of one: its sweeps may be persistent launches)
+        HIPCHK(hipMemsetAsync(h->d_acc, 0, sizeof(double) * n * B, h->stream));
+        std::unique_ptr<double, void (*)(void*)> d_qv(nullptr, free_dev), d_diag(nullptr, free_dev);     // (freed on every way out)
+        const double* qv = q_vals;
+        if (method == GMRF_VAR_RBMC) {
+            double* buf = nullptr;
+            if (!is_device_ptr(q_vals)) {
+                HIPCHK(hipMalloc(&buf, sizeof(double) * Q->nnz * B));
+                d_qv.reset(buf);
+                HIPCHK(hipMemcpyAsync(d_qv.get(), q_vals, sizeof(double) * Q->nnz * B, hipMemcpyHostToDevice, h->stream));
+                qv = d_qv.get();
             }
-            qv = d_qv;
+            HIPCHK(hipMalloc(&buf, sizeof(double) * n * B));
+            d_diag.reset(buf);
+            for (int64_t p = 0; p < B; ++p)
+                hipLaunchKernelGGL(csr_extract_diag, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, Q->d_rowptr,
+                                   Q->d_colidx, qv + p * Q->nnz, (const float*)nullptr, n, d_diag.get() + p * n);
+            HIPCHK(hipGetLastError());
         }
-        if (hipMalloc(&d_diag, sizeof(double) * n * B) != hipSuccess) { free_dev(d_qv); g_last_error = "hipMalloc(diag) failed"; return GMRF_ERR_HIP; }
-        for (int64_t p = 0; p < B; ++p)
-            hipLaunchKernelGGL(csr_extract_diag, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, Q->d_rowptr,
-                               Q->d_colidx, qv + p * Q->nnz, (const float*)nullptr, n, d_diag + p * n);
-        if (hipGetLastError() != hipSuccess) { free_dev(d_qv); free_dev(d_diag); g_last_error = "csr_extract_diag launch failed"; return GMRF_ERR_HIP; }
-    }
-    gmrf_status st = GMRF_OK;
-    for (int64_t c0 = 0; c0 < k && st == GMRF_OK; c0 += 64) {
-        const int kc = (int)std::min<int64_t>(64, k - c0);
-        st = sample_chunk(h, seed, c0, kc, nullptr, 0, k);          // every problem's chunk in one sweep
-        for (int64_t p = 0; p < B && st == GMRF_OK; ++p)
-            st = var_chunk(h, method, p, kc, Q, method == GMRF_VAR_RBMC ? qv + p * Q->nnz : nullptr,
-                           method == GMRF_VAR_RBMC ? d_diag + p * n : nullptr, h->d_acc + p * n);
-    }
-    if (st == GMRF_OK) {
+        for (int64_t c0 = 0; c0 < k; c0 += 64) {
+            const int kc = (int)std::min<int64_t>(64, k - c0);
+            GCHK(sample_chunk(h, seed, c0, kc, nullptr, 0, k));          // every problem's chunk in one sweep
+            for (int64_t p = 0; p < B; ++p)
+                GCHK(var_chunk(h, method, p, kc, Q, method == GMRF_VAR_RBMC ? qv + p * Q->nnz : nullptr,
+                               method == GMRF_VAR_RBMC ? d_diag.get() + p * n : nullptr, h->d_acc + p * n));
+        }
         for (int64_t p = 0; p < B; ++p)
             hipLaunchKernelGGL(var_finish, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->d_acc + p * n,
-                               method == GMRF_VAR_RBMC ? d_diag + p * n : (const double*)nullptr, 1.0 / (double)k, n,
+                               method == GMRF_VAR_RBMC ? d_diag.get() + p * n : (const double*)nullptr, 1.0 / (double)k, n,
                                h->d_acc + p * n);
-        if (hipGetLastError() != hipSuccess) st = GMRF_ERR_HIP;
+        HIPCHK(hipGetLastError());
         const hipMemcpyKind kind = is_device_ptr(var_out) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-        if (st == GMRF_OK && hipMemcpyAsync(var_out, h->d_acc, sizeof(double) * n * B, kind, h->stream) != hipSuccess) st = GMRF_ERR_HIP;
-    }
-    (void)hipStreamSynchronize(h->stream);
-    free_dev(d_qv); free_dev(d_diag);
-    bool repeat = false;                               // (a batch of one: its sweeps may be persistent launches)
-    const gmrf_status cs = sweep_persist_check(h, &repeat);
-    if (st == GMRF_OK) st = cs;
-    if (st == GMRF_OK && repeat) return gmrf_bt_marginal_var_batch(h, method, k, seed, Q, q_vals, var_out);      // (once)
-    return st;
+        HIPCHK(hipMemcpyAsync(var_out, h->d_acc, sizeof(double) * n * B, kind, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        return GMRF_OK;
+    }));
+    return GMRF_OK;
 }
 
 // --------------------------------------------------------------------------------- test hooks

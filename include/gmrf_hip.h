@@ -332,7 +332,10 @@ gmrf_status gmrf_streams_destroy(int32_t device, int32_t n, void** streams);
 
 /* Pipelined factorisation (factor block ranges so a broadcast of finished blocks can
  * overlap): begin uploads the matrix, step_async enqueues blocks [i0, i1) and returns,
- * end synchronises and reports SPD failures. */
+ * end synchronises and reports SPD failures.  Exception: a range that held persistent launches
+ * (stats.persist_route != 0) is waited for inside step_async, and repeated with a launch per step
+ * if one of them gave up, so that what the caller shares next is the factor; on such handles
+ * step_async returns only when its range is done. */
 gmrf_status gmrf_bt_factor_begin_csc(gmrf_handle* h, int64_t n, int64_t n_blocks,
                                      const int64_t* colptr, const int64_t* rowval,
                                      const double* nzval, int32_t index_base);

@@ -62,6 +62,7 @@ def var_batch(F):
 
 def var_accumulate(F, on_dev, method):
     acc = torch.ones(w.n, dtype=torch.float64, device="cuda") if on_dev else np.ones(w.n)       # (what was in it stays)
+    torch.cuda.synchronize()                            # (the handle's stream is its own: it does not wait for torch's)
     F.var_accumulate(acc, method, 0, 70, seed=13, Q=Q if method == "rbmc" else None)
     F.var_accumulate(acc, method, 70, 60, seed=13, Q=Q if method == "rbmc" else None)
     return acc.cpu().numpy() if on_dev else acc
@@ -76,6 +77,7 @@ def sample_mean_is_out(F):
 def posterior_b_in_samples(F):
     samples = torch.zeros((16, w.n), dtype=torch.float64, device="cuda")
     samples[0] = rhs
+    torch.cuda.synchronize()                            # (the handle's stream is its own: it does not wait for torch's)
     mean = torch.empty(w.n, dtype=torch.float64, device="cuda")
     cabi.check(lib.gmrf_bt_posterior(F._h, cabi.ptr(samples[0]), 19, 0, 16, cabi.ptr(mean), cabi.ptr(samples), w.n))
     return torch.cat([mean[None], samples]).cpu().numpy()

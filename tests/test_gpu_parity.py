@@ -1219,6 +1219,7 @@ def test_persistent_sweeps_of_one_problem_are_the_per_product_sweeps_bitwise(pkg
                                res["per_product"][4] if it % 2 == 0 else F_ref16(F, res, rhs)), (name, it)
         n0 = F.stats()["sweep_persist_launches"]
         buf = rhs.clone()
+        torch.cuda.synchronize()                        # (the handle's stream is its own: it does not wait for torch's)
         F._solve(buf, pkg._cabi.SOLVE_FULL, out=buf)                               # in place
         assert F.stats()["sweep_persist"] == 0 and F.stats()["sweep_persist_launches"] == n0
         assert torch.equal(buf, res["per_product"][0])
@@ -1413,6 +1414,7 @@ def test_persistent_sampled_variances_against_float64_reference(pkg, name):
                 assert np.array_equal(v, v_pp), (name, method, k)
                 one_shot[(method, k)] = v
         out = torch.full((w.n,), float("nan"), dtype=torch.float64, device="cuda")
+        torch.cuda.synchronize()                        # (the handle's stream is its own: it does not wait for torch's)
         F.marginal_var("rbmc", k=50, seed=seed, Q=Q, out=out)
         assert F.stats()["sweep_persist"] == 1
         assert np.array_equal(out.cpu().numpy(), one_shot[("rbmc", 50)]), name
@@ -1421,6 +1423,7 @@ def test_persistent_sampled_variances_against_float64_reference(pkg, name):
         for method in ("mc", "rbmc"):
             for on_dev in (False, True):
                 acc = torch.zeros(w.n, dtype=torch.float64, device="cuda") if on_dev else np.zeros(w.n)
+                torch.cuda.synchronize()                # (the handle's stream is its own: it does not wait for torch's)
                 F.var_accumulate(acc, method, 0, 70, seed=seed, Q=Q if method == "rbmc" else None)
                 assert F.stats()["sweep_persist"] == 1
                 F.var_accumulate(acc, method, 70, 60, seed=seed, Q=Q if method == "rbmc" else None)
@@ -1564,6 +1567,7 @@ def test_persistent_sweeps_with_aliased_arguments(pkg, lib, name):
         def b_in_samples():
             samples = torch.full((k, n), float("nan"), dtype=torch.float64, device="cuda")
             samples[0] = rhs
+            torch.cuda.synchronize()                    # (the handle's stream is its own: it does not wait for torch's)
             mean = torch.empty(n, dtype=torch.float64, device="cuda")
             cabi.check(lib.gmrf_bt_posterior(F._h, cabi.ptr(samples[0]), seed, 0, k, cabi.ptr(mean), cabi.ptr(samples), n))
             return mean, samples
@@ -1590,12 +1594,14 @@ def test_persistent_route_does_not_depend_on_the_previous_call(pkg, name):
         v_ref = F.marginal_var("mc", k=64, seed=5)
         F.set_eager(0)
         buf = rhs.clone()
+        torch.cuda.synchronize()                        # (the handle's stream is its own: it does not wait for torch's)
         F._solve(buf, pkg._cabi.SOLVE_FULL, out=buf)                               # in place
         assert F.stats()["sweep_persist"] == 0 and torch.equal(buf, mu_ref)
         v = F.marginal_var("mc", k=64, seed=5)
         assert F.stats()["sweep_persist"] == 1, name
         assert np.array_equal(v, v_ref), name
         buf = rhs.clone()
+        torch.cuda.synchronize()                        # (the handle's stream is its own: it does not wait for torch's)
         F._solve(buf, pkg._cabi.SOLVE_FULL, out=buf)
         assert F.stats()["sweep_persist"] == 0
         mu, X = F.posterior(rhs, 16, seed=7)

@@ -18,6 +18,7 @@ ERR_NOT_SPD, ERR_BAD_SHAPE, ERR_BAND, ERR_HIP, ERR_NO_FACTOR, ERR_NO_DEVICE, ERR
 SOLVE_FULL, SOLVE_FORWARD, SOLVE_BACKWARD = 0, 1, 2
 VAR_EXACT, VAR_RBMC, VAR_MC = 0, 1, 2
 BLOCK_L, BLOCK_C, BLOCK_LINV = 0, 1, 2
+ORDER_REFERENCE, ORDER_TWISTED = 0, 1
 
 # every symbol include/gmrf_hip.h declares (tests check that the library exports them all)
 EXPORTS = [
@@ -29,7 +30,7 @@ EXPORTS = [
     "gmrf_bt_set_keep_l", "gmrf_bt_storage_bytes", "gmrf_bt_set_storage", "gmrf_bt_factor_begin_csc",
     "gmrf_bt_factor_step_async", "gmrf_bt_factor_end", "gmrf_bt_stats",
     "gmrf_bt_set_profiling", "gmrf_bt_set_eager", "gmrf_bt_synchronize", "gmrf_bt_set_batch", "gmrf_bt_select_problem",
-    "gmrf_bt_marginal_var_batch", "gmrf_bt_export_size", "gmrf_bt_export_factor", "gmrf_bt_import_factor",
+    "gmrf_bt_marginal_var_batch", "gmrf_bt_set_order", "gmrf_bt_get_order", "gmrf_bt_half_stats", "gmrf_bt_export_size", "gmrf_bt_export_factor", "gmrf_bt_import_factor",
     "gmrf_comm_unique_id", "gmrf_comm_create", "gmrf_comm_destroy", "gmrf_comm_bcast_host", "gmrf_comm_allreduce_sum",
     "gmrf_bt_bcast_blocks_async", "gmrf_bt_allgather_blocks_async", "gmrf_comm_wait", "gmrf_comm_bytes", "gmrf_streams_create", "gmrf_streams_destroy",
     "gmrf_bt_packed_size", "gmrf_bt_pack_blocks_async", "gmrf_bt_unpack_blocks_async",
@@ -137,6 +138,9 @@ def load() -> C.CDLL:
         "gmrf_bt_factor_step_async": [vp, i64, i64],
         "gmrf_bt_factor_end": [vp, P(i32)],
         "gmrf_bt_stats": [vp, P(Stats)],
+        "gmrf_bt_set_order": [vp, i32, i64],
+        "gmrf_bt_get_order": [vp, P(i32), P(i64)],
+        "gmrf_bt_half_stats": [vp, i32, P(Stats)],
         "gmrf_bt_set_profiling": [vp, i32],
         "gmrf_bt_set_eager": [vp, i32],
         "gmrf_bt_synchronize": [vp],

@@ -513,15 +513,22 @@ class TridiagonalCholeskyFactor:
 
     `N` is the total size n (as in the reference, NOT the block count); `chos[i]` is the
     lower-triangular L_i, `Cs[i]` = L_{i+1,i}.
+
+    order = "twisted" (one problem): Q = T T^T, two chains that run at the same time and meet in block `meet`
+    (0-based; None = automatic).  `ldiv`, the marginal variances and `logdet` do not depend on the order; `chos[i]` is then
+    L_i (i <= meet) or the upper-triangular U_i, `Cs[i]` is G_{i+1} (i < meet) or H_i = T[i, i+1], the half-solves are
+    T^-1 b / T^-T b and a sample with a given z is mean + T^-T z (gmrf_bt_set_order).
     """
 
-    def __init__(self, device: int = 0, stream: int = 0, batch: int = 1):
+    def __init__(self, device: int = 0, stream: int = 0, batch: int = 1, order: str = "reference", meet: Optional[int] = None):
         self._h = C.c_void_p()
         self._lib = _cabi.load()
         _cabi.check(self._lib.gmrf_bt_create(device, C.c_void_p(stream), C.byref(self._h)))
         self.batch = 1
         if batch != 1:
             self.set_batch(batch)
+        if order != "reference" or meet is not None:
+            self.set_order(order, meet)
         self.N = 0
         self.n_blocks = 0
         self.block_size = 0
@@ -544,6 +551,32 @@ class TridiagonalCholeskyFactor:
     def set_batch(self, batch: int):
         _cabi.check(self._lib.gmrf_bt_set_batch(self._h, int(batch)))
         self.batch = int(batch)
+
+    def set_order(self, order: str, meet: Optional[int] = None):
+        """Elimination order "reference" or "twisted" (meeting block `meet`, None = automatic); drops the current factor."""
+        o = {"reference": _cabi.ORDER_REFERENCE, "twisted": _cabi.ORDER_TWISTED}.get(order)
+        if o is None:
+            raise ValueError('order must be "reference" or "twisted"')
+        _cabi.check(self._lib.gmrf_bt_set_order(self._h, o, -1 if meet is None else int(meet)))
+
+    @property
+    def order(self) -> str:
+        o, m = C.c_int32(0), C.c_int64(0)
+        _cabi.check(self._lib.gmrf_bt_get_order(self._h, C.byref(o), C.byref(m)))
+        return "twisted" if o.value == _cabi.ORDER_TWISTED else "reference"
+
+    @property
+    def meet(self) -> int:
+        """The meeting block (0-based): resolved by the last factorisation; n_blocks - 1 for the reference order."""
+        o, m = C.c_int32(0), C.c_int64(0)
+        _cabi.check(self._lib.gmrf_bt_get_order(self._h, C.byref(o), C.byref(m)))
+        return m.value
+
+    def half_stats(self, half: int) -> dict:
+        """stats() of one half of a twisted factor (0: blocks 0 .. meet, 1: blocks N-1 .. meet+1)."""
+        s = _cabi.Stats()
+        _cabi.check(self._lib.gmrf_bt_half_stats(self._h, int(half), C.byref(s)))
+        return {f: (list(getattr(s, f)) if hasattr(getattr(s, f), "__len__") else getattr(s, f)) for f, _ in s._fields_}
 
     def select_problem(self, p: int):
         _cabi.check(self._lib.gmrf_bt_select_problem(self._h, int(p)))
@@ -870,7 +903,8 @@ class TridiagonalCholeskyFactor:
 
 # ----------------------------------------------------------------------------- reference surface
 
-def tridiagonal_cholesky(A, N_blocks: int, device: int = 0, stream: int = 0) -> TridiagonalCholeskyFactor:
+def tridiagonal_cholesky(A, N_blocks: int, device: int = 0, stream: int = 0, order: str = "reference",
+                         meet: Optional[int] = None) -> TridiagonalCholeskyFactor:
     """tridiagonal_cholesky(A::SparseMatrixCSC, N_blocks)  (src/tridiagonal_cholesky.jl:65-82).
 
     Raises NotPositiveDefinite (PosDefException) with the failing block index, ValueError
@@ -880,7 +914,7 @@ def tridiagonal_cholesky(A, N_blocks: int, device: int = 0, stream: int = 0) -> 
     n = A.shape[0]
     if N_blocks <= 0 or n % N_blocks != 0:
         raise ValueError("size(A,1) must be a positive multiple of N_blocks")
-    return TridiagonalCholeskyFactor(device, stream).factor(A, N_blocks)
+    return TridiagonalCholeskyFactor(device, stream, order=order, meet=meet).factor(A, N_blocks)
 
 
 def forward_solve(L: TridiagonalCholeskyFactor, b):

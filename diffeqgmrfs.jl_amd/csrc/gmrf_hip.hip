@@ -135,6 +135,8 @@ struct GemmShapeStat {
     double launches = 0, ms = 0, work = 0;
 };
 
+struct TwistState;
+
 struct gmrf_handle {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -261,7 +263,59 @@ struct gmrf_handle {
     std::vector<GemmShapeStat> gemm_shapes;
     gmrf_stats stats;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    // elimination order (gmrf_bt_set_order): GMRF_ORDER_TWISTED runs the factorisation as two chains that meet in block m, on two
+    // one-problem sub-handles (TwistState); meet_req = -1: automatic
+    int order = GMRF_ORDER_REFERENCE;
+    int64_t meet_req = -1;
+    int32_t eager_bits = 0;            // last gmrf_bt_set_eager (handed on to the halves of a twisted handle)
+    TwistState* tw = nullptr;
+    // the top half of a twisted handle: block tw_blk is the meeting block, its Schur block also takes -HJ HJ^T (HJ = H_m J) and
+    // its factorisation leaves W = L_m^-1 HJ (the meeting corrections of the sweeps).  -1: a plain handle.
+    int64_t tw_blk = -1;
+    const double* tw_hj = nullptr;
+    double* tw_w = nullptr;
 };
+
+// --------------------------------------------------------------------------------- twisted (two-ended) order
+// Q = T T^T with T's diagonal blocks L_0 .. L_m (lower) and U_{m+1} .. U_{N-1} (upper), couplings G_i = T[i, i-1] (1 <= i <= m)
+// and H_i = T[i, i+1] (m <= i < N-1): two chains of about N / 2 blocks that run at the same time and meet in block m.  The handle
+// owns two one-problem sub-handles.  `top` factors blocks 0 .. m with the existing code; its meeting block also takes -H_m H_m^T
+// (the hook tw_blk / tw_hj of factor_blocks_range).  `bot` factors the FULLY index-reversed trailing matrix, x'_k = x_{n-1-k}
+// over blocks N-1 .. m+1: a plain block-tridiagonal matrix whose couplings keep the window / staircase shape (reversing the
+// block order alone would transpose them), so U_i = J L'_i J with J the flip inside a block.  The meeting coupling is kept as
+// HJ = H_m J = J C', where C' = B' L'^-T is the coupling the reversed chain would form for one more block; B-hat = J B' is
+// scattered straight from the caller's entries of Q[m+1, m].  W = L_m^-1 HJ is the one matrix both sweeps' meeting corrections
+// need:  forward  y_m -= W y'_last  (= L_m^-1 H_m y_{m+1}),  backward  y'_last -= W^T y_m  (= J H_m^T x_m with x_m = L_m^-T y_m).
+// Each half keeps its own single-stream captured graphs; the halves run on the handle's stream and on `aux`, forked and joined
+// with events.  m = N - 1: no bottom half, the handle IS its top half (the reference order, bitwise).
+struct TwistState {
+    gmrf_handle* top = nullptr;
+    gmrf_handle* bot = nullptr;
+    int64_t m = -1, N = 0, n = 0, bs = 0, bsp = 0, nnz = 0;
+    uint64_t* d_mkeys = nullptr;       // entries of Q[m+1, m] as entries of B-hat: (row gamma, column bs-1-rho) for Q[rho, gamma]
+    int64_t* d_msrc = nullptr;
+    double* d_mvals = nullptr;
+    int64_t m_count = 0;
+    double *d_Bm = nullptr, *d_HJ = nullptr, *d_W = nullptr, *d_Smm = nullptr;     // bsp x bsp, row-major
+    int64_t dense_bsp = 0;
+    double* d_nz = nullptr;            // staged host nzval (both halves gather from it)
+    const double* d_nz_cur = nullptr;  // the nzval of the current factorisation (device)
+    double* d_z = nullptr;             // column-major n x 64 samples (sampled variances)
+    double* d_var = nullptr;           // the bottom half's variances in its own (reversed) order
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+};
+
+
+static bool tw_on(const gmrf_handle* h) { return h && h->tw && h->tw->bot; }
+// A twisted handle whose meeting block is the last one IS its top half: the calls go there.
+static gmrf_handle* tw_route(gmrf_handle* h) {
+    return (h && h->order == GMRF_ORDER_TWISTED && h->tw && h->tw->top && !h->tw->bot && h->factored) ? h->tw->top : h;
+}
+static gmrf_status tw_refuse(const gmrf_handle* h, const char* what) {
+    if (!h || h->order != GMRF_ORDER_TWISTED) return GMRF_OK;
+    g_last_error = std::string(what) + ": not supported on a handle in the twisted elimination order (gmrf_bt_set_order)";
+    return GMRF_ERR_BAD_SHAPE;
+}
 
 static void destroy_graphs(gmrf_handle* h) {
     if (h->factor_graph) { (void)hipGraphExecDestroy(h->factor_graph); h->factor_graph = nullptr; }
@@ -1412,12 +1466,16 @@ static gmrf_status factor_blocks_range(gmrf_handle* h, int64_t i0, int64_t i1) {
                                h->n_entries, bstride, 1);
             HIPCHK(hipGetLastError());
         }
+        if (i == h->tw_blk && h->tw_hj)      // twisted order, meeting block: S -= H_m H_m^T = HJ HJ^T (J is an orthogonal flip)
+            GCHK(gemm(h, false, false, bsp, bsp, bsp, 0, 1, -1.0, h->tw_hj, ld, h->tw_hj, ld, 1.0, h->d_S, ld, 0, 0, 0));
         if (h->bsp > h->bs) {
             hipLaunchKernelGGL(pad_identity, dim3((unsigned)((h->bsp - h->bs + 255) / 256), nb), dim3(256), 0,
                                h->stream, h->d_S, ld, (int)h->bs, bsp, bstride);
             HIPCHK(hipGetLastError());
         }
         GCHK(potrf_block(h, h->d_S, L, X, h->d_T, (int)(i + 1)));
+        if (i == h->tw_blk && h->tw_w)       // W = L_m^-1 HJ: the coupling of the twisted sweeps' meeting corrections
+            GCHK(gemm(h, false, true, bsp, bsp, bsp, 0, 0, 1.0, X, ld, h->tw_hj, ld, 0.0, h->tw_w, ld, 0, 0, 0));
         if (!h->keep_l) {
             // L_i lives in a work buffer that the next block overwrites: its log-determinant part is taken now
             hipLaunchKernelGGL(logdet_blocks, dim3(1, nb), dim3(256), 0, h->stream, L, bstride, ld, (int)h->bs,
@@ -1829,10 +1887,12 @@ static gmrf_status sweep_launches(gmrf_handle* h, bool backward, int kp, double*
     return GMRF_OK;
 }
 
-// mode: 1 forward P->Y, 2 backward P->Y, 0 full P->Y->P (result in P)
+// mode: 1 forward P->Y, 2 backward P->Y, 0 full P->Y->P (result in P); 3 backward Y->P (the second half of a twisted solve)
+constexpr int SWEEP_BACKWARD_YP = 3;
 static gmrf_status run_sweeps(gmrf_handle* h, int mode, int kp) {
     auto body = [&]() -> gmrf_status {
         if (mode == GMRF_SOLVE_FORWARD) return sweep_launches(h, false, kp, h->d_P, h->d_Y);
+        if (mode == SWEEP_BACKWARD_YP) return sweep_launches(h, true, kp, h->d_Y, h->d_P);
         if (mode == GMRF_SOLVE_BACKWARD) return sweep_launches(h, true, kp, h->d_P, h->d_Y);
         GCHK(sweep_launches(h, false, kp, h->d_P, h->d_Y));
         return sweep_launches(h, true, kp, h->d_Y, h->d_P);
@@ -1909,6 +1969,19 @@ static gmrf_status cols_out(gmrf_handle* h, const double* panel, int k, const do
 
 constexpr int64_t KP_CHUNK = 128;
 
+// the twisted order (implemented with the variances, below)
+static void tw_free(gmrf_handle* h);
+static gmrf_status tw_analyze(gmrf_handle* h, int64_t n, int64_t N, const int64_t* colptr, const int64_t* rowval, int32_t base);
+static gmrf_status tw_numeric(gmrf_handle* h, const double* nzval, int32_t* info);
+static gmrf_status tw_solve(gmrf_handle* h, const double* b, double* y, int64_t k, int64_t ldb, int64_t ldy, int mode);
+static gmrf_status tw_sample(gmrf_handle* h, uint64_t seed, int64_t first_id, int64_t k, const double* mean, const double* z,
+                             double* out, int64_t ld);
+static gmrf_status tw_logdet(gmrf_handle* h, double* out);
+static gmrf_status tw_get_block(gmrf_handle* h, int32_t kind, int64_t i, double* out, int64_t ld);
+static gmrf_status tw_var_exact(gmrf_handle* h, double* d_out);
+static gmrf_status tw_var_accumulate_dev(gmrf_handle* h, int method, int64_t first_id, int64_t k, uint64_t seed, const gmrf_csr* Q,
+                                         double* d_acc);
+
 // ------------------------------------------------------------------------------------ C ABI
 extern "C" {
 
@@ -1950,6 +2023,7 @@ gmrf_status gmrf_bt_create(int32_t device, void* stream, gmrf_handle** out) {
 gmrf_status gmrf_bt_destroy(gmrf_handle* h) {
     if (!h) return GMRF_OK;
     (void)hipSetDevice(h->device);
+    tw_free(h);
     (void)hipStreamSynchronize(h->stream);
     persist_release(h);
     destroy_graphs(h);
@@ -1976,6 +2050,7 @@ gmrf_status gmrf_bt_destroy(gmrf_handle* h) {
 
 gmrf_status gmrf_bt_set_batch(gmrf_handle* h, int64_t batch) {
     if (!h || batch < 1 || batch > 4096) return bad_shape("batch must be in [1, 4096]");
+    if (batch != 1) GCHK(tw_refuse(h, "gmrf_bt_set_batch (batch > 1)"));
     if (batch != h->B) {
         HIPCHK(hipSetDevice(h->device));
         HIPCHK(hipStreamSynchronize(h->stream));
@@ -1998,6 +2073,8 @@ gmrf_status gmrf_bt_select_problem(gmrf_handle* h, int64_t p) {
 gmrf_status gmrf_bt_set_profiling(gmrf_handle* h, int32_t level) {
     if (!h) return bad_shape("null handle");
     h->profiling = level;
+    if (h->tw)
+        for (gmrf_handle* s : {h->tw->top, h->tw->bot}) if (s) GCHK(gmrf_bt_set_profiling(s, level));
     if (level > 0 && h->events.empty()) h->gemm_shapes.clear();
     for (int i = 0; i < GMRF_KERNEL_CLASSES; ++i) { h->stats.kernel_ms[i] = h->stats.kernel_work[i] = 0; h->stats.kernel_launches[i] = 0; }
     return GMRF_OK;
@@ -2018,17 +2095,37 @@ gmrf_status gmrf_bt_set_eager(gmrf_handle* h, int32_t eager) {
     if (((eager & 65536) != 0) != h->no_sweep_persist) { destroy_graphs(h); h->no_sweep_persist = (eager & 65536) != 0; }
     if (((eager & 131072) != 0) != h->no_scatter_fold) { destroy_graphs(h); h->no_scatter_fold = (eager & 131072) != 0; }
     h->eager = (eager & 1) != 0;
+    h->eager_bits = eager;
+    if (h->tw)
+        for (gmrf_handle* s : {h->tw->top, h->tw->bot})
+            if (s) {
+                GCHK(gmrf_bt_set_eager(s, eager));
+                if (h->tw->bot) s->no_sweep_persist = true;       // (the halves of a twisted handle never take the persistent sweep)
+            }
     return GMRF_OK;
 }
 
 gmrf_status gmrf_bt_synchronize(gmrf_handle* h) {
     if (!h) return bad_shape("null handle");
     HIPCHK(hipStreamSynchronize(h->stream));
+    if (tw_on(h)) HIPCHK(hipStreamSynchronize(h->tw->bot->stream));
     return GMRF_OK;
 }
 
 gmrf_status gmrf_bt_stats(gmrf_handle* h, gmrf_stats* out) {
     if (!h || !out) return bad_shape("null pointer");
+    if (tw_on(h)) {
+        // a twisted handle: its own timings, the halves' persistent launches (aborts summed)
+        const gmrf_stats &a = h->tw->top->stats, &b = h->tw->bot->stats;
+        *out = h->stats;
+        out->persist_route = a.persist_route;
+        out->persist_aborts = a.persist_aborts + b.persist_aborts;
+        out->persist_cus = a.persist_cus + b.persist_cus;
+        out->persist_refused = a.persist_refused | b.persist_refused;
+        out->factor_bytes = a.factor_bytes + b.factor_bytes;
+        return GMRF_OK;
+    }
+    h = tw_route(h);
     *out = h->stats;
     return GMRF_OK;
 }
@@ -2039,12 +2136,17 @@ gmrf_status gmrf_bt_factor_csc(gmrf_handle* h, int64_t n, int64_t n_blocks, cons
     if (!h) return bad_shape("null handle");
     HIPCHK(hipSetDevice(h->device));
     if (info) *info = 0;
+    if (h->order == GMRF_ORDER_TWISTED) {
+        GCHK(tw_analyze(h, n, n_blocks, colptr, rowval, index_base));
+        return tw_numeric(h, nzval, info);
+    }
     GCHK(analyze_csc(h, n, n_blocks, colptr, rowval, index_base));
     return numeric_factor(h, nzval, info);
 }
 
 gmrf_status gmrf_bt_factor_begin_csc(gmrf_handle* h, int64_t n, int64_t n_blocks, const int64_t* colptr,
                                      const int64_t* rowval, const double* nzval, int32_t index_base) {
+    GCHK(tw_refuse(h, "gmrf_bt_factor_begin_csc"));
     if (!h) return bad_shape("null handle");
     HIPCHK(hipSetDevice(h->device));
     if (colptr) GCHK(analyze_csc(h, n, n_blocks, colptr, rowval, index_base));
@@ -2063,6 +2165,7 @@ gmrf_status gmrf_bt_factor_begin_csc(gmrf_handle* h, int64_t n, int64_t n_blocks
 }
 
 gmrf_status gmrf_bt_factor_step_async(gmrf_handle* h, int64_t i0, int64_t i1) {
+    GCHK(tw_refuse(h, "gmrf_bt_factor_step_async"));
     if (!h) return bad_shape("null handle");
     if (i0 < 0 || i1 > h->N || i0 > i1) return bad_shape("bad block range");
     HIPCHK(hipSetDevice(h->device));
@@ -2075,6 +2178,7 @@ gmrf_status gmrf_bt_factor_step_async(gmrf_handle* h, int64_t i0, int64_t i1) {
 }
 
 gmrf_status gmrf_bt_factor_end(gmrf_handle* h, int32_t* info) {
+    GCHK(tw_refuse(h, "gmrf_bt_factor_end"));
     if (!h) return bad_shape("null handle");
     HIPCHK(hipSetDevice(h->device));
     gmrf_status s = factor_finish(h, info);
@@ -2086,12 +2190,14 @@ gmrf_status gmrf_bt_refactor_values(gmrf_handle* h, const double* nzval, int32_t
     if (!h) return bad_shape("null handle");
     HIPCHK(hipSetDevice(h->device));
     if (info) *info = 0;
+    if (h->order == GMRF_ORDER_TWISTED) return tw_numeric(h, nzval, info);
     return numeric_factor(h, nzval, info);
 }
 
 gmrf_status gmrf_bt_factor_blocks(gmrf_handle* h, int64_t n, int64_t n_blocks, const gmrf_sparse_block* diag,
                                   const gmrf_sparse_block* lower, int32_t index_base,
                                   int32_t compressed_by_column, int32_t* info) {
+    GCHK(tw_refuse(h, "gmrf_bt_factor_blocks"));
     if (!h || !diag || (n_blocks > 1 && !lower)) return bad_shape("null pointer");
     HIPCHK(hipSetDevice(h->device));
     if (info) *info = 0;
@@ -2133,6 +2239,7 @@ gmrf_status gmrf_bt_storage_bytes(int64_t n, int64_t n_blocks, int64_t batch, in
 
 gmrf_status gmrf_bt_set_storage(gmrf_handle* h, int64_t n, int64_t n_blocks, int64_t batch, void* dev_L, void* dev_C,
                                 void* dev_Linv) {
+    GCHK(tw_refuse(h, "gmrf_bt_set_storage"));
     if (!h || !dev_C || !dev_Linv) return bad_shape("null pointer");
     if (batch != h->B) return bad_shape("storage batch differs from the handle's batch (gmrf_bt_set_batch first)");
     if (!dev_L && h->keep_l) return bad_shape("dev_L may be NULL only after gmrf_bt_set_keep_l(h, 0)");
@@ -2165,6 +2272,7 @@ gmrf_status gmrf_bt_set_storage(gmrf_handle* h, int64_t n, int64_t n_blocks, int
 }
 
 gmrf_status gmrf_bt_set_keep_l(gmrf_handle* h, int32_t keep) {
+    GCHK(tw_refuse(h, "gmrf_bt_set_keep_l"));
     if (!h) return bad_shape("null handle");
     if ((keep != 0) == h->keep_l) return GMRF_OK;
     if (h->external_storage) return bad_shape("choose gmrf_bt_set_keep_l before gmrf_bt_set_storage");
@@ -2178,6 +2286,7 @@ gmrf_status gmrf_bt_set_keep_l(gmrf_handle* h, int32_t keep) {
 
 // Layout of the stored coupling blocks: out = {cmin, rmax, n_row_tiles, kst[0 .. n_row_tiles)} (kst relative to cmin).
 gmrf_status gmrf_bt_get_layout(gmrf_handle* h, int64_t* out, int64_t cap, int64_t* count) {
+    GCHK(tw_refuse(h, "gmrf_bt_get_layout"));
     if (!h || !count) return bad_shape("null pointer");
     if (h->N <= 0 || h->kst.empty()) { g_last_error = "no shape"; return GMRF_ERR_NO_FACTOR; }
     const int64_t nrt = h->rmax / 64;
@@ -2194,6 +2303,7 @@ gmrf_status gmrf_bt_get_layout(gmrf_handle* h, int64_t* out, int64_t cap, int64_
 // A rank that receives the factor by broadcast: shape + the root's layout (NULL: dense coupling blocks),
 // storage allocated (or the caller's, gmrf_bt_set_storage), nothing factored yet.
 gmrf_status gmrf_bt_adopt_layout(gmrf_handle* h, int64_t n, int64_t n_blocks, const int64_t* layout, int64_t count) {
+    GCHK(tw_refuse(h, "gmrf_bt_adopt_layout"));
     if (!h) return bad_shape("null handle");
     HIPCHK(hipSetDevice(h->device));
     GCHK(set_shape(h, n, n_blocks));
@@ -2225,11 +2335,13 @@ gmrf_status gmrf_bt_adopt_layout(gmrf_handle* h, int64_t n, int64_t n_blocks, co
 }
 
 gmrf_status gmrf_bt_adopt_shape(gmrf_handle* h, int64_t n, int64_t n_blocks) {
+    GCHK(tw_refuse(h, "gmrf_bt_adopt_shape"));
     return gmrf_bt_adopt_layout(h, n, n_blocks, nullptr, 0);
 }
 
 // l_blocks_valid != 0: the caller also filled the L buffer (gmrf_bt_factor_buffer kind L), so F.chos / logdet work
 gmrf_status gmrf_bt_adopt_commit(gmrf_handle* h, int32_t l_blocks_valid) {
+    GCHK(tw_refuse(h, "gmrf_bt_adopt_commit"));
     if (!h || !h->d_Linv) return bad_shape("no factor storage");
     HIPCHK(hipSetDevice(h->device));
     // Representation of the block inverses: a packed image says which form ITS sender was in when it packed (the layout record
@@ -2256,6 +2368,7 @@ gmrf_status gmrf_bt_adopt_commit(gmrf_handle* h, int32_t l_blocks_valid) {
 }
 
 gmrf_status gmrf_bt_factor_buffer(gmrf_handle* h, int32_t kind, void** dev_ptr, int64_t* bytes) {
+    GCHK(tw_refuse(h, "gmrf_bt_factor_buffer"));
     if (!h || !dev_ptr || !bytes) return bad_shape("null pointer");
     if (!h->d_Linv) { g_last_error = "no factor storage"; return GMRF_ERR_NO_FACTOR; }
     const int64_t blk = blk_elems(h) * (int64_t)sizeof(double) * h->B;
@@ -2273,6 +2386,7 @@ gmrf_status gmrf_bt_factor_buffer(gmrf_handle* h, int32_t kind, void** dev_ptr, 
 // block-range broadcast moves.  C holds the coupling blocks i0-1 .. i1-2 (C_i couples blocks i and i+1).
 gmrf_status gmrf_bt_block_range(gmrf_handle* h, int32_t kind, int64_t i0, int64_t i1, int64_t* first_elem,
                                 int64_t* n_elems, int64_t* problem_stride) {
+    GCHK(tw_refuse(h, "gmrf_bt_block_range"));
     if (!h || !first_elem || !n_elems || !problem_stride) return bad_shape("null pointer");
     if (h->N <= 0 || i0 < 0 || i1 > h->N || i0 > i1) return bad_shape("bad block range");
     if (kind == GMRF_BLOCK_C) {
@@ -2303,6 +2417,7 @@ static void packed_counts(const gmrf_handle* h, int64_t i0, int64_t i1, int64_t*
 }
 
 gmrf_status gmrf_bt_packed_size(gmrf_handle* h, int64_t i0, int64_t i1, int64_t* elems_per_problem) {
+    GCHK(tw_refuse(h, "gmrf_bt_packed_size"));
     if (!h || !elems_per_problem) return bad_shape("null pointer");
     if (h->N <= 0 || i0 < 0 || i1 > h->N || i0 >= i1) return bad_shape("bad block range");
     int64_t xe, ce, le;
@@ -2355,21 +2470,25 @@ static gmrf_status pack_blocks_on(gmrf_handle* h, hipStream_t st, int64_t i0, in
 }
 
 gmrf_status gmrf_bt_pack_blocks_async(gmrf_handle* h, int64_t i0, int64_t i1, double* dev_buf) {
+    GCHK(tw_refuse(h, "gmrf_bt_pack_blocks_async"));
     if (!h) return bad_shape("null handle");
     HIPCHK(hipSetDevice(h->device));
     return pack_blocks_on(h, h->stream, i0, i1, dev_buf, true);
 }
 
 gmrf_status gmrf_bt_unpack_blocks_async(gmrf_handle* h, int64_t i0, int64_t i1, const double* dev_buf) {
+    GCHK(tw_refuse(h, "gmrf_bt_unpack_blocks_async"));
     if (!h) return bad_shape("null handle");
     HIPCHK(hipSetDevice(h->device));
     return pack_blocks_on(h, h->stream, i0, i1, const_cast<double*>(dev_buf), false);
 }
 
 gmrf_status gmrf_bt_get_block(gmrf_handle* h, int32_t kind, int64_t i, double* out, int64_t ld) {
+    h = tw_route(h);
     if (!h || !out) return bad_shape("null pointer");
     if (!h->factored) { g_last_error = "no factor"; return GMRF_ERR_NO_FACTOR; }
     HIPCHK(hipSetDevice(h->device));
+    if (tw_on(h)) return tw_get_block(h, kind, i, out, ld);
     const int64_t bs = h->bs, bsp = h->bsp;
     if (ld < bs) return bad_shape("ld < block_size");
     // source window [rows][cols] with row stride lds, placed at (0, c0) of the logical block
@@ -2413,6 +2532,7 @@ gmrf_status gmrf_bt_get_block(gmrf_handle* h, int32_t kind, int64_t i, double* o
 static const int64_t EXPORT_MAGIC = 0x46524d47;   // "GMRF"
 
 gmrf_status gmrf_bt_export_size(gmrf_handle* h, int64_t* bytes) {
+    GCHK(tw_refuse(h, "gmrf_bt_export_size"));
     if (!h || !bytes) return bad_shape("null pointer");
     if (h->N <= 0) { g_last_error = "no shape"; return GMRF_ERR_NO_FACTOR; }
     *bytes = 64 + (int64_t)sizeof(double) * h->bs * h->bs * (3 * h->N - 1);
@@ -2420,6 +2540,7 @@ gmrf_status gmrf_bt_export_size(gmrf_handle* h, int64_t* bytes) {
 }
 
 gmrf_status gmrf_bt_export_factor(gmrf_handle* h, void* buf, int64_t bytes) {
+    GCHK(tw_refuse(h, "gmrf_bt_export_factor"));
     if (!h || !buf) return bad_shape("null pointer");
     if (!h->factored) { g_last_error = "no factor"; return GMRF_ERR_NO_FACTOR; }
     if (is_device_ptr(buf)) return bad_shape("export buffer must be host memory");
@@ -2439,6 +2560,7 @@ gmrf_status gmrf_bt_export_factor(gmrf_handle* h, void* buf, int64_t bytes) {
 }
 
 gmrf_status gmrf_bt_import_factor(gmrf_handle* h, const void* buf, int64_t bytes) {
+    GCHK(tw_refuse(h, "gmrf_bt_import_factor"));
     if (!h || !buf) return bad_shape("null pointer");
     if (is_device_ptr(buf)) return bad_shape("import buffer must be host memory");
     if (bytes < 64) return bad_shape("import buffer too small");
@@ -2651,6 +2773,7 @@ gmrf_status gmrf_comm_allreduce_sum(gmrf_comm* c, gmrf_handle* stream_of, double
 // of these blocks; receivers: the sweeps of the previous job that still read the buffers).  The root goes on
 // factoring the next range meanwhile.  with_l != 0: the raw L_i blocks follow (full squares).
 gmrf_status gmrf_bt_bcast_blocks_async(gmrf_handle* h, gmrf_comm* c, int32_t root, int64_t i0, int64_t i1, int32_t with_l) {
+    GCHK(tw_refuse(h, "gmrf_bt_bcast_blocks_async"));
     if (!h || !c) return bad_shape("null pointer");
     if (!h->d_Linv || h->N <= 0) { g_last_error = "no factor storage"; return GMRF_ERR_NO_FACTOR; }
     if (i0 < 0 || i1 > h->N || i0 >= i1 || root < 0 || root >= c->world) return bad_shape("bad block range / root");
@@ -2695,6 +2818,8 @@ gmrf_status gmrf_bt_bcast_blocks_async(gmrf_handle* h, gmrf_comm* c, int32_t roo
 // the whole batch leaving the root over each of ITS links) and the factorisation itself is spread over the ranks.
 // Enqueued on the communicator's stream behind src's stream; gmrf_comm_wait(dst, c) orders dst's stream behind the unpack.
 gmrf_status gmrf_bt_allgather_blocks_async(gmrf_handle* src, gmrf_handle* dst, gmrf_comm* c, int64_t i0, int64_t i1) {
+    GCHK(tw_refuse(src, "gmrf_bt_allgather_blocks_async"));
+    GCHK(tw_refuse(dst, "gmrf_bt_allgather_blocks_async"));
     if (!src || !dst || !c) return bad_shape("null pointer");
     if (!src->d_Linv || !dst->d_Linv || src->N <= 0) { g_last_error = "no factor storage"; return GMRF_ERR_NO_FACTOR; }
     if (src->n != dst->n || src->N != dst->N || src->bsp != dst->bsp || src->cmin != dst->cmin || src->rmax != dst->rmax || src->kst != dst->kst)
@@ -2742,11 +2867,13 @@ gmrf_status gmrf_comm_wait(gmrf_handle* h, gmrf_comm* c) {
 }
 
 gmrf_status gmrf_bt_solve(gmrf_handle* h, const double* b, double* y, int64_t k, int64_t ldb, int64_t ldy, int32_t mode) {
+    h = tw_route(h);
     if (!h || !b || !y) return bad_shape("null pointer");
     if (!h->factored) { g_last_error = "solve before factor"; return GMRF_ERR_NO_FACTOR; }
     if (k <= 0 || ldb < h->n || ldy < h->n || mode < 0 || mode > 2) return bad_shape("bad k / ldb / ldy / mode");
     if (b == y && ldb != ldy) return bad_shape("in place (y == b) needs ldb == ldy");
     HIPCHK(hipSetDevice(h->device));
+    if (tw_on(h)) return tw_solve(h, b, y, k, ldb, ldy, mode);
     if (h->B > 1 && k > KP_CHUNK) return bad_shape("with a batch of problems k is limited to 128 per call");
     const bool b_dev = is_device_ptr(b), y_dev = is_device_ptr(y);
     const int64_t nb = h->B;            // b / y hold nb consecutive groups of k columns (problem-major)
@@ -2810,11 +2937,13 @@ static gmrf_status sample_chunk(gmrf_handle* h, uint64_t seed, int64_t first_id,
 
 gmrf_status gmrf_bt_sample(gmrf_handle* h, uint64_t seed, int64_t first_id, int64_t k, const double* mean,
                            const double* z, double* out, int64_t ld) {
+    h = tw_route(h);
     if (!h || !out) return bad_shape("null pointer");
     if (!h->factored) { g_last_error = "sample before factor"; return GMRF_ERR_NO_FACTOR; }
     if (k <= 0 || ld < h->n) return bad_shape("bad k / ld");
     if (h->B > 1 && k > KP_CHUNK) return bad_shape("with a batch of problems k is limited to 128 per call");
     HIPCHK(hipSetDevice(h->device));
+    if (tw_on(h)) return tw_sample(h, seed, first_id, k, mean, z, out, ld);
     const double* d_mean = nullptr;
     GCHK(stage_vector(h, mean, &h->d_mean, &d_mean));
     const bool out_dev = is_device_ptr(out);
@@ -2840,6 +2969,32 @@ gmrf_status gmrf_bt_sample(gmrf_handle* h, uint64_t seed, int64_t first_id, int6
     return GMRF_OK;
 }
 
+// The handle's second stream `aux` on a hardware queue of its own (two streams on one queue serialise: gmrf_streams_create):
+// candidates are timed against this handle's stream with the 1 ms spin kernel, the first that overlaps is kept.  Used by
+// gmrf_bt_posterior (the samples' sweep beside the mean's) and by a twisted handle (the stream of its bottom half).
+static gmrf_status ensure_aux(gmrf_handle* h) {
+    if (h->aux_distinct) return GMRF_OK;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (h->aux) { (void)hipStreamSynchronize(h->aux); (void)hipStreamDestroy(h->aux); h->aux = nullptr; }
+    const unsigned long long ticks = 100000ull;
+    double one = 1e30;
+    for (int r = 0; r < 2; ++r) one = std::min(one, spin_pair_ms(h->stream, nullptr, ticks));
+    std::vector<hipStream_t> cand;
+    for (int c = 0; c < 12 && !h->aux; ++c) {
+        hipStream_t st = nullptr;
+        HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+        hipLaunchKernelGGL(gmrf_spin_kernel, dim3(1), dim3(64), 0, st, 1ull);      // (first use binds the stream to its queue)
+        (void)hipStreamSynchronize(st);
+        const double t = std::min(spin_pair_ms(h->stream, st, ticks), spin_pair_ms(h->stream, st, ticks));
+        if (t < 1.5 * one) h->aux = st; else cand.push_back(st);
+    }
+    if (!h->aux && !cand.empty()) { h->aux = cand.back(); cand.pop_back(); }       // (none overlaps: any will do, serialised)
+    for (hipStream_t st : cand) (void)hipStreamDestroy(st);
+    if (!h->aux) return bad_shape("internal: no second stream");
+    h->aux_distinct = true;
+    return GMRF_OK;
+}
+
 // The samples' backward sweep of gmrf_bt_posterior beside the mean's two (persistent launches, device pointers, no two of b, mean,
 // samples overlapping); ends in the synchronisation of the handle's stream.
 static gmrf_status posterior_beside(gmrf_handle* h, const double* b, uint64_t seed, int64_t first_id, int64_t k, double* mean,
@@ -2857,28 +3012,7 @@ static gmrf_status posterior_beside(gmrf_handle* h, const double* b, uint64_t se
         HIPCHK(hipMalloc(&h->d_T2, sizeof(double) * (size_t)elems));
         h->p2_elems = elems;
     }
-    if (!h->aux_distinct) {
-        // the second stream must sit on a hardware queue of its own (two streams on one queue serialise: gmrf_streams_create):
-        // candidates are timed against this handle's stream with the 1 ms spin kernel, the first that overlaps is kept
-        HIPCHK(hipStreamSynchronize(h->stream));
-        if (h->aux) { (void)hipStreamSynchronize(h->aux); (void)hipStreamDestroy(h->aux); h->aux = nullptr; }
-        const unsigned long long ticks = 100000ull;
-        double one = 1e30;
-        for (int r = 0; r < 2; ++r) one = std::min(one, spin_pair_ms(h->stream, nullptr, ticks));
-        std::vector<hipStream_t> cand;
-        for (int c = 0; c < 12 && !h->aux; ++c) {
-            hipStream_t st = nullptr;
-            HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-            hipLaunchKernelGGL(gmrf_spin_kernel, dim3(1), dim3(64), 0, st, 1ull);      // (first use binds the stream to its queue)
-            (void)hipStreamSynchronize(st);
-            const double t = std::min(spin_pair_ms(h->stream, st, ticks), spin_pair_ms(h->stream, st, ticks));
-            if (t < 1.5 * one) h->aux = st; else cand.push_back(st);
-        }
-        if (!h->aux && !cand.empty()) { h->aux = cand.back(); cand.pop_back(); }       // (none overlaps: any will do, serialised)
-        for (hipStream_t st : cand) (void)hipStreamDestroy(st);
-        if (!h->aux) return bad_shape("internal: no second stream");
-        h->aux_distinct = true;
-    }
+    GCHK(ensure_aux(h));
     h->fork_next = 0;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     GCHK(fork_event(h, &ev_fork)); GCHK(fork_event(h, &ev_join));
@@ -2917,6 +3051,7 @@ static gmrf_status posterior_beside(gmrf_handle* h, const double* b, uint64_t se
 // gmrf_bt_solve + gmrf_bt_sample: bitwise their results.  Anywhere else the call IS those two calls.
 gmrf_status gmrf_bt_posterior(gmrf_handle* h, const double* b, uint64_t seed, int64_t first_id, int64_t k, double* mean,
                               double* samples, int64_t ld) {
+    h = tw_route(h);
     if (!h || !b || !mean || !samples) return bad_shape("null pointer");
     if (!h->factored) { g_last_error = "posterior before factor"; return GMRF_ERR_NO_FACTOR; }
     if (k <= 0 || ld < h->n) return bad_shape("bad k / ld");
@@ -2928,7 +3063,8 @@ gmrf_status gmrf_bt_posterior(gmrf_handle* h, const double* b, uint64_t seed, in
     GCHK(sweep_guarded(h, {{b, vec_bytes, mean, vec_bytes}, {b, vec_bytes, samples, smp_bytes}, {mean, vec_bytes, samples, smp_bytes}},
                        [&]() -> gmrf_status {
         // (decided behind the hold, which sweep_persist_ok reads; the repeat after an abort finds the handle off the persistent form)
-        beside = h->B == 1 && k <= KP_CHUNK && k >= 2 && dev_all && !h->profiling && sweep_persist_ok(h, 1) && sweep_persist_ok(h, pad_k(k));
+        beside = !tw_on(h) && h->B == 1 && k <= KP_CHUNK && k >= 2 && dev_all && !h->profiling && sweep_persist_ok(h, 1) &&
+                 sweep_persist_ok(h, pad_k(k));      // (a twisted handle: its mean, then its samples)
         return beside ? posterior_beside(h, b, seed, first_id, k, mean, samples, ld) : GMRF_OK;
     }, [&]() -> gmrf_status {
         HIPCHK(hipStreamSynchronize(h->aux));
@@ -2967,9 +3103,11 @@ gmrf_status gmrf_bt_normals(gmrf_handle* h, uint64_t seed, int64_t first_id, int
 }
 
 gmrf_status gmrf_bt_logdet(gmrf_handle* h, double* out) {
+    h = tw_route(h);
     if (!h || !out) return bad_shape("null pointer");
     if (!h->factored) { g_last_error = "logdet before factor"; return GMRF_ERR_NO_FACTOR; }
     HIPCHK(hipSetDevice(h->device));
+    if (tw_on(h)) return tw_logdet(h, out);
     if (h->keep_l && h->l_valid) {
         hipLaunchKernelGGL(logdet_blocks, dim3((unsigned)h->N, 1), dim3(256), 0, h->stream,
                            h->d_L + h->sel * stride_pL(h), blk_elems(h), h->bsp, (int)h->bs, h->d_logdet + h->sel * h->N,
@@ -4035,7 +4173,9 @@ static gmrf_status need_single(gmrf_handle* h) {
     return GMRF_OK;
 }
 
-static gmrf_status var_exact(gmrf_handle* h, double* d_out) {
+// seeded: the twisted order's bottom half -- the caller has put the whole Sigma of the last block (its start, seeded by the
+// meeting block) into d_S; the recurrence goes on from there.
+static gmrf_status var_exact(gmrf_handle* h, double* d_out, bool seeded = false) {
     // Selected inversion (Takahashi recurrence on the block-tridiagonal factor), all problems of a batch in lock step:
     //   S_NN = X_N^T X_N,   S_ii = X_i^T (I + C_i^T S_{i+1,i+1} C_i) X_i,      X_i = Linv_i, C_i = L_{i+1,i};  d_out[B][n] = diag.
     // Round 4: what the recurrence NEEDS of S_ii is its diagonal and its leading rmax x rmax block (C_i is zero below row rmax
@@ -4067,6 +4207,12 @@ static gmrf_status var_exact(gmrf_handle* h, double* d_out) {
     double* V2 = h->d_V + bstride * h->B;                // M
     const int nt = bsp / 64, trm = rm / 64, twc = wc / 64;
     for (int64_t i = h->N - 1; i >= 0; --i) {
+        if (seeded && i == h->N - 1) {
+            hipLaunchKernelGGL(extract_diag_dense, dim3((unsigned)((h->bs + 255) / 256), nb), dim3(256), 0, h->stream, Sg, ld, (int)h->bs,
+                               d_out + i * h->bs, bstride, h->n);
+            HIPCHK(hipGetLastError());
+            continue;
+        }
         const double* X = h->d_Linv + i * bstride;
         const bool coupled = i < h->N - 1;
         if (coupled) {
@@ -4118,15 +4264,19 @@ static gmrf_status var_exact(gmrf_handle* h, double* d_out) {
 // accumulator: the samples leave the sweep as a panel (each right-hand side contiguous); the
 // transposing unpack puts the kc values of a node side by side, which is the layout the LDS-tiled
 // SpMM and the accumulator read with full 128-byte lines.
+// (panel != nullptr: the samples come from that panel, leading dimension panel_ld, blocks of pbs rows padded to pbsp -- a twisted
+//  handle passes its samples column-major, pbs = pbsp = n)
 static gmrf_status var_chunk(gmrf_handle* h, int method, int64_t p, int kc, const gmrf_csr* Q, const double* q_vals,
-                             const double* d_diag, double* d_acc) {
+                             const double* d_diag, double* d_acc, const double* panel = nullptr, int64_t panel_ld = 0,
+                             int64_t pbs = 0, int64_t pbsp = 0) {
     const int64_t n = h->n;
     const int kp = pad_k(kc), kcp = kc + (kc & 1);
     GCHK(ensure_stage(h, 2 * (int64_t)kcp * n));
     double* Xr = h->d_stage;
     double* QX = h->d_stage + (int64_t)kcp * n;
+    if (!panel) { panel = h->d_Y + p * kp * h->n_pad; panel_ld = h->n_pad; pbs = h->bs; pbsp = h->bsp; }
     hipLaunchKernelGGL(unpack_panel_rows, dim3((unsigned)((n + 63) / 64), (unsigned)((kc + 63) / 64)), dim3(256), 0, h->stream,
-                       h->d_Y + p * kp * h->n_pad, h->n_pad, Xr, (int64_t)kcp, (int)h->bs, (int)h->bsp, n, kc);
+                       panel, panel_ld, Xr, (int64_t)kcp, (int)pbs, (int)pbsp, n, kc);
     HIPCHK(hipGetLastError());
     if (method == GMRF_VAR_RBMC) GCHK(spmm_rows_device(Q, h->stream, Xr, kcp, QX, kcp, kc, q_vals));
     hipLaunchKernelGGL(rbmc_accumulate_rows, dim3((unsigned)((n + 15) / 16)), dim3(256), 0, h->stream, QX, Xr, (int64_t)kcp,
@@ -4156,6 +4306,7 @@ static gmrf_status ensure_acc(gmrf_handle* h, int64_t B) {
 
 gmrf_status gmrf_bt_var_accumulate(gmrf_handle* h, int32_t method, int64_t first_id, int64_t k, uint64_t seed,
                                    const gmrf_csr* Q, double* acc) {
+    h = tw_route(h);
     if (!h || !acc) return bad_shape("null pointer");
     if (!h->factored) { g_last_error = "variance before factor"; return GMRF_ERR_NO_FACTOR; }
     if (method != GMRF_VAR_RBMC && method != GMRF_VAR_MC) return bad_shape("accumulate needs RBMC or MC");
@@ -4169,7 +4320,7 @@ gmrf_status gmrf_bt_var_accumulate(gmrf_handle* h, int32_t method, int64_t first
     double* d_acc = dev ? acc : h->d_acc;
     GCHK(sweep_guarded(h, {}, [&]() -> gmrf_status {
         HIPCHK(hipMemcpyAsync(h->d_acc, acc, sizeof(double) * h->n, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
-        GCHK(var_accumulate_dev(h, method, first_id, k, seed, Q, d_acc));
+        GCHK(tw_on(h) ? tw_var_accumulate_dev(h, method, first_id, k, seed, Q, d_acc) : var_accumulate_dev(h, method, first_id, k, seed, Q, d_acc));
         HIPCHK(hipStreamSynchronize(h->stream));
         return GMRF_OK;
     }, [&]() -> gmrf_status {
@@ -4185,6 +4336,7 @@ gmrf_status gmrf_bt_var_accumulate(gmrf_handle* h, int32_t method, int64_t first
 
 gmrf_status gmrf_bt_marginal_var(gmrf_handle* h, int32_t method, int64_t k, uint64_t seed, const gmrf_csr* Q,
                                  double* var_out) {
+    h = tw_route(h);
     if (!h || !var_out) return bad_shape("null pointer");
     if (!h->factored) { g_last_error = "variance before factor"; return GMRF_ERR_NO_FACTOR; }
     if (method != GMRF_VAR_EXACT) {
@@ -4198,10 +4350,10 @@ gmrf_status gmrf_bt_marginal_var(gmrf_handle* h, int32_t method, int64_t k, uint
     const hipMemcpyKind kind = is_device_ptr(var_out) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
     GCHK(sweep_guarded(h, {}, [&]() -> gmrf_status {
         if (method == GMRF_VAR_EXACT) {
-            GCHK(var_exact(h, h->d_acc));              // selected inversion; var_out is [batch][n]
+            GCHK(tw_on(h) ? tw_var_exact(h, h->d_acc) : var_exact(h, h->d_acc));      // selected inversion; var_out is [batch][n]
         } else {
             HIPCHK(hipMemsetAsync(h->d_acc, 0, sizeof(double) * h->n, h->stream));
-            GCHK(var_accumulate_dev(h, method, 0, k, seed, Q, h->d_acc));
+            GCHK(tw_on(h) ? tw_var_accumulate_dev(h, method, 0, k, seed, Q, h->d_acc) : var_accumulate_dev(h, method, 0, k, seed, Q, h->d_acc));
             // finish in place: var = base + acc / k
             hipLaunchKernelGGL(var_finish, dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, h->stream, h->d_acc,
                                method == GMRF_VAR_RBMC ? Q->d_diag : (const double*)nullptr, 1.0 / (double)k, h->n, h->d_acc);
@@ -4222,6 +4374,7 @@ gmrf_status gmrf_bt_marginal_var(gmrf_handle* h, int32_t method, int64_t k, uint
 // p * k .. p * k + k - 1, so problem 0 equals what a one-problem handle computes.
 gmrf_status gmrf_bt_marginal_var_batch(gmrf_handle* h, int32_t method, int64_t k, uint64_t seed, const gmrf_csr* Q,
                                        const double* q_vals, double* var_out) {
+    GCHK(tw_refuse(h, "gmrf_bt_marginal_var_batch"));
     if (!h || !var_out) return bad_shape("null pointer");
     if (!h->factored) { g_last_error = "variance before factor"; return GMRF_ERR_NO_FACTOR; }
     if (method != GMRF_VAR_RBMC && method != GMRF_VAR_MC) return bad_shape("batch variances: RBMC or MC (exact: gmrf_bt_marginal_var)");
@@ -4266,6 +4419,515 @@ gmrf_status gmrf_bt_marginal_var_batch(gmrf_handle* h, int32_t method, int64_t k
         HIPCHK(hipStreamSynchronize(h->stream));
         return GMRF_OK;
     }));
+    return GMRF_OK;
+}
+
+// the meeting block when the two halves' forms cost a and b per block: m a = (N - 1 - m) b.  Launch-per-step over persistent
+// in-block form, per block: 1.51 measured on MI355X (darcy256 reference order: 20.22 ms with GMRF_PERSIST=0 against 13.38 ms,
+// tools/twisted_latency.py), used as 1.5; GMRF_TWIST_RATIO overrides it (tuning aid).
+static double tw_step_ratio() {
+    static const double r = [] { const char* e = getenv("GMRF_TWIST_RATIO"); const double v = e ? atof(e) : 0.0; return v > 0.0 ? v : 1.5; }();
+    return r;
+}
+static int64_t tw_auto_meet(int64_t N, bool top_persist, bool bot_persist) {
+    if (N < 3) return N - 1;
+    const double a = top_persist ? 1.0 : tw_step_ratio(), b = bot_persist ? 1.0 : tw_step_ratio();
+    const int64_t m = (int64_t)std::llround((double)(N - 1) * b / (a + b));
+    return std::min<int64_t>(std::max<int64_t>(m, 1), N - 2);
+}
+
+// The handle's OWN factor (a reference-order one) is dropped: its claim on the device's persistent-launch budget (else the halves
+// of a twisted factorisation would be refused it, and sweep_persist_ok would still let a call run persistent sweeps over the old
+// buffers), its captured graphs, and its factor storage (re-allocated by the next reference-order factorisation; caller-owned
+// storage is left to the caller).
+static void tw_drop_own_factor(gmrf_handle* h) {
+    (void)hipStreamSynchronize(h->stream);
+    persist_release(h);
+    destroy_graphs(h);
+    h->factored = false;
+    h->xsplit = 0;
+    h->l_valid = h->logdet_valid = false;
+    if (h->external_storage) return;
+    free_dev(h->d_L); free_dev(h->d_C); free_dev(h->d_Linv);
+    free_dev(h->d_S); free_dev(h->d_B); free_dev(h->d_T); free_dev(h->d_W); free_dev(h->d_logdet); free_dev(h->d_V);
+    h->d_L = h->d_C = h->d_Linv = h->d_S = h->d_B = h->d_T = h->d_W = h->d_logdet = h->d_V = nullptr;
+    h->v_elems = 0;
+    h->alloc_N = h->alloc_bsp = h->alloc_B = 0;
+    h->stats.factor_bytes = 0;
+}
+
+static void tw_free(gmrf_handle* h) {
+    TwistState* t = h->tw;
+    if (!t) return;
+    if (t->bot) (void)hipStreamSynchronize(t->bot->stream);
+    (void)hipStreamSynchronize(h->stream);
+    if (t->top) (void)gmrf_bt_destroy(t->top);
+    if (t->bot) (void)gmrf_bt_destroy(t->bot);
+    free_dev(t->d_mkeys); free_dev(t->d_msrc); free_dev(t->d_mvals);
+    free_dev(t->d_Bm); free_dev(t->d_HJ); free_dev(t->d_W); free_dev(t->d_Smm);
+    free_dev(t->d_nz); free_dev(t->d_z); free_dev(t->d_var);
+    if (t->ev_fork) (void)hipEventDestroy(t->ev_fork);
+    if (t->ev_join) (void)hipEventDestroy(t->ev_join);
+    delete t;
+    h->tw = nullptr;
+}
+
+static gmrf_status tw_new_half(gmrf_handle* h, hipStream_t st, gmrf_handle** out) {
+    GCHK(gmrf_bt_create(h->device, (void*)st, out));
+    GCHK(gmrf_bt_set_eager(*out, h->eager_bits));
+    (*out)->profiling = h->profiling;
+    return GMRF_OK;
+}
+
+static gmrf_status tw_fork(gmrf_handle* h) {
+    HIPCHK(hipEventRecord(h->tw->ev_fork, h->stream));
+    HIPCHK(hipStreamWaitEvent(h->tw->bot->stream, h->tw->ev_fork, 0));
+    return GMRF_OK;
+}
+static gmrf_status tw_join(gmrf_handle* h) {
+    HIPCHK(hipEventRecord(h->tw->ev_join, h->tw->bot->stream));
+    HIPCHK(hipStreamWaitEvent(h->stream, h->tw->ev_join, 0));
+    return GMRF_OK;
+}
+
+// symbolic phase: the meeting block, both halves' entry lists (the bottom's fully reversed) and the meeting coupling's
+static gmrf_status tw_analyze(gmrf_handle* h, int64_t n, int64_t N, const int64_t* colptr, const int64_t* rowval, int32_t base) {
+    if (!colptr || !rowval) return bad_shape("null CSC arrays");
+    if (h->B != 1) return bad_shape("the twisted order needs batch 1");
+    tw_drop_own_factor(h);                     // (a reference-order factor of this handle, whatever way it came)
+    GCHK(set_shape(h, n, N));                  // the handle's own shape: staging of host columns, normals
+    h->analyzed = false;                       // (the handle's own pattern, if it had one, is not this factor's)
+    if (h->meet_req > N - 1) return bad_shape("twisted order: meet must lie in [0, N_blocks - 1] (or -1: automatic)");
+    const int64_t bs = h->bs;
+    std::vector<std::vector<HostEntry>> dg, lo;
+    GCHK(split_csc(n, N, bs, colptr, rowval, base, dg, lo));
+    if (!h->tw) {
+        h->tw = new TwistState();
+        HIPCHK(hipEventCreateWithFlags(&h->tw->ev_fork, hipEventDisableTiming));
+        HIPCHK(hipEventCreateWithFlags(&h->tw->ev_join, hipEventDisableTiming));
+    }
+    TwistState* t = h->tw;
+    if (!t->top) GCHK(tw_new_half(h, h->stream, &t->top));
+    int64_t m = h->meet_req;
+    if (m < 0 && N < 3) m = N - 1;
+    if (m < 0 || m < N - 1) {
+        if (!t->bot) { GCHK(ensure_aux(h)); GCHK(tw_new_half(h, h->aux, &t->bot)); }
+        // the halves never take the persistent sweep: it needs every CU while the other half runs
+        t->top->no_sweep_persist = t->bot->no_sweep_persist = true;
+    }
+    if (m < 0) {
+        // automatic: which half's in-block Cholesky is the persistent form decides the balance (the CU budget holds one
+        // 1024-block launch, not two); the routes depend on the block size, not on the number of blocks
+        // (planned at the halves' block size without reshaping them: a new shape would drop their panels and graphs)
+        const int64_t bsp = 64 * next_pow2((bs + 63) / 64);
+        for (gmrf_handle* s : {t->top, t->bot}) {
+            const int64_t keep = s->bsp;
+            s->bsp = bsp;
+            persist_plan(s);
+            s->bsp = keep;
+        }
+        m = tw_auto_meet(N, t->top->persist_cus > 0, t->bot->persist_cus > 0);
+    }
+    if (m == N - 1 && t->bot) { (void)gmrf_bt_destroy(t->bot); t->bot = nullptr; }
+    if (!t->bot) t->top->no_sweep_persist = h->no_sweep_persist;
+    t->m = m; t->N = N; t->n = n; t->bs = bs; t->nnz = colptr[n] - base;
+    const int64_t nnz = t->nnz;
+    {   // top: blocks 0 .. m as they are
+        std::vector<std::vector<HostEntry>> dgt(dg.begin(), dg.begin() + m + 1), lot(lo.begin(), lo.begin() + m + 1);
+        GCHK(set_shape(t->top, (m + 1) * bs, m + 1));
+        GCHK(upload_entries(t->top, dgt, lot, nnz));
+    }
+    t->top->tw_blk = -1; t->top->tw_hj = nullptr; t->top->tw_w = nullptr;
+    t->bsp = t->top->bsp;
+    if (!t->bot) return GMRF_OK;
+    const int64_t Nb = N - 1 - m;
+    {   // bottom: block j is block N-1-j, entry (r, c) of a block -> (bs-1-r, bs-1-c); diagonal entries transposed back to the
+        // lower triangle, the coupling of bottom blocks j, j-1 is Q[N-1-j, N-j] = lo[N-j]^T
+        std::vector<std::vector<HostEntry>> dgb((size_t)Nb), lob((size_t)Nb);
+        for (int64_t j = 0; j < Nb; ++j) {
+            for (const auto& e : dg[(size_t)(N - 1 - j)]) {
+                const uint64_t r = e.key >> 32, c = e.key & 0xffffffffu;
+                dgb[(size_t)j].push_back({((uint64_t)(bs - 1 - c) << 32) | (uint64_t)(bs - 1 - r), e.src});
+            }
+            if (j >= 1)
+                for (const auto& e : lo[(size_t)(N - j)]) {
+                    const uint64_t rho = e.key >> 32, gam = e.key & 0xffffffffu;
+                    lob[(size_t)j].push_back({((uint64_t)(bs - 1 - gam) << 32) | (uint64_t)(bs - 1 - rho), e.src});
+                }
+        }
+        GCHK(set_shape(t->bot, Nb * bs, Nb));
+        GCHK(upload_entries(t->bot, dgb, lob, nnz));
+    }
+    {   // the meeting coupling: Q[rho, gamma] of lo[m+1] is B-hat[gamma][bs-1-rho]
+        std::vector<uint64_t> keys;
+        std::vector<int64_t> src;
+        for (const auto& e : lo[(size_t)(m + 1)]) {
+            const uint64_t rho = e.key >> 32, gam = e.key & 0xffffffffu;
+            keys.push_back((gam << 32) | (uint64_t)(bs - 1 - rho));
+            src.push_back(e.src);
+        }
+        free_dev(t->d_mkeys); free_dev(t->d_msrc); free_dev(t->d_mvals);
+        t->d_mkeys = nullptr; t->d_msrc = nullptr; t->d_mvals = nullptr;
+        t->m_count = (int64_t)keys.size();
+        const size_t ne = std::max<size_t>(keys.size(), 1);
+        HIPCHK(hipMalloc(&t->d_mkeys, ne * sizeof(uint64_t)));
+        HIPCHK(hipMalloc(&t->d_msrc, ne * sizeof(int64_t)));
+        HIPCHK(hipMalloc(&t->d_mvals, ne * sizeof(double)));
+        if (!keys.empty()) {
+            HIPCHK(hipMemcpyAsync(t->d_mkeys, keys.data(), keys.size() * sizeof(uint64_t), hipMemcpyHostToDevice, h->stream));
+            HIPCHK(hipMemcpyAsync(t->d_msrc, src.data(), src.size() * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+            HIPCHK(hipStreamSynchronize(h->stream));
+        }
+    }
+    if (t->dense_bsp != t->bsp) {
+        free_dev(t->d_Bm); free_dev(t->d_HJ); free_dev(t->d_W); free_dev(t->d_Smm);
+        t->d_Bm = t->d_HJ = t->d_W = t->d_Smm = nullptr; t->dense_bsp = 0;
+        const size_t bytes = sizeof(double) * (size_t)(t->bsp * t->bsp);
+        HIPCHK(hipMalloc(&t->d_Bm, bytes)); HIPCHK(hipMalloc(&t->d_HJ, bytes));
+        HIPCHK(hipMalloc(&t->d_W, bytes)); HIPCHK(hipMalloc(&t->d_Smm, bytes));
+        t->dense_bsp = t->bsp;
+    }
+    free_dev(t->d_var); t->d_var = nullptr;
+    HIPCHK(hipMalloc(&t->d_var, sizeof(double) * (size_t)(Nb * bs)));
+    free_dev(t->d_z); t->d_z = nullptr;
+    free_dev(t->d_nz); t->d_nz = nullptr;
+    return GMRF_OK;
+}
+
+// HJ = B-hat L'^-T of the bottom half's last block (= J C'), on the bottom half's stream
+static gmrf_status tw_meeting_coupling(gmrf_handle* h) {
+    TwistState* t = h->tw;
+    gmrf_handle* bot = t->bot;
+    const int bsp = (int)t->bsp;
+    HIPCHK(hipMemsetAsync(t->d_Bm, 0, sizeof(double) * (size_t)bsp * bsp, bot->stream));
+    if (t->m_count > 0) {
+        hipLaunchKernelGGL(gather_values, dim3((unsigned)((t->m_count + 255) / 256), 1), dim3(256), 0, bot->stream, t->d_nz_cur, t->d_msrc,
+                           t->m_count, t->d_mvals, t->nnz);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(scatter_block, dim3((unsigned)((t->m_count + 255) / 256), 1), dim3(256), 0, bot->stream, t->d_mkeys, t->d_mvals,
+                           (int64_t)0, t->m_count, t->d_Bm, (int64_t)bsp, t->m_count, (int64_t)0, 0);
+        HIPCHK(hipGetLastError());
+    }
+    const double* X = bot->d_Linv + (bot->N - 1) * (int64_t)bsp * bsp;
+    GCHK(gemm(bot, false, false, bsp, bsp, bsp, 0, 0, 1.0, t->d_Bm, bsp, X, bsp, 0.0, t->d_HJ, bsp, 0, 0, 0));
+    return GMRF_OK;
+}
+
+// numeric phase: bottom chain + meeting coupling on the second stream, top chain up to the meeting block on this one, then the
+// meeting block; a persistent launch that gave up goes through each half's own repeat
+static gmrf_status tw_numeric(gmrf_handle* h, const double* nzval, int32_t* info) {
+    TwistState* t = h->tw;
+    if (!t || !t->top || !t->top->analyzed) { g_last_error = "no sparsity pattern analysed"; return GMRF_ERR_NO_FACTOR; }
+    if (!nzval) return bad_shape("null nzval");
+    h->factored = false;
+    gmrf_handle *top = t->top, *bot = t->bot;
+    if (!bot) {
+        gmrf_status s = numeric_factor(top, nzval, info);
+        h->factored = top->factored;
+        h->stats.factor_ms = top->stats.factor_ms;
+        return s;
+    }
+    const int64_t m = t->m, Nb = bot->N, N = t->N;
+    const double* d_nz = nzval;
+    if (!is_device_ptr(nzval)) {
+        if (!t->d_nz) HIPCHK(hipMalloc(&t->d_nz, sizeof(double) * (size_t)std::max<int64_t>(t->nnz, 1)));
+        HIPCHK(hipMemcpyAsync(t->d_nz, nzval, sizeof(double) * t->nnz, hipMemcpyHostToDevice, h->stream));
+        d_nz = t->d_nz;
+    }
+    t->d_nz_cur = d_nz;
+    for (gmrf_handle* s : {top, bot}) {
+        GCHK(alloc_factor(s));
+        if (s->c_dirty) {
+            HIPCHK(hipMemsetAsync(s->d_C, 0, sizeof(double) * stride_pC(s) * s->B, s->stream));
+            s->c_dirty = false;
+        }
+        persist_plan(s);
+        s->factored = false;
+    }
+    top->tw_blk = m; top->tw_hj = t->d_HJ; top->tw_w = t->d_W;
+    HIPCHK(hipEventRecord(h->ev0, h->stream));
+    GCHK(tw_fork(h));
+    // second stream: the bottom chain, then the meeting coupling
+    GCHK(load_values(bot, d_nz));
+    HIPCHK(hipMemsetAsync(bot->d_info, 0, 4 * sizeof(int), bot->stream));
+    bot->info_checked = 0; bot->persist_launched = false;
+    GCHK(run_factor(bot, 0, Nb));
+    GCHK(tw_meeting_coupling(h));
+    // this stream: the top chain up to the meeting block, which waits for the coupling
+    GCHK(load_values(top, d_nz));
+    HIPCHK(hipMemsetAsync(top->d_info, 0, 4 * sizeof(int), top->stream));
+    top->info_checked = 0; top->persist_launched = false;
+    if (m > 0) GCHK(run_factor(top, 0, m));
+    GCHK(tw_join(h));
+    GCHK(factor_blocks_range(top, m, m + 1));
+    HIPCHK(hipEventRecord(h->ev1, h->stream));
+    int ib = 0, it = 0;
+    const int aborts_bot = bot->persist_aborts;
+    GCHK(persist_check_range(bot, 0, Nb, &ib));
+    if (bot->persist_aborts != aborts_bot) {
+        // the bottom chain was repeated: its coupling and the whole top half (whose meeting block read the old one) again
+        HIPCHK(hipStreamSynchronize(h->stream));
+        GCHK(tw_meeting_coupling(h));
+        HIPCHK(hipStreamSynchronize(bot->stream));
+        HIPCHK(hipMemsetAsync(top->d_info, 0, 4 * sizeof(int), top->stream));
+        top->info_checked = 0;
+        GCHK(factor_blocks_range(top, 0, m + 1));
+    }
+    GCHK(persist_check_range(top, 0, m + 1, &it));
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, h->ev0, h->ev1);
+    h->stats.factor_ms = ms;
+    top->stats.factor_ms = ms; bot->stats.factor_ms = ms;
+    if (top->profiling) prof_collect(top);
+    if (bot->profiling) prof_collect(bot);
+    int64_t fail = 0;
+    if (it >= 1 && it <= m) fail = it;                 // the top chain (its numbering is the original one)
+    else if (ib != 0) fail = N + 1 - ib;               // the bottom chain: its block j is block N-1-j
+    else if (it == m + 1) fail = m + 1;                // the meeting block
+    if (info) *info = (int32_t)fail;
+    if (fail) {
+        g_last_error = "matrix is not positive definite; failed block " + std::to_string(fail) + " (twisted order, meeting block " +
+                       std::to_string(m + 1) + ")";
+        return GMRF_ERR_NOT_SPD;
+    }
+    for (gmrf_handle* s : {top, bot}) { s->factored = true; s->l_valid = s->keep_l; s->logdet_valid = !s->keep_l; }
+    h->factored = true;
+    return GMRF_OK;
+}
+
+// the caller's columns (device, leading dimension ld) -> both panels; src == nullptr: Philox normals of samples first_id + r
+static gmrf_status tw_fill(gmrf_handle* h, const double* d_src, int64_t ld, int k, int kp, uint64_t seed, int64_t first_id) {
+    TwistState* t = h->tw;
+    const int64_t total = (int64_t)kp * (t->top->n_pad + t->bot->n_pad);
+    hipLaunchKernelGGL(tw_fill_panels, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, d_src, ld, t->top->d_P,
+                       t->top->n_pad, t->bot->d_P, t->bot->n_pad, (int)t->bs, (int)t->bsp, t->n, k, kp, seed, first_id);
+    HIPCHK(hipGetLastError());
+    return GMRF_OK;
+}
+
+// both halves' panels (P: full solve, Y: otherwise) -> the caller's (dst, ld), plus d_mean; host dst through d_stage
+static gmrf_status tw_cols_out(gmrf_handle* h, bool from_p, int k, const double* d_mean, double* dst, int64_t ld, bool dst_dev) {
+    TwistState* t = h->tw;
+    const double* pt = from_p ? t->top->d_P : t->top->d_Y;
+    const double* pb = from_p ? t->bot->d_P : t->bot->d_Y;
+    double* d = dst;
+    int64_t ldd = ld;
+    if (!dst_dev) { GCHK(ensure_stage(h, (int64_t)k * h->n)); d = h->d_stage; ldd = h->n; }
+    const int64_t total = t->n * (int64_t)k;
+    hipLaunchKernelGGL(tw_unpack_panels, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, pt, t->top->n_pad, pb,
+                       t->bot->n_pad, d, ldd, (int)t->bs, (int)t->bsp, t->n, (t->m + 1) * t->bs, k, d_mean);
+    HIPCHK(hipGetLastError());
+    if (!dst_dev)
+        HIPCHK(hipMemcpy2DAsync(dst, ld * sizeof(double), h->d_stage, h->n * sizeof(double), h->n * sizeof(double), k,
+                                hipMemcpyDeviceToHost, h->stream));
+    return GMRF_OK;
+}
+
+static gmrf_status tw_couple_launch(gmrf_handle* h, bool trans, int kp, const double* src, int64_t lds, double* dst, int64_t ldd) {
+    const int bsp = (int)h->tw->bsp;
+    const dim3 grid((unsigned)(bsp / 64), (unsigned)((kp + 15) / 16));
+    if (trans) hipLaunchKernelGGL(tw_couple<true>, grid, dim3(256), 0, h->stream, h->tw->d_W, bsp, src, lds, dst, ldd, kp);
+    else hipLaunchKernelGGL(tw_couple<false>, grid, dim3(256), 0, h->stream, h->tw->d_W, bsp, src, lds, dst, ldd, kp);
+    HIPCHK(hipGetLastError());
+    return GMRF_OK;
+}
+
+// mode FORWARD: P -> Y (T^-1), BACKWARD: P -> Y (T^-T), FULL: P -> Y -> P; both halves' sweeps run at the same time
+static gmrf_status tw_sweeps(gmrf_handle* h, int mode, int kp) {
+    TwistState* t = h->tw;
+    gmrf_handle *top = t->top, *bot = t->bot;
+    const int64_t om = t->m * t->bsp, ol = (bot->N - 1) * t->bsp;
+    if (mode == GMRF_SOLVE_BACKWARD) {
+        GCHK(tw_couple_launch(h, true, kp, top->d_P + om, top->n_pad, bot->d_P + ol, bot->n_pad));
+        GCHK(tw_fork(h));
+        GCHK(run_sweeps(top, GMRF_SOLVE_BACKWARD, kp));
+        GCHK(run_sweeps(bot, GMRF_SOLVE_BACKWARD, kp));
+        return tw_join(h);
+    }
+    GCHK(tw_fork(h));
+    GCHK(run_sweeps(top, GMRF_SOLVE_FORWARD, kp));
+    GCHK(run_sweeps(bot, GMRF_SOLVE_FORWARD, kp));
+    GCHK(tw_join(h));
+    GCHK(tw_couple_launch(h, false, kp, bot->d_Y + ol, bot->n_pad, top->d_Y + om, top->n_pad));
+    if (mode == GMRF_SOLVE_FORWARD) return GMRF_OK;
+    GCHK(tw_couple_launch(h, true, kp, top->d_Y + om, top->n_pad, bot->d_Y + ol, bot->n_pad));
+    GCHK(tw_fork(h));
+    GCHK(run_sweeps(top, SWEEP_BACKWARD_YP, kp));
+    GCHK(run_sweeps(bot, SWEEP_BACKWARD_YP, kp));
+    return tw_join(h);
+}
+
+static gmrf_status tw_panels(gmrf_handle* h, int kp) {
+    GCHK(ensure_panels(h->tw->top, kp));
+    GCHK(ensure_panels(h->tw->bot, kp));
+    return GMRF_OK;
+}
+
+static gmrf_status tw_solve(gmrf_handle* h, const double* b, double* y, int64_t k, int64_t ldb, int64_t ldy, int mode) {
+    const bool b_dev = is_device_ptr(b), y_dev = is_device_ptr(y);
+    h->stats.solve_ms = 0.0;
+    for (int64_t c0 = 0; c0 < k; c0 += KP_CHUNK) {
+        const int kc = (int)std::min<int64_t>(KP_CHUNK, k - c0);
+        const int kp = pad_k(kc);
+        GCHK(tw_panels(h, kp));
+        const double* d_b = nullptr;
+        int64_t ld_b = 0;
+        GCHK(cols_in(h, b + c0 * ldb, ldb, b_dev, kc, &d_b, &ld_b));
+        GCHK(tw_fill(h, d_b, ld_b, kc, kp, 0, 0));
+        HIPCHK(hipEventRecord(h->ev0, h->stream));
+        GCHK(tw_sweeps(h, mode, kp));
+        HIPCHK(hipEventRecord(h->ev1, h->stream));
+        GCHK(tw_cols_out(h, mode == GMRF_SOLVE_FULL, kc, nullptr, y + c0 * ldy, ldy, y_dev));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        float ms = 0.f;
+        (void)hipEventElapsedTime(&ms, h->ev0, h->ev1);
+        h->stats.solve_ms += ms;
+        h->stats.sweep_ms = ms / ((mode == GMRF_SOLVE_FULL) ? 2 : 1);
+        h->stats.sweep_bytes = sweep_bytes(h, kc);
+    }
+    return GMRF_OK;
+}
+
+// samples [first_id, first_id + kc) (or the caller's z) -> both panels -> T^-T z in the Y panels
+static gmrf_status tw_sample_chunk(gmrf_handle* h, uint64_t seed, int64_t first_id, int kc, const double* z, int64_t ldz) {
+    const int kp = pad_k(kc);
+    GCHK(tw_panels(h, kp));
+    const double* d_z = nullptr;
+    int64_t ldd = 0;
+    if (z) GCHK(cols_in(h, z, ldz, is_device_ptr(z), kc, &d_z, &ldd));
+    GCHK(tw_fill(h, d_z, ldd, kc, kp, seed, first_id));
+    return tw_sweeps(h, GMRF_SOLVE_BACKWARD, kp);
+}
+
+static gmrf_status tw_sample(gmrf_handle* h, uint64_t seed, int64_t first_id, int64_t k, const double* mean, const double* z,
+                             double* out, int64_t ld) {
+    const double* d_mean = nullptr;
+    GCHK(stage_vector(h, mean, &h->d_mean, &d_mean));
+    const bool out_dev = is_device_ptr(out);
+    HIPCHK(hipEventRecord(h->ev0, h->stream));
+    for (int64_t c0 = 0; c0 < k; c0 += KP_CHUNK) {
+        const int kc = (int)std::min<int64_t>(KP_CHUNK, k - c0);
+        GCHK(tw_sample_chunk(h, seed, first_id + c0, kc, z ? z + c0 * ld : nullptr, ld));
+        GCHK(tw_cols_out(h, false, kc, d_mean, out + c0 * ld, ld, out_dev));
+        if (!out_dev) HIPCHK(hipStreamSynchronize(h->stream));
+    }
+    HIPCHK(hipEventRecord(h->ev1, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, h->ev0, h->ev1);
+    h->stats.sample_ms = ms;
+    return GMRF_OK;
+}
+
+// exact variances: the top half's own recurrence (it starts at Sigma_mm = L_m^-T L_m^-1) on this stream; on the second stream the
+// bottom half's, seeded with  Sigma' = L'^-T (I + HJ^T Sigma_mm HJ) L'^-1  for its last block (block m+1, reversed)
+static gmrf_status tw_var_exact(gmrf_handle* h, double* d_out) {
+    TwistState* t = h->tw;
+    gmrf_handle *top = t->top, *bot = t->bot;
+    const int bsp = (int)t->bsp;
+    const int64_t bstride = (int64_t)bsp * bsp;
+    GCHK(ensure_full_inverse(top)); GCHK(ensure_full_inverse(bot));
+    GCHK(tw_fork(h));
+    {
+        const double* Xm = top->d_Linv + t->m * bstride;
+        const double* Xl = bot->d_Linv + (bot->N - 1) * bstride;
+        GCHK(gemm(bot, true, true, bsp, bsp, bsp, 0, 0, 1.0, Xm, bsp, Xm, bsp, 0.0, t->d_Smm, bsp, 0, 0, 0));           // Sigma_mm
+        GCHK(gemm(bot, false, true, bsp, bsp, bsp, 0, 0, 1.0, t->d_Smm, bsp, t->d_HJ, bsp, 0.0, bot->d_W, bsp, 0, 0, 0));  // Sigma_mm HJ
+        GCHK(gemm(bot, true, true, bsp, bsp, bsp, 0, 0, 1.0, t->d_HJ, bsp, bot->d_W, bsp, 0.0, bot->d_B, bsp, 0, 0, 0));  // HJ^T Sigma_mm HJ
+        hipLaunchKernelGGL(add_identity, dim3((unsigned)((bsp + 255) / 256)), dim3(256), 0, bot->stream, bot->d_B, (int64_t)bsp, bsp);
+        HIPCHK(hipGetLastError());
+        GCHK(gemm(bot, false, true, bsp, bsp, bsp, 0, 0, 1.0, bot->d_B, bsp, Xl, bsp, 0.0, bot->d_T, bsp, 0, 0, 0));       // (I + M) L'^-1
+        GCHK(gemm(bot, true, true, bsp, bsp, bsp, 0, 0, 1.0, Xl, bsp, bot->d_T, bsp, 0.0, bot->d_S, bsp, 0, 0, 0));        // Sigma'
+        GCHK(var_exact(bot, t->d_var, true));
+        const int64_t cnt = bot->N * t->bs;
+        hipLaunchKernelGGL(tw_reverse, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, bot->stream, t->d_var, d_out + (t->m + 1) * t->bs, cnt);
+        HIPCHK(hipGetLastError());
+    }
+    GCHK(var_exact(top, d_out));
+    return tw_join(h);
+}
+
+// sampled variances: chunks of 64 twisted samples (no mean), column-major in d_z, into the accumulator (var_chunk)
+static gmrf_status tw_var_accumulate_dev(gmrf_handle* h, int method, int64_t first_id, int64_t k, uint64_t seed, const gmrf_csr* Q,
+                                         double* d_acc) {
+    TwistState* t = h->tw;
+    if (!t->d_z) HIPCHK(hipMalloc(&t->d_z, sizeof(double) * (size_t)(64 * t->n)));
+    for (int64_t c0 = 0; c0 < k; c0 += 64) {
+        const int kc = (int)std::min<int64_t>(64, k - c0);
+        GCHK(tw_sample_chunk(h, seed, first_id + c0, kc, nullptr, 0));
+        GCHK(tw_cols_out(h, false, kc, nullptr, t->d_z, t->n, true));
+        GCHK(var_chunk(h, method, 0, kc, Q, nullptr, Q ? Q->d_diag : nullptr, d_acc, t->d_z, t->n, t->n, t->n));
+    }
+    return GMRF_OK;
+}
+
+static gmrf_status tw_logdet(gmrf_handle* h, double* out) {
+    double a = 0.0, b = 0.0;
+    GCHK(gmrf_bt_logdet(h->tw->top, &a));
+    GCHK(gmrf_bt_logdet(h->tw->bot, &b));
+    *out = a + b;
+    return GMRF_OK;
+}
+
+// blocks of T in original coordinates: a bottom block is J (block of the reversed chain) J
+static gmrf_status tw_get_block(gmrf_handle* h, int32_t kind, int64_t i, double* out, int64_t ld) {
+    TwistState* t = h->tw;
+    const int64_t N = t->N, m = t->m, bs = t->bs, bsp = t->bsp;
+    if (ld < bs) return bad_shape("ld < block_size");
+    std::vector<double> tmp((size_t)(bs * bs)), res((size_t)(bs * bs));     // column-major, leading dimension bs
+    bool flip = false;
+    if (kind == GMRF_BLOCK_L || kind == GMRF_BLOCK_LINV) {
+        if (i < 0 || i >= N) return bad_shape("block index");
+        if (i <= m) GCHK(gmrf_bt_get_block(t->top, kind, i, tmp.data(), bs));
+        else { GCHK(gmrf_bt_get_block(t->bot, kind, N - 1 - i, tmp.data(), bs)); flip = true; }
+    } else if (kind == GMRF_BLOCK_C) {
+        if (i < 0 || i >= N - 1) return bad_shape("block index");
+        if (i < m) GCHK(gmrf_bt_get_block(t->top, kind, i, tmp.data(), bs));                  // G_{i+1}
+        else if (i > m) { GCHK(gmrf_bt_get_block(t->bot, kind, N - 2 - i, tmp.data(), bs)); flip = true; }   // H_i
+        else {                                                                                 // H_m = HJ J
+            std::vector<double> hj((size_t)(bsp * bsp));
+            HIPCHK(hipMemcpyAsync(hj.data(), t->d_HJ, hj.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(hipStreamSynchronize(h->stream));
+            for (int64_t c = 0; c < bs; ++c)
+                for (int64_t r = 0; r < bs; ++r) tmp[(size_t)(c * bs + r)] = hj[(size_t)(r * bsp + (bs - 1 - c))];
+        }
+    } else return bad_shape("bad block kind");
+    for (int64_t c = 0; c < bs; ++c)
+        for (int64_t r = 0; r < bs; ++r)
+            res[(size_t)(c * bs + r)] = flip ? tmp[(size_t)((bs - 1 - c) * bs + (bs - 1 - r))] : tmp[(size_t)(c * bs + r)];
+    HIPCHK(hipMemcpy2DAsync(out, ld * sizeof(double), res.data(), bs * sizeof(double), bs * sizeof(double), bs, hipMemcpyDefault, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return GMRF_OK;
+}
+
+gmrf_status gmrf_bt_set_order(gmrf_handle* h, int32_t order, int64_t meet) {
+    if (!h) return bad_shape("null handle");
+    if (order != GMRF_ORDER_REFERENCE && order != GMRF_ORDER_TWISTED) return bad_shape("unknown elimination order");
+    if (meet < -1) return bad_shape("twisted order: meet must be -1 (automatic) or a block index");
+    if (order == GMRF_ORDER_TWISTED && h->B != 1) return bad_shape("the twisted order needs batch 1");
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    tw_free(h);
+    tw_drop_own_factor(h);
+    h->order = order;
+    h->meet_req = meet;
+    return GMRF_OK;
+}
+
+gmrf_status gmrf_bt_get_order(gmrf_handle* h, int32_t* order, int64_t* meet) {
+    if (!h || !order || !meet) return bad_shape("null pointer");
+    *order = h->order;
+    if (h->order == GMRF_ORDER_TWISTED) *meet = (h->tw && h->tw->m >= 0) ? h->tw->m : h->meet_req;
+    else *meet = h->N > 0 ? h->N - 1 : -1;
+    return GMRF_OK;
+}
+
+gmrf_status gmrf_bt_half_stats(gmrf_handle* h, int32_t half, gmrf_stats* out) {
+    if (!h || !out) return bad_shape("null pointer");
+    if (h->order != GMRF_ORDER_TWISTED || !h->tw || !h->tw->top) return bad_shape("gmrf_bt_half_stats: not a factored twisted handle");
+    if (half != 0 && half != 1) return bad_shape("half must be 0 (top) or 1 (bottom)");
+    if (half == 1 && !h->tw->bot) { memset(out, 0, sizeof(*out)); return GMRF_OK; }
+    *out = (half == 0 ? h->tw->top : h->tw->bot)->stats;
     return GMRF_OK;
 }
 

@@ -1148,4 +1148,96 @@ __global__ __launch_bounds__(256) void hbm_read_kernel(const double2* __restrict
     if (acc == 12345.678) out[0] = acc;
 }
 
+// ------------------------------------------------------------------------------- twisted order
+// A handle in the two-ended order keeps its right-hand sides in two panels: the top panel Pt[rhs][npt] holds the blocks
+// 0 .. m in the original order, the bottom panel Pb[rhs][npb] the blocks N-1 .. m+1 FULLY index-reversed: row j' (block
+// j' / bsp, offset j' % bsp < bs) of the bottom panel is dof n - 1 - ((j' / bsp) bs + j' % bsp).  Padding rows are zero.
+// src != nullptr: the caller's column-major n x k (leading dimension ld) -> both panels;
+// src == nullptr: Philox normals of samples first_id + r, keyed by the ORIGINAL dof (the draws fill_normals_panel makes).
+__global__ void tw_fill_panels(const double* __restrict__ src, int64_t ld, double* __restrict__ Pt, int64_t npt,
+                               double* __restrict__ Pb, int64_t npb, int bs, int bsp, int64_t n, int k, int kp,
+                               uint64_t seed, int64_t first_id) {
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t rows = npt + npb;
+    if (idx >= (int64_t)kp * rows) return;
+    const int64_t r = idx / rows, j = idx % rows;
+    const bool top = j < npt;
+    const int64_t jj = top ? j : j - npt;
+    const int64_t blk = jj / bsp, off = jj % bsp;
+    double v = 0.0;
+    if (r < k && off < bs) {
+        const int64_t dof = top ? blk * bs + off : n - 1 - (blk * bs + off);
+        v = src ? src[r * ld + dof] : philox_normal(seed, (uint64_t)dof, (uint64_t)(first_id + r));
+    }
+    if (top) Pt[r * npt + jj] = v;
+    else Pb[r * npb + jj] = v;
+}
+
+// both panels -> the caller's column-major n x k (leading dimension ld), plus mean[dof] if given (unpack_panel's sum).
+// ntop = (m + 1) bs: the dofs the top panel holds.
+__global__ void tw_unpack_panels(const double* __restrict__ Pt, int64_t npt, const double* __restrict__ Pb, int64_t npb,
+                                 double* __restrict__ dst, int64_t ld, int bs, int bsp, int64_t n, int64_t ntop, int k,
+                                 const double* __restrict__ mean) {
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= n * (int64_t)k) return;
+    const int64_t r = idx / n, j = idx % n;
+    double v;
+    if (j < ntop) {
+        v = Pt[r * npt + (j / bs) * bsp + j % bs];
+    } else {
+        const int64_t q = n - 1 - j;
+        v = Pb[r * npb + (q / bs) * bsp + q % bs];
+    }
+    if (mean) v += mean[j];
+    dst[r * ld + j] = v;
+}
+
+// dst[i] = src[cnt - 1 - i]: the bottom half's variances (reversed order) into the original order
+__global__ void tw_reverse(const double* __restrict__ src, double* __restrict__ dst, int64_t cnt) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < cnt) dst[i] = src[cnt - 1 - i];
+}
+
+// Meeting corrections of the twisted sweeps, one bsp-row block of k right-hand sides against the dense bsp x bsp coupling
+// W (row-major), panels with leading dimensions lds / ldd (doubles per right-hand side):
+//   TRANS = false:  dst[j][r] -= sum_c W[r][c] src[j][c]      (forward:  y_m     -= L_m^-1 H_m y_{m+1})
+//   TRANS = true:   dst[j][c] -= sum_r W[r][c] src[j][r]      (backward: y_{m+1} -= H_m^T L_m^-T y_m, reversed)
+// A workgroup (16 x 16 threads) owns 64 output rows x 16 right-hand sides; 16-wide K slices of W and of the source go through
+// LDS.  grid (bsp / 64, ceil(kp / 16)); bsp % 64 == 0.
+template <bool TRANS>
+__global__ __launch_bounds__(256) void tw_couple(const double* __restrict__ W, int bsp, const double* __restrict__ src, int64_t lds,
+                                                 double* __restrict__ dst, int64_t ldd, int kp) {
+    __shared__ double wt[64][17];      // [output row][k]
+    __shared__ double xt[16][17];      // [rhs][k]
+    const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
+    const int o0 = blockIdx.x * 64, j0 = blockIdx.y * 16;
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int k0 = 0; k0 < bsp; k0 += 16) {
+        for (int e = threadIdx.x; e < 64 * 16; e += 256) {
+            int o, kk;
+            double v;
+            if (TRANS) { kk = e >> 6; o = e & 63; v = W[(int64_t)(k0 + kk) * bsp + o0 + o]; }
+            else { o = e >> 4; kk = e & 15; v = W[(int64_t)(o0 + o) * bsp + k0 + kk]; }
+            wt[o][kk] = v;
+        }
+        {
+            const int jj = ty, kk = tx;
+            xt[jj][kk] = (j0 + jj < kp) ? src[(int64_t)(j0 + jj) * lds + k0 + kk] : 0.0;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int kk = 0; kk < 16; ++kk) {
+            const double x = xt[tx][kk];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) acc[q] += wt[ty * 4 + q][kk] * x;
+        }
+        __syncthreads();
+    }
+    if (j0 + tx < kp) {
+        double* d = dst + (int64_t)(j0 + tx) * ldd + o0 + ty * 4;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) d[q] -= acc[q];
+    }
+}
+
 }  // namespace gmrf

@@ -351,6 +351,26 @@ gmrf_status gmrf_bt_factor_end(gmrf_handle* h, int32_t* info);
 gmrf_status gmrf_bt_set_batch(gmrf_handle* h, int64_t batch);
 gmrf_status gmrf_bt_select_problem(gmrf_handle* h, int64_t p);
 
+/* Elimination order of one problem.  REFERENCE (default): L L^T, blocks 0 .. N-1 in turn, as the reference does.
+ * TWISTED: Q = T T^T with two chains that run at the same time -- blocks 0 .. m-1 downward (L_i, G_i = T[i, i-1]), blocks N-1 ..
+ * m+1 upward (upper-triangular U_i, H_i = T[i, i+1]) -- and meet in block m: L_m L_m^T = D_m - G_m G_m^T - H_m H_m^T.  The same
+ * flops in about half the dependent steps.  Order-invariant: A^-1 b, marginal variances, logdet.  Order-specific: the blocks
+ * (gmrf_bt_get_block: kind L -> L_i (i <= m) or U_i (i > m); kind C, index i -> G_{i+1} (i < m) or H_i (i >= m); kind LINV ->
+ * T_ii^-1), the half-solves (FORWARD = T^-1 b, BACKWARD = T^-T b) and a sample mean + T^-T z for a given z (the Philox z of a
+ * seed / id is the same in both orders).
+ * meet = -1: automatic (balances the two chains; N < 3: m = N - 1, which is the reference order bitwise); otherwise m in
+ * [0, N-1], checked at factor time.  Unknown order: GMRF_ERR_BAD_SHAPE.  The call drops the current factor and pattern.
+ * A twisted handle needs batch 1 and supports factor_csc, refactor_values, solve, sample, posterior, normals, marginal_var,
+ * var_accumulate, logdet, get_block, stats, synchronize, set_eager and set_profiling; every other gmrf_bt_* call on it returns
+ * GMRF_ERR_BAD_SHAPE with a gmrf_last_error that names the twisted order.  NOT_SPD: *info = the failing block, original 1-based.
+ * gmrf_bt_get_order returns the resolved m after a factorisation (N - 1 for the reference order). */
+enum { GMRF_ORDER_REFERENCE = 0, GMRF_ORDER_TWISTED = 1 };
+gmrf_status gmrf_bt_set_order(gmrf_handle* h, int32_t order, int64_t meet);
+gmrf_status gmrf_bt_get_order(gmrf_handle* h, int32_t* order, int64_t* meet);
+/* Statistics of one half of a twisted handle (half 0: blocks 0 .. m, half 1: blocks N-1 .. m+1; persist_route / persist_cus /
+ * persist_aborts of that half's factorisation).  gmrf_bt_stats of a twisted handle sums both halves' persist_aborts. */
+gmrf_status gmrf_bt_half_stats(gmrf_handle* h, int32_t half, gmrf_stats* out);
+
 gmrf_status gmrf_bt_stats(gmrf_handle* h, gmrf_stats* out);
 gmrf_status gmrf_bt_set_profiling(gmrf_handle* h, int32_t level);
 /* bit 0: plain stream launches instead of replaying captured HIP graphs; bit 1: three-launch

@@ -120,10 +120,12 @@ values for a batch of problems on the pattern of `A` (with `batch` set on the fa
 """
 function tridiagonal_cholesky(A::SparseMatrixCSC{Float64,Int}, N_blocks::Integer; device::Integer = 0,
                               F::TridiagonalCholeskyFactor = TridiagonalCholeskyFactor{Float64}(device),
-                              nzvals::StridedVecOrMat{Float64} = A.nzval)
+                              nzvals::StridedVecOrMat{Float64} = A.nzval, order::Symbol = :reference, meet::Integer = -1)
     n = size(A, 1)
     n % N_blocks == 0 || throw(DimensionMismatch("size(A,1) must be a multiple of N_blocks"))
     length(nzvals) == nnz(A) * F.batch || throw(DimensionMismatch("nzvals must hold nnz x batch values"))
+    order in (:reference, :twisted) || throw(ArgumentError("order must be :reference or :twisted"))
+    (order === :twisted || get_order(F)[1] !== :reference) && set_order!(F, order; meet = meet)
     info = Ref{Int32}(0)
     GC.@preserve A nzvals begin
         st = ccall((:gmrf_bt_factor_csc, libgmrf), Int32,
@@ -134,6 +136,27 @@ function tridiagonal_cholesky(A::SparseMatrixCSC{Float64,Int}, N_blocks::Integer
     setfield!(F, :N, n)
     setfield!(F, :n_blocks, Int(N_blocks))
     return F
+end
+
+"""
+    set_order!(F, order; meet = -1)
+
+Elimination order of a one-problem factor (gmrf_bt_set_order): `:reference` (L L^T, the reference's order) or `:twisted`
+(Q = T T^T, two chains that meet in block `meet`, 0-based; -1 = automatic).  Drops the current factor.  With `:twisted`,
+`F.chos[i]` is L_i (i <= meet) or the UPPER-triangular U_i, `F.Cs[i]` is G_{i+1} (i < meet) or H_i; `ldiv` and the
+variances do not depend on the order.
+"""
+function set_order!(F::TridiagonalCholeskyFactor, order::Symbol; meet::Integer = -1)
+    order in (:reference, :twisted) || throw(ArgumentError("order must be :reference or :twisted"))
+    check(ccall((:gmrf_bt_set_order, libgmrf), Int32, (Ptr{Cvoid}, Int32, Int64), getfield(F, :handle),
+                order === :twisted ? 1 : 0, meet))
+    return F
+end
+"(order, meet): the elimination order and the resolved meeting block (0-based; N_blocks - 1 for `:reference`)."
+function get_order(F::TridiagonalCholeskyFactor)
+    o = Ref{Int32}(0); m = Ref{Int64}(0)
+    check(ccall((:gmrf_bt_get_order, libgmrf), Int32, (Ptr{Cvoid}, Ref{Int32}, Ref{Int64}), getfield(F, :handle), o, m))
+    return (o[] == 1 ? :twisted : :reference, Int(m[]))
 end
 
 "Re-factor with new values on the same sparsity pattern (Gauss-Newton loop, scripts/solve_burger.jl:143-149)."
@@ -306,6 +329,12 @@ end
 function stats(F::TridiagonalCholeskyFactor)
     s = Ref{GmrfStats}()
     check(ccall((:gmrf_bt_stats, libgmrf), Int32, (Ptr{Cvoid}, Ref{GmrfStats}), F.handle, s))
+    return s[]
+end
+"Statistics of one half of a twisted factor (0: blocks 0 .. meet, 1: blocks N-1 .. meet+1)."
+function half_stats(F::TridiagonalCholeskyFactor, half::Integer)
+    s = Ref{GmrfStats}()
+    check(ccall((:gmrf_bt_half_stats, libgmrf), Int32, (Ptr{Cvoid}, Int32, Ref{GmrfStats}), F.handle, half, s))
     return s[]
 end
 set_profiling!(F::TridiagonalCholeskyFactor, level::Integer) =

@@ -745,6 +745,20 @@ class TridiagonalCholeskyFactor:
                                                 self.N))
         return mview, sview
 
+    def posterior_batch(self, b, k: int, seed: int = 0x5EED, first_id: int = 0):
+        """(mean, samples) of a batch in ONE call (gmrf_bt_posterior): b (B, 1, n) or (B, n) torch CUDA tensor -> mean (B, n),
+        samples (B, k, n) with the sample ids of `sample_batch` (problem p, sample s: first_id + p*k + s).  Where the samples'
+        sweep runs on the GEMM (k <= 128, padded to a multiple of 64, enough tiles) and no output overlaps an input, the mean's
+        backward sweep is the tail row of the samples' (one pass over the factor; samples' L^-T z bitwise `sample_batch`, the mean
+        at rounding level of `solve_batch`); else the call is `solve_batch` + `sample_batch`.  set_eager bit 18 keeps the latter."""
+        import torch
+        B, n = self.batch, self.N
+        b = b.reshape(B, n).contiguous()
+        mean = torch.empty((B, n), dtype=torch.float64, device=b.device)
+        out = torch.empty((B, k, n), dtype=torch.float64, device=b.device)
+        _cabi.check(self._lib.gmrf_bt_posterior(self._h, _cabi.ptr(b), seed, first_id, k, _cabi.ptr(mean), _cabi.ptr(out), n))
+        return mean, out
+
     def marginal_var(self, method: str = "exact", k: int = 50, seed: int = 0x5EED, Q: Optional[CsrMatrix] = None,
                      q_values=None, out=None):
         """diag(Q^-1).  "exact" (selected inversion), "rbmc" (the reference's RBMCStrategy(k); needs Q)

@@ -90,16 +90,25 @@ __device__ __forceinline__ void gemm_dma_tile_order(const GemmArgs& g, int& bm, 
 // fragments pair neighbouring ROW tiles the way that image pairs column tiles: MFMA tile i = 2 ip + q of a wave holds the rows
 // wm + 32 ip + 2 li + q (li = MFMA row index), which only moves where the epilogue puts a register.  Same k slots, same
 // summation order: bitwise the result of transposing A first.
-template <int BM, int BN, bool B_N, int STAGES, bool A_T = false>
+//
+// TAIL (round 6, 64 x 64 tiles, B stored [k][n]): ONE more output row, row M of A / C / D (the operands hold M + 1 rows), summed on
+// the VALU from the B tile the MFMAs already read.  The workgroups of the last row tile stage A's row M beside the tile (16 doubles
+// per K step, lanes 0 .. 7 of wave 0: one more LDS-DMA request); wave w takes k pair group w >> 1 of a K step for its 32 columns --
+// the B fragments it holds anyway -- with 4 fp64 FMAs per lane, and the 8 partial sums of a column are added in a fixed order at
+// the end.  The M rows of the MFMA tile are untouched: bitwise those of the kernel without the tail.  (The batched posterior runs
+// the mean's backward sweep as this row of the samples' sweep: gmrf_hip.hip, posterior_fused.)
+template <int BM, int BN, bool B_N, int STAGES, bool A_T = false, bool TAIL = false>
 __global__ __launch_bounds__(256, (BM + BN > 128) ? 3 : 4) void gemm_f64_dma(GemmArgs g) {
     constexpr int BK = DMA_BK;
     constexpr int MI = BM / 32, NJ = BN / 32;                    // 16 x 16 MFMA tiles of a wave: MI x NJ
     constexpr int NA = BM / 32, NB = BN / 32;                    // LDS-DMA instructions per wave and K step (A, B)
-    constexpr int A_ST = BM * BK, B_ST = BN * BK, ST = A_ST + B_ST;   // doubles per stage
+    constexpr int A_ST = BM * BK, B_ST = BN * BK, T_ST = TAIL ? BK : 0, ST = A_ST + B_ST + T_ST;   // doubles per stage
     static_assert(NJ % 2 == 0 || !B_N, "the [k][n] image pairs neighbouring column tiles");
     static_assert(MI % 2 == 0 || !A_T, "the [k][m] image pairs neighbouring row tiles");
+    static_assert(!TAIL || (BM == 64 && BN == 64 && B_N && !A_T), "the tail row: 64 x 64 tiles, B stored [k][n]");
     int bm, bn, z;
     gemm_dma_tile_order<BM, BN>(g, bm, bn, z);
+    const bool tail = TAIL && bm == g.M / BM - 1;                // (workgroup-uniform)
     const int m0 = bm * BM, n0 = bn * BN;
     if (g.lower_only == 2 && n0 > m0 + BM - 1) return;
     const int zi = z % g.nb1, zp = z / g.nb1;
@@ -157,12 +166,18 @@ __global__ __launch_bounds__(256, (BM + BN > 128) ? 3 : 4) void gemm_f64_dma(Gem
             offb[i] = (uint32_t)(((int64_t)(n0 + row) * g.ldb + 2 * ch) * 8);
         }
     }
+    const double* arow = A + (int64_t)g.M * g.lda;              // (TAIL) row M of A
     auto issue = [&](int kt, int stage) {
         const int k0 = kb + kt * BK;
         const char* abase = reinterpret_cast<const char*>(A_T ? A + (int64_t)k0 * g.lda : A + k0);
         const char* bbase = reinterpret_cast<const char*>(B_N ? B + (int64_t)k0 * g.ldb : B + k0);
         double* as = gsm + stage * ST;
         double* bs = as + A_ST;
+        // (a wave's requests of a tile are waited for by a count that assumes NA + NB of them: the one more of wave 0 only makes
+        // its count wait for one request of the next tile too -- with 2 stages every wait is vmcnt(0) anyway)
+        if constexpr (TAIL)
+            if (tail && w == 0 && lane < 8)
+                __builtin_amdgcn_global_load_lds(GMRF_GLB_PTR(arow + k0 + 2 * lane), GMRF_LDS_PTR(bs + B_ST), 16, 0, 0);
 #pragma unroll
         for (int i = 0; i < NA; ++i) {
             asm volatile("" : "+v"(offa[i]));                    // keep base + zext(offset) visible to instruction selection
@@ -180,6 +195,8 @@ __global__ __launch_bounds__(256, (BM + BN > 128) ? 3 : 4) void gemm_f64_dma(Gem
     for (int i = 0; i < MI; ++i)
 #pragma unroll
         for (int j = 0; j < NJ; ++j) acc[i][j] = (v4d){0.0, 0.0, 0.0, 0.0};
+    v2d tacc = (v2d){0.0, 0.0};                                  // (TAIL) columns wn + 2 li, + 1: k pairs 2 lq of group w >> 1
+    const int tkg = w >> 1;
 
     // fragment addresses inside a stage (doubles): A rows wm + 16 i + li, chunk kg * 4 + lq swizzled by the row
     int fa[MI], fb[NJ];
@@ -232,6 +249,9 @@ __global__ __launch_bounds__(256, (BM + BN > 128) ? 3 : 4) void gemm_f64_dma(Gem
                 for (int j = 0; j < NJ; ++j)
                     b[kg][j] = *reinterpret_cast<const v2d*>(sm + fb[j] + (B_N ? kg * 8 * BN : ((kg * 8) ^ sb2[j])));
             }
+            v2d ta = (v2d){0.0, 0.0};
+            if constexpr (TAIL)
+                if (tail) ta = *reinterpret_cast<const v2d*>(sm + A_ST + B_ST + tkg * 8 + 2 * lq);     // a(k), a(k + 1), k = 8 tkg + 2 lq
             __builtin_amdgcn_sched_barrier(0);
             if (GMRF_DMA_READS_FIRST && kt + DEPTH < nkt) issue(kt + DEPTH, (kt + DEPTH) % STAGES);
             __builtin_amdgcn_sched_barrier(0);
@@ -253,6 +273,14 @@ __global__ __launch_bounds__(256, (BM + BN > 128) ? 3 : 4) void gemm_f64_dma(Gem
                             else bv = p ? b[kg][j].y : b[kg][j].x;
                             acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, acc[i][j], 0, 0, 0);
                         }
+            if constexpr (TAIL) {
+                if (tail) {
+                    // b[kg][p] = B(8 kg + 2 lq + p, wn + 2 li .. + 1)
+                    const v2d b0 = tkg ? b[1][0] : b[0][0], b1 = tkg ? b[1][1] : b[0][1];
+                    tacc.x = fma(ta.x, b0.x, tacc.x); tacc.x = fma(ta.y, b1.x, tacc.x);
+                    tacc.y = fma(ta.x, b0.y, tacc.y); tacc.y = fma(ta.y, b1.y, tacc.y);
+                }
+            }
             __builtin_amdgcn_sched_barrier(0);
         } else if (GMRF_DMA_READS_FIRST && kt + DEPTH < nkt) issue(kt + DEPTH, (kt + DEPTH) % STAGES);
     }
@@ -306,6 +334,22 @@ __global__ __launch_bounds__(256, (BM + BN > 128) ? 3 : 4) void gemm_f64_dma(Gem
                     if (beta != 0.0) v += beta * d[i][r][j];
                     C[orow(i, r) * g.ldc + n0 + wn + j * 16 + li] = v;
                 }
+    }
+    if constexpr (TAIL) {
+        if (tail) {
+            // the 8 partial sums of a column (k pair groups x lq) through LDS, added by wave 0 in a fixed order
+            __syncthreads();                                     // every wave is done with the stages
+            *reinterpret_cast<v2d*>(gsm + (tkg * 4 + lq) * BN + wn + 2 * li) = tacc;
+            __syncthreads();
+            if (w == 0) {
+                double s = 0.0;
+#pragma unroll
+                for (int q = 0; q < 8; ++q) s += gsm[q * BN + lane];
+                double v = alpha * s;
+                if (beta != 0.0) v += beta * Dm[(int64_t)g.M * ldd + n0 + lane];
+                C[(int64_t)g.M * g.ldc + n0 + lane] = v;
+            }
+        }
     }
 }
 
@@ -366,6 +410,32 @@ inline hipError_t gemm_dma_init() {
     GMRF_DMA_ATTR(64, 128, false, 2) GMRF_DMA_ATTR(64, 128, true, 2) GMRF_DMA_ATTR(64, 128, false, 3) GMRF_DMA_ATTR(64, 128, true, 3)
 #undef GMRF_DMA_ATTR
     return e;
+}
+
+// The product plus its tail row M (see TAIL above) on the 64 x 64 tile -- the kernel launch_gemm picks for the M rows when
+// gemm_dma_shape says 1 and gemm_uses_ll does not take the launch; nothing else qualifies.  Returns false (nothing launched) if
+// the product does not.
+inline bool gemm_tail_ok(bool a_t, bool b_n, const GemmArgs& g, int batch) {
+    if (a_t || !b_n || g.lower_only || gemm_uses_ll(g, batch) || gemm_dma_shape(false, g, batch) != 1) return false;
+    // 32-bit byte offsets inside a problem's operand for the M + 1 rows (A: row M read with 64-bit addressing)
+    return (int64_t)(g.M + 1) * g.ldc * 8 < ((int64_t)1 << 32) && (!g.D || (int64_t)(g.M + 1) * g.ldd * 8 < ((int64_t)1 << 32));
+}
+inline bool gemm_try_dma_tail(hipStream_t st, bool a_t, bool b_n, const GemmArgs& g, int batch, hipEvent_t ev_start, hipEvent_t ev_stop,
+                              hipError_t* err) {
+    if (!gemm_tail_ok(a_t, b_n, g, batch)) return false;
+    GemmArgs gs = g;
+    gs.lower_only = 0;
+    const dim3 grid((unsigned)((int64_t)(g.N / 64) * (g.M / 64) * batch)), block(256);
+    const size_t lds = (size_t)gemm_dma_stages() * (64 + 64 + DMA_BK) * DMA_BK * sizeof(double);
+    if (gemm_dma_stages() == 3) {
+        if (ev_start) hipExtLaunchKernelGGL((gemm_f64_dma<64, 64, true, 3, false, true>), grid, block, lds, st, ev_start, ev_stop, 0, gs);
+        else hipLaunchKernelGGL((gemm_f64_dma<64, 64, true, 3, false, true>), grid, block, lds, st, gs);
+    } else {
+        if (ev_start) hipExtLaunchKernelGGL((gemm_f64_dma<64, 64, true, 2, false, true>), grid, block, lds, st, ev_start, ev_stop, 0, gs);
+        else hipLaunchKernelGGL((gemm_f64_dma<64, 64, true, 2, false, true>), grid, block, lds, st, gs);
+    }
+    *err = hipGetLastError();
+    return true;
 }
 
 // Launches the product on a DMA kernel if it qualifies (returns true), else leaves it to launch_gemm's other kernels.

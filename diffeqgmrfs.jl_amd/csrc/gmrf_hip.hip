@@ -204,6 +204,9 @@ struct gmrf_handle {
     bool eager = false;
     bool split_step = false;           // use the three-launch panel step also for batch 1 (experiment)
     bool sweep_no_gemm = false;        // keep 64-multiples of right-hand sides on sweep_mm (comparison)
+    bool no_fused_posterior = false;   // a batch's gmrf_bt_posterior = gmrf_bt_solve + gmrf_bt_sample (eager bit 18; comparison)
+    bool tail_probe = false;           // gemm(tail): only check whether the product qualifies (posterior_fused_ok)
+    bool tail_refused = false;         // ... one did not
     unsigned long long* dbg_stamps = nullptr;   // test hook: phase stamps of the fused panel step
     bool fork_graph = false;           // second branch in the captured factor graph (experiment, see potrf_block)
     bool no_staircase = false;         // treat the coupling window as dense (comparison; takes effect at the next analysis)
@@ -371,7 +374,7 @@ static gmrf_status gemm(gmrf_handle* h, bool a_t, bool b_n, int M, int N, int K,
                         double beta, double* C, int64_t ldc, int64_t pA, int64_t pB, int64_t pC,
                         int batch = 1, int64_t sA = 0, int64_t sB = 0, int64_t sC = 0, const double* D = nullptr,
                         int64_t ldd = 0, int64_t pD = 0, int pclass = 0, double pwork = -1.0,
-                        const int* kb_m = nullptr, const int* kb_n = nullptr, const int* ke_n = nullptr) {
+                        const int* kb_m = nullptr, const int* kb_n = nullptr, const int* ke_n = nullptr, bool tail = false) {
     GemmArgs g;
     g.kb_m = kb_m; g.kb_n = kb_n; g.ke_n = ke_n;
     g.D = D; g.ldd = ldd; g.pD = pD;
@@ -384,6 +387,38 @@ static gmrf_status gemm(gmrf_handle* h, bool a_t, bool b_n, int M, int N, int K,
     double flops = 2.0 * M * N * (double)K * batch * (double)h->B;
     if (lower_only) flops *= 0.5 * (1.0 + 64.0 / std::max(M, 64));
     if (tri) flops *= 0.5 * (1.0 + 64.0 / std::max(K, 64));
+    if (tail) {
+        // one more row, row M of A / C (gemm_f64_dma's TAIL): the kernel the M rows alone would get, or not at all.  A dry run
+        // (tail_probe) only asks whether every product of a sweep qualifies.
+        if (!gemm_tail_ok(a_t, b_n, g, batch * (int)h->B)) {
+            h->tail_refused = true;
+            return h->tail_probe ? GMRF_OK : bad_shape("internal: a product of the fused sweep does not qualify for the tail-row GEMM");
+        }
+        if (h->tail_probe) return GMRF_OK;
+        flops *= (M + 1.0) / M;
+        if (pwork >= 0.0) pwork *= (M + 1.0) / M;
+        pclass = b_n ? 15 : 14;
+        hipError_t e = hipSuccess;
+        if (h->profiling > 0) {
+            EvPair p;
+            p.kind = pclass; p.work = pwork >= 0.0 ? pwork : flops;
+            p.a = ev_get(h); p.b = ev_get(h);
+            const int64_t key[8] = {pclass, M + 1, N, K, tri, lower_only, batch * h->B, (kb_m || kb_n || ke_n) ? 1 : 0};
+            for (size_t i = 0; i < h->gemm_shapes.size() && p.shape < 0; ++i)
+                if (!memcmp(h->gemm_shapes[i].key, key, sizeof(key))) p.shape = (int)i;
+            if (p.shape < 0) {
+                GemmShapeStat st; memcpy(st.key, key, sizeof(key));
+                h->gemm_shapes.push_back(st); p.shape = (int)h->gemm_shapes.size() - 1;
+            }
+            (void)gemm_try_dma_tail(h->gemm_stream ? h->gemm_stream : h->stream, a_t, b_n, g, batch * (int)h->B, p.a, p.b, &e);
+            HIPCHK(e);
+            h->events.push_back(p);
+            return GMRF_OK;
+        }
+        (void)gemm_try_dma_tail(h->gemm_stream ? h->gemm_stream : h->stream, a_t, b_n, g, batch * (int)h->B, nullptr, nullptr, &e);
+        HIPCHK(e);
+        return GMRF_OK;
+    }
     // statistics: launches of the 128 x 128 kernel are their own classes (6: B stored [n][k],
     // 7: B stored [k][n]) whoever calls, so that a class is one kernel symbol of a rocprof trace
     if (gemm_uses_big(a_t, g, batch * (int)h->B)) { pclass = b_n ? 7 : 6; pwork = -1.0; }
@@ -1789,8 +1824,10 @@ static gmrf_status sweep_guarded(gmrf_handle* h, std::initializer_list<SweepIo> 
     return body();
 }
 
-static gmrf_status sweep_launches(gmrf_handle* h, bool backward, int kp, double* Pin, double* Yout) {
-    if (sweep_persist_ok(h, kp)) return launch_sweep_persist(h, backward, kp, Pin, Yout);
+// tail (backward, via the GEMM only): the panels hold kp + 1 rows per problem and row kp -- the mean's right-hand side -- is swept
+// as the tail row of every product (gemm_f64_dma's TAIL): the mean's backward sweep and the samples' in one pass over the factor.
+static gmrf_status sweep_launches(gmrf_handle* h, bool backward, int kp, double* Pin, double* Yout, bool tail = false) {
+    if (!tail && sweep_persist_ok(h, kp)) return launch_sweep_persist(h, backward, kp, Pin, Yout);
     const int bsp = (int)h->bsp;
     const int64_t ld = bsp, bstride = (int64_t)bsp * bsp, npad = h->n_pad;
     const int64_t N = h->N;
@@ -1798,7 +1835,7 @@ static gmrf_status sweep_launches(gmrf_handle* h, bool backward, int kp, double*
     s.ld = ld;
     const int nprob = (int)h->B;
     s.narrow = (nprob < 8 && bsp >= 512 && bsp <= SWEEP_PERSIST_XMAX) ? 1 : 0;      // (what sweep_persist's k = 1 bodies sum: 8-column blocks)
-    const int64_t pPanel = (int64_t)kp * npad;
+    const int64_t pPanel = (int64_t)(kp + (tail ? 1 : 0)) * npad;
     const int64_t pX = stride_pX(h), pCm = stride_pC(h);
     const int64_t ldc = c_ld(h), cstride = c_blk(h);
     // C_i is stored as its non-zero window (rows 0 .. rm, columns cm ..); inside it row tile t is zero
@@ -1813,6 +1850,7 @@ static gmrf_status sweep_launches(gmrf_handle* h, bool backward, int kp, double*
     // 64-multiples of right-hand sides go through the GEMM kernel (panel = the [m][k] operand) when
     // the batch gives it enough 64 x 64 tiles; a lone problem stays on sweep_mm (256 workgroups)
     const bool via_gemm = (kp % 64 == 0) && !h->sweep_no_gemm && (int64_t)nprob * (bsp / 64) * (kp / 64) >= 128;
+    if (tail && (!via_gemm || !backward)) return bad_shape("internal: the tail row needs the backward sweep on the GEMM");
     for (int64_t step = 0; step < N; ++step) {
         const int64_t i = backward ? (N - 1 - step) : step;
         double* rhs = Pin + i * bsp;               // the input panel is consumed: P_i becomes P_i - C y_prev
@@ -1828,7 +1866,7 @@ static gmrf_status sweep_launches(gmrf_handle* h, bool backward, int kp, double*
                 // T[r][m] = P[r][m] - sum_k y[r][k] c(k,m): the panel is the [m][k] operand, the block the other
                 GCHK(gemm(h, false, backward, kp, rows, kdim, 0, 0, -1.0, xin, npad, Cs, ldc, 1.0, out, npad, pPanel, pCm,
                           pPanel, 1, 0, 0, 0, nullptr, 0, 0, 0, 2.0 * h->c_streamed * kp * nprob,
-                          nullptr, backward ? nullptr : h->d_kst, backward ? h->d_mend : nullptr));
+                          nullptr, backward ? nullptr : h->d_kst, backward ? h->d_mend : nullptr, tail));
             } else {
                 s.Mat = Cs; s.ld = ldc; s.Xin = xin; s.ldx = npad; s.Bin = out; s.ldb = npad; s.Out = out; s.ldo = npad;
                 s.rows = rows; s.kdim = kdim; s.sub = 1;
@@ -1850,16 +1888,19 @@ static gmrf_status sweep_launches(gmrf_handle* h, bool backward, int kp, double*
             for (int part = 0; part < 3; ++part) {
                 const int which = backward ? 2 - part : part;          // 0: aa, 1: ba, 2: bb
                 if (via_gemm) {
+                    // (the defaults up to the tail flag)
+                    constexpr int64_t z0 = 0;
                     if (which == 0)
                         GCHK(gemm(h, false, backward, kp, p, p, backward ? TRI_B_LOWER : TRI_B_UPPER, 0, 1.0, rhs, npad, X, ld, 0.0, yout, npad,
-                                  pPanel, pX, pPanel));
+                                  pPanel, pX, pPanel, 1, z0, z0, z0, nullptr, z0, z0, 0, -1.0, nullptr, nullptr, nullptr, tail));
                     else if (which == 2)
                         GCHK(gemm(h, false, backward, kp, q, q, backward ? TRI_B_LOWER : TRI_B_UPPER, 0, 1.0, rhs + p, npad, Xbb, ld, 0.0,
-                                  yout + p, npad, pPanel, pX, pPanel));
+                                  yout + p, npad, pPanel, pX, pPanel, 1, z0, z0, z0, nullptr, z0, z0, 0, -1.0, nullptr, nullptr, nullptr, tail));
                     else if (!backward)
                         GCHK(gemm(h, false, false, kp, q, p, 0, 0, -1.0, yout, npad, Lba, ld, 1.0, rhs + p, npad, pPanel, pX, pPanel));
                     else
-                        GCHK(gemm(h, false, true, kp, p, q, 0, 0, -1.0, yout + p, npad, Lba, ld, 1.0, rhs, npad, pPanel, pX, pPanel));
+                        GCHK(gemm(h, false, true, kp, p, q, 0, 0, -1.0, yout + p, npad, Lba, ld, 1.0, rhs, npad, pPanel, pX, pPanel,
+                                  1, z0, z0, z0, nullptr, z0, z0, 0, -1.0, nullptr, nullptr, nullptr, tail));
                 } else {
                     s.ld = ld; s.ldx = npad; s.ldo = npad; s.pMat = pX; s.pXin = pPanel; s.pOut = pPanel; s.kst = nullptr; s.mend = nullptr;
                     if (which == 0) { s.Mat = X; s.Xin = rhs; s.Bin = nullptr; s.ldb = 0; s.Out = yout; s.rows = p; s.kdim = p; s.sub = 0; s.pBin = 0; }
@@ -1874,7 +1915,7 @@ static gmrf_status sweep_launches(gmrf_handle* h, bool backward, int kp, double*
         } else if (via_gemm) {
             // forward: Linv stored [m][k], zero for k > m; backward: Linv^T, stored [k][m], zero for k < m
             GCHK(gemm(h, false, backward, kp, bsp, bsp, backward ? TRI_B_LOWER : TRI_B_UPPER, 0, 1.0, rhs, npad, X, ld, 0.0,
-                      yout, npad, pPanel, pX, pPanel, 1, 0, 0, 0, nullptr, 0, 0, 0, -1.0));
+                      yout, npad, pPanel, pX, pPanel, 1, 0, 0, 0, nullptr, 0, 0, 0, -1.0, nullptr, nullptr, nullptr, tail));
         } else {
             s.Mat = X; s.ld = ld; s.Xin = rhs; s.ldx = npad; s.Bin = nullptr; s.ldb = 0; s.Out = yout; s.ldo = npad;
             s.rows = bsp; s.kdim = bsp; s.sub = 0;
@@ -1887,17 +1928,19 @@ static gmrf_status sweep_launches(gmrf_handle* h, bool backward, int kp, double*
     return GMRF_OK;
 }
 
-// mode: 1 forward P->Y, 2 backward P->Y, 0 full P->Y->P (result in P); 3 backward Y->P (the second half of a twisted solve)
-constexpr int SWEEP_BACKWARD_YP = 3;
+// mode: 1 forward P->Y, 2 backward P->Y, 0 full P->Y->P (result in P); 3 backward Y->P (the second half of a twisted solve);
+// 4 backward P->Y of kp + 1 rows per problem, row kp the tail row (posterior_fused)
+constexpr int SWEEP_BACKWARD_YP = 3, SWEEP_BACKWARD_TAIL = 4;
 static gmrf_status run_sweeps(gmrf_handle* h, int mode, int kp) {
     auto body = [&]() -> gmrf_status {
         if (mode == GMRF_SOLVE_FORWARD) return sweep_launches(h, false, kp, h->d_P, h->d_Y);
+        if (mode == SWEEP_BACKWARD_TAIL) return sweep_launches(h, true, kp, h->d_P, h->d_Y, true);
         if (mode == SWEEP_BACKWARD_YP) return sweep_launches(h, true, kp, h->d_Y, h->d_P);
         if (mode == GMRF_SOLVE_BACKWARD) return sweep_launches(h, true, kp, h->d_P, h->d_Y);
         GCHK(sweep_launches(h, false, kp, h->d_P, h->d_Y));
         return sweep_launches(h, true, kp, h->d_Y, h->d_P);
     };
-    const bool persistent = sweep_persist_ok(h, kp);
+    const bool persistent = mode != SWEEP_BACKWARD_TAIL && sweep_persist_ok(h, kp);
     if (persistent) {
         GCHK(sweep_persist_prepare(h, kp));
         h->sweep_persist_launched = true;                  // (here, not at the launch: a graph replay launches it too)
@@ -2094,6 +2137,7 @@ gmrf_status gmrf_bt_set_eager(gmrf_handle* h, int32_t eager) {
     if (((eager & 32768) != 0) != h->no_persist_panels) { destroy_graphs(h); h->no_persist_panels = (eager & 32768) != 0; }
     if (((eager & 65536) != 0) != h->no_sweep_persist) { destroy_graphs(h); h->no_sweep_persist = (eager & 65536) != 0; }
     if (((eager & 131072) != 0) != h->no_scatter_fold) { destroy_graphs(h); h->no_scatter_fold = (eager & 131072) != 0; }
+    h->no_fused_posterior = (eager & 262144) != 0;
     h->eager = (eager & 1) != 0;
     h->eager_bits = eager;
     if (h->tw)
@@ -2929,7 +2973,7 @@ static gmrf_status sample_chunk(gmrf_handle* h, uint64_t seed, int64_t first_id,
     } else {
         const int64_t total = (int64_t)kp * h->n_pad;
         hipLaunchKernelGGL(fill_normals_panel, dim3((unsigned)((total + 255) / 256), (unsigned)h->B), dim3(256), 0,
-                           h->stream, h->d_P, h->n_pad, (int)h->bs, (int)h->bsp, kc, kp, seed, first_id, id_stride);
+                           h->stream, h->d_P, h->n_pad, (int)h->bs, (int)h->bsp, kc, kp, seed, first_id, id_stride, nullptr, (int64_t)0);
         HIPCHK(hipGetLastError());
     }
     return run_sweeps(h, GMRF_SOLVE_BACKWARD, kp);
@@ -3026,7 +3070,7 @@ static gmrf_status posterior_beside(gmrf_handle* h, const double* b, uint64_t se
     {
         const int64_t total = (int64_t)kp * h->n_pad;
         hipLaunchKernelGGL(fill_normals_panel, dim3((unsigned)((total + 255) / 256), 1), dim3(256), 0, h->aux, h->d_P2, h->n_pad,
-                           (int)h->bs, (int)h->bsp, (int)k, kp, seed, first_id, k);
+                           (int)h->bs, (int)h->bsp, (int)k, kp, seed, first_id, k, nullptr, (int64_t)0);
         HIPCHK(hipGetLastError());
         GCHK(launch_sweep_persist(h, true, kp, h->d_P2, h->d_Y2, h->aux, h->d_T2));
         HIPCHK(hipEventRecord(ev_join, h->aux));
@@ -3043,12 +3087,61 @@ static gmrf_status posterior_beside(gmrf_handle* h, const double* b, uint64_t se
     return GMRF_OK;
 }
 
+// A batch's posterior with the mean's backward sweep carried in the samples' (round 6): may it run fused?  Batches only (B > 1),
+// k <= 128 with kp = pad_k(k) a multiple of 64 on the GEMM route of the sweeps, device pointers, not switched off (eager bit 18),
+// and every product of the backward sweep on the 64 x 64 LDS-DMA tile that takes the tail row (a dry run of the sweep asks).
+// Needs the panels of kp + 1 rows (ensure_panels).
+static bool posterior_fused_ok(gmrf_handle* h, int64_t k, bool dev_all) {
+    if (tw_on(h) || h->B <= 1 || !dev_all || h->no_fused_posterior || h->sweep_no_gemm || k <= 0 || k > KP_CHUNK) return false;
+    const int kp = pad_k(k);
+    if (kp % 64 != 0 || (int64_t)h->B * (h->bsp / 64) * (kp / 64) < 128) return false;
+    if ((int64_t)(kp + 1) * h->n_pad * 8 >= ((int64_t)1 << 32)) return false;
+    if (ensure_panels(h, kp + 1) != GMRF_OK) return false;
+    h->tail_probe = true; h->tail_refused = false;
+    const gmrf_status st = sweep_launches(h, true, kp, h->d_P, h->d_Y, true);
+    h->tail_probe = false;
+    return st == GMRF_OK && !h->tail_refused;
+}
+
+// The fused posterior of a batch (posterior_fused_ok): b -> P, forward k = 1 sweep P -> Y (the mean's, as gmrf_bt_solve runs it);
+// P <- normals in rows 0 .. kp - 1 and y in row kp; ONE backward sweep P -> Y over kp + 1 rows, the mean's being every product's
+// tail row (gemm_f64_dma TAIL): the factor is streamed once for both instead of once each.  Rows 0 .. k - 1 are bitwise the
+// samples' sweep of gmrf_bt_sample (same kernel, same sums); the mean is summed by the tail row instead of the k = 1 kernels (rounding
+// level).  Out: mean = row kp, samples = rows + mean.  Ends in the synchronisation of the handle's stream.
+static gmrf_status posterior_fused(gmrf_handle* h, const double* b, uint64_t seed, int64_t first_id, int64_t k, double* mean,
+                                   double* samples, int64_t ld) {
+    const int kp = pad_k(k);
+    GCHK(ensure_panels(h, kp + 1));
+    HIPCHK(hipEventRecord(h->ev0, h->stream));
+    GCHK(launch_pack(h, b, h->n, 1, 1));
+    GCHK(run_sweeps(h, GMRF_SOLVE_FORWARD, 1));
+    {
+        const int64_t total = (int64_t)(kp + 1) * h->n_pad;
+        hipLaunchKernelGGL(fill_normals_panel, dim3((unsigned)((total + 255) / 256), (unsigned)h->B), dim3(256), 0,
+                           h->stream, h->d_P, h->n_pad, (int)h->bs, (int)h->bsp, (int)k, kp, seed, first_id, k, h->d_Y, h->n_pad);
+        HIPCHK(hipGetLastError());
+    }
+    GCHK(run_sweeps(h, SWEEP_BACKWARD_TAIL, kp));
+    {
+        const int64_t total = h->n * (k + 1);
+        hipLaunchKernelGGL(unpack_panel_mean, dim3((unsigned)((total + 255) / 256), (unsigned)h->B), dim3(256), 0, h->stream, h->d_Y,
+                           h->n_pad, samples, ld, mean, (int)h->bs, (int)h->bsp, h->n, (int)k, kp);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipEventRecord(h->ev1, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (h->profiling) prof_collect(h);
+    return GMRF_OK;
+}
+
 // mean = A^-1 b and k samples mean + L^-T z in ONE call (scripts/darcy/solve_darcy_gmrf-fem.jl:190-191 calls `mean` and `rand` on one
 // factor, one after the other).  The samples' backward sweep needs nothing of the mean -- only their last step, adding it, does --
 // so where the sweeps are persistent launches (one problem, blocks of 512 .. 1024) it runs BESIDE the mean's two sweeps, on a second
 // stream with panels of its own: both are bound by their chains of hand-offs, not by the chip, and two resident workgroups per
 // CU (97 + 189 VGPRs, 13 + 33 KB of LDS) take turns in the same time one takes alone.  The same kernels and the same sums as
-// gmrf_bt_solve + gmrf_bt_sample: bitwise their results.  Anywhere else the call IS those two calls.
+// gmrf_bt_solve + gmrf_bt_sample: bitwise their results.  A batch (B > 1) whose samples' sweep runs on the GEMM and whose inputs
+// and outputs do not overlap runs posterior_fused: the mean's backward sweep as the tail row of the samples'.  Anywhere else the call
+// IS those two calls.
 gmrf_status gmrf_bt_posterior(gmrf_handle* h, const double* b, uint64_t seed, int64_t first_id, int64_t k, double* mean,
                               double* samples, int64_t ld) {
     h = tw_route(h);
@@ -3059,18 +3152,21 @@ gmrf_status gmrf_bt_posterior(gmrf_handle* h, const double* b, uint64_t seed, in
     const bool dev_all = is_device_ptr(b) && is_device_ptr(mean) && is_device_ptr(samples);
     // beside only when no two of b, mean, samples overlap (else the two calls, each with its own guard)
     const int64_t vec_bytes = h->n * h->B * (int64_t)sizeof(double), smp_bytes = cols_bytes(h->n, k * h->B, ld);
-    bool beside = false;
+    bool beside = false, fused = false;
     GCHK(sweep_guarded(h, {{b, vec_bytes, mean, vec_bytes}, {b, vec_bytes, samples, smp_bytes}, {mean, vec_bytes, samples, smp_bytes}},
                        [&]() -> gmrf_status {
         // (decided behind the hold, which sweep_persist_ok reads; the repeat after an abort finds the handle off the persistent form)
         beside = !tw_on(h) && h->B == 1 && k <= KP_CHUNK && k >= 2 && dev_all && !h->profiling && sweep_persist_ok(h, 1) &&
                  sweep_persist_ok(h, pad_k(k));      // (a twisted handle: its mean, then its samples)
-        return beside ? posterior_beside(h, b, seed, first_id, k, mean, samples, ld) : GMRF_OK;
+        if (beside) return posterior_beside(h, b, seed, first_id, k, mean, samples, ld);
+        // (the hold also marks inputs that overlap outputs: the fused pass would write the mean before the samples read b's sweep)
+        fused = !h->sweep_persist_hold && posterior_fused_ok(h, k, dev_all);
+        return fused ? posterior_fused(h, b, seed, first_id, k, mean, samples, ld) : GMRF_OK;
     }, [&]() -> gmrf_status {
-        HIPCHK(hipStreamSynchronize(h->aux));
+        if (h->aux) HIPCHK(hipStreamSynchronize(h->aux));
         return GMRF_OK;
     }));
-    if (!beside) {
+    if (!beside && !fused) {
         GCHK(gmrf_bt_solve(h, b, mean, 1, h->n, h->n, GMRF_SOLVE_FULL));
         return gmrf_bt_sample(h, seed, first_id, k, mean, nullptr, samples, ld);
     }
@@ -3094,7 +3190,7 @@ gmrf_status gmrf_bt_normals(gmrf_handle* h, uint64_t seed, int64_t first_id, int
         GCHK(ensure_panels(h, kp));
         const int64_t total = (int64_t)kp * h->n_pad;
         hipLaunchKernelGGL(fill_normals_panel, dim3((unsigned)((total + 255) / 256), (unsigned)h->B), dim3(256), 0,
-                           h->stream, h->d_P, h->n_pad, (int)h->bs, (int)h->bsp, kc, kp, seed, first_id + c0, k);
+                           h->stream, h->d_P, h->n_pad, (int)h->bs, (int)h->bsp, kc, kp, seed, first_id + c0, k, nullptr, (int64_t)0);
         HIPCHK(hipGetLastError());
         GCHK(cols_out(h, h->d_P, kc, nullptr, z + c0 * ld, ld, z_dev));
         HIPCHK(hipStreamSynchronize(h->stream));
@@ -4936,15 +5032,18 @@ gmrf_status gmrf_test_gemm(int32_t device, int64_t M, int64_t N, int64_t K, int3
                            int32_t tri_flags, int32_t lower_only, double alpha, const double* A, int64_t lda,
                            const double* B, int64_t ldb, double beta, double* C, int64_t ldc) {
     if (M % 64 || N % 64 || K % 16 || (lda & 1) || (ldb & 1)) return bad_shape("gemm test sizes");
+    // bit 65536: the 64 x 64 LDS-DMA kernel with the tail row (gemm_f64_dma TAIL): A and C hold M + 1 rows, row M summed on the VALU
+    const bool tail = (tri_flags & 65536) != 0;
+    if (tail && (transA || transB)) return bad_shape("gemm test: the tail row needs A [m][k] and B [k][n]");
     HIPCHK(hipSetDevice(device));
-    const int64_t a_rows = transA ? K : M, b_rows = transB ? N : K;
+    const int64_t a_rows = transA ? K : M + (tail ? 1 : 0), b_rows = transB ? N : K, c_rows = M + (tail ? 1 : 0);
     double *dA, *dB, *dC;
     HIPCHK(hipMalloc(&dA, sizeof(double) * a_rows * lda));
     HIPCHK(hipMalloc(&dB, sizeof(double) * b_rows * ldb));
-    HIPCHK(hipMalloc(&dC, sizeof(double) * M * ldc));
+    HIPCHK(hipMalloc(&dC, sizeof(double) * c_rows * ldc));
     HIPCHK(hipMemcpy(dA, A, sizeof(double) * a_rows * lda, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(dB, B, sizeof(double) * b_rows * ldb, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dC, C, sizeof(double) * M * ldc, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dC, C, sizeof(double) * c_rows * ldc, hipMemcpyHostToDevice));
     GemmArgs g;
     g.A = dA; g.B = dB; g.C = dC; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
     g.strideA = g.strideB = g.strideC = 0;
@@ -4956,14 +5055,27 @@ gmrf_status gmrf_test_gemm(int32_t device, int64_t M, int64_t N, int64_t K, int3
     // them: the register-staged kernels only
     const bool force_big = (tri_flags & 2048) != 0, use_ll = (tri_flags & 4096) != 0;
     const int dma_shape = (tri_flags & 8192) ? 1 : ((tri_flags & 16384) ? 2 : ((tri_flags & 32768) ? 3 : 0));
-    g.M = (int)M; g.N = (int)N; g.K = (int)K; g.tri = tri_flags & ~(2048 | 4096 | 8192 | 16384 | 32768); g.lower_only = lower_only;
+    g.M = (int)M; g.N = (int)N; g.K = (int)K; g.tri = tri_flags & ~(2048 | 4096 | 8192 | 16384 | 32768 | 65536); g.lower_only = lower_only;
     g.alpha = alpha; g.beta = beta;
     unsigned long long* dst = nullptr;
     HIPCHK(hipMalloc(&dst, 16));
     HIPCHK(hipMemset(dst, 0, 16));
-    g.stamps = (force_big || use_ll || dma_shape) ? nullptr : dst;
+    g.stamps = (force_big || use_ll || dma_shape || tail) ? nullptr : dst;
     HIPCHK(gemm_init());
     HIPCHK(gemm_dma_init());
+    if (tail) {
+        const int saved_dma = gemm_dma_policy(), saved_ll = gemm_ll_policy();
+        gemm_dma_policy() = 1; gemm_ll_policy() = 2;
+        hipError_t le = hipSuccess;
+        const bool ok = gemm_try_dma_tail(nullptr, false, true, g, 1, nullptr, nullptr, &le);
+        gemm_dma_policy() = saved_dma; gemm_ll_policy() = saved_ll;
+        if (!ok) { hipFree(dst); hipFree(dA); hipFree(dB); hipFree(dC); return bad_shape("gemm test: not a tail-row product"); }
+        HIPCHK(le);
+        HIPCHK(hipDeviceSynchronize());
+        HIPCHK(hipMemcpy(C, dC, sizeof(double) * c_rows * ldc, hipMemcpyDeviceToHost));
+        hipFree(dst); hipFree(dA); hipFree(dB); hipFree(dC);
+        return GMRF_OK;
+    }
     const int saved = gemm_big_policy(), saved_ll = gemm_ll_policy(), saved_dma = gemm_dma_policy(), saved_force = gemm_dma_force();
     gemm_big_policy() = force_big ? 1 : 2;
     gemm_ll_policy() = use_ll ? 0 : 2;
@@ -5061,9 +5173,9 @@ gmrf_status gmrf_test_gemm_rate(int32_t device, int64_t M, int64_t N, int64_t K,
     HIPCHK(hipMalloc(&dC, sizeof(double) * pm * batch));
     const int64_t tot = pm * batch;
     hipLaunchKernelGGL(fill_normals_panel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, nullptr, dA, tot, 1 << 30,
-                       1 << 30, 1, 1, 1ull, 0, 0);
+                       1 << 30, 1, 1, 1ull, 0, 0, nullptr, (int64_t)0);
     hipLaunchKernelGGL(fill_normals_panel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, nullptr, dB, tot, 1 << 30,
-                       1 << 30, 1, 1, 2ull, 0, 0);
+                       1 << 30, 1, 1, 2ull, 0, 0, nullptr, (int64_t)0);
     HIPCHK(hipMemset(dC, 0, sizeof(double) * pm * batch));
     GemmArgs g;
     g.A = dA; g.B = dB; g.C = dC; g.lda = g.ldb = g.ldc = ld;

@@ -138,16 +138,36 @@ __device__ __host__ inline double philox_normal(uint64_t seed, uint64_t dof, uin
 
 // Fill the padded panel rows [0,k) with normals of samples first_id.. (padding stays zero).
 // problem p (blockIdx.y) draws the sample ids first_id + p * id_stride + r
+// yrow != nullptr: the panel holds kp + 1 rows per problem and row kp is a copy of yrow[p * ystride ..] (n_pad values: the
+// forward sweep's result, the mean's right-hand side in the fused backward sweep of a batch's posterior)
 __global__ void fill_normals_panel(double* __restrict__ P, int64_t n_pad, int bs, int bsp,
-                                   int k, int kp, uint64_t seed, int64_t first_id, int64_t id_stride) {
+                                   int k, int kp, uint64_t seed, int64_t first_id, int64_t id_stride,
+                                   const double* __restrict__ yrow, int64_t ystride) {
     const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (int64_t)kp * n_pad) return;
+    const int rows = kp + (yrow ? 1 : 0);
+    if (idx >= (int64_t)rows * n_pad) return;
     const int64_t r = idx / n_pad, j = idx % n_pad;
     const int64_t blk = j / bsp, off = j % bsp;
     double v = 0.0;
-    if (r < k && off < bs)
+    if (r == kp) v = yrow[(int64_t)blockIdx.y * ystride + j];
+    else if (r < k && off < bs)
         v = philox_normal(seed, (uint64_t)(blk * bs + off), (uint64_t)(first_id + (int64_t)blockIdx.y * id_stride + r));
-    P[(int64_t)blockIdx.y * kp * n_pad + idx] = v;
+    P[(int64_t)blockIdx.y * rows * n_pad + idx] = v;
+}
+
+// A panel of kp + 1 rows per problem (fill_normals_panel with yrow) after the fused backward sweep: row kp is the mean, rows
+// [0, k) are L^-T z.  mean_out[p][j] = row kp; samples out (column-major, problem p's k columns after problem p - 1's) = row r +
+// row kp.  One thread per (row r <= k, dof j) of problem blockIdx.y; row k stands for row kp.
+__global__ void unpack_panel_mean(const double* __restrict__ P, int64_t n_pad, double* __restrict__ dst, int64_t ld,
+                                  double* __restrict__ mean_out, int bs, int bsp, int64_t n, int k, int kp) {
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= n * (int64_t)(k + 1)) return;
+    const int64_t r = idx / n, j = idx % n;
+    const int64_t blk = j / bs, off = j % bs;
+    const double* Pp = P + (int64_t)blockIdx.y * (kp + 1) * n_pad + blk * bsp + off;
+    const double mu = Pp[(int64_t)kp * n_pad];
+    if (r == k) mean_out[(int64_t)blockIdx.y * n + j] = mu;
+    else dst[((int64_t)blockIdx.y * k + r) * ld + j] = Pp[r * n_pad] + mu;
 }
 
 // ------------------------------------------------------------------------------- K7

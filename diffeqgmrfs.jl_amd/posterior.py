@@ -176,6 +176,14 @@ class HipEngine:
             outs = outs + [x] if keep else [x]
         return self.torch.cat(outs, dim=1) if keep else outs[0]
 
+    def posterior(self, k: int, seed: int, first_id: int, keep: bool = True):
+        """(means, samples) of `mean()` then `sample(k, means, ...)`, the same ids; a batch with k <= 128 in ONE call
+        (gmrf_bt_posterior: the mean's backward sweep rides in the samples' where they run on the GEMM)."""
+        if self.batch == 1 or k > 128:
+            mu = self.mean()
+            return mu, self.sample(k, mu, seed, first_id, keep)
+        return self.F.posterior_batch(self.rhs, k, seed=seed, first_id=first_id)
+
     def synchronize(self):
         self.torch.cuda.synchronize(self.dev)
 
@@ -327,10 +335,14 @@ class ShardedPosterior:
     def step(self, step_index: int = 0):
         """factor (+ broadcast) -> mean -> this rank's k samples.  Returns (mean, samples)."""
         self._factor_and_share()
-        mu = self.e.mean()
         nb = getattr(self.e, "batch", 1)
         first = (step_index * self.world + self.rank) * self.k * nb
-        X = self.e.sample(self.k, mu, self.seed, first) if self.keep_samples else self.e.sample(self.k, mu, self.seed, first, keep=False)
+        if self.replicate and type(self.e) is HipEngine:
+            # independent problems: mean and samples in one call (a batch: one backward pass over the factor for both)
+            mu, X = self.e.posterior(self.k, self.seed, first, keep=self.keep_samples)
+        else:
+            mu = self.e.mean()
+            X = self.e.sample(self.k, mu, self.seed, first) if self.keep_samples else self.e.sample(self.k, mu, self.seed, first, keep=False)
         self._mark(3)
         return mu, X
 

@@ -167,6 +167,11 @@ gmrf_status gmrf_bt_sample(gmrf_handle* h, uint64_t seed, int64_t first_id, int6
  * gmrf_bt_solve(mode 0) followed by gmrf_bt_sample(mean = that mean, z = NULL); where the sweeps of a handle are persistent
  * launches (one problem, blocks of 512 .. 1024, device pointers, 2 <= k <= 128) the samples' sweep runs BESIDE the mean's two on a
  * second stream.  b, mean: n doubles; samples: n x k column-major, leading dimension ld.  stats.solve_ms = the whole call.
+ * A batch (B > 1; b, mean: B x n, problem-major; samples: B groups of k columns, ids first_id + p k + s as gmrf_bt_sample draws
+ * them) whose samples' sweep runs on the GEMM (k <= 128 padded to a multiple of 64, B * bsp / 64 * kp / 64 >= 128, device
+ * pointers) makes ONE backward pass over the factor for both: the mean's backward sweep is the tail row of every product of the
+ * samples' (kp + 1 panel rows); its samples' L^-T z are the same bits as gmrf_bt_sample's, its mean agrees with gmrf_bt_solve's to
+ * rounding (summed by another kernel), stats.solve_ms = the whole call, stats.sample_ms = 0.  set_eager bit 18 keeps the two calls.
  * If two of b, mean, samples overlap the call IS the two calls (each with its own guard against overlap). */
 gmrf_status gmrf_bt_posterior(gmrf_handle* h, const double* b, uint64_t seed, int64_t first_id, int64_t k,
                               double* mean, double* samples, int64_t ld);
@@ -385,7 +390,9 @@ gmrf_status gmrf_bt_set_profiling(gmrf_handle* h, int32_t level);
  * instead of one persistent launch per panel diagonal block; bit 16: one problem's sweeps keep one launch per product
  * instead of ONE persistent launch per sweep (sweep_persist; comparison -- bit 13 switches both persistent forms off); bit 17: one problem
  * keeps scatter_block (S += D_i) as a launch of its own behind S = -C C^T instead of zero + scatter inside the spmm_bxt_tiles launch and an
- * accumulating product (comparison; same bits).
+ * accumulating product (comparison; same bits); bit 18: a batch's gmrf_bt_posterior is gmrf_bt_solve + gmrf_bt_sample (the mean's
+ * backward sweep a pass of its own) instead of the fused pass that sweeps the mean as the tail row of the samples' GEMMs
+ * (comparison; the samples' L^-T z rows are the same bits, the mean agrees to rounding).
  * (Bits 6, 9, 10, 11, 14 selected comparison routes that lost twice -- left-looking panels, in-panel updates on the GEMM kernel,
  * rank-64 panel steps of batches, 128-column panels, potrf_panel256 -- and were removed with them in round 5; they are ignored.) */
 gmrf_status gmrf_bt_set_eager(gmrf_handle* h, int32_t eager);
@@ -520,6 +527,9 @@ gmrf_status gmrf_shallow_water_p1_operators(gmrf_swe_p1* w, const double* K_vals
 /* ------------------------------------------------------------------ test hooks
  * Direct access to the dense device kernels for the parity tests (row-major operands on
  * the HOST; not part of the drop-in surface). */
+/* gmrf_test_gemm tri_flags: 2048 the 128 x 128 kernel, 4096 the 32 x 32 one, 8192 / 16384 / 32768 the LDS-DMA kernel with
+ * 64 x 64 / 128 x 64 / 64 x 128 tiles; 65536 the 64 x 64 LDS-DMA kernel with the tail row (A and C hold M + 1 rows, row M is
+ * summed on the VALU from the staged B tile; transA = transB = 0). */
 gmrf_status gmrf_test_gemm(int32_t device, int64_t M, int64_t N, int64_t K, int32_t transA,
                            int32_t transB, int32_t tri_flags, int32_t lower_only,
                            double alpha, const double* A, int64_t lda, const double* B,

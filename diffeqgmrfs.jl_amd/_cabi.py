@@ -30,7 +30,7 @@ EXPORTS = [
     "gmrf_bt_set_keep_l", "gmrf_bt_storage_bytes", "gmrf_bt_set_storage", "gmrf_bt_factor_begin_csc",
     "gmrf_bt_factor_step_async", "gmrf_bt_factor_end", "gmrf_bt_stats",
     "gmrf_bt_set_profiling", "gmrf_bt_set_eager", "gmrf_bt_synchronize", "gmrf_bt_set_batch", "gmrf_bt_select_problem",
-    "gmrf_bt_marginal_var_batch", "gmrf_bt_set_order", "gmrf_bt_get_order", "gmrf_bt_half_stats", "gmrf_bt_export_size", "gmrf_bt_export_factor", "gmrf_bt_import_factor",
+    "gmrf_bt_marginal_var_batch", "gmrf_bt_selinv", "gmrf_bt_trace_inv", "gmrf_bt_set_order", "gmrf_bt_get_order", "gmrf_bt_half_stats", "gmrf_bt_export_size", "gmrf_bt_export_factor", "gmrf_bt_import_factor",
     "gmrf_comm_unique_id", "gmrf_comm_create", "gmrf_comm_destroy", "gmrf_comm_bcast_host", "gmrf_comm_allreduce_sum",
     "gmrf_bt_bcast_blocks_async", "gmrf_bt_allgather_blocks_async", "gmrf_comm_wait", "gmrf_comm_bytes", "gmrf_streams_create", "gmrf_streams_destroy",
     "gmrf_bt_packed_size", "gmrf_bt_pack_blocks_async", "gmrf_bt_unpack_blocks_async",
@@ -148,6 +148,8 @@ def load() -> C.CDLL:
         "gmrf_bt_select_problem": [vp, i64],
         "gmrf_csr_create": [i32, vp, i64, i64, vp, vp, vp, i32, i32, P(vp)],
         "gmrf_bt_marginal_var_batch": [vp, i32, i64, u64, vp, vp, vp],
+        "gmrf_bt_selinv": [vp, vp, vp],
+        "gmrf_bt_trace_inv": [vp, vp, vp, i64, vp],
         "gmrf_bt_export_size": [vp, P(i64)],
         "gmrf_bt_export_factor": [vp, vp, i64],
         "gmrf_bt_import_factor": [vp, vp, i64],

@@ -78,6 +78,7 @@ class CsrMatrix:
         rp = A.indptr.astype(np.int64)
         ci = A.indices.astype(np.int64)
         v = A.data.astype(np.float64)
+        self.indptr, self.indices = rp, A.indices.astype(np.int32)       # the pattern (selected_inverse returns it)
         lib = _cabi.load()
         _cabi.check(lib.gmrf_csr_create(device, C.c_void_p(stream), A.shape[0], A.shape[1], _cabi.ptr(rp),
                                         _cabi.ptr(ci), _cabi.ptr(v), 0, int(values_f32), C.byref(self._h)))
@@ -468,6 +469,13 @@ class ConditionedGMRF:
     def logdet(self) -> float:
         return self.F.logdet()
 
+    def selected_inverse(self):
+        """Q_post^-1 on the pattern of Q_post (scipy.sparse.csr_matrix): the covariances of every pair of coupled dofs, with
+        the marginal variances on its diagonal."""
+        if self._csr is None:
+            self._csr = CsrMatrix(self.precision_matrix())
+        return self.F.selected_inverse(self._csr)
+
     def sqmahal(self, z) -> float:
         """`sqmahal(x_cond, z)` = (z - mean)' Q_post (z - mean) (scripts/burgers/solve_burgers_gmrf-collocation.jl:262):
         one CSR SpMV of the posterior precision (K6) and a dot product."""
@@ -784,6 +792,51 @@ class TridiagonalCholeskyFactor:
             return out
         _cabi.check(self._lib.gmrf_bt_marginal_var(self._h, m, k, seed, Q._h if Q is not None else None,
                                                    _cabi.ptr(out)))
+        return out
+
+    def selected_inverse(self, S: CsrMatrix, out=None):
+        """Entries of Sigma = Q^-1 at the stored positions of S (its values are ignored; gmrf_bt_selinv).  Every entry (r, c)
+        lies in the same or a neighbouring block, and for a coupling entry the index in the later block is below the factored
+        pattern's rmax: true for the factored matrix and any sub-pattern of it.  Batch 1: a scipy.sparse.csr_matrix with
+        S's pattern; a batch: the (batch, nnz) values in S's CSR order.  `out`: a contiguous float64 array of that shape
+        (batch 1: (nnz,)) to fill -- NumPy, or a torch tensor on the handle's device; it is then returned as it is."""
+        shape = (S.nnz,) if self.batch == 1 else (self.batch, S.nnz)
+        given = out is not None
+        out = self._out_array(out, shape)
+        _cabi.check(self._lib.gmrf_bt_selinv(self._h, S._h, _cabi.ptr(out)))
+        if given or self.batch > 1:
+            return out
+        return sp.csr_matrix((out, S.indices.copy(), S.indptr.copy()), shape=S.shape)
+
+    def trace_inv(self, S: CsrMatrix, dvals):
+        """tr(Q^-1 dQ_j) = sum_e Sigma[e] dvals[j][e] for every row j of `dvals`, (m, nnz) or (batch, m, nnz): dQ_j on S's
+        pattern, its values in S's CSR order (both triangles).  Returns (m,) or (batch, m), a NumPy array, or a device torch
+        tensor when `dvals` is one.  Sigma stays on the device; the same call gives the same bits (gmrf_bt_trace_inv)."""
+        nd = 2 if self.batch == 1 else 3
+        if dvals.ndim != nd or dvals.shape[-1] != S.nnz or (nd == 3 and dvals.shape[0] != self.batch):
+            want = "(m, nnz)" if nd == 2 else "(batch, m, nnz)"
+            raise ValueError(f"dvals must be {want} with nnz = {S.nnz}")
+        m = int(dvals.shape[-2])
+        if _is_torch(dvals):
+            import torch
+            if dvals.dtype != torch.float64:
+                raise TypeError("float64 required")
+            dvals = dvals.contiguous()
+            out = torch.empty(dvals.shape[:-1], dtype=torch.float64, device=dvals.device)
+        else:
+            dvals = np.ascontiguousarray(dvals, dtype=np.float64)
+            out = np.empty(dvals.shape[:-1], dtype=np.float64)
+        _cabi.check(self._lib.gmrf_bt_trace_inv(self._h, S._h, _cabi.ptr(dvals), m, _cabi.ptr(out)))
+        return out
+
+    @staticmethod
+    def _out_array(out, shape):
+        if out is None:
+            return np.empty(shape, dtype=np.float64)
+        ok = tuple(out.shape) == shape and (out.is_contiguous() and str(out.dtype) == "torch.float64" if _is_torch(out)
+                                            else out.flags.c_contiguous and out.dtype == np.float64)
+        if not ok:
+            raise ValueError(f"out must be a contiguous float64 array of shape {shape}")
         return out
 
     def var_accumulate(self, acc, method: str, first_id: int, k: int, seed: int = 0x5EED,

@@ -14,6 +14,7 @@
 #include <time.h>
 
 #include <algorithm>
+#include <atomic>
 #include <iterator>
 #include <cmath>
 #include <map>
@@ -39,6 +40,7 @@
 #include "sweep_persist.hpp"
 #include "swe_assemble.hpp"
 #include "fem_assemble_p2.hpp"
+#include "selinv.hpp"
 
 using namespace gmrf;
 
@@ -119,7 +121,9 @@ struct gmrf_csr {
     uint16_t* d_lidx = nullptr;        // per entry: index of its column in the tile's list
     int64_t n_ucols = 0;
     int plan_rows = 0, plan_ucap = 0, plan_ecap = 0, plan_ecap_pad = 0, plan_umax = 0;   // rows per tile, LDS capacities (distinct columns, entries)
+    uint64_t id = 0;                   // unique per created matrix (the selected-inverse plan of a handle is keyed by it)
 };
+static std::atomic<uint64_t> g_csr_ids{0};
 
 // ------------------------------------------------------------------------------------ handle
 struct EvPair {
@@ -188,6 +192,19 @@ struct gmrf_handle {
     double *d_S = nullptr, *d_B = nullptr, *d_T = nullptr, *d_W = nullptr;
     double* d_V = nullptr;             // two more work blocks per problem, allocated by the first exact-variance call (var_exact)
     int64_t v_elems = 0;
+    // selected inverse on a pattern (gmrf_bt_selinv / gmrf_bt_trace_inv): the plan of the last pattern, built on the host once per
+    // (layout, pattern); a new layout or shape (layout_gen) drops it, new values of the same pattern keep it
+    uint64_t layout_gen = 0;
+    uint64_t sel_csr = 0, sel_gen = ~0ull;            // plan of matrix id sel_csr under layout_gen sel_gen
+    int64_t sel_nnz = 0;
+    std::vector<int64_t> sel_off, sel_nd;             // [N + 1] block step i's entries; [N] how many of them read S_ii
+    int64_t* d_sel_src = nullptr;                     // [entries] element offset inside the block (row * bsp + col)
+    int64_t* d_sel_slot = nullptr;                    // [2][entries] output slot, mirrored slot (-1: none)
+    int64_t sel_cap = 0;
+    double* d_sig = nullptr;                          // [B][nnz] Sigma on the pattern (gmrf_bt_trace_inv, host output)
+    int64_t sig_elems = 0;
+    double* d_dv = nullptr;                           // staged host dvals / trace output
+    int64_t dv_elems = 0;
     int* d_info = nullptr;
     double* d_logdet = nullptr;
     int64_t alloc_N = 0, alloc_bsp = 0;
@@ -471,6 +488,7 @@ static gmrf_status set_layout(gmrf_handle* h, int64_t cmin, int64_t rmax, const 
     (void)hipStreamSynchronize(h->stream);
     destroy_graphs(h);
     h->cmin = cmin; h->rmax = rmax;
+    h->layout_gen++;
     h->kst.assign((size_t)ntile, 0);
     int64_t run = bsp - 64;                                   // envelope from the bottom: kst[t] = min over t' >= t
     for (int t = nrt - 1; t >= 0; --t) {
@@ -598,6 +616,7 @@ static gmrf_status set_shape(gmrf_handle* h, int64_t n, int64_t N) {
         h->analyzed = false;
     }
     h->n = n; h->N = N; h->bs = bs;
+    h->layout_gen++;
     h->bsp = 64 * next_pow2((bs + 63) / 64);
     h->n_pad = h->bsp * N;
     h->stats.n = n; h->stats.n_blocks = N; h->stats.block_size = bs; h->stats.block_size_padded = h->bsp;
@@ -2081,6 +2100,7 @@ gmrf_status gmrf_bt_destroy(gmrf_handle* h) {
     free_dev(h->d_info); free_dev(h->d_logdet); free_dev(h->d_pflags); free_dev(h->d_kbx); free_dev(h->d_V);
     free_dev(h->d_P); free_dev(h->d_Y); free_dev(h->d_Tp);
     free_dev(h->d_stage); free_dev(h->d_mean); free_dev(h->d_acc);
+    free_dev(h->d_sel_src); free_dev(h->d_sel_slot); free_dev(h->d_sig); free_dev(h->d_dv);
     for (auto e : h->ev_pool) (void)hipEventDestroy(e);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
@@ -3250,6 +3270,7 @@ gmrf_status gmrf_csr_create(int32_t device, void* stream, int64_t n_rows, int64_
     }
     gmrf_csr* m = new gmrf_csr();
     m->device = device;
+    m->id = ++g_csr_ids;
     m->tiles_ok = true;
     for (int64_t r = 0; r < n_rows; r += SPMV_ROWS)
         if (rp[std::min(n_rows, r + SPMV_ROWS)] - rp[r] > SPMV_CAP) { m->tiles_ok = false; break; }
@@ -4353,6 +4374,211 @@ static gmrf_status var_exact(gmrf_handle* h, double* d_out, bool seeded = false)
         }
         std::swap(Sg, Sn);
     }
+    return GMRF_OK;
+}
+
+// ------------------------------------------------------------------------ selected inverse on a pattern
+// Plan of a pattern S (gmrf_bt_selinv): every stored entry (r, c) is read from the block step that forms it -- S_ii for
+// blk(r) = blk(c) = i, Sigma_{i+1,i}[0:rmax, :] for an entry between blocks i and i+1 -- at its canonical place (the lower
+// triangle of S_ii; row in block i+1, column in block i).  Entries that share that place (the two triangles of a symmetric
+// pattern) share one plan entry with two output slots.  Built on the host from S's index arrays, uploaded once.
+static gmrf_status selinv_plan(gmrf_handle* h, const gmrf_csr* S, const char* who) {
+    if (h->sel_csr == S->id && h->sel_gen == h->layout_gen && h->d_sel_src) return GMRF_OK;
+    const int64_t n = h->n, bs = h->bs, bsp = h->bsp, rm = h->rmax, N = h->N, nnz = S->nnz;
+    std::vector<int64_t> rp((size_t)n + 1);
+    std::vector<int32_t> ci((size_t)std::max<int64_t>(nnz, 1));
+    HIPCHK(hipMemcpyAsync(rp.data(), S->d_rowptr, sizeof(int64_t) * (n + 1), hipMemcpyDeviceToHost, S->stream));
+    if (nnz > 0) HIPCHK(hipMemcpyAsync(ci.data(), S->d_colidx, sizeof(int32_t) * nnz, hipMemcpyDeviceToHost, S->stream));
+    HIPCHK(hipStreamSynchronize(S->stream));
+    struct Ent { int64_t key, src, slot; };            // key = 2 * step + (coupling ? 1 : 0)
+    std::vector<Ent> ents((size_t)nnz);
+    for (int64_t r = 0; r < n; ++r) {
+        for (int64_t e = rp[r]; e < rp[r + 1]; ++e) {
+            const int64_t c = ci[e], br = r / bs, bc = c / bs, lr = r % bs, lc = c % bs;
+            if (br == bc) {
+                ents[e] = {2 * br, std::max(lr, lc) * bsp + std::min(lr, lc), e};
+                continue;
+            }
+            const int64_t late = br > bc ? lr : lc, early = br > bc ? lc : lr;
+            if (std::abs(br - bc) > 1 || late >= rm) {
+                g_last_error = std::string(who) + ": pattern entry (" + std::to_string(r) + ", " + std::to_string(c) + ") " +
+                               (std::abs(br - bc) > 1 ? "lies " + std::to_string(std::abs(br - bc)) + " blocks off the diagonal"
+                                                      : "is a coupling entry whose index in the later block (" + std::to_string(late) +
+                                                        ") is not below rmax = " + std::to_string(rm)) +
+                               " (block size " + std::to_string(bs) + ")";
+                return GMRF_ERR_BAD_SHAPE;
+            }
+            ents[e] = {2 * std::min(br, bc) + 1, late * bsp + early, e};
+        }
+    }
+    std::sort(ents.begin(), ents.end(), [](const Ent& a, const Ent& b) {
+        return a.key != b.key ? a.key < b.key : (a.src != b.src ? a.src < b.src : a.slot < b.slot);
+    });
+    std::vector<int64_t> src, slot, slot2;
+    src.reserve((size_t)nnz); slot.reserve((size_t)nnz); slot2.reserve((size_t)nnz);
+    std::vector<int64_t> off((size_t)N + 1, 0), nd((size_t)N, 0);
+    for (size_t a = 0; a < ents.size();) {
+        size_t b = a + 1;
+        const bool pair = b < ents.size() && ents[b].key == ents[a].key && ents[b].src == ents[a].src;
+        src.push_back(ents[a].src); slot.push_back(ents[a].slot); slot2.push_back(pair ? ents[b].slot : -1);
+        const int64_t step = ents[a].key / 2;
+        off[(size_t)step + 1]++;
+        if (!(ents[a].key & 1)) nd[(size_t)step]++;
+        a = pair ? b + 1 : b;
+    }
+    for (int64_t i = 0; i < N; ++i) off[(size_t)i + 1] += off[(size_t)i];
+    const int64_t cnt = (int64_t)src.size();
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (!h->d_sel_src || h->sel_cap < cnt) {
+        free_dev(h->d_sel_src); free_dev(h->d_sel_slot); h->d_sel_src = nullptr; h->d_sel_slot = nullptr; h->sel_cap = 0;
+        HIPCHK(hipMalloc(&h->d_sel_src, sizeof(int64_t) * (size_t)std::max<int64_t>(cnt, 1)));
+        HIPCHK(hipMalloc(&h->d_sel_slot, sizeof(int64_t) * 2 * (size_t)std::max<int64_t>(cnt, 1)));
+        h->sel_cap = std::max<int64_t>(cnt, 1);
+    }
+    if (cnt > 0) {
+        HIPCHK(hipMemcpyAsync(h->d_sel_src, src.data(), sizeof(int64_t) * cnt, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(h->d_sel_slot, slot.data(), sizeof(int64_t) * cnt, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(h->d_sel_slot + h->sel_cap, slot2.data(), sizeof(int64_t) * cnt, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));       // (the vectors are locals)
+    }
+    h->sel_off = std::move(off); h->sel_nd = std::move(nd);
+    h->sel_nnz = nnz; h->sel_csr = S->id; h->sel_gen = h->layout_gen;
+    return GMRF_OK;
+}
+
+// Sigma = A^-1 on the plan's pattern into d_out[B][nnz].  The recurrence of var_exact with the same products, plus per block step
+//   Sigma_{i+1,i}[0:rmax, :] = -T1 X[cmin:, :]        rmax x bsp, K = wc from the first non-zero row of each column tile (d_kbx)
+//                                                     (Sigma L = L^-T, block row i+1 of block column i; T1 = S' C_w as formed)
+//   S_ii = X[:cmin]^T X[:cmin] + X[cmin:]^T Y[cmin:]  the whole block on its lower tiles, the two K ranges of the leading block
+// and a scatter of the step's pattern entries to their slots.  The coupling block goes to the M buffer once Y is formed, S_ii to
+// the buffer the leading block goes to (its leading rmax x rmax block is then mirrored for the next step, as var_exact does).
+static gmrf_status selinv_pattern(gmrf_handle* h, double* d_out) {
+    const int bsp = (int)h->bsp;
+    const int64_t ld = bsp, bstride = (int64_t)bsp * bsp;
+    const int64_t pX = stride_pX(h), pCm = stride_pC(h), pW = bstride;
+    const int cm = (int)h->cmin, rm = (int)h->rmax, wc = bsp - cm;
+    const unsigned nb = (unsigned)h->B;
+    GCHK(ensure_full_inverse(h));
+    if (!h->d_V || h->v_elems < 2 * bstride * h->B) {
+        HIPCHK(hipStreamSynchronize(h->stream));
+        free_dev(h->d_V); h->d_V = nullptr; h->v_elems = 0;
+        HIPCHK(hipMalloc(&h->d_V, sizeof(double) * 2 * (size_t)bstride * (size_t)h->B));
+        h->v_elems = 2 * bstride * h->B;
+    }
+    double* Sg = h->d_S;
+    double* Sn = h->d_W;
+    double* Y = h->d_T;
+    double* V1 = h->d_V;                                 // T1
+    double* V2 = h->d_V + bstride * h->B;                // M, then Sigma_{i+1,i}[0:rmax, :]
+    const int trm = rm / 64, twc = wc / 64;
+    const int64_t* slot2 = h->d_sel_slot + h->sel_cap;
+    for (int64_t i = h->N - 1; i >= 0; --i) {
+        const double* X = h->d_Linv + i * bstride;
+        const bool coupled = i < h->N - 1;
+        const int64_t e0 = h->sel_off[(size_t)i], ne = h->sel_off[(size_t)i + 1] - e0, nd = h->sel_nd[(size_t)i];
+        if (coupled) {
+            const double* C = h->d_C + i * c_blk(h);
+            GCHK(gemm(h, false, true, rm, wc, rm, 0, 0, 1.0, Sg, ld, C, c_ld(h), 0.0, V1, ld, pW, pCm, pW,
+                      1, 0, 0, 0, nullptr, 0, 0, 0, 2.0 * rm * h->c_streamed * (double)h->B, nullptr, nullptr, h->d_mend));
+            GCHK(gemm(h, true, true, wc, wc, rm, 0, 1, 1.0, V1, ld, C, c_ld(h), 0.0, V2, ld, pW, pCm, pW,
+                      1, 0, 0, 0, nullptr, 0, 0, 0, -1.0, nullptr, nullptr, h->d_mend));
+            hipLaunchKernelGGL(transpose_tiles, dim3((unsigned)(twc * (twc + 1) / 2), nb), dim3(256), 0, h->stream, V2, ld, V2, ld, pW, pW, twc, twc, 2);
+            HIPCHK(hipGetLastError());
+            GCHK(gemm(h, false, true, wc, bsp, wc, 0, 0, 1.0, V2, ld, X + (int64_t)cm * ld, ld, 1.0, Y + (int64_t)cm * ld, ld, pW, pX, pW,
+                      1, 0, 0, 0, X + (int64_t)cm * ld, ld, pX, 0, -1.0, nullptr, h->d_kbx, nullptr));
+            if (ne > nd)
+                GCHK(gemm(h, false, true, rm, bsp, wc, 0, 0, -1.0, V1, ld, X + (int64_t)cm * ld, ld, 0.0, V2, ld, pW, pX, pW,
+                          1, 0, 0, 0, nullptr, 0, 0, 0, -1.0, nullptr, h->d_kbx, nullptr));
+        }
+        // S_ii on its lower tiles: the whole block if this step has entries there, else its leading block for the next step
+        const int ms = nd > 0 ? bsp : rm;
+        if (nd > 0 || i > 0) {
+            if (coupled) {
+                if (cm > 0)
+                    GCHK(gemm(h, true, true, ms, ms, cm, TRI_A_UPPER | TRI_B_LOWER, 1, 1.0, X, ld, X, ld, 0.0, Sn, ld, pX, pX, pW));
+                GCHK(gemm(h, true, true, ms, ms, wc, 0, 1, 1.0, X + (int64_t)cm * ld, ld, Y + (int64_t)cm * ld, ld, cm > 0 ? 1.0 : 0.0, Sn, ld,
+                          pX, pW, pW, 1, 0, 0, 0, nullptr, 0, 0, 0, -1.0, h->d_kbx, nullptr, nullptr));
+            } else {
+                GCHK(gemm(h, true, true, ms, ms, bsp, TRI_A_UPPER | TRI_B_LOWER, 1, 1.0, X, ld, X, ld, 0.0, Sn, ld, pX, pX, pW));
+            }
+        }
+        if (ne > 0) {
+            hipLaunchKernelGGL(selinv_scatter, dim3((unsigned)((ne + 255) / 256), nb), dim3(256), 0, h->stream, Sn, V2, pW,
+                               h->d_sel_src, h->d_sel_slot, slot2, e0, nd, ne, d_out, h->sel_nnz);
+            HIPCHK(hipGetLastError());
+        }
+        if (i == 0) break;
+        hipLaunchKernelGGL(transpose_tiles, dim3((unsigned)(trm * (trm + 1) / 2), nb), dim3(256), 0, h->stream, Sn, ld, Sn, ld, pW, pW, trm, trm, 2);
+        HIPCHK(hipGetLastError());
+        std::swap(Sg, Sn);
+    }
+    return GMRF_OK;
+}
+
+static gmrf_status selinv_ready(gmrf_handle* h, const gmrf_csr* S, const char* who) {
+    GCHK(tw_refuse(h, who));
+    if (!h->factored) { g_last_error = std::string(who) + " before factor"; return GMRF_ERR_NO_FACTOR; }
+    if (S->n_rows != h->n || S->n_cols != h->n)
+        return bad_shape((std::string(who) + ": the pattern must be n x n with the factored n").c_str());
+    HIPCHK(hipSetDevice(h->device));
+    GCHK(selinv_plan(h, S, who));
+    return GMRF_OK;
+}
+
+static gmrf_status ensure_sig(gmrf_handle* h) {
+    const int64_t need = std::max<int64_t>(h->sel_nnz, 1) * h->B;
+    if (h->d_sig && h->sig_elems >= need) return GMRF_OK;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    free_dev(h->d_sig); h->d_sig = nullptr; h->sig_elems = 0;
+    HIPCHK(hipMalloc(&h->d_sig, sizeof(double) * (size_t)need));
+    h->sig_elems = need;
+    return GMRF_OK;
+}
+
+gmrf_status gmrf_bt_selinv(gmrf_handle* h, const gmrf_csr* S, double* vals_out) {
+    if (!h || !S || !vals_out) return bad_shape("null pointer");
+    GCHK(selinv_ready(h, S, "gmrf_bt_selinv"));
+    const bool dev = is_device_ptr(vals_out);
+    if (!dev) GCHK(ensure_sig(h));
+    double* d_out = dev ? vals_out : h->d_sig;          // every slot of the pattern is written
+    GCHK(selinv_pattern(h, d_out));
+    if (!dev) HIPCHK(hipMemcpyAsync(vals_out, d_out, sizeof(double) * h->sel_nnz * h->B, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (h->profiling) prof_collect(h);
+    return GMRF_OK;
+}
+
+gmrf_status gmrf_bt_trace_inv(gmrf_handle* h, const gmrf_csr* S, const double* dvals, int64_t m, double* out) {
+    if (!h || !S || !dvals || !out) return bad_shape("null pointer");
+    if (m <= 0 || m > 65535) return bad_shape("gmrf_bt_trace_inv: m must be in [1, 65535]");
+    GCHK(selinv_ready(h, S, "gmrf_bt_trace_inv"));
+    GCHK(ensure_sig(h));
+    const int64_t nnz = h->sel_nnz, dv_count = h->B * m * nnz;
+    const int64_t nch = std::min<int64_t>(256, std::max<int64_t>(1, (nnz + 8191) / 8192)), len = (nnz + nch - 1) / nch;
+    const bool dv_dev = is_device_ptr(dvals), out_dev = is_device_ptr(out);
+    const int64_t need = (dv_dev ? 0 : dv_count) + h->B * m * nch + (out_dev ? 0 : h->B * m);
+    if (need > 0 && (!h->d_dv || h->dv_elems < need)) {
+        HIPCHK(hipStreamSynchronize(h->stream));
+        free_dev(h->d_dv); h->d_dv = nullptr; h->dv_elems = 0;
+        HIPCHK(hipMalloc(&h->d_dv, sizeof(double) * (size_t)need));
+        h->dv_elems = need;
+    }
+    const double* d_dv = dvals;
+    if (!dv_dev) {
+        HIPCHK(hipMemcpyAsync(h->d_dv, dvals, sizeof(double) * dv_count, hipMemcpyHostToDevice, h->stream));
+        d_dv = h->d_dv;
+    }
+    double* d_part = h->d_dv + (dv_dev ? 0 : dv_count);                 // [B][m][nch] partial sums
+    double* d_res = out_dev ? out : d_part + h->B * m * nch;
+    GCHK(selinv_pattern(h, h->d_sig));
+    hipLaunchKernelGGL(pattern_dot_part, dim3((unsigned)nch, (unsigned)m, (unsigned)h->B), dim3(256), 0, h->stream, h->d_sig, d_dv, nnz, m,
+                       len, d_part);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(pattern_dot_sum, dim3((unsigned)m, (unsigned)h->B), dim3(256), 0, h->stream, d_part, nch, m, d_res);
+    HIPCHK(hipGetLastError());
+    if (!out_dev) HIPCHK(hipMemcpyAsync(out, d_res, sizeof(double) * h->B * m, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (h->profiling) prof_collect(h);
     return GMRF_OK;
 }
 

@@ -197,6 +197,22 @@ gmrf_status gmrf_bt_marginal_var(gmrf_handle* h, int32_t method, int64_t k, uint
 gmrf_status gmrf_bt_marginal_var_batch(gmrf_handle* h, int32_t method, int64_t k, uint64_t seed,
                                        const gmrf_csr* Q, const double* q_vals, double* var_out);
 
+/* Selected inverse: the entries of Sigma = A^-1 at the stored positions of S (a gmrf_csr that gives the pattern only; its
+ * values are ignored).  vals_out: [batch][nnz(S)] in S's CSR order, host or device memory (as gmrf_bt_marginal_var).
+ * Every entry (r, c) of S must satisfy |blk(r) - blk(c)| <= 1 and, when the blocks differ, the index (r or c) that falls in
+ * the LATER block must be < rmax within that block, rmax of the factored pattern (true for every entry of the matrix that
+ * was factored and of any sub-pattern of it).  Otherwise GMRF_ERR_BAD_SHAPE, and gmrf_last_error names the first offending
+ * entry.  The plan of a pattern is built on the first call and kept across refactor_values; a new analysis drops it.
+ * Batches are served in lock step (one pattern for all problems).  No factor: GMRF_ERR_NO_FACTOR; a twisted handle:
+ * GMRF_ERR_BAD_SHAPE. */
+gmrf_status gmrf_bt_selinv(gmrf_handle* h, const gmrf_csr* S, double* vals_out);
+
+/* out[p][j] = tr(A_p^-1 dA_{p,j}) = sum_e Sigma_p[e] * dvals[p][j][e]: dA_{p,j} has S's pattern, its values in S's CSR order
+ * (both triangles, as a symmetric CSR holds them).  dvals [batch][m][nnz(S)], out [batch][m]; host or device each.
+ * Sigma never leaves the device.  Deterministic: the same call gives the same bits.  Pattern rule and errors as
+ * gmrf_bt_selinv; m outside [1, 65535]: GMRF_ERR_BAD_SHAPE. */
+gmrf_status gmrf_bt_trace_inv(gmrf_handle* h, const gmrf_csr* S, const double* dvals, int64_t m, double* out);
+
 /* Accumulators for sharded variance estimation: adds this rank's contribution of samples
  * [first_id, first_id + k) to acc (length n; RBMC: sum of squared off-diagonal terms,
  * MC: sum of squares).  The caller all-reduces acc and finishes with

@@ -34,7 +34,7 @@ import GaussianMarkovRandomFields: AbstractSolver, AbstractSolverBlueprint, cons
                                    construct_conditional_solver, compute_mean, compute_variance, compute_rand!,
                                    gmrf_precision, to_matrix
 
-export BlockTridiagonalSolverBlueprint, BlockTridiagonalSolver, gn_step!, sqmahal, nll
+export BlockTridiagonalSolverBlueprint, BlockTridiagonalSolver, gn_step!, sqmahal, nll, logdet_grad
 
 """
     BlockTridiagonalSolverBlueprint(N_blocks; var_strategy = :exact, n_var_samples = 50, seed = 0x5EED, device = 0, keep_l = false)
@@ -142,6 +142,28 @@ end
 
 "Negative log-likelihood of z, `nll_soln` of the same script (:213-215): 0.5 (n log 2pi + sqmahal + logdet Sigma), logdet Sigma = -logdet Q."
 nll(s::BlockTridiagonalSolverState, z::AbstractVector) = 0.5 * (length(z) * log(2pi) + sqmahal(s, z) - logdet(s))
+
+"""
+    logdet_grad(s, dQs)
+
+`d logdet Q / d theta_j = tr(Q^-1 dQ_j)` for every `dQ_j` of `dQs` (sparse, on the precision's pattern or a part of it), from
+the selected inverse on that pattern (one recurrence for all j).  With a fixed mean the hyperparameter gradient of `nll` is
+`0.5 (r' dQ_j r - tr(Q^-1 dQ_j))`, r = z - mean.
+"""
+function logdet_grad(s::BlockTridiagonalSolverState, dQs::AbstractVector{<:SparseMatrixCSC})
+    _live(s)
+    P = s.precision
+    s.csr === nothing && (s.csr = HIP.GmrfCsr(P; device = s.bp.device))
+    dvals = zeros(Float64, nnz(P), length(dQs))
+    for (j, dQ) in enumerate(dQs)
+        size(dQ) == size(P) || throw(DimensionMismatch("dQ must have the precision's size"))
+        for c in 1:size(P, 2), e in nzrange(P, c)
+            dvals[e, j] = dQ[P.rowval[e], c]
+        end
+        count(!iszero, view(dvals, :, j)) == count(!iszero, nonzeros(dQ)) || error("dQ has entries outside the precision's pattern")
+    end
+    return HIP.trace_inv(s.precision_chol, P, dvals; csr = s.csr)
+end
 
 """
     gn_step!(s, Q, Qx_prior, J, x, obs_diff, noise)  ->  new iterate

@@ -286,6 +286,41 @@ function marginal_var_batch(F::TridiagonalCholeskyFactor, Q, q_vals::StridedVecO
     return out
 end
 
+"""
+    selinv(F, S::SparseMatrixCSC; device = 0, csr = nothing)
+
+Selected inverse: the entries of Sigma = A^-1 at the stored positions of `S` (its values are ignored), as a
+`SparseMatrixCSC` with S's pattern (a batch: an `nnz x batch` matrix of values in S's order).  Rule of the pattern
+(`gmrf_bt_selinv`): every entry (r, c) lies in the same or a neighbouring block, and for a coupling entry the index in the
+later block is below `rmax` -- true for the factored matrix and every sub-pattern of it.  The CSC arrays are passed as CSR
+arrays (of S', the same entries of the symmetric Sigma).  `csr`: a `GmrfCsr` of S made earlier (its plan stays cached).
+"""
+function selinv(F::TridiagonalCholeskyFactor, S::SparseMatrixCSC{Float64,Int}; device::Integer = 0, csr = nothing)
+    P = csr === nothing ? GmrfCsr(S; device = device) : csr
+    vals = Matrix{Float64}(undef, nnz(S), F.batch)
+    check(ccall((:gmrf_bt_selinv, libgmrf), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}), F.handle, P.handle, vals))
+    F.batch == 1 || return vals
+    return SparseMatrixCSC(size(S, 1), size(S, 2), copy(S.colptr), copy(S.rowval), vec(vals))
+end
+
+"""
+    trace_inv(F, S::SparseMatrixCSC, dvals; device = 0, csr = nothing)
+
+`tr(A^-1 dA_j)` for every column j of `dvals` (`nnz x m`, or `nnz x m x batch`): dA_j has S's pattern, its values in S's
+nzval order (both triangles).  Returns an m-vector (a batch: `m x batch`).  Sigma stays on the device; deterministic.
+"""
+function trace_inv(F::TridiagonalCholeskyFactor, S::SparseMatrixCSC{Float64,Int}, dvals::AbstractArray{Float64};
+                   device::Integer = 0, csr = nothing)
+    P = csr === nothing ? GmrfCsr(S; device = device) : csr
+    size(dvals, 1) == nnz(S) || throw(DimensionMismatch("dvals must have nnz(S) rows"))
+    m = size(dvals, 2)
+    dv = Array{Float64}(dvals)
+    out = Matrix{Float64}(undef, m, F.batch)
+    GC.@preserve dv check(ccall((:gmrf_bt_trace_inv, libgmrf), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Float64}),
+                                F.handle, P.handle, dv, m, out))
+    return F.batch == 1 ? vec(out) : out
+end
+
 "Sharded variance estimation: adds this rank's samples [first_id, first_id + k) to `acc` (all-reduce it afterwards)."
 function var_accumulate!(acc::Vector{Float64}, F::TridiagonalCholeskyFactor, first_id::Integer, k::Integer; method::Symbol = :rbmc, seed::Integer = 0x5EED, Q = nothing)
     qh = Q === nothing ? C_NULL : Q.handle

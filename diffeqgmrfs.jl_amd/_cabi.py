@@ -24,7 +24,7 @@ ORDER_REFERENCE, ORDER_TWISTED = 0, 1
 EXPORTS = [
     "gmrf_bt_create", "gmrf_bt_destroy", "gmrf_last_error", "gmrf_version",
     "gmrf_bt_factor_csc", "gmrf_bt_factor_blocks", "gmrf_bt_refactor_values",
-    "gmrf_bt_solve", "gmrf_bt_sample", "gmrf_bt_posterior", "gmrf_bt_normals", "gmrf_bt_marginal_var",
+    "gmrf_bt_solve", "gmrf_bt_sample", "gmrf_bt_posterior", "gmrf_bt_set_factor_rhs", "gmrf_bt_normals", "gmrf_bt_marginal_var",
     "gmrf_bt_var_accumulate", "gmrf_bt_logdet", "gmrf_bt_get_block", "gmrf_bt_factor_buffer",
     "gmrf_bt_adopt_shape", "gmrf_bt_adopt_commit", "gmrf_bt_adopt_layout", "gmrf_bt_get_layout", "gmrf_bt_block_range",
     "gmrf_bt_set_keep_l", "gmrf_bt_storage_bytes", "gmrf_bt_set_storage", "gmrf_bt_factor_begin_csc",
@@ -40,7 +40,7 @@ EXPORTS = [
     "gmrf_shallow_water_p1_create", "gmrf_shallow_water_p1_destroy", "gmrf_shallow_water_p1_pattern", "gmrf_shallow_water_p1_qpoints",
     "gmrf_shallow_water_p1_assemble", "gmrf_shallow_water_p1_operators",
     "gmrf_assemble_create", "gmrf_assemble_destroy", "gmrf_assemble_pattern", "gmrf_assemble_precision", "gmrf_assemble_rhs",
-    "gmrf_test_gemm", "gmrf_test_gemm_rate", "gmrf_test_gemm_shapes", "gmrf_test_potrf_tile", "gmrf_test_potrf_block", "gmrf_test_tile_timing", "gmrf_test_persist_stamps", "gmrf_test_persist_aborts", "gmrf_test_persist_budget", "gmrf_test_clock_probe_start", "gmrf_test_clock_probe_finish",
+    "gmrf_test_gemm", "gmrf_test_gemm_rate", "gmrf_test_gemm_shapes", "gmrf_test_potrf_tile", "gmrf_test_potrf_block", "gmrf_test_tile_timing", "gmrf_test_persist_stamps", "gmrf_test_persist_aborts", "gmrf_test_factor_fwd", "gmrf_test_persist_budget", "gmrf_test_clock_probe_start", "gmrf_test_clock_probe_finish",
     "gmrf_test_mfma_f64_rate", "gmrf_test_hbm_rate", "gmrf_test_microbench", "gmrf_test_symbolic_csc",
 ]
 
@@ -106,6 +106,7 @@ def load() -> C.CDLL:
         "gmrf_bt_solve": [vp, vp, vp, i64, i64, i64, i32],
         "gmrf_bt_sample": [vp, u64, i64, i64, vp, vp, vp, i64],
         "gmrf_bt_posterior": [vp, vp, u64, i64, i64, vp, vp, i64],
+        "gmrf_bt_set_factor_rhs": [vp, vp],
         "gmrf_bt_normals": [vp, u64, i64, i64, vp, i64],
         "gmrf_bt_marginal_var": [vp, i32, i64, u64, vp, vp],
         "gmrf_bt_var_accumulate": [vp, i32, i64, i64, u64, vp, vp],
@@ -187,6 +188,7 @@ def load() -> C.CDLL:
         "gmrf_test_tile_timing": [vp, i32],
         "gmrf_test_persist_stamps": [vp, i32],
         "gmrf_test_persist_aborts": [vp, vp],
+        "gmrf_test_factor_fwd": [vp, vp, vp],
         "gmrf_test_persist_budget": [i32, i32, vp, vp],
         "gmrf_test_clock_probe_start": [i32, i32, i32, P(vp)],
         "gmrf_test_clock_probe_finish": [vp, vp, vp],

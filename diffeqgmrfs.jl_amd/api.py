@@ -767,6 +767,19 @@ class TridiagonalCholeskyFactor:
         _cabi.check(self._lib.gmrf_bt_posterior(self._h, _cabi.ptr(b), seed, first_id, k, _cabi.ptr(mean), _cabi.ptr(out), n))
         return mean, out
 
+    def set_factor_rhs(self, b):
+        """Register the right-hand side of later `posterior_batch` calls (gmrf_bt_set_factor_rhs): b, a contiguous float64 torch
+        CUDA tensor of B x n values, is READ AT FACTOR TIME -- a batch's factorisations then solve L y = b inside their own products,
+        and `posterior_batch` with this same tensor skips its forward sweep.  None clears it."""
+        if b is None:
+            self._factor_rhs = None
+            _cabi.check(self._lib.gmrf_bt_set_factor_rhs(self._h, None))
+            return
+        if not (_is_torch(b) and b.is_cuda and b.is_contiguous()) or (self.N and b.numel() != self.batch * self.N):
+            raise ValueError("set_factor_rhs(): a contiguous device tensor of batch x n values")
+        self._factor_rhs = b                     # (kept alive: the library holds its pointer)
+        _cabi.check(self._lib.gmrf_bt_set_factor_rhs(self._h, _cabi.ptr(b)))
+
     def marginal_var(self, method: str = "exact", k: int = 50, seed: int = 0x5EED, Q: Optional[CsrMatrix] = None,
                      q_values=None, out=None):
         """diag(Q^-1).  "exact" (selected inversion), "rbmc" (the reference's RBMCStrategy(k); needs Q)

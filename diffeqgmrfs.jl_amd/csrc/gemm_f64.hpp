@@ -57,6 +57,14 @@ struct GemmArgs {
     const int* kb_m = nullptr;
     const int* kb_n = nullptr;
     const int* ke_n = nullptr;
+    // Tail row of gemm_f64_dma's TAIL variant on operands of its own (tC != nullptr; one problem per z, nb1 == 1):
+    //   tC[n] = tbeta * tD[n] + alpha * sum_k tA[k] b(k,n)   per problem at tA + z ptA, tC + z ptC, tD + z ptD (tD null: tD = tC)
+    // over the K range of the tile that carries it.  tC == nullptr: the tail is row M of A / C / D.
+    const double* tA = nullptr;
+    double* tC = nullptr;
+    const double* tD = nullptr;
+    int64_t ptA = 0, ptC = 0, ptD = 0;
+    double tbeta = 0.0;
 };
 
 constexpr int GEMM_BM = 64;

@@ -97,6 +97,11 @@ __device__ __forceinline__ void gemm_dma_tile_order(const GemmArgs& g, int& bm, 
 // the B fragments it holds anyway -- with 4 fp64 FMAs per lane, and the 8 partial sums of a column are added in a fixed order at
 // the end.  The M rows of the MFMA tile are untouched: bitwise those of the kernel without the tail.  (The batched posterior runs
 // the mean's backward sweep as this row of the samples' sweep: gmrf_hip.hip, posterior_fused.)
+// (round 7) The same for B stored [n][k] -- wave w then holds columns wn + li and wn + 16 + li of k pair group w >> 1 -- for
+// triangular grids (lower_only == 1) and TRI_B_UPPER products, and with operands of its own (GemmArgs::tA / tC / tD, the
+// factorisation's forward solve: gmrf_hip.hip, factor_blocks_range).  The tile that carries the tail of column tile bn is the one
+// whose K range is the tail's: the diagonal tile (bn, bn) of a triangular grid (with staircase bounds K starts at kst[bn] there,
+// as the tail's column does), else the last row tile.
 template <int BM, int BN, bool B_N, int STAGES, bool A_T = false, bool TAIL = false>
 __global__ __launch_bounds__(256, (BM + BN > 128) ? 3 : 4) void gemm_f64_dma(GemmArgs g) {
     constexpr int BK = DMA_BK;
@@ -105,10 +110,10 @@ __global__ __launch_bounds__(256, (BM + BN > 128) ? 3 : 4) void gemm_f64_dma(Gem
     constexpr int A_ST = BM * BK, B_ST = BN * BK, T_ST = TAIL ? BK : 0, ST = A_ST + B_ST + T_ST;   // doubles per stage
     static_assert(NJ % 2 == 0 || !B_N, "the [k][n] image pairs neighbouring column tiles");
     static_assert(MI % 2 == 0 || !A_T, "the [k][m] image pairs neighbouring row tiles");
-    static_assert(!TAIL || (BM == 64 && BN == 64 && B_N && !A_T), "the tail row: 64 x 64 tiles, B stored [k][n]");
+    static_assert(!TAIL || (BM == 64 && BN == 64 && !A_T), "the tail row: 64 x 64 tiles");
     int bm, bn, z;
     gemm_dma_tile_order<BM, BN>(g, bm, bn, z);
-    const bool tail = TAIL && bm == g.M / BM - 1;                // (workgroup-uniform)
+    const bool tail = TAIL && (g.lower_only == 1 ? bm == bn : bm == g.M / BM - 1);     // (workgroup-uniform)
     const int m0 = bm * BM, n0 = bn * BN;
     if (g.lower_only == 2 && n0 > m0 + BM - 1) return;
     const int zi = z % g.nb1, zp = z / g.nb1;
@@ -166,7 +171,7 @@ __global__ __launch_bounds__(256, (BM + BN > 128) ? 3 : 4) void gemm_f64_dma(Gem
             offb[i] = (uint32_t)(((int64_t)(n0 + row) * g.ldb + 2 * ch) * 8);
         }
     }
-    const double* arow = A + (int64_t)g.M * g.lda;              // (TAIL) row M of A
+    const double* arow = g.tC ? g.tA + (int64_t)zp * g.ptA : A + (int64_t)g.M * g.lda;      // (TAIL) the tail row of A
     auto issue = [&](int kt, int stage) {
         const int k0 = kb + kt * BK;
         const char* abase = reinterpret_cast<const char*>(A_T ? A + (int64_t)k0 * g.lda : A + k0);
@@ -195,7 +200,7 @@ __global__ __launch_bounds__(256, (BM + BN > 128) ? 3 : 4) void gemm_f64_dma(Gem
     for (int i = 0; i < MI; ++i)
 #pragma unroll
         for (int j = 0; j < NJ; ++j) acc[i][j] = (v4d){0.0, 0.0, 0.0, 0.0};
-    v2d tacc = (v2d){0.0, 0.0};                                  // (TAIL) columns wn + 2 li, + 1: k pairs 2 lq of group w >> 1
+    v2d tacc = (v2d){0.0, 0.0};                                  // (TAIL) columns wn + 2 li, + 1 ([k][n]) / wn + li, + 16 ([n][k]): k pairs 2 lq of group w >> 1
     const int tkg = w >> 1;
 
     // fragment addresses inside a stage (doubles): A rows wm + 16 i + li, chunk kg * 4 + lq swizzled by the row
@@ -275,10 +280,16 @@ __global__ __launch_bounds__(256, (BM + BN > 128) ? 3 : 4) void gemm_f64_dma(Gem
                         }
             if constexpr (TAIL) {
                 if (tail) {
-                    // b[kg][p] = B(8 kg + 2 lq + p, wn + 2 li .. + 1)
                     const v2d b0 = tkg ? b[1][0] : b[0][0], b1 = tkg ? b[1][1] : b[0][1];
-                    tacc.x = fma(ta.x, b0.x, tacc.x); tacc.x = fma(ta.y, b1.x, tacc.x);
-                    tacc.y = fma(ta.x, b0.y, tacc.y); tacc.y = fma(ta.y, b1.y, tacc.y);
+                    if (B_N) {
+                        // b[kg][p] = B(8 kg + 2 lq + p, wn + 2 li .. + 1)
+                        tacc.x = fma(ta.x, b0.x, tacc.x); tacc.x = fma(ta.y, b1.x, tacc.x);
+                        tacc.y = fma(ta.x, b0.y, tacc.y); tacc.y = fma(ta.y, b1.y, tacc.y);
+                    } else {
+                        // b[kg][j] = b(8 kg + 2 lq .. + 1, wn + 16 j + li)
+                        tacc.x = fma(ta.x, b0.x, tacc.x); tacc.x = fma(ta.y, b0.y, tacc.x);
+                        tacc.y = fma(ta.x, b1.x, tacc.y); tacc.y = fma(ta.y, b1.y, tacc.y);
+                    }
                 }
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -339,15 +350,23 @@ __global__ __launch_bounds__(256, (BM + BN > 128) ? 3 : 4) void gemm_f64_dma(Gem
         if (tail) {
             // the 8 partial sums of a column (k pair groups x lq) through LDS, added by wave 0 in a fixed order
             __syncthreads();                                     // every wave is done with the stages
-            *reinterpret_cast<v2d*>(gsm + (tkg * 4 + lq) * BN + wn + 2 * li) = tacc;
+            if (B_N) *reinterpret_cast<v2d*>(gsm + (tkg * 4 + lq) * BN + wn + 2 * li) = tacc;
+            else { gsm[(tkg * 4 + lq) * BN + wn + li] = tacc.x; gsm[(tkg * 4 + lq) * BN + wn + 16 + li] = tacc.y; }
             __syncthreads();
             if (w == 0) {
                 double s = 0.0;
 #pragma unroll
                 for (int q = 0; q < 8; ++q) s += gsm[q * BN + lane];
                 double v = alpha * s;
-                if (beta != 0.0) v += beta * Dm[(int64_t)g.M * ldd + n0 + lane];
-                C[(int64_t)g.M * g.ldc + n0 + lane] = v;
+                if (g.tC) {
+                    double* tc = g.tC + (int64_t)zp * g.ptC;
+                    const double* td = g.tD ? g.tD + (int64_t)zp * g.ptD : tc;
+                    if (g.tbeta != 0.0) v += g.tbeta * td[n0 + lane];
+                    tc[n0 + lane] = v;
+                } else {
+                    if (beta != 0.0) v += beta * Dm[(int64_t)g.M * ldd + n0 + lane];
+                    C[(int64_t)g.M * g.ldc + n0 + lane] = v;
+                }
             }
         }
     }
@@ -416,24 +435,39 @@ inline hipError_t gemm_dma_init() {
 // gemm_dma_shape says 1 and gemm_uses_ll does not take the launch; nothing else qualifies.  Returns false (nothing launched) if
 // the product does not.
 inline bool gemm_tail_ok(bool a_t, bool b_n, const GemmArgs& g, int batch) {
-    if (a_t || !b_n || g.lower_only || gemm_uses_ll(g, batch) || gemm_dma_shape(false, g, batch) != 1) return false;
+    if (a_t || gemm_uses_ll(g, batch) || gemm_dma_shape(false, g, batch) != 1) return false;
+    if (g.lower_only && g.M != g.N) return false;                // (a triangular grid: the diagonal tiles carry the tail)
+    if (g.tC) {
+        // operands of its own: one problem per z, 16-byte aligned tail A (LDS-DMA of 16 bytes), even problem stride
+        return g.nb1 == 1 && g.tA && ((uintptr_t)g.tA & 15) == 0 && (g.ptA & 1) == 0;
+    }
+    if (!b_n || g.lower_only) return false;
     // 32-bit byte offsets inside a problem's operand for the M + 1 rows (A: row M read with 64-bit addressing)
     return (int64_t)(g.M + 1) * g.ldc * 8 < ((int64_t)1 << 32) && (!g.D || (int64_t)(g.M + 1) * g.ldd * 8 < ((int64_t)1 << 32));
 }
 inline bool gemm_try_dma_tail(hipStream_t st, bool a_t, bool b_n, const GemmArgs& g, int batch, hipEvent_t ev_start, hipEvent_t ev_stop,
                               hipError_t* err) {
     if (!gemm_tail_ok(a_t, b_n, g, batch)) return false;
+    // (grid and tile order as gemm_try_dma sets them up for the 64 x 64 tile)
+    const bool tri_grid = g.lower_only && g.M == g.N;
     GemmArgs gs = g;
-    gs.lower_only = 0;
-    const dim3 grid((unsigned)((int64_t)(g.N / 64) * (g.M / 64) * batch)), block(256);
+    gs.lower_only = tri_grid ? 1 : 0;
+    static const bool asc_off = [] { const char* e = getenv("GMRF_GEMM_G2_ORDER"); return e && atoi(e) == 0; }();   // tuning aid
+    if (tri_grid && (g.kb_m || g.kb_n) && !asc_off) gs.tri |= DMA_ROWS_ASCENDING;
+    const int64_t nx = g.N / 64, ny = g.M / 64;
+    const dim3 grid((unsigned)((tri_grid ? ny * (ny + 1) / 2 : nx * ny) * batch)), block(256);
     const size_t lds = (size_t)gemm_dma_stages() * (64 + 64 + DMA_BK) * DMA_BK * sizeof(double);
+#define GMRF_DMA_TK(BNAT, ST)                                                                                              \
+    do {                                                                                                                   \
+        if (ev_start) hipExtLaunchKernelGGL((gemm_f64_dma<64, 64, BNAT, ST, false, true>), grid, block, lds, st, ev_start, ev_stop, 0, gs); \
+        else hipLaunchKernelGGL((gemm_f64_dma<64, 64, BNAT, ST, false, true>), grid, block, lds, st, gs);                \
+    } while (0)
     if (gemm_dma_stages() == 3) {
-        if (ev_start) hipExtLaunchKernelGGL((gemm_f64_dma<64, 64, true, 3, false, true>), grid, block, lds, st, ev_start, ev_stop, 0, gs);
-        else hipLaunchKernelGGL((gemm_f64_dma<64, 64, true, 3, false, true>), grid, block, lds, st, gs);
+        if (b_n) GMRF_DMA_TK(true, 3); else GMRF_DMA_TK(false, 3);
     } else {
-        if (ev_start) hipExtLaunchKernelGGL((gemm_f64_dma<64, 64, true, 2, false, true>), grid, block, lds, st, ev_start, ev_stop, 0, gs);
-        else hipLaunchKernelGGL((gemm_f64_dma<64, 64, true, 2, false, true>), grid, block, lds, st, gs);
+        if (b_n) GMRF_DMA_TK(true, 2); else GMRF_DMA_TK(false, 2);
     }
+#undef GMRF_DMA_TK
     *err = hipGetLastError();
     return true;
 }

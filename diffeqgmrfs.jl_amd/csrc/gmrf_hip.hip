@@ -224,6 +224,16 @@ struct gmrf_handle {
     bool no_fused_posterior = false;   // a batch's gmrf_bt_posterior = gmrf_bt_solve + gmrf_bt_sample (eager bit 18; comparison)
     bool tail_probe = false;           // gemm(tail): only check whether the product qualifies (posterior_fused_ok)
     bool tail_refused = false;         // ... one did not
+    // The forward solve inside a batch's factorisation (round 7, gmrf_bt_set_factor_rhs): with the registered right-hand side b the
+    // factor's own products also leave y = L^-1 b (tail rows of G2, the panel products and the rank-256 updates; factor_blocks_range)
+    const double* frhs = nullptr;      // registered b (device, n x B, read at factor time)
+    const double* fy_for = nullptr;    // the current factor left y = L^-1 fy_for in d_fy (nullptr: none)
+    bool fwd_run = false;              // the factorisation being enqueued carries the forward solve (factor_fwd_ok)
+    bool no_factor_fwd = false;        // set_eager bit 19: never (comparison)
+    double* d_ft = nullptr;            // [B][bsp]: t = b_i - C_i y_{i-1} of the block being factored, updated panel by panel
+    double* d_fy = nullptr;            // [B][n_pad]: y, laid out as a k = 1 panel (what fill_normals_panel reads row kp from)
+    int64_t fy_elems = 0;
+    const double* factor_graph_rhs = nullptr;   // b the captured factor graph reads (nullptr: it does not solve)
     unsigned long long* dbg_stamps = nullptr;   // test hook: phase stamps of the fused panel step
     bool fork_graph = false;           // second branch in the captured factor graph (experiment, see potrf_block)
     bool no_staircase = false;         // treat the coupling window as dense (comparison; takes effect at the next analysis)
@@ -386,13 +396,26 @@ static void prof_collect(gmrf_handle* h) {
 }
 
 // ------------------------------------------------------------------------------------ helpers
+// A tail row on operands of its own (GemmArgs::tA / tC / tD): tC = beta tD + alpha tA b, per problem strides pA / pC / pD
+struct GemmTail {
+    const double* A; int64_t pA;
+    double* C; int64_t pC;
+    const double* D; int64_t pD;
+    double beta;
+};
+
 static gmrf_status gemm(gmrf_handle* h, bool a_t, bool b_n, int M, int N, int K, int tri, int lower_only,
                         double alpha, const double* A, int64_t lda, const double* B, int64_t ldb,
                         double beta, double* C, int64_t ldc, int64_t pA, int64_t pB, int64_t pC,
                         int batch = 1, int64_t sA = 0, int64_t sB = 0, int64_t sC = 0, const double* D = nullptr,
                         int64_t ldd = 0, int64_t pD = 0, int pclass = 0, double pwork = -1.0,
-                        const int* kb_m = nullptr, const int* kb_n = nullptr, const int* ke_n = nullptr, bool tail = false) {
+                        const int* kb_m = nullptr, const int* kb_n = nullptr, const int* ke_n = nullptr, bool tail = false,
+                        const GemmTail* gt = nullptr) {
     GemmArgs g;
+    if (gt) {
+        g.tA = gt->A; g.ptA = gt->pA; g.tC = gt->C; g.ptC = gt->pC; g.tD = gt->D; g.ptD = gt->pD; g.tbeta = gt->beta;
+        tail = true;
+    }
     g.kb_m = kb_m; g.kb_n = kb_n; g.ke_n = ke_n;
     g.D = D; g.ldd = ldd; g.pD = pD;
     g.A = A; g.B = B; g.C = C;
@@ -409,7 +432,7 @@ static gmrf_status gemm(gmrf_handle* h, bool a_t, bool b_n, int M, int N, int K,
         // (tail_probe) only asks whether every product of a sweep qualifies.
         if (!gemm_tail_ok(a_t, b_n, g, batch * (int)h->B)) {
             h->tail_refused = true;
-            return h->tail_probe ? GMRF_OK : bad_shape("internal: a product of the fused sweep does not qualify for the tail-row GEMM");
+            return h->tail_probe ? GMRF_OK : bad_shape("internal: a product does not qualify for the tail-row GEMM");
         }
         if (h->tail_probe) return GMRF_OK;
         flops *= (M + 1.0) / M;
@@ -602,6 +625,7 @@ static void release_shape_buffers(gmrf_handle* h) {
     free_dev(h->d_mean); h->d_mean = nullptr;
     free_dev(h->d_acc); h->d_acc = nullptr; h->acc_B = 0;
     free_dev(h->d_stage); h->d_stage = nullptr; h->stage_cap = 0;
+    free_dev(h->d_ft); free_dev(h->d_fy); h->d_ft = h->d_fy = nullptr; h->fy_elems = 0; h->fy_for = nullptr;
 }
 
 static gmrf_status set_shape(gmrf_handle* h, int64_t n, int64_t N) {
@@ -1138,7 +1162,8 @@ static gmrf_status launch_persist(gmrf_handle* h, double* S, double* L, double* 
     return GMRF_OK;
 }
 
-static gmrf_status potrf_block(gmrf_handle* h, double* S, double* L, double* X, double* T, int blk_id) {
+// fy (batches on the 256-column panel route, factor_fwd_ok): also y_i = L_i^-1 t into fy ([B][n_pad]: this block's part), t = d_ft
+static gmrf_status potrf_block(gmrf_handle* h, double* S, double* L, double* X, double* T, int blk_id, double* fy = nullptr) {
     const int bsp = (int)h->bsp;
     const int64_t ld = bsp;
     const int nt = bsp / 64;
@@ -1217,6 +1242,7 @@ static gmrf_status potrf_block(gmrf_handle* h, double* S, double* L, double* X, 
     //   X_BA = -X_B (L_BA X_A)                        (the level-128 doubling step of this pair: X_P = [X_A 0; X_BA X_B])
     //   L[below, P] = S[below, P] X_P^T               (K = 256, X_P lower triangular)
     //   S[below, below] -= L[below, P] L[below, P]^T  (rank-256 update)
+    if (fy && (route != ROUTE_PANELS256 || overlap)) return bad_shape("internal: forward solve planned off the 256-column panel route");
     if (route == ROUTE_PANELS256 && !overlap) {
         StepArgs sa;
         sa.S = S; sa.L = L; sa.X = X; sa.ld = ld; sa.nt = nt; sa.cend = nt;
@@ -1267,7 +1293,23 @@ static gmrf_status potrf_block(gmrf_handle* h, double* S, double* L, double* X, 
                           sa.pX, pW, sa.pX));
             }
             const int m3 = nt - j - 4;                             // row tiles below the panel
-            if (m3 <= 0) continue;
+            // forward solve (fy): y_P = X_P t_P is the tail row of the panel product, t[below] -= L[below, P] y_P the tail row of the
+            // rank-256 update; the last panel has no rows below it and takes the 256^2 product on its own
+            const int64_t pT = bsp, pY = h->n_pad;
+            if (m3 <= 0) {
+                if (fy) {
+                    // y_P = X_P t_P on the forward sweep's k = 1 kernel (X_P lower triangular, 256 x 256)
+                    SweepArgs sw;
+                    sw.Mat = X + oa * ld + oa; sw.ld = ld; sw.Xin = h->d_ft + oa; sw.ldx = pT; sw.Bin = nullptr; sw.ldb = 0;
+                    sw.Out = fy + oa; sw.ldo = pY; sw.rows = 256; sw.kdim = 256; sw.sub = 0;
+                    sw.pMat = sa.pX; sw.pXin = pT; sw.pBin = 0; sw.pOut = pY;
+                    ProfScope ps(h, 3, 4.0 * 256.0 * 257.0 * nb);
+                    HIPCHK(launch_sweep(h->stream, false, true, 1, sw, (int)h->B));
+                }
+                continue;
+            }
+            const GemmTail tp{h->d_ft + oa, pT, fy + oa, pY, nullptr, 0, 0.0};
+            const GemmTail tu{fy + oa, pY, h->d_ft + oc, pT, nullptr, 0, 1.0};
             // Split representation with p = the panel width and no L blocks kept: L[p:, 0:p] is read by this panel's own
             // update only, so it is formed directly in the place it takes in Linv's storage (see gmrf_handle::xsplit)
             const bool in_slot = (j == 0 && h->xsplit == 256 && !h->keep_l);
@@ -1275,10 +1317,12 @@ static gmrf_status potrf_block(gmrf_handle* h, double* S, double* L, double* X, 
             const int64_t pLb = in_slot ? sa.pX : sa.pL;
             // L[below, P] = S[below, P] X_P^T: b(k, n) = X_P[n][k], zero for k > n (tile-K units: 1 + 2 + 3 + 4 of 16)
             GCHK(gemm(h, false, false, 64 * m3, 256, 256, TRI_B_UPPER, 0, 1.0, S + oc * ld + oa, ld, X + oa * ld + oa, ld, 0.0, Lb, ld,
-                      sa.pS, sa.pX, pLb, 1, 0, 0, 0, nullptr, 0, 0, 0, 2.0 * t3 * 10.0 * m3 * nb));
+                      sa.pS, sa.pX, pLb, 1, 0, 0, 0, nullptr, 0, 0, 0, 2.0 * t3 * 10.0 * m3 * nb, nullptr, nullptr, nullptr, false,
+                      fy ? &tp : nullptr));
             // S[r,c] -= L[r,P] L[c,P]^T for the tiles right of / below the panel
             GCHK(gemm(h, false, false, m3 * 64, m3 * 64, 256, 0, 1, -1.0, Lb, ld, Lb, ld, 1.0, S + oc * ld + oc, ld, pLb, pLb, sa.pS,
-                      1, 0, 0, 0, nullptr, 0, 0, 0, 2.0 * t3 * 4.0 * (m3 * (m3 + 1) / 2) * nb));
+                      1, 0, 0, 0, nullptr, 0, 0, 0, 2.0 * t3 * 4.0 * (m3 * (m3 + 1) / 2) * nb, nullptr, nullptr, nullptr, false,
+                      fy ? &tu : nullptr));
         }
         // X = L^-1 by recursive doubling over the 256-wide diagonal inverses -- or, split representation, everything
         // but its first block column below row p, whose place L[p:, 0:p] takes (see gmrf_handle::xsplit)
@@ -1414,6 +1458,12 @@ static gmrf_status factor_blocks_range(gmrf_handle* h, int64_t i0, int64_t i1) {
         // single rounding as D - acc, and only the rows the product does not write (>= rmax) need
         // zeroing -- a quarter of the block on darcy instead of all of it.  The first block has no product.
         const int rm_s = (i > 0) ? (int)h->rmax : 0;
+        if (h->fwd_run) {
+            // t = b_i (the rows G2's tail does not write stay so)
+            hipLaunchKernelGGL(factor_rhs_block, dim3((unsigned)((bsp + 255) / 256), nb), dim3(256), 0, h->stream, h->frhs, h->n, (int)h->bs,
+                               bsp, i, h->d_ft);
+            HIPCHK(hipGetLastError());
+        }
         // (round 5: where the coupling product of this block runs on spmm_bxt_tiles, that launch zeroes the rows as well)
         static const bool no_tiles_z = [] { const char* e = getenv("GMRF_BXT_TILES"); return e && atoi(e) == 0; }();
         const bool scatter_in_bxt = i > 0 && nb == 1 && h->sparse_b && !h->dense_g1 && h->bxt_plan_ok && !no_tiles_z && h->bxt_nrt == (int)h->rmax / 64
@@ -1510,9 +1560,11 @@ static gmrf_status factor_blocks_range(gmrf_handle* h, int64_t i0, int64_t i1) {
             }
             // S = D - C C^T             (src/tridiagonal_cholesky.jl:77): the product part.  Tile (R, R') sums over
             // the columns from max(kst[R], kst[R']) on -- the rest of the two row tiles is structurally zero.
+            // (forward solve: its tail row, y_{i-1}'s window against C^T, gives t = b_i - C y_{i-1} for the rows below rmax)
+            const GemmTail tg{h->d_fy + (i - 1) * bsp + cm, h->n_pad, h->d_ft, bsp, nullptr, 0, 1.0};
             GCHK(gemm(h, false, false, rm, rm, W, 0, 1, -1.0, C, ldc, C, ldc, scatter_in_bxt ? 1.0 : 0.0, h->d_S, ld, pC, pC,
                       bstride, 1, 0, 0, 0, nullptr, 0, 0, 0, 2.0 * 64.0 * 64.0 * h->g2_tile_k * (double)h->B,
-                      h->d_kst, h->d_kst, nullptr));
+                      h->d_kst, h->d_kst, nullptr, false, h->fwd_run ? &tg : nullptr));
         }
         if (h->diag_count[i] > 0 && !scatter_in_bxt) {
             hipLaunchKernelGGL(scatter_block, dim3((unsigned)((h->diag_count[i] + 255) / 256), nb), dim3(256), 0,
@@ -1527,7 +1579,7 @@ static gmrf_status factor_blocks_range(gmrf_handle* h, int64_t i0, int64_t i1) {
                                h->stream, h->d_S, ld, (int)h->bs, bsp, bstride);
             HIPCHK(hipGetLastError());
         }
-        GCHK(potrf_block(h, h->d_S, L, X, h->d_T, (int)(i + 1)));
+        GCHK(potrf_block(h, h->d_S, L, X, h->d_T, (int)(i + 1), h->fwd_run ? h->d_fy + i * bsp : nullptr));
         if (i == h->tw_blk && h->tw_w)       // W = L_m^-1 HJ: the coupling of the twisted sweeps' meeting corrections
             GCHK(gemm(h, false, true, bsp, bsp, bsp, 0, 0, 1.0, X, ld, h->tw_hj, ld, 0.0, h->tw_w, ld, 0, 0, 0));
         if (!h->keep_l) {
@@ -1564,9 +1616,53 @@ static gmrf_status ensure_full_inverse(gmrf_handle* h) {
 // in steady state (graphs are replayed, not re-captured) and can go once concurrent captures have been shown to be safe.
 static std::mutex g_capture_mu;
 
+// Decided once per factorisation, before anything is enqueued: may this one carry the forward solve of the registered right-hand
+// side?  Batches on the 256-column panel route, not twisted, and EVERY product that would carry a tail row -- G2, the panel
+// products, the rank-256 updates -- on the 64 x 64 LDS-DMA tile that takes it (a dry run of gemm() with the tails asks).  Else the
+// handle leaves no y, and gmrf_bt_posterior runs its forward sweep.  Allocates d_ft / d_fy.
+static gmrf_status factor_fwd_ok(gmrf_handle* h, bool* ok) {
+    *ok = false;
+    if (!h->frhs || h->no_factor_fwd || h->B <= 1 || tw_on(h) || h->tw_blk >= 0 || h->fork_graph || h->rmax <= 0) return GMRF_OK;
+    const int bsp = (int)h->bsp, nt = bsp / 64;
+    if (potrf_route(h) != ROUTE_PANELS256 || bsp % 256 != 0) return GMRF_OK;
+    const int64_t elems = h->B * h->n_pad + h->B * h->bsp;
+    if (!h->d_fy || h->fy_elems < elems) {
+        HIPCHK(hipStreamSynchronize(h->stream));
+        free_dev(h->d_ft); free_dev(h->d_fy); h->d_ft = h->d_fy = nullptr; h->fy_elems = 0; h->fy_for = nullptr;
+        HIPCHK(hipMalloc(&h->d_fy, sizeof(double) * (size_t)(h->B * h->n_pad)));
+        HIPCHK(hipMalloc(&h->d_ft, sizeof(double) * (size_t)(h->B * h->bsp)));
+        h->fy_elems = elems;
+    }
+    const int64_t ld = bsp, bstride = (int64_t)bsp * bsp, pX = stride_pX(h), pL = stride_pL(h), pC = stride_pC(h);
+    const int cm = (int)h->cmin, rm = (int)h->rmax, W = bsp - cm;
+    double* S = h->d_S; double* X = h->d_Linv; double* L = h->d_L;
+    h->tail_probe = true; h->tail_refused = false;
+    gmrf_status st = GMRF_OK;
+    if (h->N > 1) {
+        const GemmTail tg{h->d_fy + cm, h->n_pad, h->d_ft, bsp, nullptr, 0, 1.0};
+        st = gemm(h, false, false, rm, rm, W, 0, 1, -1.0, h->d_C, c_ld(h), h->d_C, c_ld(h), 0.0, S, ld, pC, pC, bstride, 1, 0, 0, 0,
+                  nullptr, 0, 0, 0, -1.0, h->d_kst, h->d_kst, nullptr, false, &tg);
+    }
+    for (int j = 0; j + 4 < nt && st == GMRF_OK; j += 4) {
+        const int64_t oa = (int64_t)j * 64, oc = oa + 256;
+        const int m3 = nt - j - 4;
+        const GemmTail tp{h->d_ft + oa, bsp, h->d_fy + oa, h->n_pad, nullptr, 0, 0.0};
+        const GemmTail tu{h->d_fy + oa, h->n_pad, h->d_ft + oc, bsp, nullptr, 0, 1.0};
+        st = gemm(h, false, false, 64 * m3, 256, 256, TRI_B_UPPER, 0, 1.0, S + oc * ld + oa, ld, X + oa * ld + oa, ld, 0.0, L + oc * ld + oa, ld,
+                  bstride, pX, pL, 1, 0, 0, 0, nullptr, 0, 0, 0, -1.0, nullptr, nullptr, nullptr, false, &tp);
+        if (st == GMRF_OK)
+            st = gemm(h, false, false, m3 * 64, m3 * 64, 256, 0, 1, -1.0, L + oc * ld + oa, ld, L + oc * ld + oa, ld, 1.0, S + oc * ld + oc, ld,
+                      pL, pL, bstride, 1, 0, 0, 0, nullptr, 0, 0, 0, -1.0, nullptr, nullptr, nullptr, false, &tu);
+    }
+    h->tail_probe = false;
+    *ok = st == GMRF_OK && !h->tail_refused;
+    return GMRF_OK;
+}
+
 static gmrf_status run_factor(gmrf_handle* h, int64_t i0, int64_t i1) {
     if (h->eager || h->profiling) { h->stats.persist_route = 0; return factor_blocks_range(h, i0, i1); }
-    if (!h->factor_graph || h->factor_graph_i0 != i0 || h->factor_graph_i1 != i1) {
+    const double* grhs = h->fwd_run ? h->frhs : nullptr;          // (the graph reads b, and the choice of launches depends on it)
+    if (!h->factor_graph || h->factor_graph_i0 != i0 || h->factor_graph_i1 != i1 || h->factor_graph_rhs != grhs) {
         std::lock_guard<std::mutex> capture_lock(g_capture_mu);
         if (h->factor_graph) { (void)hipGraphExecDestroy(h->factor_graph); h->factor_graph = nullptr; }
         hipGraph_t graph = nullptr;
@@ -1581,7 +1677,7 @@ static gmrf_status run_factor(gmrf_handle* h, int64_t i0, int64_t i1) {
         HIPCHK(e);
         HIPCHK(hipGraphInstantiate(&h->factor_graph, graph, nullptr, nullptr, 0));
         (void)hipGraphDestroy(graph);
-        h->factor_graph_i0 = i0; h->factor_graph_i1 = i1;
+        h->factor_graph_i0 = i0; h->factor_graph_i1 = i1; h->factor_graph_rhs = grhs;
     }
     h->xsplit = planned_xsplit(h);                     // (what the captured launches produce)
     h->stats.persist_route = h->factor_graph_route;
@@ -1647,9 +1743,18 @@ static gmrf_status numeric_factor(gmrf_handle* h, const double* nzval, int32_t* 
     GCHK(load_values(h, nzval));
     HIPCHK(hipMemsetAsync(h->d_info, 0, 4 * sizeof(int), h->stream));
     h->info_checked = 0; h->persist_launched = false;
-    GCHK(run_factor(h, 0, h->N));
-    HIPCHK(hipEventRecord(h->ev1, h->stream));
-    gmrf_status s = factor_finish(h, info);
+    h->fy_for = nullptr;
+    bool fwd = false;
+    GCHK(factor_fwd_ok(h, &fwd));
+    // (an abort-and-repeat inside factor_finish re-runs the blocks' launches, the forward solve's included: t is set per block)
+    h->fwd_run = fwd;
+    gmrf_status s = run_factor(h, 0, h->N);
+    if (s == GMRF_OK) {
+        (void)hipEventRecord(h->ev1, h->stream);
+        s = factor_finish(h, info);
+    }
+    h->fwd_run = false;
+    if (s == GMRF_OK && fwd) h->fy_for = h->frhs;
     float ms = 0.f;
     (void)hipEventElapsedTime(&ms, h->ev0, h->ev1);
     h->stats.factor_ms = ms;
@@ -2100,6 +2205,7 @@ gmrf_status gmrf_bt_destroy(gmrf_handle* h) {
     free_dev(h->d_info); free_dev(h->d_logdet); free_dev(h->d_pflags); free_dev(h->d_kbx); free_dev(h->d_V);
     free_dev(h->d_P); free_dev(h->d_Y); free_dev(h->d_Tp);
     free_dev(h->d_stage); free_dev(h->d_mean); free_dev(h->d_acc);
+    free_dev(h->d_ft); free_dev(h->d_fy);
     free_dev(h->d_sel_src); free_dev(h->d_sel_slot); free_dev(h->d_sig); free_dev(h->d_dv);
     for (auto e : h->ev_pool) (void)hipEventDestroy(e);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
@@ -2158,6 +2264,8 @@ gmrf_status gmrf_bt_set_eager(gmrf_handle* h, int32_t eager) {
     if (((eager & 65536) != 0) != h->no_sweep_persist) { destroy_graphs(h); h->no_sweep_persist = (eager & 65536) != 0; }
     if (((eager & 131072) != 0) != h->no_scatter_fold) { destroy_graphs(h); h->no_scatter_fold = (eager & 131072) != 0; }
     h->no_fused_posterior = (eager & 262144) != 0;
+    h->no_factor_fwd = (eager & 524288) != 0;
+    if (eager != h->eager_bits) h->fy_for = nullptr;         // (a factor of other settings: no y taken for granted)
     h->eager = (eager & 1) != 0;
     h->eager_bits = eager;
     if (h->tw)
@@ -2224,7 +2332,7 @@ gmrf_status gmrf_bt_factor_begin_csc(gmrf_handle* h, int64_t n, int64_t n_blocks
     GCHK(load_values(h, nzval));
     HIPCHK(hipMemsetAsync(h->d_info, 0, 4 * sizeof(int), h->stream));
     h->info_checked = 0; h->persist_launched = false; h->stats.persist_route = 0;
-    h->factored = false;
+    h->factored = false; h->fy_for = nullptr;
     return GMRF_OK;
 }
 
@@ -2418,7 +2526,7 @@ gmrf_status gmrf_bt_adopt_commit(gmrf_handle* h, int32_t l_blocks_valid) {
     if (seen < 0) { g_last_error = "the packed ranges of this factor carry different (or no) representation tags"; return GMRF_ERR_BAD_SHAPE; }
     const int xs = seen > 0 ? seen - 1 : h->adopt_xsplit;
     if (xs < 0 || xs >= h->bsp || xs % 64) { g_last_error = "bad representation tag in the packed image"; return GMRF_ERR_BAD_SHAPE; }
-    h->factored = true;
+    h->factored = true; h->fy_for = nullptr;
     h->xsplit = xs;
     h->l_valid = l_blocks_valid != 0 && h->keep_l;
     // the log-determinant parts travel inside the packed transport image (gmrf_bt_unpack_blocks_async): valid once
@@ -2675,7 +2783,7 @@ gmrf_status gmrf_bt_import_factor(gmrf_handle* h, const void* buf, int64_t bytes
     for (int64_t i = 0; i + 1 < N; ++i) GCHK(put(in + i * be, h->d_C + h->sel * stride_pC(h) + i * c_blk(h), false));
     in += (N - 1) * be;
     for (int64_t i = 0; i < N; ++i) GCHK(put(in + i * be, h->d_Linv + h->sel * stride_pX(h) + i * blk_elems(h), true));
-    h->factored = true; h->l_valid = true;
+    h->factored = true; h->fy_for = nullptr; h->l_valid = true;
     persist_plan(h);
     h->xsplit = 0;                                     // the image holds the full inverses
     return GMRF_OK;
@@ -3133,12 +3241,17 @@ static gmrf_status posterior_fused(gmrf_handle* h, const double* b, uint64_t see
     const int kp = pad_k(k);
     GCHK(ensure_panels(h, kp + 1));
     HIPCHK(hipEventRecord(h->ev0, h->stream));
-    GCHK(launch_pack(h, b, h->n, 1, 1));
-    GCHK(run_sweeps(h, GMRF_SOLVE_FORWARD, 1));
+    // (round 7) the factorisation of b, the registered right-hand side, left y = L^-1 b beside the factor: no forward sweep
+    const bool have_y = h->fy_for && b == h->fy_for;
+    if (!have_y) {
+        GCHK(launch_pack(h, b, h->n, 1, 1));
+        GCHK(run_sweeps(h, GMRF_SOLVE_FORWARD, 1));
+    }
     {
         const int64_t total = (int64_t)(kp + 1) * h->n_pad;
         hipLaunchKernelGGL(fill_normals_panel, dim3((unsigned)((total + 255) / 256), (unsigned)h->B), dim3(256), 0,
-                           h->stream, h->d_P, h->n_pad, (int)h->bs, (int)h->bsp, (int)k, kp, seed, first_id, k, h->d_Y, h->n_pad);
+                           h->stream, h->d_P, h->n_pad, (int)h->bs, (int)h->bsp, (int)k, kp, seed, first_id, k,
+                           have_y ? h->d_fy : h->d_Y, h->n_pad);
         HIPCHK(hipGetLastError());
     }
     GCHK(run_sweeps(h, SWEEP_BACKWARD_TAIL, kp));
@@ -3194,6 +3307,14 @@ gmrf_status gmrf_bt_posterior(gmrf_handle* h, const double* b, uint64_t seed, in
     (void)hipEventElapsedTime(&ms, h->ev0, h->ev1);
     h->stats.solve_ms = ms;                            // (mean and samples together)
     h->stats.sample_ms = 0.0;
+    return GMRF_OK;
+}
+
+gmrf_status gmrf_bt_set_factor_rhs(gmrf_handle* h, const double* b) {
+    if (!h) return bad_shape("null handle");
+    if (b && !is_device_ptr(b)) return bad_shape("the factor's right-hand side must be device memory");
+    h->frhs = b;
+    h->fy_for = nullptr;
     return GMRF_OK;
 }
 
@@ -5504,6 +5625,19 @@ gmrf_status gmrf_test_persist_stamps(double* out, int32_t n) {
 
 // How often a factorisation of this handle saw the abort word of its persistent launches (a bounded wait gave up) and was
 // repeated with the launch-per-step form (tests force it with GMRF_PERSIST_SPIN_MS=0).
+// 1 if the current factor holds y = L^-1 b for the registered b (gmrf_bt_set_factor_rhs), else 0; y_out (optional, host, n x B
+// column-major) receives that y
+gmrf_status gmrf_test_factor_fwd(gmrf_handle* h, int32_t* state, double* y_out) {
+    if (!h || !state) return bad_shape("null pointer");
+    HIPCHK(hipSetDevice(h->device));
+    *state = (h->fy_for && h->factored && h->fy_for == h->frhs) ? 1 : 0;
+    if (y_out && *state) {
+        GCHK(cols_out(h, h->d_fy, 1, nullptr, y_out, h->n, false));
+        HIPCHK(hipStreamSynchronize(h->stream));
+    }
+    return GMRF_OK;
+}
+
 gmrf_status gmrf_test_persist_aborts(gmrf_handle* h, int32_t* n) {
     if (!h || !n) return bad_shape("null argument");
     *n = h->persist_aborts;

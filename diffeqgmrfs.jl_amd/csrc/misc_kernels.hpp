@@ -84,6 +84,15 @@ __global__ void pack_tag_read(const double* __restrict__ buf, int64_t pbuf, int 
     *seen = code;
 }
 
+// ------------------------------------------------------------------------------- forward solve inside the factorisation
+// t[p][r] = b_blk of problem p as pack_panel places it (zero in the padding rows r >= bs); b column-major n x B
+__global__ void factor_rhs_block(const double* __restrict__ b, int64_t n, int bs, int bsp, int64_t blk, double* __restrict__ t) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= bsp) return;
+    const int64_t p = blockIdx.y;
+    t[p * bsp + r] = (r < bs) ? b[p * n + blk * bs + r] : 0.0;
+}
+
 // ------------------------------------------------------------------------------- panels
 // user matrix (column-major n x k, leading dimension ld) <-> padded panel P[rhs][n_pad]
 // blockIdx.y = problem p: columns [p*k, (p+1)*k) of the user matrix <-> panel p (kp * n_pad doubles)

@@ -77,6 +77,9 @@ class HipEngine:
         self.values_host = np.ascontiguousarray(values, dtype=np.float64).reshape(batch, -1)
         self.nz = torch.from_numpy(self.values_host).to(self.dev)
         self.rhs = torch.from_numpy(np.ascontiguousarray(rhs, dtype=np.float64).reshape(batch, 1, -1)).to(self.dev)
+        if batch > 1:
+            # the batch's factorisations solve L y = rhs on the way (its posterior then skips the forward sweep)
+            self.F.set_factor_rhs(self.rhs)
         self._stage = {}
         self.bytes_moved = 0
         self._pending = []

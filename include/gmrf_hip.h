@@ -176,6 +176,15 @@ gmrf_status gmrf_bt_sample(gmrf_handle* h, uint64_t seed, int64_t first_id, int6
 gmrf_status gmrf_bt_posterior(gmrf_handle* h, const double* b, uint64_t seed, int64_t first_id, int64_t k,
                               double* mean, double* samples, int64_t ld);
 
+/* Registers the right-hand side of a batch's later gmrf_bt_posterior calls: b is a DEVICE pointer, n x B (problem-major, as
+ * gmrf_bt_posterior takes it), and it is READ AT FACTOR TIME.  Later factorisations of a batch on the 256-column panel route
+ * (gmrf_bt_factor_csc / refactor_values / factor_blocks) also solve L y = b inside the factor's own products and keep y beside
+ * the factor; a fused gmrf_bt_posterior with this same pointer then skips its forward sweep (the mean agrees with the swept one
+ * to rounding).  Whatever b holds when gmrf_bt_posterior runs, the mean is that of b as the factorisation read it.  Any other way
+ * to a factor (ranges, adopt, import), a set_eager change, another b or b == NULL leaves no y: the forward sweep runs as before.
+ * set_eager bit 19 switches the forward solve inside the factorisation off. */
+gmrf_status gmrf_bt_set_factor_rhs(gmrf_handle* h, const double* b);
+
 /* The N(0,1) draws gmrf_bt_sample would use (for tests and for callers that need z). */
 gmrf_status gmrf_bt_normals(gmrf_handle* h, uint64_t seed, int64_t first_id, int64_t k,
                             double* z, int64_t ld);
@@ -408,7 +417,8 @@ gmrf_status gmrf_bt_set_profiling(gmrf_handle* h, int32_t level);
  * keeps scatter_block (S += D_i) as a launch of its own behind S = -C C^T instead of zero + scatter inside the spmm_bxt_tiles launch and an
  * accumulating product (comparison; same bits); bit 18: a batch's gmrf_bt_posterior is gmrf_bt_solve + gmrf_bt_sample (the mean's
  * backward sweep a pass of its own) instead of the fused pass that sweeps the mean as the tail row of the samples' GEMMs
- * (comparison; the samples' L^-T z rows are the same bits, the mean agrees to rounding).
+ * (comparison; the samples' L^-T z rows are the same bits, the mean agrees to rounding); bit 19: factorisations do not solve for the
+ * right-hand side of gmrf_bt_set_factor_rhs (comparison: the posterior's forward sweep runs).
  * (Bits 6, 9, 10, 11, 14 selected comparison routes that lost twice -- left-looking panels, in-panel updates on the GEMM kernel,
  * rank-64 panel steps of batches, 128-column panels, potrf_panel256 -- and were removed with them in round 5; they are ignored.) */
 gmrf_status gmrf_bt_set_eager(gmrf_handle* h, int32_t eager);
@@ -569,6 +579,9 @@ gmrf_status gmrf_test_persist_stamps(double* out, int32_t n);
 /* block ranges of this handle that were repeated with the launch-per-step form because a bounded wait inside a persistent
  * launch gave up (GMRF_PERSIST_SPIN_MS: default 2000 for one problem, 200 for batches); also in gmrf_stats.persist_aborts */
 gmrf_status gmrf_test_persist_aborts(gmrf_handle* h, int32_t* n);
+/* *state = 1 if the current factor holds y = L^-1 b for the registered b (gmrf_bt_set_factor_rhs), else 0; y_out (optional, host,
+ * n x B column-major) then receives y */
+gmrf_status gmrf_test_factor_fwd(gmrf_handle* h, int32_t* state, double* y_out);
 /* The per-device budget of CUs for persistent launches, host only (no GPU needed): `n` handles ask for demands[i] CUs one after
  * the other on a device of `cus` CUs; granted[i] = 1 if the claim fitted beside the earlier ones, 0 if it was refused (the
  * handle would take the launch-per-step routes up front instead of meeting a bounded wait). */

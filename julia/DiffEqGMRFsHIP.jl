@@ -255,6 +255,11 @@ posterior!(F::TridiagonalCholeskyFactor, b::Ptr{Float64}, mean::Ptr{Float64}, sa
         (Ptr{Cvoid}, Ptr{Float64}, UInt64, Int64, Int64, Ptr{Float64}, Ptr{Float64}, Int64),
         F.handle, b, seed, first_id, k, mean, samples, ld))
 
+"Register the right-hand side of a batch's later `posterior!` calls (a DEVICE pointer to n x B doubles, read at factor time):
+later factorisations solve L y = b on the way, and `posterior!` with this same pointer skips its forward sweep.  C_NULL clears it."
+set_factor_rhs!(F::TridiagonalCholeskyFactor, b::Ptr{Float64}) =
+    check(ccall((:gmrf_bt_set_factor_rhs, libgmrf), Int32, (Ptr{Cvoid}, Ptr{Float64}), F.handle, b))
+
 "The N(0,1) draws `sample` uses: Philox4x32-10 keyed by (seed, sample id, dof) -- independent of the GPU count."
 function normals(F::TridiagonalCholeskyFactor, k::Integer; seed::Integer = 0x5EED, first_id::Integer = 0)
     out = Matrix{Float64}(undef, F.N, k * F.batch)

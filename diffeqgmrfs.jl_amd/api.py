@@ -216,6 +216,65 @@ class PosteriorAssembler:
                                                   _cabi.ptr(out)))
         return out
 
+    # -- a batch of problems on the same patterns: arrays (B, ...) C-contiguous, NumPy or torch CUDA in, the same kind out
+    @staticmethod
+    def _mat(v, B, count, name):
+        if v is None:
+            return None
+        v = v.contiguous() if _is_torch(v) else np.ascontiguousarray(v, dtype=np.float64)
+        if _is_torch(v):
+            import torch
+            if v.dtype != torch.float64:
+                raise TypeError("float64 required")
+        if v.ndim != 2 or v.shape[0] != B or v.shape[1] != count:
+            raise ValueError(f"{name}: expected shape ({B}, {count})")
+        return v
+
+    def _q(self, q_values, B):
+        """(values, stride): one (nnz_q,) array shared by the batch (stride 0) or (B, nnz_q) per problem."""
+        if getattr(q_values, "ndim", 1) == 2:
+            return self._mat(q_values, B, self.nnz_q, "q_values"), self.nnz_q
+        return self._vec(q_values, self.nnz_q, "q_values"), 0
+
+    @staticmethod
+    def _like2(ref, shape):
+        if _is_torch(ref):
+            import torch
+            return torch.empty(shape, dtype=torch.float64, device=ref.device)
+        return np.empty(shape, dtype=np.float64)
+
+    def precision_batch(self, q_values, j_values, noise: float):
+        """j_values (B, nnz_j) -> (B, nnz_out): row p is `precision` of problem p, bit for bit.  q_values: (nnz_q,) shared or
+        (B, nnz_q) per problem."""
+        B = j_values.shape[0]
+        j = self._mat(j_values, B, self.nnz_j, "j_values")
+        q, stride = self._q(q_values, B)
+        out = self._like2(j, (B, self.nnz_out))
+        _cabi.check(_cabi.load().gmrf_assemble_precision_batch(self._h, B, _cabi.ptr(q), stride, _cabi.ptr(j), float(noise),
+                                                               _cabi.ptr(out)))
+        return out
+
+    def rhs_batch(self, base, j_values, x, obs_diff, noise: float):
+        """(B, n) right-hand sides: row p is `rhs` of problem p, bit for bit (base / obs_diff may be None)."""
+        B = j_values.shape[0]
+        j = self._mat(j_values, B, self.nnz_j, "j_values")
+        xv, b, o = self._mat(x, B, self.n, "x"), self._mat(base, B, self.n, "base"), self._mat(obs_diff, B, self.m, "obs_diff")
+        out = self._like2(j, (B, self.n))
+        _cabi.check(_cabi.load().gmrf_assemble_rhs_batch(self._h, B, _cabi.ptr(b), _cabi.ptr(j), _cabi.ptr(xv), _cabi.ptr(o),
+                                                         float(noise), _cabi.ptr(out)))
+        return out
+
+    def objective_batch(self, q_values, x_prior, x, obs_diff, noise: float):
+        """(B,) objectives (x_prior - x)' Q (x_prior - x) + noise |obs_diff|^2 (scripts/solve_burger.jl:157): a fixed-shape
+        sum, the same bits on every call and whatever batch a problem sits in."""
+        B = x.shape[0]
+        xv, xp, o = self._mat(x, B, self.n, "x"), self._mat(x_prior, B, self.n, "x_prior"), self._mat(obs_diff, B, self.m, "obs_diff")
+        q, stride = self._q(q_values, B)
+        out = self._like2(xv, (B,))
+        _cabi.check(_cabi.load().gmrf_assemble_objective_batch(self._h, B, _cabi.ptr(q), stride, _cabi.ptr(xp), _cabi.ptr(xv),
+                                                               _cabi.ptr(o), float(noise), _cabi.ptr(out)))
+        return out
+
 
 class DarcyP1Assembler:
     """Darcy stiffness matrix and load vector on the device (first piece):
@@ -317,6 +376,23 @@ class BurgersP1Tangent:
         _cabi.check(_cabi.load().gmrf_burgers_p1_tangent(self._h, _cabi.ptr(wv), _cabi.ptr(vals), _cabi.ptr(f)))
         return vals, f
 
+    def tangent_batch(self, W):
+        """W: (B, nt ns) linearisation points -> (J values (B, nnz), residuals (B, rows)), same kind as the input; row p is
+        `tangent(W[p])`, bit for bit."""
+        if _is_torch(W):
+            import torch
+            wv = W.contiguous()
+            if wv.dtype != torch.float64:
+                raise TypeError("float64 required")
+        else:
+            wv = np.ascontiguousarray(W, dtype=np.float64)
+        if wv.ndim != 2 or wv.shape[1] != self.n:
+            raise ValueError(f"W must have shape (B, {self.n})")
+        B = wv.shape[0]
+        vals, f = PosteriorAssembler._like2(wv, (B, self.nnz)), PosteriorAssembler._like2(wv, (B, self.rows))
+        _cabi.check(_cabi.load().gmrf_burgers_p1_tangent_batch(self._h, B, _cabi.ptr(wv), _cabi.ptr(vals), _cabi.ptr(f)))
+        return vals, f
+
 
 class ShallowWaterP1:
     """Element kernels of the linear shallow-water SPDE on the device (third piece):
@@ -406,6 +482,60 @@ def gn_step(F: "TridiagonalCholeskyFactor", asm: PosteriorAssembler, q_values, Q
     rhs = asm.rhs(Qx_prior, j_values, x, obs_diff, noise)
     F.refactor(a_vals)
     return ldiv(F, rhs)
+
+
+class GaussNewtonBatch:
+    """The Burgers data-set loop (scripts/burgers/solve_burgers_gmrf-fem.jl:154-233, loop body scripts/solve_burger.jl:143-180)
+    for `F.batch` problems on one mesh in lock step, resident on the device (gmrf_gn_run): per iteration
+    tangent -> A = Q + noise J'J, rhs -> refactor -> solve -> objective -> stop rule, and one status word crosses the bus.
+
+    `F` (reference order, factored once on `asm.pattern`), `asm` and `tangent` must have been created on the same device with
+    the same `stream` argument.  A problem is active while |last - cur| / |cur| > rtol and steps < max_steps; one that has
+    stopped is frozen and stays in the batch."""
+
+    def __init__(self, F: "TridiagonalCholeskyFactor", asm: PosteriorAssembler, tangent: BurgersP1Tangent):
+        self.F, self.asm, self.tangent = F, asm, tangent          # (kept alive: the library holds their handles)
+        self._h = C.c_void_p()
+        _cabi.check(_cabi.load().gmrf_gn_create(F._h, asm._h, tangent._h, C.byref(self._h)))
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            _cabi.load().gmrf_gn_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def run(self, q_values, Qx_prior, x_prior, x0, y=None, noise: float = 1e8, rtol: float = 1e-4, max_steps: int = 20):
+        """q_values (nnz_q,) shared or (B, nnz_q); Qx_prior, x_prior, x0 (B, n); y (B, m) or None (zero observations).  NumPy
+        arrays or torch CUDA tensors.  Returns (x (B, n), same kind as x0; steps (B,) int32 NumPy; objective history
+        (B, max_steps + 1) NumPy, slot 0 at the start point, NaN in the slots no step reached).  The defaults are the
+        reference's (scripts/solve_burger.jl:140, :171)."""
+        B, a = self.F.batch, self.asm
+        if x0.ndim != 2 or x0.shape[0] != B:
+            raise GmrfError(_cabi.ERR_BAD_SHAPE, f"x0: expected ({B}, {a.n}), the batch of the handle")
+        q, stride = a._q(q_values, B)
+        qx, xp, yv = a._mat(Qx_prior, B, a.n, "Qx_prior"), a._mat(x_prior, B, a.n, "x_prior"), a._mat(y, B, a.m, "y")
+        x = a._mat(x0, B, a.n, "x0")
+        x = x.clone() if _is_torch(x) else x.copy()
+        steps = np.zeros(B, dtype=np.int32)
+        hist = np.full((B, int(max_steps) + 1), np.nan)
+        info = C.c_int32(0)
+        st = _cabi.load().gmrf_gn_run(self._h, _cabi.ptr(q), stride, _cabi.ptr(qx), _cabi.ptr(xp), _cabi.ptr(x), _cabi.ptr(yv),
+                                      float(noise), float(rtol), int(max_steps), _cabi.ptr(steps), _cabi.ptr(hist), C.byref(info))
+        self.last = (x, steps, hist)                  # (after NotPositiveDefinite: the last complete iterates)
+        _cabi.check(st, info.value)
+        return x, steps, hist
+
+    def finalize(self):
+        """Tangent at the final x, assemble, re-factor: `F` then holds the factor of Q + noise J(x)' J(x) of every problem
+        (x_final of solve_burgers_gmrf-fem.jl:184-193) for posterior_batch / sample_batch / marginal_var / logdet."""
+        info = C.c_int32(0)
+        _cabi.check(_cabi.load().gmrf_gn_finalize(self._h, C.byref(info)), info.value)
+        return self.F
 
 
 class ConditionedGMRF:

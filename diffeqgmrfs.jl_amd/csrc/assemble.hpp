@@ -50,4 +50,52 @@ __global__ __launch_bounds__(256) void assemble_j_apply(const int64_t* __restric
     out[k] = (add ? add[k] : 0.0) + s;
 }
 
+// ---- a batch of problems on one pair of patterns (problem-major arrays; blockIdx.y is the problem) -------------------------
+// The index lists are shared, the values are per problem: jv[B][nnz_j], out[B][nnz_out]; q with a stride of 0 (one prior for
+// all) or nnz_q.  Each entry is summed exactly as in the one-problem kernels above -- the same fma chain in the same order,
+// the same final expression -- so problem p of a batch gets the bits of the one-problem call on its values.
+__global__ __launch_bounds__(256) void assemble_precision_batch(const int64_t* __restrict__ pptr, const int32_t* __restrict__ pa,
+                                                                const int32_t* __restrict__ pb, const int64_t* __restrict__ qmap,
+                                                                const double* __restrict__ q, int64_t q_stride,
+                                                                const double* __restrict__ jv, int64_t nnz_j, double noise,
+                                                                int64_t nnz_out, double* __restrict__ out) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= nnz_out) return;
+    const int64_t pr = blockIdx.y;
+    q += pr * q_stride; jv += pr * nnz_j; out += pr * nnz_out;
+    double s = 0.0;
+    for (int64_t p = pptr[e]; p < pptr[e + 1]; ++p) s = fma(jv[pa[p]], jv[pb[p]], s);
+    const int64_t m = qmap[e];
+    out[e] = (m >= 0 ? q[m] : 0.0) + noise * s;
+}
+
+__global__ __launch_bounds__(256) void assemble_jt_apply_batch(const int64_t* __restrict__ cptr, const int32_t* __restrict__ row,
+                                                               const int32_t* __restrict__ src, const double* __restrict__ jv,
+                                                               int64_t nnz_j, const double* __restrict__ v, int64_t m,
+                                                               const double* __restrict__ base, double noise, int64_t n,
+                                                               double* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int64_t pr = blockIdx.y;
+    jv += pr * nnz_j; v += pr * m; out += pr * n;
+    if (base) base += pr * n;
+    double s = 0.0;
+    for (int64_t p = cptr[i]; p < cptr[i + 1]; ++p) s = fma(jv[src[p]], v[row[p]], s);
+    out[i] = (base ? base[i] : 0.0) + noise * s;
+}
+
+__global__ __launch_bounds__(256) void assemble_j_apply_batch(const int64_t* __restrict__ rptr, const int32_t* __restrict__ col,
+                                                              const double* __restrict__ jv, int64_t nnz_j,
+                                                              const double* __restrict__ x, int64_t n,
+                                                              const double* __restrict__ add, int64_t m, double* __restrict__ out) {
+    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= m) return;
+    const int64_t pr = blockIdx.y;
+    jv += pr * nnz_j; x += pr * n; out += pr * m;
+    if (add) add += pr * m;
+    double s = 0.0;
+    for (int64_t p = rptr[k]; p < rptr[k + 1]; ++p) s = fma(jv[p], x[col[p]], s);
+    out[k] = (add ? add[k] : 0.0) + s;
+}
+
 }  // namespace gmrf

@@ -199,8 +199,7 @@ __host__ __device__ inline void burgers_p1_cell(double h, double w0, double w1, 
     }
 }
 
-__global__ __launch_bounds__(256) void burgers_p1_rows(BurgersP1Args a) {
-    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+__device__ __forceinline__ void burgers_p1_row(const BurgersP1Args& a, const int64_t gid) {
     const int64_t rows = (int64_t)(a.nt - 1) * a.ns;
     if (gid >= rows) return;
     const int t = (int)(gid / a.ns) + 1, i = (int)(gid % a.ns);   // slice t (0-based), rows belong to slices 1 .. nt-1
@@ -235,6 +234,18 @@ __global__ __launch_bounds__(256) void burgers_p1_rows(BurgersP1Args a) {
     double acc = 0.0;
     for (int e = 0; e < 6; ++e) acc += sv[e] * xv[e];
     a.f[gid] = acc + a.dt * v_i;
+}
+
+__global__ __launch_bounds__(256) void burgers_p1_rows(BurgersP1Args a) {
+    burgers_p1_row(a, (int64_t)blockIdx.x * blockDim.x + threadIdx.x);
+}
+
+// A batch of linearisation points on one mesh, problem-major: w[B][nt ns] -> vals[B][nnz], f[B][rows]; blockIdx.y is the problem.
+// The row function is the one-problem kernel's: the same arithmetic in the same order, so the same bits per problem.
+__global__ __launch_bounds__(256) void burgers_p1_rows_batch(BurgersP1Args a, int64_t nnz) {
+    const int64_t p = blockIdx.y, rows = (int64_t)(a.nt - 1) * a.ns;
+    a.w += p * ((int64_t)a.nt * a.ns); a.vals += p * nnz; a.f += p * rows;
+    burgers_p1_row(a, (int64_t)blockIdx.x * blockDim.x + threadIdx.x);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -273,8 +284,7 @@ __host__ __device__ inline int64_t burgers_p2_row_offset(int64_t ns, int64_t t1,
     return (t1 * (ns / 2) + i / 2) * 16 + ((i & 1) ? 10 : 0);
 }
 
-__global__ __launch_bounds__(256) void burgers_p2_rows(BurgersP1Args a) {
-    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+__device__ __forceinline__ void burgers_p2_row(const BurgersP1Args& a, const int64_t gid) {
     const int64_t rows = (int64_t)(a.nt - 1) * a.ns;
     if (gid >= rows) return;
     const int ns = a.ns, nc = ns / 2;
@@ -327,6 +337,16 @@ __global__ __launch_bounds__(256) void burgers_p2_rows(BurgersP1Args a) {
     for (int k = 0; k < cnt; ++k) acc += prev_terms[k];
     for (int k = 0; k < cnt; ++k) acc += cur_terms[k];
     a.f[gid] = acc + a.dt * v_i;
+}
+
+__global__ __launch_bounds__(256) void burgers_p2_rows(BurgersP1Args a) {
+    burgers_p2_row(a, (int64_t)blockIdx.x * blockDim.x + threadIdx.x);
+}
+
+__global__ __launch_bounds__(256) void burgers_p2_rows_batch(BurgersP1Args a, int64_t nnz) {
+    const int64_t p = blockIdx.y, rows = (int64_t)(a.nt - 1) * a.ns;
+    a.w += p * ((int64_t)a.nt * a.ns); a.vals += p * nnz; a.f += p * rows;
+    burgers_p2_row(a, (int64_t)blockIdx.x * blockDim.x + threadIdx.x);
 }
 
 }  // namespace gmrf

@@ -41,6 +41,7 @@
 #include "swe_assemble.hpp"
 #include "fem_assemble_p2.hpp"
 #include "selinv.hpp"
+#include "gauss_newton.hpp"
 
 using namespace gmrf;
 
@@ -3703,6 +3704,13 @@ struct gmrf_assembler {
     int64_t *d_pptr = nullptr, *d_qmap = nullptr, *d_jt_ptr = nullptr, *d_j_rptr = nullptr;
     int32_t *d_pa = nullptr, *d_pb = nullptr, *d_jt_row = nullptr, *d_jt_src = nullptr, *d_j_col = nullptr;
     double *d_q = nullptr, *d_jv = nullptr, *d_vn = nullptr, *d_vm = nullptr, *d_vn2 = nullptr, *d_out = nullptr;   // staging for host callers
+    // the batch calls: Q's own pattern (0-based; symmetric, so its CSC arrays are read by rows), uploaded by the first objective
+    std::vector<int64_t> q_ptr;
+    std::vector<int32_t> q_row;
+    int64_t* d_q_ptr = nullptr;
+    int32_t* d_q_row = nullptr;
+    double *d_bstage = nullptr, *d_bpart = nullptr;        // staging of host arrays / partial sums of the batch calls
+    int64_t bstage_cap = 0, bpart_cap = 0;
 };
 
 gmrf_status gmrf_assemble_create(int32_t device, void* stream, int64_t n, const int64_t* q_colptr, const int64_t* q_rowval,
@@ -3765,6 +3773,11 @@ gmrf_status gmrf_assemble_create(int32_t device, void* stream, int64_t n, const 
     }
     as->nnz_out = (int64_t)as->rowval.size();
     as->n_pairs = (int64_t)pa.size();
+    if (n < ((int64_t)1 << 31)) {
+        as->q_ptr.resize((size_t)n + 1); as->q_row.resize((size_t)nnz_q);
+        for (int64_t j = 0; j <= n; ++j) as->q_ptr[(size_t)j] = q_colptr[j] - b;
+        for (int64_t e = 0; e < nnz_q; ++e) as->q_row[(size_t)e] = (int32_t)(q_rowval[e] - b);
+    }
     if (device >= 0) {
         int count = 0;
         if (hipGetDeviceCount(&count) != hipSuccess || count <= 0 || device >= count) {
@@ -3801,6 +3814,7 @@ gmrf_status gmrf_assemble_destroy(gmrf_assembler* as) {
         free_dev(as->d_pptr); free_dev(as->d_qmap); free_dev(as->d_pa); free_dev(as->d_pb);
         free_dev(as->d_jt_ptr); free_dev(as->d_jt_row); free_dev(as->d_jt_src); free_dev(as->d_j_rptr); free_dev(as->d_j_col);
         free_dev(as->d_q); free_dev(as->d_jv); free_dev(as->d_vn); free_dev(as->d_vm); free_dev(as->d_vn2); free_dev(as->d_out);
+        free_dev(as->d_q_ptr); free_dev(as->d_q_row); free_dev(as->d_bstage); free_dev(as->d_bpart);
         if (as->own_stream) (void)hipStreamDestroy(as->stream);
     }
     delete as;
@@ -4075,6 +4089,8 @@ struct gmrf_burgers_p1 {
     int order = 1;                      // 1: P1 line (6 entries per row), 2: quadratic line (10 / 6 entries per row)
     double dt = 0.0, nu = 0.0;
     double *d_w = nullptr, *d_vals = nullptr, *d_f = nullptr;       // staging for host callers
+    double* d_bstage = nullptr;         // ... of gmrf_burgers_p1_tangent_batch
+    int64_t bstage_cap = 0;
 };
 
 static gmrf_status burgers_line_create(int32_t device, void* stream, int64_t ns, int64_t nt, double dt, double nu, int order,
@@ -4113,7 +4129,7 @@ gmrf_status gmrf_burgers_p1_destroy(gmrf_burgers_p1* b) {
     if (b->device >= 0) {
         (void)hipSetDevice(b->device);
         if (b->stream) (void)hipStreamSynchronize(b->stream);
-        free_dev(b->d_w); free_dev(b->d_vals); free_dev(b->d_f);
+        free_dev(b->d_w); free_dev(b->d_vals); free_dev(b->d_f); free_dev(b->d_bstage);
         if (b->own_stream) (void)hipStreamDestroy(b->stream);
     }
     delete b;
@@ -4182,6 +4198,391 @@ gmrf_status gmrf_burgers_p1_tangent(gmrf_burgers_p1* b, const double* w, double*
     if (!f_dev) HIPCHK(hipMemcpyAsync(f_out, b->d_f, sizeof(double) * b->rows, hipMemcpyDeviceToHost, b->stream));
     HIPCHK(hipStreamSynchronize(b->stream));
     return GMRF_OK;
+}
+
+// --------------------------------------------------------------------------------- batch forms of the Gauss-Newton glue
+// Problem-major arrays ([batch][...]); host or device pointers like the one-problem calls.  Host arrays pass through one staging
+// buffer per handle.
+struct StageItem { const double* user; int64_t count; bool out; double* dev; };
+
+static gmrf_status stage_items(hipStream_t st, double** buf, int64_t* cap, StageItem* it, int nit) {
+    int64_t need = 0;
+    for (int i = 0; i < nit; ++i) if (it[i].user && !is_device_ptr(it[i].user)) need += it[i].count;
+    if (need > *cap) {
+        HIPCHK(hipStreamSynchronize(st));
+        free_dev(*buf); *buf = nullptr; *cap = 0;
+        HIPCHK(hipMalloc(buf, sizeof(double) * (size_t)need));
+        *cap = need;
+    }
+    int64_t off = 0;
+    for (int i = 0; i < nit; ++i) {
+        if (!it[i].user) { it[i].dev = nullptr; continue; }
+        if (is_device_ptr(it[i].user)) { it[i].dev = const_cast<double*>(it[i].user); continue; }
+        it[i].dev = *buf + off; off += it[i].count;
+        if (!it[i].out) HIPCHK(hipMemcpyAsync(it[i].dev, it[i].user, sizeof(double) * it[i].count, hipMemcpyHostToDevice, st));
+    }
+    return GMRF_OK;
+}
+
+static gmrf_status unstage_items(hipStream_t st, const StageItem* it, int nit) {
+    for (int i = 0; i < nit; ++i)
+        if (it[i].out && it[i].user && it[i].dev != it[i].user)
+            HIPCHK(hipMemcpyAsync(const_cast<double*>(it[i].user), it[i].dev, sizeof(double) * it[i].count, hipMemcpyDeviceToHost, st));
+    return GMRF_OK;
+}
+
+static bool batch_ok(int64_t batch) { return batch >= 1 && batch <= 4096; }
+
+static gmrf_status launch_tangent_batch(const gmrf_burgers_p1* b, hipStream_t st, int64_t batch, const double* d_w, double* d_vals,
+                                        double* d_f) {
+    BurgersP1Args a;
+    a.ns = (int)b->ns; a.nt = (int)b->nt; a.dt = b->dt; a.nu = b->nu; a.w = d_w; a.vals = d_vals; a.f = d_f;
+    const dim3 grid((unsigned)((b->rows + 255) / 256), (unsigned)batch);
+    if (b->order == 2) hipLaunchKernelGGL(burgers_p2_rows_batch, grid, dim3(256), 0, st, a, b->nnz);
+    else hipLaunchKernelGGL(burgers_p1_rows_batch, grid, dim3(256), 0, st, a, b->nnz);
+    HIPCHK(hipGetLastError());
+    return GMRF_OK;
+}
+
+gmrf_status gmrf_burgers_p1_tangent_batch(gmrf_burgers_p1* b, int64_t batch, const double* w, double* vals_out, double* f_out) {
+    if (!b || !w || !vals_out || !f_out || !batch_ok(batch)) return bad_shape("bad Burgers tangent arguments (batch in [1, 4096])");
+    if (b->device < 0) { g_last_error = "pattern-only Burgers assembler (created with device -1)"; return GMRF_ERR_NO_DEVICE; }
+    HIPCHK(hipSetDevice(b->device));
+    StageItem it[3] = {{w, batch * b->ns * b->nt, false, nullptr}, {vals_out, batch * b->nnz, true, nullptr}, {f_out, batch * b->rows, true, nullptr}};
+    GCHK(stage_items(b->stream, &b->d_bstage, &b->bstage_cap, it, 3));
+    GCHK(launch_tangent_batch(b, b->stream, batch, it[0].dev, it[1].dev, it[2].dev));
+    GCHK(unstage_items(b->stream, it, 3));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    return GMRF_OK;
+}
+
+static gmrf_status launch_precision_batch(const gmrf_assembler* as, hipStream_t st, int64_t batch, const double* d_q, int64_t q_stride,
+                                          const double* d_jv, double noise, double* d_out) {
+    hipLaunchKernelGGL(assemble_precision_batch, dim3((unsigned)((as->nnz_out + 255) / 256), (unsigned)batch), dim3(256), 0, st,
+                       as->d_pptr, as->d_pa, as->d_pb, as->d_qmap, d_q, q_stride, d_jv, as->nnz_j, noise, as->nnz_out, d_out);
+    HIPCHK(hipGetLastError());
+    return GMRF_OK;
+}
+
+// d_v: [batch][m] work array (J x + obs_diff)
+static gmrf_status launch_rhs_batch(const gmrf_assembler* as, hipStream_t st, int64_t batch, const double* d_base, const double* d_jv,
+                                    const double* d_x, const double* d_add, double noise, double* d_v, double* d_out) {
+    hipLaunchKernelGGL(assemble_j_apply_batch, dim3((unsigned)((as->m + 255) / 256), (unsigned)batch), dim3(256), 0, st, as->d_j_rptr,
+                       as->d_j_col, d_jv, as->nnz_j, d_x, as->n, d_add, as->m, d_v);
+    hipLaunchKernelGGL(assemble_jt_apply_batch, dim3((unsigned)((as->n + 255) / 256), (unsigned)batch), dim3(256), 0, st, as->d_jt_ptr,
+                       as->d_jt_row, as->d_jt_src, d_jv, as->nnz_j, d_v, as->m, d_base, noise, as->n, d_out);
+    HIPCHK(hipGetLastError());
+    return GMRF_OK;
+}
+
+// chunks of the objective's fixed partition: a function of n and m only
+static int64_t objective_chunks(const gmrf_assembler* as) {
+    return std::min<int64_t>(1024, std::max<int64_t>(1, (std::max(as->n, as->m) + 2047) / 2048));
+}
+
+static gmrf_status objective_ready(gmrf_assembler* as) {
+    if (as->d_q_ptr) return GMRF_OK;
+    if (as->q_ptr.empty()) return bad_shape("the objective needs n < 2^31");
+    HIPCHK(hipMalloc(&as->d_q_ptr, sizeof(int64_t) * as->q_ptr.size()));
+    HIPCHK(hipMalloc(&as->d_q_row, sizeof(int32_t) * std::max<size_t>(as->q_row.size(), 1)));
+    HIPCHK(hipMemcpyAsync(as->d_q_ptr, as->q_ptr.data(), sizeof(int64_t) * as->q_ptr.size(), hipMemcpyHostToDevice, as->stream));
+    if (!as->q_row.empty())
+        HIPCHK(hipMemcpyAsync(as->d_q_row, as->q_row.data(), sizeof(int32_t) * as->q_row.size(), hipMemcpyHostToDevice, as->stream));
+    HIPCHK(hipStreamSynchronize(as->stream));
+    return GMRF_OK;
+}
+
+// d_part: [batch][objective_chunks] work array
+static gmrf_status launch_objective_batch(const gmrf_assembler* as, hipStream_t st, int64_t batch, const double* d_q, int64_t q_stride,
+                                          const double* d_xp, const double* d_x, const double* d_o, double noise, double* d_part,
+                                          double* d_obj) {
+    const int64_t nch = objective_chunks(as), len_n = (as->n + nch - 1) / nch, len_m = (as->m + nch - 1) / nch;
+    hipLaunchKernelGGL(gn_objective_part, dim3((unsigned)nch, (unsigned)batch), dim3(256), 0, st, as->d_q_ptr, as->d_q_row, d_q, q_stride,
+                       d_xp, d_x, as->n, d_o, as->m, noise, len_n, len_m, d_part);
+    hipLaunchKernelGGL(pattern_dot_sum, dim3(1, (unsigned)batch), dim3(256), 0, st, d_part, nch, (int64_t)1, d_obj);
+    HIPCHK(hipGetLastError());
+    return GMRF_OK;
+}
+
+static gmrf_status q_stride_ok(const gmrf_assembler* as, int64_t q_stride) {
+    if (q_stride != 0 && q_stride != as->nnz_q) return bad_shape("q_stride must be 0 (one Q for all problems) or nnz(Q)");
+    return GMRF_OK;
+}
+
+gmrf_status gmrf_assemble_precision_batch(gmrf_assembler* as, int64_t batch, const double* q_nzval, int64_t q_stride,
+                                          const double* j_vals, double noise, double* out_nzval) {
+    if (!as || !q_nzval || !j_vals || !out_nzval || !batch_ok(batch)) return bad_shape("null pointer or batch outside [1, 4096]");
+    GCHK(q_stride_ok(as, q_stride));
+    GCHK(as_numeric_ready(as));
+    StageItem it[3] = {{q_nzval, q_stride ? batch * as->nnz_q : as->nnz_q, false, nullptr}, {j_vals, batch * as->nnz_j, false, nullptr},
+                       {out_nzval, batch * as->nnz_out, true, nullptr}};
+    GCHK(stage_items(as->stream, &as->d_bstage, &as->bstage_cap, it, 3));
+    GCHK(launch_precision_batch(as, as->stream, batch, it[0].dev, q_stride, it[1].dev, noise, it[2].dev));
+    GCHK(unstage_items(as->stream, it, 3));
+    HIPCHK(hipStreamSynchronize(as->stream));
+    return GMRF_OK;
+}
+
+static gmrf_status as_part_buffer(gmrf_assembler* as, int64_t elems) {
+    if (as->d_bpart && as->bpart_cap >= elems) return GMRF_OK;
+    HIPCHK(hipStreamSynchronize(as->stream));
+    free_dev(as->d_bpart); as->d_bpart = nullptr; as->bpart_cap = 0;
+    HIPCHK(hipMalloc(&as->d_bpart, sizeof(double) * (size_t)elems));
+    as->bpart_cap = elems;
+    return GMRF_OK;
+}
+
+gmrf_status gmrf_assemble_rhs_batch(gmrf_assembler* as, int64_t batch, const double* base, const double* j_vals, const double* x,
+                                    const double* obs_diff, double noise, double* out) {
+    if (!as || !j_vals || !x || !out || !batch_ok(batch)) return bad_shape("null pointer or batch outside [1, 4096]");
+    GCHK(as_numeric_ready(as));
+    StageItem it[5] = {{base, batch * as->n, false, nullptr}, {j_vals, batch * as->nnz_j, false, nullptr}, {x, batch * as->n, false, nullptr},
+                       {obs_diff, batch * as->m, false, nullptr}, {out, batch * as->n, true, nullptr}};
+    GCHK(stage_items(as->stream, &as->d_bstage, &as->bstage_cap, it, 5));
+    GCHK(as_part_buffer(as, batch * as->m));
+    GCHK(launch_rhs_batch(as, as->stream, batch, it[0].dev, it[1].dev, it[2].dev, it[3].dev, noise, as->d_bpart, it[4].dev));
+    GCHK(unstage_items(as->stream, it, 5));
+    HIPCHK(hipStreamSynchronize(as->stream));
+    return GMRF_OK;
+}
+
+gmrf_status gmrf_assemble_objective_batch(gmrf_assembler* as, int64_t batch, const double* q_nzval, int64_t q_stride,
+                                          const double* x_prior, const double* x, const double* obs_diff, double noise,
+                                          double* obj_out) {
+    if (!as || !q_nzval || !x_prior || !x || !obs_diff || !obj_out || !batch_ok(batch)) return bad_shape("null pointer or batch outside [1, 4096]");
+    GCHK(q_stride_ok(as, q_stride));
+    GCHK(as_numeric_ready(as));
+    GCHK(objective_ready(as));
+    StageItem it[5] = {{q_nzval, q_stride ? batch * as->nnz_q : as->nnz_q, false, nullptr}, {x_prior, batch * as->n, false, nullptr},
+                       {x, batch * as->n, false, nullptr}, {obs_diff, batch * as->m, false, nullptr}, {obj_out, batch, true, nullptr}};
+    GCHK(stage_items(as->stream, &as->d_bstage, &as->bstage_cap, it, 5));
+    GCHK(as_part_buffer(as, batch * objective_chunks(as)));
+    GCHK(launch_objective_batch(as, as->stream, batch, it[0].dev, q_stride, it[1].dev, it[2].dev, it[3].dev, noise, as->d_bpart, it[4].dev));
+    GCHK(unstage_items(as->stream, it, 5));
+    HIPCHK(hipStreamSynchronize(as->stream));
+    return GMRF_OK;
+}
+
+// --------------------------------------------------------------------------------- the batched Gauss-Newton driver
+// B = batch of the handle Burgers problems on one mesh in lock step (scripts/solve_burger.jl:151-180 per problem).  One iteration
+// on the handle's stream:
+//     tangent(x) -> A = Q + noise J'J, rhs -> gmrf_bt_refactor_values -> solve -> tangent(candidate) -> objective -> stop rule
+// The rhs buffer is registered as the factor's right-hand side (gmrf_bt_set_factor_rhs) for the run: where that route
+// qualifies the factorisation leaves y = L^-1 rhs and the solve is the backward sweep alone.  Problems that have stopped stay in
+// the batch, frozen: their x does not change, so they are re-factored with the same values.
+struct gmrf_gn {
+    gmrf_handle* h = nullptr;
+    gmrf_assembler* as = nullptr;
+    gmrf_burgers_p1* b = nullptr;
+    int64_t B = 0;                       // what the buffers below are sized for
+    int32_t hist_steps = -1;
+    double *d_x = nullptr, *d_xn = nullptr, *d_od = nullptr, *d_on = nullptr, *d_f = nullptr, *d_v = nullptr, *d_jv = nullptr;
+    double *d_a = nullptr, *d_rhs = nullptr, *d_q = nullptr, *d_part = nullptr, *d_obj = nullptr;
+    double *d_in = nullptr;              // staged qx_prior, x_prior, y: [3][B][max(n, m)]
+    double *d_last = nullptr, *d_cur = nullptr, *d_hist = nullptr;
+    int32_t *d_steps = nullptr, *d_active = nullptr, *d_take = nullptr;
+    unsigned* h_active = nullptr;        // mapped host word the stop rule writes
+    unsigned* dev_active = nullptr;      // ... as the device addresses it
+    int64_t q_stride = 0;
+    double noise = 0.0;
+    bool have_x = false;                 // a run has left its iterate in d_x (gmrf_gn_finalize)
+    int device = 0;                      // (copies: gmrf_gn_destroy does not reach into the handle)
+    hipStream_t stream = nullptr;
+    int32_t iterations = 0, fwd_iterations = 0;      // of the last run: iterations, and those whose solve was the backward sweep alone
+};
+
+static void gn_free(gmrf_gn* g) {
+    for (double** p : {&g->d_x, &g->d_xn, &g->d_od, &g->d_on, &g->d_f, &g->d_v, &g->d_jv, &g->d_a, &g->d_rhs, &g->d_q, &g->d_part, &g->d_obj,
+                       &g->d_in, &g->d_last, &g->d_cur, &g->d_hist}) { free_dev(*p); *p = nullptr; }
+    free_dev(g->d_steps); free_dev(g->d_active); free_dev(g->d_take);
+    g->d_steps = g->d_active = g->d_take = nullptr;
+    g->B = 0; g->hist_steps = -1; g->have_x = false;
+}
+
+static gmrf_status gn_bound_ok(const gmrf_gn* g) {
+    const gmrf_handle* h = g->h;
+    if (h->order == GMRF_ORDER_TWISTED) return bad_shape("the Gauss-Newton driver takes a reference-order handle");
+    if (g->as->device != h->device || g->b->device != h->device) return bad_shape("handle, assembler and tangent must live on one device");
+    if (g->as->stream != h->stream || g->b->stream != h->stream) return bad_shape("handle, assembler and tangent must share one stream");
+    if (g->as->n != g->b->ns * g->b->nt || g->as->m != g->b->rows || g->as->nnz_j != g->b->nnz)
+        return bad_shape("the assembler's J is not the tangent's pattern");
+    return GMRF_OK;
+}
+
+gmrf_status gmrf_gn_create(gmrf_handle* h, gmrf_assembler* as, gmrf_burgers_p1* b, gmrf_gn** out) {
+    if (!h || !as || !b || !out) return bad_shape("null pointer");
+    if (as->device < 0 || b->device < 0) return bad_shape("the Gauss-Newton driver needs an assembler and a tangent with a device");
+    gmrf_gn tmp; tmp.h = h; tmp.as = as; tmp.b = b; tmp.device = h->device; tmp.stream = h->stream;
+    GCHK(gn_bound_ok(&tmp));
+    HIPCHK(hipSetDevice(h->device));
+    auto* g = new gmrf_gn(tmp);
+    hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&g->h_active), 64, hipHostMallocMapped);
+    if (e != hipSuccess) { delete g; g_last_error = std::string("gmrf_gn_create: ") + hipGetErrorString(e); return GMRF_ERR_HIP; }
+    *g->h_active = 0u;
+    void* dev_word = nullptr;
+    e = hipHostGetDevicePointer(&dev_word, g->h_active, 0);
+    if (e != hipSuccess) { (void)hipHostFree(g->h_active); delete g; g_last_error = std::string("gmrf_gn_create: ") + hipGetErrorString(e); return GMRF_ERR_HIP; }
+    g->dev_active = static_cast<unsigned*>(dev_word);
+    *out = g;
+    return GMRF_OK;
+}
+
+gmrf_status gmrf_gn_destroy(gmrf_gn* g) {
+    if (!g) return GMRF_OK;
+    (void)hipSetDevice(g->device);
+    (void)hipStreamSynchronize(g->stream);
+    gn_free(g);
+    if (g->h_active) (void)hipHostFree(g->h_active);
+    delete g;
+    return GMRF_OK;
+}
+
+static gmrf_status gn_alloc(gmrf_gn* g, int64_t B, int32_t max_steps) {
+    const gmrf_assembler* as = g->as;
+    if (g->B == B && g->hist_steps >= max_steps) return GMRF_OK;
+    HIPCHK(hipStreamSynchronize(g->h->stream));
+    gn_free(g);
+    const int64_t n = as->n, m = as->m, wide = std::max(n, m);
+    auto dm = [&](double** p, int64_t elems) { return hipMalloc(p, sizeof(double) * (size_t)std::max<int64_t>(elems, 1)); };
+    HIPCHK(dm(&g->d_x, B * n)); HIPCHK(dm(&g->d_xn, B * n)); HIPCHK(dm(&g->d_rhs, B * n));
+    HIPCHK(dm(&g->d_od, B * m)); HIPCHK(dm(&g->d_on, B * m)); HIPCHK(dm(&g->d_f, B * m)); HIPCHK(dm(&g->d_v, B * m));
+    HIPCHK(dm(&g->d_jv, B * as->nnz_j)); HIPCHK(dm(&g->d_a, B * as->nnz_out)); HIPCHK(dm(&g->d_q, B * as->nnz_q));
+    HIPCHK(dm(&g->d_part, B * objective_chunks(as))); HIPCHK(dm(&g->d_obj, B)); HIPCHK(dm(&g->d_in, 3 * B * wide));
+    HIPCHK(dm(&g->d_last, B)); HIPCHK(dm(&g->d_cur, B)); HIPCHK(dm(&g->d_hist, B * ((int64_t)max_steps + 1)));
+    HIPCHK(hipMalloc(&g->d_steps, sizeof(int32_t) * B)); HIPCHK(hipMalloc(&g->d_active, sizeof(int32_t) * B));
+    HIPCHK(hipMalloc(&g->d_take, sizeof(int32_t) * B));
+    g->B = B; g->hist_steps = max_steps;
+    return GMRF_OK;
+}
+
+// user array (host or device) -> device: where it lies, or a copy in `buf`
+static gmrf_status gn_in(gmrf_gn* g, const double* p, int64_t count, double* buf, const double** d) {
+    if (!p) { *d = nullptr; return GMRF_OK; }
+    if (is_device_ptr(p)) { *d = p; return GMRF_OK; }
+    HIPCHK(hipMemcpyAsync(buf, p, sizeof(double) * count, hipMemcpyHostToDevice, g->h->stream));
+    *d = buf;
+    return GMRF_OK;
+}
+
+static gmrf_status gn_copy_out(gmrf_gn* g, void* dst, const void* src, size_t bytes) {
+    if (!dst) return GMRF_OK;
+    HIPCHK(hipMemcpyAsync(dst, src, bytes, is_device_ptr(dst) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, g->h->stream));
+    return GMRF_OK;
+}
+
+// A^-1 rhs -> d_xn on the handle's stream.  The factorisation of the registered rhs left y = L^-1 rhs (fy_for): the backward sweep
+// of a copy of y is the whole solve; else both sweeps.  A batch's sweeps are never persistent launches, so nothing is waited for;
+// one problem goes through the guard of the persistent sweeps and ends in the stream's synchronisation.
+static gmrf_status gn_solve(gmrf_gn* g) {
+    gmrf_handle* h = g->h;
+    const int64_t vec_bytes = h->n * h->B * (int64_t)sizeof(double);
+    return sweep_guarded(h, {{g->d_rhs, vec_bytes, g->d_xn, vec_bytes}}, [&]() -> gmrf_status {
+        GCHK(ensure_panels(h, 1));
+        const bool have_y = h->fy_for && h->fy_for == g->d_rhs;
+        if (have_y) {
+            g->fwd_iterations += 1;
+            HIPCHK(hipMemcpyAsync(h->d_P, h->d_fy, sizeof(double) * (size_t)(h->B * h->n_pad), hipMemcpyDeviceToDevice, h->stream));
+            GCHK(run_sweeps(h, GMRF_SOLVE_BACKWARD, 1));
+            GCHK(launch_unpack(h, h->d_Y, g->d_xn, h->n, 1, nullptr));
+        } else {
+            GCHK(launch_pack(h, g->d_rhs, h->n, 1, 1));
+            GCHK(run_sweeps(h, GMRF_SOLVE_FULL, 1));
+            GCHK(launch_unpack(h, h->d_P, g->d_xn, h->n, 1, nullptr));
+        }
+        if (h->B == 1) HIPCHK(hipStreamSynchronize(h->stream));
+        return GMRF_OK;
+    });
+}
+
+static GnState gn_state(const gmrf_gn* g) {
+    GnState s;
+    s.last = g->d_last; s.cur = g->d_cur; s.steps = g->d_steps; s.active = g->d_active; s.take = g->d_take; s.hist = g->d_hist;
+    s.host_active = g->dev_active;
+    return s;
+}
+
+gmrf_status gmrf_gn_run(gmrf_gn* g, const double* q_nzval, int64_t q_stride, const double* qx_prior, const double* x_prior, double* x,
+                        const double* y, double noise, double rtol, int32_t max_steps, int32_t* steps_out, double* obj_hist_out,
+                        int32_t* info) {
+    if (!g || !q_nzval || !qx_prior || !x_prior || !x) return bad_shape("null pointer");
+    if (info) *info = 0;
+    gmrf_handle* h = g->h;
+    gmrf_assembler* as = g->as;
+    GCHK(gn_bound_ok(g));
+    GCHK(q_stride_ok(as, q_stride));
+    if (max_steps < 0 || max_steps > (1 << 20) || !(rtol >= 0.0)) return bad_shape("max_steps in [0, 2^20], rtol >= 0");
+    if (!h->analyzed) { g_last_error = "gmrf_gn_run: factor the assembler's pattern once on this handle first"; return GMRF_ERR_NO_FACTOR; }
+    if (h->n != as->n || h->nnz_in != as->nnz_out) return bad_shape("the handle has not analysed the assembler's pattern");
+    HIPCHK(hipSetDevice(h->device));
+    GCHK(objective_ready(as));
+    const int64_t B = h->B, n = as->n, m = as->m, wide = std::max(n, m);
+    GCHK(gn_alloc(g, B, max_steps));
+    hipStream_t st = h->stream;
+    // inputs: Q's values and the start point are copied (gmrf_gn_finalize reads them later), the rest is read where it lies
+    const int64_t q_count = q_stride ? B * as->nnz_q : as->nnz_q;
+    HIPCHK(hipMemcpyAsync(g->d_q, q_nzval, sizeof(double) * q_count, is_device_ptr(q_nzval) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(g->d_x, x, sizeof(double) * B * n, is_device_ptr(x) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+    const double *d_qxp, *d_xp, *d_y;
+    GCHK(gn_in(g, qx_prior, B * n, g->d_in, &d_qxp));
+    GCHK(gn_in(g, x_prior, B * n, g->d_in + B * wide, &d_xp));
+    GCHK(gn_in(g, y, B * m, g->d_in + 2 * B * wide, &d_y));
+    g->q_stride = q_stride; g->noise = noise; g->have_x = true;
+    const GnState s = gn_state(g);
+    // (slots of the history that no step reaches read NaN: all bits set)
+    HIPCHK(hipMemsetAsync(g->d_hist, 0xFF, sizeof(double) * B * ((size_t)max_steps + 1), st));
+    const dim3 grid_m((unsigned)((m + 255) / 256), (unsigned)B), grid_w((unsigned)((wide + 255) / 256), (unsigned)B);
+    // the start: obs_diff = y - f(x), objective, every problem active (the first `last` is +Inf)
+    GCHK(launch_tangent_batch(g->b, st, B, g->d_x, g->d_jv, g->d_f));
+    hipLaunchKernelGGL(gn_obs_diff, grid_m, dim3(256), 0, st, d_y, g->d_f, m, g->d_od);
+    GCHK(launch_objective_batch(as, st, B, g->d_q, q_stride, d_xp, g->d_x, g->d_od, noise, g->d_part, g->d_obj));
+    hipLaunchKernelGGL(gn_decide, dim3(1), dim3(256), 0, st, s, g->d_obj, B, rtol, max_steps, 1);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));
+    // the rhs buffer rides in the factorisations of this run; the caller's registration comes back afterwards
+    const double* user_frhs = h->frhs;
+    h->frhs = g->d_rhs; h->fy_for = nullptr;
+    gmrf_status status = GMRF_OK;
+    g->iterations = g->fwd_iterations = 0;
+    auto iteration = [&]() -> gmrf_status {
+        GCHK(launch_tangent_batch(g->b, st, B, g->d_x, g->d_jv, g->d_f));
+        GCHK(launch_precision_batch(as, st, B, g->d_q, q_stride, g->d_jv, noise, g->d_a));
+        GCHK(launch_rhs_batch(as, st, B, d_qxp, g->d_jv, g->d_x, g->d_od, noise, g->d_v, g->d_rhs));
+        GCHK(numeric_factor(h, g->d_a, info));
+        GCHK(gn_solve(g));
+        // the candidate's residual and objective; J's values are not needed any more this iteration and are overwritten
+        GCHK(launch_tangent_batch(g->b, st, B, g->d_xn, g->d_jv, g->d_f));
+        hipLaunchKernelGGL(gn_obs_diff, grid_m, dim3(256), 0, st, d_y, g->d_f, m, g->d_on);
+        GCHK(launch_objective_batch(as, st, B, g->d_q, q_stride, d_xp, g->d_xn, g->d_on, noise, g->d_part, g->d_obj));
+        hipLaunchKernelGGL(gn_decide, dim3(1), dim3(256), 0, st, s, g->d_obj, B, rtol, max_steps, 0);
+        hipLaunchKernelGGL(gn_apply, grid_w, dim3(256), 0, st, g->d_take, g->d_xn, g->d_x, n, g->d_on, g->d_od, m);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(st));
+        return GMRF_OK;
+    };
+    for (int32_t it = 0; it < max_steps && status == GMRF_OK; ++it) {
+        if (*reinterpret_cast<volatile unsigned*>(g->h_active) == 0u) break;
+        status = iteration();
+        if (status == GMRF_OK) g->iterations += 1;
+    }
+    h->frhs = user_frhs; h->fy_for = nullptr;
+    // x holds the last complete iterate of every problem, also after a failed factorisation
+    gmrf_status out_status = gn_copy_out(g, x, g->d_x, sizeof(double) * B * n);
+    if (out_status == GMRF_OK) out_status = gn_copy_out(g, steps_out, g->d_steps, sizeof(int32_t) * B);
+    if (out_status == GMRF_OK) out_status = gn_copy_out(g, obj_hist_out, g->d_hist, sizeof(double) * B * ((size_t)max_steps + 1));
+    HIPCHK(hipStreamSynchronize(st));
+    return status != GMRF_OK ? status : out_status;
+}
+
+gmrf_status gmrf_gn_finalize(gmrf_gn* g, int32_t* info) {
+    if (!g) return bad_shape("null pointer");
+    if (info) *info = 0;
+    if (!g->have_x || g->B != g->h->B) { g_last_error = "gmrf_gn_finalize: no run on this batch"; return GMRF_ERR_NO_FACTOR; }
+    GCHK(gn_bound_ok(g));
+    gmrf_handle* h = g->h;
+    HIPCHK(hipSetDevice(h->device));
+    GCHK(launch_tangent_batch(g->b, h->stream, g->B, g->d_x, g->d_jv, g->d_f));
+    GCHK(launch_precision_batch(g->as, h->stream, g->B, g->d_q, g->q_stride, g->d_jv, g->noise, g->d_a));
+    return numeric_factor(h, g->d_a, info);
 }
 
 // --------------------------------------------------------------------------------- shallow-water element kernels
@@ -5635,6 +6036,13 @@ gmrf_status gmrf_test_factor_fwd(gmrf_handle* h, int32_t* state, double* y_out) 
         GCHK(cols_out(h, h->d_fy, 1, nullptr, y_out, h->n, false));
         HIPCHK(hipStreamSynchronize(h->stream));
     }
+    return GMRF_OK;
+}
+
+// The last gmrf_gn_run: its iterations, and how many of them took y = L^-1 rhs from the factorisation (the forward-in-factor route)
+gmrf_status gmrf_test_gn_route(gmrf_gn* g, int32_t* iterations, int32_t* fwd_iterations) {
+    if (!g || !iterations || !fwd_iterations) return bad_shape("null pointer");
+    *iterations = g->iterations; *fwd_iterations = g->fwd_iterations;
     return GMRF_OK;
 }
 

@@ -239,7 +239,7 @@ def p1_periodic_line(ns: int):
     return M, np.full(ns, h), S, Adv
 
 
-def burgers(ns: int, nt: int, ic_noise: float = 1e8, fem_noise: float = 1e12) -> Workload:
+def burgers(ns: int, nt: int, ic_noise: float = 1e8, fem_noise: float = 1e12, ic=None) -> Workload:
     """1-D viscous Burgers space-time GMRF in the time-major ordering (t-1)*ns + s:
     Q = Q_prior + ic_noise A_ic^T A_ic + fem_noise J^T J, N = nt blocks of size ns.
 
@@ -252,7 +252,9 @@ def burgers(ns: int, nt: int, ic_noise: float = 1e8, fem_noise: float = 1e12) ->
     dt = 1.0 / (nt - 1)
     M, lumped, S, Adv = p1_periodic_line(ns)
     xs = np.arange(ns) / ns
-    ic = np.sin(2 * np.pi * xs) + 0.5 * np.sin(4 * np.pi * xs + 0.3)
+    if ic is None:                                     # (another initial condition: burgers_gauss_newton_batch)
+        ic = np.sin(2 * np.pi * xs) + 0.5 * np.sin(4 * np.pi * xs + 0.3)
+    ic = np.asarray(ic, dtype=np.float64)
     bulk = float(ic.mean())
     c = 1.0 / nu_b
     gamma = -c * bulk
@@ -300,7 +302,7 @@ def burgers(ns: int, nt: int, ic_noise: float = 1e8, fem_noise: float = 1e12) ->
                     {"dt": dt, "nu": nu_b, "nnz": int(Q.nnz)})
 
 
-def burgers_gauss_newton(ns: int, nt: int, ic_noise: float = 1e8, fem_noise: float = 1e12):
+def burgers_gauss_newton(ns: int, nt: int, ic_noise: float = 1e8, fem_noise: float = 1e12, ic=None):
     """The pieces of the reference's Gauss-Newton loop for the Burgers space-time GMRF
     (scripts/solve_burger.jl:118-180; residual tangent scripts/burgers/solve_burgers_gmrf-fem.jl:118-149)
     on the mesh of `burgers`: returns a dict with
@@ -313,9 +315,11 @@ def burgers_gauss_newton(ns: int, nt: int, ic_noise: float = 1e8, fem_noise: flo
     nu_b = 0.01 / math.pi
     dt = 1.0 / (nt - 1)
     M, lumped, S, Adv = p1_periodic_line(ns)
-    w = burgers(ns, nt, ic_noise, 0.0)                 # prior + initial-condition part only
+    w = burgers(ns, nt, ic_noise, 0.0, ic=ic)          # prior + initial-condition part only
     xs = np.arange(ns) / ns
-    ic = np.sin(2 * np.pi * xs) + 0.5 * np.sin(4 * np.pi * xs + 0.3)
+    if ic is None:
+        ic = np.sin(2 * np.pi * xs) + 0.5 * np.sin(4 * np.pi * xs + 0.3)
+    ic = np.asarray(ic, dtype=np.float64)
     x_prior = np.full(ns * nt, float(ic.mean()))
     M = M.tocsr(); S = S.tocsr(); Adv = Adv.tocsr()
     Jstat = (M + dt * nu_b * S).tocsr()
@@ -350,6 +354,47 @@ def burgers_gauss_newton(ns: int, nt: int, ic_noise: float = 1e8, fem_noise: flo
 
     return {"Q": w.Q, "Qx_prior": w.rhs, "x_prior": x_prior, "residual": residual, "jacobian": jacobian,
             "noise": fem_noise, "n_blocks": nt, "n": ns * nt, "m": ns * (nt - 1)}
+
+
+def burgers_initial_conditions(ns: int, B: int, seed: int = 0) -> np.ndarray:
+    """(B, ns) initial conditions a1 sin(2 pi x + p1) + a2 sin(4 pi x + p2) on the periodic line: problem 0 is the one of
+    `burgers` (a1 = 1, p1 = 0, a2 = 0.5, p2 = 0.3), the others draw a1 in [0.6, 1.4], a2 in [0.2, 0.8] and both phases in
+    [0, 2 pi) from `seed`."""
+    rng = np.random.default_rng(seed)
+    xs = np.arange(ns) / ns
+    out = np.empty((B, ns))
+    for p in range(B):
+        a1, a2, p1, p2 = (1.0, 0.5, 0.0, 0.3) if p == 0 else (rng.uniform(0.6, 1.4), rng.uniform(0.2, 0.8),
+                                                                 rng.uniform(0.0, 2 * np.pi), rng.uniform(0.0, 2 * np.pi))
+        out[p] = a1 * np.sin(2 * np.pi * xs + p1) + a2 * np.sin(4 * np.pi * xs + p2)
+    return out
+
+
+def burgers_gauss_newton_batch(ns: int, nt: int, B: int, seed: int = 0, ic_noise: float = 1e8, fem_noise: float = 1e12):
+    """A batch of Burgers Gauss-Newton problems on the mesh of `burgers_gauss_newton` -- the data-set loop of
+    scripts/burgers/solve_burgers_gmrf-fem.jl:154-233, where every sample brings its own initial condition and, through
+    `bulk_speed` (:86-107), its own prior.  Problem p takes `burgers_initial_conditions(ns, B, seed)[p]`; problem 0 is
+    `burgers_gauss_newton(ns, nt)`.  Returns a dict with
+      Q          the pattern (CSC; the values of problem 0),
+      q_values   (B, nnz) values of every problem's Q on that one pattern,
+      Qx_prior, x_prior   (B, n),
+      x0         (B, n) start points: x_prior with the initial condition in the first slice,
+      ic (B, ns), noise, n_blocks, n, m, dt, nu."""
+    ics = burgers_initial_conditions(ns, B, seed)
+    parts = [burgers_gauss_newton(ns, nt, ic_noise, fem_noise, ic=ics[p]) for p in range(B)]
+    Q = parts[0]["Q"]
+    q_values = np.empty((B, Q.nnz))
+    for p, g in enumerate(parts):
+        Qp = g["Q"]
+        if not (np.array_equal(Qp.indptr, Q.indptr) and np.array_equal(Qp.indices, Q.indices)):
+            raise ValueError(f"problem {p}: the prior's sparsity pattern differs from problem 0's")
+        q_values[p] = Qp.data
+    x_prior = np.stack([g["x_prior"] for g in parts])
+    x0 = x_prior.copy()
+    x0[:, :ns] = ics
+    return {"Q": Q, "q_values": q_values, "Qx_prior": np.stack([g["Qx_prior"] for g in parts]), "x_prior": x_prior, "x0": x0,
+            "ic": ics, "noise": fem_noise, "n_blocks": nt, "n": ns * nt, "m": ns * (nt - 1), "dt": 1.0 / (nt - 1),
+            "nu": 0.01 / math.pi}
 
 
 # --------------------------------------------------------------------------- analytic / toy

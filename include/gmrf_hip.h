@@ -523,6 +523,41 @@ gmrf_status gmrf_burgers_p1_pattern(const gmrf_burgers_p1* b, int64_t* nnz_out, 
                                     int32_t index_base);
 gmrf_status gmrf_burgers_p1_tangent(gmrf_burgers_p1* b, const double* w, double* vals_out, double* f_out);
 
+/* A batch of Gauss-Newton loops on one mesh (the Burgers data-set loop, scripts/burgers/solve_burgers_gmrf-fem.jl:154-233 with the
+ * loop body of scripts/solve_burger.jl:143-180).  All arrays are problem-major ([batch][...]), host or device pointers like the
+ * one-problem calls; problem p of a batch call gets the bits of the one-problem call on its slice.  q_stride: 0 = one Q for
+ * every problem, nnz(Q) = one value array per problem (the prior depends on the initial condition).
+ *     obj[p] = (x_prior_p - x_p)' Q_p (x_prior_p - x_p) + noise |obs_diff_p|^2                  (gmrf_assemble_objective_batch)
+ * is summed over a fixed partition without atomics: the same bits on every call and in every batch. */
+gmrf_status gmrf_burgers_p1_tangent_batch(gmrf_burgers_p1* b, int64_t batch, const double* w, double* vals_out, double* f_out);
+gmrf_status gmrf_assemble_precision_batch(gmrf_assembler* as, int64_t batch, const double* q_nzval, int64_t q_stride,
+                                          const double* j_vals, double noise, double* out_nzval);
+gmrf_status gmrf_assemble_rhs_batch(gmrf_assembler* as, int64_t batch, const double* base, const double* j_vals,
+                                    const double* x, const double* obs_diff, double noise, double* out);
+gmrf_status gmrf_assemble_objective_batch(gmrf_assembler* as, int64_t batch, const double* q_nzval, int64_t q_stride,
+                                          const double* x_prior, const double* x, const double* obs_diff, double noise,
+                                          double* obj_out);
+/* The driver binds a handle (reference order; its batch B is the number of problems), an assembler and a Burgers tangent that
+ * live on ONE device and ONE stream (create the three with the same stream argument); anything else is GMRF_ERR_BAD_SHAPE.
+ * gmrf_gn_run: the handle must have factored the assembler's pattern once (GMRF_ERR_NO_FACTOR before the first analysis,
+ * GMRF_ERR_BAD_SHAPE for another pattern).  Per iteration, on the handle's stream and without a host round trip but the status
+ * words: tangent -> A = Q + noise J'J and rhs -> gmrf_bt_refactor_values -> solve -> objective -> stop rule.  A problem is active
+ * while |last - cur| / |cur| > rtol and steps < max_steps (the first `last` is +Inf); a problem that has stopped is frozen (its x,
+ * history and count no longer change) and stays in the batch.  x [B][n]: in the start points, out the results; y [B][m] the
+ * observations (NULL = 0); steps_out [B]; obj_hist_out [B][max_steps + 1] (slot 0: the start point; slots no step reached: NaN).
+ * GMRF_ERR_NOT_SPD in any problem ends the run (`info`: the failing block, as gmrf_bt_refactor_values reports it); x then holds
+ * the last complete iterate of every problem and steps_out says which.  The run's right-hand sides are registered with
+ * gmrf_bt_set_factor_rhs for its duration (the caller's registration is put back); set_eager bit 19 switches that route off.
+ * gmrf_gn_finalize: tangent at the final x, assemble, re-factor -- the handle then holds the factor of
+ * Q + noise J(x)' J(x) of every problem (x_final of solve_burgers_gmrf-fem.jl:184-193) for posterior / sample / variance calls. */
+typedef struct gmrf_gn gmrf_gn;
+gmrf_status gmrf_gn_create(gmrf_handle* h, gmrf_assembler* as, gmrf_burgers_p1* b, gmrf_gn** out);
+gmrf_status gmrf_gn_destroy(gmrf_gn* g);
+gmrf_status gmrf_gn_run(gmrf_gn* g, const double* q_nzval, int64_t q_stride, const double* qx_prior, const double* x_prior,
+                        double* x, const double* y, double noise, double rtol, int32_t max_steps, int32_t* steps_out,
+                        double* obj_hist_out, int32_t* info);
+gmrf_status gmrf_gn_finalize(gmrf_gn* g, int32_t* info);
+
 /* Linear shallow-water SPDE (FEM block assembly, third piece): the element loops of `assemble_system!`,
  * /root/reference/src/spdes/shallow_water.jl:17-122 -- coupling matrix K (h-u, h-v: -H grad(phi_i) phi_j; u-h, v-h:
  * -g grad(phi_i) phi_j; u-u, v-v: k phi_i phi_j; u-v / v-u: -+ f phi_i phi_j), element-lumped mass M (`lump_matrix`, :116),
@@ -582,6 +617,8 @@ gmrf_status gmrf_test_persist_aborts(gmrf_handle* h, int32_t* n);
 /* *state = 1 if the current factor holds y = L^-1 b for the registered b (gmrf_bt_set_factor_rhs), else 0; y_out (optional, host,
  * n x B column-major) then receives y */
 gmrf_status gmrf_test_factor_fwd(gmrf_handle* h, int32_t* state, double* y_out);
+/* the last gmrf_gn_run: iterations, and those whose solve took y = L^-1 rhs from the factorisation */
+gmrf_status gmrf_test_gn_route(gmrf_gn* g, int32_t* iterations, int32_t* fwd_iterations);
 /* The per-device budget of CUs for persistent launches, host only (no GPU needed): `n` handles ask for demands[i] CUs one after
  * the other on a device of `cus` CUs; granted[i] = 1 if the claim fitted beside the earlier ones, 0 if it was refused (the
  * handle would take the launch-per-step routes up front instead of meeting a bounded wait). */

@@ -30,7 +30,7 @@ module DiffEqGMRFsHIP
 using SparseArrays, LinearAlgebra
 
 export TridiagonalCholeskyFactor, tridiagonal_cholesky, forward_solve, backward_solve, ldiv, PosteriorAssembler, GmrfCsr,
-       GmrfComm, DarcyP1Assembler, BurgersP1Tangent
+       GmrfComm, DarcyP1Assembler, BurgersP1Tangent, GaussNewtonBatch, gauss_newton_batch!
 
 const libgmrf = get(ENV, "LIBGMRF_HIP", joinpath(@__DIR__, "..", "diffeqgmrfs.jl_amd", "csrc", "libgmrf_hip.so"))
 
@@ -444,12 +444,13 @@ mutable struct PosteriorAssembler
     pattern::SparseMatrixCSC{Float64,Int}     # values 1.0; nzval order = output order of precision!
 end
 
-function PosteriorAssembler(Q::SparseMatrixCSC{Float64,Int}, J::SparseMatrixCSC{Float64,Int}; device::Integer = 0)
+function PosteriorAssembler(Q::SparseMatrixCSC{Float64,Int}, J::SparseMatrixCSC{Float64,Int}; device::Integer = 0,
+                            stream::Ptr{Cvoid} = C_NULL)
     Jt = SparseMatrixCSC(J')                   # CSC of J' = CSR of J; its nzval order is what the numeric calls expect
     h = Ref{Ptr{Cvoid}}(C_NULL)
     GC.@preserve Q Jt check(ccall((:gmrf_assemble_create, libgmrf), Int32,
         (Int32, Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Int64}, Int64, Ptr{Int64}, Ptr{Int64}, Int32, Ref{Ptr{Cvoid}}),
-        device, C_NULL, size(Q, 1), Q.colptr, Q.rowval, size(J, 1), Jt.colptr, Jt.rowval, 1, h))
+        device, stream, size(Q, 1), Q.colptr, Q.rowval, size(J, 1), Jt.colptr, Jt.rowval, 1, h))
     nnz_out = Ref{Int64}(0); nprod = Ref{Int64}(0)
     check(ccall((:gmrf_assemble_pattern, libgmrf), Int32, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}, Ptr{Int64}, Ptr{Int64}, Int32),
                 h[], nnz_out, nprod, C_NULL, C_NULL, 1))
@@ -473,6 +474,33 @@ function rhs!(out::Vector{Float64}, as::PosteriorAssembler, base, jt_nzval, x, o
     GC.@preserve out base jt_nzval x obs_diff check(ccall((:gmrf_assemble_rhs, libgmrf), Int32,
         (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Float64, Ptr{Float64}),
         as.handle, base, jt_nzval, x, obs_diff, Float64(noise), out))
+    return out
+end
+
+# batch forms ([.., batch] column-major = problem-major in memory): problem p gets the bits of the one-problem call on its column
+"nzval of Q_p + noise * J_p' * J_p for every column p of `jt_nzval`; `q_nzval` a vector (one Q for all) or a matrix (one column per problem)."
+function precision_batch!(out::Matrix{Float64}, as::PosteriorAssembler, q_nzval::VecOrMat{Float64}, jt_nzval::Matrix{Float64}, noise::Real)
+    q_stride = q_nzval isa Matrix ? size(q_nzval, 1) : 0
+    GC.@preserve out q_nzval jt_nzval check(ccall((:gmrf_assemble_precision_batch, libgmrf), Int32,
+        (Ptr{Cvoid}, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Float64, Ptr{Float64}),
+        as.handle, size(jt_nzval, 2), q_nzval, q_stride, jt_nzval, Float64(noise), out))
+    return out
+end
+
+function rhs_batch!(out::Matrix{Float64}, as::PosteriorAssembler, base, jt_nzval::Matrix{Float64}, x, obs_diff, noise::Real)
+    GC.@preserve out base jt_nzval x obs_diff check(ccall((:gmrf_assemble_rhs_batch, libgmrf), Int32,
+        (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Float64, Ptr{Float64}),
+        as.handle, size(jt_nzval, 2), base, jt_nzval, x, obs_diff, Float64(noise), out))
+    return out
+end
+
+"obj[p] = (x_prior_p - x_p)' Q_p (x_prior_p - x_p) + noise |obs_diff_p|^2 (scripts/solve_burger.jl:157), a fixed-shape sum"
+function objective_batch!(out::Vector{Float64}, as::PosteriorAssembler, q_nzval::VecOrMat{Float64}, x_prior::Matrix{Float64},
+                          x::Matrix{Float64}, obs_diff::Matrix{Float64}, noise::Real)
+    q_stride = q_nzval isa Matrix ? size(q_nzval, 1) : 0
+    GC.@preserve out q_nzval x_prior x obs_diff check(ccall((:gmrf_assemble_objective_batch, libgmrf), Int32,
+        (Ptr{Cvoid}, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Float64, Ptr{Float64}),
+        as.handle, size(x, 2), q_nzval, q_stride, x_prior, x, obs_diff, Float64(noise), out))
     return out
 end
 
@@ -518,14 +546,15 @@ mutable struct BurgersP1Tangent
     rows::Int
 end
 
-function BurgersP1Tangent(ns::Integer, nt::Integer, dt::Real, nu::Real; device::Integer = 0, order::Integer = 1)
+function BurgersP1Tangent(ns::Integer, nt::Integer, dt::Real, nu::Real; device::Integer = 0, order::Integer = 1,
+                          stream::Ptr{Cvoid} = C_NULL)
     h = Ref{Ptr{Cvoid}}(C_NULL)
     if order == 2       # the quadratic periodic line of periodic_unit_interval_discretization (src/utils.jl:42-49): ns = 2 N_x dofs by position
         check(ccall((:gmrf_burgers_p2_create, libgmrf), Int32, (Int32, Ptr{Cvoid}, Int64, Int64, Float64, Float64, Ref{Ptr{Cvoid}}),
-                    device, C_NULL, ns, nt, Float64(dt), Float64(nu), h))
+                    device, stream, ns, nt, Float64(dt), Float64(nu), h))
     else
         check(ccall((:gmrf_burgers_p1_create, libgmrf), Int32, (Int32, Ptr{Cvoid}, Int64, Int64, Float64, Float64, Ref{Ptr{Cvoid}}),
-                    device, C_NULL, ns, nt, Float64(dt), Float64(nu), h))
+                    device, stream, ns, nt, Float64(dt), Float64(nu), h))
     end
     nnz_out = Ref{Int64}(0)
     check(ccall((:gmrf_burgers_p1_pattern, libgmrf), Int32, (Ptr{Cvoid}, Ref{Int64}, Ptr{Int64}, Ptr{Int64}, Int32), h[], nnz_out, C_NULL, C_NULL, 1))
@@ -542,6 +571,59 @@ function tangent!(vals::Vector{Float64}, f::Vector{Float64}, b::BurgersP1Tangent
     GC.@preserve w vals f check(ccall((:gmrf_burgers_p1_tangent, libgmrf), Int32,
         (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), b.handle, w, vals, f))
     return vals, f
+end
+
+"`tangent!` for every column of `w` (n x batch)"
+function tangent_batch!(vals::Matrix{Float64}, f::Matrix{Float64}, b::BurgersP1Tangent, w::Matrix{Float64})
+    GC.@preserve w vals f check(ccall((:gmrf_burgers_p1_tangent_batch, libgmrf), Int32,
+        (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), b.handle, size(w, 2), w, vals, f))
+    return vals, f
+end
+
+# The Burgers data-set loop (scripts/burgers/solve_burgers_gmrf-fem.jl:154-233, loop body scripts/solve_burger.jl:143-180) for a
+# batch of problems in lock step on the device.  `F` (batch = number of problems, factored once on `as.pattern`), `as` and `b`
+# must have been created on one device and one stream.
+mutable struct GaussNewtonBatch
+    handle::Ptr{Cvoid}
+    F::TridiagonalCholeskyFactor
+    as::PosteriorAssembler
+    b::BurgersP1Tangent
+end
+
+function GaussNewtonBatch(F::TridiagonalCholeskyFactor, as::PosteriorAssembler, b::BurgersP1Tangent)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:gmrf_gn_create, libgmrf), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{Ptr{Cvoid}}), F.handle, as.handle, b.handle, h))
+    gn = GaussNewtonBatch(h[], F, as, b)
+    finalizer(g -> ccall((:gmrf_gn_destroy, libgmrf), Int32, (Ptr{Cvoid},), g.handle), gn)
+    return gn
+end
+
+"""
+    gauss_newton_batch!(x, gn, q_nzval, Qx_prior, x_prior; y = nothing, noise = 1e8, rtol = 1e-4, max_steps = 20)
+
+`x` (n x B): in the start points, out the results.  Returns `(x, steps, objective_history)`; the defaults are those of
+scripts/solve_burger.jl:140 and :171.  A problem that has stopped is frozen and stays in the batch.
+"""
+function gauss_newton_batch!(x::Matrix{Float64}, gn::GaussNewtonBatch, q_nzval::VecOrMat{Float64}, Qx_prior::Matrix{Float64},
+                             x_prior::Matrix{Float64}; y::Union{Nothing,Matrix{Float64}} = nothing, noise::Real = 1e8,
+                             rtol::Real = 1e-4, max_steps::Integer = 20)
+    B = size(x, 2)
+    q_stride = q_nzval isa Matrix ? size(q_nzval, 1) : 0
+    steps = zeros(Int32, B); hist = fill(NaN, max_steps + 1, B); info = Ref{Int32}(0)
+    yp = y === nothing ? Ptr{Float64}(C_NULL) : pointer(y)
+    st = GC.@preserve x q_nzval Qx_prior x_prior y steps hist ccall((:gmrf_gn_run, libgmrf), Int32,
+        (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Float64, Float64, Int32, Ptr{Int32},
+         Ptr{Float64}, Ref{Int32}),
+        gn.handle, q_nzval, q_stride, Qx_prior, x_prior, x, yp, Float64(noise), Float64(rtol), Int32(max_steps), steps, hist, info)
+    check(st, info[])
+    return x, steps, hist
+end
+
+"Tangent at the final x, assemble, re-factor: `gn.F` then holds the factor of Q + noise J(x)' J(x) of every problem."
+function finalize!(gn::GaussNewtonBatch)
+    info = Ref{Int32}(0)
+    check(ccall((:gmrf_gn_finalize, libgmrf), Int32, (Ptr{Cvoid}, Ref{Int32}), gn.handle, info), info[])
+    return gn.F
 end
 
 # Linear shallow-water SPDE (src/spdes/shallow_water.jl): element kernels of assemble_system! (:17-122) and the per-step

@@ -99,11 +99,10 @@ static int64_t next_pow2(int64_t v) {
     return p;
 }
 
+#include "host_util.hpp"      // free_dev, DevBuf, DevCtx, Staging
+
 // ------------------------------------------------------------------------------------ csr
-struct gmrf_csr {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
+struct gmrf_csr : DevCtx {
     int64_t n_rows = 0, n_cols = 0, nnz = 0;
     int64_t* d_rowptr = nullptr;
     int32_t* d_colidx = nullptr;
@@ -112,9 +111,7 @@ struct gmrf_csr {
     double* d_diag = nullptr;
     bool tiles128_ok = false;          // the same for 128-row tiles and 2 * SPMV_CAP
     bool tiles_ok = false;             // every SPMV_ROWS-row tile has at most SPMV_CAP entries (csr_spmv_tiles)
-    double* d_stage_x = nullptr;
-    double* d_stage_y = nullptr;
-    int64_t stage_cap = 0;
+    DevBuf stage_x, stage_y;           // host operands of gmrf_spmm / gmrf_spmm_rows
     // tile plan of csr_spmm_tiles (node-major right-hand sides), built on first use
     int plan_state = 0;                // 0: not built, 1: usable, -1: a tile exceeds the LDS image
     int64_t* d_tile_uptr = nullptr;    // [tiles + 1] ranges into d_ucols
@@ -215,7 +212,7 @@ struct gmrf_handle {
     int64_t kp_cap = 0;
     double* d_stage = nullptr;
     int64_t stage_cap = 0;
-    double* d_mean = nullptr;
+    DevBuf mean_arena;                 // a host `mean` of gmrf_bt_sample (Staging)
     double* d_acc = nullptr;           // variance accumulator / output ([acc_B][n])
     int64_t acc_B = 0;
     // graphs
@@ -488,10 +485,6 @@ static gmrf_status gemm(gmrf_handle* h, bool a_t, bool b_n, int M, int N, int K,
     return GMRF_OK;
 }
 
-static void free_dev(void* p) {
-    if (p) (void)hipFree(p);
-}
-
 // element counts / strides of the factor arrays (doubles)
 static inline int64_t blk_elems(const gmrf_handle* h) { return h->bsp * h->bsp; }
 static inline int64_t c_ld(const gmrf_handle* h) { return h->bsp - h->cmin; }                      // row stride of a stored C_i
@@ -623,7 +616,7 @@ static void release_shape_buffers(gmrf_handle* h) {
     h->sweep_graphs.clear();
     free_dev(h->d_P); free_dev(h->d_Y); free_dev(h->d_Tp);
     h->d_P = h->d_Y = h->d_Tp = nullptr; h->kp_cap = 0;
-    free_dev(h->d_mean); h->d_mean = nullptr;
+    h->mean_arena.release();
     free_dev(h->d_acc); h->d_acc = nullptr; h->acc_B = 0;
     free_dev(h->d_stage); h->d_stage = nullptr; h->stage_cap = 0;
     free_dev(h->d_ft); free_dev(h->d_fy); h->d_ft = h->d_fy = nullptr; h->fy_elems = 0; h->fy_for = nullptr;
@@ -2205,7 +2198,7 @@ gmrf_status gmrf_bt_destroy(gmrf_handle* h) {
     if (h->h_sweep_abort) { (void)hipHostFree(h->h_sweep_abort); h->h_sweep_abort = nullptr; }
     free_dev(h->d_info); free_dev(h->d_logdet); free_dev(h->d_pflags); free_dev(h->d_kbx); free_dev(h->d_V);
     free_dev(h->d_P); free_dev(h->d_Y); free_dev(h->d_Tp);
-    free_dev(h->d_stage); free_dev(h->d_mean); free_dev(h->d_acc);
+    free_dev(h->d_stage); h->mean_arena.release(); free_dev(h->d_acc);
     free_dev(h->d_ft); free_dev(h->d_fy);
     free_dev(h->d_sel_src); free_dev(h->d_sel_slot); free_dev(h->d_sig); free_dev(h->d_dv);
     for (auto e : h->ev_pool) (void)hipEventDestroy(e);
@@ -2850,10 +2843,8 @@ struct gmrf_comm {
     void* comm = nullptr;
     hipStream_t stream = nullptr;          // collectives run here, beside the handle's compute stream
     hipEvent_t ev_in = nullptr, ev_out = nullptr;
-    void* d_small = nullptr;               // staging of small host records (layout, scalars)
-    size_t small_cap = 0;
-    double* d_pack = nullptr;              // staging of the packed transport image of a block range
-    size_t pack_cap = 0;
+    DevBuf small;                          // staging of small host records (layout, scalars)
+    DevBuf pack;                           // staging of the packed transport image of a block range
     double bytes_moved = 0.0;              // factor bytes broadcast so far (gmrf_comm_bytes)
 };
 
@@ -2894,7 +2885,7 @@ gmrf_status gmrf_comm_destroy(gmrf_comm* c) {
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->comm) (void)g_rccl.CommDestroy(c->comm);
-    free_dev(c->d_small); free_dev(c->d_pack);
+    c->small.release(); c->pack.release();
     if (c->ev_in) (void)hipEventDestroy(c->ev_in);
     if (c->ev_out) (void)hipEventDestroy(c->ev_out);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -2906,14 +2897,10 @@ gmrf_status gmrf_comm_destroy(gmrf_comm* c) {
 gmrf_status gmrf_comm_bcast_host(gmrf_comm* c, void* host_buf, int64_t bytes, int32_t root) {
     if (!c || !host_buf || bytes <= 0 || root < 0 || root >= c->world) return bad_shape("bad broadcast arguments");
     HIPCHK(hipSetDevice(c->device));
-    if ((size_t)bytes > c->small_cap) {
-        free_dev(c->d_small); c->d_small = nullptr; c->small_cap = 0;
-        HIPCHK(hipMalloc(&c->d_small, (size_t)bytes));
-        c->small_cap = (size_t)bytes;
-    }
-    if (c->rank == root) HIPCHK(hipMemcpyAsync(c->d_small, host_buf, (size_t)bytes, hipMemcpyHostToDevice, c->stream));
-    NCCLCHK(g_rccl.Broadcast(c->d_small, c->d_small, (size_t)bytes, /*ncclInt8*/ 0, root, c->comm, c->stream));
-    if (c->rank != root) HIPCHK(hipMemcpyAsync(host_buf, c->d_small, (size_t)bytes, hipMemcpyDeviceToHost, c->stream));
+    GCHK(c->small.reserve(c->stream, (size_t)bytes));
+    if (c->rank == root) HIPCHK(hipMemcpyAsync(c->small.p, host_buf, (size_t)bytes, hipMemcpyHostToDevice, c->stream));
+    NCCLCHK(g_rccl.Broadcast(c->small.p, c->small.p, (size_t)bytes, /*ncclInt8*/ 0, root, c->comm, c->stream));
+    if (c->rank != root) HIPCHK(hipMemcpyAsync(host_buf, c->small.p, (size_t)bytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     return GMRF_OK;
 }
@@ -2956,18 +2943,14 @@ gmrf_status gmrf_bt_bcast_blocks_async(gmrf_handle* h, gmrf_comm* c, int32_t roo
     int64_t seg = 0;
     GCHK(gmrf_bt_packed_size(h, i0, i1, &seg));
     const size_t need = (size_t)seg * (size_t)h->B * sizeof(double);
-    if (need > c->pack_cap) {
-        HIPCHK(hipStreamSynchronize(c->stream));          // earlier transfers still use the old staging buffer
-        free_dev(c->d_pack); c->d_pack = nullptr; c->pack_cap = 0;
-        HIPCHK(hipMalloc(&c->d_pack, need));
-        c->pack_cap = need;
-    }
+    GCHK(c->pack.reserve(c->stream, need));
+    double* d_pack = c->pack.as<double>();
     HIPCHK(hipEventRecord(c->ev_in, h->stream));
     HIPCHK(hipStreamWaitEvent(c->stream, c->ev_in, 0));
-    if (c->rank == root) GCHK(pack_blocks_on(h, c->stream, i0, i1, c->d_pack, true));
-    NCCLCHK(g_rccl.Broadcast(c->d_pack, c->d_pack, (size_t)seg * (size_t)h->B, /*ncclFloat64*/ 8, root, c->comm, c->stream));
+    if (c->rank == root) GCHK(pack_blocks_on(h, c->stream, i0, i1, d_pack, true));
+    NCCLCHK(g_rccl.Broadcast(d_pack, d_pack, (size_t)seg * (size_t)h->B, /*ncclFloat64*/ 8, root, c->comm, c->stream));
     c->bytes_moved += (double)need;
-    if (c->rank != root) GCHK(pack_blocks_on(h, c->stream, i0, i1, c->d_pack, false));
+    if (c->rank != root) GCHK(pack_blocks_on(h, c->stream, i0, i1, d_pack, false));
     if (with_l) {
         int64_t first = 0, cnt = 0, pstride = 0;
         GCHK(gmrf_bt_block_range(h, GMRF_BLOCK_L, i0, i1, &first, &cnt, &pstride));
@@ -3005,20 +2988,16 @@ gmrf_status gmrf_bt_allgather_blocks_async(gmrf_handle* src, gmrf_handle* dst, g
     GCHK(gmrf_bt_packed_size(src, i0, i1, &seg));
     const size_t own = (size_t)seg * (size_t)src->B, all = own * (size_t)c->world;
     const size_t need = (own + all) * sizeof(double);          // [own image | gathered images]
-    if (need > c->pack_cap) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        free_dev(c->d_pack); c->d_pack = nullptr; c->pack_cap = 0;
-        HIPCHK(hipMalloc(&c->d_pack, need));
-        c->pack_cap = need;
-    }
+    GCHK(c->pack.reserve(c->stream, need));
+    double* d_pack = c->pack.as<double>();
     HIPCHK(hipEventRecord(c->ev_in, src->stream));
     HIPCHK(hipStreamWaitEvent(c->stream, c->ev_in, 0));
     HIPCHK(hipEventRecord(c->ev_in, dst->stream));            // dst's earlier sweeps still read the blocks the unpack overwrites
     HIPCHK(hipStreamWaitEvent(c->stream, c->ev_in, 0));
-    GCHK(pack_blocks_on(src, c->stream, i0, i1, c->d_pack, true));
-    NCCLCHK(g_rccl.AllGather(c->d_pack, c->d_pack + own, own, /*ncclFloat64*/ 8, c->comm, c->stream));
+    GCHK(pack_blocks_on(src, c->stream, i0, i1, d_pack, true));
+    NCCLCHK(g_rccl.AllGather(d_pack, d_pack + own, own, /*ncclFloat64*/ 8, c->comm, c->stream));
     c->bytes_moved += (double)(all - own) * sizeof(double);    // what came in over this rank's links
-    GCHK(pack_blocks_on(dst, c->stream, i0, i1, c->d_pack + own, false));
+    GCHK(pack_blocks_on(dst, c->stream, i0, i1, d_pack + own, false));
     return GMRF_OK;
 }
 
@@ -3080,15 +3059,6 @@ gmrf_status gmrf_bt_solve(gmrf_handle* h, const double* b, double* y, int64_t k,
     });
 }
 
-static gmrf_status stage_vector(gmrf_handle* h, const double* v, double** d_buf, const double** d_out) {
-    if (!v) { *d_out = nullptr; return GMRF_OK; }
-    if (is_device_ptr(v)) { *d_out = v; return GMRF_OK; }
-    if (!*d_buf) HIPCHK(hipMalloc(d_buf, sizeof(double) * h->n * h->B));
-    HIPCHK(hipMemcpyAsync(*d_buf, v, sizeof(double) * h->n * h->B, hipMemcpyHostToDevice, h->stream));
-    *d_out = *d_buf;
-    return GMRF_OK;
-}
-
 // draws (or loads) z for samples [first_id + c0, +kc) into panel P and runs the backward sweep -> panel Y
 static gmrf_status sample_chunk(gmrf_handle* h, uint64_t seed, int64_t first_id, int kc, const double* z,
                                 int64_t ldz, int64_t id_stride) {
@@ -3118,7 +3088,9 @@ gmrf_status gmrf_bt_sample(gmrf_handle* h, uint64_t seed, int64_t first_id, int6
     HIPCHK(hipSetDevice(h->device));
     if (tw_on(h)) return tw_sample(h, seed, first_id, k, mean, z, out, ld);
     const double* d_mean = nullptr;
-    GCHK(stage_vector(h, mean, &h->d_mean, &d_mean));
+    Staging args(h->mean_arena);
+    args.in(mean, sizeof(double) * h->n * h->B, &d_mean);
+    GCHK(args.commit(h->stream));
     const bool out_dev = is_device_ptr(out);
     // z or the mean overlaps the output: the repeat after a persistent sweep that gave up would read what the first pass wrote
     const int64_t smp_bytes = cols_bytes(h->n, k * h->B, ld);      // z and out alike
@@ -3370,13 +3342,10 @@ gmrf_status gmrf_csr_create(int32_t device, void* stream, int64_t n_rows, int64_
                             const int64_t* colidx, const double* vals, int32_t index_base, int32_t values_f32,
                             gmrf_csr** out) {
     if (!out || !rowptr || !colidx || !vals || n_rows <= 0 || n_cols <= 0) return bad_shape("bad CSR arguments");
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0 || device < 0 || device >= count) {
-        (void)hipGetLastError();
-        g_last_error = "no HIP device visible";
-        return GMRF_ERR_NO_DEVICE;
-    }
-    HIPCHK(hipSetDevice(device));
+    // (whatever fails from here on, the guard's gmrf_csr_destroy releases what has been allocated so far)
+    std::unique_ptr<gmrf_csr, gmrf_status (*)(gmrf_csr*)> guard(new gmrf_csr(), gmrf_csr_destroy);
+    gmrf_csr* m = guard.get();
+    GCHK(m->open(device, stream, hipStreamNonBlocking, "gmrf_csr_create", /*pattern_only_ok=*/false));
     const int64_t nnz = rowptr[n_rows] - index_base;
     if (nnz < 0 || rowptr[0] != index_base) return bad_shape("bad CSR row pointers");
     std::vector<int64_t> rp((size_t)n_rows + 1);
@@ -3390,8 +3359,6 @@ gmrf_status gmrf_csr_create(int32_t device, void* stream, int64_t n_rows, int64_
         if (c < 0 || c >= n_cols) return bad_shape("column index out of range");
         ci[p] = (int32_t)c;
     }
-    gmrf_csr* m = new gmrf_csr();
-    m->device = device;
     m->id = ++g_csr_ids;
     m->tiles_ok = true;
     for (int64_t r = 0; r < n_rows; r += SPMV_ROWS)
@@ -3399,54 +3366,42 @@ gmrf_status gmrf_csr_create(int32_t device, void* stream, int64_t n_rows, int64_
     m->tiles128_ok = true;
     for (int64_t r = 0; r < n_rows; r += 128)
         if (rp[std::min<int64_t>(n_rows, r + 128)] - rp[r] > 2 * SPMV_CAP) { m->tiles128_ok = false; break; }
-    // from here on a failing HIP call releases what has been allocated so far
-#define CSRCHK(expr)                                                                          \
-    do {                                                                                      \
-        hipError_t _e = (expr);                                                               \
-        if (_e != hipSuccess) {                                                               \
-            g_last_error = std::string(#expr) + ": " + hipGetErrorString(_e);                 \
-            (void)gmrf_csr_destroy(m);                                                        \
-            return GMRF_ERR_HIP;                                                              \
-        }                                                                                     \
-    } while (0)
-    if (stream) { m->stream = (hipStream_t)stream; } else { CSRCHK(hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking)); m->own_stream = true; }
     m->n_rows = n_rows; m->n_cols = n_cols; m->nnz = nnz;
-    CSRCHK(hipMalloc(&m->d_rowptr, sizeof(int64_t) * (n_rows + 1)));
-    CSRCHK(hipMalloc(&m->d_colidx, sizeof(int32_t) * std::max<int64_t>(nnz, 1)));
-    CSRCHK(hipMemcpyAsync(m->d_rowptr, rp.data(), sizeof(int64_t) * (n_rows + 1), hipMemcpyHostToDevice, m->stream));
-    CSRCHK(hipMemcpyAsync(m->d_colidx, ci.data(), sizeof(int32_t) * nnz, hipMemcpyHostToDevice, m->stream));
-    CSRCHK(hipStreamSynchronize(m->stream));
+    HIPCHK(hipMalloc(&m->d_rowptr, sizeof(int64_t) * (n_rows + 1)));
+    HIPCHK(hipMalloc(&m->d_colidx, sizeof(int32_t) * std::max<int64_t>(nnz, 1)));
+    HIPCHK(hipMemcpyAsync(m->d_rowptr, rp.data(), sizeof(int64_t) * (n_rows + 1), hipMemcpyHostToDevice, m->stream));
+    HIPCHK(hipMemcpyAsync(m->d_colidx, ci.data(), sizeof(int32_t) * nnz, hipMemcpyHostToDevice, m->stream));
+    HIPCHK(hipStreamSynchronize(m->stream));
     if (values_f32) {
         std::vector<float> vf((size_t)nnz);
         for (int64_t p = 0; p < nnz; ++p) vf[p] = (float)vals[p];
-        CSRCHK(hipMalloc(&m->d_vals32, sizeof(float) * std::max<int64_t>(nnz, 1)));
-        CSRCHK(hipMemcpyAsync(m->d_vals32, vf.data(), sizeof(float) * nnz, hipMemcpyHostToDevice, m->stream));
-        CSRCHK(hipStreamSynchronize(m->stream));
+        HIPCHK(hipMalloc(&m->d_vals32, sizeof(float) * std::max<int64_t>(nnz, 1)));
+        HIPCHK(hipMemcpyAsync(m->d_vals32, vf.data(), sizeof(float) * nnz, hipMemcpyHostToDevice, m->stream));
+        HIPCHK(hipStreamSynchronize(m->stream));
     } else {
-        CSRCHK(hipMalloc(&m->d_vals, sizeof(double) * std::max<int64_t>(nnz, 1)));
-        CSRCHK(hipMemcpyAsync(m->d_vals, vals, sizeof(double) * nnz, hipMemcpyHostToDevice, m->stream));
-        CSRCHK(hipStreamSynchronize(m->stream));
+        HIPCHK(hipMalloc(&m->d_vals, sizeof(double) * std::max<int64_t>(nnz, 1)));
+        HIPCHK(hipMemcpyAsync(m->d_vals, vals, sizeof(double) * nnz, hipMemcpyHostToDevice, m->stream));
+        HIPCHK(hipStreamSynchronize(m->stream));
     }
     if (n_rows == n_cols) {
-        CSRCHK(hipMalloc(&m->d_diag, sizeof(double) * n_rows));
+        HIPCHK(hipMalloc(&m->d_diag, sizeof(double) * n_rows));
         hipLaunchKernelGGL(csr_extract_diag, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, m->stream,
                            m->d_rowptr, m->d_colidx, m->d_vals, m->d_vals32, n_rows, m->d_diag);
-        CSRCHK(hipGetLastError());
-        CSRCHK(hipStreamSynchronize(m->stream));
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(m->stream));
     }
-#undef CSRCHK
-    *out = m;
+    *out = guard.release();
     return GMRF_OK;
 }
 
 gmrf_status gmrf_csr_destroy(gmrf_csr* m) {
     if (!m) return GMRF_OK;
-    (void)hipSetDevice(m->device);
-    (void)hipStreamSynchronize(m->stream);
-    free_dev(m->d_rowptr); free_dev(m->d_colidx); free_dev(m->d_vals); free_dev(m->d_vals32);
-    free_dev(m->d_diag); free_dev(m->d_stage_x); free_dev(m->d_stage_y);
-    free_dev(m->d_tile_uptr); free_dev(m->d_ucols); free_dev(m->d_lidx);
-    if (m->own_stream) (void)hipStreamDestroy(m->stream);
+    m->close();
+    if (m->has_device()) {
+        free_dev(m->d_rowptr); free_dev(m->d_colidx); free_dev(m->d_vals); free_dev(m->d_vals32);
+        free_dev(m->d_diag); m->stage_x.release(); m->stage_y.release();
+        free_dev(m->d_tile_uptr); free_dev(m->d_ucols); free_dev(m->d_lidx);
+    }
     delete m;
     return GMRF_OK;
 }
@@ -3623,20 +3578,16 @@ gmrf_status gmrf_spmm_rows(const gmrf_csr* S, const double* X, double* Y, int64_
     double* d_Y = Y;
     int64_t lx = ldx, ly = ldy;
     const int64_t kk = k + (k & 1);                       // staging keeps rows 16-byte aligned
-    const int64_t need = kk * std::max(S->n_rows, S->n_cols);
-    if ((!x_dev || !y_dev) && need > m->stage_cap) {
-        free_dev(m->d_stage_x); free_dev(m->d_stage_y);
-        m->d_stage_x = m->d_stage_y = nullptr;
-        HIPCHK(hipMalloc(&m->d_stage_x, sizeof(double) * need));
-        HIPCHK(hipMalloc(&m->d_stage_y, sizeof(double) * need));
-        m->stage_cap = need;
-    }
     if (!x_dev) {
-        HIPCHK(hipMemcpy2DAsync(m->d_stage_x, kk * sizeof(double), X, ldx * sizeof(double), k * sizeof(double), S->n_cols,
+        GCHK(m->stage_x.reserve(S->stream, sizeof(double) * kk * S->n_cols));
+        HIPCHK(hipMemcpy2DAsync(m->stage_x.p, kk * sizeof(double), X, ldx * sizeof(double), k * sizeof(double), S->n_cols,
                                 hipMemcpyHostToDevice, S->stream));
-        d_X = m->d_stage_x; lx = kk;
+        d_X = m->stage_x.as<double>(); lx = kk;
     }
-    if (!y_dev) { d_Y = m->d_stage_y; ly = kk; }
+    if (!y_dev) {
+        GCHK(m->stage_y.reserve(S->stream, sizeof(double) * kk * S->n_rows));
+        d_Y = m->stage_y.as<double>(); ly = kk;
+    }
     GCHK(spmm_rows_device(S, S->stream, d_X, lx, d_Y, ly, (int)k));
     if (!y_dev)
         HIPCHK(hipMemcpy2DAsync(Y, ldy * sizeof(double), d_Y, kk * sizeof(double), k * sizeof(double), S->n_rows,
@@ -3654,20 +3605,16 @@ gmrf_status gmrf_spmm(const gmrf_csr* S, const double* X, double* Y, int64_t k, 
     const double* d_X = X;
     double* d_Y = Y;
     int64_t lx = ldx, ly = ldy;
-    const int64_t need = k * std::max(S->n_rows, S->n_cols);
-    if ((!x_dev || !y_dev) && need > m->stage_cap) {
-        free_dev(m->d_stage_x); free_dev(m->d_stage_y);
-        m->d_stage_x = m->d_stage_y = nullptr;
-        HIPCHK(hipMalloc(&m->d_stage_x, sizeof(double) * need));
-        HIPCHK(hipMalloc(&m->d_stage_y, sizeof(double) * need));
-        m->stage_cap = need;
-    }
     if (!x_dev) {
-        HIPCHK(hipMemcpy2DAsync(m->d_stage_x, S->n_cols * sizeof(double), X, ldx * sizeof(double),
+        GCHK(m->stage_x.reserve(S->stream, sizeof(double) * k * S->n_cols));
+        HIPCHK(hipMemcpy2DAsync(m->stage_x.p, S->n_cols * sizeof(double), X, ldx * sizeof(double),
                                 S->n_cols * sizeof(double), k, hipMemcpyHostToDevice, S->stream));
-        d_X = m->d_stage_x; lx = S->n_cols;
+        d_X = m->stage_x.as<double>(); lx = S->n_cols;
     }
-    if (!y_dev) { d_Y = m->d_stage_y; ly = S->n_rows; }
+    if (!y_dev) {
+        GCHK(m->stage_y.reserve(S->stream, sizeof(double) * k * S->n_rows));
+        d_Y = m->stage_y.as<double>(); ly = S->n_rows;
+    }
     GCHK(spmm_device(S, S->stream, d_X, lx, d_Y, ly, (int)k));
     if (!y_dev)
         HIPCHK(hipMemcpy2DAsync(Y, ldy * sizeof(double), d_Y, S->n_rows * sizeof(double),
@@ -3695,22 +3642,19 @@ gmrf_status gmrf_spmm_rows_async(const gmrf_csr* S, const double* X, double* Y, 
 }
 
 // --------------------------------------------------------------------------------- posterior assembly
-struct gmrf_assembler {
-    int device = -1;                    // -1: symbolic only (pattern queries; no numeric phase)
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
+struct gmrf_assembler : DevCtx {        // device -1: symbolic only (pattern queries; no numeric phase)
     int64_t n = 0, m = 0, nnz_q = 0, nnz_j = 0, nnz_out = 0, n_pairs = 0;
     std::vector<int64_t> colptr, rowval;            // result pattern (CSC, 0-based, rows ascending)
     int64_t *d_pptr = nullptr, *d_qmap = nullptr, *d_jt_ptr = nullptr, *d_j_rptr = nullptr;
     int32_t *d_pa = nullptr, *d_pb = nullptr, *d_jt_row = nullptr, *d_jt_src = nullptr, *d_j_col = nullptr;
-    double *d_q = nullptr, *d_jv = nullptr, *d_vn = nullptr, *d_vm = nullptr, *d_vn2 = nullptr, *d_out = nullptr;   // staging for host callers
+    double* d_vm = nullptr;             // [m] work vector J x + obs_diff of gmrf_assemble_rhs
+    DevBuf arena;                       // host arguments of the current call (Staging)
     // the batch calls: Q's own pattern (0-based; symmetric, so its CSC arrays are read by rows), uploaded by the first objective
     std::vector<int64_t> q_ptr;
     std::vector<int32_t> q_row;
     int64_t* d_q_ptr = nullptr;
     int32_t* d_q_row = nullptr;
-    double *d_bstage = nullptr, *d_bpart = nullptr;        // staging of host arrays / partial sums of the batch calls
-    int64_t bstage_cap = 0, bpart_cap = 0;
+    DevBuf bpart;                       // work arrays of the batch calls: [batch][m] of the rhs, the objective's partial sums
 };
 
 gmrf_status gmrf_assemble_create(int32_t device, void* stream, int64_t n, const int64_t* q_colptr, const int64_t* q_rowval,
@@ -3741,7 +3685,9 @@ gmrf_status gmrf_assemble_create(int32_t device, void* stream, int64_t n, const 
     }
     // result column j = rows of Q's column j  U  { i : J[k,i] != 0 and J[k,j] != 0 for some k }
     struct Prod { int64_t i; int32_t k, a, b; };
-    auto* as = new gmrf_assembler();
+    // (whatever fails from here on, the guard's gmrf_assemble_destroy releases what has been built so far)
+    std::unique_ptr<gmrf_assembler, gmrf_status (*)(gmrf_assembler*)> guard(new gmrf_assembler(), gmrf_assemble_destroy);
+    gmrf_assembler* as = guard.get();
     as->n = n; as->m = m; as->nnz_q = nnz_q; as->nnz_j = nnz_j;
     as->colptr.assign((size_t)n + 1, 0);
     std::vector<int64_t> pptr(1, 0), qmap;
@@ -3762,7 +3708,7 @@ gmrf_status gmrf_assemble_create(int32_t device, void* stream, int64_t n, const 
         while (pi < prods.size() || qp < qe) {
             const int64_t rq = qp < qe ? q_rowval[qp] - b : INT64_MAX, rp = pi < prods.size() ? prods[pi].i : INT64_MAX;
             const int64_t r = std::min(rq, rp);
-            if (r < 0 || r >= n || r <= last_row) { delete as; return bad_shape("Q rows must be ascending within a column and in range"); }
+            if (r < 0 || r >= n || r <= last_row) return bad_shape("Q rows must be ascending within a column and in range");
             last_row = r;
             as->rowval.push_back(r);
             qmap.push_back(rq == r ? qp++ : -1);
@@ -3778,17 +3724,8 @@ gmrf_status gmrf_assemble_create(int32_t device, void* stream, int64_t n, const 
         for (int64_t j = 0; j <= n; ++j) as->q_ptr[(size_t)j] = q_colptr[j] - b;
         for (int64_t e = 0; e < nnz_q; ++e) as->q_row[(size_t)e] = (int32_t)(q_rowval[e] - b);
     }
-    if (device >= 0) {
-        int count = 0;
-        if (hipGetDeviceCount(&count) != hipSuccess || count <= 0 || device >= count) {
-            delete as;
-            g_last_error = "no HIP device visible (libgmrf_hip needs an MI355X / gfx950 GPU)";
-            return GMRF_ERR_NO_DEVICE;
-        }
-        as->device = device;
-        HIPCHK(hipSetDevice(device));
-        if (stream) as->stream = (hipStream_t)stream;
-        else { HIPCHK(hipStreamCreate(&as->stream)); as->own_stream = true; }
+    GCHK(as->open(device, stream, hipStreamDefault, "gmrf_assemble_create"));      // (a blocking stream: inherited, not chosen)
+    if (as->device >= 0) {
         auto up = [&](auto** d, const auto& v) -> hipError_t {
             using T = typename std::remove_reference<decltype(v[0])>::type;
             hipError_t e = hipMalloc((void**)d, std::max<size_t>(v.size(), 1) * sizeof(T));
@@ -3802,20 +3739,18 @@ gmrf_status gmrf_assemble_create(int32_t device, void* stream, int64_t n, const 
         HIPCHK(up(&as->d_jt_ptr, jt_ptr)); HIPCHK(up(&as->d_jt_row, jt_row)); HIPCHK(up(&as->d_jt_src, jt_src));
         HIPCHK(up(&as->d_j_rptr, j_rptr)); HIPCHK(up(&as->d_j_col, j_col));
     }
-    *out = as;
+    *out = guard.release();
     return GMRF_OK;
 }
 
 gmrf_status gmrf_assemble_destroy(gmrf_assembler* as) {
     if (!as) return GMRF_OK;
-    if (as->device >= 0) {
-        (void)hipSetDevice(as->device);
-        (void)hipStreamSynchronize(as->stream);
+    as->close();
+    if (as->has_device()) {
         free_dev(as->d_pptr); free_dev(as->d_qmap); free_dev(as->d_pa); free_dev(as->d_pb);
         free_dev(as->d_jt_ptr); free_dev(as->d_jt_row); free_dev(as->d_jt_src); free_dev(as->d_j_rptr); free_dev(as->d_j_col);
-        free_dev(as->d_q); free_dev(as->d_jv); free_dev(as->d_vn); free_dev(as->d_vm); free_dev(as->d_vn2); free_dev(as->d_out);
-        free_dev(as->d_q_ptr); free_dev(as->d_q_row); free_dev(as->d_bstage); free_dev(as->d_bpart);
-        if (as->own_stream) (void)hipStreamDestroy(as->stream);
+        free_dev(as->d_vm); free_dev(as->d_q_ptr); free_dev(as->d_q_row);
+        as->arena.release(); as->bpart.release();
     }
     delete as;
     return GMRF_OK;
@@ -3831,88 +3766,64 @@ gmrf_status gmrf_assemble_pattern(const gmrf_assembler* as, int64_t* nnz_out, in
     return GMRF_OK;
 }
 
-// host pointer -> staged device copy (lazily allocated buffer of `cap` doubles)
-static gmrf_status as_stage_in(gmrf_assembler* as, const double* p, int64_t count, double** buf, const double** d) {
-    if (!p) { *d = nullptr; return GMRF_OK; }
-    if (is_device_ptr(p)) { *d = p; return GMRF_OK; }
-    if (!*buf) HIPCHK(hipMalloc(buf, sizeof(double) * std::max<int64_t>(count, 1)));
-    HIPCHK(hipMemcpyAsync(*buf, p, sizeof(double) * count, hipMemcpyHostToDevice, as->stream));
-    *d = *buf;
-    return GMRF_OK;
-}
-
-static gmrf_status as_numeric_ready(gmrf_assembler* as) {
-    if (!as) return bad_shape("null assembler");
-    if (as->device < 0) { g_last_error = "symbolic-only assembler (created with device -1)"; return GMRF_ERR_NO_DEVICE; }
-    HIPCHK(hipSetDevice(as->device));
-    return GMRF_OK;
-}
+static const char* const AS_PATTERN_ONLY = "symbolic-only assembler";
 
 gmrf_status gmrf_assemble_precision(gmrf_assembler* as, const double* q_nzval, const double* j_vals, double noise,
                                     double* out_nzval) {
-    GCHK(as_numeric_ready(as));
+    if (!as) return bad_shape("null assembler");
+    GCHK(as->ready(AS_PATTERN_ONLY));
     if (!q_nzval || !j_vals || !out_nzval) return bad_shape("null pointer");
     const double *dq, *dj;
-    GCHK(as_stage_in(as, q_nzval, as->nnz_q, &as->d_q, &dq));
-    GCHK(as_stage_in(as, j_vals, as->nnz_j, &as->d_jv, &dj));
-    const bool dev = is_device_ptr(out_nzval);
-    double* d_out = out_nzval;
-    if (!dev) {
-        if (!as->d_out) HIPCHK(hipMalloc(&as->d_out, sizeof(double) * std::max<int64_t>(as->nnz_out, 1)));
-        d_out = as->d_out;
-    }
+    double* d_out;
+    Staging args(as->arena);
+    args.in(q_nzval, sizeof(double) * as->nnz_q, &dq);
+    args.in(j_vals, sizeof(double) * as->nnz_j, &dj);
+    args.out(out_nzval, sizeof(double) * as->nnz_out, &d_out);
+    GCHK(args.commit(as->stream));
     hipLaunchKernelGGL(assemble_precision, dim3((unsigned)((as->nnz_out + 255) / 256)), dim3(256), 0, as->stream, as->d_pptr,
                        as->d_pa, as->d_pb, as->d_qmap, dq, dj, noise, as->nnz_out, d_out);
     HIPCHK(hipGetLastError());
-    if (!dev) HIPCHK(hipMemcpyAsync(out_nzval, d_out, sizeof(double) * as->nnz_out, hipMemcpyDeviceToHost, as->stream));
+    GCHK(args.flush(as->stream));
     HIPCHK(hipStreamSynchronize(as->stream));
     return GMRF_OK;
 }
 
 gmrf_status gmrf_assemble_rhs(gmrf_assembler* as, const double* base, const double* j_vals, const double* x,
                               const double* obs_diff, double noise, double* out) {
-    GCHK(as_numeric_ready(as));
+    if (!as) return bad_shape("null assembler");
+    GCHK(as->ready(AS_PATTERN_ONLY));
     if (!j_vals || !x || !out) return bad_shape("null pointer");
     const double *dj, *dx, *dadd, *dbase;
-    GCHK(as_stage_in(as, j_vals, as->nnz_j, &as->d_jv, &dj));
-    GCHK(as_stage_in(as, x, as->n, &as->d_vn, &dx));
-    if (!as->d_vm) HIPCHK(hipMalloc(&as->d_vm, sizeof(double) * 2 * as->m));
-    dadd = obs_diff;
-    if (obs_diff && !is_device_ptr(obs_diff)) {
-        HIPCHK(hipMemcpyAsync(as->d_vm + as->m, obs_diff, sizeof(double) * as->m, hipMemcpyHostToDevice, as->stream));
-        dadd = as->d_vm + as->m;
-    }
-    GCHK(as_stage_in(as, base, as->n, &as->d_vn2, &dbase));
+    double* d_out;
+    Staging args(as->arena);
+    args.in(j_vals, sizeof(double) * as->nnz_j, &dj);
+    args.in(x, sizeof(double) * as->n, &dx);
+    args.in(obs_diff, sizeof(double) * as->m, &dadd);
+    args.in(base, sizeof(double) * as->n, &dbase);
+    args.out(out, sizeof(double) * as->n, &d_out);
+    GCHK(args.commit(as->stream));
+    if (!as->d_vm) HIPCHK(hipMalloc(&as->d_vm, sizeof(double) * as->m));
     // v = J x + obs_diff ;  out = base + noise * J' v
     hipLaunchKernelGGL(assemble_j_apply, dim3((unsigned)((as->m + 255) / 256)), dim3(256), 0, as->stream, as->d_j_rptr,
                        as->d_j_col, dj, dx, dadd, as->m, as->d_vm);
-    const bool dev = is_device_ptr(out);
-    double* d_out = out;
-    if (!dev) {
-        if (!as->d_out) HIPCHK(hipMalloc(&as->d_out, sizeof(double) * std::max<int64_t>(std::max(as->nnz_out, as->n), 1)));
-        d_out = as->d_out;
-    }
     hipLaunchKernelGGL(assemble_jt_apply, dim3((unsigned)((as->n + 255) / 256)), dim3(256), 0, as->stream, as->d_jt_ptr,
                        as->d_jt_row, as->d_jt_src, dj, as->d_vm, dbase, noise, as->n, d_out);
     HIPCHK(hipGetLastError());
-    if (!dev) HIPCHK(hipMemcpyAsync(out, d_out, sizeof(double) * as->n, hipMemcpyDeviceToHost, as->stream));
+    GCHK(args.flush(as->stream));
     HIPCHK(hipStreamSynchronize(as->stream));
     return GMRF_OK;
 }
 
 // --------------------------------------------------------------------------------- FEM block assembly (Darcy, P1)
-struct gmrf_darcy_p1 {
-    int device = -1;                    // -1: pattern only
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
+struct gmrf_darcy_p1 : DevCtx {         // device -1: pattern only
     int64_t nx = 0, ny = 0, n = 0, nnz = 0;
     int order = 1;                      // 1: P1 triangles on the nx x ny nodes; 2: quadratic triangles, dofs = the (2 nx - 1) x (2 ny - 1) lattice
     std::vector<int64_t> rowptr, colidx;            // 0-based
     int64_t* d_rowptr = nullptr;
     int32_t* d_colidx = nullptr;        // order 2: the pattern's columns and the Dirichlet mask for the generic apply! kernels
     uint8_t* d_pres = nullptr;
-    double *d_diag = nullptr, *d_mean = nullptr, *d_table = nullptr, *d_vals = nullptr, *d_f = nullptr;   // work + staging
-    int64_t table_cap = 0;
+    double *d_diag = nullptr, *d_mean = nullptr;    // work: |diagonal|, its mean
+    DevBuf arena;                       // host arguments of the current call (Staging)
 };
 
 // Pattern of the quadratic-triangle lattice: row (I, J) couples with every node of every cell it belongs to (the same
@@ -3952,7 +3863,8 @@ static void darcy_p2_pattern(gmrf_darcy_p1* d) {
 
 static gmrf_status darcy_create(int32_t device, void* stream, int64_t nx, int64_t ny, int order, gmrf_darcy_p1** out) {
     if (!out || nx < 2 || ny < 2 || nx > 32768 || ny > 32768 || (order == 2 && (nx > 16384 || ny > 16384))) return bad_shape("bad Darcy mesh size");
-    auto* d = new gmrf_darcy_p1();
+    std::unique_ptr<gmrf_darcy_p1, gmrf_status (*)(gmrf_darcy_p1*)> guard(new gmrf_darcy_p1(), gmrf_darcy_p1_destroy);
+    gmrf_darcy_p1* d = guard.get();
     d->nx = nx; d->ny = ny; d->n = nx * ny; d->order = order;
     if (order == 2) darcy_p2_pattern(d);
     else {
@@ -3970,21 +3882,12 @@ static gmrf_status darcy_create(int32_t device, void* stream, int64_t nx, int64_
         }
     }
     d->nnz = (int64_t)d->colidx.size();
-    if (device >= 0) {
-        int count = 0;
-        if (hipGetDeviceCount(&count) != hipSuccess || count <= 0 || device >= count) {
-            (void)hipGetLastError();
-            delete d;
-            g_last_error = "no HIP device visible (libgmrf_hip needs an MI355X / gfx950 GPU)";
-            return GMRF_ERR_NO_DEVICE;
-        }
-        d->device = device;
-        hipError_t e = hipSetDevice(device);
-        if (e == hipSuccess) { if (stream) d->stream = (hipStream_t)stream; else { e = hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking); d->own_stream = (e == hipSuccess); } }
-        if (e == hipSuccess) e = hipMalloc(&d->d_rowptr, sizeof(int64_t) * (d->n + 1));
-        if (e == hipSuccess) e = hipMalloc(&d->d_diag, sizeof(double) * d->n);
-        if (e == hipSuccess) e = hipMalloc(&d->d_mean, sizeof(double));
-        if (e == hipSuccess) e = hipMemcpyAsync(d->d_rowptr, d->rowptr.data(), sizeof(int64_t) * (d->n + 1), hipMemcpyHostToDevice, d->stream);
+    GCHK(d->open(device, stream, hipStreamNonBlocking, "gmrf_darcy_p1_create"));
+    if (d->device >= 0) {
+        HIPCHK(hipMalloc(&d->d_rowptr, sizeof(int64_t) * (d->n + 1)));
+        HIPCHK(hipMalloc(&d->d_diag, sizeof(double) * d->n));
+        HIPCHK(hipMalloc(&d->d_mean, sizeof(double)));
+        HIPCHK(hipMemcpyAsync(d->d_rowptr, d->rowptr.data(), sizeof(int64_t) * (d->n + 1), hipMemcpyHostToDevice, d->stream));
         std::vector<int32_t> col32;
         std::vector<uint8_t> pres;
         if (order == 2) {
@@ -3992,19 +3895,14 @@ static gmrf_status darcy_create(int32_t device, void* stream, int64_t nx, int64_
             col32.assign(d->colidx.begin(), d->colidx.end());
             pres.resize((size_t)d->n);
             for (int64_t r = 0; r < d->n; ++r) { const int64_t I = r % W, J = r / W; pres[(size_t)r] = (I == 0 || J == 0 || I == W - 1 || J == H - 1) ? 1 : 0; }
-            if (e == hipSuccess) e = hipMalloc(&d->d_colidx, sizeof(int32_t) * d->nnz);
-            if (e == hipSuccess) e = hipMalloc(&d->d_pres, (size_t)d->n);
-            if (e == hipSuccess) e = hipMemcpyAsync(d->d_colidx, col32.data(), sizeof(int32_t) * d->nnz, hipMemcpyHostToDevice, d->stream);
-            if (e == hipSuccess) e = hipMemcpyAsync(d->d_pres, pres.data(), (size_t)d->n, hipMemcpyHostToDevice, d->stream);
+            HIPCHK(hipMalloc(&d->d_colidx, sizeof(int32_t) * d->nnz));
+            HIPCHK(hipMalloc(&d->d_pres, (size_t)d->n));
+            HIPCHK(hipMemcpyAsync(d->d_colidx, col32.data(), sizeof(int32_t) * d->nnz, hipMemcpyHostToDevice, d->stream));
+            HIPCHK(hipMemcpyAsync(d->d_pres, pres.data(), (size_t)d->n, hipMemcpyHostToDevice, d->stream));
         }
-        if (e == hipSuccess) e = hipStreamSynchronize(d->stream);
-        if (e != hipSuccess) {
-            g_last_error = std::string("gmrf_darcy_p1_create: ") + hipGetErrorString(e);
-            (void)gmrf_darcy_p1_destroy(d);
-            return GMRF_ERR_HIP;
-        }
+        HIPCHK(hipStreamSynchronize(d->stream));
     }
-    *out = d;
+    *out = guard.release();
     return GMRF_OK;
 }
 
@@ -4018,12 +3916,10 @@ gmrf_status gmrf_darcy_p2_create(int32_t device, void* stream, int64_t nx, int64
 
 gmrf_status gmrf_darcy_p1_destroy(gmrf_darcy_p1* d) {
     if (!d) return GMRF_OK;
-    if (d->device >= 0) {
-        (void)hipSetDevice(d->device);
-        if (d->stream) (void)hipStreamSynchronize(d->stream);
-        free_dev(d->d_rowptr); free_dev(d->d_diag); free_dev(d->d_mean); free_dev(d->d_table); free_dev(d->d_vals); free_dev(d->d_f);
-        free_dev(d->d_colidx); free_dev(d->d_pres);
-        if (d->own_stream) (void)hipStreamDestroy(d->stream);
+    d->close();
+    if (d->has_device()) {
+        free_dev(d->d_rowptr); free_dev(d->d_diag); free_dev(d->d_mean); free_dev(d->d_colidx); free_dev(d->d_pres);
+        d->arena.release();
     }
     delete d;
     return GMRF_OK;
@@ -4040,26 +3936,19 @@ gmrf_status gmrf_darcy_p1_pattern(const gmrf_darcy_p1* d, int64_t* nnz_out, int6
 gmrf_status gmrf_darcy_p1_assemble(gmrf_darcy_p1* d, const double* coeff_table, int64_t ng, double beta, double* vals_out,
                                    double* f_out) {
     if (!d || !coeff_table || !vals_out || !f_out || ng < 2 || ng > 46340) return bad_shape("bad Darcy assembly arguments");
-    if (d->device < 0) { g_last_error = "pattern-only Darcy assembler (created with device -1)"; return GMRF_ERR_NO_DEVICE; }
-    HIPCHK(hipSetDevice(d->device));
-    const double* d_tab = coeff_table;
-    if (!is_device_ptr(coeff_table)) {
-        if (d->table_cap < ng * ng) {
-            free_dev(d->d_table); d->d_table = nullptr; d->table_cap = 0;
-            HIPCHK(hipMalloc(&d->d_table, sizeof(double) * ng * ng));
-            d->table_cap = ng * ng;
-        }
-        HIPCHK(hipMemcpyAsync(d->d_table, coeff_table, sizeof(double) * ng * ng, hipMemcpyHostToDevice, d->stream));
-        d_tab = d->d_table;
-    }
-    const bool v_dev = is_device_ptr(vals_out), f_dev = is_device_ptr(f_out);
-    if (!v_dev && !d->d_vals) HIPCHK(hipMalloc(&d->d_vals, sizeof(double) * d->nnz));
-    if (!f_dev && !d->d_f) HIPCHK(hipMalloc(&d->d_f, sizeof(double) * d->n));
+    GCHK(d->ready("pattern-only Darcy assembler"));
+    const double* d_tab;
+    double *d_vals, *d_f;
+    Staging args(d->arena);
+    args.in(coeff_table, sizeof(double) * ng * ng, &d_tab);
+    args.out(vals_out, sizeof(double) * d->nnz, &d_vals);
+    args.out(f_out, sizeof(double) * d->n, &d_f);
+    GCHK(args.commit(d->stream));
     const dim3 grid((unsigned)((d->n + 255) / 256));
     if (d->order == 2) {
         DarcyP2Args a;
         a.nx = (int)d->nx; a.ny = (int)d->ny; a.ng = (int)ng; a.table = d_tab; a.rowptr = d->d_rowptr; a.beta = beta;
-        a.vals = v_dev ? vals_out : d->d_vals; a.f = f_dev ? f_out : d->d_f; a.diag = d->d_diag;
+        a.vals = d_vals; a.f = d_f; a.diag = d->d_diag;
         hipLaunchKernelGGL(darcy_p2_rows, grid, dim3(256), 0, d->stream, a);
         hipLaunchKernelGGL(darcy_meandiag, dim3(1), dim3(256), 0, d->stream, d->d_diag, d->n, d->d_mean);
         // apply!(G, f, ch): rows and columns of the boundary lattice points, meandiag on their diagonal, f = 0 there
@@ -4068,29 +3957,23 @@ gmrf_status gmrf_darcy_p1_assemble(gmrf_darcy_p1* d, const double* coeff_table, 
     } else {
         DarcyP1Args a;
         a.nx = (int)d->nx; a.ny = (int)d->ny; a.ng = (int)ng; a.table = d_tab; a.rowptr = d->d_rowptr; a.beta = beta;
-        a.vals = v_dev ? vals_out : d->d_vals; a.f = f_dev ? f_out : d->d_f; a.diag = d->d_diag;
+        a.vals = d_vals; a.f = d_f; a.diag = d->d_diag;
         hipLaunchKernelGGL(darcy_p1_rows, grid, dim3(256), 0, d->stream, a);
         hipLaunchKernelGGL(darcy_meandiag, dim3(1), dim3(256), 0, d->stream, d->d_diag, d->n, d->d_mean);
         hipLaunchKernelGGL(darcy_p1_constrain, grid, dim3(256), 0, d->stream, a, d->d_mean);
     }
     HIPCHK(hipGetLastError());
-    if (!v_dev) HIPCHK(hipMemcpyAsync(vals_out, d->d_vals, sizeof(double) * d->nnz, hipMemcpyDeviceToHost, d->stream));
-    if (!f_dev) HIPCHK(hipMemcpyAsync(f_out, d->d_f, sizeof(double) * d->n, hipMemcpyDeviceToHost, d->stream));
+    GCHK(args.flush(d->stream));
     HIPCHK(hipStreamSynchronize(d->stream));
     return GMRF_OK;
 }
 
 // --------------------------------------------------------------------------------- Burgers tangent (8f rank 4)
-struct gmrf_burgers_p1 {
-    int device = -1;                    // -1: pattern only
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
+struct gmrf_burgers_p1 : DevCtx {       // device -1: pattern only
     int64_t ns = 0, nt = 0, rows = 0, nnz = 0;
     int order = 1;                      // 1: P1 line (6 entries per row), 2: quadratic line (10 / 6 entries per row)
     double dt = 0.0, nu = 0.0;
-    double *d_w = nullptr, *d_vals = nullptr, *d_f = nullptr;       // staging for host callers
-    double* d_bstage = nullptr;         // ... of gmrf_burgers_p1_tangent_batch
-    int64_t bstage_cap = 0;
+    DevBuf arena;                       // host arguments of the current call (Staging)
 };
 
 static gmrf_status burgers_line_create(int32_t device, void* stream, int64_t ns, int64_t nt, double dt, double nu, int order,
@@ -4098,22 +3981,11 @@ static gmrf_status burgers_line_create(int32_t device, void* stream, int64_t ns,
     if (!out || ns < 3 || nt < 2 || ns > (1 << 24) || nt > (1 << 20) || !(dt > 0.0) || !(nu >= 0.0))
         return bad_shape("bad Burgers mesh (ns >= 3 nodes, nt >= 2 slices, dt > 0, nu >= 0)");
     if (order == 2 && (ns % 2 || ns < 6)) return bad_shape("the quadratic line has an even number of dofs (>= 6): two per cell");
-    auto* b = new gmrf_burgers_p1();
+    std::unique_ptr<gmrf_burgers_p1, gmrf_status (*)(gmrf_burgers_p1*)> guard(new gmrf_burgers_p1(), gmrf_burgers_p1_destroy);
+    gmrf_burgers_p1* b = guard.get();
     b->ns = ns; b->nt = nt; b->rows = (nt - 1) * ns; b->nnz = b->rows * (order == 2 ? 8 : 6); b->dt = dt; b->nu = nu; b->order = order;
-    if (device >= 0) {
-        int count = 0;
-        if (hipGetDeviceCount(&count) != hipSuccess || count <= 0 || device >= count) {
-            (void)hipGetLastError();
-            delete b;
-            g_last_error = "no HIP device visible (libgmrf_hip needs an MI355X / gfx950 GPU)";
-            return GMRF_ERR_NO_DEVICE;
-        }
-        b->device = device;
-        hipError_t e = hipSetDevice(device);
-        if (e == hipSuccess) { if (stream) b->stream = (hipStream_t)stream; else { e = hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking); b->own_stream = (e == hipSuccess); } }
-        if (e != hipSuccess) { g_last_error = std::string("gmrf_burgers_p1_create: ") + hipGetErrorString(e); delete b; return GMRF_ERR_HIP; }
-    }
-    *out = b;
+    GCHK(b->open(device, stream, hipStreamNonBlocking, "gmrf_burgers_p1_create"));
+    *out = guard.release();
     return GMRF_OK;
 }
 
@@ -4126,12 +3998,8 @@ gmrf_status gmrf_burgers_p2_create(int32_t device, void* stream, int64_t ns, int
 
 gmrf_status gmrf_burgers_p1_destroy(gmrf_burgers_p1* b) {
     if (!b) return GMRF_OK;
-    if (b->device >= 0) {
-        (void)hipSetDevice(b->device);
-        if (b->stream) (void)hipStreamSynchronize(b->stream);
-        free_dev(b->d_w); free_dev(b->d_vals); free_dev(b->d_f); free_dev(b->d_bstage);
-        if (b->own_stream) (void)hipStreamDestroy(b->stream);
-    }
+    b->close();
+    if (b->has_device()) b->arena.release();
     delete b;
     return GMRF_OK;
 }
@@ -4176,61 +4044,24 @@ gmrf_status gmrf_burgers_p1_pattern(const gmrf_burgers_p1* b, int64_t* nnz_out, 
 
 gmrf_status gmrf_burgers_p1_tangent(gmrf_burgers_p1* b, const double* w, double* vals_out, double* f_out) {
     if (!b || !w || !vals_out || !f_out) return bad_shape("bad Burgers tangent arguments");
-    if (b->device < 0) { g_last_error = "pattern-only Burgers assembler (created with device -1)"; return GMRF_ERR_NO_DEVICE; }
-    HIPCHK(hipSetDevice(b->device));
-    const int64_t n = b->ns * b->nt;
-    const double* d_w = w;
-    if (!is_device_ptr(w)) {
-        if (!b->d_w) HIPCHK(hipMalloc(&b->d_w, sizeof(double) * n));
-        HIPCHK(hipMemcpyAsync(b->d_w, w, sizeof(double) * n, hipMemcpyHostToDevice, b->stream));
-        d_w = b->d_w;
-    }
-    const bool v_dev = is_device_ptr(vals_out), f_dev = is_device_ptr(f_out);
-    if (!v_dev && !b->d_vals) HIPCHK(hipMalloc(&b->d_vals, sizeof(double) * b->nnz));
-    if (!f_dev && !b->d_f) HIPCHK(hipMalloc(&b->d_f, sizeof(double) * b->rows));
+    GCHK(b->ready("pattern-only Burgers assembler"));
     BurgersP1Args a;
-    a.ns = (int)b->ns; a.nt = (int)b->nt; a.dt = b->dt; a.nu = b->nu; a.w = d_w;
-    a.vals = v_dev ? vals_out : b->d_vals; a.f = f_dev ? f_out : b->d_f;
+    a.ns = (int)b->ns; a.nt = (int)b->nt; a.dt = b->dt; a.nu = b->nu;
+    Staging args(b->arena);
+    args.in(w, sizeof(double) * b->ns * b->nt, &a.w);
+    args.out(vals_out, sizeof(double) * b->nnz, &a.vals);
+    args.out(f_out, sizeof(double) * b->rows, &a.f);
+    GCHK(args.commit(b->stream));
     if (b->order == 2) hipLaunchKernelGGL(burgers_p2_rows, dim3((unsigned)((b->rows + 255) / 256)), dim3(256), 0, b->stream, a);
     else hipLaunchKernelGGL(burgers_p1_rows, dim3((unsigned)((b->rows + 255) / 256)), dim3(256), 0, b->stream, a);
     HIPCHK(hipGetLastError());
-    if (!v_dev) HIPCHK(hipMemcpyAsync(vals_out, b->d_vals, sizeof(double) * b->nnz, hipMemcpyDeviceToHost, b->stream));
-    if (!f_dev) HIPCHK(hipMemcpyAsync(f_out, b->d_f, sizeof(double) * b->rows, hipMemcpyDeviceToHost, b->stream));
+    GCHK(args.flush(b->stream));
     HIPCHK(hipStreamSynchronize(b->stream));
     return GMRF_OK;
 }
 
 // --------------------------------------------------------------------------------- batch forms of the Gauss-Newton glue
-// Problem-major arrays ([batch][...]); host or device pointers like the one-problem calls.  Host arrays pass through one staging
-// buffer per handle.
-struct StageItem { const double* user; int64_t count; bool out; double* dev; };
-
-static gmrf_status stage_items(hipStream_t st, double** buf, int64_t* cap, StageItem* it, int nit) {
-    int64_t need = 0;
-    for (int i = 0; i < nit; ++i) if (it[i].user && !is_device_ptr(it[i].user)) need += it[i].count;
-    if (need > *cap) {
-        HIPCHK(hipStreamSynchronize(st));
-        free_dev(*buf); *buf = nullptr; *cap = 0;
-        HIPCHK(hipMalloc(buf, sizeof(double) * (size_t)need));
-        *cap = need;
-    }
-    int64_t off = 0;
-    for (int i = 0; i < nit; ++i) {
-        if (!it[i].user) { it[i].dev = nullptr; continue; }
-        if (is_device_ptr(it[i].user)) { it[i].dev = const_cast<double*>(it[i].user); continue; }
-        it[i].dev = *buf + off; off += it[i].count;
-        if (!it[i].out) HIPCHK(hipMemcpyAsync(it[i].dev, it[i].user, sizeof(double) * it[i].count, hipMemcpyHostToDevice, st));
-    }
-    return GMRF_OK;
-}
-
-static gmrf_status unstage_items(hipStream_t st, const StageItem* it, int nit) {
-    for (int i = 0; i < nit; ++i)
-        if (it[i].out && it[i].user && it[i].dev != it[i].user)
-            HIPCHK(hipMemcpyAsync(const_cast<double*>(it[i].user), it[i].dev, sizeof(double) * it[i].count, hipMemcpyDeviceToHost, st));
-    return GMRF_OK;
-}
-
+// Problem-major arrays ([batch][...]); host or device pointers like the one-problem calls.
 static bool batch_ok(int64_t batch) { return batch >= 1 && batch <= 4096; }
 
 static gmrf_status launch_tangent_batch(const gmrf_burgers_p1* b, hipStream_t st, int64_t batch, const double* d_w, double* d_vals,
@@ -4246,12 +4077,16 @@ static gmrf_status launch_tangent_batch(const gmrf_burgers_p1* b, hipStream_t st
 
 gmrf_status gmrf_burgers_p1_tangent_batch(gmrf_burgers_p1* b, int64_t batch, const double* w, double* vals_out, double* f_out) {
     if (!b || !w || !vals_out || !f_out || !batch_ok(batch)) return bad_shape("bad Burgers tangent arguments (batch in [1, 4096])");
-    if (b->device < 0) { g_last_error = "pattern-only Burgers assembler (created with device -1)"; return GMRF_ERR_NO_DEVICE; }
-    HIPCHK(hipSetDevice(b->device));
-    StageItem it[3] = {{w, batch * b->ns * b->nt, false, nullptr}, {vals_out, batch * b->nnz, true, nullptr}, {f_out, batch * b->rows, true, nullptr}};
-    GCHK(stage_items(b->stream, &b->d_bstage, &b->bstage_cap, it, 3));
-    GCHK(launch_tangent_batch(b, b->stream, batch, it[0].dev, it[1].dev, it[2].dev));
-    GCHK(unstage_items(b->stream, it, 3));
+    GCHK(b->ready("pattern-only Burgers assembler"));
+    const double* d_w;
+    double *d_vals, *d_f;
+    Staging args(b->arena);
+    args.in(w, sizeof(double) * batch * b->ns * b->nt, &d_w);
+    args.out(vals_out, sizeof(double) * batch * b->nnz, &d_vals);
+    args.out(f_out, sizeof(double) * batch * b->rows, &d_f);
+    GCHK(args.commit(b->stream));
+    GCHK(launch_tangent_batch(b, b->stream, batch, d_w, d_vals, d_f));
+    GCHK(args.flush(b->stream));
     HIPCHK(hipStreamSynchronize(b->stream));
     return GMRF_OK;
 }
@@ -4313,35 +4148,36 @@ gmrf_status gmrf_assemble_precision_batch(gmrf_assembler* as, int64_t batch, con
                                           const double* j_vals, double noise, double* out_nzval) {
     if (!as || !q_nzval || !j_vals || !out_nzval || !batch_ok(batch)) return bad_shape("null pointer or batch outside [1, 4096]");
     GCHK(q_stride_ok(as, q_stride));
-    GCHK(as_numeric_ready(as));
-    StageItem it[3] = {{q_nzval, q_stride ? batch * as->nnz_q : as->nnz_q, false, nullptr}, {j_vals, batch * as->nnz_j, false, nullptr},
-                       {out_nzval, batch * as->nnz_out, true, nullptr}};
-    GCHK(stage_items(as->stream, &as->d_bstage, &as->bstage_cap, it, 3));
-    GCHK(launch_precision_batch(as, as->stream, batch, it[0].dev, q_stride, it[1].dev, noise, it[2].dev));
-    GCHK(unstage_items(as->stream, it, 3));
+    GCHK(as->ready(AS_PATTERN_ONLY));
+    const double *d_q, *d_jv;
+    double* d_out;
+    Staging args(as->arena);
+    args.in(q_nzval, sizeof(double) * (q_stride ? batch * as->nnz_q : as->nnz_q), &d_q);
+    args.in(j_vals, sizeof(double) * batch * as->nnz_j, &d_jv);
+    args.out(out_nzval, sizeof(double) * batch * as->nnz_out, &d_out);
+    GCHK(args.commit(as->stream));
+    GCHK(launch_precision_batch(as, as->stream, batch, d_q, q_stride, d_jv, noise, d_out));
+    GCHK(args.flush(as->stream));
     HIPCHK(hipStreamSynchronize(as->stream));
-    return GMRF_OK;
-}
-
-static gmrf_status as_part_buffer(gmrf_assembler* as, int64_t elems) {
-    if (as->d_bpart && as->bpart_cap >= elems) return GMRF_OK;
-    HIPCHK(hipStreamSynchronize(as->stream));
-    free_dev(as->d_bpart); as->d_bpart = nullptr; as->bpart_cap = 0;
-    HIPCHK(hipMalloc(&as->d_bpart, sizeof(double) * (size_t)elems));
-    as->bpart_cap = elems;
     return GMRF_OK;
 }
 
 gmrf_status gmrf_assemble_rhs_batch(gmrf_assembler* as, int64_t batch, const double* base, const double* j_vals, const double* x,
                                     const double* obs_diff, double noise, double* out) {
     if (!as || !j_vals || !x || !out || !batch_ok(batch)) return bad_shape("null pointer or batch outside [1, 4096]");
-    GCHK(as_numeric_ready(as));
-    StageItem it[5] = {{base, batch * as->n, false, nullptr}, {j_vals, batch * as->nnz_j, false, nullptr}, {x, batch * as->n, false, nullptr},
-                       {obs_diff, batch * as->m, false, nullptr}, {out, batch * as->n, true, nullptr}};
-    GCHK(stage_items(as->stream, &as->d_bstage, &as->bstage_cap, it, 5));
-    GCHK(as_part_buffer(as, batch * as->m));
-    GCHK(launch_rhs_batch(as, as->stream, batch, it[0].dev, it[1].dev, it[2].dev, it[3].dev, noise, as->d_bpart, it[4].dev));
-    GCHK(unstage_items(as->stream, it, 5));
+    GCHK(as->ready(AS_PATTERN_ONLY));
+    const double *d_base, *d_jv, *d_x, *d_add;
+    double* d_out;
+    Staging args(as->arena);
+    args.in(base, sizeof(double) * batch * as->n, &d_base);
+    args.in(j_vals, sizeof(double) * batch * as->nnz_j, &d_jv);
+    args.in(x, sizeof(double) * batch * as->n, &d_x);
+    args.in(obs_diff, sizeof(double) * batch * as->m, &d_add);
+    args.out(out, sizeof(double) * batch * as->n, &d_out);
+    GCHK(args.commit(as->stream));
+    GCHK(as->bpart.reserve(as->stream, sizeof(double) * batch * as->m));
+    GCHK(launch_rhs_batch(as, as->stream, batch, d_base, d_jv, d_x, d_add, noise, as->bpart.as<double>(), d_out));
+    GCHK(args.flush(as->stream));
     HIPCHK(hipStreamSynchronize(as->stream));
     return GMRF_OK;
 }
@@ -4351,14 +4187,20 @@ gmrf_status gmrf_assemble_objective_batch(gmrf_assembler* as, int64_t batch, con
                                           double* obj_out) {
     if (!as || !q_nzval || !x_prior || !x || !obs_diff || !obj_out || !batch_ok(batch)) return bad_shape("null pointer or batch outside [1, 4096]");
     GCHK(q_stride_ok(as, q_stride));
-    GCHK(as_numeric_ready(as));
+    GCHK(as->ready(AS_PATTERN_ONLY));
     GCHK(objective_ready(as));
-    StageItem it[5] = {{q_nzval, q_stride ? batch * as->nnz_q : as->nnz_q, false, nullptr}, {x_prior, batch * as->n, false, nullptr},
-                       {x, batch * as->n, false, nullptr}, {obs_diff, batch * as->m, false, nullptr}, {obj_out, batch, true, nullptr}};
-    GCHK(stage_items(as->stream, &as->d_bstage, &as->bstage_cap, it, 5));
-    GCHK(as_part_buffer(as, batch * objective_chunks(as)));
-    GCHK(launch_objective_batch(as, as->stream, batch, it[0].dev, q_stride, it[1].dev, it[2].dev, it[3].dev, noise, as->d_bpart, it[4].dev));
-    GCHK(unstage_items(as->stream, it, 5));
+    const double *d_q, *d_xp, *d_x, *d_o;
+    double* d_obj;
+    Staging args(as->arena);
+    args.in(q_nzval, sizeof(double) * (q_stride ? batch * as->nnz_q : as->nnz_q), &d_q);
+    args.in(x_prior, sizeof(double) * batch * as->n, &d_xp);
+    args.in(x, sizeof(double) * batch * as->n, &d_x);
+    args.in(obs_diff, sizeof(double) * batch * as->m, &d_o);
+    args.out(obj_out, sizeof(double) * batch, &d_obj);
+    GCHK(args.commit(as->stream));
+    GCHK(as->bpart.reserve(as->stream, sizeof(double) * batch * objective_chunks(as)));
+    GCHK(launch_objective_batch(as, as->stream, batch, d_q, q_stride, d_xp, d_x, d_o, noise, as->bpart.as<double>(), d_obj));
+    GCHK(args.flush(as->stream));
     HIPCHK(hipStreamSynchronize(as->stream));
     return GMRF_OK;
 }
@@ -4378,7 +4220,7 @@ struct gmrf_gn {
     int32_t hist_steps = -1;
     double *d_x = nullptr, *d_xn = nullptr, *d_od = nullptr, *d_on = nullptr, *d_f = nullptr, *d_v = nullptr, *d_jv = nullptr;
     double *d_a = nullptr, *d_rhs = nullptr, *d_q = nullptr, *d_part = nullptr, *d_obj = nullptr;
-    double *d_in = nullptr;              // staged qx_prior, x_prior, y: [3][B][max(n, m)]
+    DevBuf in;                           // arena of a host qx_prior, x_prior, y: sized by gn_alloc, so a run's Staging never allocates
     double *d_last = nullptr, *d_cur = nullptr, *d_hist = nullptr;
     int32_t *d_steps = nullptr, *d_active = nullptr, *d_take = nullptr;
     unsigned* h_active = nullptr;        // mapped host word the stop rule writes
@@ -4393,7 +4235,8 @@ struct gmrf_gn {
 
 static void gn_free(gmrf_gn* g) {
     for (double** p : {&g->d_x, &g->d_xn, &g->d_od, &g->d_on, &g->d_f, &g->d_v, &g->d_jv, &g->d_a, &g->d_rhs, &g->d_q, &g->d_part, &g->d_obj,
-                       &g->d_in, &g->d_last, &g->d_cur, &g->d_hist}) { free_dev(*p); *p = nullptr; }
+                       &g->d_last, &g->d_cur, &g->d_hist}) { free_dev(*p); *p = nullptr; }
+    g->in.release();
     free_dev(g->d_steps); free_dev(g->d_active); free_dev(g->d_take);
     g->d_steps = g->d_active = g->d_take = nullptr;
     g->B = 0; g->hist_steps = -1; g->have_x = false;
@@ -4442,25 +4285,17 @@ static gmrf_status gn_alloc(gmrf_gn* g, int64_t B, int32_t max_steps) {
     if (g->B == B && g->hist_steps >= max_steps) return GMRF_OK;
     HIPCHK(hipStreamSynchronize(g->h->stream));
     gn_free(g);
-    const int64_t n = as->n, m = as->m, wide = std::max(n, m);
+    const int64_t n = as->n, m = as->m;
     auto dm = [&](double** p, int64_t elems) { return hipMalloc(p, sizeof(double) * (size_t)std::max<int64_t>(elems, 1)); };
     HIPCHK(dm(&g->d_x, B * n)); HIPCHK(dm(&g->d_xn, B * n)); HIPCHK(dm(&g->d_rhs, B * n));
     HIPCHK(dm(&g->d_od, B * m)); HIPCHK(dm(&g->d_on, B * m)); HIPCHK(dm(&g->d_f, B * m)); HIPCHK(dm(&g->d_v, B * m));
     HIPCHK(dm(&g->d_jv, B * as->nnz_j)); HIPCHK(dm(&g->d_a, B * as->nnz_out)); HIPCHK(dm(&g->d_q, B * as->nnz_q));
-    HIPCHK(dm(&g->d_part, B * objective_chunks(as))); HIPCHK(dm(&g->d_obj, B)); HIPCHK(dm(&g->d_in, 3 * B * wide));
+    HIPCHK(dm(&g->d_part, B * objective_chunks(as))); HIPCHK(dm(&g->d_obj, B));
+    GCHK(g->in.reserve(g->h->stream, 2 * Staging::padded(sizeof(double) * B * n) + Staging::padded(sizeof(double) * B * m)));      // qx_prior, x_prior, y
     HIPCHK(dm(&g->d_last, B)); HIPCHK(dm(&g->d_cur, B)); HIPCHK(dm(&g->d_hist, B * ((int64_t)max_steps + 1)));
     HIPCHK(hipMalloc(&g->d_steps, sizeof(int32_t) * B)); HIPCHK(hipMalloc(&g->d_active, sizeof(int32_t) * B));
     HIPCHK(hipMalloc(&g->d_take, sizeof(int32_t) * B));
     g->B = B; g->hist_steps = max_steps;
-    return GMRF_OK;
-}
-
-// user array (host or device) -> device: where it lies, or a copy in `buf`
-static gmrf_status gn_in(gmrf_gn* g, const double* p, int64_t count, double* buf, const double** d) {
-    if (!p) { *d = nullptr; return GMRF_OK; }
-    if (is_device_ptr(p)) { *d = p; return GMRF_OK; }
-    HIPCHK(hipMemcpyAsync(buf, p, sizeof(double) * count, hipMemcpyHostToDevice, g->h->stream));
-    *d = buf;
     return GMRF_OK;
 }
 
@@ -4523,9 +4358,11 @@ gmrf_status gmrf_gn_run(gmrf_gn* g, const double* q_nzval, int64_t q_stride, con
     HIPCHK(hipMemcpyAsync(g->d_q, q_nzval, sizeof(double) * q_count, is_device_ptr(q_nzval) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(g->d_x, x, sizeof(double) * B * n, is_device_ptr(x) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
     const double *d_qxp, *d_xp, *d_y;
-    GCHK(gn_in(g, qx_prior, B * n, g->d_in, &d_qxp));
-    GCHK(gn_in(g, x_prior, B * n, g->d_in + B * wide, &d_xp));
-    GCHK(gn_in(g, y, B * m, g->d_in + 2 * B * wide, &d_y));
+    Staging args(g->in);
+    args.in(qx_prior, sizeof(double) * B * n, &d_qxp);
+    args.in(x_prior, sizeof(double) * B * n, &d_xp);
+    args.in(y, sizeof(double) * B * m, &d_y);
+    GCHK(args.commit(st));
     g->q_stride = q_stride; g->noise = noise; g->have_x = true;
     const GnState s = gn_state(g);
     // (slots of the history that no step reaches read NaN: all bits set)
@@ -4586,30 +4423,22 @@ gmrf_status gmrf_gn_finalize(gmrf_gn* g, int32_t* info) {
 }
 
 // --------------------------------------------------------------------------------- shallow-water element kernels
-struct gmrf_swe_p1 {
-    int device = -1;                    // -1: patterns / quadrature points only
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
+struct gmrf_swe_p1 : DevCtx {           // device -1: patterns / quadrature points only
     int64_t nx = 0, ny = 0, nn = 0, n = 0, cells = 0, nnz_k = 0, nnz_s = 0;
     std::vector<int64_t> rowptr_k, col_k, rowptr_s, col_s;     // 0-based
     int64_t *d_rowptr_k = nullptr, *d_rowptr_s = nullptr;
     int32_t *d_col_k = nullptr, *d_col_s = nullptr;
     double *d_dk = nullptr, *d_ds = nullptr, *d_mean = nullptr;   // |diagonals|, three meandiag scalars
-    // staging for host callers
-    double *d_hq = nullptr, *d_kv = nullptr, *d_sv = nullptr, *d_ml = nullptr, *d_g = nullptr, *d_j = nullptr, *d_mt = nullptr, *d_beta = nullptr;
-    uint8_t* d_pres = nullptr;
+    DevBuf arena;                       // host arguments of the current call (Staging)
 };
 
 gmrf_status gmrf_shallow_water_p1_destroy(gmrf_swe_p1* w) {
     if (!w) return GMRF_OK;
-    if (w->device >= 0) {
-        (void)hipSetDevice(w->device);
-        if (w->stream) (void)hipStreamSynchronize(w->stream);
+    w->close();
+    if (w->has_device()) {
         free_dev(w->d_rowptr_k); free_dev(w->d_rowptr_s); free_dev(w->d_col_k); free_dev(w->d_col_s);
         free_dev(w->d_dk); free_dev(w->d_ds); free_dev(w->d_mean);
-        free_dev(w->d_hq); free_dev(w->d_kv); free_dev(w->d_sv); free_dev(w->d_ml); free_dev(w->d_g); free_dev(w->d_j);
-        free_dev(w->d_mt); free_dev(w->d_beta); free_dev(w->d_pres);
-        if (w->own_stream) (void)hipStreamDestroy(w->stream);
+        w->arena.release();
     }
     delete w;
     return GMRF_OK;
@@ -4617,7 +4446,8 @@ gmrf_status gmrf_shallow_water_p1_destroy(gmrf_swe_p1* w) {
 
 gmrf_status gmrf_shallow_water_p1_create(int32_t device, void* stream, int64_t nx, int64_t ny, gmrf_swe_p1** out) {
     if (!out || nx < 2 || ny < 2 || nx > 16384 || ny > 16384) return bad_shape("bad shallow-water mesh size");
-    auto* w = new gmrf_swe_p1();
+    std::unique_ptr<gmrf_swe_p1, gmrf_status (*)(gmrf_swe_p1*)> guard(new gmrf_swe_p1(), gmrf_shallow_water_p1_destroy);
+    gmrf_swe_p1* w = guard.get();
     w->nx = nx; w->ny = ny; w->nn = nx * ny; w->n = 3 * w->nn; w->cells = 2 * (nx - 1) * (ny - 1);
     w->rowptr_k.assign((size_t)w->n + 1, 0); w->rowptr_s.assign((size_t)w->n + 1, 0);
     w->col_k.reserve((size_t)w->n * 21); w->col_s.reserve((size_t)w->n * 7);
@@ -4638,37 +4468,23 @@ gmrf_status gmrf_shallow_water_p1_create(int32_t device, void* stream, int64_t n
         }
     }
     w->nnz_k = (int64_t)w->col_k.size(); w->nnz_s = (int64_t)w->col_s.size();
-    if (device >= 0) {
-        int count = 0;
-        if (hipGetDeviceCount(&count) != hipSuccess || count <= 0 || device >= count) {
-            (void)hipGetLastError();
-            delete w;
-            g_last_error = "no HIP device visible (libgmrf_hip needs an MI355X / gfx950 GPU)";
-            return GMRF_ERR_NO_DEVICE;
-        }
-        w->device = device;
+    GCHK(w->open(device, stream, hipStreamNonBlocking, "gmrf_shallow_water_p1_create"));
+    if (w->device >= 0) {
         std::vector<int32_t> ck(w->col_k.begin(), w->col_k.end()), cs(w->col_s.begin(), w->col_s.end());
-        hipError_t e = hipSetDevice(device);
-        if (e == hipSuccess) { if (stream) w->stream = (hipStream_t)stream; else { e = hipStreamCreateWithFlags(&w->stream, hipStreamNonBlocking); w->own_stream = (e == hipSuccess); } }
-        if (e == hipSuccess) e = hipMalloc(&w->d_rowptr_k, sizeof(int64_t) * (w->n + 1));
-        if (e == hipSuccess) e = hipMalloc(&w->d_rowptr_s, sizeof(int64_t) * (w->n + 1));
-        if (e == hipSuccess) e = hipMalloc(&w->d_col_k, sizeof(int32_t) * w->nnz_k);
-        if (e == hipSuccess) e = hipMalloc(&w->d_col_s, sizeof(int32_t) * w->nnz_s);
-        if (e == hipSuccess) e = hipMalloc(&w->d_dk, sizeof(double) * w->n);
-        if (e == hipSuccess) e = hipMalloc(&w->d_ds, sizeof(double) * w->n);
-        if (e == hipSuccess) e = hipMalloc(&w->d_mean, sizeof(double) * 4);
-        if (e == hipSuccess) e = hipMemcpyAsync(w->d_rowptr_k, w->rowptr_k.data(), sizeof(int64_t) * (w->n + 1), hipMemcpyHostToDevice, w->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(w->d_rowptr_s, w->rowptr_s.data(), sizeof(int64_t) * (w->n + 1), hipMemcpyHostToDevice, w->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(w->d_col_k, ck.data(), sizeof(int32_t) * w->nnz_k, hipMemcpyHostToDevice, w->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(w->d_col_s, cs.data(), sizeof(int32_t) * w->nnz_s, hipMemcpyHostToDevice, w->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(w->stream);
-        if (e != hipSuccess) {
-            g_last_error = std::string("gmrf_shallow_water_p1_create: ") + hipGetErrorString(e);
-            (void)gmrf_shallow_water_p1_destroy(w);
-            return GMRF_ERR_HIP;
-        }
+        HIPCHK(hipMalloc(&w->d_rowptr_k, sizeof(int64_t) * (w->n + 1)));
+        HIPCHK(hipMalloc(&w->d_rowptr_s, sizeof(int64_t) * (w->n + 1)));
+        HIPCHK(hipMalloc(&w->d_col_k, sizeof(int32_t) * w->nnz_k));
+        HIPCHK(hipMalloc(&w->d_col_s, sizeof(int32_t) * w->nnz_s));
+        HIPCHK(hipMalloc(&w->d_dk, sizeof(double) * w->n));
+        HIPCHK(hipMalloc(&w->d_ds, sizeof(double) * w->n));
+        HIPCHK(hipMalloc(&w->d_mean, sizeof(double) * 4));
+        HIPCHK(hipMemcpyAsync(w->d_rowptr_k, w->rowptr_k.data(), sizeof(int64_t) * (w->n + 1), hipMemcpyHostToDevice, w->stream));
+        HIPCHK(hipMemcpyAsync(w->d_rowptr_s, w->rowptr_s.data(), sizeof(int64_t) * (w->n + 1), hipMemcpyHostToDevice, w->stream));
+        HIPCHK(hipMemcpyAsync(w->d_col_k, ck.data(), sizeof(int32_t) * w->nnz_k, hipMemcpyHostToDevice, w->stream));
+        HIPCHK(hipMemcpyAsync(w->d_col_s, cs.data(), sizeof(int32_t) * w->nnz_s, hipMemcpyHostToDevice, w->stream));
+        HIPCHK(hipStreamSynchronize(w->stream));
     }
-    *out = w;
+    *out = guard.release();
     return GMRF_OK;
 }
 
@@ -4703,35 +4519,6 @@ gmrf_status gmrf_shallow_water_p1_qpoints(const gmrf_swe_p1* w, double* xy) {
     return GMRF_OK;
 }
 
-static gmrf_status swe_ready(gmrf_swe_p1* w) {
-    if (!w) return bad_shape("null handle");
-    if (w->device < 0) { g_last_error = "pattern-only shallow-water handle (created with device -1)"; return GMRF_ERR_NO_DEVICE; }
-    HIPCHK(hipSetDevice(w->device));
-    return GMRF_OK;
-}
-
-static gmrf_status swe_in_bytes(gmrf_swe_p1* w, const void* p, size_t bytes, void** buf, const void** d) {
-    if (!p) { *d = nullptr; return GMRF_OK; }
-    if (is_device_ptr(p)) { *d = p; return GMRF_OK; }
-    if (!*buf) HIPCHK(hipMalloc(buf, std::max<size_t>(bytes, 8)));
-    HIPCHK(hipMemcpyAsync(*buf, p, bytes, hipMemcpyHostToDevice, w->stream));
-    *d = *buf;
-    return GMRF_OK;
-}
-static gmrf_status swe_in(gmrf_swe_p1* w, const double* p, int64_t count, double** buf, const double** d) {
-    return swe_in_bytes(w, p, sizeof(double) * (size_t)count, (void**)buf, (const void**)d);
-}
-static gmrf_status swe_in(gmrf_swe_p1* w, const uint8_t* p, int64_t count, uint8_t** buf, const uint8_t** d) {
-    return swe_in_bytes(w, p, (size_t)count, (void**)buf, (const void**)d);
-}
-
-static gmrf_status swe_out(gmrf_swe_p1* w, double* user, int64_t count, double** buf, double** d) {
-    if (is_device_ptr(user)) { *d = user; return GMRF_OK; }
-    if (!*buf) HIPCHK(hipMalloc(buf, sizeof(double) * std::max<int64_t>(count, 1)));
-    *d = *buf;
-    return GMRF_OK;
-}
-
 // meandiag of a vector of |diagonal| values + apply! on CSR values
 static gmrf_status swe_constrain(gmrf_swe_p1* w, const int64_t* d_rowptr, const int32_t* d_col, const uint8_t* d_pres, const double* d_absdiag,
                                  double* d_mean, double* d_vals) {
@@ -4744,15 +4531,18 @@ static gmrf_status swe_constrain(gmrf_swe_p1* w, const int64_t* d_rowptr, const 
 
 gmrf_status gmrf_shallow_water_p1_assemble(gmrf_swe_p1* w, const double* H_q, double k, double f, double g, const uint8_t* prescribed,
                                            double* K_vals, double* M_lumped, double* S_vals) {
-    GCHK(swe_ready(w));
+    if (!w) return bad_shape("null handle");
+    GCHK(w->ready("pattern-only shallow-water handle"));
     if (!H_q || !K_vals || !M_lumped || !S_vals) return bad_shape("null pointer");
     const double* d_hq; const uint8_t* d_pres;
-    GCHK(swe_in(w, H_q, w->cells * 3, &w->d_hq, &d_hq));
-    GCHK(swe_in(w, prescribed, w->n, &w->d_pres, &d_pres));
     double *d_kv, *d_sv, *d_ml;
-    GCHK(swe_out(w, K_vals, w->nnz_k, &w->d_kv, &d_kv));
-    GCHK(swe_out(w, S_vals, w->nnz_s, &w->d_sv, &d_sv));
-    GCHK(swe_out(w, M_lumped, w->n, &w->d_ml, &d_ml));
+    Staging args(w->arena);
+    args.in(H_q, sizeof(double) * w->cells * 3, &d_hq);
+    args.in(prescribed, (size_t)w->n, &d_pres);
+    args.out(K_vals, sizeof(double) * w->nnz_k, &d_kv);
+    args.out(S_vals, sizeof(double) * w->nnz_s, &d_sv);
+    args.out(M_lumped, sizeof(double) * w->n, &d_ml);
+    GCHK(args.commit(w->stream));
     SweP1Args a;
     a.nx = (int)w->nx; a.ny = (int)w->ny; a.Hq = d_hq; a.k = k; a.f = f; a.g = g;
     a.rowptr_k = w->d_rowptr_k; a.rowptr_s = w->d_rowptr_s; a.kv = d_kv; a.sv = d_sv; a.ml = d_ml; a.dk = w->d_dk; a.ds = w->d_ds;
@@ -4767,9 +4557,7 @@ gmrf_status gmrf_shallow_water_p1_assemble(gmrf_swe_p1* w, const double* H_q, do
                            (const double*)(w->d_mean + 2), 0.0, d_ml);
         HIPCHK(hipGetLastError());
     }
-    if (d_kv != K_vals) HIPCHK(hipMemcpyAsync(K_vals, d_kv, sizeof(double) * w->nnz_k, hipMemcpyDeviceToHost, w->stream));
-    if (d_sv != S_vals) HIPCHK(hipMemcpyAsync(S_vals, d_sv, sizeof(double) * w->nnz_s, hipMemcpyDeviceToHost, w->stream));
-    if (d_ml != M_lumped) HIPCHK(hipMemcpyAsync(M_lumped, d_ml, sizeof(double) * w->n, hipMemcpyDeviceToHost, w->stream));
+    GCHK(args.flush(w->stream));
     HIPCHK(hipStreamSynchronize(w->stream));
     return GMRF_OK;
 }
@@ -4777,20 +4565,22 @@ gmrf_status gmrf_shallow_water_p1_assemble(gmrf_swe_p1* w, const double* H_q, do
 gmrf_status gmrf_shallow_water_p1_operators(gmrf_swe_p1* w, const double* K_vals, const double* M_lumped, const double* S_vals,
                                             const uint8_t* prescribed, double kappa_matern, double tau, double dt, double* G_vals,
                                             double* J_vals, double* M_tilde, double* beta) {
-    GCHK(swe_ready(w));
+    if (!w) return bad_shape("null handle");
+    GCHK(w->ready("pattern-only shallow-water handle"));
     if (!K_vals || !M_lumped || !S_vals || !G_vals || !J_vals || !M_tilde || !beta) return bad_shape("null pointer");
     if (!(kappa_matern > 0.0) || !(dt > 0.0)) return bad_shape("kappa_matern and dt must be positive");
     SweOpArgs a;
     const uint8_t* d_pres;
-    // (inputs that live on the host are staged into the buffers the assemble call uses for its outputs)
-    GCHK(swe_in(w, K_vals, w->nnz_k, &w->d_kv, &a.kv));
-    GCHK(swe_in(w, S_vals, w->nnz_s, &w->d_sv, &a.sv));
-    GCHK(swe_in(w, M_lumped, w->n, &w->d_ml, &a.ml));
-    GCHK(swe_in(w, prescribed, w->n, &w->d_pres, &d_pres));
-    GCHK(swe_out(w, G_vals, w->nnz_k, &w->d_g, &a.Gd));
-    GCHK(swe_out(w, J_vals, w->nnz_s, &w->d_j, &a.J));
-    GCHK(swe_out(w, M_tilde, w->n, &w->d_mt, &a.Mt));
-    GCHK(swe_out(w, beta, w->n, &w->d_beta, &a.beta));
+    Staging args(w->arena);
+    args.in(K_vals, sizeof(double) * w->nnz_k, &a.kv);
+    args.in(S_vals, sizeof(double) * w->nnz_s, &a.sv);
+    args.in(M_lumped, sizeof(double) * w->n, &a.ml);
+    args.in(prescribed, (size_t)w->n, &d_pres);
+    args.out(G_vals, sizeof(double) * w->nnz_k, &a.Gd);
+    args.out(J_vals, sizeof(double) * w->nnz_s, &a.J);
+    args.out(M_tilde, sizeof(double) * w->n, &a.Mt);
+    args.out(beta, sizeof(double) * w->n, &a.beta);
+    GCHK(args.commit(w->stream));
     a.n = w->n; a.rowptr_k = w->d_rowptr_k; a.col_k = w->d_col_k; a.rowptr_s = w->d_rowptr_s; a.col_s = w->d_col_s;
     a.pres = d_pres; a.kappa2 = kappa_matern * kappa_matern; a.tau = tau; a.dt = dt; a.dg = w->d_dk;
     const double nu = 2.0;                                     // :180
@@ -4798,10 +4588,7 @@ gmrf_status gmrf_shallow_water_p1_operators(gmrf_swe_p1* w, const double* K_vals
     hipLaunchKernelGGL(swe_p1_operators, dim3((unsigned)((w->n + 255) / 256)), dim3(256), 0, w->stream, a);
     HIPCHK(hipGetLastError());
     if (d_pres) GCHK(swe_constrain(w, w->d_rowptr_k, w->d_col_k, d_pres, w->d_dk, w->d_mean + 3, a.Gd));      // apply!(S_tmp, f, ch) :213
-    if (a.Gd != G_vals) HIPCHK(hipMemcpyAsync(G_vals, a.Gd, sizeof(double) * w->nnz_k, hipMemcpyDeviceToHost, w->stream));
-    if (a.J != J_vals) HIPCHK(hipMemcpyAsync(J_vals, a.J, sizeof(double) * w->nnz_s, hipMemcpyDeviceToHost, w->stream));
-    if (a.Mt != M_tilde) HIPCHK(hipMemcpyAsync(M_tilde, a.Mt, sizeof(double) * w->n, hipMemcpyDeviceToHost, w->stream));
-    if (a.beta != beta) HIPCHK(hipMemcpyAsync(beta, a.beta, sizeof(double) * w->n, hipMemcpyDeviceToHost, w->stream));
+    GCHK(args.flush(w->stream));
     HIPCHK(hipStreamSynchronize(w->stream));
     return GMRF_OK;
 }
@@ -5646,7 +5433,9 @@ static gmrf_status tw_sample_chunk(gmrf_handle* h, uint64_t seed, int64_t first_
 static gmrf_status tw_sample(gmrf_handle* h, uint64_t seed, int64_t first_id, int64_t k, const double* mean, const double* z,
                              double* out, int64_t ld) {
     const double* d_mean = nullptr;
-    GCHK(stage_vector(h, mean, &h->d_mean, &d_mean));
+    Staging args(h->mean_arena);
+    args.in(mean, sizeof(double) * h->n * h->B, &d_mean);
+    GCHK(args.commit(h->stream));
     const bool out_dev = is_device_ptr(out);
     HIPCHK(hipEventRecord(h->ev0, h->stream));
     for (int64_t c0 = 0; c0 < k; c0 += KP_CHUNK) {

@@ -1,0 +1,129 @@
+// Host-side plumbing shared by the handles of gmrf_hip.hip: a grow-only device buffer, a device context (device +
+// stream) and the staging of host-resident arguments.  Included by gmrf_hip.hip after g_last_error, HIPCHK / GCHK,
+// bad_shape and is_device_ptr; no kernels here.
+#pragma once
+
+static void free_dev(void* p) {
+    if (p) (void)hipFree(p);
+}
+
+// Grow-only device buffer.  What was enqueued on `stream` may still use the old allocation, so the stream is drained
+// before it is freed.
+struct DevBuf {
+    void* p = nullptr;
+    size_t cap = 0;                     // bytes
+
+    gmrf_status reserve(hipStream_t stream, size_t bytes) {
+        if (p && bytes <= cap) return GMRF_OK;
+        if (p) HIPCHK(hipStreamSynchronize(stream));
+        release();
+        bytes = std::max<size_t>(bytes, 16);
+        if (hipError_t e = hipMalloc(&p, bytes); e != hipSuccess) {
+            p = nullptr;
+            g_last_error = std::string("hipMalloc (DevBuf::reserve): ") + hipGetErrorString(e);
+            return GMRF_ERR_HIP;
+        }
+        cap = bytes;
+        return GMRF_OK;
+    }
+    void release() { free_dev(p); p = nullptr; cap = 0; }
+    template <class T> T* as() const { return static_cast<T*>(p); }
+};
+
+// Device and stream of a handle.  device -1: the handle was created for its host side only (patterns); nothing of the
+// GPU is touched, and ready() refuses the numeric calls.
+struct DevCtx {
+    int device = -1;
+    hipStream_t stream = nullptr;
+    bool own_stream = false;
+
+    // Binds `dev` and the caller's stream, or creates one with `stream_flags`.  `who` prefixes a HIP failure.
+    gmrf_status open(int32_t dev, void* user_stream, unsigned stream_flags, const char* who, bool pattern_only_ok = true) {
+        if (dev < 0 && pattern_only_ok) return GMRF_OK;
+        int count = 0;
+        if (hipGetDeviceCount(&count) != hipSuccess || count <= 0 || dev < 0 || dev >= count) {
+            (void)hipGetLastError();    // a failed count query leaves a sticky error
+            g_last_error = "no HIP device visible (libgmrf_hip needs an MI355X / gfx950 GPU)";
+            return GMRF_ERR_NO_DEVICE;
+        }
+        hipError_t e = hipSetDevice(dev);
+        if (e == hipSuccess) {
+            if (user_stream) stream = (hipStream_t)user_stream;
+            else { e = hipStreamCreateWithFlags(&stream, stream_flags); own_stream = (e == hipSuccess); }
+        }
+        if (e != hipSuccess) { g_last_error = std::string(who) + ": " + hipGetErrorString(e); return GMRF_ERR_HIP; }
+        device = dev;
+        return GMRF_OK;
+    }
+
+    // Before a numeric call: `what` names the handle kind in the message of a pattern-only handle.
+    gmrf_status ready(const char* what) const {
+        if (device < 0) { g_last_error = std::string(what) + " (created with device -1)"; return GMRF_ERR_NO_DEVICE; }
+        HIPCHK(hipSetDevice(device));
+        return GMRF_OK;
+    }
+
+    bool has_device() const { return device >= 0; }
+
+    // Drains the stream and destroys it if it is ours; the device stays selected for the caller's frees.
+    void close() {
+        if (!has_device()) return;
+        (void)hipSetDevice(device);
+        if (stream) (void)hipStreamSynchronize(stream);
+        if (own_stream) (void)hipStreamDestroy(stream);
+        stream = nullptr; own_stream = false;
+    }
+};
+
+// The host-or-device arguments of ONE call.  in() / out() register an argument and where its device address goes;
+// commit() sizes the handle's arena once for the call, fills in the addresses and uploads the host inputs; after the
+// kernels, flush() brings the host outputs back.  A null pointer stays null, a device pointer passes through
+// untouched, a host array gets a 16-byte aligned slice of the arena.  Nothing but the arena's capacity outlives the call.
+struct Staging {
+    struct Item { void* user; size_t bytes; void** dev; bool out; void* slice; };      // slice: its place in the arena, null if none
+    DevBuf& arena;
+    Item items[8];
+    int count = 0;
+    bool overflow = false;
+
+    explicit Staging(DevBuf& a) : arena(a) {}
+
+    template <class T> void in(const T* p, size_t bytes, const T** dev) { add(const_cast<T*>(p), bytes, (void**)dev, false); }
+    template <class T> void out(T* p, size_t bytes, T** dev) { add(p, bytes, (void**)dev, true); }
+
+    gmrf_status commit(hipStream_t stream) {
+        if (overflow) return bad_shape("too many staged arguments");
+        bool host[8];
+        size_t need = 0;
+        for (int i = 0; i < count; ++i) {
+            host[i] = items[i].user && !is_device_ptr(items[i].user);
+            if (host[i]) need += padded(items[i].bytes);
+        }
+        if (need) GCHK(arena.reserve(stream, need));
+        size_t off = 0;
+        for (int i = 0; i < count; ++i) {
+            Item& it = items[i];
+            if (!host[i]) { *it.dev = it.user; continue; }
+            *it.dev = it.slice = arena.as<char>() + off;
+            off += padded(it.bytes);
+            if (!it.out) HIPCHK(hipMemcpyAsync(it.slice, it.user, it.bytes, hipMemcpyHostToDevice, stream));
+        }
+        return GMRF_OK;
+    }
+
+    gmrf_status flush(hipStream_t stream) {
+        for (int i = 0; i < count; ++i)
+            if (items[i].out && items[i].slice)
+                HIPCHK(hipMemcpyAsync(items[i].user, items[i].slice, items[i].bytes, hipMemcpyDeviceToHost, stream));
+        return GMRF_OK;
+    }
+
+    // what an item of `bytes` takes of the arena (a caller that sizes the arena ahead of commit() sums this)
+    static size_t padded(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
+
+private:
+    void add(void* p, size_t bytes, void** dev, bool out) {
+        if (count == (int)(sizeof(items) / sizeof(items[0]))) { overflow = true; return; }
+        items[count++] = {p, bytes, dev, out, nullptr};
+    }
+};

@@ -1,6 +1,7 @@
 """Child process of tests/test_host_logic.py::test_host_side_under_address_sanitizer: loads the sanitizer build of the
 library (argv[1]) -- the ASan runtime is preloaded by the parent -- and drives every entry point that needs no GPU with
-valid, ragged and invalid inputs.  Any AddressSanitizer / UBSan report aborts the process (non-zero exit code)."""
+valid, ragged and invalid inputs.  Any AddressSanitizer / UBSan report aborts the process (non-zero exit code).
+argv[2] == "creates" (test_creates_without_a_device_under_address_sanitizer): only the creates that ask for a device."""
 import ctypes as C
 import sys
 
@@ -26,6 +27,30 @@ def symbolic(A, N, base=0):
     st = lib.gmrf_test_symbolic_csc(A.shape[0], N, ptr(cp), ptr(rv), base, ptr(out))
     return st, out
 
+
+if sys.argv[2:] == ["creates"]:
+    # Creates that ask for a device on a machine that has none: ERR_NO_DEVICE, and what the create had built by then (patterns,
+    # the half-built handle) is released by the handle's own destroy -- the sanitizer would see a double free or a use after
+    # free there (not a leak: the parent runs this child with detect_leaks=0).
+    n, m = 40, 30
+    Qm = (sp.random(n, n, density=0.1, random_state=2) + sp.identity(n)).tocsc(); Qm = (Qm + Qm.T).tocsc(); Qm.sort_indices()
+    J = sp.random(m, n, density=0.08, random_state=3, format="csr"); J.sort_indices()
+    qp, qi, jp, ji = (x.astype(np.int64) for x in (Qm.indptr, Qm.indices, J.indptr, J.indices))
+    lib.gmrf_assemble_create.argtypes = [i32, vp, i64, vp, vp, i64, vp, vp, i32, P(vp)]
+    lib.gmrf_darcy_p1_create.argtypes = lib.gmrf_darcy_p2_create.argtypes = lib.gmrf_shallow_water_p1_create.argtypes = [i32, vp, i64, i64, P(vp)]
+    lib.gmrf_burgers_p1_create.argtypes = lib.gmrf_burgers_p2_create.argtypes = [i32, vp, i64, i64, dbl, dbl, P(vp)]
+    lib.gmrf_csr_create.argtypes = [i32, vp, i64, i64, vp, vp, vp, i32, i32, P(vp)]
+    for device in (0, 3):
+        h = vp()
+        assert lib.gmrf_assemble_create(device, None, n, ptr(qp), ptr(qi), m, ptr(jp), ptr(ji), 0, C.byref(h)) == -6 and not h.value
+        for create in (lib.gmrf_darcy_p1_create, lib.gmrf_darcy_p2_create, lib.gmrf_shallow_water_p1_create):
+            assert create(device, None, 9, 5, C.byref(h)) == -6 and not h.value
+        for create in (lib.gmrf_burgers_p1_create, lib.gmrf_burgers_p2_create):
+            assert create(device, None, 16, 5, 0.1, 0.01, C.byref(h)) == -6 and not h.value
+        assert lib.gmrf_csr_create(device, None, m, n, ptr(jp), ptr(ji), ptr(J.data), 0, 0, C.byref(h)) == -6 and not h.value
+    assert lib.gmrf_csr_create(-1, None, m, n, ptr(jp), ptr(ji), ptr(J.data), 0, 0, C.byref(h)) == -6      # no pattern-only CSR matrix
+    print("asan driver ok")
+    sys.exit(0)
 
 rng = np.random.default_rng(0)
 # 1. block-tridiagonal matrices of several block sizes (padded and unpadded), 0- and 1-based

@@ -323,22 +323,37 @@ def test_shallow_water_p1_patterns_and_oracle_without_gpu(pkg):
     assert np.allclose(ops["beta"][pres], np.sqrt(0.1) * 1e-2) and np.allclose(ops["beta"][~pres], np.sqrt(0.1) * 0.5)
 
 
-def test_host_side_under_address_sanitizer(pkg, tmp_path):
-    """SURVEY section 5 ("Race detection / sanitizers"): the host side of the library -- symbolic phase of the factor (block
-    split, band check, staircase, tile plans), posterior-assembler symbolic phase, FEM patterns, argument validation -- is
-    compiled with -fsanitize=address,undefined (device code as usual) and driven through the entry points that need no GPU,
-    in a child process with the sanitizer runtime preloaded.  A report aborts the child."""
-    import subprocess
+def _asan_child(*args):
+    """tests/asan_driver.py on the sanitizer build of the library, in a child process with the sanitizer runtime preloaded."""
     import sys
     csrc = os.path.join(ROOT, "diffeqgmrfs.jl_amd", "csrc")
     subprocess.check_call(["make", "-C", csrc, "libgmrf_hip_asan.so"], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=600)
     rt = subprocess.run(["make", "-s", "-C", csrc, "asan-runtime"], capture_output=True, text=True).stdout.strip().splitlines()[-1]
     assert os.path.exists(rt), rt
     env = dict(os.environ, LD_PRELOAD=rt, ASAN_OPTIONS="detect_leaks=0:abort_on_error=0:exitcode=77", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "asan_driver.py"), os.path.join(csrc, "libgmrf_hip_asan.so")],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "asan_driver.py"), os.path.join(csrc, "libgmrf_hip_asan.so"), *args],
                        capture_output=True, text=True, env=env, timeout=600, cwd=ROOT)
     assert p.returncode == 0 and "asan driver ok" in p.stdout and "AddressSanitizer" not in p.stderr and "runtime error" not in p.stderr, \
         (p.returncode, p.stdout[-500:], p.stderr[-3000:])
+
+
+def test_host_side_under_address_sanitizer(pkg, tmp_path):
+    """SURVEY section 5 ("Race detection / sanitizers"): the host side of the library -- symbolic phase of the factor (block
+    split, band check, staircase, tile plans), posterior-assembler symbolic phase, FEM patterns, argument validation -- is
+    compiled with -fsanitize=address,undefined (device code as usual) and driven through the entry points that need no GPU,
+    in a child process with the sanitizer runtime preloaded.  A report aborts the child."""
+    _asan_child()
+
+
+def test_creates_without_a_device_under_address_sanitizer(pkg):
+    """The creates of the workload handles (posterior assembler, Darcy, Burgers, shallow water) and of a CSR matrix with
+    device = 0 on a machine without a GPU: ERR_NO_DEVICE and no handle.  The half-built handle goes through its own destroy; the
+    sanitizer would report a double free or a use after free there.  Leaks are not detected (detect_leaks=0, as in the other
+    child), and without a GPU the create fails at the device query, so a failure after that point is not reached."""
+    import torch
+    if torch.cuda.is_available():
+        pytest.skip("GPU present")
+    _asan_child("creates")
 
 
 def test_bench_refuses_a_rank_count_that_differs_from_the_launcher():

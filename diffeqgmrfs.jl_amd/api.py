@@ -328,6 +328,25 @@ class DarcyP1Assembler:
         return vals, f
 
 
+    def assemble_batch(self, tables, beta: float = 1.0):
+        """tables: (B, ng, ng) coefficient tables (NumPy array or torch CUDA tensor) -> (values (B, nnz), load vectors (B, n)),
+        same kind as the input; row p is `assemble(tables[p])`, bit for bit."""
+        if _is_torch(tables):
+            import torch
+            tab = tables.contiguous()
+            if tab.dtype != torch.float64:
+                raise TypeError("float64 required")
+        else:
+            tab = np.ascontiguousarray(tables, dtype=np.float64)
+        if tab.ndim != 3 or tab.shape[1] != tab.shape[2]:
+            raise ValueError("tables must have shape (B, ng, ng)")
+        B = tab.shape[0]
+        vals, f = PosteriorAssembler._like2(tab, (B, self.nnz)), PosteriorAssembler._like2(tab, (B, self.n))
+        _cabi.check(_cabi.load().gmrf_darcy_p1_assemble_batch(self._h, B, _cabi.ptr(tab), tab.shape[1], float(beta), _cabi.ptr(vals),
+                                                              _cabi.ptr(f)))
+        return vals, f
+
+
 class BurgersP1Tangent:
     """Residual and tangent of the implicit-Euler Burgers space-time system on the device (second
     piece): `f_and_J` of /root/reference/scripts/burgers/solve_burgers_gmrf-fem.jl:118-149 with
@@ -536,6 +555,89 @@ class GaussNewtonBatch:
         info = C.c_int32(0)
         _cabi.check(_cabi.load().gmrf_gn_finalize(self._h, C.byref(info)), info.value)
         return self.F
+
+
+class DarcyConditioningResult:
+    """What `DarcyConditioningBatch.run` returns: mean (B, n), samples (B, k_samples, n) or None, std (B, n) and std_norm (B,)
+    or None (var=None)."""
+    __slots__ = ("mean", "samples", "std", "std_norm")
+
+    def __init__(self, mean, samples, std, std_norm):
+        self.mean, self.samples, self.std, self.std_norm = mean, samples, std, std_norm
+
+
+class DarcyConditioningBatch:
+    """The Darcy data-set loop (scripts/darcy/solve_darcy_gmrf-fem.jl:176-198) for `F.batch` problems on one mesh in ONE call,
+    resident on the device (gmrf_dc_run): coefficient tables -> A, y -> Q + q_eps A'A and the information vector -> refactor ->
+    mean and samples -> marginal standard deviations and their norms.
+
+    `F` (reference order, factored once on `asm.pattern`), `asm` (built on `darcy.pattern`) and `darcy` must have been created on
+    the same device with the same `stream` argument."""
+
+    _VAR = {None: -1, "none": -1, "exact": _cabi.VAR_EXACT, "rbmc": _cabi.VAR_RBMC, "mc": _cabi.VAR_MC}
+
+    def __init__(self, F: "TridiagonalCholeskyFactor", asm: PosteriorAssembler, darcy: DarcyP1Assembler):
+        self.F, self.asm, self.darcy = F, asm, darcy              # (kept alive: the library holds their handles)
+        self._h = C.c_void_p()
+        _cabi.check(_cabi.load().gmrf_dc_create(F._h, asm._h, darcy._h, C.byref(self._h)))
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            _cabi.load().gmrf_dc_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def run(self, tables, q_values, Q_mu=None, q_eps: float = 1e8, beta: float = 1.0, k_samples: int = 1, var="rbmc",
+            k_var: int = 50, sample_seed: int = 0x5EED, var_seed: int = 0x5EED, out=None):
+        """tables (B, ng, ng); q_values (nnz_q,) shared or (B, nnz_q); Q_mu (B, n) = Q mu or None (zero prior mean).  NumPy arrays
+        or torch CUDA tensors; the result's arrays are torch tensors on the device when `tables` is one, NumPy otherwise.
+        var: "rbmc" (the reference's RBMCStrategy(k_var)), "mc", "exact" or None.  Problem p's samples carry the ids
+        p k_samples + s (`posterior_batch`), its variance draws p k_var + s (`marginal_var` of a batch).  The defaults are the
+        reference's (:163, :174).  `out`: a DarcyConditioningResult of arrays to fill instead of new ones; after
+        NotPositiveDefinite they are unchanged."""
+        B, a = self.F.batch, self.asm
+        if var not in self._VAR:
+            raise ValueError('var must be "rbmc", "mc", "exact" or None')
+        method = self._VAR[var]
+        if _is_torch(tables):
+            import torch
+            tab = tables.contiguous()
+            if tab.dtype != torch.float64:
+                raise TypeError("float64 required")
+        else:
+            tab = np.ascontiguousarray(tables, dtype=np.float64)
+        if tab.ndim != 3 or tab.shape[0] != B or tab.shape[1] != tab.shape[2]:
+            raise GmrfError(_cabi.ERR_BAD_SHAPE, f"tables: expected ({B}, ng, ng), the batch of the handle")
+        q, stride = a._q(q_values, B)
+        qm = a._mat(Q_mu, B, a.n, "Q_mu")
+        k_samples = int(k_samples)
+        if out is None:
+            like2 = PosteriorAssembler._like2
+            out = DarcyConditioningResult(like2(tab, (B, a.n)), like2(tab, (B, k_samples, a.n)) if k_samples > 0 else None,
+                                          like2(tab, (B, a.n)) if method >= 0 else None, like2(tab, (B,)) if method >= 0 else None)
+        else:
+            for name, arr, shape in (("mean", out.mean, (B, a.n)), ("samples", out.samples, (B, k_samples, a.n) if k_samples > 0 else None),
+                                     ("std", out.std, (B, a.n) if method >= 0 else None), ("std_norm", out.std_norm, (B,) if method >= 0 else None)):
+                if arr is None:
+                    continue
+                if shape is None:
+                    raise ValueError(f"out.{name} given, but this run does not produce it")
+                ok = tuple(arr.shape) == shape and (arr.is_contiguous() and str(arr.dtype) == "torch.float64" if _is_torch(arr)
+                                                    else isinstance(arr, np.ndarray) and arr.flags.c_contiguous and arr.dtype == np.float64)
+                if not ok:
+                    raise ValueError(f"out.{name} must be a contiguous float64 array of shape {shape}")
+        info = C.c_int32(0)
+        st = _cabi.load().gmrf_dc_run(self._h, _cabi.ptr(tab), tab.shape[1], float(beta), _cabi.ptr(q), stride, _cabi.ptr(qm),
+                                      float(q_eps), k_samples, int(sample_seed), method, int(k_var), int(var_seed),
+                                      _cabi.ptr(out.mean), _cabi.ptr(out.samples), _cabi.ptr(out.std), _cabi.ptr(out.std_norm),
+                                      C.byref(info))
+        _cabi.check(st, info.value)
+        return out
 
 
 class ConditionedGMRF:

@@ -78,8 +78,7 @@ __device__ __forceinline__ int stencil_slot(int dx, int dy) {
     return dy == -1 ? (dx == -1 ? 0 : 1) : (dy == 0 ? (dx == -1 ? 2 : (dx == 0 ? 3 : 4)) : (dx == 0 ? 5 : 6));
 }
 
-__global__ __launch_bounds__(256) void darcy_p1_rows(DarcyP1Args a) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+__device__ __forceinline__ void darcy_p1_row(const DarcyP1Args& a, const int64_t i) {
     const int64_t n = (int64_t)a.nx * a.ny;
     if (i >= n) return;
     const int ix = (int)(i % a.nx), iy = (int)(i / a.nx);
@@ -111,8 +110,20 @@ __global__ __launch_bounds__(256) void darcy_p1_rows(DarcyP1Args a) {
     a.diag[i] = fabs(slot[3]);
 }
 
+__global__ __launch_bounds__(256) void darcy_p1_rows(DarcyP1Args a) {
+    darcy_p1_row(a, (int64_t)blockIdx.x * blockDim.x + threadIdx.x);
+}
+
+// A batch of coefficient tables on one mesh, problem-major: table[B][ng ng] -> vals[B][nnz], f[B][n], diag[B][n]; blockIdx.y is
+// the problem.  The row function is the one-problem kernel's: the same arithmetic in the same order, so the same bits per problem.
+__global__ __launch_bounds__(256) void darcy_p1_rows_batch(DarcyP1Args a, int64_t nnz) {
+    const int64_t p = blockIdx.y, n = (int64_t)a.nx * a.ny;
+    a.table += p * ((int64_t)a.ng * a.ng); a.vals += p * nnz; a.f += p * n; a.diag += p * n;
+    darcy_p1_row(a, (int64_t)blockIdx.x * blockDim.x + threadIdx.x);
+}
+
 // meandiag: sum of |G_ii| over all nodes in a fixed order (one workgroup), divided by n
-__global__ __launch_bounds__(256) void darcy_meandiag(const double* __restrict__ diag, int64_t n, double* __restrict__ out) {
+__device__ __forceinline__ void darcy_meandiag_group(const double* __restrict__ diag, int64_t n, double* __restrict__ out) {
     __shared__ double red[256];
     const int64_t chunk = (n + 255) / 256, lo = (int64_t)threadIdx.x * chunk, hi = min(n, lo + chunk);
     double s = 0.0;
@@ -126,10 +137,18 @@ __global__ __launch_bounds__(256) void darcy_meandiag(const double* __restrict__
     if (threadIdx.x == 0) out[0] = red[0] / (double)n;
 }
 
+__global__ __launch_bounds__(256) void darcy_meandiag(const double* __restrict__ diag, int64_t n, double* __restrict__ out) {
+    darcy_meandiag_group(diag, n, out);
+}
+
+// diag[B][n] -> out[B]: one workgroup per problem (blockIdx.x), each with the one-problem kernel's partition and tree
+__global__ __launch_bounds__(256) void darcy_meandiag_batch(const double* __restrict__ diag, int64_t n, double* __restrict__ out) {
+    darcy_meandiag_group(diag + (int64_t)blockIdx.x * n, n, out + blockIdx.x);
+}
+
 // apply!(G, f, ch) for homogeneous Dirichlet data on the boundary nodes: constrained rows and columns are
 // zeroed, the constrained diagonal entries become meandiag, f vanishes there (src/problems/darcy.jl:61)
-__global__ __launch_bounds__(256) void darcy_p1_constrain(DarcyP1Args a, const double* __restrict__ meandiag) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+__device__ __forceinline__ void darcy_p1_constrain_row(const DarcyP1Args& a, const double* __restrict__ meandiag, const int64_t i) {
     const int64_t n = (int64_t)a.nx * a.ny;
     if (i >= n) return;
     const int ix = (int)(i % a.nx), iy = (int)(i / a.nx);
@@ -145,6 +164,17 @@ __global__ __launch_bounds__(256) void darcy_p1_constrain(DarcyP1Args a, const d
         ++p;
     }
     if (bi) a.f[i] = 0.0;
+}
+
+__global__ __launch_bounds__(256) void darcy_p1_constrain(DarcyP1Args a, const double* __restrict__ meandiag) {
+    darcy_p1_constrain_row(a, meandiag, (int64_t)blockIdx.x * blockDim.x + threadIdx.x);
+}
+
+// meandiag[B]; blockIdx.y is the problem
+__global__ __launch_bounds__(256) void darcy_p1_constrain_batch(DarcyP1Args a, int64_t nnz, const double* __restrict__ meandiag) {
+    const int64_t p = blockIdx.y;
+    a.vals += p * nnz; a.f += p * ((int64_t)a.nx * a.ny);
+    darcy_p1_constrain_row(a, meandiag + p, (int64_t)blockIdx.x * blockDim.x + threadIdx.x);
 }
 
 

@@ -59,9 +59,8 @@ __device__ __forceinline__ void p2_cell_nodes(int qx, int qy, bool upper, int (&
     nI[5] = (nI[2] + nI[0]) / 2; nJ[5] = (nJ[2] + nJ[0]) / 2;
 }
 
-__global__ __launch_bounds__(256) void darcy_p2_rows(DarcyP2Args a) {
+__device__ __forceinline__ void darcy_p2_row(const DarcyP2Args& a, const int64_t row) {
     const int W = 2 * a.nx - 1, H = 2 * a.ny - 1;
-    const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (row >= (int64_t)W * H) return;
     const int I = (int)(row % W), J = (int)(row / W);
     double slot[25];
@@ -140,6 +139,34 @@ __global__ __launch_bounds__(256) void darcy_p2_rows(DarcyP2Args a) {
         if (present & (1u << s)) a.vals[p++] = slot[s];
     a.f[row] = fi;
     a.diag[row] = fabs(slot[12]);
+}
+
+__global__ __launch_bounds__(256) void darcy_p2_rows(DarcyP2Args a) {
+    darcy_p2_row(a, (int64_t)blockIdx.x * blockDim.x + threadIdx.x);
+}
+
+// A batch of coefficient tables, problem-major like darcy_p1_rows_batch (n = lattice points); blockIdx.y is the problem.
+__global__ __launch_bounds__(256) void darcy_p2_rows_batch(DarcyP2Args a, int64_t nnz) {
+    const int64_t p = blockIdx.y, n = (int64_t)(2 * a.nx - 1) * (2 * a.ny - 1);
+    a.table += p * ((int64_t)a.ng * a.ng); a.vals += p * nnz; a.f += p * n; a.diag += p * n;
+    darcy_p2_row(a, (int64_t)blockIdx.x * blockDim.x + threadIdx.x);
+}
+
+// apply!(G, f, ch) of a batch: what csr_apply_constraints and vec_set_prescribed (value 0) do for one problem -- assignments
+// only --, vals[B][nnz], f[B][n], meandiag[B]; blockIdx.y is the problem.
+__global__ __launch_bounds__(256) void darcy_p2_constrain_batch(const int64_t* __restrict__ rowptr, const int32_t* __restrict__ colidx,
+                                                                const uint8_t* __restrict__ pres, int64_t n, int64_t nnz,
+                                                                const double* __restrict__ meandiag, double* __restrict__ vals,
+                                                                double* __restrict__ f) {
+    const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, p = blockIdx.y;
+    if (row >= n) return;
+    vals += p * nnz; f += p * n;
+    const bool pr = pres[row] != 0;
+    for (int64_t e = rowptr[row]; e < rowptr[row + 1]; ++e) {
+        const int64_t col = colidx[e];
+        if (pr || pres[col]) vals[e] = (col == row) ? meandiag[p] : 0.0;
+    }
+    if (pr) f[row] = 0.0;
 }
 
 }  // namespace gmrf

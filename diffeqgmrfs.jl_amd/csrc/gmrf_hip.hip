@@ -42,6 +42,7 @@
 #include "fem_assemble_p2.hpp"
 #include "selinv.hpp"
 #include "gauss_newton.hpp"
+#include "darcy_cond.hpp"
 
 using namespace gmrf;
 
@@ -215,6 +216,7 @@ struct gmrf_handle {
     DevBuf mean_arena;                 // a host `mean` of gmrf_bt_sample (Staging)
     double* d_acc = nullptr;           // variance accumulator / output ([acc_B][n])
     int64_t acc_B = 0;
+    int32_t var_group = 0, var_groups = 0;   // the last batched sampled estimator: problems per group of the stage, groups per chunk (gmrf_test_var_groups)
     // graphs
     bool eager = false;
     bool split_step = false;           // use the three-launch panel step also for batch 1 (experiment)
@@ -3542,13 +3544,13 @@ static gmrf_status spmm_rows_device(const gmrf_csr* S, hipStream_t st, const dou
 #define GMRF_SPMM_TILES(VT, VP)                                                                                          \
         do {                                                                                                             \
             if (pad && uc <= 224) hipLaunchKernelGGL((csr_spmm_tiles_pad<VT, 7>), grid, dim3(SPMM_THREADS), lds, st, S->d_rowptr, S->d_lidx, VP, \
-                                              S->d_tile_uptr, S->d_ucols, S->n_rows, d_X, ldx, d_Y, ldy, k, R, ucl, ecl);  \
+                                              S->d_tile_uptr, S->d_ucols, S->n_rows, d_X, ldx, d_Y, ldy, k, R, ucl, ecl, SpmmBatch());  \
             else if (pad) hipLaunchKernelGGL((csr_spmm_tiles_pad<VT, SPMM_NG>), grid, dim3(SPMM_THREADS), lds, st, S->d_rowptr, S->d_lidx, VP,    \
-                                    S->d_tile_uptr, S->d_ucols, S->n_rows, d_X, ldx, d_Y, ldy, k, R, ucl, ecl);            \
+                                    S->d_tile_uptr, S->d_ucols, S->n_rows, d_X, ldx, d_Y, ldy, k, R, ucl, ecl, SpmmBatch());            \
             else if (uc <= 224) hipLaunchKernelGGL((csr_spmm_tiles<VT, 7>), grid, dim3(SPMM_THREADS), lds, st, S->d_rowptr, S->d_lidx, VP, \
-                                              S->d_tile_uptr, S->d_ucols, S->n_rows, d_X, ldx, d_Y, ldy, k, R, uc, ec);  \
+                                              S->d_tile_uptr, S->d_ucols, S->n_rows, d_X, ldx, d_Y, ldy, k, R, uc, ec, SpmmBatch());  \
             else hipLaunchKernelGGL((csr_spmm_tiles<VT, SPMM_NG>), grid, dim3(SPMM_THREADS), lds, st, S->d_rowptr, S->d_lidx, VP,    \
-                                    S->d_tile_uptr, S->d_ucols, S->n_rows, d_X, ldx, d_Y, ldy, k, R, uc, ec);            \
+                                    S->d_tile_uptr, S->d_ucols, S->n_rows, d_X, ldx, d_Y, ldy, k, R, uc, ec, SpmmBatch());            \
         } while (0)
         if (vals_override) GMRF_SPMM_TILES(double, vals_override);
         else if (S->d_vals32) GMRF_SPMM_TILES(float, S->d_vals32);
@@ -3559,6 +3561,40 @@ static gmrf_status spmm_rows_device(const gmrf_csr* S, hipStream_t st, const dou
         if (vals_override) hipLaunchKernelGGL(csr_spmm_rows<double>, grid, dim3(256), 0, st, S->d_rowptr, S->d_colidx, vals_override, S->n_rows, d_X, ldx, d_Y, ldy, k);
         else if (S->d_vals32) hipLaunchKernelGGL(csr_spmm_rows<float>, grid, dim3(256), 0, st, S->d_rowptr, S->d_colidx, S->d_vals32, S->n_rows, d_X, ldx, d_Y, ldy, k);
         else hipLaunchKernelGGL(csr_spmm_rows<double>, grid, dim3(256), 0, st, S->d_rowptr, S->d_colidx, S->d_vals, S->n_rows, d_X, ldx, d_Y, ldy, k);
+    }
+    HIPCHK(hipGetLastError());
+    return GMRF_OK;
+}
+
+// The same product for `batch` problems on S's pattern in one launch: problem p has the fp64 values vals + p nnz and the
+// node-major operands d_X + p x_stride, d_Y + p y_stride.  The route (tiled, padded, plain) is chosen exactly as
+// spmm_rows_device chooses it for one problem -- the strides keep the operands 16-byte aligned or the plain kernel runs.
+static gmrf_status spmm_rows_device_batch(const gmrf_csr* S, hipStream_t st, int64_t batch, const double* vals, const double* d_X,
+                                          int64_t ldx, int64_t x_stride, double* d_Y, int64_t ldy, int64_t y_stride, int k) {
+    gmrf_csr* m = const_cast<gmrf_csr*>(S);
+    GCHK(spmm_plan(m));
+    const bool aligned = (k % 2 == 0) && (ldx % 2 == 0) && (ldy % 2 == 0) && (((uintptr_t)d_X) % 16 == 0) && (((uintptr_t)d_Y) % 16 == 0) &&
+                         (x_stride % 2 == 0) && (y_stride % 2 == 0) && (S->n_cols * ldx < ((int64_t)1 << 32));
+    if (m->plan_state == 1 && aligned) {
+        const int R = m->plan_rows, uc = m->plan_ucap, ec = m->plan_ecap;
+        const dim3 grid((unsigned)((S->n_rows + R - 1) / R), (unsigned)batch);
+        static const bool no_pad = [] { const char* e = getenv("GMRF_SPMM_PAD"); return e && atoi(e) == 0; }();   // tuning aid
+        const bool pad = m->plan_ecap_pad > 0 && !no_pad;
+        const int ecl = pad ? m->plan_ecap_pad : ec;
+        const int ucl = pad ? (m->plan_umax + 7) / 8 * 8 : uc;
+        const size_t lds = pad ? spmm_tile_pad_lds_bytes(R, ucl, ecl) : spmm_tile_lds_bytes(R, uc, ec);
+#define GMRF_SPMM_TILES_B(KERNEL, NGV, UC, EC)                                                                                \
+        hipLaunchKernelGGL((KERNEL<double, NGV, true>), grid, dim3(SPMM_THREADS), lds, st, S->d_rowptr, S->d_lidx, vals, S->d_tile_uptr, \
+                           S->d_ucols, S->n_rows, d_X, ldx, d_Y, ldy, k, R, UC, EC, sb)
+        const SpmmBatch sb{S->nnz, x_stride, y_stride};
+        if (pad && uc <= 224) GMRF_SPMM_TILES_B(csr_spmm_tiles_pad, 7, ucl, ecl);
+        else if (pad) GMRF_SPMM_TILES_B(csr_spmm_tiles_pad, SPMM_NG, ucl, ecl);
+        else if (uc <= 224) GMRF_SPMM_TILES_B(csr_spmm_tiles, 7, uc, ec);
+        else GMRF_SPMM_TILES_B(csr_spmm_tiles, SPMM_NG, uc, ec);
+#undef GMRF_SPMM_TILES_B
+    } else {
+        hipLaunchKernelGGL(csr_spmm_rows_batch<double>, dim3((unsigned)((S->n_rows + 15) / 16), (unsigned)batch), dim3(256), 0, st,
+                           S->d_rowptr, S->d_colidx, vals, S->n_rows, d_X, ldx, d_Y, ldy, k, S->nnz, x_stride, y_stride);
     }
     HIPCHK(hipGetLastError());
     return GMRF_OK;
@@ -3824,6 +3860,7 @@ struct gmrf_darcy_p1 : DevCtx {         // device -1: pattern only
     uint8_t* d_pres = nullptr;
     double *d_diag = nullptr, *d_mean = nullptr;    // work: |diagonal|, its mean
     DevBuf arena;                       // host arguments of the current call (Staging)
+    DevBuf bwork;                       // work of the batch call: [batch][n] |diagonal|, [batch] means
 };
 
 // Pattern of the quadratic-triangle lattice: row (I, J) couples with every node of every cell it belongs to (the same
@@ -3919,7 +3956,7 @@ gmrf_status gmrf_darcy_p1_destroy(gmrf_darcy_p1* d) {
     d->close();
     if (d->has_device()) {
         free_dev(d->d_rowptr); free_dev(d->d_diag); free_dev(d->d_mean); free_dev(d->d_colidx); free_dev(d->d_pres);
-        d->arena.release();
+        d->arena.release(); d->bwork.release();
     }
     delete d;
     return GMRF_OK;
@@ -4088,6 +4125,54 @@ gmrf_status gmrf_burgers_p1_tangent_batch(gmrf_burgers_p1* b, int64_t batch, con
     GCHK(launch_tangent_batch(b, b->stream, batch, d_w, d_vals, d_f));
     GCHK(args.flush(b->stream));
     HIPCHK(hipStreamSynchronize(b->stream));
+    return GMRF_OK;
+}
+
+// Darcy element kernels for a batch of coefficient tables (problem-major); d_work: [batch][n] |diagonal| then [batch] means
+static int64_t darcy_batch_work_elems(const gmrf_darcy_p1* d, int64_t batch) { return batch * d->n + batch; }
+static bool darcy_ng_ok(int64_t ng) { return ng >= 2 && ng <= 46340; }
+
+static gmrf_status launch_darcy_batch(const gmrf_darcy_p1* d, hipStream_t st, int64_t batch, const double* d_tab, int64_t ng, double beta,
+                                      double* d_vals, double* d_f, double* d_work) {
+    double* d_diag = d_work;
+    double* d_mean = d_work + batch * d->n;
+    const dim3 grid((unsigned)((d->n + 255) / 256), (unsigned)batch);
+    if (d->order == 2) {
+        DarcyP2Args a;
+        a.nx = (int)d->nx; a.ny = (int)d->ny; a.ng = (int)ng; a.table = d_tab; a.rowptr = d->d_rowptr; a.beta = beta;
+        a.vals = d_vals; a.f = d_f; a.diag = d_diag;
+        hipLaunchKernelGGL(darcy_p2_rows_batch, grid, dim3(256), 0, st, a, d->nnz);
+        hipLaunchKernelGGL(darcy_meandiag_batch, dim3((unsigned)batch), dim3(256), 0, st, d_diag, d->n, d_mean);
+        hipLaunchKernelGGL(darcy_p2_constrain_batch, grid, dim3(256), 0, st, d->d_rowptr, d->d_colidx, d->d_pres, d->n, d->nnz, d_mean,
+                           d_vals, d_f);
+    } else {
+        DarcyP1Args a;
+        a.nx = (int)d->nx; a.ny = (int)d->ny; a.ng = (int)ng; a.table = d_tab; a.rowptr = d->d_rowptr; a.beta = beta;
+        a.vals = d_vals; a.f = d_f; a.diag = d_diag;
+        hipLaunchKernelGGL(darcy_p1_rows_batch, grid, dim3(256), 0, st, a, d->nnz);
+        hipLaunchKernelGGL(darcy_meandiag_batch, dim3((unsigned)batch), dim3(256), 0, st, d_diag, d->n, d_mean);
+        hipLaunchKernelGGL(darcy_p1_constrain_batch, grid, dim3(256), 0, st, a, d->nnz, d_mean);
+    }
+    HIPCHK(hipGetLastError());
+    return GMRF_OK;
+}
+
+gmrf_status gmrf_darcy_p1_assemble_batch(gmrf_darcy_p1* d, int64_t batch, const double* coeff_tables, int64_t ng, double beta,
+                                         double* vals_out, double* f_out) {
+    if (!d || !coeff_tables || !vals_out || !f_out || !batch_ok(batch) || !darcy_ng_ok(ng))
+        return bad_shape("bad Darcy assembly arguments (batch in [1, 4096], ng in [2, 46340])");
+    GCHK(d->ready("pattern-only Darcy assembler"));
+    const double* d_tab;
+    double *d_vals, *d_f;
+    Staging args(d->arena);
+    args.in(coeff_tables, sizeof(double) * batch * ng * ng, &d_tab);
+    args.out(vals_out, sizeof(double) * batch * d->nnz, &d_vals);
+    args.out(f_out, sizeof(double) * batch * d->n, &d_f);
+    GCHK(args.commit(d->stream));
+    GCHK(d->bwork.reserve(d->stream, sizeof(double) * darcy_batch_work_elems(d, batch)));
+    GCHK(launch_darcy_batch(d, d->stream, batch, d_tab, ng, beta, d_vals, d_f, d->bwork.as<double>()));
+    GCHK(args.flush(d->stream));
+    HIPCHK(hipStreamSynchronize(d->stream));
     return GMRF_OK;
 }
 
@@ -4420,6 +4505,170 @@ gmrf_status gmrf_gn_finalize(gmrf_gn* g, int32_t* info) {
     GCHK(launch_tangent_batch(g->b, h->stream, g->B, g->d_x, g->d_jv, g->d_f));
     GCHK(launch_precision_batch(g->as, h->stream, g->B, g->d_q, g->q_stride, g->d_jv, g->noise, g->d_a));
     return numeric_factor(h, g->d_a, info);
+}
+
+// --------------------------------------------------------------------------------- the batched Darcy conditioning driver
+// B = batch of the handle Darcy data-set problems on one mesh (scripts/darcy/solve_darcy_gmrf-fem.jl:176-198 per problem) in ONE
+// call on the handle's stream:
+//     coefficient tables -> A, y -> Q + q_eps A'A, information vector -> gmrf_bt_refactor_values -> mean, samples -> variances -> std, |std|
+// The information vector is registered as the factor's right-hand side (gmrf_bt_set_factor_rhs) for the run, as gmrf_gn_run
+// does.  Mean / samples and the variances go through the public calls' own abort-and-repeat guards (sweep_guarded); every
+// intermediate -- A's values, the posterior values the RBMC product reads -- stays in the driver's buffers on the device.
+struct gmrf_dc {
+    gmrf_handle* h = nullptr;
+    gmrf_assembler* as = nullptr;
+    gmrf_darcy_p1* d = nullptr;
+    gmrf_csr* Qp = nullptr;              // the posterior pattern as a CSR matrix (tile plan of the RBMC product), made by the first RBMC run
+    DevBuf in;                           // arena of host tables, q_nzval, q_mu (Staging)
+    DevBuf work;                         // everything below, carved up by dc_alloc
+    int64_t B = 0, ks = -1;              // what `work` is carved for
+    double *d_av = nullptr, *d_y = nullptr, *d_dw = nullptr, *d_nz = nullptr, *d_rhs = nullptr, *d_mean = nullptr, *d_smp = nullptr;
+    double *d_var = nullptr, *d_diag = nullptr, *d_part = nullptr, *d_norm = nullptr;
+    int device = 0;                      // (copies: gmrf_dc_destroy does not reach into the handle)
+    hipStream_t stream = nullptr;
+    int32_t fwd_in_factor = 0;           // the last run's factorisation left y = L^-1 rhs (gmrf_test_dc_route)
+};
+
+static gmrf_status var_batch_enqueue(gmrf_handle* h, int method, int64_t k, uint64_t seed, const gmrf_csr* Q, const double* qv,
+                                     double* d_diag, double* d_var);
+
+static int64_t std_norm_chunks(int64_t n) { return std::min<int64_t>(1024, std::max<int64_t>(1, (n + 2047) / 2048)); }
+
+static gmrf_status dc_bound_ok(const gmrf_dc* g) {
+    const gmrf_handle* h = g->h;
+    GCHK(tw_refuse(h, "the Darcy conditioning driver"));
+    if (g->as->device != h->device || g->d->device != h->device) return bad_shape("handle, assembler and Darcy assembler must live on one device");
+    if (g->as->stream != h->stream || g->d->stream != h->stream) return bad_shape("handle, assembler and Darcy assembler must share one stream");
+    if (g->as->n != g->d->n || g->as->m != g->d->n || g->as->nnz_j != g->d->nnz)
+        return bad_shape("the assembler's J is not the Darcy assembler's pattern");
+    if (h->analyzed && (h->n != g->as->n || h->nnz_in != g->as->nnz_out)) return bad_shape("the handle has not analysed the assembler's pattern");
+    return GMRF_OK;
+}
+
+gmrf_status gmrf_dc_create(gmrf_handle* h, gmrf_assembler* as, gmrf_darcy_p1* d, gmrf_dc** out) {
+    if (!out || !as || !d) return bad_shape("null pointer");
+    if (as->device < 0 || d->device < 0) {
+        g_last_error = "the Darcy conditioning driver needs an assembler and a Darcy assembler with a device (created with device -1)";
+        return GMRF_ERR_NO_DEVICE;
+    }
+    if (!h) return bad_shape("null handle");
+    gmrf_dc tmp; tmp.h = h; tmp.as = as; tmp.d = d; tmp.device = h->device; tmp.stream = h->stream;
+    GCHK(dc_bound_ok(&tmp));
+    *out = new gmrf_dc(tmp);
+    return GMRF_OK;
+}
+
+gmrf_status gmrf_dc_destroy(gmrf_dc* g) {
+    if (!g) return GMRF_OK;
+    (void)hipSetDevice(g->device);
+    (void)hipStreamSynchronize(g->stream);
+    if (g->Qp) (void)gmrf_csr_destroy(g->Qp);
+    g->in.release(); g->work.release();
+    delete g;
+    return GMRF_OK;
+}
+
+static gmrf_status dc_alloc(gmrf_dc* g, int64_t B, int64_t ks) {
+    if (g->B == B && g->ks == ks && g->work.p) return GMRF_OK;
+    const gmrf_assembler* as = g->as;
+    const int64_t n = as->n;
+    int64_t total = 0;
+    auto take = [&](int64_t elems) { const int64_t at = total; total += (std::max<int64_t>(elems, 1) + 1) & ~(int64_t)1; return at; };     // (16-byte aligned pieces)
+    const int64_t o_av = take(B * as->nnz_j), o_y = take(B * n), o_dw = take(darcy_batch_work_elems(g->d, B)), o_nz = take(B * as->nnz_out);
+    const int64_t o_rhs = take(B * n), o_mean = take(B * n), o_smp = take(B * ks * n), o_var = take(B * n), o_diag = take(B * n);
+    const int64_t o_part = take(B * std_norm_chunks(n)), o_norm = take(B);
+    GCHK(g->work.reserve(g->h->stream, sizeof(double) * (size_t)total));
+    double* w = g->work.as<double>();
+    g->d_av = w + o_av; g->d_y = w + o_y; g->d_dw = w + o_dw; g->d_nz = w + o_nz; g->d_rhs = w + o_rhs; g->d_mean = w + o_mean;
+    g->d_smp = w + o_smp; g->d_var = w + o_var; g->d_diag = w + o_diag; g->d_part = w + o_part; g->d_norm = w + o_norm;
+    g->B = B; g->ks = ks;
+    return GMRF_OK;
+}
+
+// the posterior pattern (symmetric: the assembler's CSC arrays read by rows) as the matrix whose tile plan the RBMC product uses
+static gmrf_status dc_pattern_csr(gmrf_dc* g) {
+    if (g->Qp) return GMRF_OK;
+    const gmrf_assembler* as = g->as;
+    const std::vector<double> ones((size_t)std::max<int64_t>(as->nnz_out, 1), 1.0);
+    return gmrf_csr_create(g->h->device, (void*)g->h->stream, as->n, as->n, as->colptr.data(), as->rowval.data(), ones.data(), 0, 0, &g->Qp);
+}
+
+gmrf_status gmrf_dc_run(gmrf_dc* g, const double* coeff_tables, int64_t ng, double beta, const double* q_nzval, int64_t q_stride,
+                        const double* q_mu, double q_eps, int64_t k_samples, uint64_t sample_seed, int32_t var_method, int64_t k_var,
+                        uint64_t var_seed, double* mean_out, double* samples_out, double* std_out, double* std_norm_out, int32_t* info) {
+    // (the checks of the plain arguments come before anything of *g is read: tests/test_darcy_batch_cpu.py drives them without a
+    //  device, with a driver pointer that must never be followed -- keep them above the first g->)
+    if (!g || !coeff_tables || !q_nzval) return bad_shape("null pointer");
+    if (info) *info = 0;
+    if (!darcy_ng_ok(ng)) return bad_shape("ng in [2, 46340]");
+    if (k_samples < 0 || k_samples > KP_CHUNK) return bad_shape("k_samples in [0, 128]");
+    if (samples_out && k_samples == 0) return bad_shape("samples_out with k_samples = 0");
+    const bool sampled = var_method == GMRF_VAR_RBMC || var_method == GMRF_VAR_MC;
+    if (var_method != -1 && var_method != GMRF_VAR_EXACT && !sampled) return bad_shape("var_method: -1 (none), exact, RBMC or MC");
+    if (sampled && k_var <= 0) return bad_shape("k_var <= 0");
+    if (var_method == -1 && (std_out || std_norm_out)) return bad_shape("std_out / std_norm_out without a variance method");
+    gmrf_handle* h = g->h;
+    gmrf_assembler* as = g->as;
+    GCHK(dc_bound_ok(g));
+    GCHK(q_stride_ok(as, q_stride));
+    if (!h->analyzed) { g_last_error = "gmrf_dc_run: factor the assembler's pattern once on this handle first"; return GMRF_ERR_NO_FACTOR; }
+    const int64_t B = h->B, n = as->n;
+    if (!batch_ok(B)) return bad_shape("batch outside [1, 4096]");
+    HIPCHK(hipSetDevice(h->device));
+    hipStream_t st = h->stream;
+    GCHK(dc_alloc(g, B, k_samples));
+    if (var_method == GMRF_VAR_RBMC) GCHK(dc_pattern_csr(g));
+    const double *d_tab, *d_q, *d_qmu;
+    Staging args(g->in);
+    args.in(coeff_tables, sizeof(double) * B * ng * ng, &d_tab);
+    args.in(q_nzval, sizeof(double) * (q_stride ? B * as->nnz_q : as->nnz_q), &d_q);
+    args.in(q_mu, sizeof(double) * B * n, &d_qmu);
+    GCHK(args.commit(st));
+    // 1 - 3: A's values and y, the posterior values, the information vector q_mu + q_eps A' y (x = 0: A x + y is y itself)
+    GCHK(launch_darcy_batch(g->d, st, B, d_tab, ng, beta, g->d_av, g->d_y, g->d_dw));
+    GCHK(launch_precision_batch(as, st, B, d_q, q_stride, g->d_av, q_eps, g->d_nz));
+    hipLaunchKernelGGL(assemble_jt_apply_batch, dim3((unsigned)((n + 255) / 256), (unsigned)B), dim3(256), 0, st, as->d_jt_ptr, as->d_jt_row,
+                       as->d_jt_src, g->d_av, as->nnz_j, g->d_y, as->m, d_qmu, q_eps, n, g->d_rhs);
+    HIPCHK(hipGetLastError());
+    // 4 - 6 behind the registration; the caller's comes back afterwards
+    const double* user_frhs = h->frhs;
+    h->frhs = g->d_rhs; h->fy_for = nullptr;
+    g->fwd_in_factor = 0;
+    auto solve = [&]() -> gmrf_status {
+        GCHK(numeric_factor(h, g->d_nz, info));
+        g->fwd_in_factor = (h->fy_for && h->fy_for == g->d_rhs) ? 1 : 0;
+        if (k_samples > 0) GCHK(gmrf_bt_posterior(h, g->d_rhs, sample_seed, 0, k_samples, g->d_mean, g->d_smp, n));
+        else GCHK(gmrf_bt_solve(h, g->d_rhs, g->d_mean, 1, n, n, GMRF_SOLVE_FULL));
+        if (var_method == GMRF_VAR_EXACT) GCHK(gmrf_bt_marginal_var(h, GMRF_VAR_EXACT, 0, 0, nullptr, g->d_var));
+        else if (sampled)
+            GCHK(sweep_guarded(h, {}, [&]() -> gmrf_status {     // (a batch of one: its sweeps may be persistent launches)
+                GCHK(var_batch_enqueue(h, var_method, k_var, var_seed, g->Qp, g->d_nz, g->d_diag, g->d_var));
+                HIPCHK(hipStreamSynchronize(st));
+                return GMRF_OK;
+            }));
+        return GMRF_OK;
+    };
+    const gmrf_status status = solve();
+    h->frhs = user_frhs; h->fy_for = nullptr;
+    if (status != GMRF_OK) { (void)hipStreamSynchronize(st); return status; }      // (the outputs are untouched)
+    // 7: std = sqrt(var) in place, |std| per problem
+    if (var_method != -1) {
+        const int64_t nch = std_norm_chunks(n), len = (n + nch - 1) / nch;
+        hipLaunchKernelGGL(std_norm_part, dim3((unsigned)nch, (unsigned)B), dim3(256), 0, st, g->d_var, n, len, g->d_part);
+        hipLaunchKernelGGL(std_norm_finish, dim3(1, (unsigned)B), dim3(256), 0, st, g->d_part, nch, g->d_norm);
+        HIPCHK(hipGetLastError());
+    }
+    auto copy_out = [&](double* dst, const double* src, int64_t count) -> gmrf_status {
+        if (!dst) return GMRF_OK;
+        HIPCHK(hipMemcpyAsync(dst, src, sizeof(double) * (size_t)count, is_device_ptr(dst) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
+        return GMRF_OK;
+    };
+    GCHK(copy_out(mean_out, g->d_mean, B * n));
+    GCHK(copy_out(samples_out, g->d_smp, B * k_samples * n));
+    GCHK(copy_out(std_out, g->d_var, B * n));
+    GCHK(copy_out(std_norm_out, g->d_norm, B));
+    HIPCHK(hipStreamSynchronize(st));
+    return GMRF_OK;
 }
 
 // --------------------------------------------------------------------------------- shallow-water element kernels
@@ -4916,6 +5165,60 @@ static gmrf_status var_chunk(gmrf_handle* h, int method, int64_t p, int kc, cons
     return GMRF_OK;
 }
 
+// Most bytes the node-major stage of the batched estimators may take (GMRF_VAR_STAGE_MB, read at every call; default 512):
+// a problem's stage is 2 kcp n doubles (67 MB at darcy256), so a batch goes through it in groups.
+static int64_t var_stage_cap_bytes() {
+    const char* e = getenv("GMRF_VAR_STAGE_MB");
+    const int64_t mb = e ? atoll(e) : 512;
+    return std::max<int64_t>(mb, 1) << 20;
+}
+
+// The sampled estimator of every problem of a batch, enqueued on the handle's stream (no synchronisation): d_var[B][n] <- the
+// variances.  Per chunk of 64 samples one sweep serves all problems (sample_chunk); then, per group of problems that fits the
+// stage, ONE transposing unpack, ONE SpMM (RBMC; qv[B][nnz]: the problems' values on Q's pattern, device) and ONE accumulate
+// with the problem as a grid dimension -- the kernels of var_chunk with the same sums per row and entry, so problem p gets the
+// bits of var_chunk(h, method, p, ...).  d_diag[B][n]: work (RBMC).
+static gmrf_status var_batch_enqueue(gmrf_handle* h, int method, int64_t k, uint64_t seed, const gmrf_csr* Q, const double* qv,
+                                     double* d_diag, double* d_var) {
+    const int64_t n = h->n, B = h->B;
+    const bool rb = method == GMRF_VAR_RBMC;
+    const dim3 grid_n((unsigned)((n + 255) / 256), (unsigned)B);
+    HIPCHK(hipMemsetAsync(d_var, 0, sizeof(double) * n * B, h->stream));
+    if (rb) {
+        hipLaunchKernelGGL(csr_extract_diag_batch, grid_n, dim3(256), 0, h->stream, Q->d_rowptr, Q->d_colidx, qv, Q->nnz, n, d_diag);
+        HIPCHK(hipGetLastError());
+    }
+    // groups sized by the widest chunk of the call, the same for every chunk (MC has no Q X half)
+    const int64_t halves = rb ? 2 : 1;
+    const int64_t kc_max = std::min<int64_t>(64, k), per_max = halves * (kc_max + (kc_max & 1)) * n;
+    const int64_t G = std::max<int64_t>(1, std::min<int64_t>(B, var_stage_cap_bytes() / (per_max * (int64_t)sizeof(double))));
+    GCHK(ensure_stage(h, G * per_max));
+    h->var_group = (int32_t)G; h->var_groups = (int32_t)((B + G - 1) / G);
+    for (int64_t c0 = 0; c0 < k; c0 += 64) {
+        const int kc = (int)std::min<int64_t>(64, k - c0);
+        GCHK(sample_chunk(h, seed, c0, kc, nullptr, 0, k));          // every problem's chunk in one sweep
+        const int kp = pad_k(kc), kcp = kc + (kc & 1);
+        const int64_t per = halves * (int64_t)kcp * n;
+        for (int64_t g0 = 0; g0 < B; g0 += G) {
+            const int64_t gb = std::min(G, B - g0);
+            double* Xr = h->d_stage;
+            double* QX = rb ? h->d_stage + (int64_t)kcp * n : Xr;      // (MC: not read)
+            hipLaunchKernelGGL(unpack_panel_rows_batch, dim3((unsigned)((n + 63) / 64), (unsigned)((kc + 63) / 64), (unsigned)gb), dim3(256), 0,
+                               h->stream, h->d_Y + g0 * kp * h->n_pad, h->n_pad, (int64_t)kp * h->n_pad, Xr, (int64_t)kcp, per, (int)h->bs,
+                               (int)h->bsp, n, kc);
+            HIPCHK(hipGetLastError());
+            if (rb) GCHK(spmm_rows_device_batch(Q, h->stream, gb, qv + g0 * Q->nnz, Xr, kcp, per, QX, kcp, per, kc));
+            hipLaunchKernelGGL(rbmc_accumulate_rows_batch, dim3((unsigned)((n + 15) / 16), (unsigned)gb), dim3(256), 0, h->stream, QX, Xr,
+                               (int64_t)kcp, per, rb ? d_diag + g0 * n : (const double*)nullptr, n, kc, d_var + g0 * n, rb ? 0 : 1);
+            HIPCHK(hipGetLastError());
+        }
+    }
+    // finish in place: var = base + acc / k
+    hipLaunchKernelGGL(var_finish_batch, grid_n, dim3(256), 0, h->stream, d_var, rb ? d_diag : (const double*)nullptr, 1.0 / (double)k, n, d_var);
+    HIPCHK(hipGetLastError());
+    return GMRF_OK;
+}
+
 static gmrf_status var_accumulate_dev(gmrf_handle* h, int method, int64_t first_id, int64_t k, uint64_t seed,
                                       const gmrf_csr* Q, double* d_acc) {
     for (int64_t c0 = 0; c0 < k; c0 += 64) {
@@ -5015,7 +5318,6 @@ gmrf_status gmrf_bt_marginal_var_batch(gmrf_handle* h, int32_t method, int64_t k
     const int64_t n = h->n, B = h->B;
     GCHK(ensure_acc(h, B));
     GCHK(sweep_guarded(h, {}, [&]() -> gmrf_status {     // (a batch of one: its sweeps may be persistent launches)
-        HIPCHK(hipMemsetAsync(h->d_acc, 0, sizeof(double) * n * B, h->stream));
         std::unique_ptr<double, void (*)(void*)> d_qv(nullptr, free_dev), d_diag(nullptr, free_dev);     // (freed on every way out)
         const double* qv = q_vals;
         if (method == GMRF_VAR_RBMC) {
@@ -5028,23 +5330,8 @@ gmrf_status gmrf_bt_marginal_var_batch(gmrf_handle* h, int32_t method, int64_t k
             }
             HIPCHK(hipMalloc(&buf, sizeof(double) * n * B));
             d_diag.reset(buf);
-            for (int64_t p = 0; p < B; ++p)
-                hipLaunchKernelGGL(csr_extract_diag, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, Q->d_rowptr,
-                                   Q->d_colidx, qv + p * Q->nnz, (const float*)nullptr, n, d_diag.get() + p * n);
-            HIPCHK(hipGetLastError());
         }
-        for (int64_t c0 = 0; c0 < k; c0 += 64) {
-            const int kc = (int)std::min<int64_t>(64, k - c0);
-            GCHK(sample_chunk(h, seed, c0, kc, nullptr, 0, k));          // every problem's chunk in one sweep
-            for (int64_t p = 0; p < B; ++p)
-                GCHK(var_chunk(h, method, p, kc, Q, method == GMRF_VAR_RBMC ? qv + p * Q->nnz : nullptr,
-                               method == GMRF_VAR_RBMC ? d_diag.get() + p * n : nullptr, h->d_acc + p * n));
-        }
-        for (int64_t p = 0; p < B; ++p)
-            hipLaunchKernelGGL(var_finish, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->d_acc + p * n,
-                               method == GMRF_VAR_RBMC ? d_diag.get() + p * n : (const double*)nullptr, 1.0 / (double)k, n,
-                               h->d_acc + p * n);
-        HIPCHK(hipGetLastError());
+        GCHK(var_batch_enqueue(h, method, k, seed, Q, qv, d_diag.get(), h->d_acc));
         const hipMemcpyKind kind = is_device_ptr(var_out) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
         HIPCHK(hipMemcpyAsync(var_out, h->d_acc, sizeof(double) * n * B, kind, h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));
@@ -5832,6 +6119,21 @@ gmrf_status gmrf_test_factor_fwd(gmrf_handle* h, int32_t* state, double* y_out) 
 gmrf_status gmrf_test_gn_route(gmrf_gn* g, int32_t* iterations, int32_t* fwd_iterations) {
     if (!g || !iterations || !fwd_iterations) return bad_shape("null pointer");
     *iterations = g->iterations; *fwd_iterations = g->fwd_iterations;
+    return GMRF_OK;
+}
+
+// The last gmrf_dc_run: 1 if its factorisation carried the forward sweep of the information vector (the forward-in-factor route)
+gmrf_status gmrf_test_dc_route(gmrf_dc* g, int32_t* fwd_in_factor) {
+    if (!g || !fwd_in_factor) return bad_shape("null pointer");
+    *fwd_in_factor = g->fwd_in_factor;
+    return GMRF_OK;
+}
+
+// The last batched sampled estimator of this handle (gmrf_bt_marginal_var_batch, gmrf_dc_run): problems per group of the stage
+// and groups per chunk, as GMRF_VAR_STAGE_MB sized them
+gmrf_status gmrf_test_var_groups(gmrf_handle* h, int32_t* group_size, int32_t* groups) {
+    if (!h || !group_size || !groups) return bad_shape("null pointer");
+    *group_size = h->var_group; *groups = h->var_groups;
     return GMRF_OK;
 }
 

@@ -658,11 +658,17 @@ inline size_t spmm_tile_lds_bytes(int R, int ucap, int ecap) {
 
 constexpr int SPMM_THREADS = 256;
 
+// BATCH form of the two tiled kernels below: one pattern and one tile plan, B problems.  blockIdx.y is the problem, its values
+// lie at vals + p nnz, its node-major operands at X + p x_stride and Y + p y_stride (strides that keep them 16-byte aligned).
+// Everything behind the three offsets is the one-problem kernel: the same LDS image and, per row and entry, the same sums in
+// the same order.
+struct SpmmBatch { int64_t nnz = 0, x_stride = 0, y_stride = 0; };
+
 // LDS traffic decides this kernel (rocprofv3: HBM bytes = the algorithmic ones, the re-gathered rows of X
 // come from L2): a lane owns FOUR right-hand sides of one row, so the index and value of an entry are
 // read once per 4 products and the X values as 16-byte pieces -- 12 LDS cycles per 256 products instead
 // of 6 per 64 with one right-hand side per lane.
-template <typename VT, int NG>
+template <typename VT, int NG, bool BATCH = false>
 __global__ __launch_bounds__(SPMM_THREADS, 3) void csr_spmm_tiles(const int64_t* __restrict__ rowptr,
                                                                const uint16_t* __restrict__ lidx,
                                                                const VT* __restrict__ vals,
@@ -670,7 +676,10 @@ __global__ __launch_bounds__(SPMM_THREADS, 3) void csr_spmm_tiles(const int64_t*
                                                                const int32_t* __restrict__ ucols, int64_t n_rows,
                                                                const double* __restrict__ X, int64_t ldx,
                                                                double* __restrict__ Y, int64_t ldy, int k,
-                                                               int R, int ucap, int ecap) {
+                                                               int R, int ucap, int ecap, SpmmBatch batch = SpmmBatch()) {
+    if constexpr (BATCH) {                                   // blockIdx.y is the problem
+        vals += (int64_t)blockIdx.y * batch.nnz; X += (int64_t)blockIdx.y * batch.x_stride; Y += (int64_t)blockIdx.y * batch.y_stride;
+    }
     extern __shared__ __attribute__((aligned(16))) double smem[];
     double* xs = smem;                                       // [ucap][SPMM_XLD]
     double* vs = xs + (size_t)ucap * SPMM_XLD;               // [ecap]
@@ -812,7 +821,7 @@ __global__ __launch_bounds__(SPMM_THREADS, 3) void csr_spmm_tiles(const int64_t*
 // banks exactly once -- parity of u picks the 128-byte half of the bank array, bit 1 the 64-byte quarter.  With the
 // padded stride of 18 doubles the unpadded kernel's reads of rows u and u + 2 overlap in 3 of 4 slots
 // (SQ_LDS_BANK_CONFLICT = 21 % of its LDS-active cycles); stride 20: 767 us, 18: 621 us, swizzle: 585 us.
-template <typename VT, int NG>
+template <typename VT, int NG, bool BATCH = false>
 __global__ __launch_bounds__(SPMM_THREADS, 3) void csr_spmm_tiles_pad(const int64_t* __restrict__ rowptr,
                                                                    const uint16_t* __restrict__ lidx,
                                                                    const VT* __restrict__ vals,
@@ -820,7 +829,10 @@ __global__ __launch_bounds__(SPMM_THREADS, 3) void csr_spmm_tiles_pad(const int6
                                                                    const int32_t* __restrict__ ucols, int64_t n_rows,
                                                                    const double* __restrict__ X, int64_t ldx,
                                                                    double* __restrict__ Y, int64_t ldy, int k,
-                                                                   int R, int ucap, int ecap) {
+                                                                   int R, int ucap, int ecap, SpmmBatch batch = SpmmBatch()) {
+    if constexpr (BATCH) {                                   // blockIdx.y is the problem
+        vals += (int64_t)blockIdx.y * batch.nnz; X += (int64_t)blockIdx.y * batch.x_stride; Y += (int64_t)blockIdx.y * batch.y_stride;
+    }
     extern __shared__ __attribute__((aligned(16))) double smem[];
     double* xs = smem;                                       // [ucap][16], swizzled (below)
     double* vs = xs + (size_t)ucap * SPMM_KC;               // [ecap + 2 R]  (padded rows; row r skewed by 2 r doubles: rows 16 entries
@@ -954,11 +966,11 @@ inline size_t spmm_tile_pad_lds_bytes(int R, int ucap, int ecap_pad) {
 // odd k / ldx): 16 lanes along the right-hand sides, 4 rows per wave, operands straight from global
 // memory; same summation order.
 template <typename VT>
-__global__ __launch_bounds__(256) void csr_spmm_rows(const int64_t* __restrict__ rowptr,
-                                                     const int32_t* __restrict__ colidx,
-                                                     const VT* __restrict__ vals, int64_t n_rows,
-                                                     const double* __restrict__ X, int64_t ldx,
-                                                     double* __restrict__ Y, int64_t ldy, int k) {
+__device__ __forceinline__ void csr_spmm_rows_body(const int64_t* __restrict__ rowptr,
+                                                   const int32_t* __restrict__ colidx,
+                                                   const VT* __restrict__ vals, int64_t n_rows,
+                                                   const double* __restrict__ X, int64_t ldx,
+                                                   double* __restrict__ Y, int64_t ldy, int k) {
     const int t = threadIdx.x;
     const int kl = t & 15;
     const int64_t row = (int64_t)blockIdx.x * 16 + (t >> 4);
@@ -975,11 +987,32 @@ __global__ __launch_bounds__(256) void csr_spmm_rows(const int64_t* __restrict__
     }
 }
 
+template <typename VT>
+__global__ __launch_bounds__(256) void csr_spmm_rows(const int64_t* __restrict__ rowptr,
+                                                     const int32_t* __restrict__ colidx,
+                                                     const VT* __restrict__ vals, int64_t n_rows,
+                                                     const double* __restrict__ X, int64_t ldx,
+                                                     double* __restrict__ Y, int64_t ldy, int k) {
+    csr_spmm_rows_body<VT>(rowptr, colidx, vals, n_rows, X, ldx, Y, ldy, k);
+}
+
+// blockIdx.y is the problem (values at vals + p nnz, operands at X + p x_stride, Y + p y_stride)
+template <typename VT>
+__global__ __launch_bounds__(256) void csr_spmm_rows_batch(const int64_t* __restrict__ rowptr,
+                                                           const int32_t* __restrict__ colidx,
+                                                           const VT* __restrict__ vals, int64_t n_rows,
+                                                           const double* __restrict__ X, int64_t ldx,
+                                                           double* __restrict__ Y, int64_t ldy, int k, int64_t nnz,
+                                                           int64_t x_stride, int64_t y_stride) {
+    const int64_t p = blockIdx.y;
+    csr_spmm_rows_body<VT>(rowptr, colidx, vals + p * nnz, n_rows, X + p * x_stride, ldx, Y + p * y_stride, ldy, k);
+}
+
 // panel P[rhs][n_pad] (each right-hand side contiguous, padded blocks) -> node-major X[n][k] through a
 // 64 x 64 LDS tile (both sides move 128-byte pieces); blockIdx.x = 64-dof tile, blockIdx.y = 64-rhs tile
-__global__ __launch_bounds__(256) void unpack_panel_rows(const double* __restrict__ P, int64_t n_pad,
-                                                         double* __restrict__ dst, int64_t ld, int bs, int bsp,
-                                                         int64_t n, int k) {
+__device__ __forceinline__ void unpack_panel_rows_tile(const double* __restrict__ P, int64_t n_pad,
+                                                       double* __restrict__ dst, int64_t ld, int bs, int bsp,
+                                                       int64_t n, int k) {
     __shared__ double tile[64][65];
     const int t = threadIdx.x;
     const int64_t j0 = (int64_t)blockIdx.x * 64;
@@ -998,10 +1031,24 @@ __global__ __launch_bounds__(256) void unpack_panel_rows(const double* __restric
     }
 }
 
+__global__ __launch_bounds__(256) void unpack_panel_rows(const double* __restrict__ P, int64_t n_pad,
+                                                         double* __restrict__ dst, int64_t ld, int bs, int bsp,
+                                                         int64_t n, int k) {
+    unpack_panel_rows_tile(P, n_pad, dst, ld, bs, bsp, n, k);
+}
+
+// blockIdx.z is the problem: its panel lies at P + p p_stride, its node-major image goes to dst + p dst_stride
+__global__ __launch_bounds__(256) void unpack_panel_rows_batch(const double* __restrict__ P, int64_t n_pad, int64_t p_stride,
+                                                               double* __restrict__ dst, int64_t ld, int64_t dst_stride, int bs,
+                                                               int bsp, int64_t n, int k) {
+    const int64_t p = blockIdx.z;
+    unpack_panel_rows_tile(P + p * p_stride, n_pad, dst + p * dst_stride, ld, bs, bsp, n, k);
+}
+
 // acc[i] += sum_s ((QX[i][s] - d_i X[i][s]) / d_i)^2 with node-major QX, X (row stride ld): 16 lanes per node
-__global__ __launch_bounds__(256) void rbmc_accumulate_rows(const double* __restrict__ QX, const double* __restrict__ X,
-                                                            int64_t ld, const double* __restrict__ diag, int64_t n, int k,
-                                                            double* __restrict__ acc, int plain_mc) {
+__device__ __forceinline__ void rbmc_accumulate_node(const double* __restrict__ QX, const double* __restrict__ X,
+                                                     int64_t ld, const double* __restrict__ diag, int64_t n, int k,
+                                                     double* __restrict__ acc, int plain_mc) {
     const int kl = threadIdx.x & 15;
     const int64_t i = (int64_t)blockIdx.x * 16 + (threadIdx.x >> 4);
     double s = 0.0;
@@ -1015,6 +1062,20 @@ __global__ __launch_bounds__(256) void rbmc_accumulate_rows(const double* __rest
 #pragma unroll
     for (int off = 8; off > 0; off >>= 1) s += __shfl_xor(s, off, 16);
     if (i < n && kl == 0) acc[i] += s;
+}
+
+__global__ __launch_bounds__(256) void rbmc_accumulate_rows(const double* __restrict__ QX, const double* __restrict__ X,
+                                                            int64_t ld, const double* __restrict__ diag, int64_t n, int k,
+                                                            double* __restrict__ acc, int plain_mc) {
+    rbmc_accumulate_node(QX, X, ld, diag, n, k, acc, plain_mc);
+}
+
+// blockIdx.y is the problem: QX, X at + p stage_stride, diag (RBMC) and acc at + p n
+__global__ __launch_bounds__(256) void rbmc_accumulate_rows_batch(const double* __restrict__ QX, const double* __restrict__ X,
+                                                                  int64_t ld, int64_t stage_stride, const double* __restrict__ diag,
+                                                                  int64_t n, int k, double* __restrict__ acc, int plain_mc) {
+    const int64_t p = blockIdx.y;
+    rbmc_accumulate_node(QX + p * stage_stride, X + p * stage_stride, ld, plain_mc ? nullptr : diag + p * n, n, k, acc + p * n, plain_mc);
 }
 
 // ------------------------------------------------------------------------------- variances
@@ -1057,12 +1118,32 @@ __global__ void csr_extract_diag(const int64_t* __restrict__ rowptr, const int32
     diag[i] = d;
 }
 
+// vals[B][nnz] -> diag[B][n]; blockIdx.y is the problem (fp64 values: the per-problem values of a batch)
+__global__ void csr_extract_diag_batch(const int64_t* __restrict__ rowptr, const int32_t* __restrict__ colidx,
+                                       const double* __restrict__ vals, int64_t nnz, int64_t n, double* __restrict__ diag) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
+    if (i >= n) return;
+    vals += b * nnz;
+    double d = 0.0;
+    for (int64_t p = rowptr[i]; p < rowptr[i + 1]; ++p)
+        if (colidx[p] == i) d += vals[p];
+    diag[b * n + i] = d;
+}
+
 // var = base + acc * scale     (base: 1/Q_ii for RBMC, 0 for MC)
 __global__ void var_finish(const double* __restrict__ acc, const double* __restrict__ diag,
                            double scale, int64_t n, double* __restrict__ out) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     out[i] = (diag ? 1.0 / diag[i] : 0.0) + acc[i] * scale;
+}
+
+// acc, diag, out: [B][n]; blockIdx.y is the problem
+__global__ void var_finish_batch(const double* __restrict__ acc, const double* __restrict__ diag,
+                                 double scale, int64_t n, double* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, at = (int64_t)blockIdx.y * n + i;
+    if (i >= n) return;
+    out[at] = (diag ? 1.0 / diag[at] : 0.0) + acc[at] * scale;
 }
 
 // sum over the diagonal of log(L[j][j]) for every block; one workgroup per block (blockIdx.x) and

@@ -558,6 +558,35 @@ gmrf_status gmrf_gn_run(gmrf_gn* g, const double* q_nzval, int64_t q_stride, con
                         double* obj_hist_out, int32_t* info);
 gmrf_status gmrf_gn_finalize(gmrf_gn* g, int32_t* info);
 
+/* The Darcy data-set loop (scripts/darcy/solve_darcy_gmrf-fem.jl:176-198 per problem) for a batch of problems on one mesh.
+ * gmrf_darcy_p1_assemble_batch: coeff_tables [batch][ng][ng] -> vals_out [batch][nnz], f_out [batch][n]; problem p gets the bits
+ * of gmrf_darcy_p1_assemble on its table (both element orders); host or device pointers; batch in [1, 4096]. */
+gmrf_status gmrf_darcy_p1_assemble_batch(gmrf_darcy_p1* d, int64_t batch, const double* coeff_tables, int64_t ng, double beta,
+                                         double* vals_out, double* f_out);
+/* The driver binds a handle (reference order; its batch B is the number of problems), an assembler whose J is the Darcy
+ * assembler's pattern, and that Darcy assembler, all on ONE device and ONE stream (create the three with the same stream argument);
+ * anything else -- a twisted handle, a handle that analysed another pattern -- is GMRF_ERR_BAD_SHAPE, an assembler created with
+ * device -1 GMRF_ERR_NO_DEVICE.  gmrf_dc_run: the handle must have factored the assembler's pattern once (GMRF_ERR_NO_FACTOR
+ * before).  One call, on the handle's stream:
+ *     tables -> A, y (the element kernels) -> Q + q_eps A'A -> information vector q_mu + q_eps A'y, registered with
+ *     gmrf_bt_set_factor_rhs for the run (the caller's registration is put back) -> gmrf_bt_refactor_values ->
+ *     gmrf_bt_posterior (mean, k_samples samples with the sample ids of a batch: problem p, sample s = p k_samples + s) ->
+ *     variances (var_method -1: none; GMRF_VAR_EXACT; GMRF_VAR_RBMC / GMRF_VAR_MC with k_var samples, problem p drawing the ids
+ *     p k_var .. p k_var + k_var - 1 like gmrf_bt_marginal_var_batch, on the posterior values just assembled) ->
+ *     std = sqrt(var) and |std_p|_2 (a fixed-shape sum without atomics: the same bits in every batch).
+ * q_nzval: the prior's values, q_stride 0 = shared, nnz(Q) = per problem; q_mu [B][n] = Q mu or NULL (zero prior mean).
+ * coeff_tables, q_nzval, q_mu: host or device.  Outputs, each NULL (not wanted), host or device: mean_out [B][n], samples_out
+ * [B][k_samples][n] (k_samples in [0, 128]), std_out [B][n], std_norm_out [B].  GMRF_ERR_NOT_SPD ends the call with `info` as
+ * gmrf_bt_refactor_values sets it and leaves the outputs untouched.  The stage of the sampled estimators is capped
+ * (GMRF_VAR_STAGE_MB, default 512): the problems go through it in groups. */
+typedef struct gmrf_dc gmrf_dc;
+gmrf_status gmrf_dc_create(gmrf_handle* h, gmrf_assembler* as, gmrf_darcy_p1* d, gmrf_dc** out);
+gmrf_status gmrf_dc_destroy(gmrf_dc* g);
+gmrf_status gmrf_dc_run(gmrf_dc* g, const double* coeff_tables, int64_t ng, double beta, const double* q_nzval, int64_t q_stride,
+                        const double* q_mu, double q_eps, int64_t k_samples, uint64_t sample_seed, int32_t var_method, int64_t k_var,
+                        uint64_t var_seed, double* mean_out, double* samples_out, double* std_out, double* std_norm_out,
+                        int32_t* info);
+
 /* Linear shallow-water SPDE (FEM block assembly, third piece): the element loops of `assemble_system!`,
  * /root/reference/src/spdes/shallow_water.jl:17-122 -- coupling matrix K (h-u, h-v: -H grad(phi_i) phi_j; u-h, v-h:
  * -g grad(phi_i) phi_j; u-u, v-v: k phi_i phi_j; u-v / v-u: -+ f phi_i phi_j), element-lumped mass M (`lump_matrix`, :116),
@@ -619,6 +648,10 @@ gmrf_status gmrf_test_persist_aborts(gmrf_handle* h, int32_t* n);
 gmrf_status gmrf_test_factor_fwd(gmrf_handle* h, int32_t* state, double* y_out);
 /* the last gmrf_gn_run: iterations, and those whose solve took y = L^-1 rhs from the factorisation */
 gmrf_status gmrf_test_gn_route(gmrf_gn* g, int32_t* iterations, int32_t* fwd_iterations);
+/* the last gmrf_dc_run: 1 if its factorisation took y = L^-1 rhs along (the forward-in-factor route) */
+gmrf_status gmrf_test_dc_route(gmrf_dc* g, int32_t* fwd_in_factor);
+/* the last batched sampled estimator of the handle: problems per group of the stage, groups per chunk (GMRF_VAR_STAGE_MB) */
+gmrf_status gmrf_test_var_groups(gmrf_handle* h, int32_t* group_size, int32_t* groups);
 /* The per-device budget of CUs for persistent launches, host only (no GPU needed): `n` handles ask for demands[i] CUs one after
  * the other on a device of `cus` CUs; granted[i] = 1 if the claim fitted beside the earlier ones, 0 if it was refused (the
  * handle would take the launch-per-step routes up front instead of meeting a bounded wait). */

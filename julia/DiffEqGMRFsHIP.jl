@@ -30,7 +30,8 @@ module DiffEqGMRFsHIP
 using SparseArrays, LinearAlgebra
 
 export TridiagonalCholeskyFactor, tridiagonal_cholesky, forward_solve, backward_solve, ldiv, PosteriorAssembler, GmrfCsr,
-       GmrfComm, DarcyP1Assembler, BurgersP1Tangent, GaussNewtonBatch, gauss_newton_batch!
+       GmrfComm, DarcyP1Assembler, BurgersP1Tangent, GaussNewtonBatch, gauss_newton_batch!, DarcyConditioningBatch,
+       condition_on_observations_batch, assemble_batch!
 
 const libgmrf = get(ENV, "LIBGMRF_HIP", joinpath(@__DIR__, "..", "diffeqgmrfs.jl_amd", "csrc", "libgmrf_hip.so"))
 
@@ -539,6 +540,15 @@ function assemble!(vals::Vector{Float64}, f::Vector{Float64}, d::DarcyP1Assemble
     return vals, f
 end
 
+"`assemble!` for every table of `coeff` (ng x ng x batch); `vals` (nnz x batch) and `f` (n x batch): column p gets the bits of `assemble!` on table p."
+function assemble_batch!(vals::Matrix{Float64}, f::Matrix{Float64}, d::DarcyP1Assembler, coeff::Array{Float64,3}; beta::Real = 1.0)
+    ng = size(coeff, 1)
+    tabs = permutedims(coeff, (2, 1, 3))       # table[x index][y index] row-major per problem, problem-major
+    GC.@preserve tabs vals f check(ccall((:gmrf_darcy_p1_assemble_batch, libgmrf), Int32,
+        (Ptr{Cvoid}, Int64, Ptr{Float64}, Int64, Float64, Ptr{Float64}, Ptr{Float64}), d.handle, size(coeff, 3), tabs, ng, Float64(beta), vals, f))
+    return vals, f
+end
+
 # Burgers residual and tangent (f_and_J, scripts/burgers/solve_burgers_gmrf-fem.jl:118-149) on the periodic P1 line
 mutable struct BurgersP1Tangent
     handle::Ptr{Cvoid}
@@ -624,6 +634,55 @@ function finalize!(gn::GaussNewtonBatch)
     info = Ref{Int32}(0)
     check(ccall((:gmrf_gn_finalize, libgmrf), Int32, (Ptr{Cvoid}, Ref{Int32}), gn.handle, info), info[])
     return gn.F
+end
+
+# The Darcy data-set loop (scripts/darcy/solve_darcy_gmrf-fem.jl:176-198) for a batch of problems in one call on the device.
+# `F` (batch = number of problems, reference order, factored once on `as.pattern`), `as` (built on `d.pattern`) and `d` must have
+# been created on one device and one stream.
+mutable struct DarcyConditioningBatch
+    handle::Ptr{Cvoid}
+    F::TridiagonalCholeskyFactor
+    as::PosteriorAssembler
+    d::DarcyP1Assembler
+end
+
+function DarcyConditioningBatch(F::TridiagonalCholeskyFactor, as::PosteriorAssembler, d::DarcyP1Assembler)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:gmrf_dc_create, libgmrf), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{Ptr{Cvoid}}), F.handle, as.handle, d.handle, h))
+    dc = DarcyConditioningBatch(h[], F, as, d)
+    finalizer(g -> ccall((:gmrf_dc_destroy, libgmrf), Int32, (Ptr{Cvoid},), g.handle), dc)
+    return dc
+end
+
+"""
+    condition_on_observations_batch(dc, coeff, q_nzval; Q_mu = nothing, q_eps = 1e8, beta = 1.0, k_samples = 1, var = :rbmc,
+                                    k_var = 50, sample_seed = 0x5EED, var_seed = 0x5EED)
+
+`coeff` (ng x ng x B) as `ds.darcy_vars["coeff"]`; `q_nzval` the prior's values (a vector: one prior for all; a matrix: one column
+per problem); `Q_mu` (n x B) = Q * mu or nothing.  Returns `(mean (n x B), samples (n x k_samples x B), std (n x B), norm(std) (B))`
+with the defaults of scripts/darcy/solve_darcy_gmrf-fem.jl:163 and :174; `var = :exact`, `:mc` or `:none` choose the other estimators.
+"""
+function condition_on_observations_batch(dc::DarcyConditioningBatch, coeff::Array{Float64,3}, q_nzval::VecOrMat{Float64};
+                                         Q_mu::Union{Nothing,Matrix{Float64}} = nothing, q_eps::Real = 1e8, beta::Real = 1.0,
+                                         k_samples::Integer = 1, var::Symbol = :rbmc, k_var::Integer = 50,
+                                         sample_seed::Integer = 0x5EED, var_seed::Integer = 0x5EED)
+    B = size(coeff, 3); ng = size(coeff, 1); n = size(dc.as.pattern, 1)
+    method = Dict(:none => -1, :exact => 0, :rbmc => 1, :mc => 2)[var]
+    tabs = permutedims(coeff, (2, 1, 3))
+    q_stride = q_nzval isa Matrix ? size(q_nzval, 1) : 0
+    mean = Matrix{Float64}(undef, n, B); samples = Array{Float64,3}(undef, n, k_samples, B)
+    sd = Matrix{Float64}(undef, n, B); nrm = Vector{Float64}(undef, B); info = Ref{Int32}(0)
+    qm = Q_mu === nothing ? Ptr{Float64}(C_NULL) : pointer(Q_mu)
+    sp = k_samples > 0 ? pointer(samples) : Ptr{Float64}(C_NULL)
+    sdp = method >= 0 ? pointer(sd) : Ptr{Float64}(C_NULL)
+    np = method >= 0 ? pointer(nrm) : Ptr{Float64}(C_NULL)
+    st = GC.@preserve tabs q_nzval Q_mu mean samples sd nrm ccall((:gmrf_dc_run, libgmrf), Int32,
+        (Ptr{Cvoid}, Ptr{Float64}, Int64, Float64, Ptr{Float64}, Int64, Ptr{Float64}, Float64, Int64, UInt64, Int32, Int64, UInt64,
+         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{Int32}),
+        dc.handle, tabs, ng, Float64(beta), q_nzval, q_stride, qm, Float64(q_eps), k_samples, UInt64(sample_seed), Int32(method), k_var,
+        UInt64(var_seed), mean, sp, sdp, np, info)
+    check(st, info[])
+    return mean, samples, sd, nrm
 end
 
 # Linear shallow-water SPDE (src/spdes/shallow_water.jl): element kernels of assemble_system! (:17-122) and the per-step

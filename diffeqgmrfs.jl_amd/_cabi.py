@@ -42,6 +42,8 @@ EXPORTS = [
     "gmrf_assemble_create", "gmrf_assemble_destroy", "gmrf_assemble_pattern", "gmrf_assemble_precision", "gmrf_assemble_rhs",
     "gmrf_burgers_p1_tangent_batch", "gmrf_assemble_precision_batch", "gmrf_assemble_rhs_batch", "gmrf_assemble_objective_batch",
     "gmrf_gn_create", "gmrf_gn_destroy", "gmrf_gn_run", "gmrf_gn_finalize",
+    "gmrf_elliptic_p1_create", "gmrf_elliptic_p1_destroy", "gmrf_elliptic_p1_pattern", "gmrf_elliptic_p1_qpoints",
+    "gmrf_elliptic_p1_tangent", "gmrf_elliptic_p1_tangent_batch", "gmrf_elliptic_p1_load", "gmrf_gn_create_elliptic",
     "gmrf_darcy_p1_assemble_batch", "gmrf_dc_create", "gmrf_dc_destroy", "gmrf_dc_run",
     "gmrf_test_gemm", "gmrf_test_gemm_rate", "gmrf_test_gemm_shapes", "gmrf_test_potrf_tile", "gmrf_test_potrf_block", "gmrf_test_tile_timing", "gmrf_test_persist_stamps", "gmrf_test_persist_aborts", "gmrf_test_factor_fwd", "gmrf_test_gn_route", "gmrf_test_dc_route", "gmrf_test_var_groups", "gmrf_test_persist_budget", "gmrf_test_clock_probe_start", "gmrf_test_clock_probe_finish",
     "gmrf_test_mfma_f64_rate", "gmrf_test_hbm_rate", "gmrf_test_microbench", "gmrf_test_symbolic_csc",
@@ -178,6 +180,14 @@ def load() -> C.CDLL:
         "gmrf_assemble_rhs_batch": [vp, i64, vp, vp, vp, vp, dbl, vp],
         "gmrf_assemble_objective_batch": [vp, i64, vp, i64, vp, vp, vp, dbl, vp],
         "gmrf_gn_create": [vp, vp, vp, P(vp)],
+        "gmrf_gn_create_elliptic": [vp, vp, vp, P(vp)],
+        "gmrf_elliptic_p1_create": [i32, vp, i64, i64, P(vp)],
+        "gmrf_elliptic_p1_destroy": [vp],
+        "gmrf_elliptic_p1_pattern": [vp, P(i64), vp, vp, i32],
+        "gmrf_elliptic_p1_qpoints": [vp, vp],
+        "gmrf_elliptic_p1_tangent": [vp, vp, vp, vp],
+        "gmrf_elliptic_p1_tangent_batch": [vp, i64, vp, vp, vp],
+        "gmrf_elliptic_p1_load": [vp, i64, vp, vp],
         "gmrf_gn_destroy": [vp],
         "gmrf_gn_run": [vp, vp, i64, vp, vp, vp, vp, dbl, dbl, i32, vp, vp, P(i32)],
         "gmrf_gn_finalize": [vp, P(i32)],

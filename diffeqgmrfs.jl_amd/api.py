@@ -413,6 +413,82 @@ class BurgersP1Tangent:
         return vals, f
 
 
+class EllipticP1Tangent:
+    """Tangent, residual and load of the nonlinear elliptic benchmark -Lap u + u^3 = f_src on the device:
+    `f_and_J` of /root/reference/_research/elliptic_chen24.jl:280-285 with `assemble_J_cube` (:231-278) and the stiffness
+    rows and load of `assemble_J_diff_and_f` (:179-228), on the structured P1 triangle mesh of `DarcyP1Assembler` (nx x ny
+    nodes, x fastest, quads cut by the diagonal n00 - n11) with the symmetric 3-point rule.  The rows of the nodes on the four
+    sides stay zero, columns are kept.  `pattern` is the CSR matrix (values 1) whose `.data` order `tangent()` fills --
+    exactly `DarcyP1Assembler(nx, ny).pattern`, the `J` of `PosteriorAssembler`; `qpoints` (cells, 3, 2) are the quadrature
+    points at which the caller evaluates its source.  The residual does not contain the load: `load(src_q)` goes to
+    `GaussNewtonBatch.run` as `y`.  device = -1: pattern and quadrature points only (no GPU needed)."""
+
+    def __init__(self, nx: int, ny: int, device: int = 0, stream: int = 0):
+        self.nx, self.ny, self.n = int(nx), int(ny), int(nx) * int(ny)
+        self.rows = self.n
+        self.cells = 2 * (self.nx - 1) * (self.ny - 1)
+        self._h = C.c_void_p()
+        lib = _cabi.load()
+        _cabi.check(lib.gmrf_elliptic_p1_create(device, C.c_void_p(stream), nx, ny, C.byref(self._h)))
+        nnz = C.c_int64(0)
+        _cabi.check(lib.gmrf_elliptic_p1_pattern(self._h, C.byref(nnz), None, None, 0))
+        self.nnz = int(nnz.value)
+        rp, ci = np.empty(self.n + 1, dtype=np.int64), np.empty(self.nnz, dtype=np.int64)
+        _cabi.check(lib.gmrf_elliptic_p1_pattern(self._h, None, _cabi.ptr(rp), _cabi.ptr(ci), 0))
+        self.pattern = sp.csr_matrix((np.ones(self.nnz), ci, rp), shape=(self.n, self.n))
+        self.qpoints = np.empty((self.cells, 3, 2), dtype=np.float64)
+        _cabi.check(lib.gmrf_elliptic_p1_qpoints(self._h, _cabi.ptr(self.qpoints)))
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None) and self._h.value:
+                _cabi.load().gmrf_elliptic_p1_destroy(self._h)
+                self._h = C.c_void_p()
+        except Exception:
+            pass
+
+    @staticmethod
+    def _f64(a):
+        if _is_torch(a):
+            import torch
+            if a.dtype != torch.float64:
+                raise TypeError("float64 required")
+            return a.contiguous()
+        return np.ascontiguousarray(a, dtype=np.float64)
+
+    def tangent(self, w):
+        """w: (nx ny,) linearisation point (NumPy array or torch CUDA tensor).  Returns (J values in `pattern.data`
+        order, residual f(w) without the load), same kind as the input."""
+        wv = self._f64(w)
+        if wv.ndim != 1 or wv.shape[0] != self.n:
+            raise ValueError(f"w must have {self.n} entries")
+        vals, f = PosteriorAssembler._like2(wv, (self.nnz,)), PosteriorAssembler._like2(wv, (self.n,))
+        _cabi.check(_cabi.load().gmrf_elliptic_p1_tangent(self._h, _cabi.ptr(wv), _cabi.ptr(vals), _cabi.ptr(f)))
+        return vals, f
+
+    def tangent_batch(self, W):
+        """W: (B, nx ny) linearisation points -> (J values (B, nnz), residuals (B, n)), same kind as the input; row p is
+        `tangent(W[p])`, bit for bit."""
+        wv = self._f64(W)
+        if wv.ndim != 2 or wv.shape[1] != self.n:
+            raise ValueError(f"W must have shape (B, {self.n})")
+        B = wv.shape[0]
+        vals, f = PosteriorAssembler._like2(wv, (B, self.nnz)), PosteriorAssembler._like2(wv, (B, self.n))
+        _cabi.check(_cabi.load().gmrf_elliptic_p1_tangent_batch(self._h, B, _cabi.ptr(wv), _cabi.ptr(vals), _cabi.ptr(f)))
+        return vals, f
+
+    def load(self, src_q):
+        """src_q: (cells, 3) or (B, cells, 3) values of the source at `qpoints` -> b (n,) or (B, n), b[i] = int phi_i f_src, same
+        kind as the input; row p of a batch is `load(src_q[p])`, bit for bit."""
+        sv = self._f64(src_q)
+        if sv.ndim not in (2, 3) or tuple(sv.shape[-2:]) != (self.cells, 3):
+            raise ValueError(f"src_q must have shape ({self.cells}, 3) or (B, {self.cells}, 3)")
+        B = sv.shape[0] if sv.ndim == 3 else 1
+        b = PosteriorAssembler._like2(sv, (B, self.n) if sv.ndim == 3 else (self.n,))
+        _cabi.check(_cabi.load().gmrf_elliptic_p1_load(self._h, B, _cabi.ptr(sv), _cabi.ptr(b)))
+        return b
+
+
 class ShallowWaterP1:
     """Element kernels of the linear shallow-water SPDE on the device (third piece):
     `assemble_system!` of /root/reference/src/spdes/shallow_water.jl:17-122 (coupling K, element-lumped mass M, stiffness S
@@ -510,12 +586,23 @@ class GaussNewtonBatch:
 
     `F` (reference order, factored once on `asm.pattern`), `asm` and `tangent` must have been created on the same device with
     the same `stream` argument.  A problem is active while |last - cur| / |cur| > rtol and steps < max_steps; one that has
-    stopped is frozen and stays in the batch."""
+    stopped is frozen and stays in the batch.
 
-    def __init__(self, F: "TridiagonalCholeskyFactor", asm: PosteriorAssembler, tangent: BurgersP1Tangent):
+    With an `EllipticP1Tangent` the same loop is the Gauss-Newton loop of _research/elliptic_chen24.jl:142-166: pass the load
+    `tangent.load(src_q)` as `y` and noise = 3e13.  The stop rule stays the relative objective change (the reference's Newton
+    decrement lives in a package that is not available)."""
+
+    def __init__(self, F: "TridiagonalCholeskyFactor", asm: PosteriorAssembler, tangent: "BurgersP1Tangent | EllipticP1Tangent"):
         self.F, self.asm, self.tangent = F, asm, tangent          # (kept alive: the library holds their handles)
         self._h = C.c_void_p()
-        _cabi.check(_cabi.load().gmrf_gn_create(F._h, asm._h, tangent._h, C.byref(self._h)))
+        lib = _cabi.load()
+        if isinstance(tangent, EllipticP1Tangent):
+            create = lib.gmrf_gn_create_elliptic
+        elif isinstance(tangent, BurgersP1Tangent):
+            create = lib.gmrf_gn_create
+        else:
+            raise TypeError("tangent must be a BurgersP1Tangent or an EllipticP1Tangent")
+        _cabi.check(create(F._h, asm._h, tangent._h, C.byref(self._h)))
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:

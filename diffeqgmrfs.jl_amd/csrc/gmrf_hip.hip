@@ -39,6 +39,7 @@
 #include "sweep.hpp"
 #include "sweep_persist.hpp"
 #include "swe_assemble.hpp"
+#include "elliptic_assemble.hpp"
 #include "fem_assemble_p2.hpp"
 #include "selinv.hpp"
 #include "gauss_newton.hpp"
@@ -3898,26 +3899,31 @@ static void darcy_p2_pattern(gmrf_darcy_p1* d) {
         }
 }
 
-static gmrf_status darcy_create(int32_t device, void* stream, int64_t nx, int64_t ny, int order, gmrf_darcy_p1** out) {
-    if (!out || nx < 2 || ny < 2 || nx > 32768 || ny > 32768 || (order == 2 && (nx > 16384 || ny > 16384))) return bad_shape("bad Darcy mesh size");
-    std::unique_ptr<gmrf_darcy_p1, gmrf_status (*)(gmrf_darcy_p1*)> guard(new gmrf_darcy_p1(), gmrf_darcy_p1_destroy);
-    gmrf_darcy_p1* d = guard.get();
-    d->nx = nx; d->ny = ny; d->n = nx * ny; d->order = order;
-    if (order == 2) darcy_p2_pattern(d);
-    else {
-    d->rowptr.assign((size_t)d->n + 1, 0);
-    d->colidx.reserve((size_t)d->n * 7);
+// CSR pattern of the P1 triangle mesh (nx x ny nodes, x fastest, quads cut by the diagonal n00 - n11): the 7-point stencil
+// -nx-1, -nx, -1, 0, +1, +nx, +nx+1 clipped at the border, ascending columns (Darcy P1 and the elliptic tangent)
+static void p1_stencil_pattern(int64_t nx, int64_t ny, std::vector<int64_t>& rowptr, std::vector<int64_t>& colidx) {
+    rowptr.assign((size_t)(nx * ny) + 1, 0);
+    colidx.clear();
+    colidx.reserve((size_t)(nx * ny) * 7);
     const int dxs[7] = {-1, 0, -1, 0, 1, 0, 1}, dys[7] = {-1, -1, 0, 0, 0, 1, 1};
     for (int64_t iy = 0; iy < ny; ++iy)
         for (int64_t ix = 0; ix < nx; ++ix) {
             for (int s7 = 0; s7 < 7; ++s7) {
                 const int64_t jx = ix + dxs[s7], jy = iy + dys[s7];
                 if (jx < 0 || jy < 0 || jx >= nx || jy >= ny) continue;
-                d->colidx.push_back(jy * nx + jx);
+                colidx.push_back(jy * nx + jx);
             }
-            d->rowptr[(size_t)(iy * nx + ix) + 1] = (int64_t)d->colidx.size();
+            rowptr[(size_t)(iy * nx + ix) + 1] = (int64_t)colidx.size();
         }
-    }
+}
+
+static gmrf_status darcy_create(int32_t device, void* stream, int64_t nx, int64_t ny, int order, gmrf_darcy_p1** out) {
+    if (!out || nx < 2 || ny < 2 || nx > 32768 || ny > 32768 || (order == 2 && (nx > 16384 || ny > 16384))) return bad_shape("bad Darcy mesh size");
+    std::unique_ptr<gmrf_darcy_p1, gmrf_status (*)(gmrf_darcy_p1*)> guard(new gmrf_darcy_p1(), gmrf_darcy_p1_destroy);
+    gmrf_darcy_p1* d = guard.get();
+    d->nx = nx; d->ny = ny; d->n = nx * ny; d->order = order;
+    if (order == 2) darcy_p2_pattern(d);
+    else p1_stencil_pattern(nx, ny, d->rowptr, d->colidx);
     d->nnz = (int64_t)d->colidx.size();
     GCHK(d->open(device, stream, hipStreamNonBlocking, "gmrf_darcy_p1_create"));
     if (d->device >= 0) {
@@ -4128,6 +4134,132 @@ gmrf_status gmrf_burgers_p1_tangent_batch(gmrf_burgers_p1* b, int64_t batch, con
     return GMRF_OK;
 }
 
+// --------------------------------------------------------------------------------- nonlinear elliptic tangent
+struct gmrf_elliptic_p1 : DevCtx {      // device -1: pattern and quadrature points only
+    int64_t nx = 0, ny = 0, n = 0, nnz = 0, cells = 0;
+    std::vector<int64_t> rowptr, colidx;            // 0-based: the pattern of gmrf_darcy_p1_create(nx, ny)
+    int64_t* d_rowptr = nullptr;
+    DevBuf arena;                       // host arguments of the current call (Staging)
+};
+
+gmrf_status gmrf_elliptic_p1_create(int32_t device, void* stream, int64_t nx, int64_t ny, gmrf_elliptic_p1** out) {
+    if (!out || nx < 2 || ny < 2 || nx > 32768 || ny > 32768) return bad_shape("bad elliptic mesh size");
+    std::unique_ptr<gmrf_elliptic_p1, gmrf_status (*)(gmrf_elliptic_p1*)> guard(new gmrf_elliptic_p1(), gmrf_elliptic_p1_destroy);
+    gmrf_elliptic_p1* e = guard.get();
+    e->nx = nx; e->ny = ny; e->n = nx * ny; e->cells = 2 * (nx - 1) * (ny - 1);
+    p1_stencil_pattern(nx, ny, e->rowptr, e->colidx);
+    e->nnz = (int64_t)e->colidx.size();
+    GCHK(e->open(device, stream, hipStreamNonBlocking, "gmrf_elliptic_p1_create"));
+    if (e->device >= 0) {
+        HIPCHK(hipMalloc(&e->d_rowptr, sizeof(int64_t) * (e->n + 1)));
+        HIPCHK(hipMemcpyAsync(e->d_rowptr, e->rowptr.data(), sizeof(int64_t) * (e->n + 1), hipMemcpyHostToDevice, e->stream));
+        HIPCHK(hipStreamSynchronize(e->stream));
+    }
+    *out = guard.release();
+    return GMRF_OK;
+}
+
+gmrf_status gmrf_elliptic_p1_destroy(gmrf_elliptic_p1* e) {
+    if (!e) return GMRF_OK;
+    e->close();
+    if (e->has_device()) { free_dev(e->d_rowptr); e->arena.release(); }
+    delete e;
+    return GMRF_OK;
+}
+
+gmrf_status gmrf_elliptic_p1_pattern(const gmrf_elliptic_p1* e, int64_t* nnz_out, int64_t* rowptr, int64_t* colidx, int32_t index_base) {
+    if (!e) return bad_shape("null handle");
+    if (nnz_out) *nnz_out = e->nnz;
+    if (rowptr) for (int64_t i = 0; i <= e->n; ++i) rowptr[i] = e->rowptr[(size_t)i] + index_base;
+    if (colidx) for (int64_t k = 0; k < e->nnz; ++k) colidx[k] = e->colidx[(size_t)k] + index_base;
+    return GMRF_OK;
+}
+
+// spatial_coordinate(cellvalues, q_point, cell_coords) of every cell of the P1 triangle mesh under the symmetric 3-point rule:
+// xy[cell][q][2] (shallow water :52, elliptic :206)
+static void p1_triangle_qpoints(int64_t nx, int64_t ny, double* xy) {
+    const int64_t nlow = (nx - 1) * (ny - 1);
+    auto lin = [](int64_t i, int64_t n) { return (i == n - 1) ? 1.0 : (double)i * (1.0 / (double)(n - 1)); };
+    const double bary[3][3] = {{1.0 / 6, 1.0 / 6, 2.0 / 3}, {1.0 / 6, 2.0 / 3, 1.0 / 6}, {2.0 / 3, 1.0 / 6, 1.0 / 6}};
+    for (int up = 0; up < 2; ++up)
+        for (int64_t qy = 0; qy < ny - 1; ++qy)
+            for (int64_t qx = 0; qx < nx - 1; ++qx) {
+                const int64_t cell = up * nlow + qy * (nx - 1) + qx;
+                const int64_t nxs[3] = {qx, qx + 1, up ? qx : qx + 1}, nys[3] = {qy, up ? qy + 1 : qy, qy + 1};
+                for (int q = 0; q < 3; ++q) {
+                    xy[(cell * 3 + q) * 2 + 0] = (bary[q][0] * lin(nxs[0], nx) + bary[q][1] * lin(nxs[1], nx)) + bary[q][2] * lin(nxs[2], nx);
+                    xy[(cell * 3 + q) * 2 + 1] = (bary[q][0] * lin(nys[0], ny) + bary[q][1] * lin(nys[1], ny)) + bary[q][2] * lin(nys[2], ny);
+                }
+            }
+}
+
+gmrf_status gmrf_elliptic_p1_qpoints(const gmrf_elliptic_p1* e, double* xy) {
+    if (!e || !xy) return bad_shape("null pointer");
+    if (is_device_ptr(xy)) return bad_shape("quadrature points are written to host memory");
+    p1_triangle_qpoints(e->nx, e->ny, xy);
+    return GMRF_OK;
+}
+
+static gmrf_status launch_elliptic_batch(const gmrf_elliptic_p1* e, hipStream_t st, int64_t batch, const double* d_w, double* d_vals,
+                                         double* d_f) {
+    EllipticP1Args a;
+    a.nx = (int)e->nx; a.ny = (int)e->ny; a.rowptr = e->d_rowptr; a.w = d_w; a.vals = d_vals; a.f = d_f;
+    const dim3 grid((unsigned)((e->n + 255) / 256), (unsigned)batch);
+    hipLaunchKernelGGL(elliptic_p1_rows_batch, grid, dim3(256), 0, st, a, e->nnz);
+    HIPCHK(hipGetLastError());
+    return GMRF_OK;
+}
+
+gmrf_status gmrf_elliptic_p1_tangent(gmrf_elliptic_p1* e, const double* w, double* vals_out, double* f_out) {
+    if (!e || !w || !vals_out || !f_out) return bad_shape("bad elliptic tangent arguments");
+    GCHK(e->ready("pattern-only elliptic tangent"));
+    EllipticP1Args a;
+    a.nx = (int)e->nx; a.ny = (int)e->ny; a.rowptr = e->d_rowptr;
+    Staging args(e->arena);
+    args.in(w, sizeof(double) * e->n, &a.w);
+    args.out(vals_out, sizeof(double) * e->nnz, &a.vals);
+    args.out(f_out, sizeof(double) * e->n, &a.f);
+    GCHK(args.commit(e->stream));
+    hipLaunchKernelGGL(elliptic_p1_rows, dim3((unsigned)((e->n + 255) / 256)), dim3(256), 0, e->stream, a);
+    HIPCHK(hipGetLastError());
+    GCHK(args.flush(e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return GMRF_OK;
+}
+
+gmrf_status gmrf_elliptic_p1_tangent_batch(gmrf_elliptic_p1* e, int64_t batch, const double* w, double* vals_out, double* f_out) {
+    if (!e || !w || !vals_out || !f_out || !batch_ok(batch)) return bad_shape("bad elliptic tangent arguments (batch in [1, 4096])");
+    GCHK(e->ready("pattern-only elliptic tangent"));
+    const double* d_w;
+    double *d_vals, *d_f;
+    Staging args(e->arena);
+    args.in(w, sizeof(double) * batch * e->n, &d_w);
+    args.out(vals_out, sizeof(double) * batch * e->nnz, &d_vals);
+    args.out(f_out, sizeof(double) * batch * e->n, &d_f);
+    GCHK(args.commit(e->stream));
+    GCHK(launch_elliptic_batch(e, e->stream, batch, d_w, d_vals, d_f));
+    GCHK(args.flush(e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return GMRF_OK;
+}
+
+// src_q [batch][cells][3] -> b_out [batch][n]
+gmrf_status gmrf_elliptic_p1_load(gmrf_elliptic_p1* e, int64_t batch, const double* src_q, double* b_out) {
+    if (!e || !src_q || !b_out || !batch_ok(batch)) return bad_shape("bad elliptic load arguments (batch in [1, 4096])");
+    GCHK(e->ready("pattern-only elliptic tangent"));
+    EllipticLoadArgs a;
+    a.nx = (int)e->nx; a.ny = (int)e->ny;
+    Staging args(e->arena);
+    args.in(src_q, sizeof(double) * batch * e->cells * 3, &a.src);
+    args.out(b_out, sizeof(double) * batch * e->n, &a.b);
+    GCHK(args.commit(e->stream));
+    hipLaunchKernelGGL(elliptic_p1_load_batch, dim3((unsigned)((e->n + 255) / 256), (unsigned)batch), dim3(256), 0, e->stream, a);
+    HIPCHK(hipGetLastError());
+    GCHK(args.flush(e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return GMRF_OK;
+}
+
 // Darcy element kernels for a batch of coefficient tables (problem-major); d_work: [batch][n] |diagonal| then [batch] means
 static int64_t darcy_batch_work_elems(const gmrf_darcy_p1* d, int64_t batch) { return batch * d->n + batch; }
 static bool darcy_ng_ok(int64_t ng) { return ng >= 2 && ng <= 46340; }
@@ -4300,7 +4432,8 @@ gmrf_status gmrf_assemble_objective_batch(gmrf_assembler* as, int64_t batch, con
 struct gmrf_gn {
     gmrf_handle* h = nullptr;
     gmrf_assembler* as = nullptr;
-    gmrf_burgers_p1* b = nullptr;
+    gmrf_burgers_p1* b = nullptr;        // the bound tangent: Burgers (gmrf_gn_create) ...
+    gmrf_elliptic_p1* e = nullptr;       // ... or nonlinear elliptic (gmrf_gn_create_elliptic); exactly one is set
     int64_t B = 0;                       // what the buffers below are sized for
     int32_t hist_steps = -1;
     double *d_x = nullptr, *d_xn = nullptr, *d_od = nullptr, *d_on = nullptr, *d_f = nullptr, *d_v = nullptr, *d_jv = nullptr;
@@ -4327,20 +4460,31 @@ static void gn_free(gmrf_gn* g) {
     g->B = 0; g->hist_steps = -1; g->have_x = false;
 }
 
+// The one place that knows which tangent is bound: its device, stream and the shape of its J, and its batch launch.
+struct GnTangent { int device; hipStream_t stream; int64_t n, m, nnz; };
+static GnTangent gn_tangent(const gmrf_gn* g) {
+    if (g->e) return {g->e->device, g->e->stream, g->e->n, g->e->n, g->e->nnz};
+    return {g->b->device, g->b->stream, g->b->ns * g->b->nt, g->b->rows, g->b->nnz};
+}
+static gmrf_status gn_launch_tangent(const gmrf_gn* g, hipStream_t st, int64_t batch, const double* d_w, double* d_vals, double* d_f) {
+    return g->e ? launch_elliptic_batch(g->e, st, batch, d_w, d_vals, d_f) : launch_tangent_batch(g->b, st, batch, d_w, d_vals, d_f);
+}
+
 static gmrf_status gn_bound_ok(const gmrf_gn* g) {
     const gmrf_handle* h = g->h;
+    const GnTangent t = gn_tangent(g);
     if (h->order == GMRF_ORDER_TWISTED) return bad_shape("the Gauss-Newton driver takes a reference-order handle");
-    if (g->as->device != h->device || g->b->device != h->device) return bad_shape("handle, assembler and tangent must live on one device");
-    if (g->as->stream != h->stream || g->b->stream != h->stream) return bad_shape("handle, assembler and tangent must share one stream");
-    if (g->as->n != g->b->ns * g->b->nt || g->as->m != g->b->rows || g->as->nnz_j != g->b->nnz)
+    if (g->as->device != h->device || t.device != h->device) return bad_shape("handle, assembler and tangent must live on one device");
+    if (g->as->stream != h->stream || t.stream != h->stream) return bad_shape("handle, assembler and tangent must share one stream");
+    if (g->as->n != t.n || g->as->m != t.m || g->as->nnz_j != t.nnz)
         return bad_shape("the assembler's J is not the tangent's pattern");
     return GMRF_OK;
 }
 
-gmrf_status gmrf_gn_create(gmrf_handle* h, gmrf_assembler* as, gmrf_burgers_p1* b, gmrf_gn** out) {
-    if (!h || !as || !b || !out) return bad_shape("null pointer");
-    if (as->device < 0 || b->device < 0) return bad_shape("the Gauss-Newton driver needs an assembler and a tangent with a device");
-    gmrf_gn tmp; tmp.h = h; tmp.as = as; tmp.b = b; tmp.device = h->device; tmp.stream = h->stream;
+static gmrf_status gn_create(gmrf_handle* h, gmrf_assembler* as, gmrf_burgers_p1* b, gmrf_elliptic_p1* el, gmrf_gn** out) {
+    if (!h || !as || (!b && !el) || !out) return bad_shape("null pointer");
+    if (as->device < 0 || (b ? b->device : el->device) < 0) return bad_shape("the Gauss-Newton driver needs an assembler and a tangent with a device");
+    gmrf_gn tmp; tmp.h = h; tmp.as = as; tmp.b = b; tmp.e = el; tmp.device = h->device; tmp.stream = h->stream;
     GCHK(gn_bound_ok(&tmp));
     HIPCHK(hipSetDevice(h->device));
     auto* g = new gmrf_gn(tmp);
@@ -4353,6 +4497,13 @@ gmrf_status gmrf_gn_create(gmrf_handle* h, gmrf_assembler* as, gmrf_burgers_p1* 
     g->dev_active = static_cast<unsigned*>(dev_word);
     *out = g;
     return GMRF_OK;
+}
+
+gmrf_status gmrf_gn_create(gmrf_handle* h, gmrf_assembler* as, gmrf_burgers_p1* b, gmrf_gn** out) {
+    return gn_create(h, as, b, nullptr, out);
+}
+gmrf_status gmrf_gn_create_elliptic(gmrf_handle* h, gmrf_assembler* as, gmrf_elliptic_p1* e, gmrf_gn** out) {
+    return gn_create(h, as, nullptr, e, out);
 }
 
 gmrf_status gmrf_gn_destroy(gmrf_gn* g) {
@@ -4454,7 +4605,7 @@ gmrf_status gmrf_gn_run(gmrf_gn* g, const double* q_nzval, int64_t q_stride, con
     HIPCHK(hipMemsetAsync(g->d_hist, 0xFF, sizeof(double) * B * ((size_t)max_steps + 1), st));
     const dim3 grid_m((unsigned)((m + 255) / 256), (unsigned)B), grid_w((unsigned)((wide + 255) / 256), (unsigned)B);
     // the start: obs_diff = y - f(x), objective, every problem active (the first `last` is +Inf)
-    GCHK(launch_tangent_batch(g->b, st, B, g->d_x, g->d_jv, g->d_f));
+    GCHK(gn_launch_tangent(g, st, B, g->d_x, g->d_jv, g->d_f));
     hipLaunchKernelGGL(gn_obs_diff, grid_m, dim3(256), 0, st, d_y, g->d_f, m, g->d_od);
     GCHK(launch_objective_batch(as, st, B, g->d_q, q_stride, d_xp, g->d_x, g->d_od, noise, g->d_part, g->d_obj));
     hipLaunchKernelGGL(gn_decide, dim3(1), dim3(256), 0, st, s, g->d_obj, B, rtol, max_steps, 1);
@@ -4466,13 +4617,13 @@ gmrf_status gmrf_gn_run(gmrf_gn* g, const double* q_nzval, int64_t q_stride, con
     gmrf_status status = GMRF_OK;
     g->iterations = g->fwd_iterations = 0;
     auto iteration = [&]() -> gmrf_status {
-        GCHK(launch_tangent_batch(g->b, st, B, g->d_x, g->d_jv, g->d_f));
+        GCHK(gn_launch_tangent(g, st, B, g->d_x, g->d_jv, g->d_f));
         GCHK(launch_precision_batch(as, st, B, g->d_q, q_stride, g->d_jv, noise, g->d_a));
         GCHK(launch_rhs_batch(as, st, B, d_qxp, g->d_jv, g->d_x, g->d_od, noise, g->d_v, g->d_rhs));
         GCHK(numeric_factor(h, g->d_a, info));
         GCHK(gn_solve(g));
         // the candidate's residual and objective; J's values are not needed any more this iteration and are overwritten
-        GCHK(launch_tangent_batch(g->b, st, B, g->d_xn, g->d_jv, g->d_f));
+        GCHK(gn_launch_tangent(g, st, B, g->d_xn, g->d_jv, g->d_f));
         hipLaunchKernelGGL(gn_obs_diff, grid_m, dim3(256), 0, st, d_y, g->d_f, m, g->d_on);
         GCHK(launch_objective_batch(as, st, B, g->d_q, q_stride, d_xp, g->d_xn, g->d_on, noise, g->d_part, g->d_obj));
         hipLaunchKernelGGL(gn_decide, dim3(1), dim3(256), 0, st, s, g->d_obj, B, rtol, max_steps, 0);
@@ -4502,7 +4653,7 @@ gmrf_status gmrf_gn_finalize(gmrf_gn* g, int32_t* info) {
     GCHK(gn_bound_ok(g));
     gmrf_handle* h = g->h;
     HIPCHK(hipSetDevice(h->device));
-    GCHK(launch_tangent_batch(g->b, h->stream, g->B, g->d_x, g->d_jv, g->d_f));
+    GCHK(gn_launch_tangent(g, h->stream, g->B, g->d_x, g->d_jv, g->d_f));
     GCHK(launch_precision_batch(g->as, h->stream, g->B, g->d_q, g->q_stride, g->d_jv, g->noise, g->d_a));
     return numeric_factor(h, g->d_a, info);
 }
@@ -4752,19 +4903,7 @@ gmrf_status gmrf_shallow_water_p1_pattern(const gmrf_swe_p1* w, int32_t which, i
 gmrf_status gmrf_shallow_water_p1_qpoints(const gmrf_swe_p1* w, double* xy) {
     if (!w || !xy) return bad_shape("null pointer");
     if (is_device_ptr(xy)) return bad_shape("quadrature points are written to host memory");
-    const int64_t nx = w->nx, ny = w->ny, nlow = (nx - 1) * (ny - 1);
-    auto lin = [](int64_t i, int64_t n) { return (i == n - 1) ? 1.0 : (double)i * (1.0 / (double)(n - 1)); };
-    const double bary[3][3] = {{1.0 / 6, 1.0 / 6, 2.0 / 3}, {1.0 / 6, 2.0 / 3, 1.0 / 6}, {2.0 / 3, 1.0 / 6, 1.0 / 6}};
-    for (int up = 0; up < 2; ++up)
-        for (int64_t qy = 0; qy < ny - 1; ++qy)
-            for (int64_t qx = 0; qx < nx - 1; ++qx) {
-                const int64_t cell = up * nlow + qy * (nx - 1) + qx;
-                const int64_t nxs[3] = {qx, qx + 1, up ? qx : qx + 1}, nys[3] = {qy, up ? qy + 1 : qy, qy + 1};
-                for (int q = 0; q < 3; ++q) {
-                    xy[(cell * 3 + q) * 2 + 0] = (bary[q][0] * lin(nxs[0], nx) + bary[q][1] * lin(nxs[1], nx)) + bary[q][2] * lin(nxs[2], nx);
-                    xy[(cell * 3 + q) * 2 + 1] = (bary[q][0] * lin(nys[0], ny) + bary[q][1] * lin(nys[1], ny)) + bary[q][2] * lin(nys[2], ny);
-                }
-            }
+    p1_triangle_qpoints(w->nx, w->ny, xy);
     return GMRF_OK;
 }
 

@@ -222,6 +222,81 @@ def elliptic(n_xy: int, rows_per_block: int = 2, bnd_noise: float = 1e12,
                     {"kappa": kappa, "rows_per_block": rows_per_block, "nnz": int(Q.nnz)})
 
 
+def p1_triangle_qpoints(nx: int, ny: int) -> np.ndarray:
+    """(cells, 3, 2) quadrature points of the symmetric 3-point rule on the cells of `_grid_triangles` (all lower triangles,
+    then all upper): point q has the barycentric weight 2/3 on cell vertex 2 - q and 1/6 on the other two -- what
+    `EllipticP1Tangent.qpoints` and `ShallowWaterP1.qpoints` report."""
+    tri = _grid_triangles(nx, ny)
+    X = np.linspace(0.0, 1.0, nx)[tri % nx]
+    Y = np.linspace(0.0, 1.0, ny)[tri // nx]
+    bary = np.array([[1 / 6, 1 / 6, 2 / 3], [1 / 6, 2 / 3, 1 / 6], [2 / 3, 1 / 6, 1 / 6]])
+    xq = (bary[None, :, 0] * X[:, None, 0] + bary[None, :, 1] * X[:, None, 1]) + bary[None, :, 2] * X[:, None, 2]
+    yq = (bary[None, :, 0] * Y[:, None, 0] + bary[None, :, 1] * Y[:, None, 1]) + bary[None, :, 2] * Y[:, None, 2]
+    return np.stack([xq, yq], axis=2)
+
+
+def elliptic_truth(x, y, amp: float):
+    """u = sin(pi x) sin(pi y) + amp sin(2 pi x) sin(2 pi y), which vanishes on the boundary of the unit square, and its
+    source f_src = -Lap u + u^3.  Returns (u, f_src) at the points (x, y)."""
+    s1 = np.sin(np.pi * x) * np.sin(np.pi * y)
+    s2 = np.sin(2 * np.pi * x) * np.sin(2 * np.pi * y)
+    u = s1 + amp * s2
+    return u, 2 * np.pi ** 2 * s1 + amp * 8 * np.pi ** 2 * s2 + u ** 3
+
+
+def elliptic_gauss_newton_batch(n_xy, B: int, rows_per_block: int = 2, bnd_noise: float = 1e12, fem_noise: float = 3e13,
+                                amps=None):
+    """The ingredients of the reference's Gauss-Newton loop for -Lap u + u^3 = f (`gmrf_fem_solve`,
+    _research/elliptic_chen24.jl:118-161) for B problems on one P1 mesh; n_xy: nodes per side, or (nx, ny).  Problem p has the
+    true solution `elliptic_truth(., ., amps[p])` (default amps[p] = p / 2).  Returns a dict with
+      Q          the prior with the boundary conditioned in, Q_matern(alpha = 2, range 0.1) + bnd_noise A_b' A_b (CSC; :125-131),
+      q_values   its values (shared by every problem),
+      x_prior, Qx_prior, x0   (B, n): the conditioned mean (zero: u vanishes on the boundary), Q x_prior, the start point (:148-154),
+      qpoints (cells, 3, 2), src_q (B, cells, 3) the sources at the quadrature points, truth (B, n) the nodal true solutions,
+      amps, noise, n_blocks, n, m, nx, ny."""
+    nx, ny = (int(n_xy), int(n_xy)) if np.ndim(n_xy) == 0 else (int(n_xy[0]), int(n_xy[1]))
+    assert ny % rows_per_block == 0
+    lumped, G, _, (X, Y) = p1_unit_square(nx, ny)
+    kappa = math.sqrt(8.0 * 1.0) / 0.1
+    Q0 = matern_precision_2d(lumped, G, kappa, alpha=2)
+    on_bnd = (X == 0.0) | (X == 1.0) | (Y == 0.0) | (Y == 1.0)
+    Ab = sp.diags(on_bnd.astype(np.float64)).tocsr()
+    Q = (Q0 + bnd_noise * (Ab.T @ Ab)).tocsc()
+    Q = ((Q + Q.T) * 0.5).tocsc()
+    Q.sort_indices()
+    amps = 0.5 * np.arange(B) if amps is None else np.asarray(amps, dtype=np.float64)
+    if amps.shape != (B,):
+        raise ValueError(f"amps: expected {B} amplitudes")
+    qp = p1_triangle_qpoints(nx, ny)
+    n = nx * ny
+    truth, src_q = np.empty((B, n)), np.empty((B,) + qp.shape[:2])
+    for p in range(B):
+        truth[p], _ = elliptic_truth(X, Y, amps[p])
+        _, src_q[p] = elliptic_truth(qp[:, :, 0], qp[:, :, 1], amps[p])
+    x_prior = np.zeros((B, n))
+    return {"Q": Q, "q_values": Q.data.copy(), "x_prior": x_prior, "Qx_prior": np.zeros((B, n)), "x0": x_prior.copy(),
+            "qpoints": qp, "src_q": src_q, "truth": truth, "amps": amps, "noise": fem_noise, "n_blocks": ny // rows_per_block,
+            "n": n, "m": n, "nx": nx, "ny": ny}
+
+
+def elliptic_gauss_newton(n_xy, rows_per_block: int = 2, bnd_noise: float = 1e12, fem_noise: float = 3e13, amp: float = 1.0):
+    """One problem of `elliptic_gauss_newton_batch` (its arrays without the batch axis)."""
+    w = elliptic_gauss_newton_batch(n_xy, 1, rows_per_block, bnd_noise, fem_noise, amps=[amp])
+    for k in ("x_prior", "Qx_prior", "x0", "src_q", "truth"):
+        w[k] = w[k][0]
+    w["amp"] = float(amp)
+    del w["amps"]
+    return w
+
+
+def solution_errors(pred, soln) -> dict:
+    """rmse / max_err / rel_err of an iterate against the nodal truth (/root/reference/src/metrics.jl:3-13), on the host."""
+    pred, soln = np.asarray(pred, dtype=np.float64), np.asarray(soln, dtype=np.float64)
+    d = pred - soln
+    return {"rmse": float(np.sqrt(np.mean(d ** 2))), "max_err": float(np.max(np.abs(d))),
+            "rel_err": float(np.linalg.norm(d) / np.linalg.norm(soln))}
+
+
 # --------------------------------------------------------------------------- 1-D space-time
 
 def p1_periodic_line(ns: int):

@@ -558,6 +558,36 @@ gmrf_status gmrf_gn_run(gmrf_gn* g, const double* q_nzval, int64_t q_stride, con
                         double* obj_hist_out, int32_t* info);
 gmrf_status gmrf_gn_finalize(gmrf_gn* g, int32_t* info);
 
+/* Tangent, residual and load of the nonlinear elliptic benchmark -Lap u + u^3 = f_src (FEM block assembly, fourth piece;
+ * /root/reference/_research/elliptic_chen24.jl) as its Gauss-Newton loop evaluates them per iteration (f_and_J, :280-285):
+ *     J(w) = J_static + J_cube(w),  J_static[i][j] = int grad(phi_i).grad(phi_j)   (assemble_J_diff_and_f, :179-228)
+ *                                   J_cube[i][j]   = int 3 phi_i u_h^2 phi_j       (assemble_J_cube, :231-278)
+ *     f(w) = J_static w + int phi_i u_h^3          b[i] = int phi_i f_src          (the load `fe` of :222)
+ * on the structured P1 triangle mesh of the Darcy configs (nx x ny nodes, x fastest, quads cut by the diagonal n00 - n11; cell
+ * numbering: all lower triangles, then all upper, as in the shallow-water handle) with the symmetric 3-point rule of order 2
+ * (QuadratureRule{RefTriangle}(element_order + 1) of :122 for P1).  Prescribed dofs are the nodes on the four sides: their ROWS
+ * are skipped and stay zero, columns are kept, no apply! is done (:210-212, :262-264).  f does not contain the load: b goes to
+ * gmrf_gn_run as the observations y, obs_diff = y - f(x), which is the reference's J_static w + f_cube - f_static against zero
+ * observations; the handle is stateless like the Burgers one.  The pattern is exactly gmrf_darcy_p1_pattern's for the same
+ * nx, ny (explicit zeros included); the values come out in its CSR order, n = m = nx ny.  src_q [batch][cells][3]: the source at
+ * the points of _qpoints (xy [cells][3][2] doubles in host memory).  w, vals_out, f_out, src_q, b_out: host or device pointers,
+ * batch arrays problem-major with batch in [1, 4096]; problem p of a batch call gets the bits of the one-problem call on its
+ * slice.  device -1: pattern and quadrature points only. */
+typedef struct gmrf_elliptic_p1 gmrf_elliptic_p1;
+gmrf_status gmrf_elliptic_p1_create(int32_t device, void* stream, int64_t nx, int64_t ny, gmrf_elliptic_p1** out);
+gmrf_status gmrf_elliptic_p1_destroy(gmrf_elliptic_p1* e);
+gmrf_status gmrf_elliptic_p1_pattern(const gmrf_elliptic_p1* e, int64_t* nnz_out, int64_t* rowptr, int64_t* colidx,
+                                     int32_t index_base);
+gmrf_status gmrf_elliptic_p1_qpoints(const gmrf_elliptic_p1* e, double* xy);
+gmrf_status gmrf_elliptic_p1_tangent(gmrf_elliptic_p1* e, const double* w, double* vals_out, double* f_out);
+gmrf_status gmrf_elliptic_p1_tangent_batch(gmrf_elliptic_p1* e, int64_t batch, const double* w, double* vals_out, double* f_out);
+gmrf_status gmrf_elliptic_p1_load(gmrf_elliptic_p1* e, int64_t batch, const double* src_q, double* b_out);
+/* The Gauss-Newton driver bound to the elliptic tangent (the loop of gmrf_fem_solve, :142-166): the same gmrf_gn type and the
+ * same binding rules (one device, one stream, as->n == as->m == nx ny, as->nnz_j == the pattern's nnz; anything else is
+ * GMRF_ERR_BAD_SHAPE); gmrf_gn_run / _finalize / _destroy serve both tangents.  The stop rule is the driver's relative
+ * objective change, not the Newton decrement of :156-159. */
+gmrf_status gmrf_gn_create_elliptic(gmrf_handle* h, gmrf_assembler* as, gmrf_elliptic_p1* e, gmrf_gn** out);
+
 /* The Darcy data-set loop (scripts/darcy/solve_darcy_gmrf-fem.jl:176-198 per problem) for a batch of problems on one mesh.
  * gmrf_darcy_p1_assemble_batch: coeff_tables [batch][ng][ng] -> vals_out [batch][nnz], f_out [batch][n]; problem p gets the bits
  * of gmrf_darcy_p1_assemble on its table (both element orders); host or device pointers; batch in [1, 4096]. */

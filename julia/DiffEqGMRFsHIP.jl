@@ -30,7 +30,7 @@ module DiffEqGMRFsHIP
 using SparseArrays, LinearAlgebra
 
 export TridiagonalCholeskyFactor, tridiagonal_cholesky, forward_solve, backward_solve, ldiv, PosteriorAssembler, GmrfCsr,
-       GmrfComm, DarcyP1Assembler, BurgersP1Tangent, GaussNewtonBatch, gauss_newton_batch!, DarcyConditioningBatch,
+       GmrfComm, DarcyP1Assembler, BurgersP1Tangent, EllipticP1Tangent, elliptic_load!, GaussNewtonBatch, gauss_newton_batch!, DarcyConditioningBatch,
        condition_on_observations_batch, assemble_batch!
 
 const libgmrf = get(ENV, "LIBGMRF_HIP", joinpath(@__DIR__, "..", "diffeqgmrfs.jl_amd", "csrc", "libgmrf_hip.so"))
@@ -590,6 +590,51 @@ function tangent_batch!(vals::Matrix{Float64}, f::Matrix{Float64}, b::BurgersP1T
     return vals, f
 end
 
+# Tangent, residual and load of the nonlinear elliptic benchmark -Lap u + u^3 = f (f_and_J, _research/elliptic_chen24.jl:280-285,
+# with assemble_J_cube :231-278 and assemble_J_diff_and_f :179-228) on the structured P1 triangle mesh of DarcyP1Assembler
+mutable struct EllipticP1Tangent
+    handle::Ptr{Cvoid}
+    pattern::SparseMatrixCSC{Float64,Int}     # TRANSPOSE of J's pattern (CSC of J' = CSR of J), values 1.0: DarcyP1Assembler's
+    rows::Int
+    qpoints::Array{Float64,3}                 # (2, 3, cells): x / y of quadrature point q of a cell -- evaluate the source there
+end
+
+function EllipticP1Tangent(nx::Integer, ny::Integer; device::Integer = 0, stream::Ptr{Cvoid} = C_NULL)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:gmrf_elliptic_p1_create, libgmrf), Int32, (Int32, Ptr{Cvoid}, Int64, Int64, Ref{Ptr{Cvoid}}), device, stream, nx, ny, h))
+    nnz_out = Ref{Int64}(0)
+    check(ccall((:gmrf_elliptic_p1_pattern, libgmrf), Int32, (Ptr{Cvoid}, Ref{Int64}, Ptr{Int64}, Ptr{Int64}, Int32), h[], nnz_out, C_NULL, C_NULL, 1))
+    n = nx * ny
+    rowptr = Vector{Int64}(undef, n + 1); colidx = Vector{Int64}(undef, nnz_out[])
+    check(ccall((:gmrf_elliptic_p1_pattern, libgmrf), Int32, (Ptr{Cvoid}, Ref{Int64}, Ptr{Int64}, Ptr{Int64}, Int32), h[], nnz_out, rowptr, colidx, 1))
+    qp = Array{Float64,3}(undef, 2, 3, 2 * (nx - 1) * (ny - 1))
+    check(ccall((:gmrf_elliptic_p1_qpoints, libgmrf), Int32, (Ptr{Cvoid}, Ptr{Float64}), h[], qp))
+    e = EllipticP1Tangent(h[], SparseMatrixCSC(n, n, rowptr, colidx, ones(nnz_out[])), n, qp)
+    finalizer(x -> ccall((:gmrf_elliptic_p1_destroy, libgmrf), Int32, (Ptr{Cvoid},), x.handle), e)
+    return e
+end
+
+"`(J values in CSR order, f) = f_and_J(w)` without the load: pass `elliptic_load!` as `y` of `gauss_newton_batch!`."
+function tangent!(vals::Vector{Float64}, f::Vector{Float64}, e::EllipticP1Tangent, w::Vector{Float64})
+    GC.@preserve w vals f check(ccall((:gmrf_elliptic_p1_tangent, libgmrf), Int32,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), e.handle, w, vals, f))
+    return vals, f
+end
+
+"`tangent!` for every column of `w` (n x batch)"
+function tangent_batch!(vals::Matrix{Float64}, f::Matrix{Float64}, e::EllipticP1Tangent, w::Matrix{Float64})
+    GC.@preserve w vals f check(ccall((:gmrf_elliptic_p1_tangent_batch, libgmrf), Int32,
+        (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), e.handle, size(w, 2), w, vals, f))
+    return vals, f
+end
+
+"`b[i, p] = int phi_i f_src_p`: src_q[q, cell, p] = f_src_p(qpoints[:, q, cell]); b is n x batch."
+function elliptic_load!(b::Matrix{Float64}, e::EllipticP1Tangent, src_q::Array{Float64,3})
+    GC.@preserve src_q b check(ccall((:gmrf_elliptic_p1_load, libgmrf), Int32,
+        (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}), e.handle, size(src_q, 3), src_q, b))
+    return b
+end
+
 # The Burgers data-set loop (scripts/burgers/solve_burgers_gmrf-fem.jl:154-233, loop body scripts/solve_burger.jl:143-180) for a
 # batch of problems in lock step on the device.  `F` (batch = number of problems, factored once on `as.pattern`), `as` and `b`
 # must have been created on one device and one stream.
@@ -597,13 +642,23 @@ mutable struct GaussNewtonBatch
     handle::Ptr{Cvoid}
     F::TridiagonalCholeskyFactor
     as::PosteriorAssembler
-    b::BurgersP1Tangent
+    b::Union{BurgersP1Tangent,EllipticP1Tangent}
 end
 
 function GaussNewtonBatch(F::TridiagonalCholeskyFactor, as::PosteriorAssembler, b::BurgersP1Tangent)
     h = Ref{Ptr{Cvoid}}(C_NULL)
     check(ccall((:gmrf_gn_create, libgmrf), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{Ptr{Cvoid}}), F.handle, as.handle, b.handle, h))
     gn = GaussNewtonBatch(h[], F, as, b)
+    finalizer(g -> ccall((:gmrf_gn_destroy, libgmrf), Int32, (Ptr{Cvoid},), g.handle), gn)
+    return gn
+end
+
+# The same driver on the elliptic tangent: the Gauss-Newton loop of gmrf_fem_solve (_research/elliptic_chen24.jl:142-166) with
+# y = elliptic_load!(...) and noise = 3e13; the stop rule stays the relative objective change.
+function GaussNewtonBatch(F::TridiagonalCholeskyFactor, as::PosteriorAssembler, e::EllipticP1Tangent)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:gmrf_gn_create_elliptic, libgmrf), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{Ptr{Cvoid}}), F.handle, as.handle, e.handle, h))
+    gn = GaussNewtonBatch(h[], F, as, e)
     finalizer(g -> ccall((:gmrf_gn_destroy, libgmrf), Int32, (Ptr{Cvoid},), g.handle), gn)
     return gn
 end

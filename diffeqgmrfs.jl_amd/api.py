@@ -413,6 +413,61 @@ class BurgersP1Tangent:
         return vals, f
 
 
+class BurgersP1Prior:
+    """Prior of the Burgers space-time GMRF with the initial condition conditioned in, for a batch of problems on the device: the
+    "Prior" stage (`form_prior`, /root/reference/scripts/burgers/solve_burgers_gmrf-fem.jl:86-107) and the information vector of
+    the "Initial condition" stage (:161) of the data-set loop, as `workloads.burgers(ns, nt, ic_noise, 0.0, ic)` states them
+    (`workloads.burgers_prior_from_bulk`).  Every problem has its own values through bulk = mean(ic), on ONE structural pattern:
+    `pattern` is the CSC matrix (values 1; symmetric, nt blocks of ns, offsets 0, +-1, +-2 in the diagonal blocks and 0, +-1 beside
+    them) whose `.data` order `values_batch` fills.  An entry whose value is 0.0 is stored, SciPy prunes such entries: compare
+    matrices, not `.data` arrays.  P1 only: the reference's order-2 line has no restatement of the prior in `workloads` to build
+    against.  device = -1: pattern only (no GPU needed)."""
+
+    def __init__(self, ns: int, nt: int, dt: float, nu: float, ic_noise: float = 1e8, device: int = 0, stream: int = 0):
+        self.ns, self.nt, self.dt, self.nu, self.ic_noise = int(ns), int(nt), float(dt), float(nu), float(ic_noise)
+        self.n = self.ns * self.nt
+        self._h = C.c_void_p()
+        lib = _cabi.load()
+        _cabi.check(lib.gmrf_burgers_prior_create(device, C.c_void_p(stream), ns, nt, float(dt), float(nu), float(ic_noise), C.byref(self._h)))
+        nnz = C.c_int64(0)
+        _cabi.check(lib.gmrf_burgers_prior_pattern(self._h, C.byref(nnz), None, None, 0))
+        self.nnz = int(nnz.value)
+        cp, rv = np.empty(self.n + 1, dtype=np.int64), np.empty(self.nnz, dtype=np.int64)
+        _cabi.check(lib.gmrf_burgers_prior_pattern(self._h, None, _cabi.ptr(cp), _cabi.ptr(rv), 0))
+        self.pattern = sp.csc_matrix((np.ones(self.nnz), rv, cp), shape=(self.n, self.n))
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None) and self._h.value:
+                _cabi.load().gmrf_burgers_prior_destroy(self._h)
+                self._h = C.c_void_p()
+        except Exception:
+            pass
+
+    def _ics(self, ics):
+        if _is_torch(ics):
+            import torch
+            v = ics.contiguous()
+            if v.dtype != torch.float64:
+                raise TypeError("float64 required")
+        else:
+            v = np.ascontiguousarray(ics, dtype=np.float64)
+        if v.ndim != 2 or v.shape[1] != self.ns:
+            raise ValueError(f"ics must have shape (B, {self.ns})")
+        return v
+
+    def values_batch(self, ics):
+        """ics (B, ns) initial conditions -> {"bulk": (B,), "q_values": (B, nnz), "Qx_prior": (B, n)}, same kind as the input
+        (NumPy or torch CUDA).  Problem p's bits do not depend on B or on its place in the batch; the values are bitwise symmetric."""
+        v = self._ics(ics)
+        B = v.shape[0]
+        like2 = PosteriorAssembler._like2
+        out = {"bulk": like2(v, (B,)), "q_values": like2(v, (B, self.nnz)), "Qx_prior": like2(v, (B, self.n))}
+        _cabi.check(_cabi.load().gmrf_burgers_prior_values_batch(self._h, B, _cabi.ptr(v), _cabi.ptr(out["bulk"]), _cabi.ptr(out["q_values"]),
+                                                                 _cabi.ptr(out["Qx_prior"])))
+        return out
+
+
 class EllipticP1Tangent:
     """Tangent, residual and load of the nonlinear elliptic benchmark -Lap u + u^3 = f_src on the device:
     `f_and_J` of /root/reference/_research/elliptic_chen24.jl:280-285 with `assemble_J_cube` (:231-278) and the stiffness
@@ -725,6 +780,75 @@ class DarcyConditioningBatch:
                                       C.byref(info))
         _cabi.check(st, info.value)
         return out
+
+
+class BurgersInitialConditionBatch:
+    """The "Prior" and "Initial condition" stages of the Burgers data-set loop (scripts/burgers/solve_burgers_gmrf-fem.jl:154-179) for
+    `F.batch` problems in ONE call, resident on the device (gmrf_bic_run): initial conditions -> bulk, the prior's values and
+    information vector -> refactor -> x_ic = mean(x_ic), on the handle and the analysis `GaussNewtonBatch` uses afterwards:
+
+        x_ic, q, qx, _ = ic_stage.run(ics)
+        x, steps, hist = gn.run(q, qx, x_ic, x_ic)      # prior mean and start = mean(x_ic); Q_ic mean(x_ic) = qx
+        F = gn.finalize()                               # then sample_batch / marginal_var_batch
+
+    `F` (reference order, factored once on `asm.pattern`), `asm` (built on `prior.pattern` and the tangent's pattern) and `prior`
+    must have been created on the same device with the same `stream` argument."""
+
+    def __init__(self, F: "TridiagonalCholeskyFactor", asm: PosteriorAssembler, prior: BurgersP1Prior):
+        self.F, self.asm, self.prior = F, asm, prior              # (kept alive: the library holds their handles)
+        self._h = C.c_void_p()
+        _cabi.check(_cabi.load().gmrf_bic_create(F._h, asm._h, prior._h, C.byref(self._h)))
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            _cabi.load().gmrf_bic_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def run(self, ics):
+        """ics (B, ns), NumPy or torch CUDA -> (x_ic (B, n), q_values (B, nnz_q), Qx_prior (B, n), bulk (B,)) of the same kind.
+        NotPositiveDefinite carries the failing block in `.info`."""
+        B, a = self.F.batch, self.asm
+        v = self.prior._ics(ics)
+        if v.shape[0] != B:
+            raise GmrfError(_cabi.ERR_BAD_SHAPE, f"ics: expected ({B}, {self.prior.ns}), the batch of the handle")
+        like2 = PosteriorAssembler._like2
+        x_ic, q, qx, bulk = like2(v, (B, a.n)), like2(v, (B, a.nnz_q)), like2(v, (B, a.n)), like2(v, (B,))
+        info = C.c_int32(0)
+        st = _cabi.load().gmrf_bic_run(self._h, _cabi.ptr(v), _cabi.ptr(x_ic), _cabi.ptr(q), _cabi.ptr(qx), _cabi.ptr(bulk), C.byref(info))
+        _cabi.check(st, info.value)
+        return x_ic, q, qx, bulk
+
+
+def solution_errors_batch(pred, soln, first: int = 0, device: int = 0) -> np.ndarray:
+    """(B, 3) NumPy array of (rel_err, rmse, max_err) per problem (/root/reference/src/metrics.jl:3-13; `workloads.solution_errors`
+    on the host) of pred against soln, both (B, n) NumPy arrays or torch CUDA tensors, over the elements [first, n): first = ns
+    leaves the first time slice out as the scripts' [2:end, :] does.  Computed on the device with fixed-shape sums: the same bits
+    on every call and for every B."""
+    def prep(a):
+        if _is_torch(a):
+            import torch
+            if a.dtype != torch.float64:
+                raise TypeError("float64 required")
+            return a.contiguous()
+        return np.ascontiguousarray(a, dtype=np.float64)
+    p, s = prep(pred), prep(soln)
+    if p.ndim != 2 or tuple(p.shape) != tuple(s.shape):
+        raise ValueError("pred and soln must have one shape (B, n)")
+    stream = 0
+    for a in (p, s):
+        if _is_torch(a) and a.is_cuda:
+            import torch
+            device, stream = a.device.index, torch.cuda.current_stream(a.device).cuda_stream
+    out = np.empty((p.shape[0], 3), dtype=np.float64)
+    _cabi.check(_cabi.load().gmrf_field_errors_batch(int(device), C.c_void_p(stream), p.shape[0], p.shape[1], int(first), _cabi.ptr(p),
+                                                     _cabi.ptr(s), _cabi.ptr(out)))
+    return out
 
 
 class ConditionedGMRF:

@@ -44,6 +44,7 @@
 #include "selinv.hpp"
 #include "gauss_newton.hpp"
 #include "darcy_cond.hpp"
+#include "burgers_prior.hpp"
 
 using namespace gmrf;
 
@@ -4134,6 +4135,96 @@ gmrf_status gmrf_burgers_p1_tangent_batch(gmrf_burgers_p1* b, int64_t batch, con
     return GMRF_OK;
 }
 
+// --------------------------------------------------------------------------------- Burgers prior ("Prior" / "Initial condition" stages)
+struct gmrf_burgers_prior : DevCtx {    // device -1: pattern only
+    int64_t ns = 0, nt = 0, n = 0, nnz = 0;
+    double dt = 0.0, nu = 0.0, ic_noise = 0.0;
+    DevBuf arena;                       // host arguments of the current call (Staging)
+    DevBuf bulk;                        // [batch] means of a call that does not ask for them
+};
+
+gmrf_status gmrf_burgers_prior_create(int32_t device, void* stream, int64_t ns, int64_t nt, double dt, double nu, double ic_noise,
+                                      gmrf_burgers_prior** out) {
+    if (!out || nt < 2 || ns > (1 << 24) || nt > (1 << 20) || !(dt > 0.0) || !(nu > 0.0) || !(ic_noise >= 0.0) || !std::isfinite(ic_noise))
+        return bad_shape("bad Burgers prior (nt >= 2 slices, dt > 0, nu > 0, ic_noise >= 0)");
+    if (ns < 5) return bad_shape("the Burgers prior needs ns >= 5 nodes: fewer fold the periodic offsets 0, +-1, +-2 onto each other");
+    std::unique_ptr<gmrf_burgers_prior, gmrf_status (*)(gmrf_burgers_prior*)> guard(new gmrf_burgers_prior(), gmrf_burgers_prior_destroy);
+    gmrf_burgers_prior* p = guard.get();
+    p->ns = ns; p->nt = nt; p->n = ns * nt; p->nnz = burgers_prior_nnz(ns, nt); p->dt = dt; p->nu = nu; p->ic_noise = ic_noise;
+    GCHK(p->open(device, stream, hipStreamNonBlocking, "gmrf_burgers_prior_create"));
+    *out = guard.release();
+    return GMRF_OK;
+}
+
+gmrf_status gmrf_burgers_prior_destroy(gmrf_burgers_prior* p) {
+    if (!p) return GMRF_OK;
+    p->close();
+    if (p->has_device()) { p->arena.release(); p->bulk.release(); }
+    delete p;
+    return GMRF_OK;
+}
+
+// CSC pattern of Q_ic (symmetric, both triangles, rows ascending): burgers_prior_entry is its one statement
+gmrf_status gmrf_burgers_prior_pattern(const gmrf_burgers_prior* p, int64_t* nnz_out, int64_t* colptr, int64_t* rowval, int32_t index_base) {
+    if (!p) return bad_shape("null handle");
+    if (index_base != 0 && index_base != 1) return bad_shape("index_base must be 0 or 1");
+    if (nnz_out) *nnz_out = p->nnz;
+    if (colptr) {
+        for (int64_t j = 0; j < p->n; ++j) colptr[j] = burgers_prior_colptr(p->ns, p->nt, j / p->ns, j % p->ns) + index_base;
+        colptr[p->n] = p->nnz + index_base;
+    }
+    if (rowval)
+        for (int64_t e = 0; e < p->nnz; ++e) {
+            int64_t row, col;
+            burgers_prior_entry(p->ns, p->nt, e, &row, &col);
+            rowval[e] = row + index_base;
+        }
+    return GMRF_OK;
+}
+
+static BurgersPriorArgs prior_args(const gmrf_burgers_prior* p) {
+    BurgersPriorArgs a;
+    a.ns = p->ns; a.nt = p->nt; a.dt = p->dt; a.nu = p->nu; a.ic_noise = p->ic_noise;
+    return a;
+}
+
+// d_q / d_qx: nullptr = not wanted
+static gmrf_status launch_prior_batch(const gmrf_burgers_prior* p, hipStream_t st, int64_t batch, const double* d_ic, double* d_bulk,
+                                      double* d_q, double* d_qx) {
+    const BurgersPriorArgs a = prior_args(p);
+    hipLaunchKernelGGL(burgers_bulk_batch, dim3(1, (unsigned)batch), dim3(256), 0, st, d_ic, p->ns, d_bulk);
+    if (d_q)
+        hipLaunchKernelGGL(burgers_prior_values_batch, dim3((unsigned)((p->nnz + 255) / 256), (unsigned)batch), dim3(256), 0, st, a, d_bulk,
+                           p->nnz, d_q);
+    if (d_qx)
+        hipLaunchKernelGGL(burgers_prior_rhs_batch, dim3((unsigned)((p->n + 255) / 256), (unsigned)batch), dim3(256), 0, st, a, d_bulk, d_ic,
+                           d_qx);
+    HIPCHK(hipGetLastError());
+    return GMRF_OK;
+}
+
+gmrf_status gmrf_burgers_prior_values_batch(gmrf_burgers_prior* p, int64_t batch, const double* ic, double* bulk_out, double* q_values_out,
+                                            double* qx_out) {
+    if (!p || !ic || !batch_ok(batch)) return bad_shape("bad Burgers prior arguments (batch in [1, 4096])");
+    GCHK(p->ready("pattern-only Burgers prior"));
+    const double* d_ic;
+    double *d_bulk, *d_q, *d_qx;
+    Staging args(p->arena);
+    args.in(ic, sizeof(double) * batch * p->ns, &d_ic);
+    args.out(bulk_out, sizeof(double) * batch, &d_bulk);
+    args.out(q_values_out, sizeof(double) * batch * p->nnz, &d_q);
+    args.out(qx_out, sizeof(double) * batch * p->n, &d_qx);
+    GCHK(args.commit(p->stream));
+    if (!d_bulk) {
+        GCHK(p->bulk.reserve(p->stream, sizeof(double) * batch));
+        d_bulk = p->bulk.as<double>();
+    }
+    GCHK(launch_prior_batch(p, p->stream, batch, d_ic, d_bulk, d_q, d_qx));
+    GCHK(args.flush(p->stream));
+    HIPCHK(hipStreamSynchronize(p->stream));
+    return GMRF_OK;
+}
+
 // --------------------------------------------------------------------------------- nonlinear elliptic tangent
 struct gmrf_elliptic_p1 : DevCtx {      // device -1: pattern and quadrature points only
     int64_t nx = 0, ny = 0, n = 0, nnz = 0, cells = 0;
@@ -4541,28 +4632,34 @@ static gmrf_status gn_copy_out(gmrf_gn* g, void* dst, const void* src, size_t by
     return GMRF_OK;
 }
 
-// A^-1 rhs -> d_xn on the handle's stream.  The factorisation of the registered rhs left y = L^-1 rhs (fy_for): the backward sweep
+// A^-1 d_rhs -> d_out on the handle's stream.  The factorisation of the registered rhs left y = L^-1 rhs (fy_for): the backward sweep
 // of a copy of y is the whole solve; else both sweeps.  A batch's sweeps are never persistent launches, so nothing is waited for;
-// one problem goes through the guard of the persistent sweeps and ends in the stream's synchronisation.
-static gmrf_status gn_solve(gmrf_gn* g) {
-    gmrf_handle* h = g->h;
+// one problem goes through the guard of the persistent sweeps and ends in the stream's synchronisation.  *took_y: which it was.
+static gmrf_status solve_registered(gmrf_handle* h, const double* d_rhs, double* d_out, bool* took_y) {
     const int64_t vec_bytes = h->n * h->B * (int64_t)sizeof(double);
-    return sweep_guarded(h, {{g->d_rhs, vec_bytes, g->d_xn, vec_bytes}}, [&]() -> gmrf_status {
+    return sweep_guarded(h, {{d_rhs, vec_bytes, d_out, vec_bytes}}, [&]() -> gmrf_status {
         GCHK(ensure_panels(h, 1));
-        const bool have_y = h->fy_for && h->fy_for == g->d_rhs;
+        const bool have_y = h->fy_for && h->fy_for == d_rhs;
+        *took_y = have_y;
         if (have_y) {
-            g->fwd_iterations += 1;
             HIPCHK(hipMemcpyAsync(h->d_P, h->d_fy, sizeof(double) * (size_t)(h->B * h->n_pad), hipMemcpyDeviceToDevice, h->stream));
             GCHK(run_sweeps(h, GMRF_SOLVE_BACKWARD, 1));
-            GCHK(launch_unpack(h, h->d_Y, g->d_xn, h->n, 1, nullptr));
+            GCHK(launch_unpack(h, h->d_Y, d_out, h->n, 1, nullptr));
         } else {
-            GCHK(launch_pack(h, g->d_rhs, h->n, 1, 1));
+            GCHK(launch_pack(h, d_rhs, h->n, 1, 1));
             GCHK(run_sweeps(h, GMRF_SOLVE_FULL, 1));
-            GCHK(launch_unpack(h, h->d_P, g->d_xn, h->n, 1, nullptr));
+            GCHK(launch_unpack(h, h->d_P, d_out, h->n, 1, nullptr));
         }
         if (h->B == 1) HIPCHK(hipStreamSynchronize(h->stream));
         return GMRF_OK;
     });
+}
+
+static gmrf_status gn_solve(gmrf_gn* g) {
+    bool took_y = false;
+    GCHK(solve_registered(g->h, g->d_rhs, g->d_xn, &took_y));
+    if (took_y) g->fwd_iterations += 1;
+    return GMRF_OK;
 }
 
 static GnState gn_state(const gmrf_gn* g) {
@@ -4820,6 +4917,169 @@ gmrf_status gmrf_dc_run(gmrf_dc* g, const double* coeff_tables, int64_t ng, doub
     GCHK(copy_out(std_norm_out, g->d_norm, B));
     HIPCHK(hipStreamSynchronize(st));
     return GMRF_OK;
+}
+
+// --------------------------------------------------------------------------------- the batched Burgers initial-condition stage
+// B = batch of the handle problems of the Burgers data-set loop (scripts/burgers/solve_burgers_gmrf-fem.jl:154-208), its "Prior"
+// and "Initial condition" stages in ONE call on the handle's stream:
+//     ic -> bulk, Q_ic's values, Qx_prior (burgers_prior.hpp) -> Q_ic in the order of the assembler's pattern -> gmrf_bt_refactor_values
+//     -> x_ic = Q_ic^-1 Qx_prior = mean(x_ic)
+// on the handle and the analysis the Gauss-Newton driver uses afterwards: the assembler's pattern, that of Q + J'J, filled by the
+// assembler's own kernel with noise 0 and J = 0.  Qx_prior is registered as the factor's right-hand side (gmrf_bt_set_factor_rhs)
+// for the run, as gmrf_dc_run does; the caller's registration comes back afterwards.
+struct gmrf_bic {
+    gmrf_handle* h = nullptr;
+    gmrf_assembler* as = nullptr;
+    gmrf_burgers_prior* pr = nullptr;
+    DevBuf in;                           // arena of a host ic (Staging)
+    DevBuf work;                         // everything below, carved up by bic_alloc
+    int64_t B = 0;                       // what `work` is carved for
+    double *d_bulk = nullptr, *d_q = nullptr, *d_qx = nullptr, *d_jz = nullptr, *d_a = nullptr, *d_x = nullptr;
+    int device = 0;                      // (copies: gmrf_bic_destroy does not reach into the handle)
+    hipStream_t stream = nullptr;
+    int32_t fwd_in_factor = 0;           // the last run's factorisation left y = L^-1 Qx_prior (gmrf_test_bic_route)
+};
+
+static gmrf_status bic_bound_ok(const gmrf_bic* g) {
+    const gmrf_handle* h = g->h;
+    GCHK(tw_refuse(h, "the Burgers initial-condition driver"));
+    if (g->as->device != h->device || g->pr->device != h->device) return bad_shape("handle, assembler and Burgers prior must live on one device");
+    if (g->as->stream != h->stream || g->pr->stream != h->stream) return bad_shape("handle, assembler and Burgers prior must share one stream");
+    if (g->as->n != g->pr->n || g->as->nnz_q != g->pr->nnz) return bad_shape("the assembler's Q is not the Burgers prior's pattern");
+    if (h->analyzed && (h->n != g->as->n || h->nnz_in != g->as->nnz_out)) return bad_shape("the handle has not analysed the assembler's pattern");
+    return GMRF_OK;
+}
+
+gmrf_status gmrf_bic_create(gmrf_handle* h, gmrf_assembler* as, gmrf_burgers_prior* prior, gmrf_bic** out) {
+    if (!out || !as || !prior) return bad_shape("null pointer");
+    if (as->device < 0 || prior->device < 0) {
+        g_last_error = "the Burgers initial-condition driver needs an assembler and a Burgers prior with a device (created with device -1)";
+        return GMRF_ERR_NO_DEVICE;
+    }
+    if (!h) return bad_shape("null handle");
+    gmrf_bic tmp; tmp.h = h; tmp.as = as; tmp.pr = prior; tmp.device = h->device; tmp.stream = h->stream;
+    GCHK(bic_bound_ok(&tmp));
+    // the same sizes are not yet the same pattern: entry by entry against the prior's statement of it
+    if (as->q_ptr.empty()) return bad_shape("the Burgers initial-condition driver needs n < 2^31");
+    for (int64_t j = 0; j <= as->n; ++j) {
+        const int64_t at = j < as->n ? burgers_prior_colptr(prior->ns, prior->nt, j / prior->ns, j % prior->ns) : prior->nnz;
+        if (as->q_ptr[(size_t)j] != at) return bad_shape("the assembler's Q is not the Burgers prior's pattern");
+    }
+    for (int64_t e = 0; e < prior->nnz; ++e) {
+        int64_t row, col;
+        burgers_prior_entry(prior->ns, prior->nt, e, &row, &col);
+        if (as->q_row[(size_t)e] != row) return bad_shape("the assembler's Q is not the Burgers prior's pattern");
+    }
+    *out = new gmrf_bic(tmp);
+    return GMRF_OK;
+}
+
+gmrf_status gmrf_bic_destroy(gmrf_bic* g) {
+    if (!g) return GMRF_OK;
+    (void)hipSetDevice(g->device);
+    (void)hipStreamSynchronize(g->stream);
+    g->in.release(); g->work.release();
+    delete g;
+    return GMRF_OK;
+}
+
+static gmrf_status bic_alloc(gmrf_bic* g, int64_t B) {
+    if (g->B == B && g->work.p) return GMRF_OK;
+    const gmrf_assembler* as = g->as;
+    int64_t total = 0;
+    auto take = [&](int64_t elems) { const int64_t at = total; total += (std::max<int64_t>(elems, 1) + 1) & ~(int64_t)1; return at; };     // (16-byte aligned pieces)
+    const int64_t o_bulk = take(B), o_q = take(B * as->nnz_q), o_qx = take(B * as->n), o_jz = take(as->nnz_j), o_a = take(B * as->nnz_out);
+    const int64_t o_x = take(B * as->n);
+    GCHK(g->work.reserve(g->h->stream, sizeof(double) * (size_t)total));
+    double* w = g->work.as<double>();
+    g->d_bulk = w + o_bulk; g->d_q = w + o_q; g->d_qx = w + o_qx; g->d_jz = w + o_jz; g->d_a = w + o_a; g->d_x = w + o_x;
+    // J = 0, once: one array serves every problem (a stride of 0), and nothing writes it
+    HIPCHK(hipMemsetAsync(g->d_jz, 0, sizeof(double) * (size_t)std::max<int64_t>(as->nnz_j, 1), g->h->stream));
+    g->B = B;
+    return GMRF_OK;
+}
+
+gmrf_status gmrf_bic_run(gmrf_bic* g, const double* ic, double* x_ic_out, double* q_values_out, double* qx_out, double* bulk_out,
+                         int32_t* info) {
+    if (!g || !ic || !x_ic_out) return bad_shape("null pointer");
+    if (info) *info = 0;
+    gmrf_handle* h = g->h;
+    gmrf_assembler* as = g->as;
+    GCHK(bic_bound_ok(g));
+    if (!h->analyzed) { g_last_error = "gmrf_bic_run: factor the assembler's pattern once on this handle first"; return GMRF_ERR_NO_FACTOR; }
+    const int64_t B = h->B, n = as->n;
+    if (!batch_ok(B)) return bad_shape("batch outside [1, 4096]");
+    HIPCHK(hipSetDevice(h->device));
+    hipStream_t st = h->stream;
+    GCHK(bic_alloc(g, B));
+    const double* d_ic;
+    Staging args(g->in);
+    args.in(ic, sizeof(double) * B * g->pr->ns, &d_ic);
+    GCHK(args.commit(st));
+    // 1 - 2: the prior's values and information vector, Q_ic in the order of the handle's analysis (noise 0, J = 0 at stride 0)
+    GCHK(launch_prior_batch(g->pr, st, B, d_ic, g->d_bulk, g->d_q, g->d_qx));
+    hipLaunchKernelGGL(assemble_precision_batch, dim3((unsigned)((as->nnz_out + 255) / 256), (unsigned)B), dim3(256), 0, st, as->d_pptr,
+                       as->d_pa, as->d_pb, as->d_qmap, g->d_q, as->nnz_q, g->d_jz, (int64_t)0, 0.0, as->nnz_out, g->d_a);
+    HIPCHK(hipGetLastError());
+    // 3 - 4 behind the registration; the caller's comes back afterwards
+    const double* user_frhs = h->frhs;
+    h->frhs = g->d_qx; h->fy_for = nullptr;
+    g->fwd_in_factor = 0;
+    auto solve = [&]() -> gmrf_status {
+        GCHK(numeric_factor(h, g->d_a, info));
+        bool took_y = false;
+        GCHK(solve_registered(h, g->d_qx, g->d_x, &took_y));
+        g->fwd_in_factor = took_y ? 1 : 0;
+        return GMRF_OK;
+    };
+    const gmrf_status status = solve();
+    h->frhs = user_frhs; h->fy_for = nullptr;
+    if (status != GMRF_OK) { (void)hipStreamSynchronize(st); return status; }      // (the outputs are untouched)
+    auto copy_out = [&](double* dst, const double* src, int64_t count) -> gmrf_status {
+        if (!dst) return GMRF_OK;
+        HIPCHK(hipMemcpyAsync(dst, src, sizeof(double) * (size_t)count, is_device_ptr(dst) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
+        return GMRF_OK;
+    };
+    GCHK(copy_out(x_ic_out, g->d_x, B * n));
+    GCHK(copy_out(q_values_out, g->d_q, B * as->nnz_q));
+    GCHK(copy_out(qx_out, g->d_qx, B * n));
+    GCHK(copy_out(bulk_out, g->d_bulk, B));
+    HIPCHK(hipStreamSynchronize(st));
+    return GMRF_OK;
+}
+
+// --------------------------------------------------------------------------------- batched error metrics (src/metrics.jl)
+static int64_t field_errors_chunks(int64_t count) { return std::min<int64_t>(1024, std::max<int64_t>(1, (count + 2047) / 2048)); }
+
+gmrf_status gmrf_field_errors_batch(int32_t device, void* stream, int64_t batch, int64_t n, int64_t first, const double* pred,
+                                    const double* soln, double* out) {
+    if (!pred || !soln || !out || !batch_ok(batch)) return bad_shape("null pointer or batch outside [1, 4096]");
+    if (n <= 0 || first < 0 || first >= n) return bad_shape("the elements [first, n) must not be empty");
+    DevCtx ctx;
+    GCHK(ctx.open(device, stream, hipStreamNonBlocking, "gmrf_field_errors_batch", false));
+    DevBuf arena, part;
+    const int64_t count = n - first, nch = field_errors_chunks(count), len = (count + nch - 1) / nch;
+    const double *d_pred, *d_soln;
+    double* d_out;
+    Staging args(arena);
+    args.in(pred, sizeof(double) * batch * n, &d_pred);
+    args.in(soln, sizeof(double) * batch * n, &d_soln);
+    args.out(out, sizeof(double) * batch * 3, &d_out);
+    auto run = [&]() -> gmrf_status {
+        GCHK(args.commit(ctx.stream));
+        GCHK(part.reserve(ctx.stream, sizeof(double) * (size_t)(batch * nch * 3)));
+        hipLaunchKernelGGL(field_errors_part, dim3((unsigned)nch, (unsigned)batch), dim3(256), 0, ctx.stream, d_pred, d_soln, n, first, len,
+                           part.as<double>());
+        hipLaunchKernelGGL(field_errors_finish, dim3(1, (unsigned)batch), dim3(256), 0, ctx.stream, part.as<double>(), nch, count, d_out);
+        HIPCHK(hipGetLastError());
+        GCHK(args.flush(ctx.stream));
+        HIPCHK(hipStreamSynchronize(ctx.stream));
+        return GMRF_OK;
+    };
+    const gmrf_status status = run();
+    ctx.close();                        // (drains the stream before the buffers go)
+    arena.release(); part.release();
+    return status;
 }
 
 // --------------------------------------------------------------------------------- shallow-water element kernels
@@ -6263,6 +6523,13 @@ gmrf_status gmrf_test_gn_route(gmrf_gn* g, int32_t* iterations, int32_t* fwd_ite
 
 // The last gmrf_dc_run: 1 if its factorisation carried the forward sweep of the information vector (the forward-in-factor route)
 gmrf_status gmrf_test_dc_route(gmrf_dc* g, int32_t* fwd_in_factor) {
+    if (!g || !fwd_in_factor) return bad_shape("null pointer");
+    *fwd_in_factor = g->fwd_in_factor;
+    return GMRF_OK;
+}
+
+// The last gmrf_bic_run: 1 if its factorisation carried the forward sweep of Qx_prior (the forward-in-factor route)
+gmrf_status gmrf_test_bic_route(gmrf_bic* g, int32_t* fwd_in_factor) {
     if (!g || !fwd_in_factor) return bad_shape("null pointer");
     *fwd_in_factor = g->fwd_in_factor;
     return GMRF_OK;

@@ -314,23 +314,17 @@ def p1_periodic_line(ns: int):
     return M, np.full(ns, h), S, Adv
 
 
-def burgers(ns: int, nt: int, ic_noise: float = 1e8, fem_noise: float = 1e12, ic=None) -> Workload:
-    """1-D viscous Burgers space-time GMRF in the time-major ordering (t-1)*ns + s:
-    Q = Q_prior + ic_noise A_ic^T A_ic + fem_noise J^T J, N = nt blocks of size ns.
-
-    Q_prior: implicit-Euler state-space blocks  G x_{t+1} = M x_t + noise  with
-    G = M + dt (nu S + gamma Adv) and a Matern(alpha=2) initial precision
-    (scripts/burgers/solve_burgers_gmrf-fem.jl:86-107; block structure of joint_ssm,
-    SURVEY.md appendix A).  J = J_static + dt J_adv(u) linearised at the initial
-    condition (scripts/burgers/solve_burgers_gmrf-fem.jl:118-149)."""
+def burgers_prior_from_bulk(ns: int, nt: int, bulk: float, ic, ic_noise: float = 1e8):
+    """The prior part of `burgers` with the bulk speed passed in: returns (Qp, Aic, rhs) with Qp the prior precision (CSR; the
+    implicit-Euler state-space blocks G x_{t+1} = M x_t + noise, G = M + dt (nu c S + gamma Adv), gamma = -c bulk, and the
+    Matern(alpha=2) initial precision; scripts/burgers/solve_burgers_gmrf-fem.jl:86-107), Aic the restriction to the first
+    slice and rhs = Qp (bulk 1) + ic_noise Aic' ic, the information vector of the prior conditioned on the initial condition
+    (:161).  `burgers` calls it with bulk = mean(ic); the device prior (`BurgersP1Prior`) is tested against it at its own mean."""
     nu_b = 0.01 / math.pi
     dt = 1.0 / (nt - 1)
     M, lumped, S, Adv = p1_periodic_line(ns)
-    xs = np.arange(ns) / ns
-    if ic is None:                                     # (another initial condition: burgers_gauss_newton_batch)
-        ic = np.sin(2 * np.pi * xs) + 0.5 * np.sin(4 * np.pi * xs + 0.3)
     ic = np.asarray(ic, dtype=np.float64)
-    bulk = float(ic.mean())
+    bulk = float(bulk)
     c = 1.0 / nu_b
     gamma = -c * bulk
     tau = 0.1 * math.sqrt(c)
@@ -353,6 +347,29 @@ def burgers(ns: int, nt: int, ic_noise: float = 1e8, fem_noise: float = 1e12, ic
             blocks[t][t - 1] = -GWM
             blocks[t - 1][t] = -GWM.T
     Qp = sp.bmat(blocks, format="csr")
+    Aic = sp.hstack([sp.identity(ns, format="csr"), sp.csr_matrix((ns, ns * (nt - 1)))]).tocsr()
+    mu0 = np.full(ns * nt, bulk)
+    rhs = Qp @ mu0 + ic_noise * (Aic.T @ ic)
+    return Qp, Aic, np.asarray(rhs)
+
+
+def burgers(ns: int, nt: int, ic_noise: float = 1e8, fem_noise: float = 1e12, ic=None) -> Workload:
+    """1-D viscous Burgers space-time GMRF in the time-major ordering (t-1)*ns + s:
+    Q = Q_prior + ic_noise A_ic^T A_ic + fem_noise J^T J, N = nt blocks of size ns.
+
+    Q_prior: implicit-Euler state-space blocks  G x_{t+1} = M x_t + noise  with
+    G = M + dt (nu S + gamma Adv) and a Matern(alpha=2) initial precision
+    (scripts/burgers/solve_burgers_gmrf-fem.jl:86-107; block structure of joint_ssm,
+    SURVEY.md appendix A; stated in `burgers_prior_from_bulk`).  J = J_static + dt J_adv(u) linearised at the initial
+    condition (scripts/burgers/solve_burgers_gmrf-fem.jl:118-149)."""
+    nu_b = 0.01 / math.pi
+    dt = 1.0 / (nt - 1)
+    M, lumped, S, Adv = p1_periodic_line(ns)
+    xs = np.arange(ns) / ns
+    if ic is None:                                     # (another initial condition: burgers_gauss_newton_batch)
+        ic = np.sin(2 * np.pi * xs) + 0.5 * np.sin(4 * np.pi * xs + 0.3)
+    ic = np.asarray(ic, dtype=np.float64)
+    Qp, Aic, rhs = burgers_prior_from_bulk(ns, nt, float(ic.mean()), ic, ic_noise)
     # Burgers residual tangent: rows couple slices t-1 and t only.
     u = ic
     Jadv = (sp.diags(u) @ Adv + sp.diags(Adv @ u)).tocsr()   # d/du of u u_x, lumped
@@ -367,13 +384,10 @@ def burgers(ns: int, nt: int, ic_noise: float = 1e8, fem_noise: float = 1e12, ic
                 row[k] = sp.csr_matrix((ns, ns))
         rowsJ.append(row)
     J = sp.bmat(rowsJ, format="csr")
-    Aic = sp.hstack([sp.identity(ns, format="csr"), sp.csr_matrix((ns, ns * (nt - 1)))]).tocsr()
     Q = (Qp + ic_noise * (Aic.T @ Aic) + fem_noise * (J.T @ J)).tocsc()
     Q = ((Q + Q.T) * 0.5).tocsc()
     Q.sort_indices()
-    mu0 = np.full(ns * nt, bulk)
-    rhs = Qp @ mu0 + ic_noise * (Aic.T @ ic)
-    return Workload(f"burgers{ns}x{nt}", Q, np.asarray(rhs), nt,
+    return Workload(f"burgers{ns}x{nt}", Q, rhs, nt,
                     {"dt": dt, "nu": nu_b, "nnz": int(Q.nnz)})
 
 

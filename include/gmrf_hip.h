@@ -523,6 +523,29 @@ gmrf_status gmrf_burgers_p1_pattern(const gmrf_burgers_p1* b, int64_t* nnz_out, 
                                     int32_t index_base);
 gmrf_status gmrf_burgers_p1_tangent(gmrf_burgers_p1* b, const double* w, double* vals_out, double* f_out);
 
+/* The prior of the Burgers space-time GMRF for a batch of problems (the "Prior" stage of the data-set loop, form_prior of
+ * scripts/burgers/solve_burgers_gmrf-fem.jl:86-107, and the information vector of its "Initial condition" stage, :161) on the
+ * periodic P1 line with lumped mass, ns nodes, nt slices, time-major index -- the mesh of gmrf_burgers_p1_create.  Every problem
+ * brings its initial condition ic [ns]; the prior depends on it through bulk = mean(ic):
+ *     Q_ic = Q_prior(bulk) + ic_noise A_ic' A_ic,      Qx_prior = Q_prior(bulk) (bulk 1) + ic_noise A_ic' ic
+ * with A_ic the restriction to the first slice, so that Q_ic^-1 Qx_prior is the mean of the prior conditioned on the initial
+ * condition.  The pattern is structural: symmetric CSC, both triangles, rows ascending, nt blocks of ns; diagonal blocks hold the
+ * periodic offsets 0, +-1, +-2, the blocks beside them 0, +-1; nnz = (11 nt - 6) ns; fixed by (ns, nt), an entry whose value is
+ * 0.0 is stored.  ns < 5 (the offsets fold onto each other), nt < 2, nu <= 0: GMRF_ERR_BAD_SHAPE.  The quadratic line of
+ * gmrf_burgers_p2_create has no prior here.
+ * gmrf_burgers_prior_values_batch: ic [batch][ns] -> bulk_out [batch], q_values_out [batch][nnz] in the order of _pattern (the
+ * q_nzval of gmrf_gn_run at q_stride = nnz), qx_out [batch][nt ns]; each output may be NULL, every pointer host or device memory;
+ * batch in [1, 4096].  The means are fixed-shape sums without atomics, the values are bitwise symmetric, and problem p's bits do
+ * not depend on the batch or on its place in it.  device -1: pattern only. */
+typedef struct gmrf_burgers_prior gmrf_burgers_prior;
+gmrf_status gmrf_burgers_prior_create(int32_t device, void* stream, int64_t ns, int64_t nt, double dt, double nu, double ic_noise,
+                                      gmrf_burgers_prior** out);
+gmrf_status gmrf_burgers_prior_destroy(gmrf_burgers_prior* p);
+gmrf_status gmrf_burgers_prior_pattern(const gmrf_burgers_prior* p, int64_t* nnz_out, int64_t* colptr, int64_t* rowval,
+                                       int32_t index_base);
+gmrf_status gmrf_burgers_prior_values_batch(gmrf_burgers_prior* p, int64_t batch, const double* ic, double* bulk_out,
+                                            double* q_values_out, double* qx_out);
+
 /* A batch of Gauss-Newton loops on one mesh (the Burgers data-set loop, scripts/burgers/solve_burgers_gmrf-fem.jl:154-233 with the
  * loop body of scripts/solve_burger.jl:143-180).  All arrays are problem-major ([batch][...]), host or device pointers like the
  * one-problem calls; problem p of a batch call gets the bits of the one-problem call on its slice.  q_stride: 0 = one Q for
@@ -557,6 +580,32 @@ gmrf_status gmrf_gn_run(gmrf_gn* g, const double* q_nzval, int64_t q_stride, con
                         double* x, const double* y, double noise, double rtol, int32_t max_steps, int32_t* steps_out,
                         double* obj_hist_out, int32_t* info);
 gmrf_status gmrf_gn_finalize(gmrf_gn* g, int32_t* info);
+
+/* The "Prior" and "Initial condition" stages of the Burgers data-set loop (solve_burgers_gmrf-fem.jl:154-179) for a batch, on
+ * the handle and the analysis gmrf_gn_run uses afterwards.  The driver binds a handle (reference order; its batch B is the
+ * number of problems), an assembler whose Q pattern is the prior's (gmrf_burgers_prior_pattern) and that prior, all on ONE device
+ * and ONE stream; anything else -- a twisted handle, a handle that analysed another pattern, another Q pattern -- is
+ * GMRF_ERR_BAD_SHAPE, an assembler or prior created with device -1 GMRF_ERR_NO_DEVICE.  gmrf_bic_run: the handle must have
+ * factored the assembler's pattern once (GMRF_ERR_NO_FACTOR before).  One call, on the handle's stream:
+ *     ic [B][ns] -> bulk, Q_ic's values, Qx_prior -> Q_ic on the assembler's pattern (its J'J entries 0) -> Qx_prior registered with
+ *     gmrf_bt_set_factor_rhs for the run (the caller's registration is put back) -> gmrf_bt_refactor_values -> x_ic = Q_ic^-1 Qx_prior
+ *     (the backward sweep alone where the factorisation carried the forward one; set_eager bit 19 switches that off).
+ * x_ic [B][n] is mean(x_ic) of :172-179: prior mean and start point of gmrf_gn_run, with q_values_out as its q_nzval and qx_out
+ * (= Q_ic x_ic) as its qx_prior.  ic, x_ic_out: host or device; q_values_out [B][nnz(Q)], qx_out [B][n], bulk_out [B]: NULL (not
+ * wanted), host or device.  GMRF_ERR_NOT_SPD ends the call with `info` as gmrf_bt_refactor_values sets it and leaves the outputs
+ * untouched.  The handle is left as any refactorisation leaves it: a later gmrf_gn_run does not see that the stage ran. */
+typedef struct gmrf_bic gmrf_bic;
+gmrf_status gmrf_bic_create(gmrf_handle* h, gmrf_assembler* as, gmrf_burgers_prior* prior, gmrf_bic** out);
+gmrf_status gmrf_bic_destroy(gmrf_bic* g);
+gmrf_status gmrf_bic_run(gmrf_bic* g, const double* ic, double* x_ic_out, double* q_values_out, double* qx_out, double* bulk_out,
+                         int32_t* info);
+
+/* Error metrics of a batch of fields against their truths (src/metrics.jl:3-13) over the elements [first, n) of every problem:
+ * out [batch][3] = (rel_err, rmse, max_err) = (|d|_2 / |soln|_2, sqrt(mean(d^2)), max |d|) with d = pred - soln; first = ns skips
+ * the first time slice as the scripts' [2:end, :] does.  pred, soln [batch][n], out: host or device; stream NULL: one of the
+ * call's own.  Fixed-shape sums without atomics: the same bits on every call and in every batch.  A zero soln gives inf / nan. */
+gmrf_status gmrf_field_errors_batch(int32_t device, void* stream, int64_t batch, int64_t n, int64_t first, const double* pred,
+                                    const double* soln, double* out);
 
 /* Tangent, residual and load of the nonlinear elliptic benchmark -Lap u + u^3 = f_src (FEM block assembly, fourth piece;
  * /root/reference/_research/elliptic_chen24.jl) as its Gauss-Newton loop evaluates them per iteration (f_and_J, :280-285):
@@ -680,6 +729,8 @@ gmrf_status gmrf_test_factor_fwd(gmrf_handle* h, int32_t* state, double* y_out);
 gmrf_status gmrf_test_gn_route(gmrf_gn* g, int32_t* iterations, int32_t* fwd_iterations);
 /* the last gmrf_dc_run: 1 if its factorisation took y = L^-1 rhs along (the forward-in-factor route) */
 gmrf_status gmrf_test_dc_route(gmrf_dc* g, int32_t* fwd_in_factor);
+/* the last gmrf_bic_run: 1 if its factorisation took y = L^-1 Qx_prior along (the forward-in-factor route) */
+gmrf_status gmrf_test_bic_route(gmrf_bic* g, int32_t* fwd_in_factor);
 /* the last batched sampled estimator of the handle: problems per group of the stage, groups per chunk (GMRF_VAR_STAGE_MB) */
 gmrf_status gmrf_test_var_groups(gmrf_handle* h, int32_t* group_size, int32_t* groups);
 /* The per-device budget of CUs for persistent launches, host only (no GPU needed): `n` handles ask for demands[i] CUs one after

@@ -31,6 +31,7 @@ using SparseArrays, LinearAlgebra
 
 export TridiagonalCholeskyFactor, tridiagonal_cholesky, forward_solve, backward_solve, ldiv, PosteriorAssembler, GmrfCsr,
        GmrfComm, DarcyP1Assembler, BurgersP1Tangent, EllipticP1Tangent, elliptic_load!, GaussNewtonBatch, gauss_newton_batch!, DarcyConditioningBatch,
+       BurgersP1Prior, prior_values_batch!, BurgersInitialConditionBatch, initial_condition_batch, solution_errors_batch,
        condition_on_observations_batch, assemble_batch!
 
 const libgmrf = get(ENV, "LIBGMRF_HIP", joinpath(@__DIR__, "..", "diffeqgmrfs.jl_amd", "csrc", "libgmrf_hip.so"))
@@ -738,6 +739,82 @@ function condition_on_observations_batch(dc::DarcyConditioningBatch, coeff::Arra
         UInt64(var_seed), mean, sp, sdp, np, info)
     check(st, info[])
     return mean, samples, sd, nrm
+end
+
+# The prior of the Burgers space-time GMRF (form_prior, scripts/burgers/solve_burgers_gmrf-fem.jl:86-107) on the periodic P1 line of
+# BurgersP1Tangent, with the initial condition conditioned in (:161): every problem brings its own values through bulk = mean(ic).
+# P1 only: the quadratic line has no prior here.
+mutable struct BurgersP1Prior
+    handle::Ptr{Cvoid}
+    pattern::SparseMatrixCSC{Float64,Int}     # Q_ic's structural pattern (symmetric, values 1.0): the `nzval` order of the values
+    ns::Int
+end
+
+function BurgersP1Prior(ns::Integer, nt::Integer, dt::Real, nu::Real; ic_noise::Real = 1e8, device::Integer = 0,
+                        stream::Ptr{Cvoid} = C_NULL)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:gmrf_burgers_prior_create, libgmrf), Int32, (Int32, Ptr{Cvoid}, Int64, Int64, Float64, Float64, Float64, Ref{Ptr{Cvoid}}),
+                device, stream, ns, nt, Float64(dt), Float64(nu), Float64(ic_noise), h))
+    nnz_out = Ref{Int64}(0)
+    check(ccall((:gmrf_burgers_prior_pattern, libgmrf), Int32, (Ptr{Cvoid}, Ref{Int64}, Ptr{Int64}, Ptr{Int64}, Int32), h[], nnz_out, C_NULL, C_NULL, 1))
+    n = ns * nt
+    colptr = Vector{Int64}(undef, n + 1); rowval = Vector{Int64}(undef, nnz_out[])
+    check(ccall((:gmrf_burgers_prior_pattern, libgmrf), Int32, (Ptr{Cvoid}, Ref{Int64}, Ptr{Int64}, Ptr{Int64}, Int32), h[], nnz_out, colptr, rowval, 1))
+    p = BurgersP1Prior(h[], SparseMatrixCSC(n, n, colptr, rowval, ones(nnz_out[])), ns)
+    finalizer(x -> ccall((:gmrf_burgers_prior_destroy, libgmrf), Int32, (Ptr{Cvoid},), x.handle), p)
+    return p
+end
+
+"`ics` (ns x batch) -> `bulk` (batch), `q_values` (nnz x batch, the `q_nzval` of `gauss_newton_batch!`), `Qx_prior` (n x batch)"
+function prior_values_batch!(bulk::Vector{Float64}, q_values::Matrix{Float64}, Qx_prior::Matrix{Float64}, p::BurgersP1Prior,
+                             ics::Matrix{Float64})
+    GC.@preserve ics bulk q_values Qx_prior check(ccall((:gmrf_burgers_prior_values_batch, libgmrf), Int32,
+        (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), p.handle, size(ics, 2), ics, bulk, q_values, Qx_prior))
+    return bulk, q_values, Qx_prior
+end
+
+# The "Prior" and "Initial condition" stages of the Burgers data-set loop (:154-179) for a batch, on the handle and the analysis
+# `gauss_newton_batch!` uses afterwards.  `F` (batch = number of problems, reference order, factored once on `as.pattern`), `as`
+# (built on `prior.pattern` and the tangent's pattern) and `prior` must have been created on one device and one stream.
+mutable struct BurgersInitialConditionBatch
+    handle::Ptr{Cvoid}
+    F::TridiagonalCholeskyFactor
+    as::PosteriorAssembler
+    prior::BurgersP1Prior
+end
+
+function BurgersInitialConditionBatch(F::TridiagonalCholeskyFactor, as::PosteriorAssembler, prior::BurgersP1Prior)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:gmrf_bic_create, libgmrf), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{Ptr{Cvoid}}), F.handle, as.handle, prior.handle, h))
+    g = BurgersInitialConditionBatch(h[], F, as, prior)
+    finalizer(x -> ccall((:gmrf_bic_destroy, libgmrf), Int32, (Ptr{Cvoid},), x.handle), g)
+    return g
+end
+
+"""
+    initial_condition_batch(g, ics)
+
+`ics` (ns x B).  Returns `(x_ic (n x B), q_values (nnz x B), Qx_prior (n x B), bulk (B))`: `x_ic` is `mean(x_ic)` of
+scripts/burgers/solve_burgers_gmrf-fem.jl:172-179, prior mean and start point of `gauss_newton_batch!(copy(x_ic), gn, q_values, Qx_prior, x_ic)`.
+"""
+function initial_condition_batch(g::BurgersInitialConditionBatch, ics::Matrix{Float64})
+    B = size(ics, 2); n = size(g.prior.pattern, 1); nnz_q = length(g.prior.pattern.nzval)
+    x_ic = Matrix{Float64}(undef, n, B); q_values = Matrix{Float64}(undef, nnz_q, B); Qx_prior = Matrix{Float64}(undef, n, B)
+    bulk = Vector{Float64}(undef, B); info = Ref{Int32}(0)
+    st = GC.@preserve ics x_ic q_values Qx_prior bulk ccall((:gmrf_bic_run, libgmrf), Int32,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{Int32}),
+        g.handle, ics, x_ic, q_values, Qx_prior, bulk, info)
+    check(st, info[])
+    return x_ic, q_values, Qx_prior, bulk
+end
+
+"`(rel_err, rmse, max_err)` per problem (3 x B) of `pred` against `soln` (n x B) over the rows `first + 1 : n` (src/metrics.jl:3-13)"
+function solution_errors_batch(pred::Matrix{Float64}, soln::Matrix{Float64}; first::Integer = 0, device::Integer = 0)
+    out = Matrix{Float64}(undef, 3, size(pred, 2))
+    GC.@preserve pred soln out check(ccall((:gmrf_field_errors_batch, libgmrf), Int32,
+        (Int32, Ptr{Cvoid}, Int64, Int64, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+        device, C_NULL, size(pred, 2), size(pred, 1), first, pred, soln, out))
+    return out
 end
 
 # Linear shallow-water SPDE (src/spdes/shallow_water.jl): element kernels of assemble_system! (:17-122) and the per-step

@@ -36,6 +36,13 @@ enum : int {
     TRI_B_UPPER = 8    // b(k,n) == 0 for k > n
 };
 
+// Where a call's outputs are (device memory, written in front of the sweep that reads it): samples[(p k + r) ld + j], mean[p n + j]
+struct GemmDirectOut {
+    double* samples;
+    double* mean;
+    int64_t ld, k;
+};
+
 struct GemmArgs {
     const double* A;
     const double* B;
@@ -65,6 +72,11 @@ struct GemmArgs {
     const double* tD = nullptr;
     int64_t ptA = 0, ptC = 0, ptD = 0;
     double tbeta = 0.0;
+    // Direct output of gemm_f64_dma's DOUT variant (dout != nullptr; one problem per z): the product's N columns are the dofs
+    // o_j0 .. of the caller's arrays, the first o_cols of them real (the rest padding, not written); o_n = dofs per problem
+    const GemmDirectOut* dout = nullptr;
+    int64_t o_j0 = 0, o_n = 0;
+    int o_cols = 0;
 };
 
 constexpr int GEMM_BM = 64;

@@ -44,7 +44,7 @@ constexpr size_t gemm_dma_lds_bytes(int stages) { return (size_t)stages * (BM + 
 // Tile order over the 1-D grid: XCD-grouped problems (blockIdx % 8 = group), inside a group longest K first.
 // lower_only == 1: triangular grid of BM x BN tiles that touch the lower triangle (M == N).
 template <int BM, int BN>
-__device__ __forceinline__ void gemm_dma_tile_order(const GemmArgs& g, int& bm, int& bn, int& z) {
+__device__ __forceinline__ void gemm_dma_tile_order(const GemmArgs& g, int bid, int gdim, int& bm, int& bn, int& z) {
     const int nx = g.N / BN, ny = g.M / BM;
     int tpp;
     if (g.lower_only == 1) {
@@ -52,9 +52,9 @@ __device__ __forceinline__ void gemm_dma_tile_order(const GemmArgs& g, int& bm, 
         if (BM >= BN) tpp = (BM / BN) * ny * (ny + 1) / 2;
         else tpp = 0;                                           // (not launched: see launch_gemm_dma)
     } else tpp = nx * ny;
-    const int nz = (int)gridDim.x / tpp;
+    const int nz = gdim / tpp;
     const int groups = (nz % 8 == 0) ? 8 : 1;
-    const int xg = (int)blockIdx.x % groups, q = (int)blockIdx.x / groups, nzg = nz / groups;
+    const int xg = bid % groups, q = bid / groups, nzg = nz / groups;
     int zq;
     if (g.lower_only == 1) {
         constexpr int R = BM / BN > 0 ? BM / BN : 1;            // column tiles per diagonal step
@@ -102,8 +102,17 @@ __device__ __forceinline__ void gemm_dma_tile_order(const GemmArgs& g, int& bm, 
 // factorisation's forward solve: gmrf_hip.hip, factor_blocks_range).  The tile that carries the tail of column tile bn is the one
 // whose K range is the tail's: the diagonal tile (bn, bn) of a triangular grid (with staircase bounds K starts at kst[bn] there,
 // as the tail's column does), else the last row tile.
-template <int BM, int BN, bool B_N, int STAGES, bool A_T = false, bool TAIL = false>
-__global__ __launch_bounds__(256, (BM + BN > 128) ? 3 : 4) void gemm_f64_dma(GemmArgs g) {
+//
+// DOUT (round 13, TAIL with B stored [k][n] and the tail in row M): the product that finishes x_i of the fused posterior's backward
+// sweep also writes the caller's arrays -- samples[(p k + r) ld + j] = tile row r + tail row for r < k, mean[p n + j] = tail row --
+// which used to be a pass of its own over the whole result panel (unpack_panel_mean).  Every row tile then sums the tail row
+// (the same sums in the same order: the same bits), the last one stores it; the tail's sum moves in front of the tile's stores.
+// Where the caller's arrays are (GemmDirectOut) is read from device memory: a captured sweep graph holds no pointer of a call.
+//
+// The body is a function of (descriptor, workgroup index, workgroups of the descriptor) so that one launch can run two
+// descriptors (gemm_f64_dma_grouped below); gemm_f64_dma itself is the body at (g, blockIdx.x, gridDim.x).
+template <int BM, int BN, bool B_N, int STAGES, bool A_T, bool TAIL, bool DOUT>
+__device__ __forceinline__ void gemm_dma_body(const GemmArgs& g, const int bid, const int gdim) {
     constexpr int BK = DMA_BK;
     constexpr int MI = BM / 32, NJ = BN / 32;                    // 16 x 16 MFMA tiles of a wave: MI x NJ
     constexpr int NA = BM / 32, NB = BN / 32;                    // LDS-DMA instructions per wave and K step (A, B)
@@ -111,9 +120,11 @@ __global__ __launch_bounds__(256, (BM + BN > 128) ? 3 : 4) void gemm_f64_dma(Gem
     static_assert(NJ % 2 == 0 || !B_N, "the [k][n] image pairs neighbouring column tiles");
     static_assert(MI % 2 == 0 || !A_T, "the [k][m] image pairs neighbouring row tiles");
     static_assert(!TAIL || (BM == 64 && BN == 64 && !A_T), "the tail row: 64 x 64 tiles");
+    static_assert(!DOUT || (TAIL && B_N), "direct output: the tail-row product on B [k][n]");
     int bm, bn, z;
-    gemm_dma_tile_order<BM, BN>(g, bm, bn, z);
-    const bool tail = TAIL && (g.lower_only == 1 ? bm == bn : bm == g.M / BM - 1);     // (workgroup-uniform)
+    gemm_dma_tile_order<BM, BN>(g, bid, gdim, bm, bn, z);
+    const bool tail_owner = TAIL && (g.lower_only == 1 ? bm == bn : bm == g.M / BM - 1);     // (workgroup-uniform)
+    const bool tail = DOUT || tail_owner;               // (DOUT: every row tile sums the tail row, its owner stores it)
     const int m0 = bm * BM, n0 = bn * BN;
     if (g.lower_only == 2 && n0 > m0 + BM - 1) return;
     const int zi = z % g.nb1, zp = z / g.nb1;
@@ -303,6 +314,34 @@ __global__ __launch_bounds__(256, (BM + BN > 128) ? 3 : 4) void gemm_f64_dma(Gem
     auto orow = [&](int i, int r) -> int64_t {          // row of register r of the wave's MFMA tile i
         return A_T ? m0 + wm + 32 * (i >> 1) + 2 * (lq + 4 * r) + (i & 1) : m0 + wm + i * 16 + lq + 4 * r;
     };
+    // (DOUT) the tail row first: its 8 partial sums per column through LDS as below, the finished row kept in LDS for every wave
+    v2d mu[NJ / 2 > 0 ? NJ / 2 : 1];
+    double* o_s = nullptr;
+    int64_t o_ld = 0;
+    int o_k = 0;
+    if constexpr (DOUT) {
+        const GemmDirectOut o = *g.dout;                         // (uniform: scalar loads)
+        o_ld = o.ld; o_k = (int)o.k;
+        o_s = o.samples + (int64_t)zp * o.k * o.ld + g.o_j0;
+        __syncthreads();                                         // every wave is done with the stages
+        *reinterpret_cast<v2d*>(gsm + (tkg * 4 + lq) * BN + wn + 2 * li) = tacc;
+        __syncthreads();
+        if (w == 0) {
+            double s = 0.0;
+#pragma unroll
+            for (int q = 0; q < 8; ++q) s += gsm[q * BN + lane];
+            double v = alpha * s;
+            if (beta != 0.0) v += beta * Dm[(int64_t)g.M * ldd + n0 + lane];
+            if (tail_owner) {
+                C[(int64_t)g.M * g.ldc + n0 + lane] = v;
+                if (n0 + lane < g.o_cols) o.mean[(int64_t)zp * g.o_n + g.o_j0 + n0 + lane] = v;
+            }
+            gsm[8 * BN + lane] = v;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int jp = 0; jp < NJ / 2; ++jp) mu[jp] = *reinterpret_cast<const v2d*>(gsm + 8 * BN + wn + jp * 32 + 2 * li);
+    }
     if (B_N) {
         v2d d[MI][4][NJ / 2 > 0 ? NJ / 2 : 1];
         if (beta != 0.0) {
@@ -323,6 +362,15 @@ __global__ __launch_bounds__(256, (BM + BN > 128) ? 3 : 4) void gemm_f64_dma(Gem
                     v2d v = (v2d){alpha * acc[i][2 * jp][r], alpha * acc[i][2 * jp + 1][r]};
                     if (beta != 0.0) { v.x += beta * d[i][r][jp].x; v.y += beta * d[i][r][jp].y; }
                     *reinterpret_cast<v2d*>(C + orow(i, r) * g.ldc + n0 + wn + jp * 32 + 2 * li) = v;
+                    if constexpr (DOUT) {
+                        // the caller's layout: sample row r of the problem is a column of ld doubles (8-byte stores: j0 may be odd)
+                        const int c = n0 + wn + jp * 32 + 2 * li;
+                        if (orow(i, r) < o_k) {
+                            double* sp = o_s + orow(i, r) * o_ld + c;
+                            if (c < g.o_cols) sp[0] = __dadd_rn(v.x, mu[jp].x);
+                            if (c + 1 < g.o_cols) sp[1] = __dadd_rn(v.y, mu[jp].y);
+                        }
+                    }
                 }
     } else {
         double d[MI][4][NJ];
@@ -346,7 +394,7 @@ __global__ __launch_bounds__(256, (BM + BN > 128) ? 3 : 4) void gemm_f64_dma(Gem
                     C[orow(i, r) * g.ldc + n0 + wn + j * 16 + li] = v;
                 }
     }
-    if constexpr (TAIL) {
+    if constexpr (TAIL && !DOUT) {
         if (tail) {
             // the 8 partial sums of a column (k pair groups x lq) through LDS, added by wave 0 in a fixed order
             __syncthreads();                                     // every wave is done with the stages
@@ -370,6 +418,29 @@ __global__ __launch_bounds__(256, (BM + BN > 128) ? 3 : 4) void gemm_f64_dma(Gem
             }
         }
     }
+}
+
+__global__ void set_direct_out(GemmDirectOut* o, double* samples, double* mean, int64_t ld, int64_t k) {
+    o->samples = samples; o->mean = mean; o->ld = ld; o->k = k;
+}
+
+template <int BM, int BN, bool B_N, int STAGES, bool A_T = false, bool TAIL = false, bool DOUT = false>
+__global__ __launch_bounds__(256, (BM + BN > 128) ? 3 : 4) void gemm_f64_dma(GemmArgs g) {
+    gemm_dma_body<BM, BN, B_N, STAGES, A_T, TAIL, DOUT>(g, (int)blockIdx.x, (int)gridDim.x);
+}
+
+// Two independent products in ONE launch (round 13, 64 x 64 tiles): workgroups [0, wg0) run descriptor g0, [wg0, wg0 + wg1) run g1,
+// each exactly as its own launch of wg0 / wg1 workgroups would (same body, same tile order inside the descriptor, same sums: the
+// same bits).  The descriptor and its B layout (bit 0 / bit 1 of b_n: g0 / g1 stored [k][n]) are chosen once per workgroup from
+// blockIdx.x -- wave-uniform -- in front of the K loop; the K loops themselves are the two bodies unchanged.  A multiple of 8 for
+// wg0 keeps g1's problems on the XCDs a launch of its own would put them on (a matter of locality only).
+template <int STAGES>
+__global__ __launch_bounds__(256, 4) void gemm_f64_dma_grouped(GemmArgs g0, GemmArgs g1, int wg0, int wg1, int b_n) {
+    const bool second = (int)blockIdx.x >= wg0;
+    const GemmArgs g = second ? g1 : g0;
+    const int bid = second ? (int)blockIdx.x - wg0 : (int)blockIdx.x, gdim = second ? wg1 : wg0;
+    if ((b_n >> (second ? 1 : 0)) & 1) gemm_dma_body<64, 64, true, STAGES, false, false, false>(g, bid, gdim);
+    else gemm_dma_body<64, 64, false, STAGES, false, false, false>(g, bid, gdim);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -437,11 +508,15 @@ inline hipError_t gemm_dma_init() {
 inline bool gemm_tail_ok(bool a_t, bool b_n, const GemmArgs& g, int batch) {
     if (a_t || gemm_uses_ll(g, batch) || gemm_dma_shape(false, g, batch) != 1) return false;
     if (g.lower_only && g.M != g.N) return false;                // (a triangular grid: the diagonal tiles carry the tail)
+    if (g.tC && g.dout) return false;
     if (g.tC) {
         // operands of its own: one problem per z, 16-byte aligned tail A (LDS-DMA of 16 bytes), even problem stride
         return g.nb1 == 1 && g.tA && ((uintptr_t)g.tA & 15) == 0 && (g.ptA & 1) == 0;
     }
-    if (!b_n || g.lower_only) return false;
+    if (!b_n || g.lower_only) return false;                      // (so a direct output, g.dout, is on B [k][n] with the tail in row M)
+    if (g.dout && g.nb1 != 1) return false;
+    // (a direct output: EVERY row tile sums the tail row, so the tail must not read C and must share every tile's K range)
+    if (g.dout && (g.beta != 0.0 || g.kb_m || g.kb_n || g.ke_n)) return false;
     // 32-bit byte offsets inside a problem's operand for the M + 1 rows (A: row M read with 64-bit addressing)
     return (int64_t)(g.M + 1) * g.ldc * 8 < ((int64_t)1 << 32) && (!g.D || (int64_t)(g.M + 1) * g.ldd * 8 < ((int64_t)1 << 32));
 }
@@ -462,11 +537,19 @@ inline bool gemm_try_dma_tail(hipStream_t st, bool a_t, bool b_n, const GemmArgs
         if (ev_start) hipExtLaunchKernelGGL((gemm_f64_dma<64, 64, BNAT, ST, false, true>), grid, block, lds, st, ev_start, ev_stop, 0, gs); \
         else hipLaunchKernelGGL((gemm_f64_dma<64, 64, BNAT, ST, false, true>), grid, block, lds, st, gs);                \
     } while (0)
-    if (gemm_dma_stages() == 3) {
+#define GMRF_DMA_TKO(ST)                                                                                                   \
+    do {                                                                                                                   \
+        if (ev_start) hipExtLaunchKernelGGL((gemm_f64_dma<64, 64, true, ST, false, true, true>), grid, block, lds, st, ev_start, ev_stop, 0, gs); \
+        else hipLaunchKernelGGL((gemm_f64_dma<64, 64, true, ST, false, true, true>), grid, block, lds, st, gs);          \
+    } while (0)
+    if (g.dout) {
+        if (gemm_dma_stages() == 3) GMRF_DMA_TKO(3); else GMRF_DMA_TKO(2);
+    } else if (gemm_dma_stages() == 3) {
         if (b_n) GMRF_DMA_TK(true, 3); else GMRF_DMA_TK(false, 3);
     } else {
         if (b_n) GMRF_DMA_TK(true, 2); else GMRF_DMA_TK(false, 2);
     }
+#undef GMRF_DMA_TKO
 #undef GMRF_DMA_TK
     *err = hipGetLastError();
     return true;
@@ -509,6 +592,45 @@ inline bool gemm_try_dma(hipStream_t st, bool a_t, bool b_n, const GemmArgs& g, 
     else GMRF_DMA_GO(64, 64);
 #undef GMRF_DMA_K
 #undef GMRF_DMA_GO
+    *err = hipGetLastError();
+    return true;
+}
+
+// Two products as ONE launch of gemm_f64_dma_grouped (64 x 64 tiles): may they?  Both on A [m][k], without a tail, each a launch
+// the 64 x 64 LDS-DMA kernel takes on its own.  (The kernels launch_gemm would pick for either -- the 32 x 32 one for a handful of
+// problems, the wide tiles -- sum every output element in the same order: grouping changes no bit.)
+inline bool gemm_grouped_ok(const GemmArgs& g0, const GemmArgs& g1, int batch) {
+    if (gemm_dma_policy() == 0 || g0.tC || g1.tC || g0.dout || g1.dout) return false;
+    if (g0.lower_only && g0.M != g0.N) return false;             // (an early-exit grid: not needed here)
+    if (g1.lower_only && g1.M != g1.N) return false;
+    return gemm_dma_shape(false, g0, batch) != 0 && gemm_dma_shape(false, g1, batch) != 0;
+}
+inline int64_t gemm_dma_grid64(const GemmArgs& g, int batch) {
+    const int64_t nx = g.N / 64, ny = g.M / 64;
+    return ((g.lower_only && g.M == g.N) ? ny * (ny + 1) / 2 : nx * ny) * batch;
+}
+inline bool gemm_try_dma_grouped(hipStream_t st, bool b_n0, const GemmArgs& g0, bool b_n1, const GemmArgs& g1, int batch,
+                                 hipEvent_t ev_start, hipEvent_t ev_stop, hipError_t* err) {
+    if (!gemm_grouped_ok(g0, g1, batch)) return false;
+    static const bool asc_off = [] { const char* e = getenv("GMRF_GEMM_G2_ORDER"); return e && atoi(e) == 0; }();   // tuning aid
+    GemmArgs gs[2] = {g0, g1};
+    for (GemmArgs& g : gs) {                                     // (as gemm_try_dma sets a launch of its own up)
+        const bool tri_grid = g.lower_only && g.M == g.N;
+        g.lower_only = tri_grid ? 1 : 0;
+        if (tri_grid && (g.kb_m || g.kb_n) && !asc_off) g.tri |= DMA_ROWS_ASCENDING;
+    }
+    const int wg0 = (int)gemm_dma_grid64(g0, batch), wg1 = (int)gemm_dma_grid64(g1, batch);
+    const int bn = (b_n0 ? 1 : 0) | (b_n1 ? 2 : 0);
+    const dim3 grid((unsigned)(wg0 + wg1)), block(256);
+    const int stages = gemm_dma_stages();
+    const size_t lds = gemm_dma_lds_bytes<64, 64>(stages);
+#define GMRF_DMA_GK(ST)                                                                                                   \
+    do {                                                                                                                  \
+        if (ev_start) hipExtLaunchKernelGGL((gemm_f64_dma_grouped<ST>), grid, block, lds, st, ev_start, ev_stop, 0, gs[0], gs[1], wg0, wg1, bn); \
+        else hipLaunchKernelGGL((gemm_f64_dma_grouped<ST>), grid, block, lds, st, gs[0], gs[1], wg0, wg1, bn);           \
+    } while (0)
+    if (stages == 3) GMRF_DMA_GK(3); else GMRF_DMA_GK(2);
+#undef GMRF_DMA_GK
     *err = hipGetLastError();
     return true;
 }

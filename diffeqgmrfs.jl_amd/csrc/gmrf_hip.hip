@@ -232,6 +232,8 @@ struct gmrf_handle {
     const double* fy_for = nullptr;    // the current factor left y = L^-1 fy_for in d_fy (nullptr: none)
     bool fwd_run = false;              // the factorisation being enqueued carries the forward solve (factor_fwd_ok)
     bool no_factor_fwd = false;        // set_eager bit 19: never (comparison)
+    bool no_grouped_gemm = false;      // set_eager bit 20: the panel chain's two independent 128^3 products stay two launches (comparison)
+    GemmDirectOut* d_dout = nullptr;   // where the fused posterior's last products write the caller's mean / samples (posterior_fused_ok allocates)
     double* d_ft = nullptr;            // [B][bsp]: t = b_i - C_i y_{i-1} of the block being factored, updated panel by panel
     double* d_fy = nullptr;            // [B][n_pad]: y, laid out as a k = 1 panel (what fill_normals_panel reads row kp from)
     int64_t fy_elems = 0;
@@ -399,12 +401,33 @@ static void prof_collect(gmrf_handle* h) {
 
 // ------------------------------------------------------------------------------------ helpers
 // A tail row on operands of its own (GemmArgs::tA / tC / tD): tC = beta tD + alpha tA b, per problem strides pA / pC / pD
+// C == nullptr: the tail is row M of the product's own operands.  out (then; B [k][n]): the product also writes the caller's mean and
+// samples (gemm_f64_dma's DOUT) -- its columns are the dofs j0 .. of a problem, the first `cols` of them real
 struct GemmTail {
     const double* A; int64_t pA;
     double* C; int64_t pC;
     const double* D; int64_t pD;
     double beta;
+    const GemmDirectOut* out = nullptr;
+    int64_t j0 = 0;
+    int cols = 0;
 };
+
+// the flops gemm() books for one product of `nprob` problems (a triangular grid and a triangular operand by their 64-wide tiles)
+static inline double gemm_flops(int M, int N, int K, int tri, int lower_only, double nprob) {
+    double flops = 2.0 * M * N * (double)K * nprob;
+    if (lower_only) flops *= 0.5 * (1.0 + 64.0 / std::max(M, 64));
+    if (tri) flops *= 0.5 * (1.0 + 64.0 / std::max(K, 64));
+    return flops;
+}
+// the row of gemm_by_shape with this key (added at its first launch)
+static int gemm_shape_row(gmrf_handle* h, const int64_t (&key)[8]) {
+    for (size_t i = 0; i < h->gemm_shapes.size(); ++i)
+        if (!memcmp(h->gemm_shapes[i].key, key, sizeof(key))) return (int)i;
+    GemmShapeStat st; memcpy(st.key, key, sizeof(key));
+    h->gemm_shapes.push_back(st);
+    return (int)h->gemm_shapes.size() - 1;
+}
 
 static gmrf_status gemm(gmrf_handle* h, bool a_t, bool b_n, int M, int N, int K, int tri, int lower_only,
                         double alpha, const double* A, int64_t lda, const double* B, int64_t ldb,
@@ -415,7 +438,8 @@ static gmrf_status gemm(gmrf_handle* h, bool a_t, bool b_n, int M, int N, int K,
                         const GemmTail* gt = nullptr) {
     GemmArgs g;
     if (gt) {
-        g.tA = gt->A; g.ptA = gt->pA; g.tC = gt->C; g.ptC = gt->pC; g.tD = gt->D; g.ptD = gt->pD; g.tbeta = gt->beta;
+        if (gt->C) { g.tA = gt->A; g.ptA = gt->pA; g.tC = gt->C; g.ptC = gt->pC; g.tD = gt->D; g.ptD = gt->pD; g.tbeta = gt->beta; }
+        g.dout = gt->out; g.o_j0 = gt->j0; g.o_cols = gt->cols; g.o_n = h->n;
         tail = true;
     }
     g.kb_m = kb_m; g.kb_n = kb_n; g.ke_n = ke_n;
@@ -426,9 +450,7 @@ static gmrf_status gemm(gmrf_handle* h, bool a_t, bool b_n, int M, int N, int K,
     g.pA = pA; g.pB = pB; g.pC = pC; g.nb1 = batch;
     g.M = M; g.N = N; g.K = K; g.tri = tri; g.lower_only = lower_only;
     g.alpha = alpha; g.beta = beta; g.stamps = nullptr;
-    double flops = 2.0 * M * N * (double)K * batch * (double)h->B;
-    if (lower_only) flops *= 0.5 * (1.0 + 64.0 / std::max(M, 64));
-    if (tri) flops *= 0.5 * (1.0 + 64.0 / std::max(K, 64));
+    double flops = gemm_flops(M, N, K, tri, lower_only, batch * (double)h->B);
     if (tail) {
         // one more row, row M of A / C (gemm_f64_dma's TAIL): the kernel the M rows alone would get, or not at all.  A dry run
         // (tail_probe) only asks whether every product of a sweep qualifies.
@@ -446,12 +468,7 @@ static gmrf_status gemm(gmrf_handle* h, bool a_t, bool b_n, int M, int N, int K,
             p.kind = pclass; p.work = pwork >= 0.0 ? pwork : flops;
             p.a = ev_get(h); p.b = ev_get(h);
             const int64_t key[8] = {pclass, M + 1, N, K, tri, lower_only, batch * h->B, (kb_m || kb_n || ke_n) ? 1 : 0};
-            for (size_t i = 0; i < h->gemm_shapes.size() && p.shape < 0; ++i)
-                if (!memcmp(h->gemm_shapes[i].key, key, sizeof(key))) p.shape = (int)i;
-            if (p.shape < 0) {
-                GemmShapeStat st; memcpy(st.key, key, sizeof(key));
-                h->gemm_shapes.push_back(st); p.shape = (int)h->gemm_shapes.size() - 1;
-            }
+            p.shape = gemm_shape_row(h, key);
             (void)gemm_try_dma_tail(h->gemm_stream ? h->gemm_stream : h->stream, a_t, b_n, g, batch * (int)h->B, p.a, p.b, &e);
             HIPCHK(e);
             h->events.push_back(p);
@@ -475,17 +492,62 @@ static gmrf_status gemm(gmrf_handle* h, bool a_t, bool b_n, int M, int N, int K,
         p.kind = pclass; p.work = pwork >= 0.0 ? pwork : flops;
         p.a = ev_get(h); p.b = ev_get(h);
         const int64_t key[8] = {pclass, M, N, K, tri, lower_only, batch * h->B, (kb_m || kb_n || ke_n) ? 1 : 0};
-        for (size_t i = 0; i < h->gemm_shapes.size() && p.shape < 0; ++i)
-            if (!memcmp(h->gemm_shapes[i].key, key, sizeof(key))) p.shape = (int)i;
-        if (p.shape < 0) {
-            GemmShapeStat st; memcpy(st.key, key, sizeof(key));
-            h->gemm_shapes.push_back(st); p.shape = (int)h->gemm_shapes.size() - 1;
-        }
+        p.shape = gemm_shape_row(h, key);
         HIPCHK(launch_gemm(h->gemm_stream ? h->gemm_stream : h->stream, a_t, b_n, g, batch * (int)h->B, p.a, p.b));
         h->events.push_back(p);
         return GMRF_OK;
     }
     HIPCHK(launch_gemm(h->gemm_stream ? h->gemm_stream : h->stream, a_t, b_n, g, batch * (int)h->B));
+    return GMRF_OK;
+}
+
+// One of two independent products (both on A [m][k], one problem per z) that gemm_pair runs as ONE launch
+struct GemmOne {
+    bool b_n; int M, N, K, tri, lower_only;
+    double alpha; const double* A; int64_t lda; const double* B; int64_t ldb; double beta; double* C; int64_t ldc;
+    int64_t pA, pB, pC;
+    double pwork;                      // work to book (< 0: the product's flops)
+};
+static gmrf_status gemm_one(gmrf_handle* h, const GemmOne& q) {
+    return gemm(h, false, q.b_n, q.M, q.N, q.K, q.tri, q.lower_only, q.alpha, q.A, q.lda, q.B, q.ldb, q.beta, q.C, q.ldc, q.pA, q.pB, q.pC,
+                1, 0, 0, 0, nullptr, 0, 0, 0, q.pwork);
+}
+// Two products neither of which reads what the other writes, as one launch of gemm_f64_dma_grouped where both qualify (and set_eager
+// bit 20 does not keep them apart), else one after the other.  Statistics: ONE launch of class 14 (the LDS-DMA kernel; the grouped
+// symbol has no class of its own) with both products' work, and one gemm_by_shape row: M = both products' rows, tri / lower_only =
+// the first product's flags | the second's << 8.
+static gmrf_status gemm_pair(gmrf_handle* h, const GemmOne& q0, const GemmOne& q1) {
+    GemmArgs g[2];
+    const GemmOne* q[2] = {&q0, &q1};
+    double work[2];
+    for (int i = 0; i < 2; ++i) {
+        GemmArgs& a = g[i];
+        a.A = q[i]->A; a.B = q[i]->B; a.C = q[i]->C; a.lda = q[i]->lda; a.ldb = q[i]->ldb; a.ldc = q[i]->ldc;
+        a.strideA = a.strideB = a.strideC = 0;
+        a.pA = q[i]->pA; a.pB = q[i]->pB; a.pC = q[i]->pC; a.nb1 = 1;
+        a.M = q[i]->M; a.N = q[i]->N; a.K = q[i]->K; a.tri = q[i]->tri; a.lower_only = q[i]->lower_only;
+        a.alpha = q[i]->alpha; a.beta = q[i]->beta; a.D = nullptr; a.ldd = 0; a.pD = 0; a.stamps = nullptr;
+        work[i] = q[i]->pwork >= 0.0 ? q[i]->pwork : gemm_flops(a.M, a.N, a.K, a.tri, a.lower_only, (double)h->B);
+    }
+    if (h->no_grouped_gemm || !gemm_grouped_ok(g[0], g[1], (int)h->B)) {
+        GCHK(gemm_one(h, q0));
+        return gemm_one(h, q1);
+    }
+    hipStream_t st = h->gemm_stream ? h->gemm_stream : h->stream;
+    hipError_t e = hipSuccess;
+    if (h->profiling > 0) {
+        EvPair p;
+        p.kind = 14; p.work = work[0] + work[1];
+        p.a = ev_get(h); p.b = ev_get(h);
+        const int64_t key[8] = {14, q0.M + q1.M, q0.N, q0.K, q0.tri | (q1.tri << 8), q0.lower_only | (q1.lower_only << 8), h->B, 0};
+        p.shape = gemm_shape_row(h, key);
+        (void)gemm_try_dma_grouped(st, q0.b_n, g[0], q1.b_n, g[1], (int)h->B, p.a, p.b, &e);
+        HIPCHK(e);
+        h->events.push_back(p);
+        return GMRF_OK;
+    }
+    (void)gemm_try_dma_grouped(st, q0.b_n, g[0], q1.b_n, g[1], (int)h->B, nullptr, nullptr, &e);
+    HIPCHK(e);
     return GMRF_OK;
 }
 
@@ -1273,20 +1335,25 @@ static gmrf_status potrf_block(gmrf_handle* h, double* S, double* L, double* X, 
                 GCHK(launch_persist(h, S + oa * ld + oa, L + oa * ld + oa, X + oa * ld + oa, 4, 0, 4, 2, blk_id, fl));
             } else {
                 GCHK(diag128(j));
-                // The four 128^3 products of the panel -- L_BA = S_BA X_A^T, S_BB -= L_BA L_BA^T before the second diagonal block,
-                // X_BA = -X_B (L_BA X_A) after it -- are four GEMM launches of 256 workgroups (13 % of a step's GEMM time at 20.7 TF/s).
+                // The four 128^3 products of the panel are three GEMM launches: L_BA = S_BA X_A^T (256 workgroups at batch 64); then
+                // S_BB -= L_BA L_BA^T and T = L_BA X_A together (192 + 256), both in front of the second diagonal block; and
+                // X_BA = -X_B T (256) after it.  Until round 13 they were four launches, T behind the second diagonal block
+                // (13 % of a step's GEMM time at 20.7 TF/s).
                 // (Round 4 built and measured the alternative, ONE workgroup per problem in two launches, bitwise the same results:
                 //  the time-weighted GEMM fraction rose to 0.66 and the job got SLOWER, 45.6 k against 48.1 k solves/s -- twelve
-                //  dependent 64^3 products take one CU 57 us, the four launches 39 us.  Removed in round 5.)
-                // L_BA = S_BA X_A^T (X_A lower triangular, stored [n][k]);  S_BB -= L_BA L_BA^T (lower tiles)
+                //  dependent 64^3 products take one CU 57 us, the four launches of then 39 us.  Removed in round 5.)
+                // L_BA = S_BA X_A^T (X_A lower triangular, stored [n][k])
                 GCHK(gemm(h, false, false, 128, 128, 128, TRI_B_UPPER, 0, 1.0, S + ob * ld + oa, ld, X + oa * ld + oa, ld, 0.0, L + ob * ld + oa, ld,
                           sa.pS, sa.pX, sa.pL, 1, 0, 0, 0, nullptr, 0, 0, 0, 2.0 * t3 * 3.0 * 2.0 * nb));
-                GCHK(gemm(h, false, false, 128, 128, 128, 0, 1, -1.0, L + ob * ld + oa, ld, L + ob * ld + oa, ld, 1.0, S + ob * ld + ob, ld,
-                          sa.pL, sa.pL, sa.pS, 1, 0, 0, 0, nullptr, 0, 0, 0, 2.0 * t3 * 2.0 * 3.0 * nb));
+                // S_BB -= L_BA L_BA^T (lower tiles), and T = L_BA X_A -- the first half of X_BA = -X_B (L_BA X_A), the level-128 doubling step of this pair (T is the
+                // work block doubling_levels uses) -- reads L_BA and X_A only, as the update of S_BB reads L_BA only: ONE launch of
+                // 192 + 256 workgroups per 64 problems in front of the second diagonal block instead of a launch on either side of it
+                GCHK(gemm_pair(h,
+                               GemmOne{false, 128, 128, 128, 0, 1, -1.0, L + ob * ld + oa, ld, L + ob * ld + oa, ld, 1.0, S + ob * ld + ob, ld,
+                                       sa.pL, sa.pL, sa.pS, 2.0 * t3 * 2.0 * 3.0 * nb},
+                               GemmOne{true, 128, 128, 128, TRI_B_LOWER, 0, 1.0, L + ob * ld + oa, ld, X + oa * ld + oa, ld, 0.0, T + ob * ld + oa, ld,
+                                       sa.pL, sa.pX, pW, -1.0}));
                 GCHK(diag128(j + 2));
-                // X_BA = -X_B (L_BA X_A): the level-128 doubling step of this pair (T is the work block doubling_levels uses)
-                GCHK(gemm(h, false, true, 128, 128, 128, TRI_B_LOWER, 0, 1.0, L + ob * ld + oa, ld, X + oa * ld + oa, ld, 0.0, T + ob * ld + oa, ld,
-                          sa.pL, sa.pX, pW));
                 GCHK(gemm(h, false, true, 128, 128, 128, TRI_A_LOWER, 0, -1.0, X + ob * ld + ob, ld, T + ob * ld + oa, ld, 0.0, X + ob * ld + oa, ld,
                           sa.pX, pW, sa.pX));
             }
@@ -1948,7 +2015,9 @@ static gmrf_status sweep_guarded(gmrf_handle* h, std::initializer_list<SweepIo> 
 
 // tail (backward, via the GEMM only): the panels hold kp + 1 rows per problem and row kp -- the mean's right-hand side -- is swept
 // as the tail row of every product (gemm_f64_dma's TAIL): the mean's backward sweep and the samples' in one pass over the factor.
-static gmrf_status sweep_launches(gmrf_handle* h, bool backward, int kp, double* Pin, double* Yout, bool tail = false) {
+// dout (with tail): the products that finish x_i also write the caller's mean and samples (gemm_f64_dma's DOUT)
+static gmrf_status sweep_launches(gmrf_handle* h, bool backward, int kp, double* Pin, double* Yout, bool tail = false,
+                                  const GemmDirectOut* dout = nullptr) {
     if (!tail && sweep_persist_ok(h, kp)) return launch_sweep_persist(h, backward, kp, Pin, Yout);
     const int bsp = (int)h->bsp;
     const int64_t ld = bsp, bstride = (int64_t)bsp * bsp, npad = h->n_pad;
@@ -1973,6 +2042,7 @@ static gmrf_status sweep_launches(gmrf_handle* h, bool backward, int kp, double*
     // the batch gives it enough 64 x 64 tiles; a lone problem stays on sweep_mm (256 workgroups)
     const bool via_gemm = (kp % 64 == 0) && !h->sweep_no_gemm && (int64_t)nprob * (bsp / 64) * (kp / 64) >= 128;
     if (tail && (!via_gemm || !backward)) return bad_shape("internal: the tail row needs the backward sweep on the GEMM");
+    if (dout && !tail) return bad_shape("internal: direct output needs the tail-row sweep");
     for (int64_t step = 0; step < N; ++step) {
         const int64_t i = backward ? (N - 1 - step) : step;
         double* rhs = Pin + i * bsp;               // the input panel is consumed: P_i becomes P_i - C y_prev
@@ -2001,6 +2071,8 @@ static gmrf_status sweep_launches(gmrf_handle* h, bool backward, int kp, double*
         // y_i = Linv_i T   /   x_i = Linv_i^T T
         const double* X = h->d_Linv + i * bstride;
         double* yout = Yout + i * bsp;
+        // (dout) columns c of a product that starts at column `first` of the block are the dofs i bs + first + c, real while first + c < bs
+        auto direct = [&](int first) { return GemmTail{nullptr, 0, nullptr, 0, nullptr, 0, 0.0, dout, i * h->bs + first, (int)h->bs - first}; };
         if (h->xsplit > 0) {
             // split representation: [X_aa 0; L_ba X_bb] in the block's storage.  forward: y_a = X_aa t_a, t_b -= L_ba y_a,
             // y_b = X_bb t_b;  backward: x_b = X_bb^T t_b, t_a -= L_ba^T x_b, x_a = X_aa^T t_a.  Same bytes, same flops.
@@ -2012,12 +2084,15 @@ static gmrf_status sweep_launches(gmrf_handle* h, bool backward, int kp, double*
                 if (via_gemm) {
                     // (the defaults up to the tail flag)
                     constexpr int64_t z0 = 0;
+                    const GemmTail da = direct(0), db = direct(p);
                     if (which == 0)
                         GCHK(gemm(h, false, backward, kp, p, p, backward ? TRI_B_LOWER : TRI_B_UPPER, 0, 1.0, rhs, npad, X, ld, 0.0, yout, npad,
-                                  pPanel, pX, pPanel, 1, z0, z0, z0, nullptr, z0, z0, 0, -1.0, nullptr, nullptr, nullptr, tail));
+                                  pPanel, pX, pPanel, 1, z0, z0, z0, nullptr, z0, z0, 0, -1.0, nullptr, nullptr, nullptr, tail,
+                                  dout ? &da : nullptr));
                     else if (which == 2)
                         GCHK(gemm(h, false, backward, kp, q, q, backward ? TRI_B_LOWER : TRI_B_UPPER, 0, 1.0, rhs + p, npad, Xbb, ld, 0.0,
-                                  yout + p, npad, pPanel, pX, pPanel, 1, z0, z0, z0, nullptr, z0, z0, 0, -1.0, nullptr, nullptr, nullptr, tail));
+                                  yout + p, npad, pPanel, pX, pPanel, 1, z0, z0, z0, nullptr, z0, z0, 0, -1.0, nullptr, nullptr, nullptr, tail,
+                                  dout ? &db : nullptr));
                     else if (!backward)
                         GCHK(gemm(h, false, false, kp, q, p, 0, 0, -1.0, yout, npad, Lba, ld, 1.0, rhs + p, npad, pPanel, pX, pPanel));
                     else
@@ -2036,8 +2111,9 @@ static gmrf_status sweep_launches(gmrf_handle* h, bool backward, int kp, double*
             }
         } else if (via_gemm) {
             // forward: Linv stored [m][k], zero for k > m; backward: Linv^T, stored [k][m], zero for k < m
+            const GemmTail da = direct(0);
             GCHK(gemm(h, false, backward, kp, bsp, bsp, backward ? TRI_B_LOWER : TRI_B_UPPER, 0, 1.0, rhs, npad, X, ld, 0.0,
-                      yout, npad, pPanel, pX, pPanel, 1, 0, 0, 0, nullptr, 0, 0, 0, -1.0, nullptr, nullptr, nullptr, tail));
+                      yout, npad, pPanel, pX, pPanel, 1, 0, 0, 0, nullptr, 0, 0, 0, -1.0, nullptr, nullptr, nullptr, tail, dout ? &da : nullptr));
         } else {
             s.Mat = X; s.ld = ld; s.Xin = rhs; s.ldx = npad; s.Bin = nullptr; s.ldb = 0; s.Out = yout; s.ldo = npad;
             s.rows = bsp; s.kdim = bsp; s.sub = 0;
@@ -2056,7 +2132,7 @@ constexpr int SWEEP_BACKWARD_YP = 3, SWEEP_BACKWARD_TAIL = 4;
 static gmrf_status run_sweeps(gmrf_handle* h, int mode, int kp) {
     auto body = [&]() -> gmrf_status {
         if (mode == GMRF_SOLVE_FORWARD) return sweep_launches(h, false, kp, h->d_P, h->d_Y);
-        if (mode == SWEEP_BACKWARD_TAIL) return sweep_launches(h, true, kp, h->d_P, h->d_Y, true);
+        if (mode == SWEEP_BACKWARD_TAIL) return sweep_launches(h, true, kp, h->d_P, h->d_Y, true, h->d_dout);
         if (mode == SWEEP_BACKWARD_YP) return sweep_launches(h, true, kp, h->d_Y, h->d_P);
         if (mode == GMRF_SOLVE_BACKWARD) return sweep_launches(h, true, kp, h->d_P, h->d_Y);
         GCHK(sweep_launches(h, false, kp, h->d_P, h->d_Y));
@@ -2200,7 +2276,7 @@ gmrf_status gmrf_bt_destroy(gmrf_handle* h) {
     free_dev(h->d_S); free_dev(h->d_B); free_dev(h->d_T); free_dev(h->d_W);
     free_dev(h->d_sweep_flags); free_dev(h->d_Tsw); free_dev(h->d_P2); free_dev(h->d_Y2); free_dev(h->d_T2);
     if (h->h_sweep_abort) { (void)hipHostFree(h->h_sweep_abort); h->h_sweep_abort = nullptr; }
-    free_dev(h->d_info); free_dev(h->d_logdet); free_dev(h->d_pflags); free_dev(h->d_kbx); free_dev(h->d_V);
+    free_dev(h->d_dout); free_dev(h->d_info); free_dev(h->d_logdet); free_dev(h->d_pflags); free_dev(h->d_kbx); free_dev(h->d_V);
     free_dev(h->d_P); free_dev(h->d_Y); free_dev(h->d_Tp);
     free_dev(h->d_stage); h->mean_arena.release(); free_dev(h->d_acc);
     free_dev(h->d_ft); free_dev(h->d_fy);
@@ -2263,6 +2339,7 @@ gmrf_status gmrf_bt_set_eager(gmrf_handle* h, int32_t eager) {
     if (((eager & 131072) != 0) != h->no_scatter_fold) { destroy_graphs(h); h->no_scatter_fold = (eager & 131072) != 0; }
     h->no_fused_posterior = (eager & 262144) != 0;
     h->no_factor_fwd = (eager & 524288) != 0;
+    if (((eager & 1048576) != 0) != h->no_grouped_gemm) { destroy_graphs(h); h->no_grouped_gemm = (eager & 1048576) != 0; }
     if (eager != h->eager_bits) h->fy_for = nullptr;         // (a factor of other settings: no y taken for granted)
     h->eager = (eager & 1) != 0;
     h->eager_bits = eager;
@@ -3202,8 +3279,9 @@ static bool posterior_fused_ok(gmrf_handle* h, int64_t k, bool dev_all) {
     if (kp % 64 != 0 || (int64_t)h->B * (h->bsp / 64) * (kp / 64) < 128) return false;
     if ((int64_t)(kp + 1) * h->n_pad * 8 >= ((int64_t)1 << 32)) return false;
     if (ensure_panels(h, kp + 1) != GMRF_OK) return false;
+    if (!h->d_dout && hipMalloc(&h->d_dout, sizeof(GemmDirectOut)) != hipSuccess) { (void)hipGetLastError(); return false; }
     h->tail_probe = true; h->tail_refused = false;
-    const gmrf_status st = sweep_launches(h, true, kp, h->d_P, h->d_Y, true);
+    const gmrf_status st = sweep_launches(h, true, kp, h->d_P, h->d_Y, true, h->d_dout);
     h->tail_probe = false;
     return st == GMRF_OK && !h->tail_refused;
 }
@@ -3231,13 +3309,11 @@ static gmrf_status posterior_fused(gmrf_handle* h, const double* b, uint64_t see
                            have_y ? h->d_fy : h->d_Y, h->n_pad);
         HIPCHK(hipGetLastError());
     }
+    // (round 13) the products that finish x_i write mean and samples themselves: where to is handed over in device memory (the
+    // sweep's captured graph holds no pointer of a call), by a one-thread launch in front of the sweep
+    hipLaunchKernelGGL(set_direct_out, dim3(1), dim3(1), 0, h->stream, h->d_dout, samples, mean, ld, k);
+    HIPCHK(hipGetLastError());
     GCHK(run_sweeps(h, SWEEP_BACKWARD_TAIL, kp));
-    {
-        const int64_t total = h->n * (k + 1);
-        hipLaunchKernelGGL(unpack_panel_mean, dim3((unsigned)((total + 255) / 256), (unsigned)h->B), dim3(256), 0, h->stream, h->d_Y,
-                           h->n_pad, samples, ld, mean, (int)h->bs, (int)h->bsp, h->n, (int)k, kp);
-        HIPCHK(hipGetLastError());
-    }
     HIPCHK(hipEventRecord(h->ev1, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     if (h->profiling) prof_collect(h);
@@ -6313,6 +6389,59 @@ gmrf_status gmrf_test_gemm(int32_t device, int64_t M, int64_t N, int64_t K, int3
     HIPCHK(hipMemcpy(g_tile_stamps, dst, 16, hipMemcpyDeviceToHost));
     hipFree(dst);
     hipFree(dA); hipFree(dB); hipFree(dC);
+    return GMRF_OK;
+}
+
+// Two products C_i = beta_i C_i + alpha_i A_i b_i of `batch` problems each (host arrays, contiguous per problem: A [M][K], B [K][N] if
+// b_n else [N][K], C [M][N]) on the 64 x 64 LDS-DMA kernel: grouped != 0 as ONE launch of gemm_f64_dma_grouped, else as two launches.
+// desc: M, N, K, b_n, tri, lower_only of product 0, then of product 1; ab: alpha_0, beta_0, alpha_1, beta_1.
+gmrf_status gmrf_test_gemm_pair(int32_t device, int32_t batch, int32_t grouped, const int64_t* desc, const double* ab,
+                                const double* A0, const double* B0, double* C0, const double* A1, const double* B1, double* C1) {
+    if (!desc || !ab || !A0 || !B0 || !C0 || !A1 || !B1 || !C1 || batch < 1) return bad_shape("gemm pair test: null pointer / batch");
+    HIPCHK(hipSetDevice(device));
+    HIPCHK(gemm_init());
+    HIPCHK(gemm_dma_init());
+    const double* hA[2] = {A0, A1};
+    const double* hB[2] = {B0, B1};
+    double* hC[2] = {C0, C1};
+    double *dA[2] = {nullptr, nullptr}, *dB[2] = {nullptr, nullptr}, *dC[2] = {nullptr, nullptr};
+    GemmArgs g[2];
+    bool b_n[2];
+    auto drop = [&]() { for (int i = 0; i < 2; ++i) { free_dev(dA[i]); free_dev(dB[i]); free_dev(dC[i]); } };
+    for (int i = 0; i < 2; ++i) {
+        const int64_t M = desc[6 * i], N = desc[6 * i + 1], K = desc[6 * i + 2];
+        b_n[i] = desc[6 * i + 3] != 0;
+        if (M <= 0 || N <= 0 || K <= 0 || M % 64 || N % 64 || K % 16) { drop(); return bad_shape("gemm pair test sizes"); }
+        const size_t na = sizeof(double) * M * K * batch, nb = sizeof(double) * K * N * batch, nc = sizeof(double) * M * N * batch;
+        hipError_t e = hipMalloc(&dA[i], na);
+        if (e == hipSuccess) e = hipMalloc(&dB[i], nb);
+        if (e == hipSuccess) e = hipMalloc(&dC[i], nc);
+        if (e == hipSuccess) e = hipMemcpy(dA[i], hA[i], na, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(dB[i], hB[i], nb, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(dC[i], hC[i], nc, hipMemcpyHostToDevice);
+        if (e != hipSuccess) { drop(); HIPCHK(e); }
+        GemmArgs& a = g[i];
+        a.A = dA[i]; a.B = dB[i]; a.C = dC[i]; a.lda = K; a.ldb = b_n[i] ? N : K; a.ldc = N;
+        a.strideA = a.strideB = a.strideC = 0;
+        a.pA = M * K; a.pB = K * N; a.pC = M * N; a.nb1 = 1;
+        a.M = (int)M; a.N = (int)N; a.K = (int)K; a.tri = (int)desc[6 * i + 4]; a.lower_only = (int)desc[6 * i + 5];
+        a.alpha = ab[2 * i]; a.beta = ab[2 * i + 1]; a.D = nullptr; a.ldd = 0; a.pD = 0; a.stamps = nullptr;
+    }
+    const int saved = gemm_big_policy(), saved_ll = gemm_ll_policy(), saved_dma = gemm_dma_policy(), saved_force = gemm_dma_force();
+    gemm_big_policy() = 2; gemm_ll_policy() = 2; gemm_dma_policy() = 2; gemm_dma_force() = 1;
+    hipError_t le = hipSuccess;
+    bool ok = true;
+    if (grouped) ok = gemm_try_dma_grouped(nullptr, b_n[0], g[0], b_n[1], g[1], batch, nullptr, nullptr, &le);
+    else {
+        for (int i = 0; i < 2 && ok && le == hipSuccess; ++i) ok = gemm_try_dma(nullptr, false, b_n[i], g[i], batch, nullptr, nullptr, &le);
+    }
+    gemm_big_policy() = saved; gemm_ll_policy() = saved_ll; gemm_dma_policy() = saved_dma; gemm_dma_force() = saved_force;
+    if (!ok) { drop(); return bad_shape("gemm pair test: not a pair of LDS-DMA products"); }
+    if (le == hipSuccess) le = hipDeviceSynchronize();
+    for (int i = 0; i < 2 && le == hipSuccess; ++i)
+        le = hipMemcpy(hC[i], dC[i], sizeof(double) * g[i].M * g[i].N * batch, hipMemcpyDeviceToHost);
+    drop();
+    HIPCHK(le);
     return GMRF_OK;
 }
 

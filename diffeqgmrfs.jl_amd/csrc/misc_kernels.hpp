@@ -164,21 +164,6 @@ __global__ void fill_normals_panel(double* __restrict__ P, int64_t n_pad, int bs
     P[(int64_t)blockIdx.y * rows * n_pad + idx] = v;
 }
 
-// A panel of kp + 1 rows per problem (fill_normals_panel with yrow) after the fused backward sweep: row kp is the mean, rows
-// [0, k) are L^-T z.  mean_out[p][j] = row kp; samples out (column-major, problem p's k columns after problem p - 1's) = row r +
-// row kp.  One thread per (row r <= k, dof j) of problem blockIdx.y; row k stands for row kp.
-__global__ void unpack_panel_mean(const double* __restrict__ P, int64_t n_pad, double* __restrict__ dst, int64_t ld,
-                                  double* __restrict__ mean_out, int bs, int bsp, int64_t n, int k, int kp) {
-    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= n * (int64_t)(k + 1)) return;
-    const int64_t r = idx / n, j = idx % n;
-    const int64_t blk = j / bs, off = j % bs;
-    const double* Pp = P + (int64_t)blockIdx.y * (kp + 1) * n_pad + blk * bsp + off;
-    const double mu = Pp[(int64_t)kp * n_pad];
-    if (r == k) mean_out[(int64_t)blockIdx.y * n + j] = mu;
-    else dst[((int64_t)blockIdx.y * k + r) * ld + j] = Pp[r * n_pad] + mu;
-}
-
 // ------------------------------------------------------------------------------- K7
 // C = B * X^T with the lower block B kept SPARSE (src/tridiagonal_cholesky.jl:74 forms
 // `A[block_idcs, prev_block_idcs] / L'`; a FEM / finite-difference coupling block has a handful of

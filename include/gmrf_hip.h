@@ -83,6 +83,7 @@ typedef struct {
      *  8 potrf_panel                             9 potrf_update
      * 10 spmm_bxt (sparse C = B X^T)          13 gemm_f64_ll (32 x 32 tile GEMM of small launches)
      * 14 / 15 gemm_f64_dma<.., B [n][k]> / <.., B [k][n]> (LDS-DMA staged GEMM: the batches' products since round 3)
+     *    (14 also books gemm_f64_dma_grouped, two products in one launch: ONE launch with both products' flops; round 13)
      * 16 potrf_diag128 (128 x 128 diagonal block of a batch: two tile Choleskys + the block's inverse)
      * 17 potrf_persist (one problem: the in-block Cholesky of a block / a 256-column panel in ONE persistent launch; small
      *    batches: the 256 x 256 diagonal block of a panel.  Round 4 booked these under class 1; class 17 was potrf_panel256, removed)
@@ -418,7 +419,9 @@ gmrf_status gmrf_bt_set_profiling(gmrf_handle* h, int32_t level);
  * accumulating product (comparison; same bits); bit 18: a batch's gmrf_bt_posterior is gmrf_bt_solve + gmrf_bt_sample (the mean's
  * backward sweep a pass of its own) instead of the fused pass that sweeps the mean as the tail row of the samples' GEMMs
  * (comparison; the samples' L^-T z rows are the same bits, the mean agrees to rounding); bit 19: factorisations do not solve for the
- * right-hand side of gmrf_bt_set_factor_rhs (comparison: the posterior's forward sweep runs).
+ * right-hand side of gmrf_bt_set_factor_rhs (comparison: the posterior's forward sweep runs); bit 20: the two independent 128^3
+ * products of a 256-column panel's diagonal chain (S_BB -= L_BA L_BA^T and T = L_BA X_A) stay two launches instead of ONE launch of
+ * gemm_f64_dma_grouped (comparison; same bits).
  * (Bits 6, 9, 10, 11, 14 selected comparison routes that lost twice -- left-looking panels, in-panel updates on the GEMM kernel,
  * rank-64 panel steps of batches, 128-column panels, potrf_panel256 -- and were removed with them in round 5; they are ignored.) */
 gmrf_status gmrf_bt_set_eager(gmrf_handle* h, int32_t eager);
@@ -703,6 +706,11 @@ gmrf_status gmrf_test_gemm(int32_t device, int64_t M, int64_t N, int64_t K, int3
                            int32_t transB, int32_t tri_flags, int32_t lower_only,
                            double alpha, const double* A, int64_t lda, const double* B,
                            int64_t ldb, double beta, double* C, int64_t ldc);
+/* Two products of `batch` problems each on the 64 x 64 LDS-DMA kernel (host arrays, contiguous per problem: A [M][K], B [K][N] if b_n
+ * else [N][K], C [M][N], in and out): grouped != 0 as ONE launch of gemm_f64_dma_grouped, else as two launches.  desc: M, N, K, b_n,
+ * tri, lower_only of product 0, then of product 1; ab: alpha_0, beta_0, alpha_1, beta_1. */
+gmrf_status gmrf_test_gemm_pair(int32_t device, int32_t batch, int32_t grouped, const int64_t* desc, const double* ab,
+                                const double* A0, const double* B0, double* C0, const double* A1, const double* B1, double* C1);
 /* Device-resident timing of one GEMM shape (random operands): batch problems, big = 1 takes the
  * 128 x 128 kernel, 0 the 64 x 64 one, 2 the launcher's own choice. */
 gmrf_status gmrf_test_gemm_rate(int32_t device, int64_t M, int64_t N, int64_t K, int32_t transB,

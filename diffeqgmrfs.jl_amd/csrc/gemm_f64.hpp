@@ -54,6 +54,8 @@ struct GemmArgs {
     int M, N, K;
     int tri;
     int lower_only;                      // skip tiles strictly above the block diagonal (launcher: 1 = triangular grid, 2 = early exit)
+                                         // -- tiles of the kernel that runs: 64 x 64 (register-staged and every LDS-DMA shape), 128 x 128
+                                         // or 32 x 32; what is written above the diagonal inside a diagonal 128 x 128 tile is the product
     double alpha, beta;
     const double* D;                     // addend: C = beta * D + alpha * A B  (nullptr: D = C, in place)
     int64_t ldd, pD;                     // its row stride and problem stride
@@ -74,6 +76,7 @@ struct GemmArgs {
     double tbeta = 0.0;
     // Direct output of gemm_f64_dma's DOUT variant (dout != nullptr; one problem per z): the product's N columns are the dofs
     // o_j0 .. of the caller's arrays, the first o_cols of them real (the rest padding, not written); o_n = dofs per problem
+    // (every row tile sums the tail row over ITS K range: beta == 0, no K bounds, no TRI_A_* -- gemm_tail_ok refuses the rest)
     const GemmDirectOut* dout = nullptr;
     int64_t o_j0 = 0, o_n = 0;
     int o_cols = 0;

@@ -516,7 +516,8 @@ inline bool gemm_tail_ok(bool a_t, bool b_n, const GemmArgs& g, int batch) {
     if (!b_n || g.lower_only) return false;                      // (so a direct output, g.dout, is on B [k][n] with the tail in row M)
     if (g.dout && g.nb1 != 1) return false;
     // (a direct output: EVERY row tile sums the tail row, so the tail must not read C and must share every tile's K range)
-    if (g.dout && (g.beta != 0.0 || g.kb_m || g.kb_n || g.ke_n)) return false;
+    // (TRI_A_* give the row tiles of one column tile different K ranges; TRI_B_* do not)
+    if (g.dout && (g.beta != 0.0 || g.kb_m || g.kb_n || g.ke_n || (g.tri & (TRI_A_LOWER | TRI_A_UPPER)))) return false;
     // 32-bit byte offsets inside a problem's operand for the M + 1 rows (A: row M read with 64-bit addressing)
     return (int64_t)(g.M + 1) * g.ldc * 8 < ((int64_t)1 << 32) && (!g.D || (int64_t)(g.M + 1) * g.ldd * 8 < ((int64_t)1 << 32));
 }

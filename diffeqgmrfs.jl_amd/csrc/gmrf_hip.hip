@@ -6445,6 +6445,152 @@ gmrf_status gmrf_test_gemm_pair(int32_t device, int32_t batch, int32_t grouped, 
     return GMRF_OK;
 }
 
+// One launch of a fully general GemmArgs on ONE chosen route (tests/test_gpu_gemm_desc.py).  Host buffers are copied whole, the
+// descriptor is checked against their sizes before anything is launched (furthest element addressed per operand), C / tC / the
+// direct-out arrays come back whole.  desc (28 x int64): M, N, K, transA, b_n, tri, lower_only, batch, nb1, lda, ldb, ldc, ldd,
+// strideA, strideB, strideC, pA, pB, pC, pD, ptA, ptC, ptD, o_j0, o_n, o_cols, o_ld, o_k.  abt: alpha, beta, tbeta.
+// route: 0 register-staged 64 x 64, 1 the 128 x 128 kernel, 2 the 32 x 32 one, 3 / 4 / 5 LDS-DMA 64 x 64 / 128 x 64 / 64 x 128,
+// 6 the tail-row product (row M of A / C / D unless tC is given; samples != nullptr: with the direct output), 7 launch_gemm's
+// own choice with every policy at its default.  *family: 1 / 2 register-staged at BK 16 / 32 (+ 256: single stage), 3 the
+// 128 x 128 kernel, 4 the 32 x 32 one, 5 / 6 / 7 LDS-DMA by tile shape, 8 tail row, 9 tail row with direct output.  A forced
+// route the descriptor does not qualify for is GMRF_ERR_BAD_SHAPE and launches nothing.  The family is this hook's statement of
+// launch_gemm's order of questions (gemm_uses_big, gemm_dma_shape, gemm_uses_ll, K % 32, grid.x > 768): it holds with the
+// launcher's tuning variables GMRF_GEMM_SINGLE_STAGE, GMRF_GEMM_BK16 and GMRF_GEMM_LL_MAX_TILES unset, as the tests run.
+gmrf_status gmrf_test_gemm_desc(int32_t device, int32_t route, const int64_t* desc, const double* abt,
+                                const double* A, int64_t nA, const double* B, int64_t nB, double* C, int64_t nC,
+                                const double* D, int64_t nD, const double* tA, int64_t ntA, double* tC, int64_t ntC,
+                                const double* tD, int64_t ntD, const int32_t* kb_m, int64_t n_kb_m, const int32_t* kb_n,
+                                int64_t n_kb_n, const int32_t* ke_n, int64_t n_ke_n, double* samples, int64_t n_samples,
+                                double* mean, int64_t n_mean, int32_t* family) {
+    if (!desc || !abt || !A || !B || !C || !family) return bad_shape("gemm desc test: null pointer");
+    *family = 0;
+    const int64_t M = desc[0], N = desc[1], K = desc[2];
+    const bool a_t = desc[3] != 0, b_n = desc[4] != 0;
+    const int64_t tri = desc[5], lower_only = desc[6], batch = desc[7], nb1 = desc[8];
+    const int64_t lda = desc[9], ldb = desc[10], ldc = desc[11], ldd = desc[12];
+    const int64_t sA = desc[13], sB = desc[14], sC = desc[15], pA = desc[16], pB = desc[17], pC = desc[18], pD = desc[19];
+    const int64_t ptA = desc[20], ptC = desc[21], ptD = desc[22], o_j0 = desc[23], o_n = desc[24], o_cols = desc[25];
+    const int64_t o_ld = desc[26], o_k = desc[27];
+    if (route < 0 || route > 7) return bad_shape("gemm desc test: unknown route");
+    if (M <= 0 || N <= 0 || K <= 0 || M % 64 || N % 64 || K % 16 || M > 16384 || N > 16384 || K > 16384)
+        return bad_shape("gemm desc test: sizes");
+    if (tri < 0 || tri > 15 || (lower_only != 0 && lower_only != 1)) return bad_shape("gemm desc test: tri / lower_only");
+    if (batch < 1 || nb1 < 1 || batch % nb1 || batch > 4096) return bad_shape("gemm desc test: batch is not a multiple of nb1");
+    const int64_t strides[] = {sA, sB, sC, pA, pB, pC, pD, ptA, ptC, ptD};
+    for (int64_t s : strides)
+        if (s < 0 || s > ((int64_t)1 << 40)) return bad_shape("gemm desc test: negative stride");
+    const bool tail = route == 6, own_tail = tail && tC != nullptr, dout = tail && samples != nullptr;
+    if (!tail && (tA || tC || tD || samples || mean)) return bad_shape("gemm desc test: tail operands without the tail route");
+    if (dout && (!mean || own_tail)) return bad_shape("gemm desc test: direct output");
+    if (!dout && mean) return bad_shape("gemm desc test: mean without samples");
+    if (own_tail && !tA) return bad_shape("gemm desc test: tC without tA");
+    if (!own_tail && (tA || tD)) return bad_shape("gemm desc test: tA / tD without tC");
+    const int64_t rows = M + ((tail && !own_tail) ? 1 : 0);      // rows of A (stored [m][k]) / C / D
+    if (lda < (a_t ? M : K) || ldb < (b_n ? N : K) || ldc < N || (D && ldd < N) || lda > ((int64_t)1 << 24) || ldb > ((int64_t)1 << 24) ||
+        ldc > ((int64_t)1 << 24) || ldd > ((int64_t)1 << 24))
+        return bad_shape("gemm desc test: leading dimension");
+    // the furthest element each operand is addressed at (all strides >= 0) must lie inside its buffer
+    const int64_t np = batch / nb1, zin = (nb1 - 1), zout = (np - 1);
+    const int64_t needA = zin * sA + zout * pA + (a_t ? (K - 1) * lda + M : (rows - 1) * lda + K);
+    const int64_t needB = zin * sB + zout * pB + (b_n ? (K - 1) * ldb + N : (N - 1) * ldb + K);
+    const int64_t needC = zin * sC + zout * pC + (rows - 1) * ldc + N;
+    const int64_t needD = zout * pD + (rows - 1) * ldd + N;
+    if (needA > nA || needB > nB || needC > nC || (D && needD > nD)) return bad_shape("gemm desc test: operand buffer too small");
+    if (own_tail && (zout * ptA + K > ntA || zout * ptC + N > ntC || (tD && zout * ptD + N > ntD)))
+        return bad_shape("gemm desc test: tail buffer too small");
+    if ((kb_m && n_kb_m < M / 64) || (kb_n && n_kb_n < N / 64) || (ke_n && n_ke_n < N / 64)) return bad_shape("gemm desc test: K bounds too short");
+    const int32_t* kbs[3] = {kb_m, kb_n, ke_n};
+    const int64_t nkb[3] = {M / 64, N / 64, N / 64};
+    for (int a = 0; a < 3; ++a)
+        for (int64_t i = 0; kbs[a] && i < nkb[a]; ++i)
+            if (kbs[a][i] < 0 || kbs[a][i] > K || kbs[a][i] % 64) return bad_shape("gemm desc test: K bound value");
+    if (dout) {
+        if (o_k < 0 || o_k > M || o_cols < 0 || o_cols > N || o_j0 < 0 || o_ld < 0 || o_n < 0 || o_ld > ((int64_t)1 << 24) || o_n > ((int64_t)1 << 30))
+            return bad_shape("gemm desc test: direct-out fields");
+        if (o_cols > 0 && o_k > 0 && (zout * o_k + o_k - 1) * o_ld + o_j0 + o_cols > n_samples) return bad_shape("gemm desc test: samples too small");
+        if (o_cols > 0 && zout * o_n + o_j0 + o_cols > n_mean) return bad_shape("gemm desc test: mean too small");
+    }
+    HIPCHK(hipSetDevice(device));
+    HIPCHK(gemm_init());
+    HIPCHK(gemm_dma_init());
+
+    std::vector<void*> owned;
+    auto drop = [&]() { for (void* p : owned) free_dev(p); owned.clear(); };
+    hipError_t e = hipSuccess;
+    auto up = [&](const void* host, int64_t count, size_t elem) -> void* {
+        if (!host || e != hipSuccess) return nullptr;
+        void* d = nullptr;
+        e = hipMalloc(&d, std::max<size_t>((size_t)count * elem, 16));
+        if (e != hipSuccess) return nullptr;
+        owned.push_back(d);
+        if (count > 0) e = hipMemcpy(d, host, (size_t)count * elem, hipMemcpyHostToDevice);
+        return d;
+    };
+    GemmArgs g;
+    g.A = (const double*)up(A, nA, 8); g.B = (const double*)up(B, nB, 8); g.C = (double*)up(C, nC, 8);
+    g.D = (const double*)up(D, nD, 8);
+    g.tA = (const double*)up(tA, ntA, 8); g.tC = (double*)up(tC, ntC, 8); g.tD = (const double*)up(tD, ntD, 8);
+    g.kb_m = (const int*)up(kb_m, n_kb_m, 4); g.kb_n = (const int*)up(kb_n, n_kb_n, 4); g.ke_n = (const int*)up(ke_n, n_ke_n, 4);
+    double* d_samples = (double*)up(samples, n_samples, 8);
+    double* d_mean = (double*)up(mean, n_mean, 8);
+    GemmDirectOut* d_out = nullptr;
+    if (dout && e == hipSuccess) {
+        e = hipMalloc(&d_out, sizeof(GemmDirectOut));
+        if (e == hipSuccess) {
+            owned.push_back(d_out);
+            hipLaunchKernelGGL(set_direct_out, dim3(1), dim3(1), 0, nullptr, d_out, d_samples, d_mean, o_ld, o_k);
+            e = hipGetLastError();
+        }
+    }
+    if (e != hipSuccess) { drop(); HIPCHK(e); }
+    g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.ldd = D ? ldd : 0;
+    g.strideA = sA; g.strideB = sB; g.strideC = sC; g.pA = pA; g.pB = pB; g.pC = pC; g.pD = D ? pD : 0;
+    g.nb1 = (int)nb1; g.M = (int)M; g.N = (int)N; g.K = (int)K; g.tri = (int)tri; g.lower_only = (int)lower_only;
+    g.alpha = abt[0]; g.beta = abt[1]; g.tbeta = abt[2];
+    g.ptA = ptA; g.ptC = ptC; g.ptD = ptD;
+    g.stamps = nullptr;
+    g.dout = d_out; g.o_j0 = o_j0; g.o_n = o_n; g.o_cols = (int)o_cols;
+
+    const int saved_big = gemm_big_policy(), saved_ll = gemm_ll_policy(), saved_dma = gemm_dma_policy(), saved_force = gemm_dma_force();
+    auto restore = [&]() { gemm_big_policy() = saved_big; gemm_ll_policy() = saved_ll; gemm_dma_policy() = saved_dma; gemm_dma_force() = saved_force; };
+    // route:                   0  1  2  3  4  5  6  7
+    static const int big_p[] = {2, 1, 2, 2, 2, 2, 2, 0};
+    static const int ll_p[] = {2, 2, 0, 2, 2, 2, 2, 0};
+    static const int dma_p[] = {0, 0, 0, 2, 2, 2, 1, 2};
+    static const int force_p[] = {0, 0, 0, 1, 2, 3, 0, 0};
+    gemm_big_policy() = big_p[route]; gemm_ll_policy() = ll_p[route]; gemm_dma_policy() = dma_p[route]; gemm_dma_force() = force_p[route];
+    const int nz = (int)batch;
+    int fam;
+    hipError_t le = hipSuccess;
+    if (tail) {
+        fam = gemm_try_dma_tail(nullptr, a_t, b_n, g, nz, nullptr, nullptr, &le) ? (dout ? 9 : 8) : 0;     // (false: nothing launched)
+    } else {
+        // (the order launch_gemm asks in)
+        if (gemm_uses_big(a_t, g, nz)) fam = 3;
+        else if (!gemm_uses_ll(g, nz) && gemm_dma_shape(a_t, g, nz) != 0) fam = 4 + gemm_dma_shape(a_t, g, nz);
+        else if (gemm_uses_ll(g, nz)) fam = 4;
+        else {
+            const bool tri_grid = lower_only && M == N;
+            const int64_t sx = N / GEMM_BN, sy = M / GEMM_BM;
+            fam = (K % 32 == 0 ? 2 : 1) + ((tri_grid ? sx * (sx + 1) / 2 : sx * sy) * batch > 768 ? 256 : 0);
+        }
+        static const int want[] = {0, 3, 4, 5, 6, 7};
+        if (route == 0 ? (fam & 255) > 2 : (route < 6 && fam != want[route])) fam = 0;
+        if (fam) le = launch_gemm(nullptr, a_t, b_n, g, nz);
+    }
+    restore();
+    if (!fam) { drop(); return bad_shape("gemm desc test: the descriptor does not qualify for the route"); }
+    if (le == hipSuccess) le = hipDeviceSynchronize();
+    if (le == hipSuccess) le = hipMemcpy(C, g.C, sizeof(double) * nC, hipMemcpyDeviceToHost);
+    if (le == hipSuccess && own_tail) le = hipMemcpy(tC, g.tC, sizeof(double) * ntC, hipMemcpyDeviceToHost);
+    if (le == hipSuccess && dout && n_samples > 0) le = hipMemcpy(samples, d_samples, sizeof(double) * n_samples, hipMemcpyDeviceToHost);
+    if (le == hipSuccess && dout && n_mean > 0) le = hipMemcpy(mean, d_mean, sizeof(double) * n_mean, hipMemcpyDeviceToHost);
+    drop();
+    HIPCHK(le);
+    *family = fam;
+    return GMRF_OK;
+}
+
 // rows of 11 doubles per distinct GEMM launch shape seen while profiling was on: class, M, N, K, tri, lower_only, problems,
 // per-tile K bounds?, launches, ms, work (flops as booked in kernel_work).  *n_rows = rows available (may exceed cap_rows).
 gmrf_status gmrf_test_gemm_shapes(gmrf_handle* h, double* rows, int64_t cap_rows, int64_t* n_rows) {

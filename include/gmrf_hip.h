@@ -711,6 +711,20 @@ gmrf_status gmrf_test_gemm(int32_t device, int64_t M, int64_t N, int64_t K, int3
  * tri, lower_only of product 0, then of product 1; ab: alpha_0, beta_0, alpha_1, beta_1. */
 gmrf_status gmrf_test_gemm_pair(int32_t device, int32_t batch, int32_t grouped, const int64_t* desc, const double* ab,
                                 const double* A0, const double* B0, double* C0, const double* A1, const double* B1, double* C1);
+/* One launch of a general GEMM descriptor on one chosen route; host buffers with their element counts, copied whole both ways
+ * (any of D, tA, tC, tD, the K bounds and samples / mean may be null).  desc (28 x int64): M, N, K, transA, b_n, tri, lower_only,
+ * batch, nb1, lda, ldb, ldc, ldd, strideA, strideB, strideC, pA, pB, pC, pD, ptA, ptC, ptD, o_j0, o_n, o_cols, o_ld, o_k; abt: alpha,
+ * beta, tbeta.  route: 0 register-staged 64 x 64, 1 128 x 128, 2 32 x 32, 3 / 4 / 5 LDS-DMA 64 x 64 / 128 x 64 / 64 x 128, 6 tail row
+ * (row M of A / C / D unless tC is given; with the direct output if samples is given), 7 the launcher's own choice.  *family: 1 / 2
+ * register-staged at BK 16 / 32 (+ 256 single stage), 3 128 x 128, 4 32 x 32, 5 / 6 / 7 LDS-DMA by tile shape, 8 tail row, 9 tail row
+ * with direct output.  Buffers too small for the descriptor, or a forced route it does not qualify for: GMRF_ERR_BAD_SHAPE, nothing
+ * launched. */
+gmrf_status gmrf_test_gemm_desc(int32_t device, int32_t route, const int64_t* desc, const double* abt,
+                                const double* A, int64_t nA, const double* B, int64_t nB, double* C, int64_t nC,
+                                const double* D, int64_t nD, const double* tA, int64_t ntA, double* tC, int64_t ntC,
+                                const double* tD, int64_t ntD, const int32_t* kb_m, int64_t n_kb_m, const int32_t* kb_n,
+                                int64_t n_kb_n, const int32_t* ke_n, int64_t n_ke_n, double* samples, int64_t n_samples,
+                                double* mean, int64_t n_mean, int32_t* family);
 /* Device-resident timing of one GEMM shape (random operands): batch problems, big = 1 takes the
  * 128 x 128 kernel, 0 the 64 x 64 one, 2 the launcher's own choice. */
 gmrf_status gmrf_test_gemm_rate(int32_t device, int64_t M, int64_t N, int64_t K, int32_t transB,

@@ -42,7 +42,7 @@ EXPORTS = [
     "gmrf_assemble_create", "gmrf_assemble_destroy", "gmrf_assemble_pattern", "gmrf_assemble_precision", "gmrf_assemble_rhs",
     "gmrf_burgers_p1_tangent_batch", "gmrf_assemble_precision_batch", "gmrf_assemble_rhs_batch", "gmrf_assemble_objective_batch",
     "gmrf_gn_create", "gmrf_gn_destroy", "gmrf_gn_run", "gmrf_gn_finalize",
-    "gmrf_elliptic_p1_create", "gmrf_elliptic_p1_destroy", "gmrf_elliptic_p1_pattern", "gmrf_elliptic_p1_qpoints",
+    "gmrf_elliptic_p1_create", "gmrf_elliptic_p2_create", "gmrf_elliptic_p1_destroy", "gmrf_elliptic_p1_pattern", "gmrf_elliptic_p1_qpoints",
     "gmrf_elliptic_p1_tangent", "gmrf_elliptic_p1_tangent_batch", "gmrf_elliptic_p1_load", "gmrf_gn_create_elliptic",
     "gmrf_darcy_p1_assemble_batch", "gmrf_dc_create", "gmrf_dc_destroy", "gmrf_dc_run",
     "gmrf_burgers_prior_create", "gmrf_burgers_prior_destroy", "gmrf_burgers_prior_pattern", "gmrf_burgers_prior_values_batch",
@@ -184,6 +184,7 @@ def load() -> C.CDLL:
         "gmrf_gn_create": [vp, vp, vp, P(vp)],
         "gmrf_gn_create_elliptic": [vp, vp, vp, P(vp)],
         "gmrf_elliptic_p1_create": [i32, vp, i64, i64, P(vp)],
+        "gmrf_elliptic_p2_create": [i32, vp, i64, i64, P(vp)],
         "gmrf_elliptic_p1_destroy": [vp],
         "gmrf_elliptic_p1_pattern": [vp, P(i64), vp, vp, i32],
         "gmrf_elliptic_p1_qpoints": [vp, vp],

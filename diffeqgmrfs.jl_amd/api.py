@@ -476,22 +476,32 @@ class EllipticP1Tangent:
     sides stay zero, columns are kept.  `pattern` is the CSR matrix (values 1) whose `.data` order `tangent()` fills --
     exactly `DarcyP1Assembler(nx, ny).pattern`, the `J` of `PosteriorAssembler`; `qpoints` (cells, 3, 2) are the quadrature
     points at which the caller evaluates its source.  The residual does not contain the load: `load(src_q)` goes to
-    `GaussNewtonBatch.run` as `y`.  device = -1: pattern and quadrature points only (no GPU needed)."""
+    `GaussNewtonBatch.run` as `y`.  device = -1: pattern and quadrature points only (no GPU needed).
 
-    def __init__(self, nx: int, ny: int, device: int = 0, stream: int = 0):
-        self.nx, self.ny, self.n = int(nx), int(ny), int(nx) * int(ny)
+    order = 2: the reference's default element (`element_order = 2` of `gmrf_fem_solve`, :118-122), `Lagrange{RefTriangle,2}` under
+    `QuadratureRule{RefTriangle}(3)` on the lattice of `DarcyP1Assembler(nx, ny, order=2)`: n = (2 nx - 1)(2 ny - 1) dofs (vertices
+    and edge midpoints, x fastest), `pattern` exactly that assembler's, `nq` = 4 quadrature points per cell, `qpoints` (cells, 4, 2)
+    and `load` of (cells, 4); prescribed rows are the lattice points on the four sides (gmrf_elliptic_p2_create)."""
+
+    def __init__(self, nx: int, ny: int, device: int = 0, stream: int = 0, order: int = 1):
+        if order not in (1, 2):
+            raise ValueError("order must be 1 or 2")
+        self.nx, self.ny, self.order = int(nx), int(ny), int(order)
+        self.n = (2 * self.nx - 1) * (2 * self.ny - 1) if self.order == 2 else self.nx * self.ny
+        self.nq = 4 if self.order == 2 else 3
         self.rows = self.n
         self.cells = 2 * (self.nx - 1) * (self.ny - 1)
         self._h = C.c_void_p()
         lib = _cabi.load()
-        _cabi.check(lib.gmrf_elliptic_p1_create(device, C.c_void_p(stream), nx, ny, C.byref(self._h)))
+        create = lib.gmrf_elliptic_p2_create if self.order == 2 else lib.gmrf_elliptic_p1_create
+        _cabi.check(create(device, C.c_void_p(stream), nx, ny, C.byref(self._h)))
         nnz = C.c_int64(0)
         _cabi.check(lib.gmrf_elliptic_p1_pattern(self._h, C.byref(nnz), None, None, 0))
         self.nnz = int(nnz.value)
         rp, ci = np.empty(self.n + 1, dtype=np.int64), np.empty(self.nnz, dtype=np.int64)
         _cabi.check(lib.gmrf_elliptic_p1_pattern(self._h, None, _cabi.ptr(rp), _cabi.ptr(ci), 0))
         self.pattern = sp.csr_matrix((np.ones(self.nnz), ci, rp), shape=(self.n, self.n))
-        self.qpoints = np.empty((self.cells, 3, 2), dtype=np.float64)
+        self.qpoints = np.empty((self.cells, self.nq, 2), dtype=np.float64)
         _cabi.check(lib.gmrf_elliptic_p1_qpoints(self._h, _cabi.ptr(self.qpoints)))
 
     def __del__(self):
@@ -512,7 +522,7 @@ class EllipticP1Tangent:
         return np.ascontiguousarray(a, dtype=np.float64)
 
     def tangent(self, w):
-        """w: (nx ny,) linearisation point (NumPy array or torch CUDA tensor).  Returns (J values in `pattern.data`
+        """w: (n,) linearisation point (NumPy array or torch CUDA tensor).  Returns (J values in `pattern.data`
         order, residual f(w) without the load), same kind as the input."""
         wv = self._f64(w)
         if wv.ndim != 1 or wv.shape[0] != self.n:
@@ -522,7 +532,7 @@ class EllipticP1Tangent:
         return vals, f
 
     def tangent_batch(self, W):
-        """W: (B, nx ny) linearisation points -> (J values (B, nnz), residuals (B, n)), same kind as the input; row p is
+        """W: (B, n) linearisation points -> (J values (B, nnz), residuals (B, n)), same kind as the input; row p is
         `tangent(W[p])`, bit for bit."""
         wv = self._f64(W)
         if wv.ndim != 2 or wv.shape[1] != self.n:
@@ -533,11 +543,11 @@ class EllipticP1Tangent:
         return vals, f
 
     def load(self, src_q):
-        """src_q: (cells, 3) or (B, cells, 3) values of the source at `qpoints` -> b (n,) or (B, n), b[i] = int phi_i f_src, same
+        """src_q: (cells, nq) or (B, cells, nq) values of the source at `qpoints` -> b (n,) or (B, n), b[i] = int phi_i f_src, same
         kind as the input; row p of a batch is `load(src_q[p])`, bit for bit."""
         sv = self._f64(src_q)
-        if sv.ndim not in (2, 3) or tuple(sv.shape[-2:]) != (self.cells, 3):
-            raise ValueError(f"src_q must have shape ({self.cells}, 3) or (B, {self.cells}, 3)")
+        if sv.ndim not in (2, 3) or tuple(sv.shape[-2:]) != (self.cells, self.nq):
+            raise ValueError(f"src_q must have shape ({self.cells}, {self.nq}) or (B, {self.cells}, {self.nq})")
         B = sv.shape[0] if sv.ndim == 3 else 1
         b = PosteriorAssembler._like2(sv, (B, self.n) if sv.ndim == 3 else (self.n,))
         _cabi.check(_cabi.load().gmrf_elliptic_p1_load(self._h, B, _cabi.ptr(sv), _cabi.ptr(b)))

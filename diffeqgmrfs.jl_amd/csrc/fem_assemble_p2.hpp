@@ -59,6 +59,28 @@ __device__ __forceinline__ void p2_cell_nodes(int qx, int qy, bool upper, int (&
     nI[5] = (nI[2] + nI[0]) / 2; nJ[5] = (nJ[2] + nJ[0]) / 2;
 }
 
+// The cells of a lattice point by dof class c = (I & 1) + 2 (J & 1), in ascending cell number: entry e is (quad offset in x, in y
+// from (I / 2, J / 2) rounded down, upper?, local index of the point in the cell).
+//   class 0, a vertex: its six cells;
+//   class 1, a horizontal edge: (1-2) of the lower cell above it, (2-3) of the upper cell below;
+//   class 2, a vertical edge: (2-3) of the lower cell left of it, (3-1) of the upper cell right;
+//   class 3, a diagonal: (3-1) of the lower, (1-2) of the upper cell of its quad.
+__host__ __device__ constexpr int p2_class_ncells(int c) { return c == 0 ? 6 : 2; }
+__host__ __device__ constexpr int p2_class_cell(int c, int e, int u) {
+    constexpr int t[4][6][4] = {{{-1, -1, 0, 2}, {-1, 0, 0, 1}, {0, 0, 0, 0}, {-1, -1, 1, 1}, {0, -1, 1, 2}, {0, 0, 1, 0}},
+                                {{0, 0, 0, 3}, {0, -1, 1, 4}},
+                                {{-1, 0, 0, 4}, {0, 0, 1, 5}},
+                                {{0, 0, 0, 5}, {0, 0, 1, 3}}};
+    return t[c][e][u];
+}
+
+// The 4-point Dunavant rule of degree 3 in the order that fixes every summation over quadrature points.
+struct P2QPoint { double xi, eta, w; };
+__host__ __device__ constexpr P2QPoint p2_tri_qpoint(int q) {
+    constexpr P2QPoint t[4] = {{1.0 / 3.0, 1.0 / 3.0, -27.0 / 96.0}, {0.2, 0.2, 25.0 / 96.0}, {0.6, 0.2, 25.0 / 96.0}, {0.2, 0.6, 25.0 / 96.0}};
+    return t[q];
+}
+
 __device__ __forceinline__ void darcy_p2_row(const DarcyP2Args& a, const int64_t row) {
     const int W = 2 * a.nx - 1, H = 2 * a.ny - 1;
     if (row >= (int64_t)W * H) return;
@@ -72,24 +94,21 @@ __device__ __forceinline__ void darcy_p2_row(const DarcyP2Args& a, const int64_t
     int cand[6][4];
     int nc;
     if (!(I & 1) && !(J & 1)) {
-        const int t[6][4] = {{-1, -1, 0, 2}, {-1, 0, 0, 1}, {0, 0, 0, 0}, {-1, -1, 1, 1}, {0, -1, 1, 2}, {0, 0, 1, 0}};
-        nc = 6;
-        for (int e = 0; e < 6; ++e) for (int u = 0; u < 4; ++u) cand[e][u] = t[e][u];
-    } else if ((I & 1) && !(J & 1)) {           // horizontal edge: (1-2) of the lower cell above it, (2-3) of the upper cell below
-        const int t[2][4] = {{0, 0, 0, 3}, {0, -1, 1, 4}};
-        nc = 2;
-        for (int e = 0; e < 2; ++e) for (int u = 0; u < 4; ++u) cand[e][u] = t[e][u];
-    } else if (!(I & 1) && (J & 1)) {           // vertical edge: (2-3) of the lower cell left of it, (3-1) of the upper cell right
-        const int t[2][4] = {{-1, 0, 0, 4}, {0, 0, 1, 5}};
-        nc = 2;
-        for (int e = 0; e < 2; ++e) for (int u = 0; u < 4; ++u) cand[e][u] = t[e][u];
-    } else {                                    // diagonal: (3-1) of the lower, (1-2) of the upper cell of its quad
-        const int t[2][4] = {{0, 0, 0, 5}, {0, 0, 1, 3}};
-        nc = 2;
-        for (int e = 0; e < 2; ++e) for (int u = 0; u < 4; ++u) cand[e][u] = t[e][u];
+        nc = p2_class_ncells(0);
+        for (int e = 0; e < 6; ++e) for (int u = 0; u < 4; ++u) cand[e][u] = p2_class_cell(0, e, u);
+    } else if ((I & 1) && !(J & 1)) {
+        nc = p2_class_ncells(1);
+        for (int e = 0; e < 2; ++e) for (int u = 0; u < 4; ++u) cand[e][u] = p2_class_cell(1, e, u);
+    } else if (!(I & 1) && (J & 1)) {
+        nc = p2_class_ncells(2);
+        for (int e = 0; e < 2; ++e) for (int u = 0; u < 4; ++u) cand[e][u] = p2_class_cell(2, e, u);
+    } else {
+        nc = p2_class_ncells(3);
+        for (int e = 0; e < 2; ++e) for (int u = 0; u < 4; ++u) cand[e][u] = p2_class_cell(3, e, u);
     }
-    const double qxi[4] = {1.0 / 3.0, 0.2, 0.6, 0.2}, qeta[4] = {1.0 / 3.0, 0.2, 0.2, 0.6};
-    const double qw[4] = {-27.0 / 96.0, 25.0 / 96.0, 25.0 / 96.0, 25.0 / 96.0};
+    const double qxi[4] = {p2_tri_qpoint(0).xi, p2_tri_qpoint(1).xi, p2_tri_qpoint(2).xi, p2_tri_qpoint(3).xi};
+    const double qeta[4] = {p2_tri_qpoint(0).eta, p2_tri_qpoint(1).eta, p2_tri_qpoint(2).eta, p2_tri_qpoint(3).eta};
+    const double qw[4] = {p2_tri_qpoint(0).w, p2_tri_qpoint(1).w, p2_tri_qpoint(2).w, p2_tri_qpoint(3).w};
     for (int e = 0; e < nc; ++e) {
         const int qx = I / 2 + cand[e][0], qy = J / 2 + cand[e][1];
         if (qx < 0 || qy < 0 || qx >= a.nx - 1 || qy >= a.ny - 1) continue;

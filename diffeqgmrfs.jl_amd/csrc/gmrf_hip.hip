@@ -40,6 +40,7 @@
 #include "sweep_persist.hpp"
 #include "swe_assemble.hpp"
 #include "elliptic_assemble.hpp"
+#include "elliptic_assemble_p2.hpp"
 #include "fem_assemble_p2.hpp"
 #include "selinv.hpp"
 #include "gauss_newton.hpp"
@@ -3943,11 +3944,11 @@ struct gmrf_darcy_p1 : DevCtx {         // device -1: pattern only
 
 // Pattern of the quadratic-triangle lattice: row (I, J) couples with every node of every cell it belongs to (the same
 // enumeration as darcy_p2_rows: 5 x 5 window of lattice offsets, touched entries in ascending column order).
-static void darcy_p2_pattern(gmrf_darcy_p1* d) {
-    const int64_t nx = d->nx, ny = d->ny, W = 2 * nx - 1, H = 2 * ny - 1;
-    d->n = W * H;
-    d->rowptr.assign((size_t)d->n + 1, 0);
-    d->colidx.reserve((size_t)d->n * 12);
+static void p2_lattice_pattern(int64_t nx, int64_t ny, std::vector<int64_t>& rowptr, std::vector<int64_t>& colidx) {
+    const int64_t W = 2 * nx - 1, H = 2 * ny - 1;
+    rowptr.assign((size_t)(W * H) + 1, 0);
+    colidx.clear();
+    colidx.reserve((size_t)(W * H) * 12);
     for (int64_t J = 0; J < H; ++J)
         for (int64_t I = 0; I < W; ++I) {
             unsigned present = 0u;
@@ -3971,9 +3972,14 @@ static void darcy_p2_pattern(gmrf_darcy_p1* d) {
                 for (int j = 0; j < 6; ++j) present |= 1u << (unsigned)((nJ[j] - J + 2) * 5 + (nI[j] - I + 2));
             }
             for (int s5 = 0; s5 < 25; ++s5)
-                if (present & (1u << s5)) d->colidx.push_back((J + s5 / 5 - 2) * W + (I + s5 % 5 - 2));
-            d->rowptr[(size_t)(J * W + I) + 1] = (int64_t)d->colidx.size();
+                if (present & (1u << s5)) colidx.push_back((J + s5 / 5 - 2) * W + (I + s5 % 5 - 2));
+            rowptr[(size_t)(J * W + I) + 1] = (int64_t)colidx.size();
         }
+}
+
+static void darcy_p2_pattern(gmrf_darcy_p1* d) {
+    d->n = (2 * d->nx - 1) * (2 * d->ny - 1);
+    p2_lattice_pattern(d->nx, d->ny, d->rowptr, d->colidx);
 }
 
 // CSR pattern of the P1 triangle mesh (nx x ny nodes, x fastest, quads cut by the diagonal n00 - n11): the 7-point stencil
@@ -4304,17 +4310,19 @@ gmrf_status gmrf_burgers_prior_values_batch(gmrf_burgers_prior* p, int64_t batch
 // --------------------------------------------------------------------------------- nonlinear elliptic tangent
 struct gmrf_elliptic_p1 : DevCtx {      // device -1: pattern and quadrature points only
     int64_t nx = 0, ny = 0, n = 0, nnz = 0, cells = 0;
-    std::vector<int64_t> rowptr, colidx;            // 0-based: the pattern of gmrf_darcy_p1_create(nx, ny)
+    int order = 1, nq = 3;              // element order and quadrature points per cell (order 2: the lattice of gmrf_darcy_p2_create, 4)
+    std::vector<int64_t> rowptr, colidx;            // 0-based: the pattern of gmrf_darcy_p1_create / _p2_create(nx, ny)
     int64_t* d_rowptr = nullptr;
     DevBuf arena;                       // host arguments of the current call (Staging)
 };
 
-gmrf_status gmrf_elliptic_p1_create(int32_t device, void* stream, int64_t nx, int64_t ny, gmrf_elliptic_p1** out) {
-    if (!out || nx < 2 || ny < 2 || nx > 32768 || ny > 32768) return bad_shape("bad elliptic mesh size");
+static gmrf_status elliptic_create(int32_t device, void* stream, int64_t nx, int64_t ny, int order, gmrf_elliptic_p1** out) {
+    if (!out || nx < 2 || ny < 2 || nx > 32768 || ny > 32768 || (order == 2 && (nx > 16384 || ny > 16384))) return bad_shape("bad elliptic mesh size");
     std::unique_ptr<gmrf_elliptic_p1, gmrf_status (*)(gmrf_elliptic_p1*)> guard(new gmrf_elliptic_p1(), gmrf_elliptic_p1_destroy);
     gmrf_elliptic_p1* e = guard.get();
-    e->nx = nx; e->ny = ny; e->n = nx * ny; e->cells = 2 * (nx - 1) * (ny - 1);
-    p1_stencil_pattern(nx, ny, e->rowptr, e->colidx);
+    e->nx = nx; e->ny = ny; e->cells = 2 * (nx - 1) * (ny - 1); e->order = order;
+    if (order == 2) { e->n = (2 * nx - 1) * (2 * ny - 1); e->nq = 4; p2_lattice_pattern(nx, ny, e->rowptr, e->colidx); }
+    else { e->n = nx * ny; e->nq = 3; p1_stencil_pattern(nx, ny, e->rowptr, e->colidx); }
     e->nnz = (int64_t)e->colidx.size();
     GCHK(e->open(device, stream, hipStreamNonBlocking, "gmrf_elliptic_p1_create"));
     if (e->device >= 0) {
@@ -4324,6 +4332,14 @@ gmrf_status gmrf_elliptic_p1_create(int32_t device, void* stream, int64_t nx, in
     }
     *out = guard.release();
     return GMRF_OK;
+}
+
+gmrf_status gmrf_elliptic_p1_create(int32_t device, void* stream, int64_t nx, int64_t ny, gmrf_elliptic_p1** out) {
+    return elliptic_create(device, stream, nx, ny, 1, out);
+}
+
+gmrf_status gmrf_elliptic_p2_create(int32_t device, void* stream, int64_t nx, int64_t ny, gmrf_elliptic_p1** out) {
+    return elliptic_create(device, stream, nx, ny, 2, out);
 }
 
 gmrf_status gmrf_elliptic_p1_destroy(gmrf_elliptic_p1* e) {
@@ -4360,18 +4376,48 @@ static void p1_triangle_qpoints(int64_t nx, int64_t ny, double* xy) {
             }
 }
 
+// The same for the quadratic triangles under the 4-point rule of fem_assemble_p2.hpp: xy[cell][q][2], the straight-sided cell's
+// xi_x x_1 + xi_y x_2 + gamma x_3 in the unfused order of darcy_p2_row
+static void p2_triangle_qpoints(int64_t nx, int64_t ny, double* xy) {
+#pragma clang fp contract(off)
+    const int64_t nlow = (nx - 1) * (ny - 1);
+    auto lin = [](int64_t i, int64_t n) { return (i == n - 1) ? 1.0 : (double)i * (1.0 / (double)(n - 1)); };
+    for (int up = 0; up < 2; ++up)
+        for (int64_t qy = 0; qy < ny - 1; ++qy)
+            for (int64_t qx = 0; qx < nx - 1; ++qx) {
+                const int64_t cell = up * nlow + qy * (nx - 1) + qx;
+                const int64_t vx[3] = {qx, qx + 1, up ? qx : qx + 1}, vy[3] = {qy, up ? qy + 1 : qy, qy + 1};
+                const double x1 = lin(vx[0], nx), x2 = lin(vx[1], nx), x3 = lin(vx[2], nx);
+                const double y1 = lin(vy[0], ny), y2 = lin(vy[1], ny), y3 = lin(vy[2], ny);
+                for (int q = 0; q < 4; ++q) {
+                    const double xx = p2_tri_qpoint(q).xi, xe = p2_tri_qpoint(q).eta, g = 1.0 - xx - xe;
+                    const double t0 = xx * x1, t1 = xe * x2, t2 = g * x3, u0 = xx * y1, u1 = xe * y2, u2 = g * y3;      // (products first: no contraction)
+                    xy[(cell * 4 + q) * 2 + 0] = (t0 + t1) + t2;
+                    xy[(cell * 4 + q) * 2 + 1] = (u0 + u1) + u2;
+                }
+            }
+}
+
 gmrf_status gmrf_elliptic_p1_qpoints(const gmrf_elliptic_p1* e, double* xy) {
     if (!e || !xy) return bad_shape("null pointer");
     if (is_device_ptr(xy)) return bad_shape("quadrature points are written to host memory");
-    p1_triangle_qpoints(e->nx, e->ny, xy);
+    if (e->order == 2) p2_triangle_qpoints(e->nx, e->ny, xy);
+    else p1_triangle_qpoints(e->nx, e->ny, xy);
     return GMRF_OK;
 }
 
 static gmrf_status launch_elliptic_batch(const gmrf_elliptic_p1* e, hipStream_t st, int64_t batch, const double* d_w, double* d_vals,
                                          double* d_f) {
+    const dim3 grid((unsigned)((e->n + 255) / 256), (unsigned)batch);
+    if (e->order == 2) {
+        EllipticP2Args a;
+        a.nx = (int)e->nx; a.ny = (int)e->ny; a.rowptr = e->d_rowptr; a.w = d_w; a.vals = d_vals; a.f = d_f;
+        hipLaunchKernelGGL(elliptic_p2_rows_batch, grid, dim3(256), 0, st, a, e->nnz);
+        HIPCHK(hipGetLastError());
+        return GMRF_OK;
+    }
     EllipticP1Args a;
     a.nx = (int)e->nx; a.ny = (int)e->ny; a.rowptr = e->d_rowptr; a.w = d_w; a.vals = d_vals; a.f = d_f;
-    const dim3 grid((unsigned)((e->n + 255) / 256), (unsigned)batch);
     hipLaunchKernelGGL(elliptic_p1_rows_batch, grid, dim3(256), 0, st, a, e->nnz);
     HIPCHK(hipGetLastError());
     return GMRF_OK;
@@ -4387,7 +4433,12 @@ gmrf_status gmrf_elliptic_p1_tangent(gmrf_elliptic_p1* e, const double* w, doubl
     args.out(vals_out, sizeof(double) * e->nnz, &a.vals);
     args.out(f_out, sizeof(double) * e->n, &a.f);
     GCHK(args.commit(e->stream));
-    hipLaunchKernelGGL(elliptic_p1_rows, dim3((unsigned)((e->n + 255) / 256)), dim3(256), 0, e->stream, a);
+    if (e->order == 2) {
+        EllipticP2Args a2;
+        a2.nx = a.nx; a2.ny = a.ny; a2.rowptr = a.rowptr; a2.w = a.w; a2.vals = a.vals; a2.f = a.f;
+        hipLaunchKernelGGL(elliptic_p2_rows, dim3((unsigned)((e->n + 255) / 256)), dim3(256), 0, e->stream, a2);
+    } else
+        hipLaunchKernelGGL(elliptic_p1_rows, dim3((unsigned)((e->n + 255) / 256)), dim3(256), 0, e->stream, a);
     HIPCHK(hipGetLastError());
     GCHK(args.flush(e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
@@ -4410,17 +4461,23 @@ gmrf_status gmrf_elliptic_p1_tangent_batch(gmrf_elliptic_p1* e, int64_t batch, c
     return GMRF_OK;
 }
 
-// src_q [batch][cells][3] -> b_out [batch][n]
+// src_q [batch][cells][nq] -> b_out [batch][n]
 gmrf_status gmrf_elliptic_p1_load(gmrf_elliptic_p1* e, int64_t batch, const double* src_q, double* b_out) {
     if (!e || !src_q || !b_out || !batch_ok(batch)) return bad_shape("bad elliptic load arguments (batch in [1, 4096])");
     GCHK(e->ready("pattern-only elliptic tangent"));
     EllipticLoadArgs a;
     a.nx = (int)e->nx; a.ny = (int)e->ny;
     Staging args(e->arena);
-    args.in(src_q, sizeof(double) * batch * e->cells * 3, &a.src);
+    args.in(src_q, sizeof(double) * batch * e->cells * e->nq, &a.src);
     args.out(b_out, sizeof(double) * batch * e->n, &a.b);
     GCHK(args.commit(e->stream));
-    hipLaunchKernelGGL(elliptic_p1_load_batch, dim3((unsigned)((e->n + 255) / 256), (unsigned)batch), dim3(256), 0, e->stream, a);
+    const dim3 grid((unsigned)((e->n + 255) / 256), (unsigned)batch);
+    if (e->order == 2) {
+        EllipticP2LoadArgs a2;
+        a2.nx = a.nx; a2.ny = a.ny; a2.src = a.src; a2.b = a.b;
+        hipLaunchKernelGGL(elliptic_p2_load_batch, grid, dim3(256), 0, e->stream, a2);
+    } else
+        hipLaunchKernelGGL(elliptic_p1_load_batch, grid, dim3(256), 0, e->stream, a);
     HIPCHK(hipGetLastError());
     GCHK(args.flush(e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));

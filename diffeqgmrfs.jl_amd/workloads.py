@@ -235,6 +235,111 @@ def p1_triangle_qpoints(nx: int, ny: int) -> np.ndarray:
     return np.stack([xq, yq], axis=2)
 
 
+# Lagrange{RefTriangle,2} in Ferrite's reference coordinates (vertices at xi = (1, 0), (0, 1), (0, 0), then the nodes of the edges
+# (1-2), (2-3), (3-1)) and the 4-point rule of degree 3 taken for QuadratureRule{RefTriangle}(3): what csrc/fem_assemble_p2.hpp
+# documents for the device and oracle/bt_oracle.py for the parity target.
+_P2_TRI_RULE = ((1.0 / 3.0, 1.0 / 3.0, -27.0 / 96.0), (0.2, 0.2, 25.0 / 96.0), (0.6, 0.2, 25.0 / 96.0), (0.2, 0.6, 25.0 / 96.0))
+
+
+def _p2_ref_grad(xi: float, eta: float) -> np.ndarray:
+    g = 1.0 - xi - eta
+    return np.array([[4.0 * xi - 1.0, 0.0], [0.0, 4.0 * eta - 1.0], [-(4.0 * g - 1.0), -(4.0 * g - 1.0)],
+                     [4.0 * eta, 4.0 * xi], [-4.0 * eta, 4.0 * (g - eta)], [4.0 * (g - xi), -4.0 * xi]])
+
+
+def _p2_lattice_cells(nx: int, ny: int):
+    """(cells, 6) lattice dofs of the quadratic triangles on `_grid_triangles` in Ferrite's local order, and the (cells, 3)
+    vertex node ids.  Dofs are the points of the (2 nx - 1) x (2 ny - 1) lattice, x fastest."""
+    tri = _grid_triangles(nx, ny)
+    vI, vJ = 2 * (tri % nx), 2 * (tri // nx)
+    I = np.concatenate([vI, (vI + np.roll(vI, -1, axis=1)) // 2], axis=1)
+    J = np.concatenate([vJ, (vJ + np.roll(vJ, -1, axis=1)) // 2], axis=1)
+    return J * (2 * nx - 1) + I, tri
+
+
+def p2_unit_square(nx: int, ny: int):
+    """Lumped mass (diag), stiffness G and coordinates (X, Y) of quadratic triangles on the unit square: the triangulation of
+    `p1_unit_square` on nx x ny vertices, dofs = the points of the (2 nx - 1) x (2 ny - 1) lattice (vertices and edge midpoints, x
+    fastest), so a block of consecutive lattice rows is a contiguous index range.  G is assembled under the 4-point rule of
+    degree 3 (it is `assemble_darcy_diff_matrix_p2` of the oracle with coefficient 1 and no constraints; explicit zeros kept).
+
+    The lumped mass is the HRZ (diagonal-scaling) one: every cell gives |T| / 19 to each of its vertices and 16 |T| / 57 to each
+    of its edge midpoints -- the diagonal of the consistent P2 mass (|T| / 30 and 8 |T| / 45) scaled to sum to |T|.  Row-sum
+    lumping is unusable here (a P2 vertex function integrates to zero).  This is a stated deviation: the reference lumps inside
+    GaussianMarkovRandomFields.jl, which is not available to compare against."""
+    cells, tri = _p2_lattice_cells(nx, ny)
+    xs, ys = np.linspace(0.0, 1.0, nx), np.linspace(0.0, 1.0, ny)
+    Xv, Yv = xs[tri % nx], ys[tri // nx]
+    a, b = Xv[:, 0] - Xv[:, 2], Xv[:, 1] - Xv[:, 2]            # J = [[a, b], [c, d]] = [x_1 - x_3, x_2 - x_3]
+    c, d = Yv[:, 0] - Yv[:, 2], Yv[:, 1] - Yv[:, 2]
+    det = a * d - b * c
+    Ge = np.zeros((cells.shape[0], 6, 6))
+    for xi, eta, wq in _P2_TRI_RULE:
+        dN = _p2_ref_grad(xi, eta)
+        gx = (d[:, None] * dN[None, :, 0] - c[:, None] * dN[None, :, 1]) / det[:, None]        # J^-T grad_xi
+        gy = (-b[:, None] * dN[None, :, 0] + a[:, None] * dN[None, :, 1]) / det[:, None]
+        Ge += (gx[:, :, None] * gx[:, None, :] + gy[:, :, None] * gy[:, None, :]) * (wq * np.abs(det))[:, None, None]
+    W, H = 2 * nx - 1, 2 * ny - 1
+    n = W * H
+    rows = np.repeat(cells[:, :, None], 6, axis=2).ravel()
+    cols = np.repeat(cells[:, None, :], 6, axis=1).ravel()
+    G = sp.coo_matrix((Ge.ravel(), (rows, cols)), shape=(n, n)).tocsr()
+    G.sort_indices()
+    area = 0.5 * np.abs(det)
+    share = np.concatenate([np.repeat((area / 19.0)[:, None], 3, axis=1), np.repeat((16.0 * area / 57.0)[:, None], 3, axis=1)], axis=1)
+    lumped = np.bincount(cells.ravel(), weights=share.ravel(), minlength=n)
+    I, J = np.arange(n) % W, np.arange(n) // W
+    X = 0.5 * (xs[I // 2] + xs[(I + 1) // 2])
+    Y = 0.5 * (ys[J // 2] + ys[(J + 1) // 2])
+    return lumped, G, (X, Y)
+
+
+def p2_triangle_qpoints(nx: int, ny: int) -> np.ndarray:
+    """(cells, 4, 2) quadrature points of the 4-point rule of degree 3 on the cells of `_grid_triangles`:
+    xi x_1 + eta x_2 + (1 - xi - eta) x_3 -- what `EllipticP1Tangent(nx, ny, order=2).qpoints` reports."""
+    tri = _grid_triangles(nx, ny)
+    X = np.linspace(0.0, 1.0, nx)[tri % nx]
+    Y = np.linspace(0.0, 1.0, ny)[tri // nx]
+    out = np.empty((tri.shape[0], 4, 2))
+    for q, (xi, eta, _) in enumerate(_P2_TRI_RULE):
+        g = 1.0 - xi - eta
+        out[:, q, 0] = (xi * X[:, 0] + eta * X[:, 1]) + g * X[:, 2]
+        out[:, q, 1] = (xi * Y[:, 0] + eta * Y[:, 1]) + g * Y[:, 2]
+    return out
+
+
+def _elliptic_gauss_newton_batch_p2(nx: int, ny: int, B: int, rows_per_block: int, bnd_noise: float, fem_noise: float, amps):
+    """`elliptic_gauss_newton_batch` on quadratic triangles: the same dictionary on the (2 nx - 1) x (2 ny - 1) lattice.
+    Dofs that share a cell are at most 2 lattice rows apart and both K C^-1 K and J'J are two hops, so the posterior reaches 4
+    rows: rows_per_block >= 4 must divide the odd 2 ny - 1 (5 with ny = 3, 8, 13, ... is the smallest)."""
+    W, H = 2 * nx - 1, 2 * ny - 1
+    assert H % rows_per_block == 0, "rows_per_block must divide 2 ny - 1"
+    lumped, G, (X, Y) = p2_unit_square(nx, ny)
+    kappa = math.sqrt(8.0 * 1.0) / 0.1
+    Q0 = matern_precision_2d(lumped, G, kappa, alpha=2)
+    n = W * H
+    I, J = np.arange(n) % W, np.arange(n) // W
+    on_bnd = (I == 0) | (J == 0) | (I == W - 1) | (J == H - 1)
+    Ab = sp.diags(on_bnd.astype(np.float64)).tocsr()
+    Q = (Q0 + bnd_noise * (Ab.T @ Ab)).tocsc()
+    Q = ((Q + Q.T) * 0.5).tocsc()
+    Q.sort_indices()
+    n_blocks = H // rows_per_block
+    P = G.copy()
+    P.data = np.ones_like(P.data)                             # the tangent's pattern: every pair of dofs that share a cell
+    post = abs(Q) + (P.T @ P)
+    assert block_bandwidth_ok(post, n_blocks), "Q + J'J is not block tridiagonal at this rows_per_block"
+    qp = p2_triangle_qpoints(nx, ny)
+    truth, src_q = np.empty((B, n)), np.empty((B,) + qp.shape[:2])
+    for p in range(B):
+        truth[p], _ = elliptic_truth(X, Y, amps[p])
+        _, src_q[p] = elliptic_truth(qp[:, :, 0], qp[:, :, 1], amps[p])
+    x_prior = np.zeros((B, n))
+    return {"Q": Q, "q_values": Q.data.copy(), "x_prior": x_prior, "Qx_prior": np.zeros((B, n)), "x0": x_prior.copy(),
+            "qpoints": qp, "src_q": src_q, "truth": truth, "amps": amps, "noise": fem_noise, "n_blocks": n_blocks,
+            "n": n, "m": n, "nx": nx, "ny": ny, "order": 2}
+
+
 def elliptic_truth(x, y, amp: float):
     """u = sin(pi x) sin(pi y) + amp sin(2 pi x) sin(2 pi y), which vanishes on the boundary of the unit square, and its
     source f_src = -Lap u + u^3.  Returns (u, f_src) at the points (x, y)."""
@@ -245,7 +350,7 @@ def elliptic_truth(x, y, amp: float):
 
 
 def elliptic_gauss_newton_batch(n_xy, B: int, rows_per_block: int = 2, bnd_noise: float = 1e12, fem_noise: float = 3e13,
-                                amps=None):
+                                amps=None, order: int = 1):
     """The ingredients of the reference's Gauss-Newton loop for -Lap u + u^3 = f (`gmrf_fem_solve`,
     _research/elliptic_chen24.jl:118-161) for B problems on one P1 mesh; n_xy: nodes per side, or (nx, ny).  Problem p has the
     true solution `elliptic_truth(., ., amps[p])` (default amps[p] = p / 2).  Returns a dict with
@@ -253,8 +358,19 @@ def elliptic_gauss_newton_batch(n_xy, B: int, rows_per_block: int = 2, bnd_noise
       q_values   its values (shared by every problem),
       x_prior, Qx_prior, x0   (B, n): the conditioned mean (zero: u vanishes on the boundary), Q x_prior, the start point (:148-154),
       qpoints (cells, 3, 2), src_q (B, cells, 3) the sources at the quadrature points, truth (B, n) the nodal true solutions,
-      amps, noise, n_blocks, n, m, nx, ny."""
+      amps, noise, n_blocks, n, m, nx, ny.
+    order = 2: the same on the reference's default quadratic triangles (`element_order = 2`, :118-122) -- n_xy counts vertices,
+    the dofs are the (2 nx - 1) x (2 ny - 1) lattice of `p2_unit_square` (whose lumped mass is a stated deviation), qpoints
+    (cells, 4, 2), src_q (B, cells, 4), n_blocks = (2 ny - 1) // rows_per_block with rows_per_block >= 4 (5 is the smallest), and
+    the key "order"."""
     nx, ny = (int(n_xy), int(n_xy)) if np.ndim(n_xy) == 0 else (int(n_xy[0]), int(n_xy[1]))
+    if order not in (1, 2):
+        raise ValueError("order must be 1 or 2")
+    if order == 2:
+        amps = 0.5 * np.arange(B) if amps is None else np.asarray(amps, dtype=np.float64)
+        if amps.shape != (B,):
+            raise ValueError(f"amps: expected {B} amplitudes")
+        return _elliptic_gauss_newton_batch_p2(nx, ny, B, rows_per_block, bnd_noise, fem_noise, amps)
     assert ny % rows_per_block == 0
     lumped, G, _, (X, Y) = p1_unit_square(nx, ny)
     kappa = math.sqrt(8.0 * 1.0) / 0.1
@@ -279,9 +395,10 @@ def elliptic_gauss_newton_batch(n_xy, B: int, rows_per_block: int = 2, bnd_noise
             "n": n, "m": n, "nx": nx, "ny": ny}
 
 
-def elliptic_gauss_newton(n_xy, rows_per_block: int = 2, bnd_noise: float = 1e12, fem_noise: float = 3e13, amp: float = 1.0):
+def elliptic_gauss_newton(n_xy, rows_per_block: int = 2, bnd_noise: float = 1e12, fem_noise: float = 3e13, amp: float = 1.0,
+                          order: int = 1):
     """One problem of `elliptic_gauss_newton_batch` (its arrays without the batch axis)."""
-    w = elliptic_gauss_newton_batch(n_xy, 1, rows_per_block, bnd_noise, fem_noise, amps=[amp])
+    w = elliptic_gauss_newton_batch(n_xy, 1, rows_per_block, bnd_noise, fem_noise, amps=[amp], order=order)
     for k in ("x_prior", "Qx_prior", "x0", "src_q", "truth"):
         w[k] = w[k][0]
     w["amp"] = float(amp)

@@ -634,8 +634,16 @@ gmrf_status gmrf_elliptic_p1_qpoints(const gmrf_elliptic_p1* e, double* xy);
 gmrf_status gmrf_elliptic_p1_tangent(gmrf_elliptic_p1* e, const double* w, double* vals_out, double* f_out);
 gmrf_status gmrf_elliptic_p1_tangent_batch(gmrf_elliptic_p1* e, int64_t batch, const double* w, double* vals_out, double* f_out);
 gmrf_status gmrf_elliptic_p1_load(gmrf_elliptic_p1* e, int64_t batch, const double* src_q, double* b_out);
+/* The same tangent, residual and load with the reference's default element (element_order = 2 of gmrf_fem_solve, :118-122):
+ * Lagrange{RefTriangle,2} under QuadratureRule{RefTriangle}(3).  Element, 4-point rule, lattice and local node order are those of
+ * gmrf_darcy_p2_create (see its comment): dofs are the points of the (2 nx - 1) x (2 ny - 1) lattice, x fastest, n = m =
+ * (2 nx - 1)(2 ny - 1), and the pattern is exactly gmrf_darcy_p2_create(nx, ny)'s (explicit zeros included).  Prescribed dofs are
+ * the lattice points on the four sides.  The handle is the P1 type: _pattern / _qpoints / _tangent / _tangent_batch / _load /
+ * _destroy and gmrf_gn_create_elliptic serve both orders, with xy [cells][4][2] and src_q [batch][cells][4] for this one
+ * (cells = 2 (nx - 1)(ny - 1), numbered as for P1).  nx, ny <= 16384.  device -1: pattern and quadrature points only. */
+gmrf_status gmrf_elliptic_p2_create(int32_t device, void* stream, int64_t nx, int64_t ny, gmrf_elliptic_p1** out);
 /* The Gauss-Newton driver bound to the elliptic tangent (the loop of gmrf_fem_solve, :142-166): the same gmrf_gn type and the
- * same binding rules (one device, one stream, as->n == as->m == nx ny, as->nnz_j == the pattern's nnz; anything else is
+ * same binding rules (one device, one stream, as->n == as->m == the tangent's n, as->nnz_j == the pattern's nnz; anything else is
  * GMRF_ERR_BAD_SHAPE); gmrf_gn_run / _finalize / _destroy serve both tangents.  The stop rule is the driver's relative
  * objective change, not the Newton decrement of :156-159. */
 gmrf_status gmrf_gn_create_elliptic(gmrf_handle* h, gmrf_assembler* as, gmrf_elliptic_p1* e, gmrf_gn** out);

@@ -592,23 +592,29 @@ function tangent_batch!(vals::Matrix{Float64}, f::Matrix{Float64}, b::BurgersP1T
 end
 
 # Tangent, residual and load of the nonlinear elliptic benchmark -Lap u + u^3 = f (f_and_J, _research/elliptic_chen24.jl:280-285,
-# with assemble_J_cube :231-278 and assemble_J_diff_and_f :179-228) on the structured P1 triangle mesh of DarcyP1Assembler
+# with assemble_J_cube :231-278 and assemble_J_diff_and_f :179-228) on the structured triangle mesh of DarcyP1Assembler: P1, or
+# with order = 2 the reference's default quadratic triangles on the (2nx-1) x (2ny-1) lattice under the 4-point rule
 mutable struct EllipticP1Tangent
     handle::Ptr{Cvoid}
     pattern::SparseMatrixCSC{Float64,Int}     # TRANSPOSE of J's pattern (CSC of J' = CSR of J), values 1.0: DarcyP1Assembler's
     rows::Int
-    qpoints::Array{Float64,3}                 # (2, 3, cells): x / y of quadrature point q of a cell -- evaluate the source there
+    qpoints::Array{Float64,3}                 # (2, nq, cells): x / y of quadrature point q of a cell -- evaluate the source there (nq = 3, order 2: 4)
 end
 
-function EllipticP1Tangent(nx::Integer, ny::Integer; device::Integer = 0, stream::Ptr{Cvoid} = C_NULL)
+function EllipticP1Tangent(nx::Integer, ny::Integer; device::Integer = 0, stream::Ptr{Cvoid} = C_NULL, order::Integer = 1)
+    order in (1, 2) || throw(ArgumentError("order must be 1 or 2"))
     h = Ref{Ptr{Cvoid}}(C_NULL)
-    check(ccall((:gmrf_elliptic_p1_create, libgmrf), Int32, (Int32, Ptr{Cvoid}, Int64, Int64, Ref{Ptr{Cvoid}}), device, stream, nx, ny, h))
+    if order == 2
+        check(ccall((:gmrf_elliptic_p2_create, libgmrf), Int32, (Int32, Ptr{Cvoid}, Int64, Int64, Ref{Ptr{Cvoid}}), device, stream, nx, ny, h))
+    else
+        check(ccall((:gmrf_elliptic_p1_create, libgmrf), Int32, (Int32, Ptr{Cvoid}, Int64, Int64, Ref{Ptr{Cvoid}}), device, stream, nx, ny, h))
+    end
     nnz_out = Ref{Int64}(0)
     check(ccall((:gmrf_elliptic_p1_pattern, libgmrf), Int32, (Ptr{Cvoid}, Ref{Int64}, Ptr{Int64}, Ptr{Int64}, Int32), h[], nnz_out, C_NULL, C_NULL, 1))
-    n = nx * ny
+    n = order == 2 ? (2nx - 1) * (2ny - 1) : nx * ny
     rowptr = Vector{Int64}(undef, n + 1); colidx = Vector{Int64}(undef, nnz_out[])
     check(ccall((:gmrf_elliptic_p1_pattern, libgmrf), Int32, (Ptr{Cvoid}, Ref{Int64}, Ptr{Int64}, Ptr{Int64}, Int32), h[], nnz_out, rowptr, colidx, 1))
-    qp = Array{Float64,3}(undef, 2, 3, 2 * (nx - 1) * (ny - 1))
+    qp = Array{Float64,3}(undef, 2, order == 2 ? 4 : 3, 2 * (nx - 1) * (ny - 1))
     check(ccall((:gmrf_elliptic_p1_qpoints, libgmrf), Int32, (Ptr{Cvoid}, Ptr{Float64}), h[], qp))
     e = EllipticP1Tangent(h[], SparseMatrixCSC(n, n, rowptr, colidx, ones(nnz_out[])), n, qp)
     finalizer(x -> ccall((:gmrf_elliptic_p1_destroy, libgmrf), Int32, (Ptr{Cvoid},), x.handle), e)

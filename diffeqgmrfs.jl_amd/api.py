@@ -348,22 +348,40 @@ class DarcyP1Assembler:
 
 
 class BurgersP1Tangent:
-    """Residual and tangent of the implicit-Euler Burgers space-time system on the device (second
+    """Residual and tangent of the Burgers space-time system on the device (second
     piece): `f_and_J` of /root/reference/scripts/burgers/solve_burgers_gmrf-fem.jl:118-149 with
     `assemble_burgers_advection_matrix` (src/problems/burgers.jl:5-59) per time slice and the static part of
     `assemble_burgers_mass_diffusion_matrices` (:60-98), on the periodic P1 line (ns nodes on [0,1), nt slices,
     time-major index) or, with order = 2, the quadratic periodic line.  `pattern` is the CSR matrix (values 1, (nt-1) ns x nt ns, 6 entries per row) whose `.data`
-    order `tangent()` fills -- the `J` of `PosteriorAssembler`.  device = -1: pattern only (no GPU needed)."""
+    order `tangent()` fills -- the `J` of `PosteriorAssembler`.  device = -1: pattern only (no GPU needed).
 
-    def __init__(self, ns: int, nt: int, dt: float, nu: float, device: int = 0, stream: int = 0, order: int = 1):
-        """order = 2: the quadratic periodic line of the reference's scripts (src/utils.jl:42-49): ns = 2 N_x dofs numbered by
-        position, vertex rows of J with 10 entries, midpoint rows with 6 (gmrf_burgers_p2_create)."""
+    scheme = "cn": Crank-Nicolson, `f_and_J_CN` of _research/burgers_chen24.jl:121-132, :195-226 (the same pattern).
+    bc = "dirichlet": an interval of `length` with homogeneous Dirichlet ends (:101-108), ns = order * cells + 1 dofs numbered by
+    position; the rows and columns of dofs 0 and ns - 1 hold stored zeros and f is 0 there (a prior pins them), and a row holds
+    its in-range columns only.  All 8 combinations of (order, scheme, bc) are served (gmrf_burgers_line_create)."""
+
+    SCHEMES = {"euler": 0, "cn": 1}
+    BCS = {"periodic": 0, "dirichlet": 1}
+
+    def __init__(self, ns: int, nt: int, dt: float, nu: float, device: int = 0, stream: int = 0, order: int = 1,
+                 scheme: str = "euler", bc: str = "periodic", length: float = 1.0):
+        """ns: the number of dofs.  order = 2: the quadratic line of the reference's scripts (src/utils.jl:42-49): dofs numbered by
+        position, vertex rows of J with 10 entries, midpoint rows with 6; ns = 2 N_x (periodic) or 2 N_x + 1 (dirichlet)."""
         self.ns, self.nt, self.dt, self.nu, self.order = int(ns), int(nt), float(dt), float(nu), int(order)
+        self.scheme, self.bc, self.length = scheme, bc, float(length)
+        if scheme not in self.SCHEMES or bc not in self.BCS or self.order not in (1, 2):
+            raise GmrfError(_cabi.ERR_BAD_SHAPE, f"BurgersP1Tangent: order {order!r} (1, 2), scheme {scheme!r} {tuple(self.SCHEMES)}, "
+                                                 f"bc {bc!r} {tuple(self.BCS)}")
+        ends = 1 if bc == "dirichlet" else 0
+        if (self.ns - ends) % self.order:
+            raise GmrfError(_cabi.ERR_BAD_SHAPE, f"BurgersP1Tangent: ns = {ns} is not {self.order} * cells + {ends}, the dofs of the "
+                                                 f"order-{self.order} {bc} line")
+        self.cells = (self.ns - ends) // self.order
         self.rows, self.n = (self.nt - 1) * self.ns, self.nt * self.ns
         self._h = C.c_void_p()
         lib = _cabi.load()
-        create = lib.gmrf_burgers_p2_create if self.order == 2 else lib.gmrf_burgers_p1_create
-        _cabi.check(create(device, C.c_void_p(stream), ns, nt, float(dt), float(nu), C.byref(self._h)))
+        _cabi.check(lib.gmrf_burgers_line_create(device, C.c_void_p(stream), self.cells, nt, float(dt), float(nu), self.order,
+                                                 self.SCHEMES[scheme], self.BCS[bc], self.length, C.byref(self._h)))
         nnz = C.c_int64(0)
         _cabi.check(lib.gmrf_burgers_p1_pattern(self._h, C.byref(nnz), None, None, 0))
         self.nnz = int(nnz.value)
@@ -655,7 +673,10 @@ class GaussNewtonBatch:
 
     With an `EllipticP1Tangent` the same loop is the Gauss-Newton loop of _research/elliptic_chen24.jl:142-166: pass the load
     `tangent.load(src_q)` as `y` and noise = 3e13.  The stop rule stays the relative objective change (the reference's Newton
-    decrement lives in a package that is not available)."""
+    decrement lives in a package that is not available).
+
+    With a `BurgersP1Tangent(..., scheme="cn", bc="dirichlet")` it is the loop of _research/burgers_chen24.jl:139-152 on the
+    problems of `workloads.burgers_chen24_batch` (zero observations; the same stop rule)."""
 
     def __init__(self, F: "TridiagonalCholeskyFactor", asm: PosteriorAssembler, tangent: "BurgersP1Tangent | EllipticP1Tangent"):
         self.F, self.asm, self.tangent = F, asm, tangent          # (kept alive: the library holds their handles)

@@ -30,6 +30,7 @@
 #include "../../include/gmrf_hip.h"
 #include "assemble.hpp"
 #include "fem_assemble.hpp"
+#include "burgers_line.hpp"
 #include "gemm_f64.hpp"
 #include "gemm_f64_dma.hpp"
 #include "microbench.hpp"
@@ -4097,92 +4098,88 @@ gmrf_status gmrf_darcy_p1_assemble(gmrf_darcy_p1* d, const double* coeff_table, 
 // --------------------------------------------------------------------------------- Burgers tangent (8f rank 4)
 struct gmrf_burgers_p1 : DevCtx {       // device -1: pattern only
     int64_t ns = 0, nt = 0, rows = 0, nnz = 0;
-    int order = 1;                      // 1: P1 line (6 entries per row), 2: quadratic line (10 / 6 entries per row)
-    double dt = 0.0, nu = 0.0;
+    int order = 1;                      // 1: P1 line, 2: quadratic line
+    int scheme = GMRF_BURGERS_EULER, bc = GMRF_BURGERS_PERIODIC;
+    double dt = 0.0, nu = 0.0, h = 0.0; // h: cell length
+    std::vector<int64_t> rowptr;        // 0-based row pointer of J
+    int64_t* d_rowptr = nullptr;        // dirichlet only: the periodic rows have a closed form
     DevBuf arena;                       // host arguments of the current call (Staging)
 };
 
-static gmrf_status burgers_line_create(int32_t device, void* stream, int64_t ns, int64_t nt, double dt, double nu, int order,
-                                       gmrf_burgers_p1** out) {
-    if (!out || ns < 3 || nt < 2 || ns > (1 << 24) || nt > (1 << 20) || !(dt > 0.0) || !(nu >= 0.0))
-        return bad_shape("bad Burgers mesh (ns >= 3 nodes, nt >= 2 slices, dt > 0, nu >= 0)");
-    if (order == 2 && (ns % 2 || ns < 6)) return bad_shape("the quadratic line has an even number of dofs (>= 6): two per cell");
+// The in-slice columns of row i, ascending: the window {i-1, i, i+1} (P1, quadratic midpoint) or {i-2 .. i+2} (quadratic
+// vertex), wrapped on the periodic line, clipped to [0, ns) on the Dirichlet interval.  Returns their number.
+static int burgers_line_row_cols(const gmrf_burgers_p1* b, int64_t i, int64_t (&c)[5]) {
+    const int64_t r = (b->order == 2 && !(i & 1)) ? 2 : 1;
+    int cnt = 0;
+    for (int64_t j = i - r; j <= i + r; ++j) {
+        if (b->bc == GMRF_BURGERS_PERIODIC) c[cnt++] = (j + b->ns) % b->ns;
+        else if (j >= 0 && j < b->ns) c[cnt++] = j;
+    }
+    std::sort(c, c + cnt);
+    return cnt;
+}
+
+gmrf_status gmrf_burgers_line_create(int32_t device, void* stream, int64_t nc, int64_t nt, double dt, double nu, int32_t order,
+                                     int32_t scheme, int32_t bc, double length, gmrf_burgers_p1** out) {
+    const bool dirichlet = bc == GMRF_BURGERS_DIRICHLET;
+    if (!out || (order != 1 && order != 2) || (scheme != GMRF_BURGERS_EULER && scheme != GMRF_BURGERS_CN) ||
+        (bc != GMRF_BURGERS_PERIODIC && !dirichlet))
+        return bad_shape("bad Burgers line (order 1 or 2, scheme euler or cn, bc periodic or dirichlet)");
+    if (nc < (dirichlet ? 2 : 3) || nt < 2 || nc > (1 << 24) || order * nc + (dirichlet ? 1 : 0) > (1 << 24) || nt > (1 << 20) ||
+        !(dt > 0.0) || !(nu >= 0.0) || !(length > 0.0) || !std::isfinite(length))
+        return bad_shape("bad Burgers mesh (>= 3 cells, >= 2 on the Dirichlet interval; nt >= 2 slices, dt > 0, nu >= 0, length > 0)");
     std::unique_ptr<gmrf_burgers_p1, gmrf_status (*)(gmrf_burgers_p1*)> guard(new gmrf_burgers_p1(), gmrf_burgers_p1_destroy);
     gmrf_burgers_p1* b = guard.get();
-    b->ns = ns; b->nt = nt; b->rows = (nt - 1) * ns; b->nnz = b->rows * (order == 2 ? 8 : 6); b->dt = dt; b->nu = nu; b->order = order;
-    GCHK(b->open(device, stream, hipStreamNonBlocking, "gmrf_burgers_p1_create"));
+    b->ns = order * nc + (dirichlet ? 1 : 0); b->nt = nt; b->rows = (nt - 1) * b->ns; b->dt = dt; b->nu = nu; b->order = order;
+    b->scheme = scheme; b->bc = bc; b->h = length / (double)nc;
+    b->rowptr.resize((size_t)b->rows + 1);
+    b->rowptr[0] = 0;
+    for (int64_t r = 0; r < b->rows; ++r) {
+        int64_t c[5];
+        b->rowptr[(size_t)r + 1] = b->rowptr[(size_t)r] + 2 * burgers_line_row_cols(b, r % b->ns, c);
+    }
+    b->nnz = b->rowptr[(size_t)b->rows];
+    GCHK(b->open(device, stream, hipStreamNonBlocking, "gmrf_burgers_line_create"));
+    if (b->device >= 0 && dirichlet) {
+        HIPCHK(hipMalloc(&b->d_rowptr, sizeof(int64_t) * (b->rows + 1)));
+        HIPCHK(hipMemcpyAsync(b->d_rowptr, b->rowptr.data(), sizeof(int64_t) * (b->rows + 1), hipMemcpyHostToDevice, b->stream));
+        HIPCHK(hipStreamSynchronize(b->stream));
+    }
     *out = guard.release();
     return GMRF_OK;
 }
 
 gmrf_status gmrf_burgers_p1_create(int32_t device, void* stream, int64_t ns, int64_t nt, double dt, double nu, gmrf_burgers_p1** out) {
-    return burgers_line_create(device, stream, ns, nt, dt, nu, 1, out);
+    return gmrf_burgers_line_create(device, stream, ns, nt, dt, nu, 1, GMRF_BURGERS_EULER, GMRF_BURGERS_PERIODIC, 1.0, out);
 }
 gmrf_status gmrf_burgers_p2_create(int32_t device, void* stream, int64_t ns, int64_t nt, double dt, double nu, gmrf_burgers_p1** out) {
-    return burgers_line_create(device, stream, ns, nt, dt, nu, 2, out);
+    if (ns % 2) return bad_shape("the quadratic line has an even number of dofs (>= 6): two per cell");
+    return gmrf_burgers_line_create(device, stream, ns / 2, nt, dt, nu, 2, GMRF_BURGERS_EULER, GMRF_BURGERS_PERIODIC, 1.0, out);
 }
 
 gmrf_status gmrf_burgers_p1_destroy(gmrf_burgers_p1* b) {
     if (!b) return GMRF_OK;
     b->close();
-    if (b->has_device()) b->arena.release();
+    if (b->has_device()) { free_dev(b->d_rowptr); b->arena.release(); }
     delete b;
     return GMRF_OK;
 }
 
-// CSR pattern of J: row (t, i), t = 1 .. nt-1 (0-based slices), holds the columns {i-1, i, i+1} (periodic) of slices
-// t-1 and t, ascending
+// CSR pattern of J: row (t, i), t = 1 .. nt-1 (0-based slices), holds the columns of burgers_line_row_cols of slices t-1 and t,
+// ascending
 gmrf_status gmrf_burgers_p1_pattern(const gmrf_burgers_p1* b, int64_t* nnz_out, int64_t* rowptr, int64_t* colidx,
                                     int32_t index_base) {
     if (!b) return bad_shape("null handle");
     if (nnz_out) *nnz_out = b->nnz;
-    if (b->order == 2) {
-        // quadratic line: vertex rows (even i) hold the columns i-2 .. i+2, midpoint rows i-1 .. i+1 (periodic), of slices t-1 and t
-        if (rowptr) {
-            for (int64_t r = 0; r < b->rows; ++r) rowptr[r] = burgers_p2_row_offset(b->ns, r / b->ns, r % b->ns) + index_base;
-            rowptr[b->rows] = b->nnz + index_base;
-        }
-        if (colidx)
-            for (int64_t r = 0; r < b->rows; ++r) {
-                const int64_t t = r / b->ns + 1, i = r % b->ns;
-                const int cnt = (i & 1) ? 3 : 5;
-                int64_t c[5];
-                for (int k = 0; k < cnt; ++k) c[k] = (i - cnt / 2 + k + b->ns) % b->ns;
-                std::sort(c, c + cnt);
-                int64_t* out = colidx + burgers_p2_row_offset(b->ns, t - 1, i);
-                for (int k = 0; k < cnt; ++k) { out[k] = (t - 1) * b->ns + c[k] + index_base; out[cnt + k] = t * b->ns + c[k] + index_base; }
-            }
-        return GMRF_OK;
-    }
-    if (rowptr) for (int64_t r = 0; r <= b->rows; ++r) rowptr[r] = 6 * r + index_base;
+    if (rowptr) for (int64_t r = 0; r <= b->rows; ++r) rowptr[r] = b->rowptr[(size_t)r] + index_base;
     if (colidx)
         for (int64_t r = 0; r < b->rows; ++r) {
-            const int64_t t = r / b->ns + 1, i = r % b->ns;
-            int64_t c[3] = {(i + b->ns - 1) % b->ns, i, (i + 1) % b->ns};
-            std::sort(c, c + 3);
-            for (int k = 0; k < 3; ++k) {
-                colidx[6 * r + k] = (t - 1) * b->ns + c[k] + index_base;
-                colidx[6 * r + 3 + k] = t * b->ns + c[k] + index_base;
-            }
+            const int64_t t = r / b->ns + 1;
+            int64_t c[5];
+            const int cnt = burgers_line_row_cols(b, r % b->ns, c);
+            int64_t* out = colidx + b->rowptr[(size_t)r];
+            for (int k = 0; k < cnt; ++k) { out[k] = (t - 1) * b->ns + c[k] + index_base; out[cnt + k] = t * b->ns + c[k] + index_base; }
         }
-    return GMRF_OK;
-}
-
-gmrf_status gmrf_burgers_p1_tangent(gmrf_burgers_p1* b, const double* w, double* vals_out, double* f_out) {
-    if (!b || !w || !vals_out || !f_out) return bad_shape("bad Burgers tangent arguments");
-    GCHK(b->ready("pattern-only Burgers assembler"));
-    BurgersP1Args a;
-    a.ns = (int)b->ns; a.nt = (int)b->nt; a.dt = b->dt; a.nu = b->nu;
-    Staging args(b->arena);
-    args.in(w, sizeof(double) * b->ns * b->nt, &a.w);
-    args.out(vals_out, sizeof(double) * b->nnz, &a.vals);
-    args.out(f_out, sizeof(double) * b->rows, &a.f);
-    GCHK(args.commit(b->stream));
-    if (b->order == 2) hipLaunchKernelGGL(burgers_p2_rows, dim3((unsigned)((b->rows + 255) / 256)), dim3(256), 0, b->stream, a);
-    else hipLaunchKernelGGL(burgers_p1_rows, dim3((unsigned)((b->rows + 255) / 256)), dim3(256), 0, b->stream, a);
-    HIPCHK(hipGetLastError());
-    GCHK(args.flush(b->stream));
-    HIPCHK(hipStreamSynchronize(b->stream));
     return GMRF_OK;
 }
 
@@ -4190,14 +4187,56 @@ gmrf_status gmrf_burgers_p1_tangent(gmrf_burgers_p1* b, const double* w, double*
 // Problem-major arrays ([batch][...]); host or device pointers like the one-problem calls.
 static bool batch_ok(int64_t batch) { return batch >= 1 && batch <= 4096; }
 
+// Implicit Euler on the periodic unit line keeps the kernels of fem_assemble.hpp (and their bits), which know the cell length
+// 1 / cells only; every other variant, another length included, is a burgers_line_rows instance.
+static bool burgers_unit_euler_periodic(const gmrf_burgers_p1* b) {
+    return b->scheme == GMRF_BURGERS_EULER && b->bc == GMRF_BURGERS_PERIODIC && b->h == 1.0 / (double)(b->ns / b->order);
+}
+
 static gmrf_status launch_tangent_batch(const gmrf_burgers_p1* b, hipStream_t st, int64_t batch, const double* d_w, double* d_vals,
                                         double* d_f) {
-    BurgersP1Args a;
-    a.ns = (int)b->ns; a.nt = (int)b->nt; a.dt = b->dt; a.nu = b->nu; a.w = d_w; a.vals = d_vals; a.f = d_f;
+    const bool cn = b->scheme == GMRF_BURGERS_CN, dir = b->bc == GMRF_BURGERS_DIRICHLET, p2 = b->order == 2;
     const dim3 grid((unsigned)((b->rows + 255) / 256), (unsigned)batch);
-    if (b->order == 2) hipLaunchKernelGGL(burgers_p2_rows_batch, grid, dim3(256), 0, st, a, b->nnz);
-    else hipLaunchKernelGGL(burgers_p1_rows_batch, grid, dim3(256), 0, st, a, b->nnz);
+    if (burgers_unit_euler_periodic(b)) {
+        BurgersP1Args a;
+        a.ns = (int)b->ns; a.nt = (int)b->nt; a.dt = b->dt; a.nu = b->nu; a.w = d_w; a.vals = d_vals; a.f = d_f;
+        if (p2) hipLaunchKernelGGL(burgers_p2_rows_batch, grid, dim3(256), 0, st, a, b->nnz);
+        else hipLaunchKernelGGL(burgers_p1_rows_batch, grid, dim3(256), 0, st, a, b->nnz);
+    } else {
+        BurgersLineArgs a;
+        a.ns = (int)b->ns; a.nt = (int)b->nt; a.dt = b->dt; a.nu = b->nu; a.h = b->h; a.rowptr = b->d_rowptr; a.w = d_w; a.vals = d_vals; a.f = d_f;
+        void (*kern)(BurgersLineArgs, int64_t) =
+            p2 ? (cn ? (dir ? burgers_line_rows<2, true, true> : burgers_line_rows<2, true, false>)
+                     : (dir ? burgers_line_rows<2, false, true> : burgers_line_rows<2, false, false>))
+               : (cn ? (dir ? burgers_line_rows<1, true, true> : burgers_line_rows<1, true, false>)
+                     : (dir ? burgers_line_rows<1, false, true> : burgers_line_rows<1, false, false>));
+        hipLaunchKernelGGL(kern, grid, dim3(256), 0, st, a, b->nnz);
+    }
     HIPCHK(hipGetLastError());
+    return GMRF_OK;
+}
+
+gmrf_status gmrf_burgers_p1_tangent(gmrf_burgers_p1* b, const double* w, double* vals_out, double* f_out) {
+    if (!b || !w || !vals_out || !f_out) return bad_shape("bad Burgers tangent arguments");
+    GCHK(b->ready("pattern-only Burgers assembler"));
+    const double* d_w;
+    double *d_vals, *d_f;
+    Staging args(b->arena);
+    args.in(w, sizeof(double) * b->ns * b->nt, &d_w);
+    args.out(vals_out, sizeof(double) * b->nnz, &d_vals);
+    args.out(f_out, sizeof(double) * b->rows, &d_f);
+    GCHK(args.commit(b->stream));
+    if (burgers_unit_euler_periodic(b)) {
+        BurgersP1Args a;
+        a.ns = (int)b->ns; a.nt = (int)b->nt; a.dt = b->dt; a.nu = b->nu; a.w = d_w; a.vals = d_vals; a.f = d_f;
+        if (b->order == 2) hipLaunchKernelGGL(burgers_p2_rows, dim3((unsigned)((b->rows + 255) / 256)), dim3(256), 0, b->stream, a);
+        else hipLaunchKernelGGL(burgers_p1_rows, dim3((unsigned)((b->rows + 255) / 256)), dim3(256), 0, b->stream, a);
+        HIPCHK(hipGetLastError());
+    } else {
+        GCHK(launch_tangent_batch(b, b->stream, 1, d_w, d_vals, d_f));
+    }
+    GCHK(args.flush(b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
     return GMRF_OK;
 }
 

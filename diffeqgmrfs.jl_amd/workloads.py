@@ -23,6 +23,7 @@ from dataclasses import dataclass, field
 
 import numpy as np
 import scipy.sparse as sp
+import scipy.sparse.linalg as spla
 
 
 @dataclass
@@ -601,6 +602,104 @@ def burgers_gauss_newton_batch(ns: int, nt: int, B: int, seed: int = 0, ic_noise
     return {"Q": Q, "q_values": q_values, "Qx_prior": np.stack([g["Qx_prior"] for g in parts]), "x_prior": x_prior, "x0": x0,
             "ic": ics, "noise": fem_noise, "n_blocks": nt, "n": ns * nt, "m": ns * (nt - 1), "dt": 1.0 / (nt - 1),
             "nu": 0.01 / math.pi}
+
+
+def dirichlet_line(nc: int, order: int = 1, length: float = 2.0):
+    """The interval of `length` in nc cells, P1 or quadratic, ns = order nc + 1 dofs numbered by position: consistent mass M,
+    lumped mass (row sums) and stiffness S, nothing prescribed.  Quadratic cell e has the dofs (2e, 2e+2, 2e+1) = (left, right,
+    middle) with the closed-form element matrices h/30 [4 -1 2; -1 4 2; 2 2 16] and 1/(3h) [7 1 -8; 1 7 -8; -8 -8 16]."""
+    h = length / nc
+    if order == 1:
+        dofs = np.stack([np.arange(nc), np.arange(nc) + 1], axis=1)
+        Me = h / 6.0 * np.array([[2.0, 1.0], [1.0, 2.0]])
+        Se = 1.0 / h * np.array([[1.0, -1.0], [-1.0, 1.0]])
+    elif order == 2:
+        dofs = np.stack([2 * np.arange(nc), 2 * np.arange(nc) + 2, 2 * np.arange(nc) + 1], axis=1)
+        Me = h / 30.0 * np.array([[4.0, -1.0, 2.0], [-1.0, 4.0, 2.0], [2.0, 2.0, 16.0]])
+        Se = 1.0 / (3.0 * h) * np.array([[7.0, 1.0, -8.0], [1.0, 7.0, -8.0], [-8.0, -8.0, 16.0]])
+    else:
+        raise ValueError("order 1 or 2")
+    ns, nb = order * nc + 1, order + 1
+    I = np.repeat(dofs, nb, axis=1).ravel()
+    J = np.tile(dofs, (1, nb)).ravel()
+    M = sp.coo_matrix((np.tile(Me.ravel(), nc), (I, J)), shape=(ns, ns)).tocsr()
+    S = sp.coo_matrix((np.tile(Se.ravel(), nc), (I, J)), shape=(ns, ns)).tocsr()
+    return M, np.asarray(M.sum(axis=1)).ravel(), S
+
+
+def burgers_cole_hopf(x, t: float, nu: float, amp: float = 1.0) -> np.ndarray:
+    """Burgers on the line with u(x, 0) = -amp sin(pi x) by the Cole-Hopf transform, 100-point Gauss-Hermite
+    (`SolveBurgers_ColeHopf`, _research/burgers_chen24.jl:68-74, with the amplitude carried through the transform):
+    u = -amp sum_k w_k sin(pi s_k) e_k / sum_k w_k e_k,  e_k = exp(-amp cos(pi s_k) / (2 pi nu)),  s_k = x - sqrt(4 nu t) z_k."""
+    z, wq = np.polynomial.hermite.hermgauss(100)
+    s = np.asarray(x, dtype=np.float64)[:, None] - math.sqrt(4.0 * nu * t) * z[None, :]
+    e = np.exp(-amp * np.cos(np.pi * s) / (2.0 * np.pi * nu))
+    return -amp * np.sum(wq * np.sin(np.pi * s) * e, axis=1) / np.sum(wq * e, axis=1)
+
+
+def burgers_chen24_batch(nc: int, nt: int, B: int, nu: float, amps, order: int = 2, scheme: str = "cn", ic_noise: float = 1e12,
+                         fem_noise: float = 1e12):
+    """The Burgers benchmark _research/burgers_chen24.jl as a batch of Gauss-Newton problems for
+    `BurgersP1Tangent(ns, nt, dt, nu, order=order, scheme=scheme, bc="dirichlet", length=2.0)`: nc cells on [-1, 1] with homogeneous
+    Dirichlet ends (:101-108), ns = order nc + 1 dofs x_i = -1 + 2 i / (ns - 1), nt slices on [0, T = 1]; problem p has the initial
+    condition -amps[p] sin(pi x) and the truth of `burgers_cole_hopf` at T.  Host side only.
+
+    The prior is THIS PROJECT'S restatement, not the reference's (`form_prior`, :79-99): the package that builds that one is
+    not available, and its Matern smoothness 2 / 1 (initial / spatial SPDE) is not reproduced.  It is the construction of
+    `burgers_prior_from_bulk` -- implicit-Euler state-space blocks G x_{t+1} = M x_t + noise with G = M + dt (nu c S + gamma Adv),
+    c = 1 / nu, gamma = -c bulk, and the Matern(alpha = 2) initial precision with range sqrt(1 / nc) -- with bulk = mean(ic) = 0
+    (so the advection term drops out and every problem has the same prior), on the lumped mass and stiffness of the Dirichlet
+    line's own element (`dirichlet_line`), and with the two end dofs of every slice pinned by 1e8 on their diagonal (the
+    reference's prescribed_noise = 1e-8).  The initial condition is observed at the interior dofs of slice 0 with ic_noise.
+
+    Returns the dict of `burgers_gauss_newton_batch` (Q the pattern (CSC), q_values (B, nnz), Qx_prior, x_prior, x0 (B, n), ic,
+    noise, n_blocks, n, m, dt, nu; x_prior = x0 = the mean of the prior conditioned on the initial condition, Qx_prior = Q x_prior,
+    as the reference passes mean(u_ic), :139-146) plus ns, nc, order, scheme, length = 2.0, amps, xs (ns,) and truth (B, ns) at T = 1."""
+    if order not in (1, 2) or nc < 2 or nt < 2 or B != len(amps):
+        raise ValueError("order 1 or 2, nc >= 2, nt >= 2, one amplitude per problem")
+    ns = order * nc + 1
+    dt = 1.0 / (nt - 1)
+    xs = -1.0 + 2.0 * np.arange(ns) / (ns - 1)
+    amps = np.asarray(amps, dtype=np.float64)
+    ics = -amps[:, None] * np.sin(np.pi * xs)[None, :]
+    ics[:, 0] = 0.0; ics[:, -1] = 0.0                   # (sin(+-pi) is 1.2e-16 in floating point)
+    _, lumped, S = dirichlet_line(nc, order, 2.0)
+    c = 1.0 / nu
+    tau = 0.1 * math.sqrt(c)
+    kappa = math.sqrt(8.0 * 1.5) / math.sqrt(1.0 / nc)
+    Ml = sp.diags(lumped)
+    K = (kappa ** 2) * Ml + S
+    Q0 = (K @ sp.diags(1.0 / lumped) @ K).tocsr()
+    Gm = (Ml + dt * (nu * c * S)).tocsr()               # (gamma = -c bulk = 0)
+    W = sp.diags(np.full(ns, 1.0 / (dt * tau * tau)) / lumped)
+    GWG, MWM, GWM = (Gm.T @ W @ Gm).tocsr(), (Ml.T @ W @ Ml).tocsr(), (Gm.T @ W @ Ml).tocsr()
+    pin = np.zeros(ns); pin[0] = pin[-1] = 1e8
+    blocks = [[None] * nt for _ in range(nt)]
+    for t in range(nt):
+        d = GWG if t > 0 else Q0
+        if t < nt - 1:
+            d = d + MWM
+        blocks[t][t] = d + sp.diags(pin)
+        if t > 0:
+            blocks[t][t - 1] = -GWM
+            blocks[t - 1][t] = -GWM.T
+    Qp = sp.bmat(blocks, format="csr")
+    n, m = ns * nt, ns * (nt - 1)
+    interior = np.arange(1, ns - 1)
+    Aic = sp.csr_matrix((np.ones(ns - 2), (np.arange(ns - 2), interior)), shape=(ns - 2, n))
+    Q = (Qp + ic_noise * (Aic.T @ Aic)).tocsc()
+    Q = ((Q + Q.T) * 0.5).tocsc()
+    Q.sort_indices()
+    # the prior conditioned on the initial condition: information vector Qp 0 + ic_noise Aic' ic, mean Q^-1 of it -- the start
+    # point and the x_prior of the objective, as the reference passes mean(u_ic) for both (:139-146)
+    Qx_prior = np.stack([ic_noise * (Aic.T @ ics[p, interior]) for p in range(B)])
+    x_prior = np.ascontiguousarray(spla.splu(Q).solve(Qx_prior.T).T)
+    x0 = x_prior.copy()
+    truth = np.stack([burgers_cole_hopf(xs, 1.0, nu, float(a)) for a in amps])
+    truth[:, 0] = 0.0; truth[:, -1] = 0.0
+    return {"Q": Q, "q_values": np.tile(Q.data, (B, 1)), "Qx_prior": Qx_prior, "x_prior": x_prior, "x0": x0, "ic": ics,
+            "noise": fem_noise, "n_blocks": nt, "n": n, "m": m, "dt": dt, "nu": nu, "ns": ns, "nc": nc, "order": order,
+            "scheme": scheme, "length": 2.0, "amps": amps, "xs": xs, "truth": truth}
 
 
 # --------------------------------------------------------------------------- analytic / toy

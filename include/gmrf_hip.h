@@ -521,6 +521,26 @@ gmrf_status gmrf_burgers_p1_create(int32_t device, void* stream, int64_t ns, int
  * _tangent and _destroy serve both element orders. */
 gmrf_status gmrf_burgers_p2_create(int32_t device, void* stream, int64_t ns, int64_t nt, double dt, double nu,
                                    gmrf_burgers_p1** out);
+/* The common creator: the line tangent over three independent choices (all 8 combinations), behind the same handle --
+ * _pattern, _tangent, _tangent_batch, _destroy and gmrf_gn_create / _run / _finalize serve every variant.
+ *   order   1 or 2, the elements above.
+ *   scheme  GMRF_BURGERS_EULER as above, or GMRF_BURGERS_CN, Crank-Nicolson (J_static_CN, nonlinear_primal_tangent_CN,
+ *           f_and_J_CN of _research/burgers_chen24.jl:121-132, :195-226): for the row block of the step t-1 -> t
+ *               J[:, t-1] = -M + (dt nu 0.5) G + (dt 0.5) A(w_{t-1}),    J[:, t] = M + (dt nu 0.5) G + (dt 0.5) A(w_t),
+ *               f = (static part of the row) . w + dt 0.5 (v(w_{t-1}) + v(w_t))
+ *           with A, v the advection tangent and residual of one slice.  The pattern is implicit Euler's (consistent mass).
+ *   bc      GMRF_BURGERS_PERIODIC: nc cells on [0, length), order nc dofs, wrap-around columns, as above;
+ *           GMRF_BURGERS_DIRICHLET: nc cells on an interval of that length with homogeneous Dirichlet ends
+ *           (_research/burgers_chen24.jl:101-108): ns = order nc + 1 dofs numbered by position, dofs 0 and ns-1 prescribed and
+ *           treated as src/problems/burgers.jl:53-57, :87-92 treats them: their rows and columns of J hold stored 0.0 and f
+ *           is 0.0 there, so m = (nt-1) ns stays uniform (a prior pins them).  A row holds its in-range columns only.
+ * Only `length` enters (the cell length is length / nc), not the interval's origin.  gmrf_burgers_p1_create(ns) is
+ * (nc = ns, order 1, euler, periodic, 1.0), gmrf_burgers_p2_create(ns) is (nc = ns / 2, order 2, ...): same kernels, same bits.
+ * GMRF_ERR_BAD_SHAPE: an unknown order, scheme or bc, length <= 0, nc < 3 (periodic) or < 2 (dirichlet), nt < 2. */
+typedef enum { GMRF_BURGERS_EULER = 0, GMRF_BURGERS_CN = 1 } gmrf_burgers_scheme;
+typedef enum { GMRF_BURGERS_PERIODIC = 0, GMRF_BURGERS_DIRICHLET = 1 } gmrf_burgers_bc;
+gmrf_status gmrf_burgers_line_create(int32_t device, void* stream, int64_t nc, int64_t nt, double dt, double nu, int32_t order,
+                                     int32_t scheme, int32_t bc, double length, gmrf_burgers_p1** out);
 gmrf_status gmrf_burgers_p1_destroy(gmrf_burgers_p1* b);
 gmrf_status gmrf_burgers_p1_pattern(const gmrf_burgers_p1* b, int64_t* nnz_out, int64_t* rowptr, int64_t* colidx,
                                     int32_t index_base);

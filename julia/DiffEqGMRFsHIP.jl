@@ -557,15 +557,31 @@ mutable struct BurgersP1Tangent
     rows::Int
 end
 
+# order = 2: the quadratic line of periodic_unit_interval_discretization (src/utils.jl:42-49), dofs numbered by position.
+# scheme = :cn: Crank-Nicolson (f_and_J_CN, _research/burgers_chen24.jl:121-132, :195-226).  bc = :dirichlet: an interval of `length`
+# with homogeneous Dirichlet ends (:101-108), ns = order * cells + 1; the rows and columns of dofs 1 and ns hold stored zeros.
+# ns is the number of dofs; all 8 combinations go through gmrf_burgers_line_create.
 function BurgersP1Tangent(ns::Integer, nt::Integer, dt::Real, nu::Real; device::Integer = 0, order::Integer = 1,
-                          stream::Ptr{Cvoid} = C_NULL)
+                          stream::Ptr{Cvoid} = C_NULL, scheme::Symbol = :euler, bc::Symbol = :periodic, length::Real = 1.0)
+    schemes = Dict(:euler => 0, :cn => 1); bcs = Dict(:periodic => 0, :dirichlet => 1)
+    (haskey(schemes, scheme) && haskey(bcs, bc) && order in (1, 2)) ||
+        throw(ArgumentError("BurgersP1Tangent: order 1 or 2, scheme :euler or :cn, bc :periodic or :dirichlet"))
+    ends = bc == :dirichlet ? 1 : 0
+    (ns - ends) % order == 0 ||
+        throw(ArgumentError("BurgersP1Tangent: ns = $ns is not $order * cells + $ends, the dofs of the order-$order $bc line"))
     h = Ref{Ptr{Cvoid}}(C_NULL)
-    if order == 2       # the quadratic periodic line of periodic_unit_interval_discretization (src/utils.jl:42-49): ns = 2 N_x dofs by position
-        check(ccall((:gmrf_burgers_p2_create, libgmrf), Int32, (Int32, Ptr{Cvoid}, Int64, Int64, Float64, Float64, Ref{Ptr{Cvoid}}),
-                    device, stream, ns, nt, Float64(dt), Float64(nu), h))
+    if scheme == :euler && bc == :periodic && length == 1.0       # the two entry points of the unit periodic line (they forward to the common creator)
+        if order == 2
+            check(ccall((:gmrf_burgers_p2_create, libgmrf), Int32, (Int32, Ptr{Cvoid}, Int64, Int64, Float64, Float64, Ref{Ptr{Cvoid}}),
+                        device, stream, ns, nt, Float64(dt), Float64(nu), h))
+        else
+            check(ccall((:gmrf_burgers_p1_create, libgmrf), Int32, (Int32, Ptr{Cvoid}, Int64, Int64, Float64, Float64, Ref{Ptr{Cvoid}}),
+                        device, stream, ns, nt, Float64(dt), Float64(nu), h))
+        end
     else
-        check(ccall((:gmrf_burgers_p1_create, libgmrf), Int32, (Int32, Ptr{Cvoid}, Int64, Int64, Float64, Float64, Ref{Ptr{Cvoid}}),
-                    device, stream, ns, nt, Float64(dt), Float64(nu), h))
+        check(ccall((:gmrf_burgers_line_create, libgmrf), Int32,
+                    (Int32, Ptr{Cvoid}, Int64, Int64, Float64, Float64, Int32, Int32, Int32, Float64, Ref{Ptr{Cvoid}}),
+                    device, stream, div(ns - ends, order), nt, Float64(dt), Float64(nu), order, schemes[scheme], bcs[bc], Float64(length), h))
     end
     nnz_out = Ref{Int64}(0)
     check(ccall((:gmrf_burgers_p1_pattern, libgmrf), Int32, (Ptr{Cvoid}, Ref{Int64}, Ptr{Int64}, Ptr{Int64}, Int32), h[], nnz_out, C_NULL, C_NULL, 1))

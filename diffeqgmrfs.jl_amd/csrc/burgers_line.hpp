@@ -4,8 +4,8 @@
 //   scheme  implicit Euler (f_and_J, scripts/burgers/solve_burgers_gmrf-fem.jl:118-149) or Crank-Nicolson (J_static_CN,
 //           nonlinear_primal_tangent_CN, f_and_J_CN: _research/burgers_chen24.jl:121-132, :195-226);
 //   bc      the periodic line (wrap-around columns) or an interval with homogeneous Dirichlet ends (_research/burgers_chen24.jl:101-108).
-// Implicit Euler on the periodic line of length 1 is served by burgers_p1_rows / burgers_p2_rows of fem_assemble.hpp, which keep
-// their bits and know that cell length only; the kernels here serve everything else.
+// Implicit Euler on the periodic line of length 1 is served by burgers_p1_rows_batch / burgers_p2_rows_batch of fem_assemble.hpp,
+// which keep their bits and know that cell length only; the kernels here serve everything else.
 //
 // Row block of the step t-1 -> t (t = 1 .. nt-1, 0-based), with M, G the consistent mass and stiffness, A(w), v(w) the assembled
 // advection tangent and residual of one slice:

@@ -41,8 +41,8 @@ struct EllipticLoadArgs {
     double* b;                      // [n]
 };
 
-// Floating-point contraction is switched off in every function below (as in lin_coord): the one-problem and the batch kernel
-// then round a row identically whatever the compiler would otherwise fuse in either of them.
+// Floating-point contraction is switched off in every function below (as in lin_coord): a row then rounds as the host oracle
+// does, whatever the compiler would otherwise fuse in the kernel it is inlined into.
 
 // signed 2 |T| of one cell as the determinant of the cell Jacobian (as in swe_p1_rows), with the coefficients of the P1 gradients
 __device__ __forceinline__ double elliptic_cell_area2(int nx, int ny, const int (&nxs)[3], const int (&nys)[3], double (&b)[3], double (&c)[3]) {
@@ -138,12 +138,8 @@ __device__ __forceinline__ void elliptic_p1_row(const EllipticP1Args& a, const i
     a.f[i] = acc + vi;
 }
 
-__global__ __launch_bounds__(256) void elliptic_p1_rows(EllipticP1Args a) {
-    elliptic_p1_row(a, (int64_t)blockIdx.x * blockDim.x + threadIdx.x);
-}
-
-// A batch of linearisation points on one mesh, problem-major: w[B][n] -> vals[B][nnz], f[B][n]; blockIdx.y is the problem.
-// The row function is the one-problem kernel's: the same arithmetic in the same order, so the same bits per problem.
+// A batch of linearisation points on one mesh, problem-major: w[B][n] -> vals[B][nnz], f[B][n]; blockIdx.y is the problem
+// (a one-problem call is a batch of 1).  A row's arithmetic does not depend on the problem's place in the batch.
 __global__ __launch_bounds__(256) void elliptic_p1_rows_batch(EllipticP1Args a, int64_t nnz) {
     const int64_t p = blockIdx.y, n = (int64_t)a.nx * a.ny;
     a.w += p * n; a.vals += p * nnz; a.f += p * n;

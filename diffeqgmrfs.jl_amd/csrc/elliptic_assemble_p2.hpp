@@ -41,8 +41,8 @@ struct EllipticP2LoadArgs {
     double* b;                      // [n]
 };
 
-// Floating-point contraction is switched off in every function below, as in elliptic_assemble.hpp: the one-problem and the batch
-// kernel then round a row identically whatever the compiler would otherwise fuse in either of them.  (The shape functions of
+// Floating-point contraction is switched off in every function below, as in elliptic_assemble.hpp: a row then rounds as the host
+// oracle does, whatever the compiler would otherwise fuse in the kernel it is inlined into.  (The shape functions of
 // fem_assemble_p2.hpp are evaluated at literal quadrature points and fold to constants.)
 
 // the affine geometry of the cell whose nodes have the lattice coordinates (I0 + rI, J0 + rJ): det J and J^-1 with
@@ -151,12 +151,8 @@ __device__ __forceinline__ void elliptic_p2_row(const EllipticP2Args& a, const i
     }
 }
 
-__global__ __launch_bounds__(256) void elliptic_p2_rows(EllipticP2Args a) {
-    elliptic_p2_row(a, (int64_t)blockIdx.x * blockDim.x + threadIdx.x);
-}
-
-// A batch of linearisation points on one mesh, problem-major: w[B][n] -> vals[B][nnz], f[B][n]; blockIdx.y is the problem.
-// The row function is the one-problem kernel's: the same arithmetic in the same order, so the same bits per problem.
+// A batch of linearisation points on one mesh, problem-major: w[B][n] -> vals[B][nnz], f[B][n]; blockIdx.y is the problem
+// (a one-problem call is a batch of 1).  A row's arithmetic does not depend on the problem's place in the batch.
 __global__ __launch_bounds__(256) void elliptic_p2_rows_batch(EllipticP2Args a, int64_t nnz) {
     const int64_t p = blockIdx.y, n = (int64_t)(2 * a.nx - 1) * (2 * a.ny - 1);
     a.w += p * n; a.vals += p * nnz; a.f += p * n;

@@ -110,12 +110,8 @@ __device__ __forceinline__ void darcy_p1_row(const DarcyP1Args& a, const int64_t
     a.diag[i] = fabs(slot[3]);
 }
 
-__global__ __launch_bounds__(256) void darcy_p1_rows(DarcyP1Args a) {
-    darcy_p1_row(a, (int64_t)blockIdx.x * blockDim.x + threadIdx.x);
-}
-
 // A batch of coefficient tables on one mesh, problem-major: table[B][ng ng] -> vals[B][nnz], f[B][n], diag[B][n]; blockIdx.y is
-// the problem.  The row function is the one-problem kernel's: the same arithmetic in the same order, so the same bits per problem.
+// the problem (a one-problem call is a batch of 1).  A row's arithmetic does not depend on the problem's place in the batch.
 __global__ __launch_bounds__(256) void darcy_p1_rows_batch(DarcyP1Args a, int64_t nnz) {
     const int64_t p = blockIdx.y, n = (int64_t)a.nx * a.ny;
     a.table += p * ((int64_t)a.ng * a.ng); a.vals += p * nnz; a.f += p * n; a.diag += p * n;
@@ -141,7 +137,7 @@ __global__ __launch_bounds__(256) void darcy_meandiag(const double* __restrict__
     darcy_meandiag_group(diag, n, out);
 }
 
-// diag[B][n] -> out[B]: one workgroup per problem (blockIdx.x), each with the one-problem kernel's partition and tree
+// diag[B][n] -> out[B]: one workgroup per problem (blockIdx.x), each with the partition and tree of darcy_meandiag
 __global__ __launch_bounds__(256) void darcy_meandiag_batch(const double* __restrict__ diag, int64_t n, double* __restrict__ out) {
     darcy_meandiag_group(diag + (int64_t)blockIdx.x * n, n, out + blockIdx.x);
 }
@@ -164,10 +160,6 @@ __device__ __forceinline__ void darcy_p1_constrain_row(const DarcyP1Args& a, con
         ++p;
     }
     if (bi) a.f[i] = 0.0;
-}
-
-__global__ __launch_bounds__(256) void darcy_p1_constrain(DarcyP1Args a, const double* __restrict__ meandiag) {
-    darcy_p1_constrain_row(a, meandiag, (int64_t)blockIdx.x * blockDim.x + threadIdx.x);
 }
 
 // meandiag[B]; blockIdx.y is the problem
@@ -266,12 +258,8 @@ __device__ __forceinline__ void burgers_p1_row(const BurgersP1Args& a, const int
     a.f[gid] = acc + a.dt * v_i;
 }
 
-__global__ __launch_bounds__(256) void burgers_p1_rows(BurgersP1Args a) {
-    burgers_p1_row(a, (int64_t)blockIdx.x * blockDim.x + threadIdx.x);
-}
-
-// A batch of linearisation points on one mesh, problem-major: w[B][nt ns] -> vals[B][nnz], f[B][rows]; blockIdx.y is the problem.
-// The row function is the one-problem kernel's: the same arithmetic in the same order, so the same bits per problem.
+// A batch of linearisation points on one mesh, problem-major: w[B][nt ns] -> vals[B][nnz], f[B][rows]; blockIdx.y is the problem
+// (a one-problem call is a batch of 1).  A row's arithmetic does not depend on the problem's place in the batch.
 __global__ __launch_bounds__(256) void burgers_p1_rows_batch(BurgersP1Args a, int64_t nnz) {
     const int64_t p = blockIdx.y, rows = (int64_t)(a.nt - 1) * a.ns;
     a.w += p * ((int64_t)a.nt * a.ns); a.vals += p * nnz; a.f += p * rows;
@@ -367,10 +355,6 @@ __device__ __forceinline__ void burgers_p2_row(const BurgersP1Args& a, const int
     for (int k = 0; k < cnt; ++k) acc += prev_terms[k];
     for (int k = 0; k < cnt; ++k) acc += cur_terms[k];
     a.f[gid] = acc + a.dt * v_i;
-}
-
-__global__ __launch_bounds__(256) void burgers_p2_rows(BurgersP1Args a) {
-    burgers_p2_row(a, (int64_t)blockIdx.x * blockDim.x + threadIdx.x);
 }
 
 __global__ __launch_bounds__(256) void burgers_p2_rows_batch(BurgersP1Args a, int64_t nnz) {

@@ -160,10 +160,6 @@ __device__ __forceinline__ void darcy_p2_row(const DarcyP2Args& a, const int64_t
     a.diag[row] = fabs(slot[12]);
 }
 
-__global__ __launch_bounds__(256) void darcy_p2_rows(DarcyP2Args a) {
-    darcy_p2_row(a, (int64_t)blockIdx.x * blockDim.x + threadIdx.x);
-}
-
 // A batch of coefficient tables, problem-major like darcy_p1_rows_batch (n = lattice points); blockIdx.y is the problem.
 __global__ __launch_bounds__(256) void darcy_p2_rows_batch(DarcyP2Args a, int64_t nnz) {
     const int64_t p = blockIdx.y, n = (int64_t)(2 * a.nx - 1) * (2 * a.ny - 1);
@@ -171,8 +167,9 @@ __global__ __launch_bounds__(256) void darcy_p2_rows_batch(DarcyP2Args a, int64_
     darcy_p2_row(a, (int64_t)blockIdx.x * blockDim.x + threadIdx.x);
 }
 
-// apply!(G, f, ch) of a batch: what csr_apply_constraints and vec_set_prescribed (value 0) do for one problem -- assignments
-// only --, vals[B][nnz], f[B][n], meandiag[B]; blockIdx.y is the problem.
+// apply!(G, f, ch) for homogeneous Dirichlet data on the boundary lattice points (pres[row] != 0): constrained rows and columns
+// are zeroed, the constrained diagonal entries become the problem's meandiag, f vanishes there -- assignments only.
+// vals[B][nnz], f[B][n], meandiag[B]; blockIdx.y is the problem.
 __global__ __launch_bounds__(256) void darcy_p2_constrain_batch(const int64_t* __restrict__ rowptr, const int32_t* __restrict__ colidx,
                                                                 const uint8_t* __restrict__ pres, int64_t n, int64_t nnz,
                                                                 const double* __restrict__ meandiag, double* __restrict__ vals,

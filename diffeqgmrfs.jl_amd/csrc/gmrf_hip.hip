@@ -104,7 +104,7 @@ static int64_t next_pow2(int64_t v) {
     return p;
 }
 
-#include "host_util.hpp"      // free_dev, DevBuf, DevCtx, Staging
+#include "host_util.hpp"      // free_dev, DevBuf, DevCtx, Staging, Carve
 
 // ------------------------------------------------------------------------------------ csr
 struct gmrf_csr : DevCtx {
@@ -3763,14 +3763,13 @@ struct gmrf_assembler : DevCtx {        // device -1: symbolic only (pattern que
     std::vector<int64_t> colptr, rowval;            // result pattern (CSC, 0-based, rows ascending)
     int64_t *d_pptr = nullptr, *d_qmap = nullptr, *d_jt_ptr = nullptr, *d_j_rptr = nullptr;
     int32_t *d_pa = nullptr, *d_pb = nullptr, *d_jt_row = nullptr, *d_jt_src = nullptr, *d_j_col = nullptr;
-    double* d_vm = nullptr;             // [m] work vector J x + obs_diff of gmrf_assemble_rhs
     DevBuf arena;                       // host arguments of the current call (Staging)
     // the batch calls: Q's own pattern (0-based; symmetric, so its CSC arrays are read by rows), uploaded by the first objective
     std::vector<int64_t> q_ptr;
     std::vector<int32_t> q_row;
     int64_t* d_q_ptr = nullptr;
     int32_t* d_q_row = nullptr;
-    DevBuf bpart;                       // work arrays of the batch calls: [batch][m] of the rhs, the objective's partial sums
+    DevBuf bpart;                       // work arrays: [batch][m] (J x + obs_diff) of the rhs, the objective's partial sums
 };
 
 gmrf_status gmrf_assemble_create(int32_t device, void* stream, int64_t n, const int64_t* q_colptr, const int64_t* q_rowval,
@@ -3865,7 +3864,7 @@ gmrf_status gmrf_assemble_destroy(gmrf_assembler* as) {
     if (as->has_device()) {
         free_dev(as->d_pptr); free_dev(as->d_qmap); free_dev(as->d_pa); free_dev(as->d_pb);
         free_dev(as->d_jt_ptr); free_dev(as->d_jt_row); free_dev(as->d_jt_src); free_dev(as->d_j_rptr); free_dev(as->d_j_col);
-        free_dev(as->d_vm); free_dev(as->d_q_ptr); free_dev(as->d_q_row);
+        free_dev(as->d_q_ptr); free_dev(as->d_q_row);
         as->arena.release(); as->bpart.release();
     }
     delete as;
@@ -3884,24 +3883,18 @@ gmrf_status gmrf_assemble_pattern(const gmrf_assembler* as, int64_t* nnz_out, in
 
 static const char* const AS_PATTERN_ONLY = "symbolic-only assembler";
 
+// (defined with the batch forms below: a one-problem call is a batch of 1)
+static gmrf_status assemble_precision_staged(gmrf_assembler* as, int64_t batch, const double* q_nzval, int64_t q_stride,
+                                             const double* j_vals, double noise, double* out_nzval);
+static gmrf_status assemble_rhs_staged(gmrf_assembler* as, int64_t batch, const double* base, const double* j_vals, const double* x,
+                                       const double* obs_diff, double noise, double* out);
+
 gmrf_status gmrf_assemble_precision(gmrf_assembler* as, const double* q_nzval, const double* j_vals, double noise,
                                     double* out_nzval) {
     if (!as) return bad_shape("null assembler");
     GCHK(as->ready(AS_PATTERN_ONLY));
     if (!q_nzval || !j_vals || !out_nzval) return bad_shape("null pointer");
-    const double *dq, *dj;
-    double* d_out;
-    Staging args(as->arena);
-    args.in(q_nzval, sizeof(double) * as->nnz_q, &dq);
-    args.in(j_vals, sizeof(double) * as->nnz_j, &dj);
-    args.out(out_nzval, sizeof(double) * as->nnz_out, &d_out);
-    GCHK(args.commit(as->stream));
-    hipLaunchKernelGGL(assemble_precision, dim3((unsigned)((as->nnz_out + 255) / 256)), dim3(256), 0, as->stream, as->d_pptr,
-                       as->d_pa, as->d_pb, as->d_qmap, dq, dj, noise, as->nnz_out, d_out);
-    HIPCHK(hipGetLastError());
-    GCHK(args.flush(as->stream));
-    HIPCHK(hipStreamSynchronize(as->stream));
-    return GMRF_OK;
+    return assemble_precision_staged(as, 1, q_nzval, 0, j_vals, noise, out_nzval);
 }
 
 gmrf_status gmrf_assemble_rhs(gmrf_assembler* as, const double* base, const double* j_vals, const double* x,
@@ -3909,25 +3902,7 @@ gmrf_status gmrf_assemble_rhs(gmrf_assembler* as, const double* base, const doub
     if (!as) return bad_shape("null assembler");
     GCHK(as->ready(AS_PATTERN_ONLY));
     if (!j_vals || !x || !out) return bad_shape("null pointer");
-    const double *dj, *dx, *dadd, *dbase;
-    double* d_out;
-    Staging args(as->arena);
-    args.in(j_vals, sizeof(double) * as->nnz_j, &dj);
-    args.in(x, sizeof(double) * as->n, &dx);
-    args.in(obs_diff, sizeof(double) * as->m, &dadd);
-    args.in(base, sizeof(double) * as->n, &dbase);
-    args.out(out, sizeof(double) * as->n, &d_out);
-    GCHK(args.commit(as->stream));
-    if (!as->d_vm) HIPCHK(hipMalloc(&as->d_vm, sizeof(double) * as->m));
-    // v = J x + obs_diff ;  out = base + noise * J' v
-    hipLaunchKernelGGL(assemble_j_apply, dim3((unsigned)((as->m + 255) / 256)), dim3(256), 0, as->stream, as->d_j_rptr,
-                       as->d_j_col, dj, dx, dadd, as->m, as->d_vm);
-    hipLaunchKernelGGL(assemble_jt_apply, dim3((unsigned)((as->n + 255) / 256)), dim3(256), 0, as->stream, as->d_jt_ptr,
-                       as->d_jt_row, as->d_jt_src, dj, as->d_vm, dbase, noise, as->n, d_out);
-    HIPCHK(hipGetLastError());
-    GCHK(args.flush(as->stream));
-    HIPCHK(hipStreamSynchronize(as->stream));
-    return GMRF_OK;
+    return assemble_rhs_staged(as, 1, base, j_vals, x, obs_diff, noise, out);
 }
 
 // --------------------------------------------------------------------------------- FEM block assembly (Darcy, P1)
@@ -3936,15 +3911,14 @@ struct gmrf_darcy_p1 : DevCtx {         // device -1: pattern only
     int order = 1;                      // 1: P1 triangles on the nx x ny nodes; 2: quadratic triangles, dofs = the (2 nx - 1) x (2 ny - 1) lattice
     std::vector<int64_t> rowptr, colidx;            // 0-based
     int64_t* d_rowptr = nullptr;
-    int32_t* d_colidx = nullptr;        // order 2: the pattern's columns and the Dirichlet mask for the generic apply! kernels
+    int32_t* d_colidx = nullptr;        // order 2: the pattern's columns and the Dirichlet mask for darcy_p2_constrain_batch
     uint8_t* d_pres = nullptr;
-    double *d_diag = nullptr, *d_mean = nullptr;    // work: |diagonal|, its mean
     DevBuf arena;                       // host arguments of the current call (Staging)
-    DevBuf bwork;                       // work of the batch call: [batch][n] |diagonal|, [batch] means
+    DevBuf bwork;                       // work of an assembly: [batch][n] |diagonal|, [batch] means
 };
 
 // Pattern of the quadratic-triangle lattice: row (I, J) couples with every node of every cell it belongs to (the same
-// enumeration as darcy_p2_rows: 5 x 5 window of lattice offsets, touched entries in ascending column order).
+// enumeration as darcy_p2_row: 5 x 5 window of lattice offsets, touched entries in ascending column order).
 static void p2_lattice_pattern(int64_t nx, int64_t ny, std::vector<int64_t>& rowptr, std::vector<int64_t>& colidx) {
     const int64_t W = 2 * nx - 1, H = 2 * ny - 1;
     rowptr.assign((size_t)(W * H) + 1, 0);
@@ -4012,8 +3986,6 @@ static gmrf_status darcy_create(int32_t device, void* stream, int64_t nx, int64_
     GCHK(d->open(device, stream, hipStreamNonBlocking, "gmrf_darcy_p1_create"));
     if (d->device >= 0) {
         HIPCHK(hipMalloc(&d->d_rowptr, sizeof(int64_t) * (d->n + 1)));
-        HIPCHK(hipMalloc(&d->d_diag, sizeof(double) * d->n));
-        HIPCHK(hipMalloc(&d->d_mean, sizeof(double)));
         HIPCHK(hipMemcpyAsync(d->d_rowptr, d->rowptr.data(), sizeof(int64_t) * (d->n + 1), hipMemcpyHostToDevice, d->stream));
         std::vector<int32_t> col32;
         std::vector<uint8_t> pres;
@@ -4045,7 +4017,7 @@ gmrf_status gmrf_darcy_p1_destroy(gmrf_darcy_p1* d) {
     if (!d) return GMRF_OK;
     d->close();
     if (d->has_device()) {
-        free_dev(d->d_rowptr); free_dev(d->d_diag); free_dev(d->d_mean); free_dev(d->d_colidx); free_dev(d->d_pres);
+        free_dev(d->d_rowptr); free_dev(d->d_colidx); free_dev(d->d_pres);
         d->arena.release(); d->bwork.release();
     }
     delete d;
@@ -4060,39 +4032,15 @@ gmrf_status gmrf_darcy_p1_pattern(const gmrf_darcy_p1* d, int64_t* nnz_out, int6
     return GMRF_OK;
 }
 
+static bool darcy_ng_ok(int64_t ng) { return ng >= 2 && ng <= 46340; }
+// (defined with the batch form below: a one-problem call is a batch of 1)
+static gmrf_status darcy_assemble_staged(gmrf_darcy_p1* d, int64_t batch, const double* coeff_tables, int64_t ng, double beta,
+                                         double* vals_out, double* f_out);
+
 gmrf_status gmrf_darcy_p1_assemble(gmrf_darcy_p1* d, const double* coeff_table, int64_t ng, double beta, double* vals_out,
                                    double* f_out) {
-    if (!d || !coeff_table || !vals_out || !f_out || ng < 2 || ng > 46340) return bad_shape("bad Darcy assembly arguments");
-    GCHK(d->ready("pattern-only Darcy assembler"));
-    const double* d_tab;
-    double *d_vals, *d_f;
-    Staging args(d->arena);
-    args.in(coeff_table, sizeof(double) * ng * ng, &d_tab);
-    args.out(vals_out, sizeof(double) * d->nnz, &d_vals);
-    args.out(f_out, sizeof(double) * d->n, &d_f);
-    GCHK(args.commit(d->stream));
-    const dim3 grid((unsigned)((d->n + 255) / 256));
-    if (d->order == 2) {
-        DarcyP2Args a;
-        a.nx = (int)d->nx; a.ny = (int)d->ny; a.ng = (int)ng; a.table = d_tab; a.rowptr = d->d_rowptr; a.beta = beta;
-        a.vals = d_vals; a.f = d_f; a.diag = d->d_diag;
-        hipLaunchKernelGGL(darcy_p2_rows, grid, dim3(256), 0, d->stream, a);
-        hipLaunchKernelGGL(darcy_meandiag, dim3(1), dim3(256), 0, d->stream, d->d_diag, d->n, d->d_mean);
-        // apply!(G, f, ch): rows and columns of the boundary lattice points, meandiag on their diagonal, f = 0 there
-        hipLaunchKernelGGL(csr_apply_constraints, grid, dim3(256), 0, d->stream, d->d_rowptr, d->d_colidx, d->d_pres, d->n, d->d_mean, a.vals);
-        hipLaunchKernelGGL(vec_set_prescribed, grid, dim3(256), 0, d->stream, d->d_pres, d->n, (const double*)nullptr, 0.0, a.f);
-    } else {
-        DarcyP1Args a;
-        a.nx = (int)d->nx; a.ny = (int)d->ny; a.ng = (int)ng; a.table = d_tab; a.rowptr = d->d_rowptr; a.beta = beta;
-        a.vals = d_vals; a.f = d_f; a.diag = d->d_diag;
-        hipLaunchKernelGGL(darcy_p1_rows, grid, dim3(256), 0, d->stream, a);
-        hipLaunchKernelGGL(darcy_meandiag, dim3(1), dim3(256), 0, d->stream, d->d_diag, d->n, d->d_mean);
-        hipLaunchKernelGGL(darcy_p1_constrain, grid, dim3(256), 0, d->stream, a, d->d_mean);
-    }
-    HIPCHK(hipGetLastError());
-    GCHK(args.flush(d->stream));
-    HIPCHK(hipStreamSynchronize(d->stream));
-    return GMRF_OK;
+    if (!d || !coeff_table || !vals_out || !f_out || !darcy_ng_ok(ng)) return bad_shape("bad Darcy assembly arguments");
+    return darcy_assemble_staged(d, 1, coeff_table, ng, beta, vals_out, f_out);
 }
 
 // --------------------------------------------------------------------------------- Burgers tangent (8f rank 4)
@@ -4184,7 +4132,7 @@ gmrf_status gmrf_burgers_p1_pattern(const gmrf_burgers_p1* b, int64_t* nnz_out, 
 }
 
 // --------------------------------------------------------------------------------- batch forms of the Gauss-Newton glue
-// Problem-major arrays ([batch][...]); host or device pointers like the one-problem calls.
+// Problem-major arrays ([batch][...]), host or device pointers; the one-problem calls are these at batch 1.
 static bool batch_ok(int64_t batch) { return batch >= 1 && batch <= 4096; }
 
 // Implicit Euler on the periodic unit line keeps the kernels of fem_assemble.hpp (and their bits), which know the cell length
@@ -4216,32 +4164,8 @@ static gmrf_status launch_tangent_batch(const gmrf_burgers_p1* b, hipStream_t st
     return GMRF_OK;
 }
 
-gmrf_status gmrf_burgers_p1_tangent(gmrf_burgers_p1* b, const double* w, double* vals_out, double* f_out) {
-    if (!b || !w || !vals_out || !f_out) return bad_shape("bad Burgers tangent arguments");
-    GCHK(b->ready("pattern-only Burgers assembler"));
-    const double* d_w;
-    double *d_vals, *d_f;
-    Staging args(b->arena);
-    args.in(w, sizeof(double) * b->ns * b->nt, &d_w);
-    args.out(vals_out, sizeof(double) * b->nnz, &d_vals);
-    args.out(f_out, sizeof(double) * b->rows, &d_f);
-    GCHK(args.commit(b->stream));
-    if (burgers_unit_euler_periodic(b)) {
-        BurgersP1Args a;
-        a.ns = (int)b->ns; a.nt = (int)b->nt; a.dt = b->dt; a.nu = b->nu; a.w = d_w; a.vals = d_vals; a.f = d_f;
-        if (b->order == 2) hipLaunchKernelGGL(burgers_p2_rows, dim3((unsigned)((b->rows + 255) / 256)), dim3(256), 0, b->stream, a);
-        else hipLaunchKernelGGL(burgers_p1_rows, dim3((unsigned)((b->rows + 255) / 256)), dim3(256), 0, b->stream, a);
-        HIPCHK(hipGetLastError());
-    } else {
-        GCHK(launch_tangent_batch(b, b->stream, 1, d_w, d_vals, d_f));
-    }
-    GCHK(args.flush(b->stream));
-    HIPCHK(hipStreamSynchronize(b->stream));
-    return GMRF_OK;
-}
-
-gmrf_status gmrf_burgers_p1_tangent_batch(gmrf_burgers_p1* b, int64_t batch, const double* w, double* vals_out, double* f_out) {
-    if (!b || !w || !vals_out || !f_out || !batch_ok(batch)) return bad_shape("bad Burgers tangent arguments (batch in [1, 4096])");
+// The body of gmrf_burgers_p1_tangent and its batch form after their argument checks; a one-problem call is a batch of 1.
+static gmrf_status burgers_tangent_staged(gmrf_burgers_p1* b, int64_t batch, const double* w, double* vals_out, double* f_out) {
     GCHK(b->ready("pattern-only Burgers assembler"));
     const double* d_w;
     double *d_vals, *d_f;
@@ -4254,6 +4178,16 @@ gmrf_status gmrf_burgers_p1_tangent_batch(gmrf_burgers_p1* b, int64_t batch, con
     GCHK(args.flush(b->stream));
     HIPCHK(hipStreamSynchronize(b->stream));
     return GMRF_OK;
+}
+
+gmrf_status gmrf_burgers_p1_tangent(gmrf_burgers_p1* b, const double* w, double* vals_out, double* f_out) {
+    if (!b || !w || !vals_out || !f_out) return bad_shape("bad Burgers tangent arguments");
+    return burgers_tangent_staged(b, 1, w, vals_out, f_out);
+}
+
+gmrf_status gmrf_burgers_p1_tangent_batch(gmrf_burgers_p1* b, int64_t batch, const double* w, double* vals_out, double* f_out) {
+    if (!b || !w || !vals_out || !f_out || !batch_ok(batch)) return bad_shape("bad Burgers tangent arguments (batch in [1, 4096])");
+    return burgers_tangent_staged(b, batch, w, vals_out, f_out);
 }
 
 // --------------------------------------------------------------------------------- Burgers prior ("Prior" / "Initial condition" stages)
@@ -4448,44 +4382,18 @@ gmrf_status gmrf_elliptic_p1_qpoints(const gmrf_elliptic_p1* e, double* xy) {
 static gmrf_status launch_elliptic_batch(const gmrf_elliptic_p1* e, hipStream_t st, int64_t batch, const double* d_w, double* d_vals,
                                          double* d_f) {
     const dim3 grid((unsigned)((e->n + 255) / 256), (unsigned)batch);
-    if (e->order == 2) {
-        EllipticP2Args a;
+    auto launch = [&](auto kern, auto a) {
         a.nx = (int)e->nx; a.ny = (int)e->ny; a.rowptr = e->d_rowptr; a.w = d_w; a.vals = d_vals; a.f = d_f;
-        hipLaunchKernelGGL(elliptic_p2_rows_batch, grid, dim3(256), 0, st, a, e->nnz);
-        HIPCHK(hipGetLastError());
-        return GMRF_OK;
-    }
-    EllipticP1Args a;
-    a.nx = (int)e->nx; a.ny = (int)e->ny; a.rowptr = e->d_rowptr; a.w = d_w; a.vals = d_vals; a.f = d_f;
-    hipLaunchKernelGGL(elliptic_p1_rows_batch, grid, dim3(256), 0, st, a, e->nnz);
+        hipLaunchKernelGGL(kern, grid, dim3(256), 0, st, a, e->nnz);
+    };
+    if (e->order == 2) launch(elliptic_p2_rows_batch, EllipticP2Args{});
+    else launch(elliptic_p1_rows_batch, EllipticP1Args{});
     HIPCHK(hipGetLastError());
     return GMRF_OK;
 }
 
-gmrf_status gmrf_elliptic_p1_tangent(gmrf_elliptic_p1* e, const double* w, double* vals_out, double* f_out) {
-    if (!e || !w || !vals_out || !f_out) return bad_shape("bad elliptic tangent arguments");
-    GCHK(e->ready("pattern-only elliptic tangent"));
-    EllipticP1Args a;
-    a.nx = (int)e->nx; a.ny = (int)e->ny; a.rowptr = e->d_rowptr;
-    Staging args(e->arena);
-    args.in(w, sizeof(double) * e->n, &a.w);
-    args.out(vals_out, sizeof(double) * e->nnz, &a.vals);
-    args.out(f_out, sizeof(double) * e->n, &a.f);
-    GCHK(args.commit(e->stream));
-    if (e->order == 2) {
-        EllipticP2Args a2;
-        a2.nx = a.nx; a2.ny = a.ny; a2.rowptr = a.rowptr; a2.w = a.w; a2.vals = a.vals; a2.f = a.f;
-        hipLaunchKernelGGL(elliptic_p2_rows, dim3((unsigned)((e->n + 255) / 256)), dim3(256), 0, e->stream, a2);
-    } else
-        hipLaunchKernelGGL(elliptic_p1_rows, dim3((unsigned)((e->n + 255) / 256)), dim3(256), 0, e->stream, a);
-    HIPCHK(hipGetLastError());
-    GCHK(args.flush(e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    return GMRF_OK;
-}
-
-gmrf_status gmrf_elliptic_p1_tangent_batch(gmrf_elliptic_p1* e, int64_t batch, const double* w, double* vals_out, double* f_out) {
-    if (!e || !w || !vals_out || !f_out || !batch_ok(batch)) return bad_shape("bad elliptic tangent arguments (batch in [1, 4096])");
+// The body of gmrf_elliptic_p1_tangent and its batch form after their argument checks; a one-problem call is a batch of 1.
+static gmrf_status elliptic_tangent_staged(gmrf_elliptic_p1* e, int64_t batch, const double* w, double* vals_out, double* f_out) {
     GCHK(e->ready("pattern-only elliptic tangent"));
     const double* d_w;
     double *d_vals, *d_f;
@@ -4500,23 +4408,33 @@ gmrf_status gmrf_elliptic_p1_tangent_batch(gmrf_elliptic_p1* e, int64_t batch, c
     return GMRF_OK;
 }
 
+gmrf_status gmrf_elliptic_p1_tangent(gmrf_elliptic_p1* e, const double* w, double* vals_out, double* f_out) {
+    if (!e || !w || !vals_out || !f_out) return bad_shape("bad elliptic tangent arguments");
+    return elliptic_tangent_staged(e, 1, w, vals_out, f_out);
+}
+
+gmrf_status gmrf_elliptic_p1_tangent_batch(gmrf_elliptic_p1* e, int64_t batch, const double* w, double* vals_out, double* f_out) {
+    if (!e || !w || !vals_out || !f_out || !batch_ok(batch)) return bad_shape("bad elliptic tangent arguments (batch in [1, 4096])");
+    return elliptic_tangent_staged(e, batch, w, vals_out, f_out);
+}
+
 // src_q [batch][cells][nq] -> b_out [batch][n]
 gmrf_status gmrf_elliptic_p1_load(gmrf_elliptic_p1* e, int64_t batch, const double* src_q, double* b_out) {
     if (!e || !src_q || !b_out || !batch_ok(batch)) return bad_shape("bad elliptic load arguments (batch in [1, 4096])");
     GCHK(e->ready("pattern-only elliptic tangent"));
-    EllipticLoadArgs a;
-    a.nx = (int)e->nx; a.ny = (int)e->ny;
+    const double* d_src;
+    double* d_b;
     Staging args(e->arena);
-    args.in(src_q, sizeof(double) * batch * e->cells * e->nq, &a.src);
-    args.out(b_out, sizeof(double) * batch * e->n, &a.b);
+    args.in(src_q, sizeof(double) * batch * e->cells * e->nq, &d_src);
+    args.out(b_out, sizeof(double) * batch * e->n, &d_b);
     GCHK(args.commit(e->stream));
     const dim3 grid((unsigned)((e->n + 255) / 256), (unsigned)batch);
-    if (e->order == 2) {
-        EllipticP2LoadArgs a2;
-        a2.nx = a.nx; a2.ny = a.ny; a2.src = a.src; a2.b = a.b;
-        hipLaunchKernelGGL(elliptic_p2_load_batch, grid, dim3(256), 0, e->stream, a2);
-    } else
-        hipLaunchKernelGGL(elliptic_p1_load_batch, grid, dim3(256), 0, e->stream, a);
+    auto launch = [&](auto kern, auto a) {
+        a.nx = (int)e->nx; a.ny = (int)e->ny; a.src = d_src; a.b = d_b;
+        hipLaunchKernelGGL(kern, grid, dim3(256), 0, e->stream, a);
+    };
+    if (e->order == 2) launch(elliptic_p2_load_batch, EllipticP2LoadArgs{});
+    else launch(elliptic_p1_load_batch, EllipticLoadArgs{});
     HIPCHK(hipGetLastError());
     GCHK(args.flush(e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
@@ -4525,25 +4443,24 @@ gmrf_status gmrf_elliptic_p1_load(gmrf_elliptic_p1* e, int64_t batch, const doub
 
 // Darcy element kernels for a batch of coefficient tables (problem-major); d_work: [batch][n] |diagonal| then [batch] means
 static int64_t darcy_batch_work_elems(const gmrf_darcy_p1* d, int64_t batch) { return batch * d->n + batch; }
-static bool darcy_ng_ok(int64_t ng) { return ng >= 2 && ng <= 46340; }
 
 static gmrf_status launch_darcy_batch(const gmrf_darcy_p1* d, hipStream_t st, int64_t batch, const double* d_tab, int64_t ng, double beta,
                                       double* d_vals, double* d_f, double* d_work) {
     double* d_diag = d_work;
     double* d_mean = d_work + batch * d->n;
     const dim3 grid((unsigned)((d->n + 255) / 256), (unsigned)batch);
-    if (d->order == 2) {
-        DarcyP2Args a;
+    auto fill = [&](auto a) {
         a.nx = (int)d->nx; a.ny = (int)d->ny; a.ng = (int)ng; a.table = d_tab; a.rowptr = d->d_rowptr; a.beta = beta;
         a.vals = d_vals; a.f = d_f; a.diag = d_diag;
-        hipLaunchKernelGGL(darcy_p2_rows_batch, grid, dim3(256), 0, st, a, d->nnz);
+        return a;
+    };
+    if (d->order == 2) {
+        hipLaunchKernelGGL(darcy_p2_rows_batch, grid, dim3(256), 0, st, fill(DarcyP2Args{}), d->nnz);
         hipLaunchKernelGGL(darcy_meandiag_batch, dim3((unsigned)batch), dim3(256), 0, st, d_diag, d->n, d_mean);
         hipLaunchKernelGGL(darcy_p2_constrain_batch, grid, dim3(256), 0, st, d->d_rowptr, d->d_colidx, d->d_pres, d->n, d->nnz, d_mean,
                            d_vals, d_f);
     } else {
-        DarcyP1Args a;
-        a.nx = (int)d->nx; a.ny = (int)d->ny; a.ng = (int)ng; a.table = d_tab; a.rowptr = d->d_rowptr; a.beta = beta;
-        a.vals = d_vals; a.f = d_f; a.diag = d_diag;
+        const DarcyP1Args a = fill(DarcyP1Args{});
         hipLaunchKernelGGL(darcy_p1_rows_batch, grid, dim3(256), 0, st, a, d->nnz);
         hipLaunchKernelGGL(darcy_meandiag_batch, dim3((unsigned)batch), dim3(256), 0, st, d_diag, d->n, d_mean);
         hipLaunchKernelGGL(darcy_p1_constrain_batch, grid, dim3(256), 0, st, a, d->nnz, d_mean);
@@ -4552,10 +4469,9 @@ static gmrf_status launch_darcy_batch(const gmrf_darcy_p1* d, hipStream_t st, in
     return GMRF_OK;
 }
 
-gmrf_status gmrf_darcy_p1_assemble_batch(gmrf_darcy_p1* d, int64_t batch, const double* coeff_tables, int64_t ng, double beta,
+// The body of gmrf_darcy_p1_assemble and its batch form after their argument checks; a one-problem call is a batch of 1.
+static gmrf_status darcy_assemble_staged(gmrf_darcy_p1* d, int64_t batch, const double* coeff_tables, int64_t ng, double beta,
                                          double* vals_out, double* f_out) {
-    if (!d || !coeff_tables || !vals_out || !f_out || !batch_ok(batch) || !darcy_ng_ok(ng))
-        return bad_shape("bad Darcy assembly arguments (batch in [1, 4096], ng in [2, 46340])");
     GCHK(d->ready("pattern-only Darcy assembler"));
     const double* d_tab;
     double *d_vals, *d_f;
@@ -4569,6 +4485,13 @@ gmrf_status gmrf_darcy_p1_assemble_batch(gmrf_darcy_p1* d, int64_t batch, const 
     GCHK(args.flush(d->stream));
     HIPCHK(hipStreamSynchronize(d->stream));
     return GMRF_OK;
+}
+
+gmrf_status gmrf_darcy_p1_assemble_batch(gmrf_darcy_p1* d, int64_t batch, const double* coeff_tables, int64_t ng, double beta,
+                                         double* vals_out, double* f_out) {
+    if (!d || !coeff_tables || !vals_out || !f_out || !batch_ok(batch) || !darcy_ng_ok(ng))
+        return bad_shape("bad Darcy assembly arguments (batch in [1, 4096], ng in [2, 46340])");
+    return darcy_assemble_staged(d, batch, coeff_tables, ng, beta, vals_out, f_out);
 }
 
 static gmrf_status launch_precision_batch(const gmrf_assembler* as, hipStream_t st, int64_t batch, const double* d_q, int64_t q_stride,
@@ -4624,11 +4547,9 @@ static gmrf_status q_stride_ok(const gmrf_assembler* as, int64_t q_stride) {
     return GMRF_OK;
 }
 
-gmrf_status gmrf_assemble_precision_batch(gmrf_assembler* as, int64_t batch, const double* q_nzval, int64_t q_stride,
-                                          const double* j_vals, double noise, double* out_nzval) {
-    if (!as || !q_nzval || !j_vals || !out_nzval || !batch_ok(batch)) return bad_shape("null pointer or batch outside [1, 4096]");
-    GCHK(q_stride_ok(as, q_stride));
-    GCHK(as->ready(AS_PATTERN_ONLY));
+// The bodies of the assembly calls after their argument checks; a one-problem call is a batch of 1.
+static gmrf_status assemble_precision_staged(gmrf_assembler* as, int64_t batch, const double* q_nzval, int64_t q_stride,
+                                             const double* j_vals, double noise, double* out_nzval) {
     const double *d_q, *d_jv;
     double* d_out;
     Staging args(as->arena);
@@ -4642,10 +4563,8 @@ gmrf_status gmrf_assemble_precision_batch(gmrf_assembler* as, int64_t batch, con
     return GMRF_OK;
 }
 
-gmrf_status gmrf_assemble_rhs_batch(gmrf_assembler* as, int64_t batch, const double* base, const double* j_vals, const double* x,
-                                    const double* obs_diff, double noise, double* out) {
-    if (!as || !j_vals || !x || !out || !batch_ok(batch)) return bad_shape("null pointer or batch outside [1, 4096]");
-    GCHK(as->ready(AS_PATTERN_ONLY));
+static gmrf_status assemble_rhs_staged(gmrf_assembler* as, int64_t batch, const double* base, const double* j_vals, const double* x,
+                                       const double* obs_diff, double noise, double* out) {
     const double *d_base, *d_jv, *d_x, *d_add;
     double* d_out;
     Staging args(as->arena);
@@ -4660,6 +4579,21 @@ gmrf_status gmrf_assemble_rhs_batch(gmrf_assembler* as, int64_t batch, const dou
     GCHK(args.flush(as->stream));
     HIPCHK(hipStreamSynchronize(as->stream));
     return GMRF_OK;
+}
+
+gmrf_status gmrf_assemble_precision_batch(gmrf_assembler* as, int64_t batch, const double* q_nzval, int64_t q_stride,
+                                          const double* j_vals, double noise, double* out_nzval) {
+    if (!as || !q_nzval || !j_vals || !out_nzval || !batch_ok(batch)) return bad_shape("null pointer or batch outside [1, 4096]");
+    GCHK(q_stride_ok(as, q_stride));
+    GCHK(as->ready(AS_PATTERN_ONLY));
+    return assemble_precision_staged(as, batch, q_nzval, q_stride, j_vals, noise, out_nzval);
+}
+
+gmrf_status gmrf_assemble_rhs_batch(gmrf_assembler* as, int64_t batch, const double* base, const double* j_vals, const double* x,
+                                    const double* obs_diff, double noise, double* out) {
+    if (!as || !j_vals || !x || !out || !batch_ok(batch)) return bad_shape("null pointer or batch outside [1, 4096]");
+    GCHK(as->ready(AS_PATTERN_ONLY));
+    return assemble_rhs_staged(as, batch, base, j_vals, x, obs_diff, noise, out);
 }
 
 gmrf_status gmrf_assemble_objective_batch(gmrf_assembler* as, int64_t batch, const double* q_nzval, int64_t q_stride,
@@ -4685,6 +4619,59 @@ gmrf_status gmrf_assemble_objective_batch(gmrf_assembler* as, int64_t batch, con
     return GMRF_OK;
 }
 
+// --------------------------------------------------------------------------------- what the batched drivers share
+// gmrf_gn, gmrf_dc and gmrf_bic bind a handle and an assembler (and one more object of their own) that live on one device and
+// stream, keep their device buffers in one carved allocation, and run with a buffer of theirs registered as the factor's rhs.
+struct DriverBase {
+    gmrf_handle* h = nullptr;
+    gmrf_assembler* as = nullptr;
+    int device = 0;                      // (copies: a destroy does not reach into the handle)
+    hipStream_t stream = nullptr;
+    DevBuf in;                           // arena of a run's host arguments (Staging)
+    DevBuf work;                         // every device buffer of the driver, carved up by its *_alloc
+    int64_t B = 0;                       // the batch `work` is carved for
+
+    void bind(gmrf_handle* handle, gmrf_assembler* assembler) { h = handle; as = assembler; device = handle->device; stream = handle->stream; }
+    void close() {
+        (void)hipSetDevice(device);
+        (void)hipStreamSynchronize(stream);
+        in.release(); work.release();
+    }
+};
+
+// The driver's `rhs` is the factor's registered right-hand side (gmrf_bt_set_factor_rhs) while this lives: where that route
+// qualifies the factorisation leaves y = L^-1 rhs.  The caller's registration comes back on every way out.
+struct FactorRhsScope {
+    gmrf_handle* h;
+    const double* saved;
+    FactorRhsScope(gmrf_handle* handle, const double* rhs) : h(handle), saved(handle->frhs) { h->frhs = rhs; h->fy_for = nullptr; }
+    ~FactorRhsScope() { h->frhs = saved; h->fy_for = nullptr; }
+    FactorRhsScope(const FactorRhsScope&) = delete;
+    FactorRhsScope& operator=(const FactorRhsScope&) = delete;
+};
+
+// a driver's result to the caller's host or device array; null: not wanted
+static gmrf_status copy_out(hipStream_t st, void* dst, const void* src, size_t bytes) {
+    if (!dst) return GMRF_OK;
+    HIPCHK(hipMemcpyAsync(dst, src, bytes, is_device_ptr(dst) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
+    return GMRF_OK;
+}
+
+// The binding checks every driver makes.  `peer` names the driver's third object, which lives on (peer_device, peer_stream).
+static gmrf_status driver_same_device_stream(const DriverBase* g, int peer_device, hipStream_t peer_stream, const char* peer) {
+    const gmrf_handle* h = g->h;
+    if (g->as->device != h->device || peer_device != h->device)
+        return bad_shape((std::string("handle, assembler and ") + peer + " must live on one device").c_str());
+    if (g->as->stream != h->stream || peer_stream != h->stream)
+        return bad_shape((std::string("handle, assembler and ") + peer + " must share one stream").c_str());
+    return GMRF_OK;
+}
+// ... and, after its own pattern comparison: a handle that has analysed a pattern has analysed the assembler's
+static gmrf_status driver_analysis_ok(const DriverBase* g) {
+    if (g->h->analyzed && (g->h->n != g->as->n || g->h->nnz_in != g->as->nnz_out)) return bad_shape("the handle has not analysed the assembler's pattern");
+    return GMRF_OK;
+}
+
 // --------------------------------------------------------------------------------- the batched Gauss-Newton driver
 // B = batch of the handle Burgers problems on one mesh in lock step (scripts/solve_burger.jl:151-180 per problem).  One iteration
 // on the handle's stream:
@@ -4692,16 +4679,12 @@ gmrf_status gmrf_assemble_objective_batch(gmrf_assembler* as, int64_t batch, con
 // The rhs buffer is registered as the factor's right-hand side (gmrf_bt_set_factor_rhs) for the run: where that route
 // qualifies the factorisation leaves y = L^-1 rhs and the solve is the backward sweep alone.  Problems that have stopped stay in
 // the batch, frozen: their x does not change, so they are re-factored with the same values.
-struct gmrf_gn {
-    gmrf_handle* h = nullptr;
-    gmrf_assembler* as = nullptr;
+struct gmrf_gn : DriverBase {
     gmrf_burgers_p1* b = nullptr;        // the bound tangent: Burgers (gmrf_gn_create) ...
     gmrf_elliptic_p1* e = nullptr;       // ... or nonlinear elliptic (gmrf_gn_create_elliptic); exactly one is set
-    int64_t B = 0;                       // what the buffers below are sized for
-    int32_t hist_steps = -1;
+    int32_t hist_steps = -1;             // the steps `work` is carved for
     double *d_x = nullptr, *d_xn = nullptr, *d_od = nullptr, *d_on = nullptr, *d_f = nullptr, *d_v = nullptr, *d_jv = nullptr;
     double *d_a = nullptr, *d_rhs = nullptr, *d_q = nullptr, *d_part = nullptr, *d_obj = nullptr;
-    DevBuf in;                           // arena of a host qx_prior, x_prior, y: sized by gn_alloc, so a run's Staging never allocates
     double *d_last = nullptr, *d_cur = nullptr, *d_hist = nullptr;
     int32_t *d_steps = nullptr, *d_active = nullptr, *d_take = nullptr;
     unsigned* h_active = nullptr;        // mapped host word the stop rule writes
@@ -4709,19 +4692,8 @@ struct gmrf_gn {
     int64_t q_stride = 0;
     double noise = 0.0;
     bool have_x = false;                 // a run has left its iterate in d_x (gmrf_gn_finalize)
-    int device = 0;                      // (copies: gmrf_gn_destroy does not reach into the handle)
-    hipStream_t stream = nullptr;
     int32_t iterations = 0, fwd_iterations = 0;      // of the last run: iterations, and those whose solve was the backward sweep alone
 };
-
-static void gn_free(gmrf_gn* g) {
-    for (double** p : {&g->d_x, &g->d_xn, &g->d_od, &g->d_on, &g->d_f, &g->d_v, &g->d_jv, &g->d_a, &g->d_rhs, &g->d_q, &g->d_part, &g->d_obj,
-                       &g->d_last, &g->d_cur, &g->d_hist}) { free_dev(*p); *p = nullptr; }
-    g->in.release();
-    free_dev(g->d_steps); free_dev(g->d_active); free_dev(g->d_take);
-    g->d_steps = g->d_active = g->d_take = nullptr;
-    g->B = 0; g->hist_steps = -1; g->have_x = false;
-}
 
 // The one place that knows which tangent is bound: its device, stream and the shape of its J, and its batch launch.
 struct GnTangent { int device; hipStream_t stream; int64_t n, m, nnz; };
@@ -4737,8 +4709,7 @@ static gmrf_status gn_bound_ok(const gmrf_gn* g) {
     const gmrf_handle* h = g->h;
     const GnTangent t = gn_tangent(g);
     if (h->order == GMRF_ORDER_TWISTED) return bad_shape("the Gauss-Newton driver takes a reference-order handle");
-    if (g->as->device != h->device || t.device != h->device) return bad_shape("handle, assembler and tangent must live on one device");
-    if (g->as->stream != h->stream || t.stream != h->stream) return bad_shape("handle, assembler and tangent must share one stream");
+    GCHK(driver_same_device_stream(g, t.device, t.stream, "tangent"));
     if (g->as->n != t.n || g->as->m != t.m || g->as->nnz_j != t.nnz)
         return bad_shape("the assembler's J is not the tangent's pattern");
     return GMRF_OK;
@@ -4747,7 +4718,7 @@ static gmrf_status gn_bound_ok(const gmrf_gn* g) {
 static gmrf_status gn_create(gmrf_handle* h, gmrf_assembler* as, gmrf_burgers_p1* b, gmrf_elliptic_p1* el, gmrf_gn** out) {
     if (!h || !as || (!b && !el) || !out) return bad_shape("null pointer");
     if (as->device < 0 || (b ? b->device : el->device) < 0) return bad_shape("the Gauss-Newton driver needs an assembler and a tangent with a device");
-    gmrf_gn tmp; tmp.h = h; tmp.as = as; tmp.b = b; tmp.e = el; tmp.device = h->device; tmp.stream = h->stream;
+    gmrf_gn tmp; tmp.bind(h, as); tmp.b = b; tmp.e = el;
     GCHK(gn_bound_ok(&tmp));
     HIPCHK(hipSetDevice(h->device));
     auto* g = new gmrf_gn(tmp);
@@ -4771,9 +4742,7 @@ gmrf_status gmrf_gn_create_elliptic(gmrf_handle* h, gmrf_assembler* as, gmrf_ell
 
 gmrf_status gmrf_gn_destroy(gmrf_gn* g) {
     if (!g) return GMRF_OK;
-    (void)hipSetDevice(g->device);
-    (void)hipStreamSynchronize(g->stream);
-    gn_free(g);
+    g->close();
     if (g->h_active) (void)hipHostFree(g->h_active);
     delete g;
     return GMRF_OK;
@@ -4782,25 +4751,22 @@ gmrf_status gmrf_gn_destroy(gmrf_gn* g) {
 static gmrf_status gn_alloc(gmrf_gn* g, int64_t B, int32_t max_steps) {
     const gmrf_assembler* as = g->as;
     if (g->B == B && g->hist_steps >= max_steps) return GMRF_OK;
-    HIPCHK(hipStreamSynchronize(g->h->stream));
-    gn_free(g);
+    g->B = 0; g->hist_steps = -1; g->have_x = false;     // (the iterate of an earlier run goes with its layout)
     const int64_t n = as->n, m = as->m;
-    auto dm = [&](double** p, int64_t elems) { return hipMalloc(p, sizeof(double) * (size_t)std::max<int64_t>(elems, 1)); };
-    HIPCHK(dm(&g->d_x, B * n)); HIPCHK(dm(&g->d_xn, B * n)); HIPCHK(dm(&g->d_rhs, B * n));
-    HIPCHK(dm(&g->d_od, B * m)); HIPCHK(dm(&g->d_on, B * m)); HIPCHK(dm(&g->d_f, B * m)); HIPCHK(dm(&g->d_v, B * m));
-    HIPCHK(dm(&g->d_jv, B * as->nnz_j)); HIPCHK(dm(&g->d_a, B * as->nnz_out)); HIPCHK(dm(&g->d_q, B * as->nnz_q));
-    HIPCHK(dm(&g->d_part, B * objective_chunks(as))); HIPCHK(dm(&g->d_obj, B));
+    auto lay = [&](char* base) {
+        Carve c{base};
+        c(&g->d_x, B * n); c(&g->d_xn, B * n); c(&g->d_rhs, B * n);
+        c(&g->d_od, B * m); c(&g->d_on, B * m); c(&g->d_f, B * m); c(&g->d_v, B * m);
+        c(&g->d_jv, B * as->nnz_j); c(&g->d_a, B * as->nnz_out); c(&g->d_q, B * as->nnz_q);
+        c(&g->d_part, B * objective_chunks(as)); c(&g->d_obj, B);
+        c(&g->d_last, B); c(&g->d_cur, B); c(&g->d_hist, B * ((int64_t)max_steps + 1));
+        c(&g->d_steps, B); c(&g->d_active, B); c(&g->d_take, B);
+        return c.used;
+    };
+    GCHK(g->work.reserve(g->h->stream, lay(nullptr)));
+    lay(g->work.as<char>());
     GCHK(g->in.reserve(g->h->stream, 2 * Staging::padded(sizeof(double) * B * n) + Staging::padded(sizeof(double) * B * m)));      // qx_prior, x_prior, y
-    HIPCHK(dm(&g->d_last, B)); HIPCHK(dm(&g->d_cur, B)); HIPCHK(dm(&g->d_hist, B * ((int64_t)max_steps + 1)));
-    HIPCHK(hipMalloc(&g->d_steps, sizeof(int32_t) * B)); HIPCHK(hipMalloc(&g->d_active, sizeof(int32_t) * B));
-    HIPCHK(hipMalloc(&g->d_take, sizeof(int32_t) * B));
     g->B = B; g->hist_steps = max_steps;
-    return GMRF_OK;
-}
-
-static gmrf_status gn_copy_out(gmrf_gn* g, void* dst, const void* src, size_t bytes) {
-    if (!dst) return GMRF_OK;
-    HIPCHK(hipMemcpyAsync(dst, src, bytes, is_device_ptr(dst) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, g->h->stream));
     return GMRF_OK;
 }
 
@@ -4852,7 +4818,7 @@ gmrf_status gmrf_gn_run(gmrf_gn* g, const double* q_nzval, int64_t q_stride, con
     GCHK(q_stride_ok(as, q_stride));
     if (max_steps < 0 || max_steps > (1 << 20) || !(rtol >= 0.0)) return bad_shape("max_steps in [0, 2^20], rtol >= 0");
     if (!h->analyzed) { g_last_error = "gmrf_gn_run: factor the assembler's pattern once on this handle first"; return GMRF_ERR_NO_FACTOR; }
-    if (h->n != as->n || h->nnz_in != as->nnz_out) return bad_shape("the handle has not analysed the assembler's pattern");
+    GCHK(driver_analysis_ok(g));
     HIPCHK(hipSetDevice(h->device));
     GCHK(objective_ready(as));
     const int64_t B = h->B, n = as->n, m = as->m, wide = std::max(n, m);
@@ -4880,9 +4846,7 @@ gmrf_status gmrf_gn_run(gmrf_gn* g, const double* q_nzval, int64_t q_stride, con
     hipLaunchKernelGGL(gn_decide, dim3(1), dim3(256), 0, st, s, g->d_obj, B, rtol, max_steps, 1);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(st));
-    // the rhs buffer rides in the factorisations of this run; the caller's registration comes back afterwards
-    const double* user_frhs = h->frhs;
-    h->frhs = g->d_rhs; h->fy_for = nullptr;
+    const FactorRhsScope registered(h, g->d_rhs);         // the rhs buffer rides in the factorisations of this run
     gmrf_status status = GMRF_OK;
     g->iterations = g->fwd_iterations = 0;
     auto iteration = [&]() -> gmrf_status {
@@ -4906,11 +4870,10 @@ gmrf_status gmrf_gn_run(gmrf_gn* g, const double* q_nzval, int64_t q_stride, con
         status = iteration();
         if (status == GMRF_OK) g->iterations += 1;
     }
-    h->frhs = user_frhs; h->fy_for = nullptr;
     // x holds the last complete iterate of every problem, also after a failed factorisation
-    gmrf_status out_status = gn_copy_out(g, x, g->d_x, sizeof(double) * B * n);
-    if (out_status == GMRF_OK) out_status = gn_copy_out(g, steps_out, g->d_steps, sizeof(int32_t) * B);
-    if (out_status == GMRF_OK) out_status = gn_copy_out(g, obj_hist_out, g->d_hist, sizeof(double) * B * ((size_t)max_steps + 1));
+    gmrf_status out_status = copy_out(st, x, g->d_x, sizeof(double) * B * n);
+    if (out_status == GMRF_OK) out_status = copy_out(st, steps_out, g->d_steps, sizeof(int32_t) * B);
+    if (out_status == GMRF_OK) out_status = copy_out(st, obj_hist_out, g->d_hist, sizeof(double) * B * ((size_t)max_steps + 1));
     HIPCHK(hipStreamSynchronize(st));
     return status != GMRF_OK ? status : out_status;
 }
@@ -4934,18 +4897,12 @@ gmrf_status gmrf_gn_finalize(gmrf_gn* g, int32_t* info) {
 // The information vector is registered as the factor's right-hand side (gmrf_bt_set_factor_rhs) for the run, as gmrf_gn_run
 // does.  Mean / samples and the variances go through the public calls' own abort-and-repeat guards (sweep_guarded); every
 // intermediate -- A's values, the posterior values the RBMC product reads -- stays in the driver's buffers on the device.
-struct gmrf_dc {
-    gmrf_handle* h = nullptr;
-    gmrf_assembler* as = nullptr;
+struct gmrf_dc : DriverBase {
     gmrf_darcy_p1* d = nullptr;
     gmrf_csr* Qp = nullptr;              // the posterior pattern as a CSR matrix (tile plan of the RBMC product), made by the first RBMC run
-    DevBuf in;                           // arena of host tables, q_nzval, q_mu (Staging)
-    DevBuf work;                         // everything below, carved up by dc_alloc
-    int64_t B = 0, ks = -1;              // what `work` is carved for
+    int64_t ks = -1;                     // the samples `work` is carved for
     double *d_av = nullptr, *d_y = nullptr, *d_dw = nullptr, *d_nz = nullptr, *d_rhs = nullptr, *d_mean = nullptr, *d_smp = nullptr;
     double *d_var = nullptr, *d_diag = nullptr, *d_part = nullptr, *d_norm = nullptr;
-    int device = 0;                      // (copies: gmrf_dc_destroy does not reach into the handle)
-    hipStream_t stream = nullptr;
     int32_t fwd_in_factor = 0;           // the last run's factorisation left y = L^-1 rhs (gmrf_test_dc_route)
 };
 
@@ -4957,12 +4914,10 @@ static int64_t std_norm_chunks(int64_t n) { return std::min<int64_t>(1024, std::
 static gmrf_status dc_bound_ok(const gmrf_dc* g) {
     const gmrf_handle* h = g->h;
     GCHK(tw_refuse(h, "the Darcy conditioning driver"));
-    if (g->as->device != h->device || g->d->device != h->device) return bad_shape("handle, assembler and Darcy assembler must live on one device");
-    if (g->as->stream != h->stream || g->d->stream != h->stream) return bad_shape("handle, assembler and Darcy assembler must share one stream");
+    GCHK(driver_same_device_stream(g, g->d->device, g->d->stream, "Darcy assembler"));
     if (g->as->n != g->d->n || g->as->m != g->d->n || g->as->nnz_j != g->d->nnz)
         return bad_shape("the assembler's J is not the Darcy assembler's pattern");
-    if (h->analyzed && (h->n != g->as->n || h->nnz_in != g->as->nnz_out)) return bad_shape("the handle has not analysed the assembler's pattern");
-    return GMRF_OK;
+    return driver_analysis_ok(g);
 }
 
 gmrf_status gmrf_dc_create(gmrf_handle* h, gmrf_assembler* as, gmrf_darcy_p1* d, gmrf_dc** out) {
@@ -4972,7 +4927,7 @@ gmrf_status gmrf_dc_create(gmrf_handle* h, gmrf_assembler* as, gmrf_darcy_p1* d,
         return GMRF_ERR_NO_DEVICE;
     }
     if (!h) return bad_shape("null handle");
-    gmrf_dc tmp; tmp.h = h; tmp.as = as; tmp.d = d; tmp.device = h->device; tmp.stream = h->stream;
+    gmrf_dc tmp; tmp.bind(h, as); tmp.d = d;
     GCHK(dc_bound_ok(&tmp));
     *out = new gmrf_dc(tmp);
     return GMRF_OK;
@@ -4980,10 +4935,8 @@ gmrf_status gmrf_dc_create(gmrf_handle* h, gmrf_assembler* as, gmrf_darcy_p1* d,
 
 gmrf_status gmrf_dc_destroy(gmrf_dc* g) {
     if (!g) return GMRF_OK;
-    (void)hipSetDevice(g->device);
-    (void)hipStreamSynchronize(g->stream);
+    g->close();
     if (g->Qp) (void)gmrf_csr_destroy(g->Qp);
-    g->in.release(); g->work.release();
     delete g;
     return GMRF_OK;
 }
@@ -4992,15 +4945,15 @@ static gmrf_status dc_alloc(gmrf_dc* g, int64_t B, int64_t ks) {
     if (g->B == B && g->ks == ks && g->work.p) return GMRF_OK;
     const gmrf_assembler* as = g->as;
     const int64_t n = as->n;
-    int64_t total = 0;
-    auto take = [&](int64_t elems) { const int64_t at = total; total += (std::max<int64_t>(elems, 1) + 1) & ~(int64_t)1; return at; };     // (16-byte aligned pieces)
-    const int64_t o_av = take(B * as->nnz_j), o_y = take(B * n), o_dw = take(darcy_batch_work_elems(g->d, B)), o_nz = take(B * as->nnz_out);
-    const int64_t o_rhs = take(B * n), o_mean = take(B * n), o_smp = take(B * ks * n), o_var = take(B * n), o_diag = take(B * n);
-    const int64_t o_part = take(B * std_norm_chunks(n)), o_norm = take(B);
-    GCHK(g->work.reserve(g->h->stream, sizeof(double) * (size_t)total));
-    double* w = g->work.as<double>();
-    g->d_av = w + o_av; g->d_y = w + o_y; g->d_dw = w + o_dw; g->d_nz = w + o_nz; g->d_rhs = w + o_rhs; g->d_mean = w + o_mean;
-    g->d_smp = w + o_smp; g->d_var = w + o_var; g->d_diag = w + o_diag; g->d_part = w + o_part; g->d_norm = w + o_norm;
+    auto lay = [&](char* base) {
+        Carve c{base};
+        c(&g->d_av, B * as->nnz_j); c(&g->d_y, B * n); c(&g->d_dw, darcy_batch_work_elems(g->d, B)); c(&g->d_nz, B * as->nnz_out);
+        c(&g->d_rhs, B * n); c(&g->d_mean, B * n); c(&g->d_smp, B * ks * n); c(&g->d_var, B * n); c(&g->d_diag, B * n);
+        c(&g->d_part, B * std_norm_chunks(n)); c(&g->d_norm, B);
+        return c.used;
+    };
+    GCHK(g->work.reserve(g->h->stream, lay(nullptr)));
+    lay(g->work.as<char>());
     g->B = B; g->ks = ks;
     return GMRF_OK;
 }
@@ -5051,10 +5004,9 @@ gmrf_status gmrf_dc_run(gmrf_dc* g, const double* coeff_tables, int64_t ng, doub
                        as->d_jt_src, g->d_av, as->nnz_j, g->d_y, as->m, d_qmu, q_eps, n, g->d_rhs);
     HIPCHK(hipGetLastError());
     // 4 - 6 behind the registration; the caller's comes back afterwards
-    const double* user_frhs = h->frhs;
-    h->frhs = g->d_rhs; h->fy_for = nullptr;
     g->fwd_in_factor = 0;
     auto solve = [&]() -> gmrf_status {
+        const FactorRhsScope registered(h, g->d_rhs);
         GCHK(numeric_factor(h, g->d_nz, info));
         g->fwd_in_factor = (h->fy_for && h->fy_for == g->d_rhs) ? 1 : 0;
         if (k_samples > 0) GCHK(gmrf_bt_posterior(h, g->d_rhs, sample_seed, 0, k_samples, g->d_mean, g->d_smp, n));
@@ -5069,7 +5021,6 @@ gmrf_status gmrf_dc_run(gmrf_dc* g, const double* coeff_tables, int64_t ng, doub
         return GMRF_OK;
     };
     const gmrf_status status = solve();
-    h->frhs = user_frhs; h->fy_for = nullptr;
     if (status != GMRF_OK) { (void)hipStreamSynchronize(st); return status; }      // (the outputs are untouched)
     // 7: std = sqrt(var) in place, |std| per problem
     if (var_method != -1) {
@@ -5078,15 +5029,10 @@ gmrf_status gmrf_dc_run(gmrf_dc* g, const double* coeff_tables, int64_t ng, doub
         hipLaunchKernelGGL(std_norm_finish, dim3(1, (unsigned)B), dim3(256), 0, st, g->d_part, nch, g->d_norm);
         HIPCHK(hipGetLastError());
     }
-    auto copy_out = [&](double* dst, const double* src, int64_t count) -> gmrf_status {
-        if (!dst) return GMRF_OK;
-        HIPCHK(hipMemcpyAsync(dst, src, sizeof(double) * (size_t)count, is_device_ptr(dst) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
-        return GMRF_OK;
-    };
-    GCHK(copy_out(mean_out, g->d_mean, B * n));
-    GCHK(copy_out(samples_out, g->d_smp, B * k_samples * n));
-    GCHK(copy_out(std_out, g->d_var, B * n));
-    GCHK(copy_out(std_norm_out, g->d_norm, B));
+    GCHK(copy_out(st, mean_out, g->d_mean, sizeof(double) * B * n));
+    GCHK(copy_out(st, samples_out, g->d_smp, sizeof(double) * B * k_samples * n));
+    GCHK(copy_out(st, std_out, g->d_var, sizeof(double) * B * n));
+    GCHK(copy_out(st, std_norm_out, g->d_norm, sizeof(double) * B));
     HIPCHK(hipStreamSynchronize(st));
     return GMRF_OK;
 }
@@ -5099,27 +5045,18 @@ gmrf_status gmrf_dc_run(gmrf_dc* g, const double* coeff_tables, int64_t ng, doub
 // on the handle and the analysis the Gauss-Newton driver uses afterwards: the assembler's pattern, that of Q + J'J, filled by the
 // assembler's own kernel with noise 0 and J = 0.  Qx_prior is registered as the factor's right-hand side (gmrf_bt_set_factor_rhs)
 // for the run, as gmrf_dc_run does; the caller's registration comes back afterwards.
-struct gmrf_bic {
-    gmrf_handle* h = nullptr;
-    gmrf_assembler* as = nullptr;
+struct gmrf_bic : DriverBase {
     gmrf_burgers_prior* pr = nullptr;
-    DevBuf in;                           // arena of a host ic (Staging)
-    DevBuf work;                         // everything below, carved up by bic_alloc
-    int64_t B = 0;                       // what `work` is carved for
     double *d_bulk = nullptr, *d_q = nullptr, *d_qx = nullptr, *d_jz = nullptr, *d_a = nullptr, *d_x = nullptr;
-    int device = 0;                      // (copies: gmrf_bic_destroy does not reach into the handle)
-    hipStream_t stream = nullptr;
     int32_t fwd_in_factor = 0;           // the last run's factorisation left y = L^-1 Qx_prior (gmrf_test_bic_route)
 };
 
 static gmrf_status bic_bound_ok(const gmrf_bic* g) {
     const gmrf_handle* h = g->h;
     GCHK(tw_refuse(h, "the Burgers initial-condition driver"));
-    if (g->as->device != h->device || g->pr->device != h->device) return bad_shape("handle, assembler and Burgers prior must live on one device");
-    if (g->as->stream != h->stream || g->pr->stream != h->stream) return bad_shape("handle, assembler and Burgers prior must share one stream");
+    GCHK(driver_same_device_stream(g, g->pr->device, g->pr->stream, "Burgers prior"));
     if (g->as->n != g->pr->n || g->as->nnz_q != g->pr->nnz) return bad_shape("the assembler's Q is not the Burgers prior's pattern");
-    if (h->analyzed && (h->n != g->as->n || h->nnz_in != g->as->nnz_out)) return bad_shape("the handle has not analysed the assembler's pattern");
-    return GMRF_OK;
+    return driver_analysis_ok(g);
 }
 
 gmrf_status gmrf_bic_create(gmrf_handle* h, gmrf_assembler* as, gmrf_burgers_prior* prior, gmrf_bic** out) {
@@ -5129,7 +5066,7 @@ gmrf_status gmrf_bic_create(gmrf_handle* h, gmrf_assembler* as, gmrf_burgers_pri
         return GMRF_ERR_NO_DEVICE;
     }
     if (!h) return bad_shape("null handle");
-    gmrf_bic tmp; tmp.h = h; tmp.as = as; tmp.pr = prior; tmp.device = h->device; tmp.stream = h->stream;
+    gmrf_bic tmp; tmp.bind(h, as); tmp.pr = prior;
     GCHK(bic_bound_ok(&tmp));
     // the same sizes are not yet the same pattern: entry by entry against the prior's statement of it
     if (as->q_ptr.empty()) return bad_shape("the Burgers initial-condition driver needs n < 2^31");
@@ -5148,9 +5085,7 @@ gmrf_status gmrf_bic_create(gmrf_handle* h, gmrf_assembler* as, gmrf_burgers_pri
 
 gmrf_status gmrf_bic_destroy(gmrf_bic* g) {
     if (!g) return GMRF_OK;
-    (void)hipSetDevice(g->device);
-    (void)hipStreamSynchronize(g->stream);
-    g->in.release(); g->work.release();
+    g->close();
     delete g;
     return GMRF_OK;
 }
@@ -5158,13 +5093,14 @@ gmrf_status gmrf_bic_destroy(gmrf_bic* g) {
 static gmrf_status bic_alloc(gmrf_bic* g, int64_t B) {
     if (g->B == B && g->work.p) return GMRF_OK;
     const gmrf_assembler* as = g->as;
-    int64_t total = 0;
-    auto take = [&](int64_t elems) { const int64_t at = total; total += (std::max<int64_t>(elems, 1) + 1) & ~(int64_t)1; return at; };     // (16-byte aligned pieces)
-    const int64_t o_bulk = take(B), o_q = take(B * as->nnz_q), o_qx = take(B * as->n), o_jz = take(as->nnz_j), o_a = take(B * as->nnz_out);
-    const int64_t o_x = take(B * as->n);
-    GCHK(g->work.reserve(g->h->stream, sizeof(double) * (size_t)total));
-    double* w = g->work.as<double>();
-    g->d_bulk = w + o_bulk; g->d_q = w + o_q; g->d_qx = w + o_qx; g->d_jz = w + o_jz; g->d_a = w + o_a; g->d_x = w + o_x;
+    auto lay = [&](char* base) {
+        Carve c{base};
+        c(&g->d_bulk, B); c(&g->d_q, B * as->nnz_q); c(&g->d_qx, B * as->n); c(&g->d_jz, as->nnz_j); c(&g->d_a, B * as->nnz_out);
+        c(&g->d_x, B * as->n);
+        return c.used;
+    };
+    GCHK(g->work.reserve(g->h->stream, lay(nullptr)));
+    lay(g->work.as<char>());
     // J = 0, once: one array serves every problem (a stride of 0), and nothing writes it
     HIPCHK(hipMemsetAsync(g->d_jz, 0, sizeof(double) * (size_t)std::max<int64_t>(as->nnz_j, 1), g->h->stream));
     g->B = B;
@@ -5194,10 +5130,9 @@ gmrf_status gmrf_bic_run(gmrf_bic* g, const double* ic, double* x_ic_out, double
                        as->d_pa, as->d_pb, as->d_qmap, g->d_q, as->nnz_q, g->d_jz, (int64_t)0, 0.0, as->nnz_out, g->d_a);
     HIPCHK(hipGetLastError());
     // 3 - 4 behind the registration; the caller's comes back afterwards
-    const double* user_frhs = h->frhs;
-    h->frhs = g->d_qx; h->fy_for = nullptr;
     g->fwd_in_factor = 0;
     auto solve = [&]() -> gmrf_status {
+        const FactorRhsScope registered(h, g->d_qx);
         GCHK(numeric_factor(h, g->d_a, info));
         bool took_y = false;
         GCHK(solve_registered(h, g->d_qx, g->d_x, &took_y));
@@ -5205,17 +5140,11 @@ gmrf_status gmrf_bic_run(gmrf_bic* g, const double* ic, double* x_ic_out, double
         return GMRF_OK;
     };
     const gmrf_status status = solve();
-    h->frhs = user_frhs; h->fy_for = nullptr;
     if (status != GMRF_OK) { (void)hipStreamSynchronize(st); return status; }      // (the outputs are untouched)
-    auto copy_out = [&](double* dst, const double* src, int64_t count) -> gmrf_status {
-        if (!dst) return GMRF_OK;
-        HIPCHK(hipMemcpyAsync(dst, src, sizeof(double) * (size_t)count, is_device_ptr(dst) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
-        return GMRF_OK;
-    };
-    GCHK(copy_out(x_ic_out, g->d_x, B * n));
-    GCHK(copy_out(q_values_out, g->d_q, B * as->nnz_q));
-    GCHK(copy_out(qx_out, g->d_qx, B * n));
-    GCHK(copy_out(bulk_out, g->d_bulk, B));
+    GCHK(copy_out(st, x_ic_out, g->d_x, sizeof(double) * B * n));
+    GCHK(copy_out(st, q_values_out, g->d_q, sizeof(double) * B * as->nnz_q));
+    GCHK(copy_out(st, qx_out, g->d_qx, sizeof(double) * B * n));
+    GCHK(copy_out(st, bulk_out, g->d_bulk, sizeof(double) * B));
     HIPCHK(hipStreamSynchronize(st));
     return GMRF_OK;
 }

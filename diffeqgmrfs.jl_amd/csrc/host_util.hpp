@@ -1,5 +1,5 @@
-// Host-side plumbing shared by the handles of gmrf_hip.hip: a grow-only device buffer, a device context (device +
-// stream) and the staging of host-resident arguments.  Included by gmrf_hip.hip after g_last_error, HIPCHK / GCHK,
+// Host-side plumbing shared by the handles of gmrf_hip.hip: a grow-only device buffer and its carving into pieces, a device
+// context (device + stream) and the staging of host-resident arguments.  Included by gmrf_hip.hip after g_last_error, HIPCHK / GCHK,
 // bad_shape and is_device_ptr; no kernels here.
 #pragma once
 
@@ -125,5 +125,16 @@ private:
     void add(void* p, size_t bytes, void** dev, bool out) {
         if (count == (int)(sizeof(items) / sizeof(items[0]))) { overflow = true; return; }
         items[count++] = {p, bytes, dev, out, nullptr};
+    }
+};
+
+// Lays the pieces of one allocation out behind `base`, each 16-byte aligned and never empty.  A layout runs twice over the same
+// list: with a null base for the size alone (no piece is written), then with the buffer.
+struct Carve {
+    char* base;
+    size_t used = 0;
+    template <class T> void operator()(T** piece, int64_t elems) {
+        if (base) *piece = reinterpret_cast<T*>(base + used);
+        used += Staging::padded(sizeof(T) * (size_t)std::max<int64_t>(elems, 1));
     }
 };

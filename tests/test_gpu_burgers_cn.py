@@ -79,7 +79,7 @@ def test_crank_nicolson_against_the_euler_kernel(pkg, order, bc):
     Each device value is within 1e-14 max |J| of the exact one (the parity bound above), so the two sides differ by at most
     (1 + 1/2 + 1/2) and (1 + 1/2 + 3/2) times that."""
     nc, nt = 67, 5
-    length = 1.0 if bc == "periodic" else LENGTH        # (periodic, length 1: the Euler side is burgers_p1_rows / burgers_p2_rows)
+    length = 1.0 if bc == "periodic" else LENGTH        # (periodic, length 1: the Euler side is burgers_p1_rows_batch / burgers_p2_rows_batch)
     be, bc_ = tangent(pkg, nc, nt, order, "euler", bc, length), tangent(pkg, nc, nt, order, "cn", bc, length)
     w = smooth_plus_noise(be.ns, nt, 9)
     ve, _ = be.tangent(w)

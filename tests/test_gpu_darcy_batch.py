@@ -118,6 +118,27 @@ def test_assembly_batch_is_the_one_problem_call_bitwise(pkg, order, nx, ny):
         assert np.max(np.abs(fb[p] - fo)) < 1e-14 * np.max(np.abs(fo))
 
 
+@pytest.mark.parametrize("order", [1, 2])
+def test_one_darcy_assembler_serves_every_call_in_turn(pkg, order):
+    """One assembler's batch and one-problem calls share its arena and its work buffer: batch of 3, table 1, batch of 3 again,
+    table 2, with host arrays and with device tensors.  Every result is that of the same call on a fresh assembler, and each
+    one-problem result is its row of the batch, bit for bit.  5 x 4 nodes, ng = 7: interior, edge and corner rows, a 2 x 2
+    block of quadratic cells."""
+    import torch
+    nx, ny, ng = 5, 4, 7
+    tabs = np.exp(np.random.default_rng(11).standard_normal((3, ng, ng)))
+    host = lambda a: a.cpu().numpy() if torch.is_tensor(a) else a      # noqa: E731
+    for kind, t in (("host", tabs), ("device", torch.from_numpy(tabs).cuda())):
+        calls = [("assemble_batch", t), ("assemble", t[1]), ("assemble_batch", t), ("assemble", t[2])]
+        d = pkg.DarcyP1Assembler(nx, ny, order=order)
+        got = [[host(a) for a in getattr(d, name)(arg, beta=2.0)] for name, arg in calls]
+        for i, (name, arg) in enumerate(calls):
+            want = getattr(pkg.DarcyP1Assembler(nx, ny, order=order), name)(arg, beta=2.0)
+            assert all(np.array_equal(g, host(w)) for g, w in zip(got[i], want)), (kind, i, name)
+        for one, row in ((1, 1), (3, 2)):
+            assert all(np.array_equal(g, b[row]) for g, b in zip(got[one], got[0])), (kind, row)
+
+
 def _run_vs_composed(pkg, e, device_inputs):
     import torch
     rng = np.random.default_rng(4)

@@ -6890,6 +6890,48 @@ gmrf_status gmrf_test_potrf_block(int32_t device, int64_t bs, double* S, double*
     return s;
 }
 
+// potrf_block once, on whichever route a handle of this shape takes: N = 1, `batch` problems, set_eager(eager_bits), keep_l, a
+// coupling window that starts at cmin (what planned_xsplit looks at).  S, L, Linv: host, [batch][bs][bs]; all three are uploaded
+// whole (so the caller decides what the kernels find where they do not write) and L, Linv are read back whole.  info: the info
+// word as the kernels left it (0, or 1 + problem).  route[4] = {potrf_route, stats.persist_route, xsplit, persistent waits that
+// gave up}.  Launches what the factorisation launches and nothing else; no stamps, no forward solve.
+gmrf_status gmrf_test_potrf_route(int32_t device, int64_t bs, int32_t batch, int32_t eager_bits, int64_t cmin, int32_t keep_l,
+                                  double* S, double* L, double* Linv, int32_t* info, int32_t* route) {
+    if (!S || !L || !Linv || !info || !route) return bad_shape("null pointer");
+    if (bs < 64 || bs % 64 || next_pow2(bs / 64) != bs / 64) return bad_shape("bs must be 64 * 2^p");
+    if (batch < 1) return bad_shape("batch must be >= 1");
+    if (cmin < 0 || cmin >= bs || cmin % 64) return bad_shape("cmin must be a multiple of 64 in [0, bs)");
+    gmrf_handle* h = nullptr;
+    GCHK(gmrf_bt_create(device, nullptr, &h));
+    h->N = 1; h->n = bs; h->bs = bs; h->bsp = bs; h->n_pad = bs; h->B = batch;
+    h->keep_l = keep_l != 0;
+    gmrf_status s = gmrf_bt_set_eager(h, eager_bits);
+    if (s == GMRF_OK) s = set_layout(h, cmin, bs, std::vector<int64_t>((size_t)(bs / 64), cmin));
+    if (s == GMRF_OK) s = alloc_factor(h);
+    if (s == GMRF_OK) {
+        const size_t bytes = sizeof(double) * (size_t)bs * (size_t)bs * (size_t)batch;
+        h->xsplit = planned_xsplit(h);
+        persist_plan(h);
+        hipError_t e = hipMemcpyAsync(h->d_S, S, bytes, hipMemcpyHostToDevice, h->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(h->d_L, L, bytes, hipMemcpyHostToDevice, h->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(h->d_Linv, Linv, bytes, hipMemcpyHostToDevice, h->stream);
+        if (e != hipSuccess) s = GMRF_ERR_HIP;
+        if (s == GMRF_OK) s = potrf_block(h, h->d_S, h->d_L, h->d_Linv, h->d_T, 1);
+        if (s == GMRF_OK) {
+            int hi[2] = {0, 0};
+            (void)hipMemcpyAsync(hi, h->d_info, 2 * sizeof(int), hipMemcpyDeviceToHost, h->stream);
+            (void)hipMemcpyAsync(L, h->d_L, bytes, hipMemcpyDeviceToHost, h->stream);
+            (void)hipMemcpyAsync(Linv, h->d_Linv, bytes, hipMemcpyDeviceToHost, h->stream);
+            if (hipStreamSynchronize(h->stream) != hipSuccess) s = GMRF_ERR_HIP;
+            if (s == GMRF_OK && hi[1] != 0) persist_give_up(h);          // (counted, not repeated: the caller sees it in route[3])
+            *info = hi[0];
+            route[0] = potrf_route(h); route[1] = h->stats.persist_route; route[2] = h->xsplit; route[3] = h->persist_aborts;
+        }
+    }
+    gmrf_bt_destroy(h);
+    return s;
+}
+
 gmrf_status gmrf_test_mfma_f64_rate(int32_t device, double* tflops) {
     HIPCHK(hipSetDevice(device));
     double* d;

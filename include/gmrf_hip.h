@@ -766,6 +766,16 @@ gmrf_status gmrf_test_potrf_tile(int32_t device, double* tile64 /* in: SPD, out:
 gmrf_status gmrf_test_tile_timing(double* out, int32_t n);
 gmrf_status gmrf_test_potrf_block(int32_t device, int64_t bs, double* S /* in/out: L */,
                                   double* Linv, int32_t* info);
+/* The in-block Cholesky (potrf_block) once, on the route a handle of this shape takes: one block per problem, `batch` problems,
+ * gmrf_bt_set_eager(eager_bits), gmrf_bt_set_keep_l(keep_l), a coupling window that starts at column cmin (a multiple of 64 in
+ * [0, bs): what decides the split inverse).  bs = 64 * 2^p.  S, L, Linv: host, [batch][bs][bs] row-major; all three are uploaded
+ * whole and L, Linv read back whole, so the caller sees what the kernels wrote and what they left.  *info: 0, or 1 + the index of a
+ * problem with a non-positive pivot.  route[4]: the route (1 fused, 2 big one-problem, 3 256-column panels, 4 steps),
+ * gmrf_stats.persist_route of the launches (0 none, 1 block, 2 panel, 3 diagonal block of a batch), the split p of the inverse
+ * (0: full), and the number of persistent waits that gave up.  Bad arguments: GMRF_ERR_BAD_SHAPE, nothing launched.
+ * tests/potrf_ref.py states the contract of the three buffers. */
+gmrf_status gmrf_test_potrf_route(int32_t device, int64_t bs, int32_t batch, int32_t eager_bits, int64_t cmin, int32_t keep_l,
+                                  double* S, double* L, double* Linv, int32_t* info, int32_t* route);
 /* s_memtime stamps of the chain workgroup of the last gmrf_test_potrf_block that took the persistent form
  * (csrc/potrf_persist.hpp): out[0] = tile 0 done, then eight per step (tools/persist_stamps.py names them); cycles relative to out[0], -1 = not written. */
 gmrf_status gmrf_test_persist_stamps(double* out, int32_t n);

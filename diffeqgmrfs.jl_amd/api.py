@@ -438,8 +438,8 @@ class BurgersP1Prior:
     (`workloads.burgers_prior_from_bulk`).  Every problem has its own values through bulk = mean(ic), on ONE structural pattern:
     `pattern` is the CSC matrix (values 1; symmetric, nt blocks of ns, offsets 0, +-1, +-2 in the diagonal blocks and 0, +-1 beside
     them) whose `.data` order `values_batch` fills.  An entry whose value is 0.0 is stored, SciPy prunes such entries: compare
-    matrices, not `.data` arrays.  P1 only: the reference's order-2 line has no restatement of the prior in `workloads` to build
-    against.  device = -1: pattern only (no GPU needed)."""
+    matrices, not `.data` arrays.  The other lines of `BurgersP1Tangent` -- quadratic, dirichlet, any length -- have their prior in
+    `BurgersLinePrior`.  device = -1: pattern only (no GPU needed)."""
 
     def __init__(self, ns: int, nt: int, dt: float, nu: float, ic_noise: float = 1e8, device: int = 0, stream: int = 0):
         self.ns, self.nt, self.dt, self.nu, self.ic_noise = int(ns), int(nt), float(dt), float(nu), float(ic_noise)
@@ -484,6 +484,41 @@ class BurgersP1Prior:
         _cabi.check(_cabi.load().gmrf_burgers_prior_values_batch(self._h, B, _cabi.ptr(v), _cabi.ptr(out["bulk"]), _cabi.ptr(out["q_values"]),
                                                                  _cabi.ptr(out["Qx_prior"])))
         return out
+
+
+class BurgersLinePrior(BurgersP1Prior):
+    """`BurgersP1Prior` on every line `BurgersP1Tangent` serves: nc cells of length / nc, order 1 or 2, bc = "periodic" (ns =
+    order nc dofs) or "dirichlet" (ns = order nc + 1, `pin` added on the diagonal of dofs 0 and ns - 1 of every slice) -- the
+    periodic quadratic line the reference's `form_prior` runs on (/root/reference/scripts/burgers/solve_burgers_gmrf-fem.jl:71-72,
+    :86-107) and the interval of _research/burgers_chen24.jl, as `workloads.burgers_line_prior_from_bulk` states the prior.
+    ic_obs = "all": the initial condition is observed at every dof of slice 0 that is not pinned; "vertices" (order 2): at the even
+    ones of them, one point per cell; bulk is the mean of ic over the observed dofs (ics stay (B, ns)).  `pattern` holds the offsets
+    0 .. +-2 order in the diagonal blocks and 0 .. +-order beside them, wrapped (periodic) or clipped (dirichlet).  `.pattern`,
+    `.values_batch` and `BurgersInitialConditionBatch` as for `BurgersP1Prior`; (order 1, periodic, length 1) is that prior
+    evaluated by other kernels (gmrf_burgers_line_prior_create).  device = -1: pattern only."""
+
+    IC_OBS = {"all": 0, "vertices": 1}
+
+    def __init__(self, nc: int, nt: int, dt: float, nu: float, order: int = 2, bc: str = "periodic", length: float = 1.0,
+                 ic_noise: float = 1e8, pin: float = 1e8, ic_obs: str = "all", device: int = 0, stream: int = 0):
+        if bc not in BurgersP1Tangent.BCS or ic_obs not in self.IC_OBS:
+            raise GmrfError(_cabi.ERR_BAD_SHAPE, f"BurgersLinePrior: bc {bc!r} {tuple(BurgersP1Tangent.BCS)}, ic_obs {ic_obs!r} "
+                                                 f"{tuple(self.IC_OBS)}")
+        self.nc, self.nt, self.dt, self.nu, self.ic_noise = int(nc), int(nt), float(dt), float(nu), float(ic_noise)
+        self.order, self.bc, self.length, self.pin, self.ic_obs = int(order), bc, float(length), float(pin), ic_obs
+        self.ns = self.order * self.nc + (1 if bc == "dirichlet" else 0)
+        self.n = self.ns * self.nt
+        self._h = C.c_void_p()
+        lib = _cabi.load()
+        _cabi.check(lib.gmrf_burgers_line_prior_create(device, C.c_void_p(stream), self.nc, self.nt, self.dt, self.nu, self.ic_noise,
+                                                       self.order, BurgersP1Tangent.BCS[bc], self.length, self.pin, self.IC_OBS[ic_obs],
+                                                       C.byref(self._h)))
+        nnz = C.c_int64(0)
+        _cabi.check(lib.gmrf_burgers_prior_pattern(self._h, C.byref(nnz), None, None, 0))
+        self.nnz = int(nnz.value)
+        cp, rv = np.empty(self.n + 1, dtype=np.int64), np.empty(self.nnz, dtype=np.int64)
+        _cabi.check(lib.gmrf_burgers_prior_pattern(self._h, None, _cabi.ptr(cp), _cabi.ptr(rv), 0))
+        self.pattern = sp.csc_matrix((np.ones(self.nnz), rv, cp), shape=(self.n, self.n))
 
 
 class EllipticP1Tangent:
@@ -823,7 +858,7 @@ class BurgersInitialConditionBatch:
         F = gn.finalize()                               # then sample_batch / marginal_var_batch
 
     `F` (reference order, factored once on `asm.pattern`), `asm` (built on `prior.pattern` and the tangent's pattern) and `prior`
-    must have been created on the same device with the same `stream` argument."""
+    (a `BurgersP1Prior` or a `BurgersLinePrior`, with the `BurgersP1Tangent` of the same line in `asm`) must have been created on the same device with the same `stream` argument."""
 
     def __init__(self, F: "TridiagonalCholeskyFactor", asm: PosteriorAssembler, prior: BurgersP1Prior):
         self.F, self.asm, self.prior = F, asm, prior              # (kept alive: the library holds their handles)

@@ -47,6 +47,7 @@
 #include "gauss_newton.hpp"
 #include "darcy_cond.hpp"
 #include "burgers_prior.hpp"
+#include "burgers_line_prior.hpp"
 
 using namespace gmrf;
 
@@ -4194,9 +4195,22 @@ gmrf_status gmrf_burgers_p1_tangent_batch(gmrf_burgers_p1* b, int64_t batch, con
 struct gmrf_burgers_prior : DevCtx {    // device -1: pattern only
     int64_t ns = 0, nt = 0, n = 0, nnz = 0;
     double dt = 0.0, nu = 0.0, ic_noise = 0.0;
+    bool general = false;               // gmrf_burgers_line_prior_create's: `line` states it, burgers_line_prior.hpp evaluates it
+    BurgersLinePriorArgs line{};
     DevBuf arena;                       // host arguments of the current call (Staging)
     DevBuf bulk;                        // [batch] means of a call that does not ask for them
 };
+
+// the pattern by its one statement: the P1 periodic prior's or the general line's
+static int64_t prior_colptr(const gmrf_burgers_prior* p, int64_t j) {
+    if (p->general) return burgers_line_prior_colptr(p->line, j / p->ns, j % p->ns);
+    return burgers_prior_colptr(p->ns, p->nt, j / p->ns, j % p->ns);
+}
+
+static void prior_entry(const gmrf_burgers_prior* p, int64_t e, int64_t* row, int64_t* col) {
+    if (p->general) burgers_line_prior_entry(p->line, e, row, col);
+    else burgers_prior_entry(p->ns, p->nt, e, row, col);
+}
 
 gmrf_status gmrf_burgers_prior_create(int32_t device, void* stream, int64_t ns, int64_t nt, double dt, double nu, double ic_noise,
                                       gmrf_burgers_prior** out) {
@@ -4207,6 +4221,36 @@ gmrf_status gmrf_burgers_prior_create(int32_t device, void* stream, int64_t ns, 
     gmrf_burgers_prior* p = guard.get();
     p->ns = ns; p->nt = nt; p->n = ns * nt; p->nnz = burgers_prior_nnz(ns, nt); p->dt = dt; p->nu = nu; p->ic_noise = ic_noise;
     GCHK(p->open(device, stream, hipStreamNonBlocking, "gmrf_burgers_prior_create"));
+    *out = guard.release();
+    return GMRF_OK;
+}
+
+gmrf_status gmrf_burgers_line_prior_create(int32_t device, void* stream, int64_t nc, int64_t nt, double dt, double nu, double ic_noise,
+                                           int32_t order, int32_t bc, double length, double pin, int32_t ic_obs, gmrf_burgers_prior** out) {
+    if (!out) return bad_shape("null pointer");
+    if (order != 1 && order != 2) return bad_shape("Burgers line prior: order must be 1 or 2");
+    if (bc != GMRF_BURGERS_PERIODIC && bc != GMRF_BURGERS_DIRICHLET) return bad_shape("Burgers line prior: bc must be GMRF_BURGERS_PERIODIC or GMRF_BURGERS_DIRICHLET");
+    if (ic_obs != GMRF_BURGERS_IC_ALL && ic_obs != GMRF_BURGERS_IC_VERTICES) return bad_shape("Burgers line prior: ic_obs must be GMRF_BURGERS_IC_ALL or GMRF_BURGERS_IC_VERTICES");
+    if (ic_obs == GMRF_BURGERS_IC_VERTICES && order != 2) return bad_shape("Burgers line prior: ic_obs = vertices needs order 2 (every dof of the P1 line is a vertex)");
+    if (!(length > 0.0) || !std::isfinite(length)) return bad_shape("Burgers line prior: length must be > 0");
+    if (!(nu > 0.0) || !std::isfinite(nu)) return bad_shape("Burgers line prior: nu must be > 0");
+    if (!(dt > 0.0) || !std::isfinite(dt)) return bad_shape("Burgers line prior: dt must be > 0");
+    if (!(pin >= 0.0) || !std::isfinite(pin)) return bad_shape("Burgers line prior: pin must be >= 0");
+    if (!(ic_noise >= 0.0) || !std::isfinite(ic_noise)) return bad_shape("Burgers line prior: ic_noise must be >= 0");
+    if (nt < 2 || nt > (1 << 20)) return bad_shape("Burgers line prior: nt must be >= 2 slices (and <= 2^20)");
+    if (nc > (1 << 23)) return bad_shape("Burgers line prior: nc must be <= 2^23 cells");
+    if (bc == GMRF_BURGERS_PERIODIC && order * nc < 4 * order + 1)
+        return bad_shape("Burgers line prior: the periodic line needs order * nc >= 4 * order + 1 dofs: fewer fold the offsets 0 .. +-2 order onto each other");
+    if (bc == GMRF_BURGERS_DIRICHLET && nc < 2) return bad_shape("Burgers line prior: the dirichlet line needs nc >= 2 cells");
+    std::unique_ptr<gmrf_burgers_prior, gmrf_status (*)(gmrf_burgers_prior*)> guard(new gmrf_burgers_prior(), gmrf_burgers_prior_destroy);
+    gmrf_burgers_prior* p = guard.get();
+    BurgersLinePriorArgs& a = p->line;
+    a.nc = nc; a.nt = nt; a.order = order; a.periodic = bc == GMRF_BURGERS_PERIODIC ? 1 : 0; a.vertices = ic_obs == GMRF_BURGERS_IC_VERTICES ? 1 : 0;
+    a.ns = order * nc + (a.periodic ? 0 : 1);
+    a.dt = dt; a.nu = nu; a.ic_noise = ic_noise; a.h = length / (double)nc; a.pin = a.periodic ? 0.0 : pin;
+    p->general = true;
+    p->ns = a.ns; p->nt = nt; p->n = a.ns * nt; p->nnz = burgers_line_prior_nnz(a); p->dt = dt; p->nu = nu; p->ic_noise = ic_noise;
+    GCHK(p->open(device, stream, hipStreamNonBlocking, "gmrf_burgers_line_prior_create"));
     *out = guard.release();
     return GMRF_OK;
 }
@@ -4225,13 +4269,13 @@ gmrf_status gmrf_burgers_prior_pattern(const gmrf_burgers_prior* p, int64_t* nnz
     if (index_base != 0 && index_base != 1) return bad_shape("index_base must be 0 or 1");
     if (nnz_out) *nnz_out = p->nnz;
     if (colptr) {
-        for (int64_t j = 0; j < p->n; ++j) colptr[j] = burgers_prior_colptr(p->ns, p->nt, j / p->ns, j % p->ns) + index_base;
+        for (int64_t j = 0; j < p->n; ++j) colptr[j] = prior_colptr(p, j) + index_base;
         colptr[p->n] = p->nnz + index_base;
     }
     if (rowval)
         for (int64_t e = 0; e < p->nnz; ++e) {
             int64_t row, col;
-            burgers_prior_entry(p->ns, p->nt, e, &row, &col);
+            prior_entry(p, e, &row, &col);
             rowval[e] = row + index_base;
         }
     return GMRF_OK;
@@ -4246,6 +4290,18 @@ static BurgersPriorArgs prior_args(const gmrf_burgers_prior* p) {
 // d_q / d_qx: nullptr = not wanted
 static gmrf_status launch_prior_batch(const gmrf_burgers_prior* p, hipStream_t st, int64_t batch, const double* d_ic, double* d_bulk,
                                       double* d_q, double* d_qx) {
+    if (p->general) {
+        const BurgersLinePriorArgs& l = p->line;
+        hipLaunchKernelGGL(burgers_line_bulk_batch, dim3(1, (unsigned)batch), dim3(256), 0, st, l, d_ic, d_bulk);
+        if (d_q)
+            hipLaunchKernelGGL(burgers_line_prior_values_batch, dim3((unsigned)((p->nnz + 255) / 256), (unsigned)batch), dim3(256), 0, st, l,
+                               d_bulk, p->nnz, d_q);
+        if (d_qx)
+            hipLaunchKernelGGL(burgers_line_prior_rhs_batch, dim3((unsigned)((p->n + 255) / 256), (unsigned)batch), dim3(256), 0, st, l, d_bulk,
+                               d_ic, d_qx);
+        HIPCHK(hipGetLastError());
+        return GMRF_OK;
+    }
     const BurgersPriorArgs a = prior_args(p);
     hipLaunchKernelGGL(burgers_bulk_batch, dim3(1, (unsigned)batch), dim3(256), 0, st, d_ic, p->ns, d_bulk);
     if (d_q)
@@ -5071,12 +5127,12 @@ gmrf_status gmrf_bic_create(gmrf_handle* h, gmrf_assembler* as, gmrf_burgers_pri
     // the same sizes are not yet the same pattern: entry by entry against the prior's statement of it
     if (as->q_ptr.empty()) return bad_shape("the Burgers initial-condition driver needs n < 2^31");
     for (int64_t j = 0; j <= as->n; ++j) {
-        const int64_t at = j < as->n ? burgers_prior_colptr(prior->ns, prior->nt, j / prior->ns, j % prior->ns) : prior->nnz;
+        const int64_t at = j < as->n ? prior_colptr(prior, j) : prior->nnz;
         if (as->q_ptr[(size_t)j] != at) return bad_shape("the assembler's Q is not the Burgers prior's pattern");
     }
     for (int64_t e = 0; e < prior->nnz; ++e) {
         int64_t row, col;
-        burgers_prior_entry(prior->ns, prior->nt, e, &row, &col);
+        prior_entry(prior, e, &row, &col);
         if (as->q_row[(size_t)e] != row) return bad_shape("the assembler's Q is not the Burgers prior's pattern");
     }
     *out = new gmrf_bic(tmp);

@@ -471,6 +471,99 @@ def burgers_prior_from_bulk(ns: int, nt: int, bulk: float, ic, ic_noise: float =
     return Qp, Aic, np.asarray(rhs)
 
 
+def line_operators(nc: int, order: int = 1, bc: str = "periodic", length: float = 1.0):
+    """The line of `length` in nc cells, P1 or quadratic, with its dofs numbered by position: consistent mass M, lumped mass (row
+    sums), stiffness S and the consistent advection matrix Adv[i][j] = int phi_i phi_j' (all CSR).  bc = "periodic": order nc dofs,
+    the last cell wraps around to dof 0 -- `p1_periodic_line(nc)` at order 1 and length 1; bc = "dirichlet": order nc + 1 dofs,
+    nothing prescribed -- M, lumped and S of `dirichlet_line(nc, order, length)`.  Quadratic cell e has the dofs (2e, 2e+2, 2e+1) =
+    (left, right, middle); its advection matrix in that order is 1/6 [-3 -1 4; 1 3 -4; -4 4 0] (P1: 1/2 [-1 1; -1 1]); the entries
+    of Adv that add up to zero (the diagonal of an inner vertex) are not stored.  The lumped mass of the periodic P1 line is stated
+    as `p1_periodic_line` states it, h: the floating-point row sum 4h/6 + h/6 + h/6 is an ulp off at most sizes."""
+    if order not in (1, 2) or bc not in ("periodic", "dirichlet") or nc < 2 or not length > 0.0:
+        raise ValueError("order 1 or 2, bc 'periodic' or 'dirichlet', nc >= 2, length > 0")
+    h = length / nc
+    if order == 1:
+        dofs = np.stack([np.arange(nc), np.arange(nc) + 1], axis=1)
+        Me = h / 6.0 * np.array([[2.0, 1.0], [1.0, 2.0]])
+        Se = 1.0 / h * np.array([[1.0, -1.0], [-1.0, 1.0]])
+        Ae = 0.5 * np.array([[-1.0, 1.0], [-1.0, 1.0]])
+    else:
+        dofs = np.stack([2 * np.arange(nc), 2 * np.arange(nc) + 2, 2 * np.arange(nc) + 1], axis=1)
+        Me = h / 30.0 * np.array([[4.0, -1.0, 2.0], [-1.0, 4.0, 2.0], [2.0, 2.0, 16.0]])
+        Se = 1.0 / (3.0 * h) * np.array([[7.0, 1.0, -8.0], [1.0, 7.0, -8.0], [-8.0, -8.0, 16.0]])
+        Ae = np.array([[-3.0, -1.0, 4.0], [1.0, 3.0, -4.0], [-4.0, 4.0, 0.0]]) / 6.0
+    ns, nb = order * nc + (1 if bc == "dirichlet" else 0), order + 1
+    dofs = dofs % ns                                     # (the periodic line's last cell ends at dof 0)
+    I = np.repeat(dofs, nb, axis=1).ravel()
+    J = np.tile(dofs, (1, nb)).ravel()
+    M, S, Adv = (sp.coo_matrix((np.tile(E.ravel(), nc), (I, J)), shape=(ns, ns)).tocsr() for E in (Me, Se, Ae))
+    Adv.eliminate_zeros()
+    lumped = np.full(ns, h) if (order == 1 and bc == "periodic") else np.asarray(M.sum(axis=1)).ravel()
+    return M, lumped, S, Adv
+
+
+def burgers_line_ic_observed(ns: int, order: int, bc: str, ic_obs: str = "all") -> np.ndarray:
+    """The dofs of slice 0 at which the initial condition is observed: "all" = every dof that is not pinned (the dirichlet line's
+    dofs 0 and ns-1 are), "vertices" (order 2) = the even ones of them, a data grid with one point per cell."""
+    if ic_obs not in ("all", "vertices") or (ic_obs == "vertices" and order != 2):
+        raise ValueError("ic_obs 'all' or, at order 2, 'vertices'")
+    obs = np.arange(ns) if bc == "periodic" else np.arange(1, ns - 1)
+    return obs[obs % 2 == 0] if ic_obs == "vertices" else obs
+
+
+def burgers_line_prior_from_bulk(nc: int, nt: int, dt: float, nu: float, bulk: float, ic, order: int = 2, bc: str = "periodic",
+                                 length: float = 1.0, ic_noise: float = 1e8, pin: float = 1e8, ic_obs: str = "all"):
+    """`burgers_prior_from_bulk` on any line of `line_operators` -- the reference's periodic quadratic line
+    (scripts/burgers/solve_burgers_gmrf-fem.jl:71-72, form_prior :86-107) and the interval of _research/burgers_chen24.jl, where it is
+    the construction of `burgers_chen24_batch`: returns (Q_prior, A_ic, rhs) with
+        c = 1 / nu, gamma = -c bulk, tau = 0.1 sqrt(c), kappa^2 = 12 nc, Ml = diag(lumped), K = kappa^2 Ml + S, Q0 = K Ml^-1 K,
+        G = Ml + dt (nu c S + gamma Adv), W = diag(1 / (dt tau^2) / lumped),
+        block (t, t) = G'WG (t > 0) or Q0 (t = 0), + Ml W Ml for t < nt-1;    block (t, t-1) = -G'W Ml,
+    on the dirichlet line `pin` (the reference's prescribed_noise = 1e-8) added on the diagonal of dofs 0 and ns-1 of every slice,
+    A_ic the restriction to the observed dofs of slice 0 (`burgers_line_ic_observed`) and
+        rhs = Q_prior(without the pins) (bulk 1) + ic_noise A_ic' ic[observed],
+    ic being the whole slice (ns,).  `bulk` is meant to be mean(ic[observed]); the device prior (`BurgersLinePrior`) is tested
+    against this function at its own mean.  (order 1, periodic, length 1, nu = 0.01 / pi, dt = 1 / (nt-1)) is
+    `burgers_prior_from_bulk`, bit for bit."""
+    M, lumped, S, Adv = line_operators(nc, order, bc, length)
+    ns = lumped.shape[0]
+    ic = np.asarray(ic, dtype=np.float64)
+    bulk = float(bulk)
+    c = 1.0 / nu
+    gamma = -c * bulk
+    tau = 0.1 * math.sqrt(c)
+    kappa = math.sqrt(8.0 * 1.5) / math.sqrt(1.0 / nc)
+    Ml = sp.diags(lumped)
+    K = (kappa ** 2) * Ml + S
+    Q0 = (K @ sp.diags(1.0 / lumped) @ K).tocsr()
+    Gm = (Ml + dt * (nu * c * S + gamma * Adv)).tocsr()
+    W = sp.diags(np.full(ns, 1.0 / (dt * tau * tau)) / lumped)
+    GWG = (Gm.T @ W @ Gm).tocsr()
+    MWM = (Ml.T @ W @ Ml).tocsr()
+    GWM = (Gm.T @ W @ Ml).tocsr()
+    pins = np.zeros(ns)
+    if bc == "dirichlet":
+        pins[0] = pins[-1] = pin
+
+    def assemble(with_pins):
+        blocks = [[None] * nt for _ in range(nt)]
+        for t in range(nt):
+            d = GWG if t > 0 else Q0
+            if t < nt - 1:
+                d = d + MWM
+            blocks[t][t] = d + sp.diags(pins) if with_pins else d
+            if t > 0:
+                blocks[t][t - 1] = -GWM
+                blocks[t - 1][t] = -GWM.T
+        return sp.bmat(blocks, format="csr")
+    free = assemble(False)
+    Qp = assemble(True) if bc == "dirichlet" else free
+    obs = burgers_line_ic_observed(ns, order, bc, ic_obs)
+    Aic = sp.csr_matrix((np.ones(obs.size), (np.arange(obs.size), obs)), shape=(obs.size, ns * nt))
+    rhs = free @ np.full(ns * nt, bulk) + ic_noise * (Aic.T @ ic[obs])
+    return Qp, Aic, np.asarray(rhs)
+
+
 def burgers(ns: int, nt: int, ic_noise: float = 1e8, fem_noise: float = 1e12, ic=None) -> Workload:
     """1-D viscous Burgers space-time GMRF in the time-major ordering (t-1)*ns + s:
     Q = Q_prior + ic_noise A_ic^T A_ic + fem_noise J^T J, N = nt blocks of size ns.

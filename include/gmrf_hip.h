@@ -554,8 +554,8 @@ gmrf_status gmrf_burgers_p1_tangent(gmrf_burgers_p1* b, const double* w, double*
  * with A_ic the restriction to the first slice, so that Q_ic^-1 Qx_prior is the mean of the prior conditioned on the initial
  * condition.  The pattern is structural: symmetric CSC, both triangles, rows ascending, nt blocks of ns; diagonal blocks hold the
  * periodic offsets 0, +-1, +-2, the blocks beside them 0, +-1; nnz = (11 nt - 6) ns; fixed by (ns, nt), an entry whose value is
- * 0.0 is stored.  ns < 5 (the offsets fold onto each other), nt < 2, nu <= 0: GMRF_ERR_BAD_SHAPE.  The quadratic line of
- * gmrf_burgers_p2_create has no prior here.
+ * 0.0 is stored.  ns < 5 (the offsets fold onto each other), nt < 2, nu <= 0: GMRF_ERR_BAD_SHAPE.  The other lines of
+ * gmrf_burgers_line_create have their prior in gmrf_burgers_line_prior_create below.
  * gmrf_burgers_prior_values_batch: ic [batch][ns] -> bulk_out [batch], q_values_out [batch][nnz] in the order of _pattern (the
  * q_nzval of gmrf_gn_run at q_stride = nnz), qx_out [batch][nt ns]; each output may be NULL, every pointer host or device memory;
  * batch in [1, 4096].  The means are fixed-shape sums without atomics, the values are bitwise symmetric, and problem p's bits do
@@ -568,6 +568,30 @@ gmrf_status gmrf_burgers_prior_pattern(const gmrf_burgers_prior* p, int64_t* nnz
                                        int32_t index_base);
 gmrf_status gmrf_burgers_prior_values_batch(gmrf_burgers_prior* p, int64_t batch, const double* ic, double* bulk_out,
                                             double* q_values_out, double* qx_out);
+/* The same prior on every line gmrf_burgers_line_create serves: the periodic QUADRATIC line that form_prior runs on in
+ * /root/reference/scripts/burgers/solve_burgers_gmrf-fem.jl:71-72, :86-107 (element_order = 2), and the interval with pinned ends
+ * of _research/burgers_chen24.jl:79-108 (prescribed_noise = 1e-8, i.e. pin = 1e8), with this project's restatement of the prior
+ * (`workloads.burgers_line_prior_from_bulk`): nc cells of length / nc, ns = order nc (periodic) or order nc + 1 (dirichlet) dofs
+ * numbered by position, l the lumped mass (row sums), S the stiffness, Adv[i][j] = int phi_i phi_j', c = 1 / nu, gamma = -c bulk,
+ * tau = 0.1 sqrt(c), kappa^2 = 12 nc:
+ *     K = kappa^2 diag(l) + S,  G = diag(l) + dt (nu c S + gamma Adv),  W = diag((1 / (dt tau^2)) / l)
+ *     block (t, t) = G'WG (t > 0) or K diag(1 / l) K (t = 0), + diag(l) W diag(l) for t < nt-1;   block (t, t-1) = -G'W diag(l)
+ *     dirichlet: + pin on the diagonal of dofs 0 and ns-1 of every slice (pin is ignored on the periodic line)
+ *     Q_ic = Q_prior + ic_noise A_ic' A_ic,   Qx_prior = Q_prior(without the pins) (bulk 1) + ic_noise A_ic' ic
+ * A_ic observes slice 0 at GMRF_BURGERS_IC_ALL, every dof that is not pinned, or GMRF_BURGERS_IC_VERTICES (order 2), the even ones
+ * of them -- a data grid of one point per cell; bulk is the mean of ic over the observed dofs (ic is [ns] either way).  The pattern
+ * is structural, symmetric CSC, both triangles, rows ascending: offsets 0 .. +-2 order in the diagonal blocks and 0 .. +-order
+ * beside them, wrapped (periodic) or clipped to the slice (dirichlet); an entry whose value is 0.0 is stored;
+ * nnz = ((4o+1) nt + 2 (2o+1) (nt-1)) ns (periodic), nt ((4o+1) ns - 2o (2o+1)) + 2 (nt-1) ((2o+1) ns - o (o+1)) (dirichlet).
+ * The handle is a gmrf_burgers_prior: _pattern, _values_batch (same outputs, pointer kinds and guarantees), _destroy and
+ * gmrf_bic_create / _run serve it.  (order 1, periodic, length 1, all) is the prior of gmrf_burgers_prior_create evaluated by
+ * other kernels: the same pattern and bulk, values equal to rounding.  GMRF_ERR_BAD_SHAPE, the argument named: an unknown order, bc
+ * or ic_obs, vertices at order 1, length <= 0, nu <= 0, dt <= 0, pin < 0, nt < 2, periodic with order nc < 4 order + 1 (the
+ * offsets fold), dirichlet with nc < 2.  device -1: pattern only. */
+typedef enum { GMRF_BURGERS_IC_ALL = 0, GMRF_BURGERS_IC_VERTICES = 1 } gmrf_burgers_ic_obs;
+gmrf_status gmrf_burgers_line_prior_create(int32_t device, void* stream, int64_t nc, int64_t nt, double dt, double nu,
+                                           double ic_noise, int32_t order, int32_t bc, double length, double pin, int32_t ic_obs,
+                                           gmrf_burgers_prior** out);
 
 /* A batch of Gauss-Newton loops on one mesh (the Burgers data-set loop, scripts/burgers/solve_burgers_gmrf-fem.jl:154-233 with the
  * loop body of scripts/solve_burger.jl:143-180).  All arrays are problem-major ([batch][...]), host or device pointers like the

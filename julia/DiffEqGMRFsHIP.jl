@@ -31,7 +31,7 @@ using SparseArrays, LinearAlgebra
 
 export TridiagonalCholeskyFactor, tridiagonal_cholesky, forward_solve, backward_solve, ldiv, PosteriorAssembler, GmrfCsr,
        GmrfComm, DarcyP1Assembler, BurgersP1Tangent, EllipticP1Tangent, elliptic_load!, GaussNewtonBatch, gauss_newton_batch!, DarcyConditioningBatch,
-       BurgersP1Prior, prior_values_batch!, BurgersInitialConditionBatch, initial_condition_batch, solution_errors_batch,
+       BurgersP1Prior, BurgersLinePrior, prior_values_batch!, BurgersInitialConditionBatch, initial_condition_batch, solution_errors_batch,
        condition_on_observations_batch, assemble_batch!
 
 const libgmrf = get(ENV, "LIBGMRF_HIP", joinpath(@__DIR__, "..", "diffeqgmrfs.jl_amd", "csrc", "libgmrf_hip.so"))
@@ -765,7 +765,7 @@ end
 
 # The prior of the Burgers space-time GMRF (form_prior, scripts/burgers/solve_burgers_gmrf-fem.jl:86-107) on the periodic P1 line of
 # BurgersP1Tangent, with the initial condition conditioned in (:161): every problem brings its own values through bulk = mean(ic).
-# P1 only: the quadratic line has no prior here.
+# The other lines of BurgersP1Tangent have theirs in `BurgersLinePrior` below, behind the same struct.
 mutable struct BurgersP1Prior
     handle::Ptr{Cvoid}
     pattern::SparseMatrixCSC{Float64,Int}     # Q_ic's structural pattern (symmetric, values 1.0): the `nzval` order of the values
@@ -779,6 +779,31 @@ function BurgersP1Prior(ns::Integer, nt::Integer, dt::Real, nu::Real; ic_noise::
                 device, stream, ns, nt, Float64(dt), Float64(nu), Float64(ic_noise), h))
     nnz_out = Ref{Int64}(0)
     check(ccall((:gmrf_burgers_prior_pattern, libgmrf), Int32, (Ptr{Cvoid}, Ref{Int64}, Ptr{Int64}, Ptr{Int64}, Int32), h[], nnz_out, C_NULL, C_NULL, 1))
+    n = ns * nt
+    colptr = Vector{Int64}(undef, n + 1); rowval = Vector{Int64}(undef, nnz_out[])
+    check(ccall((:gmrf_burgers_prior_pattern, libgmrf), Int32, (Ptr{Cvoid}, Ref{Int64}, Ptr{Int64}, Ptr{Int64}, Int32), h[], nnz_out, colptr, rowval, 1))
+    p = BurgersP1Prior(h[], SparseMatrixCSC(n, n, colptr, rowval, ones(nnz_out[])), ns)
+    finalizer(x -> ccall((:gmrf_burgers_prior_destroy, libgmrf), Int32, (Ptr{Cvoid},), x.handle), p)
+    return p
+end
+
+# The same prior on every line BurgersP1Tangent serves (gmrf_burgers_line_prior_create): nc cells of length / nc, order 1 or 2,
+# bc = :periodic (ns = order nc) or :dirichlet (ns = order nc + 1, `pin` on the diagonal of dofs 1 and ns of every slice) -- the
+# periodic quadratic line of scripts/burgers/solve_burgers_gmrf-fem.jl:71-72 and the interval of _research/burgers_chen24.jl.
+# ic_obs = :all observes every dof of the first slice that is not pinned, :vertices (order 2) the odd ones (1-based) of them.
+# Returns a BurgersP1Prior: prior_values_batch! and BurgersInitialConditionBatch serve it.
+function BurgersLinePrior(nc::Integer, nt::Integer, dt::Real, nu::Real; order::Integer = 2, bc::Symbol = :periodic, length::Real = 1.0,
+                          ic_noise::Real = 1e8, pin::Real = 1e8, ic_obs::Symbol = :all, device::Integer = 0, stream::Ptr{Cvoid} = C_NULL)
+    bcs = Dict(:periodic => 0, :dirichlet => 1); obs = Dict(:all => 0, :vertices => 1)
+    (haskey(bcs, bc) && haskey(obs, ic_obs)) || throw(ArgumentError("bc :periodic or :dirichlet, ic_obs :all or :vertices"))
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:gmrf_burgers_line_prior_create, libgmrf), Int32,
+                (Int32, Ptr{Cvoid}, Int64, Int64, Float64, Float64, Float64, Int32, Int32, Float64, Float64, Int32, Ref{Ptr{Cvoid}}),
+                device, stream, nc, nt, Float64(dt), Float64(nu), Float64(ic_noise), Int32(order), Int32(bcs[bc]), Float64(length),
+                Float64(pin), Int32(obs[ic_obs]), h))
+    nnz_out = Ref{Int64}(0)
+    check(ccall((:gmrf_burgers_prior_pattern, libgmrf), Int32, (Ptr{Cvoid}, Ref{Int64}, Ptr{Int64}, Ptr{Int64}, Int32), h[], nnz_out, C_NULL, C_NULL, 1))
+    ns = order * nc + (bc == :dirichlet ? 1 : 0)
     n = ns * nt
     colptr = Vector{Int64}(undef, n + 1); rowval = Vector{Int64}(undef, nnz_out[])
     check(ccall((:gmrf_burgers_prior_pattern, libgmrf), Int32, (Ptr{Cvoid}, Ref{Int64}, Ptr{Int64}, Ptr{Int64}, Int32), h[], nnz_out, colptr, rowval, 1))

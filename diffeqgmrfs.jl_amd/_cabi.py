@@ -36,7 +36,7 @@ EXPORTS = [
     "gmrf_bt_packed_size", "gmrf_bt_pack_blocks_async", "gmrf_bt_unpack_blocks_async",
     "gmrf_csr_create", "gmrf_csr_destroy", "gmrf_spmm", "gmrf_spmm_rows", "gmrf_spmm_async", "gmrf_spmm_rows_async",
     "gmrf_darcy_p1_create", "gmrf_darcy_p2_create", "gmrf_darcy_p1_destroy", "gmrf_darcy_p1_pattern", "gmrf_darcy_p1_assemble",
-    "gmrf_burgers_p1_create", "gmrf_burgers_p2_create", "gmrf_burgers_line_create", "gmrf_burgers_p1_destroy", "gmrf_burgers_p1_pattern", "gmrf_burgers_p1_tangent",
+    "gmrf_burgers_p1_create", "gmrf_burgers_p2_create", "gmrf_burgers_line_create", "gmrf_burgers_colloc_create", "gmrf_burgers_p1_destroy", "gmrf_burgers_p1_pattern", "gmrf_burgers_p1_tangent",
     "gmrf_shallow_water_p1_create", "gmrf_shallow_water_p1_destroy", "gmrf_shallow_water_p1_pattern", "gmrf_shallow_water_p1_qpoints",
     "gmrf_shallow_water_p1_assemble", "gmrf_shallow_water_p1_operators",
     "gmrf_assemble_create", "gmrf_assemble_destroy", "gmrf_assemble_pattern", "gmrf_assemble_precision", "gmrf_assemble_rhs",
@@ -175,6 +175,7 @@ def load() -> C.CDLL:
         "gmrf_burgers_p1_create": [i32, vp, i64, i64, dbl, dbl, P(vp)],
         "gmrf_burgers_p2_create": [i32, vp, i64, i64, dbl, dbl, P(vp)],
         "gmrf_burgers_line_create": [i32, vp, i64, i64, dbl, dbl, i32, i32, i32, dbl, P(vp)],
+        "gmrf_burgers_colloc_create": [i32, vp, i64, i64, dbl, dbl, dbl, i64, vp, P(vp)],
         "gmrf_burgers_p1_destroy": [vp],
         "gmrf_burgers_p1_pattern": [vp, P(i64), vp, vp, i32],
         "gmrf_burgers_p1_tangent": [vp, vp, vp, vp],

@@ -382,6 +382,11 @@ class BurgersP1Tangent:
         lib = _cabi.load()
         _cabi.check(lib.gmrf_burgers_line_create(device, C.c_void_p(stream), self.cells, nt, float(dt), float(nu), self.order,
                                                  self.SCHEMES[scheme], self.BCS[bc], self.length, C.byref(self._h)))
+        self._read_pattern()
+
+    def _read_pattern(self):
+        """nnz and `pattern` of the created handle (rows and n are set)."""
+        lib = _cabi.load()
         nnz = C.c_int64(0)
         _cabi.check(lib.gmrf_burgers_p1_pattern(self._h, C.byref(nnz), None, None, 0))
         self.nnz = int(nnz.value)
@@ -429,6 +434,31 @@ class BurgersP1Tangent:
         vals, f = PosteriorAssembler._like2(wv, (B, self.nnz)), PosteriorAssembler._like2(wv, (B, self.rows))
         _cabi.check(_cabi.load().gmrf_burgers_p1_tangent_batch(self._h, B, _cabi.ptr(wv), _cabi.ptr(vals), _cabi.ptr(f)))
         return vals, f
+
+
+class BurgersCollocationTangent(BurgersP1Tangent):
+    """Residual and tangent of the implicit-Euler Burgers step evaluated at collocation points on the periodic quadratic line, on
+    the device: `f_and_J` of the reference's scripts/burgers/solve_burgers_gmrf-collocation.jl:186-192 with `J_static` (:183) and
+    the operators `A_coll`, du/dx, d2u/dx2 of :167-169.  nc cells of length / nc, ns = 2 nc dofs numbered by position; `points`
+    are npts coordinates in [0, length), in any order.  Row (t-1) npts + c (t = 1 .. nt-1) is point c of the step t-1 -> t:
+        f = u - u_prev + dt u u_x - dt nu u_xx,    J[., t-1] = -a,    J[., t] = a + dt (u_x a + u d) - dt nu s
+    with a, d, s the values and derivatives of the three shape functions of the point's cell.  `pattern` is the CSR matrix (values 1,
+    (nt-1) npts x nt ns, 6 entries per row, zeros stored) whose `.data` order `tangent()` / `tangent_batch()` fill.  A
+    `BurgersP1Tangent` to `PosteriorAssembler` and `GaussNewtonBatch`.  device = -1: pattern only (no GPU needed).
+
+    Gauss-Newton without damping on this residual -- the reference's algorithm -- does not converge on coarse meshes at the
+    nu = 0.01 / pi and T = 1 of the FEM loop's tests."""
+
+    def __init__(self, nc: int, nt: int, dt: float, nu: float, points, length: float = 1.0, device: int = 0, stream: int = 0):
+        self.cells, self.nt, self.dt, self.nu, self.length = int(nc), int(nt), float(dt), float(nu), float(length)
+        self.ns, self.order, self.scheme, self.bc = 2 * self.cells, 2, "collocation", "periodic"
+        self.points = np.ascontiguousarray(points, dtype=np.float64).reshape(-1).copy()
+        self.npts = int(self.points.shape[0])
+        self.rows, self.n = (self.nt - 1) * self.npts, self.nt * self.ns
+        self._h = C.c_void_p()
+        _cabi.check(_cabi.load().gmrf_burgers_colloc_create(device, C.c_void_p(stream), self.cells, self.nt, self.dt, self.nu,
+                                                            self.length, self.npts, _cabi.ptr(self.points), C.byref(self._h)))
+        self._read_pattern()
 
 
 class BurgersP1Prior:
@@ -711,7 +741,10 @@ class GaussNewtonBatch:
     decrement lives in a package that is not available).
 
     With a `BurgersP1Tangent(..., scheme="cn", bc="dirichlet")` it is the loop of _research/burgers_chen24.jl:139-152 on the
-    problems of `workloads.burgers_chen24_batch` (zero observations; the same stop rule)."""
+    problems of `workloads.burgers_chen24_batch` (zero observations; the same stop rule).
+
+    With a `BurgersCollocationTangent` it is the loop of scripts/burgers/solve_burgers_gmrf-collocation.jl:236-246 on the problems
+    of `workloads.burgers_collocation_batch` (zero observations, noise = 1e8; the same stop rule)."""
 
     def __init__(self, F: "TridiagonalCholeskyFactor", asm: PosteriorAssembler, tangent: "BurgersP1Tangent | EllipticP1Tangent"):
         self.F, self.asm, self.tangent = F, asm, tangent          # (kept alive: the library holds their handles)

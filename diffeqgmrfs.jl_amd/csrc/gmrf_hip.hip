@@ -31,6 +31,7 @@
 #include "assemble.hpp"
 #include "fem_assemble.hpp"
 #include "burgers_line.hpp"
+#include "burgers_colloc.hpp"
 #include "gemm_f64.hpp"
 #include "gemm_f64_dma.hpp"
 #include "microbench.hpp"
@@ -4052,6 +4053,10 @@ struct gmrf_burgers_p1 : DevCtx {       // device -1: pattern only
     double dt = 0.0, nu = 0.0, h = 0.0; // h: cell length
     std::vector<int64_t> rowptr;        // 0-based row pointer of J
     int64_t* d_rowptr = nullptr;        // dirichlet only: the periodic rows have a closed form
+    int64_t npts = 0;                   // GMRF_BURGERS_COLLOCATION (gmrf_burgers_colloc_create): the points of a slice, their
+    std::vector<int32_t> cell;          // cells, and the device table of burgers_colloc.hpp: cells, then a and d as [3][npts]
+    int32_t* d_cell = nullptr;
+    double* d_shape = nullptr;          // a at 0, d at 3 npts
     DevBuf arena;                       // host arguments of the current call (Staging)
 };
 
@@ -4106,10 +4111,53 @@ gmrf_status gmrf_burgers_p2_create(int32_t device, void* stream, int64_t ns, int
     return gmrf_burgers_line_create(device, stream, ns / 2, nt, dt, nu, 2, GMRF_BURGERS_EULER, GMRF_BURGERS_PERIODIC, 1.0, out);
 }
 
+// The collocation tangent of burgers_colloc.hpp on the periodic quadratic line.  The per-point table is computed here, once, in
+// double precision; the pattern reads the same cells.
+gmrf_status gmrf_burgers_colloc_create(int32_t device, void* stream, int64_t nc, int64_t nt, double dt, double nu, double length,
+                                       int64_t npts, const double* points, gmrf_burgers_p1** out) {
+    if (!out || !points) return bad_shape("null pointer");
+    if (nc < 3 || nt < 2 || nc > (1 << 23) || nt > (1 << 20) || npts < 1 || npts > (1 << 24) || !(dt > 0.0) || !(nu >= 0.0) ||
+        !(length > 0.0) || !std::isfinite(length) || ((nt - 1) * npts + 255) / 256 > 0x7fffffffLL)
+        return bad_shape("bad Burgers collocation mesh (>= 3 cells, nt >= 2 slices, >= 1 point, dt > 0, nu >= 0, length > 0)");
+    const double h = length / (double)nc;
+    for (int64_t c = 0; c < npts; ++c)
+        if (!std::isfinite(points[c]) || points[c] < 0.0 || !(points[c] < length)) {
+            g_last_error = "collocation point " + std::to_string(c) + " = " + std::to_string(points[c]) + " is not in [0, length = " +
+                           std::to_string(length) + ")";
+            return GMRF_ERR_BAD_SHAPE;
+        }
+    std::unique_ptr<gmrf_burgers_p1, gmrf_status (*)(gmrf_burgers_p1*)> guard(new gmrf_burgers_p1(), gmrf_burgers_p1_destroy);
+    gmrf_burgers_p1* b = guard.get();
+    b->ns = 2 * nc; b->nt = nt; b->npts = npts; b->rows = (nt - 1) * npts; b->nnz = 6 * b->rows; b->dt = dt; b->nu = nu; b->order = 2;
+    b->scheme = GMRF_BURGERS_COLLOCATION; b->bc = GMRF_BURGERS_PERIODIC; b->h = h;
+    b->cell.resize((size_t)npts);
+    std::vector<double> shape((size_t)(6 * npts));
+    for (int64_t c = 0; c < npts; ++c) {
+        const int64_t e = std::min((int64_t)std::floor(points[c] / h), nc - 1);
+        const double xi = 2.0 * (points[c] - (double)e * h) / h - 1.0;
+        const double a[3] = {0.5 * xi * (xi - 1.0), 0.5 * xi * (xi + 1.0), 1.0 - xi * xi};
+        const double d[3] = {(xi - 0.5) * (2.0 / h), (xi + 0.5) * (2.0 / h), (-2.0 * xi) * (2.0 / h)};
+        b->cell[(size_t)c] = (int32_t)e;
+        for (int k = 0; k < 3; ++k) { shape[(size_t)(k * npts + c)] = a[k]; shape[(size_t)((3 + k) * npts + c)] = d[k]; }
+    }
+    b->rowptr.resize((size_t)b->rows + 1);
+    for (int64_t r = 0; r <= b->rows; ++r) b->rowptr[(size_t)r] = 6 * r;
+    GCHK(b->open(device, stream, hipStreamNonBlocking, "gmrf_burgers_colloc_create"));
+    if (b->device >= 0) {
+        HIPCHK(hipMalloc(&b->d_cell, sizeof(int32_t) * npts));
+        HIPCHK(hipMalloc(&b->d_shape, sizeof(double) * 6 * npts));
+        HIPCHK(hipMemcpyAsync(b->d_cell, b->cell.data(), sizeof(int32_t) * npts, hipMemcpyHostToDevice, b->stream));
+        HIPCHK(hipMemcpyAsync(b->d_shape, shape.data(), sizeof(double) * 6 * npts, hipMemcpyHostToDevice, b->stream));
+        HIPCHK(hipStreamSynchronize(b->stream));
+    }
+    *out = guard.release();
+    return GMRF_OK;
+}
+
 gmrf_status gmrf_burgers_p1_destroy(gmrf_burgers_p1* b) {
     if (!b) return GMRF_OK;
     b->close();
-    if (b->has_device()) { free_dev(b->d_rowptr); b->arena.release(); }
+    if (b->has_device()) { free_dev(b->d_rowptr); free_dev(b->d_cell); free_dev(b->d_shape); b->arena.release(); }
     delete b;
     return GMRF_OK;
 }
@@ -4121,7 +4169,16 @@ gmrf_status gmrf_burgers_p1_pattern(const gmrf_burgers_p1* b, int64_t* nnz_out, 
     if (!b) return bad_shape("null handle");
     if (nnz_out) *nnz_out = b->nnz;
     if (rowptr) for (int64_t r = 0; r <= b->rows; ++r) rowptr[r] = b->rowptr[(size_t)r] + index_base;
-    if (colidx)
+    if (colidx && b->scheme == GMRF_BURGERS_COLLOCATION) {
+        // row (t, c): the three dofs of the point's cell, ascending -- the wrap cell's right dof is column 0
+        for (int64_t r = 0; r < b->rows; ++r) {
+            const int64_t t = r / b->npts + 1, e = b->cell[(size_t)(r % b->npts)];
+            const bool wrap = 2 * e + 2 == b->ns;
+            const int64_t c[3] = {wrap ? 0 : 2 * e, wrap ? 2 * e : 2 * e + 1, wrap ? 2 * e + 1 : 2 * e + 2};
+            int64_t* out = colidx + 6 * r;
+            for (int k = 0; k < 3; ++k) { out[k] = (t - 1) * b->ns + c[k] + index_base; out[3 + k] = t * b->ns + c[k] + index_base; }
+        }
+    } else if (colidx)
         for (int64_t r = 0; r < b->rows; ++r) {
             const int64_t t = r / b->ns + 1;
             int64_t c[5];
@@ -4146,7 +4203,14 @@ static gmrf_status launch_tangent_batch(const gmrf_burgers_p1* b, hipStream_t st
                                         double* d_f) {
     const bool cn = b->scheme == GMRF_BURGERS_CN, dir = b->bc == GMRF_BURGERS_DIRICHLET, p2 = b->order == 2;
     const dim3 grid((unsigned)((b->rows + 255) / 256), (unsigned)batch);
-    if (burgers_unit_euler_periodic(b)) {
+    if (b->scheme == GMRF_BURGERS_COLLOCATION) {
+        BurgersCollocArgs a;
+        const double s = 4.0 / (b->h * b->h);
+        a.ns = (int)b->ns; a.nt = (int)b->nt; a.npts = (int)b->npts; a.dt = b->dt; a.nu = b->nu;
+        a.s[0] = s; a.s[1] = s; a.s[2] = -2.0 * s;
+        a.cell = b->d_cell; a.a = b->d_shape; a.d = b->d_shape + 3 * b->npts; a.w = d_w; a.vals = d_vals; a.f = d_f;
+        hipLaunchKernelGGL(burgers_colloc_rows, grid, dim3(256), 0, st, a);
+    } else if (burgers_unit_euler_periodic(b)) {
         BurgersP1Args a;
         a.ns = (int)b->ns; a.nt = (int)b->nt; a.dt = b->dt; a.nu = b->nu; a.w = d_w; a.vals = d_vals; a.f = d_f;
         if (p2) hipLaunchKernelGGL(burgers_p2_rows_batch, grid, dim3(256), 0, st, a, b->nnz);

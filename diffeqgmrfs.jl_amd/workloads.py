@@ -795,6 +795,53 @@ def burgers_chen24_batch(nc: int, nt: int, B: int, nu: float, amps, order: int =
             "scheme": scheme, "length": 2.0, "amps": amps, "xs": xs, "truth": truth}
 
 
+def burgers_collocation_points(x_coords, npts: int) -> np.ndarray:
+    """The collocation grid of scripts/burgers/solve_burgers_gmrf-collocation.jl:164-165: npts points from x_coords[0] + 1/npts
+    to x_coords[-1] - 1/npts, both included."""
+    x_coords = np.asarray(x_coords, dtype=np.float64)
+    dx = 1.0 / npts
+    return np.linspace(x_coords[0] + dx, x_coords[-1] - dx, npts)
+
+
+def burgers_collocation_batch(nc: int, nt: int, npts: int, B: int, nu: float, T: float, amp: float, seed: int = 0,
+                              ic_noise: float = 1e8, noise: float = 1e8):
+    """A batch of Gauss-Newton problems for `BurgersCollocationTangent(nc, nt, dt, nu, points)`: the data-set loop of
+    scripts/burgers/solve_burgers_gmrf-collocation.jl:217-246 on nc quadratic cells of the periodic unit line (ns = 2 nc dofs
+    x_i = i / ns), nt slices on [0, T], with the residual observed at `burgers_collocation_points(arange(ns) / ns, npts)` under
+    `noise` (noise_collocation, :195).  Problem p has the initial condition amp * `burgers_initial_conditions(ns, B, seed)[p]`, the
+    prior `burgers_line_prior_from_bulk(nc, nt, dt, nu, mean(ic), ic, order=2, bc="periodic", ic_noise=ic_noise)` with the
+    initial condition observed at every dof of slice 0 (Q = Q_prior + ic_noise A_ic' A_ic), and x_ic = Q^-1 rhs, the mean of
+    that conditioned prior (:224).  Host side only.
+
+    Returns the dict of `burgers_chen24_batch`: Q the pattern (CSC; the values of problem 0), q_values (B, nnz), Qx_prior (the
+    information vector of that conditioned prior, Q x_ic), x_prior = x0 = x_ic (B, n) -- the reference passes mean(x_ic) for both
+    (:237, :242) --, ic (B, ns), points (npts,), noise,
+    n_blocks = nt, n, m = (nt-1) npts, dt = T / (nt-1), nu, ns, nc, npts, order = 2, scheme = "collocation", length = 1.0, T, amp.
+
+    Gauss-Newton without damping on this residual, the reference's algorithm, does not converge on coarse meshes at the
+    nu = 0.01 / pi, T = 1 and amplitudes of `burgers_gauss_newton_batch`; the loop tests run at nu = 0.02, T = 0.05, amp = 0.5."""
+    if nc < 3 or nt < 2 or npts < 1 or B < 1:
+        raise ValueError("nc >= 3, nt >= 2, npts >= 1, B >= 1")
+    ns = 2 * nc
+    dt = T / (nt - 1)
+    ics = amp * burgers_initial_conditions(ns, B, seed)
+    points = burgers_collocation_points(np.arange(ns) / ns, npts)
+    Qs, rhs = [], []
+    for p in range(B):
+        Qp, Aic, r = burgers_line_prior_from_bulk(nc, nt, dt, nu, float(ics[p].mean()), ics[p], order=2, bc="periodic",
+                                                  ic_noise=ic_noise)
+        Qc = (Qp + ic_noise * (Aic.T @ Aic)).tocsc()
+        Qc = ((Qc + Qc.T) * 0.5).tocsc()
+        Qc.sort_indices()
+        if p and not (np.array_equal(Qc.indptr, Qs[0].indptr) and np.array_equal(Qc.indices, Qs[0].indices)):
+            raise ValueError(f"problem {p}: the prior's sparsity pattern differs from problem 0's")
+        Qs.append(Qc); rhs.append(r)
+    x_ic = np.stack([spla.splu(Qs[p]).solve(rhs[p]) for p in range(B)])
+    return {"Q": Qs[0], "q_values": np.stack([Q.data for Q in Qs]), "Qx_prior": np.stack(rhs), "x_prior": x_ic, "x0": x_ic.copy(),
+            "ic": ics, "points": points, "noise": noise, "n_blocks": nt, "n": ns * nt, "m": (nt - 1) * npts, "dt": dt, "nu": nu,
+            "ns": ns, "nc": nc, "npts": npts, "order": 2, "scheme": "collocation", "length": 1.0, "T": T, "amp": amp}
+
+
 # --------------------------------------------------------------------------- analytic / toy
 
 def laplace_kappa_grid(nx: int, ny: int, kappa2: float = 0.5) -> Workload:

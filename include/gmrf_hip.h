@@ -541,6 +541,25 @@ typedef enum { GMRF_BURGERS_EULER = 0, GMRF_BURGERS_CN = 1 } gmrf_burgers_scheme
 typedef enum { GMRF_BURGERS_PERIODIC = 0, GMRF_BURGERS_DIRICHLET = 1 } gmrf_burgers_bc;
 gmrf_status gmrf_burgers_line_create(int32_t device, void* stream, int64_t nc, int64_t nt, double dt, double nu, int32_t order,
                                      int32_t scheme, int32_t bc, double length, gmrf_burgers_p1** out);
+/* The same handle for the COLLOCATION form of the implicit-Euler step: residual and tangent evaluated at points instead of
+ * tested against basis functions -- f_and_J of the reference's scripts/burgers/solve_burgers_gmrf-collocation.jl:186-192 with
+ * J_static (:183) and the operators A_coll, du/dx, d2u/dx2 of :167-169 -- on the periodic quadratic line above: nc cells of
+ * length / nc, ns = 2 nc dofs numbered by position, cell e with the dofs (left, right, middle) = (2e, (2e+2) mod ns, 2e+1).
+ * `points` is a HOST array of npts coordinates in [0, length), in any order, several of them in one cell if need be.  Per point,
+ * once at creation and in double precision: e = min(floor(x / h), nc - 1), xi = 2 (x - e h) / h - 1, shape values
+ * a = (xi(xi-1)/2, xi(xi+1)/2, 1 - xi^2), first derivatives d = (xi - 1/2, xi + 1/2, -2 xi) 2/h, second derivatives
+ * s = (1, 1, -2) 4/h^2.  Row r = (t-1) npts + c (t = 1 .. nt-1, 0-based slices; rows = (nt-1) npts), with u = sum a_k w_t[k],
+ * u_x = sum d_k w_t[k], u_xx = sum s_k w_t[k], u- = sum a_k w_{t-1}[k] summed in the local order (left, right, middle):
+ *     f_r = u - u- + dt u u_x - dt nu u_xx,    J[r, t-1, k] = -a_k,    J[r, t, k] = a_k + dt (u_x a_k + u d_k) - dt nu s_k.
+ * Six stored entries per row (nnz = 6 rows): the cell's three dofs of slice t-1 in ascending column order, then of slice t; the
+ * wrap cell's columns sort as (0, 2e, 2e+1).  An entry that is exactly 0.0 (a point on a vertex) is stored.  _pattern, _tangent,
+ * _tangent_batch, _destroy and gmrf_gn_create / _run / _finalize serve the handle; device -1 gives the pattern only.
+ * GMRF_BURGERS_COLLOCATION is the handle's scheme, and a value gmrf_burgers_line_create keeps rejecting.
+ * GMRF_ERR_BAD_SHAPE: nc < 3, nt < 2, npts < 1, dt <= 0, nu < 0, length <= 0, or a point that is not finite or not in
+ * [0, length) -- gmrf_last_error names it. */
+enum { GMRF_BURGERS_COLLOCATION = 2 };
+gmrf_status gmrf_burgers_colloc_create(int32_t device, void* stream, int64_t nc, int64_t nt, double dt, double nu,
+                                       double length, int64_t npts, const double* points, gmrf_burgers_p1** out);
 gmrf_status gmrf_burgers_p1_destroy(gmrf_burgers_p1* b);
 gmrf_status gmrf_burgers_p1_pattern(const gmrf_burgers_p1* b, int64_t* nnz_out, int64_t* rowptr, int64_t* colidx,
                                     int32_t index_base);

@@ -30,7 +30,7 @@ module DiffEqGMRFsHIP
 using SparseArrays, LinearAlgebra
 
 export TridiagonalCholeskyFactor, tridiagonal_cholesky, forward_solve, backward_solve, ldiv, PosteriorAssembler, GmrfCsr,
-       GmrfComm, DarcyP1Assembler, BurgersP1Tangent, EllipticP1Tangent, elliptic_load!, GaussNewtonBatch, gauss_newton_batch!, DarcyConditioningBatch,
+       GmrfComm, DarcyP1Assembler, BurgersP1Tangent, BurgersCollocationTangent, EllipticP1Tangent, elliptic_load!, GaussNewtonBatch, gauss_newton_batch!, DarcyConditioningBatch,
        BurgersP1Prior, BurgersLinePrior, prior_values_batch!, BurgersInitialConditionBatch, initial_condition_batch, solution_errors_batch,
        condition_on_observations_batch, assemble_batch!
 
@@ -589,6 +589,27 @@ function BurgersP1Tangent(ns::Integer, nt::Integer, dt::Real, nu::Real; device::
     rowptr = Vector{Int64}(undef, rows + 1); colidx = Vector{Int64}(undef, nnz_out[])
     check(ccall((:gmrf_burgers_p1_pattern, libgmrf), Int32, (Ptr{Cvoid}, Ref{Int64}, Ptr{Int64}, Ptr{Int64}, Int32), h[], nnz_out, rowptr, colidx, 1))
     b = BurgersP1Tangent(h[], SparseMatrixCSC(nt * ns, rows, rowptr, colidx, ones(nnz_out[])), rows)
+    finalizer(x -> ccall((:gmrf_burgers_p1_destroy, libgmrf), Int32, (Ptr{Cvoid},), x.handle), b)
+    return b
+end
+
+# The collocation form (f_and_J, scripts/burgers/solve_burgers_gmrf-collocation.jl:186-192, J_static :183) on the periodic quadratic
+# line: nc cells of length / nc, ns = 2 nc dofs, `points` in [0, length) in any order; row (t-1) npts + c is point c of the step
+# t-1 -> t, six entries per row.  The handle is a BurgersP1Tangent: tangent!, tangent_batch! and GaussNewtonBatch take it unchanged.
+function BurgersCollocationTangent(nc::Integer, nt::Integer, dt::Real, nu::Real, points::AbstractVector{<:Real};
+                                   length::Real = 1.0, device::Integer = 0, stream::Ptr{Cvoid} = C_NULL)
+    pts = Vector{Float64}(points)
+    npts = Base.length(pts)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve pts check(ccall((:gmrf_burgers_colloc_create, libgmrf), Int32,
+        (Int32, Ptr{Cvoid}, Int64, Int64, Float64, Float64, Float64, Int64, Ptr{Float64}, Ref{Ptr{Cvoid}}),
+        device, stream, nc, nt, Float64(dt), Float64(nu), Float64(length), npts, pts, h))
+    nnz_out = Ref{Int64}(0)
+    check(ccall((:gmrf_burgers_p1_pattern, libgmrf), Int32, (Ptr{Cvoid}, Ref{Int64}, Ptr{Int64}, Ptr{Int64}, Int32), h[], nnz_out, C_NULL, C_NULL, 1))
+    rows = (nt - 1) * npts
+    rowptr = Vector{Int64}(undef, rows + 1); colidx = Vector{Int64}(undef, nnz_out[])
+    check(ccall((:gmrf_burgers_p1_pattern, libgmrf), Int32, (Ptr{Cvoid}, Ref{Int64}, Ptr{Int64}, Ptr{Int64}, Int32), h[], nnz_out, rowptr, colidx, 1))
+    b = BurgersP1Tangent(h[], SparseMatrixCSC(nt * 2 * nc, rows, rowptr, colidx, ones(nnz_out[])), rows)
     finalizer(x -> ccall((:gmrf_burgers_p1_destroy, libgmrf), Int32, (Ptr{Cvoid},), x.handle), b)
     return b
 end

@@ -275,6 +275,22 @@ class PosteriorAssembler:
                                                                _cabi.ptr(o), float(noise), _cabi.ptr(out)))
         return out
 
+    def quadform_batch(self, a_values, x, z):
+        """(B,) quadratic forms (z - x)' A (z - x), `sqmahal(x, z)` of scripts/burgers/solve_burgers_gmrf-collocation.jl:208-215:
+        a_values (nnz_out,) shared or (B, nnz_out) per problem, the values on `pattern` as `precision_batch` returns them; x, z
+        (B, n).  One pass over the values on the device, a fixed-shape sum: the same bits on every call and whatever batch a
+        problem sits in (gmrf_assemble_quadform_batch)."""
+        B = x.shape[0]
+        xv, zv = self._mat(x, B, self.n, "x"), self._mat(z, B, self.n, "z")
+        if getattr(a_values, "ndim", 1) == 2:
+            a, stride = self._mat(a_values, B, self.nnz_out, "a_values"), self.nnz_out
+        else:
+            a, stride = self._vec(a_values, self.nnz_out, "a_values"), 0
+        out = self._like2(xv, (B,))
+        _cabi.check(_cabi.load().gmrf_assemble_quadform_batch(self._h, B, _cabi.ptr(a), stride, _cabi.ptr(xv), _cabi.ptr(zv),
+                                                              _cabi.ptr(out)))
+        return out
+
 
 class DarcyP1Assembler:
     """Darcy stiffness matrix and load vector on the device (first piece):
@@ -797,6 +813,63 @@ class GaussNewtonBatch:
         _cabi.check(_cabi.load().gmrf_gn_finalize(self._h, C.byref(info)), info.value)
         return self.F
 
+    _VAR = {None: -1, "none": -1, "exact": _cabi.VAR_EXACT, "rbmc": _cabi.VAR_RBMC, "mc": _cabi.VAR_MC}
+
+    def posterior(self, z=None, first: int = 0, k_samples: int = 1, var="rbmc", k_var: int = 50, sample_seed: int = 0x5EED,
+                  var_seed: int = 0x5EED, out=None):
+        """Everything `solve_problem` returns for the final iterate of the last `run`, in ONE call on the device
+        (gmrf_gn_posterior): `finalize()`, then k_samples samples x + L^-T z (ids of `sample_batch`), the marginal standard
+        deviations by `var` ("rbmc" = the reference's RBMCStrategy(k_var), "mc", "exact" or None; problem p draws the ids
+        p k_var + s) and their norms, logdet, and -- with z (B, n), the reference solution's dofs -- sqmahal(x, z), nll and
+        (rel_err, rmse, max_err) of x against z over the elements [first, n) (first = ns: the scripts' [2:end, :]).  Each piece
+        is bitwise the public call (`sample_batch`, `marginal_var`, `logdet_batch`, `quadform_batch`, `solution_errors_batch`).
+        The result's arrays are torch tensors on the device when z -- or, without z, the last run's x -- is one, NumPy
+        otherwise.  `out`: a GaussNewtonPosterior of arrays to fill instead of new ones (`x` is not written); after
+        NotPositiveDefinite they are unchanged."""
+        B, a = self.F.batch, self.asm
+        if var not in self._VAR:
+            raise ValueError('var must be "rbmc", "mc", "exact" or None')
+        method = self._VAR[var]
+        k_samples = int(k_samples)
+        zv = a._mat(z, B, a.n, "z")
+        x_last = self.last[0] if getattr(self, "last", None) is not None else None
+        ref = zv if zv is not None else (x_last if x_last is not None else np.empty(0))
+        shapes = (("samples", (B, k_samples, a.n) if k_samples > 0 else None), ("std", (B, a.n) if method >= 0 else None),
+                  ("std_norm", (B,) if method >= 0 else None), ("logdet", (B,)), ("sqmahal", (B,) if zv is not None else None),
+                  ("nll", (B,) if zv is not None else None), ("errors", (B, 3) if zv is not None else None))
+        if out is None:
+            like2 = PosteriorAssembler._like2
+            out = GaussNewtonPosterior(x_last, **{name: (like2(ref, shape) if shape is not None else None) for name, shape in shapes})
+        else:
+            for name, shape in shapes:
+                arr = getattr(out, name)
+                if arr is None:
+                    continue
+                if shape is None:
+                    raise ValueError(f"out.{name} given, but this call does not produce it")
+                ok = tuple(arr.shape) == shape and (arr.is_contiguous() and str(arr.dtype) == "torch.float64" if _is_torch(arr)
+                                                    else isinstance(arr, np.ndarray) and arr.flags.c_contiguous and arr.dtype == np.float64)
+                if not ok:
+                    raise ValueError(f"out.{name} must be a contiguous float64 array of shape {shape}")
+        info = C.c_int32(0)
+        st = _cabi.load().gmrf_gn_posterior(self._h, _cabi.ptr(zv), int(first), k_samples, int(sample_seed), method, int(k_var),
+                                            int(var_seed), _cabi.ptr(out.samples), _cabi.ptr(out.std), _cabi.ptr(out.std_norm),
+                                            _cabi.ptr(out.logdet), _cabi.ptr(out.sqmahal), _cabi.ptr(out.nll), _cabi.ptr(out.errors),
+                                            C.byref(info))
+        _cabi.check(st, info.value)
+        return out
+
+
+class GaussNewtonPosterior:
+    """What `GaussNewtonBatch.posterior` returns: x (B, n), the final iterate of the run; samples (B, k_samples, n) or None; std
+    (B, n) and std_norm (B,) or None (var=None); logdet (B,); sqmahal (B,), nll (B,) and errors (B, 3) = (rel_err, rmse, max_err),
+    or None without z."""
+    __slots__ = ("x", "samples", "std", "std_norm", "logdet", "sqmahal", "nll", "errors")
+
+    def __init__(self, x=None, samples=None, std=None, std_norm=None, logdet=None, sqmahal=None, nll=None, errors=None):
+        self.x, self.samples, self.std, self.std_norm = x, samples, std, std_norm
+        self.logdet, self.sqmahal, self.nll, self.errors = logdet, sqmahal, nll, errors
+
 
 class DarcyConditioningResult:
     """What `DarcyConditioningBatch.run` returns: mean (B, n), samples (B, k_samples, n) or None, std (B, n) and std_norm (B,)
@@ -888,7 +961,7 @@ class BurgersInitialConditionBatch:
 
         x_ic, q, qx, _ = ic_stage.run(ics)
         x, steps, hist = gn.run(q, qx, x_ic, x_ic)      # prior mean and start = mean(x_ic); Q_ic mean(x_ic) = qx
-        F = gn.finalize()                               # then sample_batch / marginal_var_batch
+        post = gn.posterior(z=soln_dofs, first=ns)      # samples, std, logdet, sqmahal, nll, errors (or F = gn.finalize() and the calls)
 
     `F` (reference order, factored once on `asm.pattern`), `asm` (built on `prior.pattern` and the tangent's pattern) and `prior`
     (a `BurgersP1Prior` or a `BurgersLinePrior`, with the `BurgersP1Tangent` of the same line in `asm`) must have been created on the same device with the same `stream` argument."""
@@ -1250,6 +1323,14 @@ class TridiagonalCholeskyFactor:
         v = C.c_double(0.0)
         _cabi.check(self._lib.gmrf_bt_logdet(self._h, C.byref(v)))
         return v.value
+
+    def logdet_batch(self, out=None):
+        """(B,) logdet of every problem in one call (gmrf_bt_logdet_batch): entry p is bitwise `logdet()` after
+        `select_problem(p)`.  `out`: a contiguous float64 array of B values to fill -- NumPy, or a torch tensor on the handle's
+        device; default: a new NumPy array."""
+        out = self._out_array(out, (self.batch,))
+        _cabi.check(self._lib.gmrf_bt_logdet_batch(self._h, _cabi.ptr(out)))
+        return out
 
     def normals(self, k: int, seed: int = 0x5EED, first_id: int = 0, like=None):
         if self.batch != 1:

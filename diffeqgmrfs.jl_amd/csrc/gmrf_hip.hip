@@ -47,6 +47,7 @@
 #include "selinv.hpp"
 #include "gauss_newton.hpp"
 #include "darcy_cond.hpp"
+#include "gn_posterior.hpp"
 #include "burgers_prior.hpp"
 #include "burgers_line_prior.hpp"
 
@@ -219,7 +220,7 @@ struct gmrf_handle {
     int64_t kp_cap = 0;
     double* d_stage = nullptr;
     int64_t stage_cap = 0;
-    DevBuf mean_arena;                 // a host `mean` of gmrf_bt_sample (Staging)
+    DevBuf mean_arena;                 // a host `mean` of gmrf_bt_sample, a host `out` of gmrf_bt_logdet_batch (Staging)
     double* d_acc = nullptr;           // variance accumulator / output ([acc_B][n])
     int64_t acc_B = 0;
     int32_t var_group = 0, var_groups = 0;   // the last batched sampled estimator: problems per group of the stage, groups per chunk (gmrf_test_var_groups)
@@ -3421,6 +3422,36 @@ gmrf_status gmrf_bt_logdet(gmrf_handle* h, double* out) {
     return GMRF_OK;
 }
 
+// logdet of every problem -> d_out[B] (device), enqueued on the handle's stream: the parts as gmrf_bt_logdet takes them (from the
+// resident L blocks, else what the factorisation left), then one thread per problem adds them in its order
+static gmrf_status logdet_batch_enqueue(gmrf_handle* h, double* d_out) {
+    if (h->keep_l && h->l_valid) {
+        hipLaunchKernelGGL(logdet_blocks, dim3((unsigned)h->N, (unsigned)h->B), dim3(256), 0, h->stream, h->d_L, blk_elems(h), h->bsp,
+                           (int)h->bs, h->d_logdet, stride_pL(h), h->N);
+    } else if (!h->logdet_valid) {
+        g_last_error = "neither the L blocks nor the log-determinant parts of this factor are resident (adopted as raw buffers without L)";
+        return GMRF_ERR_NO_FACTOR;
+    }
+    hipLaunchKernelGGL(logdet_sum_batch, dim3((unsigned)((h->B + 255) / 256)), dim3(256), 0, h->stream, h->d_logdet, h->N, h->B, d_out);
+    HIPCHK(hipGetLastError());
+    return GMRF_OK;
+}
+
+gmrf_status gmrf_bt_logdet_batch(gmrf_handle* h, double* out) {
+    if (!h || !out) return bad_shape("null pointer");
+    GCHK(tw_refuse(h, "gmrf_bt_logdet_batch"));
+    if (!h->factored) { g_last_error = "logdet before factor"; return GMRF_ERR_NO_FACTOR; }
+    HIPCHK(hipSetDevice(h->device));
+    double* d_out;
+    Staging args(h->mean_arena);
+    args.out(out, sizeof(double) * h->B, &d_out);
+    GCHK(args.commit(h->stream));
+    GCHK(logdet_batch_enqueue(h, d_out));
+    GCHK(args.flush(h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return GMRF_OK;
+}
+
 // --------------------------------------------------------------------------------- CSR / SpMM
 gmrf_status gmrf_csr_create(int32_t device, void* stream, int64_t n_rows, int64_t n_cols, const int64_t* rowptr,
                             const int64_t* colidx, const double* vals, int32_t index_base, int32_t values_f32,
@@ -3771,7 +3802,10 @@ struct gmrf_assembler : DevCtx {        // device -1: symbolic only (pattern que
     std::vector<int32_t> q_row;
     int64_t* d_q_ptr = nullptr;
     int32_t* d_q_row = nullptr;
-    DevBuf bpart;                       // work arrays: [batch][m] (J x + obs_diff) of the rhs, the objective's partial sums
+    // ... and the result pattern the same way (colptr / rowval with 32-bit rows), uploaded by the first quadratic form
+    int64_t* d_o_ptr = nullptr;
+    int32_t* d_o_row = nullptr;
+    DevBuf bpart;                       // work arrays: [batch][m] (J x + obs_diff) of the rhs, the partial sums of the objective / quadratic form
 };
 
 gmrf_status gmrf_assemble_create(int32_t device, void* stream, int64_t n, const int64_t* q_colptr, const int64_t* q_rowval,
@@ -3866,7 +3900,7 @@ gmrf_status gmrf_assemble_destroy(gmrf_assembler* as) {
     if (as->has_device()) {
         free_dev(as->d_pptr); free_dev(as->d_qmap); free_dev(as->d_pa); free_dev(as->d_pb);
         free_dev(as->d_jt_ptr); free_dev(as->d_jt_row); free_dev(as->d_jt_src); free_dev(as->d_j_rptr); free_dev(as->d_j_col);
-        free_dev(as->d_q_ptr); free_dev(as->d_q_row);
+        free_dev(as->d_q_ptr); free_dev(as->d_q_row); free_dev(as->d_o_ptr); free_dev(as->d_o_row);
         as->arena.release(); as->bpart.release();
     }
     delete as;
@@ -4739,6 +4773,53 @@ gmrf_status gmrf_assemble_objective_batch(gmrf_assembler* as, int64_t batch, con
     return GMRF_OK;
 }
 
+// chunks of the fixed partition of a sum over n elements (std_norm_part, quadform_part): a function of n only
+static int64_t std_norm_chunks(int64_t n) { return std::min<int64_t>(1024, std::max<int64_t>(1, (n + 2047) / 2048)); }
+
+static gmrf_status quadform_ready(gmrf_assembler* as) {
+    if (as->d_o_ptr) return GMRF_OK;
+    if (as->n >= ((int64_t)1 << 31)) return bad_shape("the quadratic form needs n < 2^31");
+    const std::vector<int32_t> row(as->rowval.begin(), as->rowval.end());
+    HIPCHK(hipMalloc(&as->d_o_ptr, sizeof(int64_t) * as->colptr.size()));
+    HIPCHK(hipMalloc(&as->d_o_row, sizeof(int32_t) * std::max<size_t>(row.size(), 1)));
+    HIPCHK(hipMemcpyAsync(as->d_o_ptr, as->colptr.data(), sizeof(int64_t) * as->colptr.size(), hipMemcpyHostToDevice, as->stream));
+    if (!row.empty()) HIPCHK(hipMemcpyAsync(as->d_o_row, row.data(), sizeof(int32_t) * row.size(), hipMemcpyHostToDevice, as->stream));
+    HIPCHK(hipStreamSynchronize(as->stream));        // (`row` goes with this scope)
+    return GMRF_OK;
+}
+
+// d_part: [batch][std_norm_chunks(n)] work array; quadform_ready(as) has run
+static gmrf_status launch_quadform_batch(const gmrf_assembler* as, hipStream_t st, int64_t batch, const double* d_a, int64_t a_stride,
+                                         const double* d_x, const double* d_z, double* d_part, double* d_out) {
+    const int64_t nch = std_norm_chunks(as->n), len = (as->n + nch - 1) / nch;
+    hipLaunchKernelGGL(quadform_part, dim3((unsigned)nch, (unsigned)batch), dim3(256), 0, st, as->d_o_ptr, as->d_o_row, d_a, a_stride, d_x,
+                       d_z, as->n, len, d_part);
+    hipLaunchKernelGGL(pattern_dot_sum, dim3(1, (unsigned)batch), dim3(256), 0, st, d_part, nch, (int64_t)1, d_out);
+    HIPCHK(hipGetLastError());
+    return GMRF_OK;
+}
+
+gmrf_status gmrf_assemble_quadform_batch(gmrf_assembler* as, int64_t batch, const double* a_nzval, int64_t a_stride, const double* x,
+                                         const double* z, double* out) {
+    if (!as || !a_nzval || !x || !z || !out || !batch_ok(batch)) return bad_shape("null pointer or batch outside [1, 4096]");
+    if (a_stride != 0 && a_stride != as->nnz_out) return bad_shape("a_stride must be 0 (one A for all problems) or nnz of the assembled pattern");
+    GCHK(as->ready(AS_PATTERN_ONLY));
+    GCHK(quadform_ready(as));
+    const double *d_a, *d_x, *d_z;
+    double* d_out;
+    Staging args(as->arena);
+    args.in(a_nzval, sizeof(double) * (a_stride ? batch * as->nnz_out : as->nnz_out), &d_a);
+    args.in(x, sizeof(double) * batch * as->n, &d_x);
+    args.in(z, sizeof(double) * batch * as->n, &d_z);
+    args.out(out, sizeof(double) * batch, &d_out);
+    GCHK(args.commit(as->stream));
+    GCHK(as->bpart.reserve(as->stream, sizeof(double) * batch * std_norm_chunks(as->n)));
+    GCHK(launch_quadform_batch(as, as->stream, batch, d_a, a_stride, d_x, d_z, as->bpart.as<double>(), d_out));
+    GCHK(args.flush(as->stream));
+    HIPCHK(hipStreamSynchronize(as->stream));
+    return GMRF_OK;
+}
+
 // --------------------------------------------------------------------------------- what the batched drivers share
 // gmrf_gn, gmrf_dc and gmrf_bic bind a handle and an assembler (and one more object of their own) that live on one device and
 // stream, keep their device buffers in one carved allocation, and run with a buffer of theirs registered as the factor's rhs.
@@ -4750,12 +4831,15 @@ struct DriverBase {
     DevBuf in;                           // arena of a run's host arguments (Staging)
     DevBuf work;                         // every device buffer of the driver, carved up by its *_alloc
     int64_t B = 0;                       // the batch `work` is carved for
+    gmrf_csr* Qp = nullptr;              // the posterior pattern as a CSR matrix (tile plan of the RBMC product), made by the first RBMC run
 
     void bind(gmrf_handle* handle, gmrf_assembler* assembler) { h = handle; as = assembler; device = handle->device; stream = handle->stream; }
     void close() {
         (void)hipSetDevice(device);
         (void)hipStreamSynchronize(stream);
         in.release(); work.release();
+        if (Qp) (void)gmrf_csr_destroy(Qp);
+        Qp = nullptr;
     }
 };
 
@@ -4792,6 +4876,41 @@ static gmrf_status driver_analysis_ok(const DriverBase* g) {
     return GMRF_OK;
 }
 
+// the posterior pattern (symmetric: the assembler's CSC arrays read by rows) as the matrix whose tile plan the RBMC product uses
+static gmrf_status driver_pattern_csr(DriverBase* g) {
+    if (g->Qp) return GMRF_OK;
+    const gmrf_assembler* as = g->as;
+    const std::vector<double> ones((size_t)std::max<int64_t>(as->nnz_out, 1), 1.0);
+    return gmrf_csr_create(g->h->device, (void*)g->h->stream, as->n, as->n, as->colptr.data(), as->rowval.data(), ones.data(), 0, 0, &g->Qp);
+}
+
+static gmrf_status var_batch_enqueue(gmrf_handle* h, int method, int64_t k, uint64_t seed, const gmrf_csr* Q, const double* qv,
+                                     double* d_diag, double* d_var);
+
+// The variance tail of a driver's stage on the factor its handle holds: d_var [B][n] <- the marginal variances by var_method
+// (-1: nothing is done), the sampled estimators on the posterior values d_nz [B][nnz] just assembled, with d_diag [B][n] as work
+// and driver_pattern_csr made for RBMC.  Behind the public calls' own abort-and-repeat guard.
+static gmrf_status driver_variances(DriverBase* g, int32_t var_method, int64_t k_var, uint64_t var_seed, const double* d_nz,
+                                    double* d_diag, double* d_var) {
+    gmrf_handle* h = g->h;
+    if (var_method == GMRF_VAR_EXACT) return gmrf_bt_marginal_var(h, GMRF_VAR_EXACT, 0, 0, nullptr, d_var);
+    if (var_method != GMRF_VAR_RBMC && var_method != GMRF_VAR_MC) return GMRF_OK;
+    return sweep_guarded(h, {}, [&]() -> gmrf_status {     // (a batch of one: its sweeps may be persistent launches)
+        GCHK(var_batch_enqueue(h, var_method, k_var, var_seed, g->Qp, d_nz, d_diag, d_var));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        return GMRF_OK;
+    });
+}
+
+// ... and its last line: std = sqrt(var) in place, d_norm [B] <- |std_p|_2; d_part: [B][std_norm_chunks(n)] work
+static gmrf_status driver_std_norm(const DriverBase* g, double* d_var, double* d_part, double* d_norm) {
+    const int64_t n = g->as->n, B = g->h->B, nch = std_norm_chunks(n), len = (n + nch - 1) / nch;
+    hipLaunchKernelGGL(std_norm_part, dim3((unsigned)nch, (unsigned)B), dim3(256), 0, g->h->stream, d_var, n, len, d_part);
+    hipLaunchKernelGGL(std_norm_finish, dim3(1, (unsigned)B), dim3(256), 0, g->h->stream, d_part, nch, d_norm);
+    HIPCHK(hipGetLastError());
+    return GMRF_OK;
+}
+
 // --------------------------------------------------------------------------------- the batched Gauss-Newton driver
 // B = batch of the handle Burgers problems on one mesh in lock step (scripts/solve_burger.jl:151-180 per problem).  One iteration
 // on the handle's stream:
@@ -4813,6 +4932,11 @@ struct gmrf_gn : DriverBase {
     double noise = 0.0;
     bool have_x = false;                 // a run has left its iterate in d_x (gmrf_gn_finalize)
     int32_t iterations = 0, fwd_iterations = 0;      // of the last run: iterations, and those whose solve was the backward sweep alone
+    // the posterior stage (gmrf_gn_posterior): buffers of its own, carved for (post_B, post_ks); the run's layout is not touched
+    DevBuf post;
+    int64_t post_B = 0, post_ks = -1;
+    double *d_smp = nullptr, *d_var = nullptr, *d_diag = nullptr, *d_spart = nullptr, *d_norm = nullptr;
+    double *d_ld = nullptr, *d_sq = nullptr, *d_nll = nullptr, *d_err = nullptr, *d_epart = nullptr;
 };
 
 // The one place that knows which tangent is bound: its device, stream and the shape of its J, and its batch launch.
@@ -4863,6 +4987,7 @@ gmrf_status gmrf_gn_create_elliptic(gmrf_handle* h, gmrf_assembler* as, gmrf_ell
 gmrf_status gmrf_gn_destroy(gmrf_gn* g) {
     if (!g) return GMRF_OK;
     g->close();
+    g->post.release();
     if (g->h_active) (void)hipHostFree(g->h_active);
     delete g;
     return GMRF_OK;
@@ -4998,16 +5123,21 @@ gmrf_status gmrf_gn_run(gmrf_gn* g, const double* q_nzval, int64_t q_stride, con
     return status != GMRF_OK ? status : out_status;
 }
 
+// tangent at the run's final x, A = Q + noise J'J into d_a, factor (a run on this batch has been checked for)
+static gmrf_status gn_factor_final(gmrf_gn* g, int32_t* info) {
+    gmrf_handle* h = g->h;
+    GCHK(gn_launch_tangent(g, h->stream, g->B, g->d_x, g->d_jv, g->d_f));
+    GCHK(launch_precision_batch(g->as, h->stream, g->B, g->d_q, g->q_stride, g->d_jv, g->noise, g->d_a));
+    return numeric_factor(h, g->d_a, info);
+}
+
 gmrf_status gmrf_gn_finalize(gmrf_gn* g, int32_t* info) {
     if (!g) return bad_shape("null pointer");
     if (info) *info = 0;
     if (!g->have_x || g->B != g->h->B) { g_last_error = "gmrf_gn_finalize: no run on this batch"; return GMRF_ERR_NO_FACTOR; }
     GCHK(gn_bound_ok(g));
-    gmrf_handle* h = g->h;
-    HIPCHK(hipSetDevice(h->device));
-    GCHK(gn_launch_tangent(g, h->stream, g->B, g->d_x, g->d_jv, g->d_f));
-    GCHK(launch_precision_batch(g->as, h->stream, g->B, g->d_q, g->q_stride, g->d_jv, g->noise, g->d_a));
-    return numeric_factor(h, g->d_a, info);
+    HIPCHK(hipSetDevice(g->h->device));
+    return gn_factor_final(g, info);
 }
 
 // --------------------------------------------------------------------------------- the batched Darcy conditioning driver
@@ -5019,17 +5149,11 @@ gmrf_status gmrf_gn_finalize(gmrf_gn* g, int32_t* info) {
 // intermediate -- A's values, the posterior values the RBMC product reads -- stays in the driver's buffers on the device.
 struct gmrf_dc : DriverBase {
     gmrf_darcy_p1* d = nullptr;
-    gmrf_csr* Qp = nullptr;              // the posterior pattern as a CSR matrix (tile plan of the RBMC product), made by the first RBMC run
     int64_t ks = -1;                     // the samples `work` is carved for
     double *d_av = nullptr, *d_y = nullptr, *d_dw = nullptr, *d_nz = nullptr, *d_rhs = nullptr, *d_mean = nullptr, *d_smp = nullptr;
     double *d_var = nullptr, *d_diag = nullptr, *d_part = nullptr, *d_norm = nullptr;
     int32_t fwd_in_factor = 0;           // the last run's factorisation left y = L^-1 rhs (gmrf_test_dc_route)
 };
-
-static gmrf_status var_batch_enqueue(gmrf_handle* h, int method, int64_t k, uint64_t seed, const gmrf_csr* Q, const double* qv,
-                                     double* d_diag, double* d_var);
-
-static int64_t std_norm_chunks(int64_t n) { return std::min<int64_t>(1024, std::max<int64_t>(1, (n + 2047) / 2048)); }
 
 static gmrf_status dc_bound_ok(const gmrf_dc* g) {
     const gmrf_handle* h = g->h;
@@ -5056,7 +5180,6 @@ gmrf_status gmrf_dc_create(gmrf_handle* h, gmrf_assembler* as, gmrf_darcy_p1* d,
 gmrf_status gmrf_dc_destroy(gmrf_dc* g) {
     if (!g) return GMRF_OK;
     g->close();
-    if (g->Qp) (void)gmrf_csr_destroy(g->Qp);
     delete g;
     return GMRF_OK;
 }
@@ -5076,14 +5199,6 @@ static gmrf_status dc_alloc(gmrf_dc* g, int64_t B, int64_t ks) {
     lay(g->work.as<char>());
     g->B = B; g->ks = ks;
     return GMRF_OK;
-}
-
-// the posterior pattern (symmetric: the assembler's CSC arrays read by rows) as the matrix whose tile plan the RBMC product uses
-static gmrf_status dc_pattern_csr(gmrf_dc* g) {
-    if (g->Qp) return GMRF_OK;
-    const gmrf_assembler* as = g->as;
-    const std::vector<double> ones((size_t)std::max<int64_t>(as->nnz_out, 1), 1.0);
-    return gmrf_csr_create(g->h->device, (void*)g->h->stream, as->n, as->n, as->colptr.data(), as->rowval.data(), ones.data(), 0, 0, &g->Qp);
 }
 
 gmrf_status gmrf_dc_run(gmrf_dc* g, const double* coeff_tables, int64_t ng, double beta, const double* q_nzval, int64_t q_stride,
@@ -5110,7 +5225,7 @@ gmrf_status gmrf_dc_run(gmrf_dc* g, const double* coeff_tables, int64_t ng, doub
     HIPCHK(hipSetDevice(h->device));
     hipStream_t st = h->stream;
     GCHK(dc_alloc(g, B, k_samples));
-    if (var_method == GMRF_VAR_RBMC) GCHK(dc_pattern_csr(g));
+    if (var_method == GMRF_VAR_RBMC) GCHK(driver_pattern_csr(g));
     const double *d_tab, *d_q, *d_qmu;
     Staging args(g->in);
     args.in(coeff_tables, sizeof(double) * B * ng * ng, &d_tab);
@@ -5131,24 +5246,12 @@ gmrf_status gmrf_dc_run(gmrf_dc* g, const double* coeff_tables, int64_t ng, doub
         g->fwd_in_factor = (h->fy_for && h->fy_for == g->d_rhs) ? 1 : 0;
         if (k_samples > 0) GCHK(gmrf_bt_posterior(h, g->d_rhs, sample_seed, 0, k_samples, g->d_mean, g->d_smp, n));
         else GCHK(gmrf_bt_solve(h, g->d_rhs, g->d_mean, 1, n, n, GMRF_SOLVE_FULL));
-        if (var_method == GMRF_VAR_EXACT) GCHK(gmrf_bt_marginal_var(h, GMRF_VAR_EXACT, 0, 0, nullptr, g->d_var));
-        else if (sampled)
-            GCHK(sweep_guarded(h, {}, [&]() -> gmrf_status {     // (a batch of one: its sweeps may be persistent launches)
-                GCHK(var_batch_enqueue(h, var_method, k_var, var_seed, g->Qp, g->d_nz, g->d_diag, g->d_var));
-                HIPCHK(hipStreamSynchronize(st));
-                return GMRF_OK;
-            }));
-        return GMRF_OK;
+        return driver_variances(g, var_method, k_var, var_seed, g->d_nz, g->d_diag, g->d_var);
     };
     const gmrf_status status = solve();
     if (status != GMRF_OK) { (void)hipStreamSynchronize(st); return status; }      // (the outputs are untouched)
     // 7: std = sqrt(var) in place, |std| per problem
-    if (var_method != -1) {
-        const int64_t nch = std_norm_chunks(n), len = (n + nch - 1) / nch;
-        hipLaunchKernelGGL(std_norm_part, dim3((unsigned)nch, (unsigned)B), dim3(256), 0, st, g->d_var, n, len, g->d_part);
-        hipLaunchKernelGGL(std_norm_finish, dim3(1, (unsigned)B), dim3(256), 0, st, g->d_part, nch, g->d_norm);
-        HIPCHK(hipGetLastError());
-    }
+    if (var_method != -1) GCHK(driver_std_norm(g, g->d_var, g->d_part, g->d_norm));
     GCHK(copy_out(st, mean_out, g->d_mean, sizeof(double) * B * n));
     GCHK(copy_out(st, samples_out, g->d_smp, sizeof(double) * B * k_samples * n));
     GCHK(copy_out(st, std_out, g->d_var, sizeof(double) * B * n));
@@ -5272,6 +5375,16 @@ gmrf_status gmrf_bic_run(gmrf_bic* g, const double* ic, double* x_ic_out, double
 // --------------------------------------------------------------------------------- batched error metrics (src/metrics.jl)
 static int64_t field_errors_chunks(int64_t count) { return std::min<int64_t>(1024, std::max<int64_t>(1, (count + 2047) / 2048)); }
 
+// d_part: [batch][field_errors_chunks(n - first)][3] work array; d_out: [batch][3]
+static gmrf_status launch_field_errors_batch(hipStream_t st, int64_t batch, int64_t n, int64_t first, const double* d_pred,
+                                             const double* d_soln, double* d_part, double* d_out) {
+    const int64_t count = n - first, nch = field_errors_chunks(count), len = (count + nch - 1) / nch;
+    hipLaunchKernelGGL(field_errors_part, dim3((unsigned)nch, (unsigned)batch), dim3(256), 0, st, d_pred, d_soln, n, first, len, d_part);
+    hipLaunchKernelGGL(field_errors_finish, dim3(1, (unsigned)batch), dim3(256), 0, st, d_part, nch, count, d_out);
+    HIPCHK(hipGetLastError());
+    return GMRF_OK;
+}
+
 gmrf_status gmrf_field_errors_batch(int32_t device, void* stream, int64_t batch, int64_t n, int64_t first, const double* pred,
                                     const double* soln, double* out) {
     if (!pred || !soln || !out || !batch_ok(batch)) return bad_shape("null pointer or batch outside [1, 4096]");
@@ -5279,7 +5392,6 @@ gmrf_status gmrf_field_errors_batch(int32_t device, void* stream, int64_t batch,
     DevCtx ctx;
     GCHK(ctx.open(device, stream, hipStreamNonBlocking, "gmrf_field_errors_batch", false));
     DevBuf arena, part;
-    const int64_t count = n - first, nch = field_errors_chunks(count), len = (count + nch - 1) / nch;
     const double *d_pred, *d_soln;
     double* d_out;
     Staging args(arena);
@@ -5288,11 +5400,8 @@ gmrf_status gmrf_field_errors_batch(int32_t device, void* stream, int64_t batch,
     args.out(out, sizeof(double) * batch * 3, &d_out);
     auto run = [&]() -> gmrf_status {
         GCHK(args.commit(ctx.stream));
-        GCHK(part.reserve(ctx.stream, sizeof(double) * (size_t)(batch * nch * 3)));
-        hipLaunchKernelGGL(field_errors_part, dim3((unsigned)nch, (unsigned)batch), dim3(256), 0, ctx.stream, d_pred, d_soln, n, first, len,
-                           part.as<double>());
-        hipLaunchKernelGGL(field_errors_finish, dim3(1, (unsigned)batch), dim3(256), 0, ctx.stream, part.as<double>(), nch, count, d_out);
-        HIPCHK(hipGetLastError());
+        GCHK(part.reserve(ctx.stream, sizeof(double) * (size_t)(batch * field_errors_chunks(n - first) * 3)));
+        GCHK(launch_field_errors_batch(ctx.stream, batch, n, first, d_pred, d_soln, part.as<double>(), d_out));
         GCHK(args.flush(ctx.stream));
         HIPCHK(hipStreamSynchronize(ctx.stream));
         return GMRF_OK;
@@ -5301,6 +5410,88 @@ gmrf_status gmrf_field_errors_batch(int32_t device, void* stream, int64_t batch,
     ctx.close();                        // (drains the stream before the buffers go)
     arena.release(); part.release();
     return status;
+}
+
+// --------------------------------------------------------------------------------- the posterior stage of the Gauss-Newton driver
+// What the data-set loops do with the final iterate (solve_burgers_gmrf-fem.jl:184-208, -collocation.jl:248-263, the final GMRF of
+// _research/elliptic_chen24.jl) for the batch of the last gmrf_gn_run, in ONE call on the handle's stream:
+//     gmrf_gn_finalize's tangent, A = Q + noise J'J and factor -> samples x + L^-T z -> variances -> std, |std| -> logdet, sqmahal, nll
+//     -> errors of x against z
+// Samples and variances go through the public calls' own abort-and-repeat guards; A's values, which the RBMC product and the
+// quadratic form read, the samples' mean x and every score stay in the driver's buffers on the device.
+static gmrf_status gn_post_alloc(gmrf_gn* g, int64_t B, int64_t ks) {
+    if (g->post_B == B && g->post_ks == ks && g->post.p) return GMRF_OK;
+    const int64_t n = g->as->n;
+    auto lay = [&](char* base) {
+        Carve c{base};
+        c(&g->d_smp, B * ks * n); c(&g->d_var, B * n); c(&g->d_diag, B * n); c(&g->d_spart, B * std_norm_chunks(n)); c(&g->d_norm, B);
+        c(&g->d_ld, B); c(&g->d_sq, B); c(&g->d_nll, B); c(&g->d_err, B * 3); c(&g->d_epart, B * field_errors_chunks(n) * 3);
+        return c.used;
+    };
+    GCHK(g->post.reserve(g->h->stream, lay(nullptr)));
+    lay(g->post.as<char>());
+    g->post_B = B; g->post_ks = ks;
+    return GMRF_OK;
+}
+
+gmrf_status gmrf_gn_posterior(gmrf_gn* g, const double* z, int64_t first, int64_t k_samples, uint64_t sample_seed, int32_t var_method,
+                              int64_t k_var, uint64_t var_seed, double* samples_out, double* std_out, double* std_norm_out,
+                              double* logdet_out, double* sqmahal_out, double* nll_out, double* errors_out, int32_t* info) {
+    // (the checks of the plain arguments come before anything of *g is read, as in gmrf_dc_run: tests/test_gn_posterior_cpu.py
+    //  drives them without a device, with a driver pointer that must never be followed -- keep them above the first g->)
+    if (!g) return bad_shape("null pointer");
+    if (info) *info = 0;
+    if (k_samples < 0 || k_samples > KP_CHUNK) return bad_shape("k_samples in [0, 128]");
+    if (samples_out && k_samples == 0) return bad_shape("samples_out with k_samples = 0");
+    const bool sampled = var_method == GMRF_VAR_RBMC || var_method == GMRF_VAR_MC;
+    if (var_method != -1 && var_method != GMRF_VAR_EXACT && !sampled) return bad_shape("var_method: -1 (none), exact, RBMC or MC");
+    if (sampled && k_var <= 0) return bad_shape("k_var <= 0");
+    if (var_method == -1 && (std_out || std_norm_out)) return bad_shape("std_out / std_norm_out without a variance method");
+    if (!z && (sqmahal_out || nll_out || errors_out)) return bad_shape("sqmahal_out / nll_out / errors_out without z");
+    if (first < 0) return bad_shape("first < 0");
+    if (!g->have_x || g->B != g->h->B) { g_last_error = "gmrf_gn_posterior: no run on this batch"; return GMRF_ERR_NO_FACTOR; }
+    GCHK(gn_bound_ok(g));
+    gmrf_handle* h = g->h;
+    gmrf_assembler* as = g->as;
+    const int64_t B = g->B, n = as->n;
+    if (errors_out && first >= n) return bad_shape("the elements [first, n) must not be empty");
+    HIPCHK(hipSetDevice(h->device));
+    hipStream_t st = h->stream;
+    const bool want_sq = sqmahal_out || nll_out, want_ld = logdet_out || nll_out;
+    GCHK(gn_post_alloc(g, B, k_samples));
+    if (var_method == GMRF_VAR_RBMC) GCHK(driver_pattern_csr(g));
+    if (want_sq) GCHK(quadform_ready(as));
+    const double* d_z;
+    Staging args(g->in);
+    args.in(z, sizeof(double) * B * n, &d_z);
+    GCHK(args.commit(st));
+    // 1: the factor at the final iterate
+    const gmrf_status status = gn_factor_final(g, info);
+    if (status != GMRF_OK) { (void)hipStreamSynchronize(st); return status; }      // (the outputs are untouched)
+    // 2 - 3: samples around the iterate (nothing is solved for the mean), variances on the values just assembled, std and |std|
+    if (k_samples > 0) GCHK(gmrf_bt_sample(h, sample_seed, 0, k_samples, g->d_x, nullptr, g->d_smp, n));
+    GCHK(driver_variances(g, var_method, k_var, var_seed, g->d_a, g->d_diag, g->d_var));
+    if (var_method != -1) GCHK(driver_std_norm(g, g->d_var, g->d_spart, g->d_norm));
+    // 4: scores
+    if (want_ld) GCHK(logdet_batch_enqueue(h, g->d_ld));
+    if (want_sq) GCHK(launch_quadform_batch(as, st, B, g->d_a, as->nnz_out, g->d_x, d_z, g->d_spart, g->d_sq));
+    if (nll_out) {
+        hipLaunchKernelGGL(nll_batch, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, (double)n, std::log(2.0 * M_PI), g->d_sq, g->d_ld, B,
+                           g->d_nll);
+        HIPCHK(hipGetLastError());
+    }
+    // 5: errors of the iterate against z over [first, n)
+    if (errors_out) GCHK(launch_field_errors_batch(st, B, n, first, g->d_x, d_z, g->d_epart, g->d_err));
+    // 6
+    GCHK(copy_out(st, samples_out, g->d_smp, sizeof(double) * B * k_samples * n));
+    GCHK(copy_out(st, std_out, g->d_var, sizeof(double) * B * n));
+    GCHK(copy_out(st, std_norm_out, g->d_norm, sizeof(double) * B));
+    GCHK(copy_out(st, logdet_out, g->d_ld, sizeof(double) * B));
+    GCHK(copy_out(st, sqmahal_out, g->d_sq, sizeof(double) * B));
+    GCHK(copy_out(st, nll_out, g->d_nll, sizeof(double) * B));
+    GCHK(copy_out(st, errors_out, g->d_err, sizeof(double) * B * 3));
+    HIPCHK(hipStreamSynchronize(st));
+    return GMRF_OK;
 }
 
 // --------------------------------------------------------------------------------- shallow-water element kernels

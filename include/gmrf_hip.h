@@ -233,6 +233,13 @@ gmrf_status gmrf_bt_var_accumulate(gmrf_handle* h, int32_t method, int64_t first
 
 /* logdet(A) = 2 sum_i sum_j log (L_i)_jj. */
 gmrf_status gmrf_bt_logdet(gmrf_handle* h, double* out);
+/* logdet of EVERY problem of the handle in one call (the per-problem `logdet(x_final)` of the data-set loops,
+ * scripts/burgers/solve_burgers_gmrf-collocation.jl:262): out [B], host or device.  Problem p gets the bits of gmrf_bt_logdet
+ * after gmrf_bt_select_problem(h, p): the same per-block parts (from the resident L blocks, else what the factorisation left), added
+ * in block order by one thread per problem and doubled.  One launch or two and one synchronisation instead of B round trips.
+ * GMRF_ERR_BAD_SHAPE on a handle in the twisted order, GMRF_ERR_NO_FACTOR before a factorisation or for a factor adopted
+ * without its L blocks. */
+gmrf_status gmrf_bt_logdet_batch(gmrf_handle* h, double* out);
 
 /* ------------------------------------------------------------------ factor access
  * Copy one dense block of the factor to `out` (block_size x block_size, column-major,
@@ -626,6 +633,14 @@ gmrf_status gmrf_assemble_rhs_batch(gmrf_assembler* as, int64_t batch, const dou
 gmrf_status gmrf_assemble_objective_batch(gmrf_assembler* as, int64_t batch, const double* q_nzval, int64_t q_stride,
                                           const double* x_prior, const double* x, const double* obs_diff, double noise,
                                           double* obj_out);
+/* out[p] = (z_p - x_p)' A_p (z_p - x_p): `sqmahal(x_final, z)` of scripts/burgers/solve_burgers_gmrf-collocation.jl:208-215 for a
+ * batch, with A_p the symmetric matrix on the assembler's OUTPUT pattern (gmrf_assemble_pattern: nnz_out entries, both triangles,
+ * in that order) and the values a_nzval[p] -- what gmrf_assemble_precision_batch wrote.  a_stride: 0 = one value array for every
+ * problem, nnz_out = one per problem.  x, z [batch][n], out [batch]; every pointer host or device.  One pass over the values,
+ * z - x formed as it is read; summed over a fixed partition of the columns (it depends on n only) without atomics: the same bits on
+ * every call and in every batch.  Needs n < 2^31. */
+gmrf_status gmrf_assemble_quadform_batch(gmrf_assembler* as, int64_t batch, const double* a_nzval, int64_t a_stride,
+                                         const double* x, const double* z, double* out);
 /* The driver binds a handle (reference order; its batch B is the number of problems), an assembler and a Burgers tangent that
  * live on ONE device and ONE stream (create the three with the same stream argument); anything else is GMRF_ERR_BAD_SHAPE.
  * gmrf_gn_run: the handle must have factored the assembler's pattern once (GMRF_ERR_NO_FACTOR before the first analysis,
@@ -646,6 +661,28 @@ gmrf_status gmrf_gn_run(gmrf_gn* g, const double* q_nzval, int64_t q_stride, con
                         double* x, const double* y, double noise, double rtol, int32_t max_steps, int32_t* steps_out,
                         double* obj_hist_out, int32_t* info);
 gmrf_status gmrf_gn_finalize(gmrf_gn* g, int32_t* info);
+/* The posterior stage of the data-set loops on the final iterate (x_final of solve_burgers_gmrf-fem.jl:184-208, collocation
+ * :248-263, the final GMRF of _research/elliptic_chen24.jl) for the batch of the last gmrf_gn_run (GMRF_ERR_NO_FACTOR without
+ * one, as gmrf_gn_finalize), every tangent the driver serves.  One call, on the handle's stream:
+ *     what gmrf_gn_finalize does (tangent at x, A = Q + noise J'J with the run's noise, gmrf_bt_refactor_values) ->
+ *     k_samples samples x_p + L_p^-T z (gmrf_bt_sample with the iterate as the mean, the sample ids of a batch: problem p, sample
+ *     s = p k_samples + s; k_samples in [0, 128]) ->
+ *     variances (var_method -1: none; GMRF_VAR_EXACT; GMRF_VAR_RBMC / GMRF_VAR_MC with k_var samples, problem p drawing the ids
+ *     p k_var .. p k_var + k_var - 1 like gmrf_bt_marginal_var_batch, on the values of A just assembled; the stage capped by
+ *     GMRF_VAR_STAGE_MB as in gmrf_dc_run) -> std = sqrt(var) and |std_p|_2 ->
+ *     logdet_p (gmrf_bt_logdet_batch), sqmahal_p = (z_p - x_p)' A_p (z_p - x_p) (gmrf_assemble_quadform_batch on the values of A),
+ *     nll_p = 0.5 * ((n * log(2 pi) + sqmahal_p) - logdet_p), each operation rounded on its own (:208-215, :262-263) ->
+ *     errors_p = (rel_err, rmse, max_err) of x_p against z_p over the elements [first, n) (gmrf_field_errors_batch; first = ns skips
+ *     the first slice as the scripts' [2:end, :] does).
+ * Every step is the public call named, on the driver's device buffers: the results are bitwise those of the calls made one after
+ * the other.  z [B][n]: the reference solution's dofs, host or device, or NULL -- then sqmahal_out, nll_out and errors_out must be
+ * NULL (GMRF_ERR_BAD_SHAPE).  Outputs, each NULL (not wanted), host or device: samples_out [B][k_samples][n], std_out [B][n],
+ * std_norm_out [B], logdet_out [B], sqmahal_out [B], nll_out [B], errors_out [B][3].  GMRF_ERR_NOT_SPD ends the call with `info`
+ * as gmrf_bt_refactor_values sets it and leaves every output untouched.  The handle is left holding the factor, as after
+ * gmrf_gn_finalize; a later gmrf_gn_run does not see that the stage ran. */
+gmrf_status gmrf_gn_posterior(gmrf_gn* g, const double* z, int64_t first, int64_t k_samples, uint64_t sample_seed, int32_t var_method,
+                              int64_t k_var, uint64_t var_seed, double* samples_out, double* std_out, double* std_norm_out,
+                              double* logdet_out, double* sqmahal_out, double* nll_out, double* errors_out, int32_t* info);
 
 /* The "Prior" and "Initial condition" stages of the Burgers data-set loop (solve_burgers_gmrf-fem.jl:154-179) for a batch, on
  * the handle and the analysis gmrf_gn_run uses afterwards.  The driver binds a handle (reference order; its batch B is the

@@ -32,7 +32,7 @@ using SparseArrays, LinearAlgebra
 export TridiagonalCholeskyFactor, tridiagonal_cholesky, forward_solve, backward_solve, ldiv, PosteriorAssembler, GmrfCsr,
        GmrfComm, DarcyP1Assembler, BurgersP1Tangent, BurgersCollocationTangent, EllipticP1Tangent, elliptic_load!, GaussNewtonBatch, gauss_newton_batch!, DarcyConditioningBatch,
        BurgersP1Prior, BurgersLinePrior, prior_values_batch!, BurgersInitialConditionBatch, initial_condition_batch, solution_errors_batch,
-       condition_on_observations_batch, assemble_batch!
+       condition_on_observations_batch, assemble_batch!, logdet_batch, quadform_batch!, posterior!
 
 const libgmrf = get(ENV, "LIBGMRF_HIP", joinpath(@__DIR__, "..", "diffeqgmrfs.jl_amd", "csrc", "libgmrf_hip.so"))
 
@@ -342,6 +342,13 @@ function LinearAlgebra.logdet(F::TridiagonalCholeskyFactor)
     return v[]
 end
 
+"logdet of every problem of a batch in one call; entry p is bitwise `logdet(select_problem!(F, p - 1))`."
+function logdet_batch(F::TridiagonalCholeskyFactor)
+    out = Vector{Float64}(undef, F.batch)
+    GC.@preserve out check(ccall((:gmrf_bt_logdet_batch, libgmrf), Int32, (Ptr{Cvoid}, Ptr{Float64}), F.handle, out))
+    return out
+end
+
 # --- factor image: checkpoint / resume, and all of F.chos / F.Cs in one call
 function export_factor(F::TridiagonalCholeskyFactor)
     nbytes = Ref{Int64}(0)
@@ -503,6 +510,15 @@ function objective_batch!(out::Vector{Float64}, as::PosteriorAssembler, q_nzval:
     GC.@preserve out q_nzval x_prior x obs_diff check(ccall((:gmrf_assemble_objective_batch, libgmrf), Int32,
         (Ptr{Cvoid}, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Float64, Ptr{Float64}),
         as.handle, size(x, 2), q_nzval, q_stride, x_prior, x, obs_diff, Float64(noise), out))
+    return out
+end
+
+"out[p] = (z_p - x_p)' A_p (z_p - x_p) with A_p's values on `as.pattern` (`sqmahal`, solve_burgers_gmrf-collocation.jl:208-215), a fixed-shape sum"
+function quadform_batch!(out::Vector{Float64}, as::PosteriorAssembler, a_nzval::VecOrMat{Float64}, x::Matrix{Float64}, z::Matrix{Float64})
+    a_stride = a_nzval isa Matrix ? size(a_nzval, 1) : 0
+    GC.@preserve out a_nzval x z check(ccall((:gmrf_assemble_quadform_batch, libgmrf), Int32,
+        (Ptr{Cvoid}, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+        as.handle, size(x, 2), a_nzval, a_stride, x, z, out))
     return out
 end
 
@@ -733,6 +749,36 @@ function finalize!(gn::GaussNewtonBatch)
     info = Ref{Int32}(0)
     check(ccall((:gmrf_gn_finalize, libgmrf), Int32, (Ptr{Cvoid}, Ref{Int32}), gn.handle, info), info[])
     return gn.F
+end
+
+"""
+    posterior!(gn; z = nothing, first = 0, k_samples = 1, var = :rbmc, k_var = 50, sample_seed = 0x5EED, var_seed = 0x5EED)
+
+Everything `solve_problem` returns for the final iterate of the last `gauss_newton_batch!`, in one call on the device: `finalize!`,
+samples (n x k_samples x B), std (n x B) and norm(std) (B), logdet (B) and -- with `z` (n x B), the reference solution's dofs --
+sqmahal (B), nll (B) and errors (3 x B) = (rel_err, rmse, max_err) over the elements first + 1 : n.  Returns a named tuple; what
+the call does not produce is `nothing`.
+"""
+function posterior!(gn::GaussNewtonBatch; z::Union{Nothing,Matrix{Float64}} = nothing, first::Integer = 0, k_samples::Integer = 1,
+                    var::Symbol = :rbmc, k_var::Integer = 50, sample_seed::Integer = 0x5EED, var_seed::Integer = 0x5EED)
+    B = gn.F.batch; n = size(gn.as.pattern, 1)
+    method = Dict(:none => -1, :exact => 0, :rbmc => 1, :mc => 2)[var]
+    samples = k_samples > 0 ? Array{Float64,3}(undef, n, k_samples, B) : nothing
+    sd = method >= 0 ? Matrix{Float64}(undef, n, B) : nothing
+    nrm = method >= 0 ? Vector{Float64}(undef, B) : nothing
+    ld = Vector{Float64}(undef, B)
+    sq = z === nothing ? nothing : Vector{Float64}(undef, B)
+    nl = z === nothing ? nothing : Vector{Float64}(undef, B)
+    errs = z === nothing ? nothing : Matrix{Float64}(undef, 3, B)
+    p(a) = a === nothing ? Ptr{Float64}(C_NULL) : pointer(a)
+    info = Ref{Int32}(0)
+    st = GC.@preserve z samples sd nrm ld sq nl errs ccall((:gmrf_gn_posterior, libgmrf), Int32,
+        (Ptr{Cvoid}, Ptr{Float64}, Int64, Int64, UInt64, Int32, Int64, UInt64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{Int32}),
+        gn.handle, p(z), first, k_samples, UInt64(sample_seed), Int32(method), k_var, UInt64(var_seed), p(samples), p(sd), p(nrm), p(ld),
+        p(sq), p(nl), p(errs), info)
+    check(st, info[])
+    return (samples = samples, std = sd, std_norm = nrm, logdet = ld, sqmahal = sq, nll = nl, errors = errs)
 end
 
 # The Darcy data-set loop (scripts/darcy/solve_darcy_gmrf-fem.jl:176-198) for a batch of problems in one call on the device.

@@ -48,8 +48,8 @@ EXPORTS = [
     "gmrf_burgers_prior_create", "gmrf_burgers_line_prior_create", "gmrf_burgers_prior_destroy", "gmrf_burgers_prior_pattern", "gmrf_burgers_prior_values_batch",
     "gmrf_bic_create", "gmrf_bic_destroy", "gmrf_bic_run", "gmrf_field_errors_batch",
     "gmrf_bt_logdet_batch", "gmrf_assemble_quadform_batch", "gmrf_gn_posterior",
-    "gmrf_test_gemm", "gmrf_test_gemm_desc", "gmrf_test_gemm_pair", "gmrf_test_gemm_rate", "gmrf_test_gemm_shapes", "gmrf_test_potrf_tile", "gmrf_test_potrf_block", "gmrf_test_potrf_route", "gmrf_test_tile_timing", "gmrf_test_persist_stamps", "gmrf_test_persist_aborts", "gmrf_test_factor_fwd", "gmrf_test_gn_route", "gmrf_test_dc_route", "gmrf_test_bic_route", "gmrf_test_var_groups", "gmrf_test_persist_budget", "gmrf_test_clock_probe_start", "gmrf_test_clock_probe_finish",
-    "gmrf_test_mfma_f64_rate", "gmrf_test_hbm_rate", "gmrf_test_microbench", "gmrf_test_symbolic_csc",
+    "gmrf_test_gemm", "gmrf_test_gemm_desc", "gmrf_test_gemm_env", "gmrf_test_envelope", "gmrf_test_gemm_pair", "gmrf_test_gemm_rate", "gmrf_test_gemm_shapes", "gmrf_test_potrf_tile", "gmrf_test_potrf_block", "gmrf_test_potrf_route", "gmrf_test_tile_timing", "gmrf_test_persist_stamps", "gmrf_test_persist_aborts", "gmrf_test_factor_fwd", "gmrf_test_gn_route", "gmrf_test_dc_route", "gmrf_test_bic_route", "gmrf_test_var_groups", "gmrf_test_persist_budget", "gmrf_test_clock_probe_start", "gmrf_test_clock_probe_finish",
+    "gmrf_test_mfma_f64_rate", "gmrf_test_hbm_rate", "gmrf_test_microbench", "gmrf_test_symbolic_csc", "gmrf_test_envelope_csc",
 ]
 
 
@@ -226,6 +226,8 @@ def load() -> C.CDLL:
         "gmrf_test_gemm": [i32, i64, i64, i64, i32, i32, i32, i32, dbl, vp, i64, vp, i64, dbl, vp, i64],
         "gmrf_test_gemm_shapes": [vp, P(dbl), i64, P(i64)],
         "gmrf_test_gemm_desc": [i32, i32, vp, vp] + [vp, i64] * 12 + [P(i32)],
+        "gmrf_test_gemm_env": [i32, i32, vp, vp] + [vp, i64] * 11 + [i32, P(i32)],
+        "gmrf_test_envelope": [vp, vp, vp, i64, P(i64), P(i32)],
         "gmrf_test_gemm_pair": [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp],
         "gmrf_test_gemm_rate": [i32, i64, i64, i64, i32, i32, i32, i32, i32, i32, P(dbl)],
         "gmrf_test_potrf_tile": [i32, vp, vp, P(i32)],
@@ -246,6 +248,7 @@ def load() -> C.CDLL:
         "gmrf_test_hbm_rate": [i32, i64, P(dbl)],
         "gmrf_test_microbench": [i32, vp, i32],
         "gmrf_test_symbolic_csc": [i64, i64, vp, vp, i32, vp],
+        "gmrf_test_envelope_csc": [i64, i64, vp, vp, i32, vp, vp, vp, i64, P(i64)],
     }
     for name, args in sigs.items():
         fn = getattr(lib, name)

@@ -1501,6 +1501,18 @@ class TridiagonalCholeskyFactor:
         return [dict({k: int(r[i]) for i, k in enumerate(names)}, launches=int(r[8]), ms=float(r[9]), flops=float(r[10]))
                 for r in buf[: int(n.value)]]
 
+    def envelope(self):
+        """The envelope bounds of the analysed pattern (test hook gmrf_test_envelope): (lo, hi, state), lo / hi int32 arrays
+        [n_blocks][padded block size / 64] of in-block columns (None where the blocks are no multiple of 256), state 0 none,
+        1 trivial for every panel, 2 in use."""
+        n, state = C.c_int64(0), C.c_int32(0)
+        _cabi.check(self._lib.gmrf_test_envelope(self._h, None, None, 0, C.byref(n), C.byref(state)))
+        if n.value == 0:
+            return None, None, int(state.value)
+        lo, hi = np.zeros(n.value, np.int32), np.zeros(n.value, np.int32)
+        _cabi.check(self._lib.gmrf_test_envelope(self._h, _cabi.ptr(lo), _cabi.ptr(hi), n.value, C.byref(n), C.byref(state)))
+        return lo, hi, int(state.value)
+
     def set_profiling(self, level: int):
         _cabi.check(self._lib.gmrf_bt_set_profiling(self._h, level))
 

@@ -66,6 +66,10 @@ struct GemmArgs {
     const int* kb_m = nullptr;
     const int* kb_n = nullptr;
     const int* ke_n = nullptr;
+    // (round 19) upper K bound per 64-row tile of A, the mirror of kb_m: row tile t of A is zero from column ke_m[t] on.  Only the
+    // LDS-DMA kernels (gemm_f64_dma.hpp) read it -- there the parts of a wider tile need not be monotone: it starts at the smallest
+    // of its parts' lower bounds and ends at the largest of their upper ones.  A hint: gemm() drops it in front of any other kernel.
+    const int* ke_m = nullptr;
     // Tail row of gemm_f64_dma's TAIL variant on operands of its own (tC != nullptr; one problem per z, nb1 == 1):
     //   tC[n] = tbeta * tD[n] + alpha * sum_k tA[k] b(k,n)   per problem at tA + z ptA, tC + z ptC, tD + z ptD (tD null: tD = tC)
     // over the K range of the tile that carries it.  tC == nullptr: the tail is row M of A / C / D.

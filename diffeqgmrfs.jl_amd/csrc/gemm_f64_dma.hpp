@@ -141,9 +141,12 @@ __device__ __forceinline__ void gemm_dma_body(const GemmArgs& g, const int bid, 
     if (g.tri & TRI_B_UPPER) ke = min(ke, n0 + BN);
     // staircase bounds are kept per 64-wide tile and are monotone: a wider tile starts at its first part's bound and
     // ends at its last part's (the parts' own zero ranges hold real zeros)
-    if (g.kb_m) kb = max(kb, g.kb_m[bm * (BM / 64)]);
-    if (g.kb_n) kb = max(kb, g.kb_n[bn * (BN / 64)]);
+    // (round 19: the envelope bounds of potrf_block need not be monotone -- a wider tile takes the smallest start of its parts,
+    // which is the first part's for a staircase, and the largest ke_m)
+    if (g.kb_m) kb = max(kb, BM > 64 ? min(g.kb_m[bm * (BM / 64)], g.kb_m[bm * (BM / 64) + BM / 64 - 1]) : g.kb_m[bm]);
+    if (g.kb_n) kb = max(kb, BN > 64 ? min(g.kb_n[bn * (BN / 64)], g.kb_n[bn * (BN / 64) + BN / 64 - 1]) : g.kb_n[bn]);
     if (g.ke_n) ke = min(ke, g.ke_n[bn * (BN / 64) + BN / 64 - 1]);
+    if (g.ke_m) ke = min(ke, BM > 64 ? max(g.ke_m[bm * (BM / 64)], g.ke_m[bm * (BM / 64) + BM / 64 - 1]) : g.ke_m[bm]);
     const int nkt = (ke > kb) ? (ke - kb) / BK : 0;
 
     extern __shared__ __attribute__((aligned(16))) double gsm[];
@@ -479,7 +482,7 @@ inline int gemm_dma_shape(bool a_t, const GemmArgs& g, int batch) {
     // The wide tiles pay on full products only (1024^3 x 16: 65 - 69 TF/s against 61 - 64 with 64 x 64 tiles); on the factor's
     // triangular / lower-only / staircase launches their idle quadrants and longer tails lose what the fewer fragment reads gain
     // (tools/gemm_dma_rate.py: G2 304 us against 280 us, rank-256 update of 768^2 101 against 88 us).
-    const bool plain = !g.lower_only && !g.tri && !g.kb_m && !g.kb_n && !g.ke_n;
+    const bool plain = !g.lower_only && !g.tri && !g.kb_m && !g.kb_n && !g.ke_n && !g.ke_m;
     const int64_t t64 = (int64_t)(g.M / 64) * (g.N / 64) * batch;
     if (policy >= 3 || (plain && t64 >= 2048)) {
         if (g.M % 128 == 0) return 2;
@@ -517,7 +520,7 @@ inline bool gemm_tail_ok(bool a_t, bool b_n, const GemmArgs& g, int batch) {
     if (g.dout && g.nb1 != 1) return false;
     // (a direct output: EVERY row tile sums the tail row, so the tail must not read C and must share every tile's K range)
     // (TRI_A_* give the row tiles of one column tile different K ranges; TRI_B_* do not)
-    if (g.dout && (g.beta != 0.0 || g.kb_m || g.kb_n || g.ke_n || (g.tri & (TRI_A_LOWER | TRI_A_UPPER)))) return false;
+    if (g.dout && (g.beta != 0.0 || g.kb_m || g.kb_n || g.ke_n || g.ke_m || (g.tri & (TRI_A_LOWER | TRI_A_UPPER)))) return false;
     // 32-bit byte offsets inside a problem's operand for the M + 1 rows (A: row M read with 64-bit addressing)
     return (int64_t)(g.M + 1) * g.ldc * 8 < ((int64_t)1 << 32) && (!g.D || (int64_t)(g.M + 1) * g.ldd * 8 < ((int64_t)1 << 32));
 }

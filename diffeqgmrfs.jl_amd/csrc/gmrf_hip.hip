@@ -177,6 +177,19 @@ struct gmrf_handle {
     double c_streamed = 0.0;           // doubles of one C_i inside the staircase (what a k = 1 sweep reads)
     double g2_tile_k = 0.0;            // sum over lower tiles of the K extent of S = -C C^T (flop accounting)
     bool c_dirty = false;              // C must be re-zeroed (new pattern)
+    // (round 19) Envelope of the rows of a Schur block that S = D_i - C C^T leaves as D_i's (build_symbolic: env_lo / env_hi, in-block
+    // columns per block and 64-row tile) and what potrf_block passes of it per block i and 256-column panel p, relative to the panel:
+    // env_host / d_env[((i np + p) 4 + a) nt + bm], bm = row tile below the panel; a = 0: kb (row tile bm of L[below, P] is zero left
+    // of it), 1: ke (row tile bm of S[below, P] is zero from it on), 2 / 3: kb / ke with the LAST row tile's trivial (it carries a tail
+    // row of operands of its own).  env_has[i np + p]: bit 0 some kb > 0, bit 1 some kb > 0 or ke < 256, bit 2 the same for a = 2 / 3.
+    // d_env_ken[4 i + bn]: row tiles of L[256:, 0:256] that column tile bn meets, as a K end (the backward sweep's L_ba^T product).
+    std::vector<int> env_lo, env_hi, env_host, env_ken;
+    std::vector<unsigned char> env_has, env_ken_has;
+    int* d_env = nullptr;
+    int* d_env_ken = nullptr;
+    bool env_ok = false;               // the arrays above describe the analysed pattern and the current layout
+    bool no_env = false;               // set_eager bit 21: no envelope bounds (comparison)
+    bool tw_half = false;              // a half of a twisted handle: never takes them
     int* d_lo_rowptr = nullptr;
     int* d_dg_rowptr = nullptr;       // [N][bsp + 1]: the diagonal blocks' entries row by row (absolute positions in d_keys)
     // tile plan of the sparse C = B X^T (spmm_bxt_tiles): per lower block and 64-row tile the distinct columns, per entry its index into them
@@ -440,7 +453,9 @@ static gmrf_status gemm(gmrf_handle* h, bool a_t, bool b_n, int M, int N, int K,
                         int batch = 1, int64_t sA = 0, int64_t sB = 0, int64_t sC = 0, const double* D = nullptr,
                         int64_t ldd = 0, int64_t pD = 0, int pclass = 0, double pwork = -1.0,
                         const int* kb_m = nullptr, const int* kb_n = nullptr, const int* ke_n = nullptr, bool tail = false,
-                        const GemmTail* gt = nullptr) {
+                        const GemmTail* gt = nullptr, const int* ke_m = nullptr, bool hints = false) {
+    // ke_m: upper K bound per row tile of A (GemmArgs::ke_m, the LDS-DMA kernels only).  hints: the K bounds of this call are optional
+    // (the operands hold real zeros outside them) -- a launch that another kernel family takes gets none of them, and ke_m never
     GemmArgs g;
     if (gt) {
         if (gt->C) { g.tA = gt->A; g.ptA = gt->pA; g.tC = gt->C; g.ptC = gt->pC; g.tD = gt->D; g.ptD = gt->pD; g.tbeta = gt->beta; }
@@ -455,6 +470,11 @@ static gmrf_status gemm(gmrf_handle* h, bool a_t, bool b_n, int M, int N, int K,
     g.pA = pA; g.pB = pB; g.pC = pC; g.nb1 = batch;
     g.M = M; g.N = N; g.K = K; g.tri = tri; g.lower_only = lower_only;
     g.alpha = alpha; g.beta = beta; g.stamps = nullptr;
+    g.ke_m = ke_m;
+    if ((ke_m || hints) && (gemm_uses_big(a_t, g, batch * (int)h->B) || gemm_uses_ll(g, batch * (int)h->B) || !gemm_uses_dma(a_t, g, batch * (int)h->B))) {
+        g.ke_m = ke_m = nullptr;
+        if (hints) { g.kb_m = kb_m = nullptr; g.kb_n = kb_n = nullptr; g.ke_n = ke_n = nullptr; pwork = -1.0; }
+    }
     double flops = gemm_flops(M, N, K, tri, lower_only, batch * (double)h->B);
     if (tail) {
         // one more row, row M of A / C (gemm_f64_dma's TAIL): the kernel the M rows alone would get, or not at all.  A dry run
@@ -472,7 +492,7 @@ static gmrf_status gemm(gmrf_handle* h, bool a_t, bool b_n, int M, int N, int K,
             EvPair p;
             p.kind = pclass; p.work = pwork >= 0.0 ? pwork : flops;
             p.a = ev_get(h); p.b = ev_get(h);
-            const int64_t key[8] = {pclass, M + 1, N, K, tri, lower_only, batch * h->B, (kb_m || kb_n || ke_n) ? 1 : 0};
+            const int64_t key[8] = {pclass, M + 1, N, K, tri, lower_only, batch * h->B, (kb_m || kb_n || ke_n || ke_m) ? 1 : 0};
             p.shape = gemm_shape_row(h, key);
             (void)gemm_try_dma_tail(h->gemm_stream ? h->gemm_stream : h->stream, a_t, b_n, g, batch * (int)h->B, p.a, p.b, &e);
             HIPCHK(e);
@@ -496,7 +516,7 @@ static gmrf_status gemm(gmrf_handle* h, bool a_t, bool b_n, int M, int N, int K,
         EvPair p;
         p.kind = pclass; p.work = pwork >= 0.0 ? pwork : flops;
         p.a = ev_get(h); p.b = ev_get(h);
-        const int64_t key[8] = {pclass, M, N, K, tri, lower_only, batch * h->B, (kb_m || kb_n || ke_n) ? 1 : 0};
+        const int64_t key[8] = {pclass, M, N, K, tri, lower_only, batch * h->B, (kb_m || kb_n || ke_n || ke_m) ? 1 : 0};
         p.shape = gemm_shape_row(h, key);
         HIPCHK(launch_gemm(h->gemm_stream ? h->gemm_stream : h->stream, a_t, b_n, g, batch * (int)h->B, p.a, p.b));
         h->events.push_back(p);
@@ -577,6 +597,7 @@ static gmrf_status set_layout(gmrf_handle* h, int64_t cmin, int64_t rmax, const 
     destroy_graphs(h);
     h->cmin = cmin; h->rmax = rmax;
     h->layout_gen++;
+    h->env_ok = false;                                        // (the envelope bounds belong to the analysed pattern's layout: upload_envelope)
     h->kst.assign((size_t)ntile, 0);
     int64_t run = bsp - 64;                                   // envelope from the bottom: kst[t] = min over t' >= t
     for (int t = nrt - 1; t >= 0; --t) {
@@ -759,7 +780,40 @@ struct SymbolicPlan {
     std::vector<uint16_t> lidx;
     int ecap = 0, nrt = 0;
     std::vector<int> drowptr;          // [N][bsp + 1]: a diagonal block's entries row by row
+    // (round 19) [N][bsp / 64], in-block columns: the rows of S_i = D_i - C C^T that the product does not write (all of block 0, rows
+    // >= rmax otherwise) keep D_i's sparsity until a panel they meet has been eliminated.  env_lo: the smallest column of D_i in the
+    // tile's rows (the diagonal counts), rounded down to 64 -- L is zero left of it (envelope theorem).  env_hi: the largest column
+    // + 1 of D_i in those rows INSIDE the 256-column panel of env_lo, rounded up to 64 (no earlier panel has touched the rows, so
+    // S[rows, panel] is still D_i's); the panel's end where the tile lies in that panel itself.  Other tiles: 0 and bsp.
+    std::vector<int> env_lo, env_hi;
 };
+
+static void build_envelope(int64_t N, int64_t bsp, const std::vector<std::vector<HostEntry>>& dg, int64_t rmax, SymbolicPlan& sp) {
+    const int nt = (int)(bsp / 64);
+    sp.env_lo.assign((size_t)(N * nt), 0);
+    sp.env_hi.assign((size_t)(N * nt), (int)bsp);
+    std::vector<int64_t> lo((size_t)nt), hi((size_t)nt);
+    for (int64_t i = 0; i < N; ++i) {
+        const int64_t rm = i > 0 ? rmax : 0;
+        for (int t = 0; t < nt; ++t) lo[(size_t)t] = 64 * (int64_t)t;
+        for (auto& e : dg[(size_t)i]) {
+            const int64_t r = (int64_t)(e.key >> 32), c = (int64_t)(e.key & 0xffffffffu);
+            lo[(size_t)(r / 64)] = std::min(lo[(size_t)(r / 64)], c);
+        }
+        for (int t = 0; t < nt; ++t) { lo[(size_t)t] = lo[(size_t)t] / 64 * 64; hi[(size_t)t] = 0; }
+        for (auto& e : dg[(size_t)i]) {
+            const int64_t r = (int64_t)(e.key >> 32), c = (int64_t)(e.key & 0xffffffffu);
+            const int64_t p0 = lo[(size_t)(r / 64)] / 256 * 256;
+            if (c >= p0 && c < p0 + 256) hi[(size_t)(r / 64)] = std::max(hi[(size_t)(r / 64)], c + 1);
+        }
+        for (int t = 0; t < nt; ++t) {
+            if (64 * (int64_t)t < rm) continue;
+            const int64_t p0 = lo[(size_t)t] / 256 * 256;
+            sp.env_lo[(size_t)(i * nt + t)] = (int)lo[(size_t)t];
+            sp.env_hi[(size_t)(i * nt + t)] = (int)((64 * (int64_t)t < p0 + 256) ? std::min(p0 + 256, bsp) : (hi[(size_t)t] + 63) / 64 * 64);
+        }
+    }
+}
 
 static void build_symbolic(int64_t N, int64_t bsp, const std::vector<std::vector<HostEntry>>& dg,
                            const std::vector<std::vector<HostEntry>>& lo, bool no_staircase, SymbolicPlan& sp, bool group_tiles = true) {
@@ -796,6 +850,7 @@ static void build_symbolic(int64_t N, int64_t bsp, const std::vector<std::vector
         if (no_staircase) std::fill(first.begin(), first.end(), cmin);
         sp.cmin = cmin; sp.rmax = rmax; sp.first = first;
     }
+    build_envelope(N, bsp, dg, sp.rmax, sp);
     // row pointers into the lower blocks' entry lists for the sparse C = B X^T (spmm_bxt)
     sp.rowptr.assign((size_t)(N * (bsp + 1)), 0);
     int64_t max_row = 0;
@@ -890,6 +945,71 @@ static void build_symbolic(int64_t N, int64_t bsp, const std::vector<std::vector
     }
 }
 
+// (round 19) What potrf_block and the backward sweep pass of the envelope (gmrf_handle::env_host), per block and 256-column panel
+// (gmrf_handle::env_host / env_ken / env_has / env_ken_has; any: some panel of some block has a non-trivial bound)
+struct EnvHost { std::vector<int> host, ken; std::vector<unsigned char> has, ken_has; bool any = false; };
+// (host only: gmrf_test_envelope_csc reaches it without a device)
+static void derive_envelope(int64_t N, int64_t bsp, const SymbolicPlan& sp, EnvHost& o) {
+    const int nt = (int)(bsp / 64), np = nt / 4;
+    auto& env_host = o.host; auto& env_has = o.has; auto& env_ken = o.ken; auto& env_ken_has = o.ken_has;
+    env_host.assign((size_t)(N * np * 4 * nt), 0);
+    env_has.assign((size_t)(N * np), 0);
+    env_ken.assign((size_t)(N * 4), 0);
+    env_ken_has.assign((size_t)N, 0);
+    bool any = false;
+    for (int64_t i = 0; i < N; ++i)
+        for (int p = 0; p < np; ++p) {
+            const int oa = 256 * p, m3 = nt - 4 * p - 4;
+            int* a = env_host.data() + (size_t)((i * np + p) * 4) * nt;
+            unsigned char has = 0;
+            for (int bm = 0; bm < m3; ++bm) {
+                const int t = 4 * p + 4 + bm, lo = sp.env_lo[(size_t)(i * nt + t)], hi = sp.env_hi[(size_t)(i * nt + t)];
+                const int kb = std::min(std::max(lo - oa, 0), 256);
+                const int ke = (lo >= oa && lo < oa + 256) ? std::min(std::max(hi - oa, kb), 256) : 256;
+                a[bm] = kb; a[nt + bm] = ke;
+                const bool last = bm == m3 - 1;
+                a[2 * nt + bm] = last ? 0 : kb; a[3 * nt + bm] = last ? 256 : ke;
+                if (kb > 0) has |= 1;
+                if (kb > 0 || ke < 256) has |= 2;
+                if (!last && (kb > 0 || ke < 256)) has |= 4;
+            }
+            for (int bm = m3; bm < nt; ++bm) { a[bm] = a[2 * nt + bm] = 0; a[nt + bm] = a[3 * nt + bm] = 256; }
+            env_has[(size_t)(i * np + p)] = has;
+            any = any || has;
+            if (p == 0 && m3 > 0) {
+                // column tile bn of L[256:, 0:256] is non-zero in row tile bm only where kb[bm] <= 64 bn
+                for (int bn = 0; bn < 4; ++bn) {
+                    int end = 0;
+                    for (int bm = 0; bm < m3; ++bm) if (a[bm] <= 64 * bn) end = 64 * (bm + 1);
+                    env_ken[(size_t)(i * 4 + bn)] = end;
+                    if (end < 64 * m3) env_ken_has[(size_t)i] = 1;
+                }
+            }
+        }
+    o.any = any;
+}
+static gmrf_status upload_envelope(gmrf_handle* h, const SymbolicPlan& sp) {
+    h->env_ok = false;
+    const int64_t N = h->N, bsp = h->bsp;
+    const int nt = (int)(bsp / 64);
+    if (N <= 0 || bsp % 256 != 0 || (int64_t)sp.env_lo.size() != N * nt) return GMRF_OK;
+    h->env_lo = sp.env_lo; h->env_hi = sp.env_hi;
+    EnvHost eh;
+    derive_envelope(N, bsp, sp, eh);
+    h->env_host.swap(eh.host); h->env_has.swap(eh.has); h->env_ken.swap(eh.ken); h->env_ken_has.swap(eh.ken_has);
+    const bool any = eh.any;
+    free_dev(h->d_env); free_dev(h->d_env_ken);
+    h->d_env = nullptr; h->d_env_ken = nullptr;
+    if (!any) return GMRF_OK;                                  // (no such structure: every launch as without the bounds)
+    HIPCHK(hipMalloc(&h->d_env, h->env_host.size() * sizeof(int)));
+    HIPCHK(hipMalloc(&h->d_env_ken, h->env_ken.size() * sizeof(int)));
+    HIPCHK(hipMemcpyAsync(h->d_env, h->env_host.data(), h->env_host.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->d_env_ken, h->env_ken.data(), h->env_ken.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->env_ok = true;
+    return GMRF_OK;
+}
+
 static gmrf_status upload_entries(gmrf_handle* h, const std::vector<std::vector<HostEntry>>& dg,
                                   const std::vector<std::vector<HostEntry>>& lo, int64_t nnz_in) {
     const int64_t N = h->N;
@@ -900,6 +1020,7 @@ static gmrf_status upload_entries(gmrf_handle* h, const std::vector<std::vector<
     h->diag_first = sp.diag_first; h->diag_count = sp.diag_count; h->low_first = sp.low_first; h->low_count = sp.low_count;
     const auto& keys = sp.keys; const auto& src = sp.src;
     GCHK(set_layout(h, sp.cmin, sp.rmax, sp.first));
+    GCHK(upload_envelope(h, sp));
     free_dev(h->d_keys); free_dev(h->d_vals); free_dev(h->d_src); free_dev(h->d_nz_stage);
     h->d_keys = nullptr; h->d_vals = nullptr; h->d_src = nullptr; h->d_nz_stage = nullptr;
     h->n_entries = (int64_t)keys.size();
@@ -1227,6 +1348,42 @@ static gmrf_status launch_persist(gmrf_handle* h, double* S, double* L, double* 
     return GMRF_OK;
 }
 
+// (round 19) The envelope bounds of block i's panel p for the panel product (pp_kb / pp_ke: GemmArgs::kb_m / ke_m) and the rank-256
+// update (upd_kb: kb_m and kb_n), null where the panel has none (or set_eager bit 21, one problem, a twisted order: the launches of
+// before), and the 64-wide K units the two launches then execute -- what their ProfScope books, as G2's g2_tile_k does.
+struct EnvPanel { const int* pp_kb; const int* pp_ke; const int* upd_kb; double units_pp, units_upd; };
+// 64-wide K units the panel product (rows a / a + 1 of a panel's four bound arrays: kb / ke) and the update (kb) execute
+static double env_units_pp(const int* host, int nt, int m3, int a) {
+    double u = 0.0;
+    for (int bm = 0; bm < m3; ++bm)
+        for (int bn = 0; bn < 4; ++bn) u += std::max(0, std::min(64 * (bn + 1), host[(a + 1) * nt + bm]) - host[a * nt + bm]) / 64;
+    return u;
+}
+static double env_units_upd(const int* host, int m3) {
+    double u = 0.0;
+    for (int bm = 0; bm < m3; ++bm)
+        for (int bn = 0; bn <= bm; ++bn) u += (256 - std::max(host[bm], host[bn])) / 64;
+    return u;
+}
+static EnvPanel env_panel(const gmrf_handle* h, int64_t i, int p, bool tail_rides) {
+    const int nt = (int)(h->bsp / 64), np = nt / 4, m3 = nt - 4 * p - 4;
+    EnvPanel e{nullptr, nullptr, nullptr, 10.0 * m3, 4.0 * (m3 * (m3 + 1) / 2)};
+    if (!h->env_ok || h->no_env || h->B <= 1 || h->tw || h->tw_half || h->tw_blk >= 0 || i < 0 || i >= h->N || p < 0 || p >= np || m3 <= 0) return e;
+    const size_t at = (size_t)((i * np + p) * 4) * nt;
+    const unsigned char has = h->env_has[(size_t)(i * np + p)];
+    const int* host = h->env_host.data() + at;
+    if (has & (tail_rides ? 4 : 2)) {
+        const int a = tail_rides ? 2 : 0;
+        e.pp_kb = h->d_env + at + (size_t)a * nt; e.pp_ke = h->d_env + at + (size_t)(a + 1) * nt;
+        e.units_pp = env_units_pp(host, nt, m3, a);
+    }
+    if (has & 1) {
+        e.upd_kb = h->d_env + at;
+        e.units_upd = env_units_upd(host, m3);
+    }
+    return e;
+}
+
 // fy (batches on the 256-column panel route, factor_fwd_ok): also y_i = L_i^-1 t into fy ([B][n_pad]: this block's part), t = d_ft
 static gmrf_status potrf_block(gmrf_handle* h, double* S, double* L, double* X, double* T, int blk_id, double* fy = nullptr) {
     const int bsp = (int)h->bsp;
@@ -1385,14 +1542,19 @@ static gmrf_status potrf_block(gmrf_handle* h, double* S, double* L, double* X, 
             const bool in_slot = (j == 0 && h->xsplit == 256 && !h->keep_l);
             double* Lb = in_slot ? X + oc * ld + oa : L + oc * ld + oa;
             const int64_t pLb = in_slot ? sa.pX : sa.pL;
+            // (round 19) Envelope bounds, relative to the panel (gmrf_handle::env_host): the rows below the panel that S = D_i - C C^T did
+            // not write and no earlier panel has met are still D_i's -- row tile bm of S[below, P] is zero outside [kb, ke), of
+            // L[below, P] left of kb.  The products skip those K ranges (sums of 0 x: the same bits); a panel product whose last row
+            // tile carries the forward solve's tail row keeps that tile's full range (the tail's own).
+            const EnvPanel ev = env_panel(h, blk_id - 1, j / 4, fy != nullptr);
             // L[below, P] = S[below, P] X_P^T: b(k, n) = X_P[n][k], zero for k > n (tile-K units: 1 + 2 + 3 + 4 of 16)
             GCHK(gemm(h, false, false, 64 * m3, 256, 256, TRI_B_UPPER, 0, 1.0, S + oc * ld + oa, ld, X + oa * ld + oa, ld, 0.0, Lb, ld,
-                      sa.pS, sa.pX, pLb, 1, 0, 0, 0, nullptr, 0, 0, 0, 2.0 * t3 * 10.0 * m3 * nb, nullptr, nullptr, nullptr, false,
-                      fy ? &tp : nullptr));
+                      sa.pS, sa.pX, pLb, 1, 0, 0, 0, nullptr, 0, 0, 0, 2.0 * t3 * ev.units_pp * nb, ev.pp_kb, nullptr, nullptr, false,
+                      fy ? &tp : nullptr, ev.pp_ke, true));
             // S[r,c] -= L[r,P] L[c,P]^T for the tiles right of / below the panel
             GCHK(gemm(h, false, false, m3 * 64, m3 * 64, 256, 0, 1, -1.0, Lb, ld, Lb, ld, 1.0, S + oc * ld + oc, ld, pLb, pLb, sa.pS,
-                      1, 0, 0, 0, nullptr, 0, 0, 0, 2.0 * t3 * 4.0 * (m3 * (m3 + 1) / 2) * nb, nullptr, nullptr, nullptr, false,
-                      fy ? &tu : nullptr));
+                      1, 0, 0, 0, nullptr, 0, 0, 0, 2.0 * t3 * ev.units_upd * nb, ev.upd_kb, ev.upd_kb, nullptr, false,
+                      fy ? &tu : nullptr, nullptr, true));
         }
         // X = L^-1 by recursive doubling over the 256-wide diagonal inverses -- or, split representation, everything
         // but its first block column below row p, whose place L[p:, 0:p] takes (see gmrf_handle::xsplit)
@@ -1718,11 +1880,14 @@ static gmrf_status factor_fwd_ok(gmrf_handle* h, bool* ok) {
         const int m3 = nt - j - 4;
         const GemmTail tp{h->d_ft + oa, bsp, h->d_fy + oa, h->n_pad, nullptr, 0, 0.0};
         const GemmTail tu{h->d_fy + oa, h->n_pad, h->d_ft + oc, bsp, nullptr, 0, 1.0};
+        // (the envelope bounds potrf_block passes -- those of a block behind the first, as good as any: what qualifies does not
+        // depend on their values)
+        const EnvPanel ev = env_panel(h, std::min<int64_t>(1, h->N - 1), j / 4, true);
         st = gemm(h, false, false, 64 * m3, 256, 256, TRI_B_UPPER, 0, 1.0, S + oc * ld + oa, ld, X + oa * ld + oa, ld, 0.0, L + oc * ld + oa, ld,
-                  bstride, pX, pL, 1, 0, 0, 0, nullptr, 0, 0, 0, -1.0, nullptr, nullptr, nullptr, false, &tp);
+                  bstride, pX, pL, 1, 0, 0, 0, nullptr, 0, 0, 0, -1.0, ev.pp_kb, nullptr, nullptr, false, &tp, ev.pp_ke, true);
         if (st == GMRF_OK)
             st = gemm(h, false, false, m3 * 64, m3 * 64, 256, 0, 1, -1.0, L + oc * ld + oa, ld, L + oc * ld + oa, ld, 1.0, S + oc * ld + oc, ld,
-                      pL, pL, bstride, 1, 0, 0, 0, nullptr, 0, 0, 0, -1.0, nullptr, nullptr, nullptr, false, &tu);
+                      pL, pL, bstride, 1, 0, 0, 0, nullptr, 0, 0, 0, -1.0, ev.upd_kb, ev.upd_kb, nullptr, false, &tu, nullptr, true);
     }
     h->tail_probe = false;
     *ok = st == GMRF_OK && !h->tail_refused;
@@ -2100,9 +2265,15 @@ static gmrf_status sweep_launches(gmrf_handle* h, bool backward, int kp, double*
                                   dout ? &db : nullptr));
                     else if (!backward)
                         GCHK(gemm(h, false, false, kp, q, p, 0, 0, -1.0, yout, npad, Lba, ld, 1.0, rhs + p, npad, pPanel, pX, pPanel));
-                    else
+                    else {
+                        // (round 19) envelope: column tile bn of L_ba = L[256:, 0:256] is zero below row env_ken[bn] (gmrf_handle)
+                        const bool env = p == 256 && h->env_ok && !h->no_env && !h->tw && !h->tw_half && h->tw_blk < 0 && h->env_ken_has[(size_t)i];
+                        double units = 0.0;
+                        for (int bn = 0; env && bn < 4; ++bn) units += h->env_ken[(size_t)(i * 4 + bn)] / 64;
                         GCHK(gemm(h, false, true, kp, p, q, 0, 0, -1.0, yout + p, npad, Lba, ld, 1.0, rhs, npad, pPanel, pX, pPanel,
-                                  1, z0, z0, z0, nullptr, z0, z0, 0, -1.0, nullptr, nullptr, nullptr, tail));
+                                  1, z0, z0, z0, nullptr, z0, z0, 0, env ? 2.0 * kp * 64.0 * 64.0 * units * nprob : -1.0, nullptr, nullptr,
+                                  env ? h->d_env_ken + i * 4 : nullptr, tail, nullptr, nullptr, env));
+                    }
                 } else {
                     s.ld = ld; s.ldx = npad; s.ldo = npad; s.pMat = pX; s.pXin = pPanel; s.pOut = pPanel; s.kst = nullptr; s.mend = nullptr;
                     if (which == 0) { s.Mat = X; s.Xin = rhs; s.Bin = nullptr; s.ldb = 0; s.Out = yout; s.rows = p; s.kdim = p; s.sub = 0; s.pBin = 0; }
@@ -2274,7 +2445,7 @@ gmrf_status gmrf_bt_destroy(gmrf_handle* h) {
     persist_release(h);
     destroy_graphs(h);
     free_dev(h->d_keys); free_dev(h->d_vals); free_dev(h->d_src); free_dev(h->d_nz_stage);
-    free_dev(h->d_lo_rowptr); free_dev(h->d_dg_rowptr); free_dev(h->d_kst); free_dev(h->d_mend);
+    free_dev(h->d_lo_rowptr); free_dev(h->d_dg_rowptr); free_dev(h->d_kst); free_dev(h->d_mend); free_dev(h->d_env); free_dev(h->d_env_ken);
     free_dev(h->d_bxt_uptr); free_dev(h->d_bxt_ucols); free_dev(h->d_bxt_lidx); free_dev(h->d_bxt_gtiles);
     if (!h->external_storage) { free_dev(h->d_L); free_dev(h->d_C); free_dev(h->d_Linv); }
     else if (!h->keep_l) free_dev(h->d_L);               // the one-block work buffer is ours
@@ -2345,6 +2516,7 @@ gmrf_status gmrf_bt_set_eager(gmrf_handle* h, int32_t eager) {
     h->no_fused_posterior = (eager & 262144) != 0;
     h->no_factor_fwd = (eager & 524288) != 0;
     if (((eager & 1048576) != 0) != h->no_grouped_gemm) { destroy_graphs(h); h->no_grouped_gemm = (eager & 1048576) != 0; }
+    if (((eager & 2097152) != 0) != h->no_env) { destroy_graphs(h); h->no_env = (eager & 2097152) != 0; }
     if (eager != h->eager_bits) h->fy_for = nullptr;         // (a factor of other settings: no y taken for granted)
     h->eager = (eager & 1) != 0;
     h->eager_bits = eager;
@@ -6205,6 +6377,7 @@ static gmrf_status tw_new_half(gmrf_handle* h, hipStream_t st, gmrf_handle** out
     GCHK(gmrf_bt_create(h->device, (void*)st, out));
     GCHK(gmrf_bt_set_eager(*out, h->eager_bits));
     (*out)->profiling = h->profiling;
+    (*out)->tw_half = true;
     return GMRF_OK;
 }
 
@@ -6792,12 +6965,13 @@ gmrf_status gmrf_test_gemm_pair(int32_t device, int32_t batch, int32_t grouped, 
 // route the descriptor does not qualify for is GMRF_ERR_BAD_SHAPE and launches nothing.  The family is this hook's statement of
 // launch_gemm's order of questions (gemm_uses_big, gemm_dma_shape, gemm_uses_ll, K % 32, grid.x > 768): it holds with the
 // launcher's tuning variables GMRF_GEMM_SINGLE_STAGE, GMRF_GEMM_BK16 and GMRF_GEMM_LL_MAX_TILES unset, as the tests run.
-gmrf_status gmrf_test_gemm_desc(int32_t device, int32_t route, const int64_t* desc, const double* abt,
-                                const double* A, int64_t nA, const double* B, int64_t nB, double* C, int64_t nC,
-                                const double* D, int64_t nD, const double* tA, int64_t ntA, double* tC, int64_t ntC,
-                                const double* tD, int64_t ntD, const int32_t* kb_m, int64_t n_kb_m, const int32_t* kb_n,
-                                int64_t n_kb_n, const int32_t* ke_n, int64_t n_ke_n, double* samples, int64_t n_samples,
-                                double* mean, int64_t n_mean, int32_t* family) {
+// (ke_m, grouped: gmrf_test_gemm_env below)
+static gmrf_status gemm_desc_run(int32_t device, int32_t route, const int64_t* desc, const double* abt,
+                                 const double* A, int64_t nA, const double* B, int64_t nB, double* C, int64_t nC,
+                                 const double* D, int64_t nD, const double* tA, int64_t ntA, double* tC, int64_t ntC,
+                                 const double* tD, int64_t ntD, const int32_t* kb_m, int64_t n_kb_m, const int32_t* kb_n,
+                                 int64_t n_kb_n, const int32_t* ke_n, int64_t n_ke_n, double* samples, int64_t n_samples,
+                                 double* mean, int64_t n_mean, int32_t* family, const int32_t* ke_m, int64_t n_ke_m, int32_t grouped) {
     if (!desc || !abt || !A || !B || !C || !family) return bad_shape("gemm desc test: null pointer");
     *family = 0;
     const int64_t M = desc[0], N = desc[1], K = desc[2];
@@ -6834,10 +7008,12 @@ gmrf_status gmrf_test_gemm_desc(int32_t device, int32_t route, const int64_t* de
     if (needA > nA || needB > nB || needC > nC || (D && needD > nD)) return bad_shape("gemm desc test: operand buffer too small");
     if (own_tail && (zout * ptA + K > ntA || zout * ptC + N > ntC || (tD && zout * ptD + N > ntD)))
         return bad_shape("gemm desc test: tail buffer too small");
-    if ((kb_m && n_kb_m < M / 64) || (kb_n && n_kb_n < N / 64) || (ke_n && n_ke_n < N / 64)) return bad_shape("gemm desc test: K bounds too short");
-    const int32_t* kbs[3] = {kb_m, kb_n, ke_n};
-    const int64_t nkb[3] = {M / 64, N / 64, N / 64};
-    for (int a = 0; a < 3; ++a)
+    if ((kb_m && n_kb_m < M / 64) || (kb_n && n_kb_n < N / 64) || (ke_n && n_ke_n < N / 64) || (ke_m && n_ke_m < M / 64))
+        return bad_shape("gemm desc test: K bounds too short");
+    if (grouped < 0 || grouped > 2 || (grouped && route != 3)) return bad_shape("gemm desc test: grouped launches are of the 64 x 64 LDS-DMA kernel");
+    const int32_t* kbs[4] = {kb_m, kb_n, ke_n, ke_m};
+    const int64_t nkb[4] = {M / 64, N / 64, N / 64, M / 64};
+    for (int a = 0; a < 4; ++a)
         for (int64_t i = 0; kbs[a] && i < nkb[a]; ++i)
             if (kbs[a][i] < 0 || kbs[a][i] > K || kbs[a][i] % 64) return bad_shape("gemm desc test: K bound value");
     if (dout) {
@@ -6867,6 +7043,7 @@ gmrf_status gmrf_test_gemm_desc(int32_t device, int32_t route, const int64_t* de
     g.D = (const double*)up(D, nD, 8);
     g.tA = (const double*)up(tA, ntA, 8); g.tC = (double*)up(tC, ntC, 8); g.tD = (const double*)up(tD, ntD, 8);
     g.kb_m = (const int*)up(kb_m, n_kb_m, 4); g.kb_n = (const int*)up(kb_n, n_kb_n, 4); g.ke_n = (const int*)up(ke_n, n_ke_n, 4);
+    g.ke_m = (const int*)up(ke_m, n_ke_m, 4);
     double* d_samples = (double*)up(samples, n_samples, 8);
     double* d_mean = (double*)up(mean, n_mean, 8);
     GemmDirectOut* d_out = nullptr;
@@ -6912,7 +7089,13 @@ gmrf_status gmrf_test_gemm_desc(int32_t device, int32_t route, const int64_t* de
         }
         static const int want[] = {0, 3, 4, 5, 6, 7};
         if (route == 0 ? (fam & 255) > 2 : (route < 6 && fam != want[route])) fam = 0;
-        if (fam) le = launch_gemm(nullptr, a_t, b_n, g, nz);
+        if (fam && grouped) {
+            // the descriptor as the first / second product of a grouped launch; the other is its copy on an output buffer of its own
+            GemmArgs g2 = g;
+            g2.C = (double*)up(C, nC, 8);
+            le = e;
+            if (le == hipSuccess && !gemm_try_dma_grouped(nullptr, b_n, grouped == 1 ? g : g2, b_n, grouped == 1 ? g2 : g, nz, nullptr, nullptr, &le)) fam = 0;
+        } else if (fam) le = launch_gemm(nullptr, a_t, b_n, g, nz);
     }
     restore();
     if (!fam) { drop(); return bad_shape("gemm desc test: the descriptor does not qualify for the route"); }
@@ -6924,6 +7107,39 @@ gmrf_status gmrf_test_gemm_desc(int32_t device, int32_t route, const int64_t* de
     drop();
     HIPCHK(le);
     *family = fam;
+    return GMRF_OK;
+}
+
+gmrf_status gmrf_test_gemm_desc(int32_t device, int32_t route, const int64_t* desc, const double* abt,
+                                const double* A, int64_t nA, const double* B, int64_t nB, double* C, int64_t nC,
+                                const double* D, int64_t nD, const double* tA, int64_t ntA, double* tC, int64_t ntC,
+                                const double* tD, int64_t ntD, const int32_t* kb_m, int64_t n_kb_m, const int32_t* kb_n,
+                                int64_t n_kb_n, const int32_t* ke_n, int64_t n_ke_n, double* samples, int64_t n_samples,
+                                double* mean, int64_t n_mean, int32_t* family) {
+    return gemm_desc_run(device, route, desc, abt, A, nA, B, nB, C, nC, D, nD, tA, ntA, tC, ntC, tD, ntD, kb_m, n_kb_m, kb_n, n_kb_n,
+                         ke_n, n_ke_n, samples, n_samples, mean, n_mean, family, nullptr, 0, 0);
+}
+// gmrf_test_gemm_desc with GemmArgs::ke_m (upper K bound per 64-row tile of A: M / 64 values, multiples of 64) and, grouped = 1 / 2
+// (route 3 only), the descriptor as the first / second product of ONE gemm_f64_dma_grouped launch beside a copy of itself.
+gmrf_status gmrf_test_gemm_env(int32_t device, int32_t route, const int64_t* desc, const double* abt,
+                               const double* A, int64_t nA, const double* B, int64_t nB, double* C, int64_t nC,
+                               const double* D, int64_t nD, const double* tA, int64_t ntA, double* tC, int64_t ntC,
+                               const double* tD, int64_t ntD, const int32_t* kb_m, int64_t n_kb_m, const int32_t* kb_n,
+                               int64_t n_kb_n, const int32_t* ke_n, int64_t n_ke_n, const int32_t* ke_m, int64_t n_ke_m,
+                               int32_t grouped, int32_t* family) {
+    return gemm_desc_run(device, route, desc, abt, A, nA, B, nB, C, nC, D, nD, tA, ntA, tC, ntC, tD, ntD, kb_m, n_kb_m, kb_n, n_kb_n,
+                         ke_n, n_ke_n, nullptr, 0, nullptr, 0, family, ke_m, n_ke_m, grouped);
+}
+// The envelope bounds of the analysed pattern (gmrf_handle::env_lo / env_hi: [n_blocks][bsp / 64], in-block columns) and what the
+// factorisation does with them: *state = 0 none computed (blocks not a multiple of 256), 1 computed but trivial for every panel
+// (every launch as without them), 2 in use.  *n_vals = values per array (may exceed cap).
+gmrf_status gmrf_test_envelope(gmrf_handle* h, int32_t* lo, int32_t* hi, int64_t cap, int64_t* n_vals, int32_t* state) {
+    if (!h || !n_vals || !state) return bad_shape("null argument");
+    const int64_t want = h->N * (h->bsp / 64);
+    const bool have = h->bsp % 256 == 0 && (int64_t)h->env_lo.size() == want && h->analyzed;
+    *n_vals = have ? want : 0;
+    *state = !have ? 0 : (h->env_ok ? 2 : 1);
+    for (int64_t i = 0; have && lo && hi && i < std::min(cap, want); ++i) { lo[i] = h->env_lo[(size_t)i]; hi[i] = h->env_hi[(size_t)i]; }
     return GMRF_OK;
 }
 
@@ -7291,6 +7507,37 @@ gmrf_status gmrf_test_symbolic_csc(int64_t n, int64_t n_blocks, const int64_t* c
     for (int64_t v : sp.first) mix((uint64_t)v);
     out8[0] = sp.cmin; out8[1] = sp.rmax; out8[2] = (int64_t)sp.keys.size(); out8[3] = sp.max_row; out8[4] = sp.sparse_b;
     out8[5] = sp.bxt_ok; out8[6] = sp.ecap; out8[7] = (int64_t)(sum >> 1);
+    return GMRF_OK;
+}
+
+// The envelope bounds of a pattern without a device (build_envelope / derive_envelope): lo, hi as gmrf_test_envelope returns them
+// ([n_blocks][bsp / 64]), and units[n_blocks][bsp / 256][3]: the 64-wide K units of a panel's product without / with a tail row riding
+// and of its rank-256 update, as the factorisation books them.  cap: values lo and hi can hold; *n_vals = n_blocks * bsp / 64, or 0
+// where the blocks are no multiple of 256.
+gmrf_status gmrf_test_envelope_csc(int64_t n, int64_t n_blocks, const int64_t* colptr, const int64_t* rowval, int32_t index_base,
+                                   int32_t* lo, int32_t* hi, double* units, int64_t cap, int64_t* n_vals) {
+    if (!colptr || !rowval || !n_vals) return bad_shape("null pointer");
+    if (n <= 0 || n_blocks <= 0 || n % n_blocks != 0) return bad_shape("n must be a positive multiple of N_blocks");
+    const int64_t bs = n / n_blocks, bsp = 64 * next_pow2((bs + 63) / 64);
+    std::vector<std::vector<HostEntry>> dg, lw;
+    GCHK(split_csc(n, n_blocks, bs, colptr, rowval, index_base, dg, lw));
+    SymbolicPlan sp;
+    build_symbolic(n_blocks, bsp, dg, lw, false, sp);
+    const int nt = (int)(bsp / 64), np = nt / 4;
+    *n_vals = bsp % 256 == 0 ? n_blocks * nt : 0;
+    if (*n_vals == 0 || !lo || !hi || cap < *n_vals) return GMRF_OK;
+    for (int64_t k = 0; k < *n_vals; ++k) { lo[k] = sp.env_lo[(size_t)k]; hi[k] = sp.env_hi[(size_t)k]; }
+    if (units) {
+        EnvHost eh;
+        derive_envelope(n_blocks, bsp, sp, eh);
+        for (int64_t i = 0; i < n_blocks; ++i)
+            for (int p = 0; p < np; ++p) {
+                const int* host = eh.host.data() + (size_t)((i * np + p) * 4) * nt;
+                const int m3 = nt - 4 * p - 4;
+                double* u = units + (i * np + p) * 3;
+                u[0] = env_units_pp(host, nt, m3, 0); u[1] = env_units_pp(host, nt, m3, 2); u[2] = env_units_upd(host, m3);
+            }
+    }
     return GMRF_OK;
 }
 

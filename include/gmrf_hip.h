@@ -428,7 +428,9 @@ gmrf_status gmrf_bt_set_profiling(gmrf_handle* h, int32_t level);
  * (comparison; the samples' L^-T z rows are the same bits, the mean agrees to rounding); bit 19: factorisations do not solve for the
  * right-hand side of gmrf_bt_set_factor_rhs (comparison: the posterior's forward sweep runs); bit 20: the two independent 128^3
  * products of a 256-column panel's diagonal chain (S_BB -= L_BA L_BA^T and T = L_BA X_A) stay two launches instead of ONE launch of
- * gemm_f64_dma_grouped (comparison; same bits).
+ * gemm_f64_dma_grouped (comparison; same bits); bit 21: the batched factorisation's panel products and rank-256 updates, and the
+ * backward sweep's L_ba^T product, run over their whole K ranges instead of skipping the 64-wide K units outside the blocks'
+ * envelope (comparison; same bits).
  * (Bits 6, 9, 10, 11, 14 selected comparison routes that lost twice -- left-looking panels, in-panel updates on the GEMM kernel,
  * rank-64 panel steps of batches, 128-column panels, potrf_panel256 -- and were removed with them in round 5; they are ignored.) */
 gmrf_status gmrf_bt_set_eager(gmrf_handle* h, int32_t eager);
@@ -833,6 +835,20 @@ gmrf_status gmrf_test_gemm_desc(int32_t device, int32_t route, const int64_t* de
                                 const double* tD, int64_t ntD, const int32_t* kb_m, int64_t n_kb_m, const int32_t* kb_n,
                                 int64_t n_kb_n, const int32_t* ke_n, int64_t n_ke_n, double* samples, int64_t n_samples,
                                 double* mean, int64_t n_mean, int32_t* family);
+/* gmrf_test_gemm_desc with GemmArgs::ke_m (an upper K bound per 64-row tile of A, the LDS-DMA kernels' only: routes 3 .. 6) and
+ * without the direct output.  grouped = 1 / 2 (route 3): the descriptor runs as the first / second product of ONE launch of
+ * gemm_f64_dma_grouped, beside a copy of itself that writes a buffer of its own. */
+gmrf_status gmrf_test_gemm_env(int32_t device, int32_t route, const int64_t* desc, const double* abt,
+                               const double* A, int64_t nA, const double* B, int64_t nB, double* C, int64_t nC,
+                               const double* D, int64_t nD, const double* tA, int64_t ntA, double* tC, int64_t ntC,
+                               const double* tD, int64_t ntD, const int32_t* kb_m, int64_t n_kb_m, const int32_t* kb_n,
+                               int64_t n_kb_n, const int32_t* ke_n, int64_t n_ke_n, const int32_t* ke_m, int64_t n_ke_m,
+                               int32_t grouped, int32_t* family);
+/* The envelope bounds the symbolic phase derived per block and 64-row tile ([n_blocks][bsp / 64] each, in-block columns; blocks that
+ * are a multiple of 256): lo = first column of D_i in the rows S = D_i - C C^T leaves untouched, rounded down to 64 (0 elsewhere),
+ * hi = end of D_i's columns inside lo's 256-column panel, rounded up to 64 (the panel's end for a tile inside that panel, bsp
+ * elsewhere).  *state: 0 none, 1 trivial for every panel (the launches of before), 2 in use.  *n_vals: values per array. */
+gmrf_status gmrf_test_envelope(gmrf_handle* h, int32_t* lo, int32_t* hi, int64_t cap, int64_t* n_vals, int32_t* state);
 /* Device-resident timing of one GEMM shape (random operands): batch problems, big = 1 takes the
  * 128 x 128 kernel, 0 the 64 x 64 one, 2 the launcher's own choice. */
 gmrf_status gmrf_test_gemm_rate(int32_t device, int64_t M, int64_t N, int64_t K, int32_t transB,
@@ -889,6 +905,12 @@ gmrf_status gmrf_test_microbench(int32_t device, double* out, int32_t n);
  * side.  out8 = {cmin, rmax, entries, longest lower-block row, sparse route?, tile plan?, plan capacity, checksum}. */
 gmrf_status gmrf_test_symbolic_csc(int64_t n, int64_t n_blocks, const int64_t* colptr, const int64_t* rowval,
                                    int32_t index_base, int64_t* out8);
+
+/* The envelope bounds of a pattern, host only (no device): lo / hi as gmrf_test_envelope ([n_blocks][bsp / 64]; cap = what they can
+ * hold) and units[n_blocks][bsp / 256][3] = 64-wide K units of each panel's product without / with a tail row riding and of its
+ * rank-256 update.  *n_vals = n_blocks * bsp / 64 (0: blocks no multiple of 256). */
+gmrf_status gmrf_test_envelope_csc(int64_t n, int64_t n_blocks, const int64_t* colptr, const int64_t* rowval, int32_t index_base,
+                                   int32_t* lo, int32_t* hi, double* units, int64_t cap, int64_t* n_vals);
 
 #ifdef __cplusplus
 }

@@ -422,10 +422,10 @@ static void prof_collect(gmrf_handle* h) {
 // C == nullptr: the tail is row M of the product's own operands.  out (then; B [k][n]): the product also writes the caller's mean and
 // samples (gemm_f64_dma's DOUT) -- its columns are the dofs j0 .. of a problem, the first `cols` of them real
 struct GemmTail {
-    const double* A; int64_t pA;
-    double* C; int64_t pC;
-    const double* D; int64_t pD;
-    double beta;
+    const double* A = nullptr; int64_t pA = 0;
+    double* C = nullptr; int64_t pC = 0;
+    const double* D = nullptr; int64_t pD = 0;
+    double beta = 0.0;
     const GemmDirectOut* out = nullptr;
     int64_t j0 = 0;
     int cols = 0;
@@ -447,39 +447,90 @@ static int gemm_shape_row(gmrf_handle* h, const int64_t (&key)[8]) {
     return (int)h->gemm_shapes.size() - 1;
 }
 
-static gmrf_status gemm(gmrf_handle* h, bool a_t, bool b_n, int M, int N, int K, int tri, int lower_only,
-                        double alpha, const double* A, int64_t lda, const double* B, int64_t ldb,
-                        double beta, double* C, int64_t ldc, int64_t pA, int64_t pB, int64_t pC,
-                        int batch = 1, int64_t sA = 0, int64_t sB = 0, int64_t sC = 0, const double* D = nullptr,
-                        int64_t ldd = 0, int64_t pD = 0, int pclass = 0, double pwork = -1.0,
-                        const int* kb_m = nullptr, const int* kb_n = nullptr, const int* ke_n = nullptr, bool tail = false,
-                        const GemmTail* gt = nullptr, const int* ke_m = nullptr, bool hints = false) {
-    // ke_m: upper K bound per row tile of A (GemmArgs::ke_m, the LDS-DMA kernels only).  hints: the K bounds of this call are optional
-    // (the operands hold real zeros outside them) -- a launch that another kernel family takes gets none of them, and ke_m never
+// One dense product as gemm() takes it:  C = beta (D or C) + alpha op(A) op(B)  for every problem of the handle's batch, operand
+// P of problem z at P + z pP.  The constructor and a() / b() / c() give what every product has; everything below them is OPTIONAL
+// and absent unless the call site names it.  A new option is a new named field with its setter, absent by default.
+struct GemmCall {
+    bool a_t, b_n;                     // A stored [k][m] (else [m][k]); B stored [k][n] (else [n][k])
+    int M, N, K;
+    double alpha, beta;
+    const double* A = nullptr; int64_t lda = 0, pA = 0;
+    const double* B = nullptr; int64_t ldb = 0, pB = 0;
+    double* C = nullptr; int64_t ldc = 0, pC = 0;
+    int tri = 0, lower_only = 0;       // TRI_* of the operands; only the tiles on and below the block diagonal
+    int batch = 1; int64_t sA = 0, sB = 0, sC = 0;                 // products per problem, and their strides
+    const double* D = nullptr; int64_t ldd = 0, pD = 0;            // addend (null: C, in place)
+    int pclass = 0; double pwork = -1.0;                           // statistics class (0: by kernel) and work (< 0: the product's flops)
+    // K bounds per 64-wide tile (GemmArgs): from max(kb_m[bm], kb_n[bn]) to min(ke_m[bm], ke_n[bn]).  ke_m is for the LDS-DMA
+    // kernels only.  hints: the bounds are optional (the operands hold real zeros outside them) -- a launch that another kernel
+    // family takes gets none of them and books its flops; ke_m is such a hint always
+    const int* kb_m = nullptr; const int* kb_n = nullptr; const int* ke_m = nullptr; const int* ke_n = nullptr;
+    bool hints = false;
+    bool tail = false, tail_own = false;                           // one more row: row M of A / C, or (tail_own) on gt's operands
+    GemmTail gt;
+
+    GemmCall(bool a_t_, bool b_n_, int M_, int N_, int K_, double alpha_, double beta_)
+        : a_t(a_t_), b_n(b_n_), M(M_), N(N_), K(K_), alpha(alpha_), beta(beta_) {}
+    GemmCall& a(const double* p, int64_t ld, int64_t pp) { A = p; lda = ld; pA = pp; return *this; }
+    GemmCall& b(const double* p, int64_t ld, int64_t pp) { B = p; ldb = ld; pB = pp; return *this; }
+    GemmCall& c(double* p, int64_t ld, int64_t pp) { C = p; ldc = ld; pC = pp; return *this; }
+    GemmCall& triangular(int flags) { tri = flags; return *this; }
+    GemmCall& lower() { lower_only = 1; return *this; }
+    GemmCall& batched(int n, int64_t sa, int64_t sb, int64_t sc) { batch = n; sA = sa; sB = sb; sC = sc; return *this; }
+    GemmCall& addend(const double* p, int64_t ld, int64_t pp) { D = p; ldd = ld; pD = pp; return *this; }
+    GemmCall& work(double w, int cls = 0) { pwork = w; pclass = cls; return *this; }
+    GemmCall& k_begin(const int* m, const int* n) { kb_m = m; kb_n = n; return *this; }
+    GemmCall& k_end(const int* m, const int* n) { ke_m = m; ke_n = n; return *this; }
+    GemmCall& k_hints(bool on = true) { hints = on; return *this; }
+    GemmCall& tail_row(bool on = true) { tail = on; return *this; }
+    GemmCall& tail_ops(const GemmTail* t) { if (t) { tail = tail_own = true; gt = *t; } return *this; }   // (null: none)
+};
+
+static void gemm_fill(const gmrf_handle* h, const GemmCall& c, GemmArgs& g) {
+    if (c.tail_own) {
+        const GemmTail& t = c.gt;
+        if (t.C) { g.tA = t.A; g.ptA = t.pA; g.tC = t.C; g.ptC = t.pC; g.tD = t.D; g.ptD = t.pD; g.tbeta = t.beta; }
+        g.dout = t.out; g.o_j0 = t.j0; g.o_cols = t.cols; g.o_n = h->n;
+    }
+    g.A = c.A; g.B = c.B; g.C = c.C; g.lda = c.lda; g.ldb = c.ldb; g.ldc = c.ldc; g.pA = c.pA; g.pB = c.pB; g.pC = c.pC;
+    g.nb1 = c.batch; g.strideA = c.sA; g.strideB = c.sB; g.strideC = c.sC;
+    g.D = c.D; g.ldd = c.ldd; g.pD = c.pD;
+    g.M = c.M; g.N = c.N; g.K = c.K; g.tri = c.tri; g.lower_only = c.lower_only; g.alpha = c.alpha; g.beta = c.beta; g.stamps = nullptr;
+    g.kb_m = c.kb_m; g.kb_n = c.kb_n; g.ke_n = c.ke_n; g.ke_m = c.ke_m;
+}
+
+// Runs one GEMM launch on the handle's GEMM stream -- run(stream, begin, end) -> hipError_t; when profiling, with an event pair
+// for the dispatch's own begin / end time stamps (see launch_gemm) booked as {kind, work, gemm_by_shape row of `key`}
+template <class Run>
+static gmrf_status gemm_run(gmrf_handle* h, int kind, double work, const int64_t (&key)[8], Run&& run) {
+    hipStream_t st = h->gemm_stream ? h->gemm_stream : h->stream;
+    if (h->profiling <= 0) { HIPCHK(run(st, nullptr, nullptr)); return GMRF_OK; }
+    EvPair p;
+    p.kind = kind; p.work = work;
+    p.a = ev_get(h); p.b = ev_get(h);
+    p.shape = gemm_shape_row(h, key);
+    HIPCHK(run(st, p.a, p.b));
+    h->events.push_back(p);
+    return GMRF_OK;
+}
+
+static gmrf_status gemm(gmrf_handle* h, const GemmCall& c) {
     GemmArgs g;
-    if (gt) {
-        if (gt->C) { g.tA = gt->A; g.ptA = gt->pA; g.tC = gt->C; g.ptC = gt->pC; g.tD = gt->D; g.ptD = gt->pD; g.tbeta = gt->beta; }
-        g.dout = gt->out; g.o_j0 = gt->j0; g.o_cols = gt->cols; g.o_n = h->n;
-        tail = true;
+    gemm_fill(h, c, g);
+    const bool a_t = c.a_t, b_n = c.b_n;
+    const int M = c.M, nz = c.batch * (int)h->B;
+    int pclass = c.pclass;
+    double pwork = c.pwork;
+    if ((g.ke_m || c.hints) && (gemm_uses_big(a_t, g, nz) || gemm_uses_ll(g, nz) || !gemm_uses_dma(a_t, g, nz))) {
+        g.ke_m = nullptr;
+        if (c.hints) { g.kb_m = g.kb_n = g.ke_n = nullptr; pwork = -1.0; }
     }
-    g.kb_m = kb_m; g.kb_n = kb_n; g.ke_n = ke_n;
-    g.D = D; g.ldd = ldd; g.pD = pD;
-    g.A = A; g.B = B; g.C = C;
-    g.lda = lda; g.ldb = ldb; g.ldc = ldc;
-    g.strideA = sA; g.strideB = sB; g.strideC = sC;
-    g.pA = pA; g.pB = pB; g.pC = pC; g.nb1 = batch;
-    g.M = M; g.N = N; g.K = K; g.tri = tri; g.lower_only = lower_only;
-    g.alpha = alpha; g.beta = beta; g.stamps = nullptr;
-    g.ke_m = ke_m;
-    if ((ke_m || hints) && (gemm_uses_big(a_t, g, batch * (int)h->B) || gemm_uses_ll(g, batch * (int)h->B) || !gemm_uses_dma(a_t, g, batch * (int)h->B))) {
-        g.ke_m = ke_m = nullptr;
-        if (hints) { g.kb_m = kb_m = nullptr; g.kb_n = kb_n = nullptr; g.ke_n = ke_n = nullptr; pwork = -1.0; }
-    }
-    double flops = gemm_flops(M, N, K, tri, lower_only, batch * (double)h->B);
-    if (tail) {
+    double flops = gemm_flops(M, c.N, c.K, c.tri, c.lower_only, c.batch * (double)h->B);
+    const int64_t bounded = (g.kb_m || g.kb_n || g.ke_n || g.ke_m) ? 1 : 0;
+    if (c.tail) {
         // one more row, row M of A / C (gemm_f64_dma's TAIL): the kernel the M rows alone would get, or not at all.  A dry run
         // (tail_probe) only asks whether every product of a sweep qualifies.
-        if (!gemm_tail_ok(a_t, b_n, g, batch * (int)h->B)) {
+        if (!gemm_tail_ok(a_t, b_n, g, nz)) {
             h->tail_refused = true;
             return h->tail_probe ? GMRF_OK : bad_shape("internal: a product does not qualify for the tail-row GEMM");
         }
@@ -487,93 +538,49 @@ static gmrf_status gemm(gmrf_handle* h, bool a_t, bool b_n, int M, int N, int K,
         flops *= (M + 1.0) / M;
         if (pwork >= 0.0) pwork *= (M + 1.0) / M;
         pclass = b_n ? 15 : 14;
-        hipError_t e = hipSuccess;
-        if (h->profiling > 0) {
-            EvPair p;
-            p.kind = pclass; p.work = pwork >= 0.0 ? pwork : flops;
-            p.a = ev_get(h); p.b = ev_get(h);
-            const int64_t key[8] = {pclass, M + 1, N, K, tri, lower_only, batch * h->B, (kb_m || kb_n || ke_n || ke_m) ? 1 : 0};
-            p.shape = gemm_shape_row(h, key);
-            (void)gemm_try_dma_tail(h->gemm_stream ? h->gemm_stream : h->stream, a_t, b_n, g, batch * (int)h->B, p.a, p.b, &e);
-            HIPCHK(e);
-            h->events.push_back(p);
-            return GMRF_OK;
-        }
-        (void)gemm_try_dma_tail(h->gemm_stream ? h->gemm_stream : h->stream, a_t, b_n, g, batch * (int)h->B, nullptr, nullptr, &e);
-        HIPCHK(e);
-        return GMRF_OK;
-    }
-    // statistics: launches of the 128 x 128 kernel are their own classes (6: B stored [n][k],
-    // 7: B stored [k][n]) whoever calls, so that a class is one kernel symbol of a rocprof trace
-    if (gemm_uses_big(a_t, g, batch * (int)h->B)) { pclass = b_n ? 7 : 6; pwork = -1.0; }
-    else if (pclass == 0) {
-        if (gemm_uses_ll(g, batch * (int)h->B)) pclass = 13;
-        else if (gemm_uses_dma(a_t, g, batch * (int)h->B)) pclass = a_t ? 18 : (b_n ? 15 : 14);   // gemm_f64_dma<.., B [n][k]> / <.., B [k][n]> / <.., A [k][m]>
+    } else if (gemm_uses_big(a_t, g, nz)) {
+        // statistics: launches of the 128 x 128 kernel are their own classes (6: B stored [n][k],
+        // 7: B stored [k][n]) whoever calls, so that a class is one kernel symbol of a rocprof trace
+        pclass = b_n ? 7 : 6; pwork = -1.0;
+    } else if (pclass == 0) {
+        if (gemm_uses_ll(g, nz)) pclass = 13;
+        else if (gemm_uses_dma(a_t, g, nz)) pclass = a_t ? 18 : (b_n ? 15 : 14);   // gemm_f64_dma<.., B [n][k]> / <.., B [k][n]> / <.., A [k][m]>
         else pclass = a_t ? 12 : (b_n ? 11 : 0);
     }
-    if (h->profiling > 0) {
-        // GEMM classes: the dispatch's own begin / end time stamps (see launch_gemm), not an event pair around the launch
-        EvPair p;
-        p.kind = pclass; p.work = pwork >= 0.0 ? pwork : flops;
-        p.a = ev_get(h); p.b = ev_get(h);
-        const int64_t key[8] = {pclass, M, N, K, tri, lower_only, batch * h->B, (kb_m || kb_n || ke_n || ke_m) ? 1 : 0};
-        p.shape = gemm_shape_row(h, key);
-        HIPCHK(launch_gemm(h->gemm_stream ? h->gemm_stream : h->stream, a_t, b_n, g, batch * (int)h->B, p.a, p.b));
-        h->events.push_back(p);
-        return GMRF_OK;
-    }
-    HIPCHK(launch_gemm(h->gemm_stream ? h->gemm_stream : h->stream, a_t, b_n, g, batch * (int)h->B));
-    return GMRF_OK;
+    const int64_t key[8] = {pclass, c.tail ? M + 1 : M, c.N, c.K, c.tri, c.lower_only, c.batch * h->B, bounded};
+    return gemm_run(h, pclass, pwork >= 0.0 ? pwork : flops, key, [&](hipStream_t st, hipEvent_t ea, hipEvent_t eb) {
+        if (!c.tail) return launch_gemm(st, a_t, b_n, g, nz, ea, eb);
+        hipError_t e = hipSuccess;
+        (void)gemm_try_dma_tail(st, a_t, b_n, g, nz, ea, eb, &e);
+        return e;
+    });
 }
 
-// One of two independent products (both on A [m][k], one problem per z) that gemm_pair runs as ONE launch
-struct GemmOne {
-    bool b_n; int M, N, K, tri, lower_only;
-    double alpha; const double* A; int64_t lda; const double* B; int64_t ldb; double beta; double* C; int64_t ldc;
-    int64_t pA, pB, pC;
-    double pwork;                      // work to book (< 0: the product's flops)
-};
-static gmrf_status gemm_one(gmrf_handle* h, const GemmOne& q) {
-    return gemm(h, false, q.b_n, q.M, q.N, q.K, q.tri, q.lower_only, q.alpha, q.A, q.lda, q.B, q.ldb, q.beta, q.C, q.ldc, q.pA, q.pB, q.pC,
-                1, 0, 0, 0, nullptr, 0, 0, 0, q.pwork);
-}
 // Two products neither of which reads what the other writes, as one launch of gemm_f64_dma_grouped where both qualify (and set_eager
-// bit 20 does not keep them apart), else one after the other.  Statistics: ONE launch of class 14 (the LDS-DMA kernel; the grouped
-// symbol has no class of its own) with both products' work, and one gemm_by_shape row: M = both products' rows, tri / lower_only =
-// the first product's flags | the second's << 8.
-static gmrf_status gemm_pair(gmrf_handle* h, const GemmOne& q0, const GemmOne& q1) {
+// bit 20 does not keep them apart), else one after the other.  Both on A [m][k], one per problem, with no addend, K bounds or tail.
+// Statistics: ONE launch of class 14 (the LDS-DMA kernel; the grouped symbol has no class of its own) with both products' work, and
+// one gemm_by_shape row: M = both products' rows, tri / lower_only = the first product's flags | the second's << 8.
+static gmrf_status gemm_pair(gmrf_handle* h, const GemmCall& q0, const GemmCall& q1) {
     GemmArgs g[2];
-    const GemmOne* q[2] = {&q0, &q1};
+    const GemmCall* q[2] = {&q0, &q1};
     double work[2];
     for (int i = 0; i < 2; ++i) {
-        GemmArgs& a = g[i];
-        a.A = q[i]->A; a.B = q[i]->B; a.C = q[i]->C; a.lda = q[i]->lda; a.ldb = q[i]->ldb; a.ldc = q[i]->ldc;
-        a.strideA = a.strideB = a.strideC = 0;
-        a.pA = q[i]->pA; a.pB = q[i]->pB; a.pC = q[i]->pC; a.nb1 = 1;
-        a.M = q[i]->M; a.N = q[i]->N; a.K = q[i]->K; a.tri = q[i]->tri; a.lower_only = q[i]->lower_only;
-        a.alpha = q[i]->alpha; a.beta = q[i]->beta; a.D = nullptr; a.ldd = 0; a.pD = 0; a.stamps = nullptr;
-        work[i] = q[i]->pwork >= 0.0 ? q[i]->pwork : gemm_flops(a.M, a.N, a.K, a.tri, a.lower_only, (double)h->B);
+        const GemmCall& c = *q[i];
+        if (c.a_t || c.batch != 1 || c.D || c.kb_m || c.kb_n || c.ke_m || c.ke_n || c.hints || c.tail || c.pclass)
+            return bad_shape("internal: a product of a GEMM pair is on A [m][k], one per problem, with no addend, K bounds or tail");
+        gemm_fill(h, c, g[i]);
+        work[i] = c.pwork >= 0.0 ? c.pwork : gemm_flops(c.M, c.N, c.K, c.tri, c.lower_only, (double)h->B);
     }
     if (h->no_grouped_gemm || !gemm_grouped_ok(g[0], g[1], (int)h->B)) {
-        GCHK(gemm_one(h, q0));
-        return gemm_one(h, q1);
+        GCHK(gemm(h, q0));
+        return gemm(h, q1);
     }
-    hipStream_t st = h->gemm_stream ? h->gemm_stream : h->stream;
-    hipError_t e = hipSuccess;
-    if (h->profiling > 0) {
-        EvPair p;
-        p.kind = 14; p.work = work[0] + work[1];
-        p.a = ev_get(h); p.b = ev_get(h);
-        const int64_t key[8] = {14, q0.M + q1.M, q0.N, q0.K, q0.tri | (q1.tri << 8), q0.lower_only | (q1.lower_only << 8), h->B, 0};
-        p.shape = gemm_shape_row(h, key);
-        (void)gemm_try_dma_grouped(st, q0.b_n, g[0], q1.b_n, g[1], (int)h->B, p.a, p.b, &e);
-        HIPCHK(e);
-        h->events.push_back(p);
-        return GMRF_OK;
-    }
-    (void)gemm_try_dma_grouped(st, q0.b_n, g[0], q1.b_n, g[1], (int)h->B, nullptr, nullptr, &e);
-    HIPCHK(e);
-    return GMRF_OK;
+    const int64_t key[8] = {14, q0.M + q1.M, q0.N, q0.K, q0.tri | (q1.tri << 8), q0.lower_only | (q1.lower_only << 8), h->B, 0};
+    return gemm_run(h, 14, work[0] + work[1], key, [&](hipStream_t st, hipEvent_t ea, hipEvent_t eb) {
+        hipError_t e = hipSuccess;
+        (void)gemm_try_dma_grouped(st, q0.b_n, g[0], q1.b_n, g[1], (int)h->B, ea, eb, &e);
+        return e;
+    });
 }
 
 // element counts / strides of the factor arrays (doubles)
@@ -1136,12 +1143,25 @@ static gmrf_status load_values(gmrf_handle* h, const double* nzval) {
 }
 
 // ------------------------------------------------------------------------------------ numeric factor
+// One doubling pair  T21 = L21 X11,  X21 = -X22 T21  on the m x n block at rows r .., columns c .. of L (problem stride pL), X and
+// T:  X11 = X[c:c+n, c:c+n] and X22 = X[r:r+m, r:r+m], both lower triangular.  `pairs` such blocks, `st` elements apart, in one
+// launch each.  which: bit 0 the first product, bit 1 the second.
+static gmrf_status doubling_pair(gmrf_handle* h, const double* L, int64_t pL, double* X, double* T, int r, int c, int m, int n,
+                                 int pairs, int64_t st, int which = 3) {
+    const int64_t ld = h->bsp, pX = stride_pX(h), pW = ld * ld, o21 = r * ld + c;
+    if (which & 1)
+        GCHK(gemm(h, GemmCall(false, true, m, n, n, 1.0, 0.0).a(L + o21, ld, pL).b(X + c * ld + c, ld, pX).c(T + o21, ld, pW)
+                         .triangular(TRI_B_LOWER).batched(pairs, st, st, st)));
+    if (which & 2)
+        GCHK(gemm(h, GemmCall(false, true, m, n, m, -1.0, 0.0).a(X + r * ld + r, ld, pX).b(T + o21, ld, pW).c(X + o21, ld, pX)
+                         .triangular(TRI_A_LOWER).batched(pairs, st, st, st)));
+    return GMRF_OK;
+}
+
 // Recursive doubling  X21 = -X22 (L21 X11)  over pairs of hh-wide diagonal blocks, levels hh = lo .. hi.
 // half: -1 all pairs, 0 / 1 only the pairs inside the first / second half of the block.
 static gmrf_status doubling_levels(gmrf_handle* h, double* L, double* X, double* T, int lo, int hi, int half, int split = 0) {
     const int bsp = (int)h->bsp;
-    const int64_t ld = bsp;
-    const int64_t pL = stride_pL(h), pX = stride_pX(h), pW = (int64_t)bsp * bsp;
     if (split > 0 && half >= 0) return bad_shape("internal: the split inverse is not assembled half by half");
     for (int hh = lo; hh <= hi && hh < bsp; hh *= 2) {
         int pairs = bsp / (2 * hh), first = 0;
@@ -1150,39 +1170,19 @@ static gmrf_status doubling_levels(gmrf_handle* h, double* L, double* X, double*
             // split representation (split = p, a power of two): the first block column [0, p) of the rows >= p is not
             // assembled.  Level p: the first pair IS that part; above: the first pair keeps its columns [p, hh) --
             // T[:, p:hh] = L21[:, p:hh] X11[p:hh, p:hh],  X21[:, p:hh] = -X22 T[:, p:hh]
-            if (hh > split) {
-                const int q = split, w = hh - q;
-                GCHK(gemm(h, false, true, hh, w, w, TRI_B_LOWER, 0, 1.0, L + (int64_t)hh * ld + q, ld, X + (int64_t)q * ld + q, ld, 0.0,
-                          T + (int64_t)hh * ld + q, ld, pL, pX, pW));
-                GCHK(gemm(h, false, true, hh, w, hh, TRI_A_LOWER, 0, -1.0, X + (int64_t)hh * ld + hh, ld, T + (int64_t)hh * ld + q, ld, 0.0,
-                          X + (int64_t)hh * ld + q, ld, pX, pW, pX));
-            }
+            if (hh > split) GCHK(doubling_pair(h, L, stride_pL(h), X, T, hh, split, hh, hh - split, 1, 0));
             first = 1; pairs -= 1;
         }
         if (pairs <= 0) continue;
-        const int64_t st = (int64_t)2 * hh * ld + 2 * hh, o = first * st;
-        // T21 = L21 * X11
-        GCHK(gemm(h, false, true, hh, hh, hh, TRI_B_LOWER, 0, 1.0, L + o + (int64_t)hh * ld, ld, X + o, ld, 0.0,
-                  T + o + (int64_t)hh * ld, ld, pL, pX, pW, pairs, st, st, st));
-        // X21 = -X22 * T21
-        GCHK(gemm(h, false, true, hh, hh, hh, TRI_A_LOWER, 0, -1.0, X + o + (int64_t)hh * ld + hh, ld,
-                  T + o + (int64_t)hh * ld, ld, 0.0, X + o + (int64_t)hh * ld, ld, pX, pW, pX, pairs, st, st, st));
+        GCHK(doubling_pair(h, L, stride_pL(h), X, T, first * 2 * hh + hh, first * 2 * hh, hh, hh, pairs, (int64_t)2 * hh * bsp + 2 * hh));
     }
     return GMRF_OK;
 }
 
 // The top level (hh = bsp / 2, one pair) in its two halves: T21 = L21 X11, then X21 = -X22 T21.
 static gmrf_status doubling_top(gmrf_handle* h, double* L, double* X, double* T, bool first_product, bool second_product) {
-    const int bsp = (int)h->bsp, hh = bsp / 2;
-    const int64_t ld = bsp;
-    const int64_t pL = stride_pL(h), pX = stride_pX(h), pW = (int64_t)bsp * bsp;
-    if (first_product)
-        GCHK(gemm(h, false, true, hh, hh, hh, TRI_B_LOWER, 0, 1.0, L + (int64_t)hh * ld, ld, X, ld, 0.0, T + (int64_t)hh * ld, ld,
-                  pL, pX, pW));
-    if (second_product)
-        GCHK(gemm(h, false, true, hh, hh, hh, TRI_A_LOWER, 0, -1.0, X + (int64_t)hh * ld + hh, ld, T + (int64_t)hh * ld, ld, 0.0,
-                  X + (int64_t)hh * ld, ld, pX, pW, pX));
-    return GMRF_OK;
+    const int hh = (int)h->bsp / 2;
+    return doubling_pair(h, L, stride_pL(h), X, T, hh, 0, hh, hh, 1, 0, (first_product ? 1 : 0) | (second_product ? 2 : 0));
 }
 
 static gmrf_status fork_event(gmrf_handle* h, hipEvent_t* out) {
@@ -1384,6 +1384,50 @@ static EnvPanel env_panel(const gmrf_handle* h, int64_t i, int p, bool tail_ride
     return e;
 }
 
+// The factor's three tail-carrying products, one builder each: factor_blocks_range / potrf_block launch what they return, and
+// factor_fwd_ok asks gemm() about the same descriptions in a dry run.
+// G2 of block i >= 1,  S = D - C C^T  (src/tridiagonal_cholesky.jl:77): the product part.  Tile (R, R') sums over the columns from
+// max(kst[R], kst[R']) on -- the rest of the two row tiles is structurally zero.  accumulate: D_i is in S already.
+// (tail: the forward solve's row, y_{i-1}'s window against C^T, gives t = b_i - C y_{i-1} for the rows below rmax)
+static GemmCall g2_product(const gmrf_handle* h, int64_t i, bool accumulate, bool tail) {
+    const int bsp = (int)h->bsp, cm = (int)h->cmin, rm = (int)h->rmax;
+    const double* C = h->d_C + (i - 1) * c_blk(h);
+    const GemmTail tg{h->d_fy + (i - 1) * bsp + cm, h->n_pad, h->d_ft, bsp, nullptr, 0, 1.0};
+    return GemmCall(false, false, rm, rm, bsp - cm, -1.0, accumulate ? 1.0 : 0.0).a(C, c_ld(h), stride_pC(h)).b(C, c_ld(h), stride_pC(h))
+        .c(h->d_S, bsp, (int64_t)bsp * bsp).lower().work(2.0 * 64.0 * 64.0 * h->g2_tile_k * (double)h->B)
+        .k_begin(h->d_kst, h->d_kst).tail_ops(tail ? &tg : nullptr);
+}
+// The 256-column panel at column tile j of a block (S, L, X) with rows below it, and the bounds `ev` of its envelope (env_panel):
+// where L[below, P] lies.  Split representation with p = the panel width and no L blocks kept: L[p:, 0:p] is read by this panel's
+// own update only, so it is formed directly in the place it takes in Linv's storage (see gmrf_handle::xsplit)
+struct PanelBelow { double* Lb; int64_t pLb; };
+static PanelBelow panel_below(const gmrf_handle* h, double* L, double* X, int j) {
+    const int64_t at = ((int64_t)j * 64 + 256) * h->bsp + (int64_t)j * 64;
+    const bool in_slot = (j == 0 && h->xsplit == 256 && !h->keep_l);
+    return in_slot ? PanelBelow{X + at, stride_pX(h)} : PanelBelow{L + at, stride_pL(h)};
+}
+// L[below, P] = S[below, P] X_P^T: b(k, n) = X_P[n][k], zero for k > n (tile-K units: 1 + 2 + 3 + 4 of 16).
+// fy (this block's part of the forward solve, or null): y_P = X_P t_P is the product's tail row
+static GemmCall panel_product(const gmrf_handle* h, double* S, double* L, double* X, int j, const EnvPanel& ev, double* fy) {
+    const int64_t ld = h->bsp, oa = (int64_t)j * 64, oc = oa + 256;
+    const int m3 = (int)(ld / 64) - j - 4;
+    const PanelBelow lb = panel_below(h, L, X, j);
+    const GemmTail tp{h->d_ft + oa, ld, fy + oa, h->n_pad, nullptr, 0, 0.0};
+    return GemmCall(false, false, 64 * m3, 256, 256, 1.0, 0.0).a(S + oc * ld + oa, ld, ld * ld).b(X + oa * ld + oa, ld, stride_pX(h))
+        .c(lb.Lb, ld, lb.pLb).triangular(TRI_B_UPPER).work(2.0 * 64.0 * 64.0 * 64.0 * ev.units_pp * (double)h->B)
+        .k_begin(ev.pp_kb, nullptr).k_end(ev.pp_ke, nullptr).k_hints().tail_ops(fy ? &tp : nullptr);
+}
+// S[r,c] -= L[r,P] L[c,P]^T for the tiles right of / below the panel.  fy: t[below] -= L[below, P] y_P is the update's tail row
+static GemmCall panel_update(const gmrf_handle* h, double* S, double* L, double* X, int j, const EnvPanel& ev, double* fy) {
+    const int64_t ld = h->bsp, oa = (int64_t)j * 64, oc = oa + 256;
+    const int m3 = (int)(ld / 64) - j - 4;
+    const PanelBelow lb = panel_below(h, L, X, j);
+    const GemmTail tu{fy + oa, h->n_pad, h->d_ft + oc, ld, nullptr, 0, 1.0};
+    return GemmCall(false, false, m3 * 64, m3 * 64, 256, -1.0, 1.0).a(lb.Lb, ld, lb.pLb).b(lb.Lb, ld, lb.pLb).c(S + oc * ld + oc, ld, ld * ld)
+        .lower().work(2.0 * 64.0 * 64.0 * 64.0 * ev.units_upd * (double)h->B).k_begin(ev.upd_kb, ev.upd_kb).k_hints()
+        .tail_ops(fy ? &tu : nullptr);
+}
+
 // fy (batches on the 256-column panel route, factor_fwd_ok): also y_i = L_i^-1 t into fy ([B][n_pad]: this block's part), t = d_ft
 static gmrf_status potrf_block(gmrf_handle* h, double* S, double* L, double* X, double* T, int blk_id, double* fy = nullptr) {
     const int bsp = (int)h->bsp;
@@ -1491,7 +1535,7 @@ static gmrf_status potrf_block(gmrf_handle* h, double* S, double* L, double* X, 
         static const bool no_small = [] { const char* e = getenv("GMRF_PERSIST_PANELS"); return e && atoi(e) == 0; }();   // tuning aid
         const bool persist_panels = !no_small && !h->no_persist_panels && persist_fits(h, 4, 0, 4, 2);
         for (int j = 0; j < nt; j += 4) {
-            const int64_t oa = (int64_t)j * 64, ob = oa + 128, oc = oa + 256;
+            const int64_t oa = (int64_t)j * 64, ob = oa + 128;
             if (persist_panels) {
                 const double fl = (4.0 * t3 / 3.0 + 2.0 * t3 * (6.0 * 0.625 + 10.0 + 10.0 + 6.0 * 0.625)) * nb;
                 GCHK(launch_persist(h, S + oa * ld + oa, L + oa * ld + oa, X + oa * ld + oa, 4, 0, 4, 2, blk_id, fl));
@@ -1505,19 +1549,19 @@ static gmrf_status potrf_block(gmrf_handle* h, double* S, double* L, double* X, 
                 //  the time-weighted GEMM fraction rose to 0.66 and the job got SLOWER, 45.6 k against 48.1 k solves/s -- twelve
                 //  dependent 64^3 products take one CU 57 us, the four launches of then 39 us.  Removed in round 5.)
                 // L_BA = S_BA X_A^T (X_A lower triangular, stored [n][k])
-                GCHK(gemm(h, false, false, 128, 128, 128, TRI_B_UPPER, 0, 1.0, S + ob * ld + oa, ld, X + oa * ld + oa, ld, 0.0, L + ob * ld + oa, ld,
-                          sa.pS, sa.pX, sa.pL, 1, 0, 0, 0, nullptr, 0, 0, 0, 2.0 * t3 * 3.0 * 2.0 * nb));
+                GCHK(gemm(h, GemmCall(false, false, 128, 128, 128, 1.0, 0.0).a(S + ob * ld + oa, ld, sa.pS).b(X + oa * ld + oa, ld, sa.pX)
+                                 .c(L + ob * ld + oa, ld, sa.pL).triangular(TRI_B_UPPER).work(2.0 * t3 * 3.0 * 2.0 * nb)));
                 // S_BB -= L_BA L_BA^T (lower tiles), and T = L_BA X_A -- the first half of X_BA = -X_B (L_BA X_A), the level-128 doubling step of this pair (T is the
                 // work block doubling_levels uses) -- reads L_BA and X_A only, as the update of S_BB reads L_BA only: ONE launch of
                 // 192 + 256 workgroups per 64 problems in front of the second diagonal block instead of a launch on either side of it
                 GCHK(gemm_pair(h,
-                               GemmOne{false, 128, 128, 128, 0, 1, -1.0, L + ob * ld + oa, ld, L + ob * ld + oa, ld, 1.0, S + ob * ld + ob, ld,
-                                       sa.pL, sa.pL, sa.pS, 2.0 * t3 * 2.0 * 3.0 * nb},
-                               GemmOne{true, 128, 128, 128, TRI_B_LOWER, 0, 1.0, L + ob * ld + oa, ld, X + oa * ld + oa, ld, 0.0, T + ob * ld + oa, ld,
-                                       sa.pL, sa.pX, pW, -1.0}));
+                               GemmCall(false, false, 128, 128, 128, -1.0, 1.0).a(L + ob * ld + oa, ld, sa.pL).b(L + ob * ld + oa, ld, sa.pL)
+                                   .c(S + ob * ld + ob, ld, sa.pS).lower().work(2.0 * t3 * 2.0 * 3.0 * nb),
+                               GemmCall(false, true, 128, 128, 128, 1.0, 0.0).a(L + ob * ld + oa, ld, sa.pL).b(X + oa * ld + oa, ld, sa.pX)
+                                   .c(T + ob * ld + oa, ld, pW).triangular(TRI_B_LOWER)));
                 GCHK(diag128(j + 2));
-                GCHK(gemm(h, false, true, 128, 128, 128, TRI_A_LOWER, 0, -1.0, X + ob * ld + ob, ld, T + ob * ld + oa, ld, 0.0, X + ob * ld + oa, ld,
-                          sa.pX, pW, sa.pX));
+                GCHK(gemm(h, GemmCall(false, true, 128, 128, 128, -1.0, 0.0).a(X + ob * ld + ob, ld, sa.pX).b(T + ob * ld + oa, ld, pW)
+                                 .c(X + ob * ld + oa, ld, sa.pX).triangular(TRI_A_LOWER)));
             }
             const int m3 = nt - j - 4;                             // row tiles below the panel
             // forward solve (fy): y_P = X_P t_P is the tail row of the panel product, t[below] -= L[below, P] y_P the tail row of the
@@ -1535,26 +1579,13 @@ static gmrf_status potrf_block(gmrf_handle* h, double* S, double* L, double* X, 
                 }
                 continue;
             }
-            const GemmTail tp{h->d_ft + oa, pT, fy + oa, pY, nullptr, 0, 0.0};
-            const GemmTail tu{fy + oa, pY, h->d_ft + oc, pT, nullptr, 0, 1.0};
-            // Split representation with p = the panel width and no L blocks kept: L[p:, 0:p] is read by this panel's own
-            // update only, so it is formed directly in the place it takes in Linv's storage (see gmrf_handle::xsplit)
-            const bool in_slot = (j == 0 && h->xsplit == 256 && !h->keep_l);
-            double* Lb = in_slot ? X + oc * ld + oa : L + oc * ld + oa;
-            const int64_t pLb = in_slot ? sa.pX : sa.pL;
             // (round 19) Envelope bounds, relative to the panel (gmrf_handle::env_host): the rows below the panel that S = D_i - C C^T did
             // not write and no earlier panel has met are still D_i's -- row tile bm of S[below, P] is zero outside [kb, ke), of
             // L[below, P] left of kb.  The products skip those K ranges (sums of 0 x: the same bits); a panel product whose last row
             // tile carries the forward solve's tail row keeps that tile's full range (the tail's own).
             const EnvPanel ev = env_panel(h, blk_id - 1, j / 4, fy != nullptr);
-            // L[below, P] = S[below, P] X_P^T: b(k, n) = X_P[n][k], zero for k > n (tile-K units: 1 + 2 + 3 + 4 of 16)
-            GCHK(gemm(h, false, false, 64 * m3, 256, 256, TRI_B_UPPER, 0, 1.0, S + oc * ld + oa, ld, X + oa * ld + oa, ld, 0.0, Lb, ld,
-                      sa.pS, sa.pX, pLb, 1, 0, 0, 0, nullptr, 0, 0, 0, 2.0 * t3 * ev.units_pp * nb, ev.pp_kb, nullptr, nullptr, false,
-                      fy ? &tp : nullptr, ev.pp_ke, true));
-            // S[r,c] -= L[r,P] L[c,P]^T for the tiles right of / below the panel
-            GCHK(gemm(h, false, false, m3 * 64, m3 * 64, 256, 0, 1, -1.0, Lb, ld, Lb, ld, 1.0, S + oc * ld + oc, ld, pLb, pLb, sa.pS,
-                      1, 0, 0, 0, nullptr, 0, 0, 0, 2.0 * t3 * ev.units_upd * nb, ev.upd_kb, ev.upd_kb, nullptr, false,
-                      fy ? &tu : nullptr, nullptr, true));
+            GCHK(gemm(h, panel_product(h, S, L, X, j, ev, fy)));
+            GCHK(gemm(h, panel_update(h, S, L, X, j, ev, fy)));
         }
         // X = L^-1 by recursive doubling over the 256-wide diagonal inverses -- or, split representation, everything
         // but its first block column below row p, whose place L[p:, 0:p] takes (see gmrf_handle::xsplit)
@@ -1634,8 +1665,8 @@ static gmrf_status potrf_block(gmrf_handle* h, double* S, double* L, double* X, 
             const int j0 = cend - pw, mr = nt - cend;
             const double* Lp = L + (int64_t)cend * 64 * ld + (int64_t)j0 * 64;
             double* Sr = S + (int64_t)cend * 64 * ld + (int64_t)cend * 64;
-            GCHK(gemm(h, false, false, mr * 64, mr * 64, pw * 64, 0, 1, -1.0, Lp, ld, Lp, ld, 1.0, Sr, ld, sa.pL, sa.pL,
-                      sa.pS, 1, 0, 0, 0, nullptr, 0, 0, 0, 2.0 * 64.0 * 64.0 * (pw * 64.0) * (mr * (mr + 1) / 2) * (double)h->B));
+            GCHK(gemm(h, GemmCall(false, false, mr * 64, mr * 64, pw * 64, -1.0, 1.0).a(Lp, ld, sa.pL).b(Lp, ld, sa.pL).c(Sr, ld, sa.pS).lower()
+                             .work(2.0 * 64.0 * 64.0 * (pw * 64.0) * (mr * (mr + 1) / 2) * (double)h->B)));
         }
         if (overlap && j + 1 == nt / 2) {
             HIPCHK(hipEventRecord(ev_fork, h->stream));
@@ -1786,17 +1817,11 @@ static gmrf_status factor_blocks_range(gmrf_handle* h, int64_t i0, int64_t i1) {
                 else hipLaunchKernelGGL(spmm_bxt<32>, grid, dim3(256), 0, h->stream, ba);
                 HIPCHK(hipGetLastError());
             } else {
-                GCHK(gemm(h, false, false, rm, W, W, TRI_B_UPPER, 0, 1.0, h->d_B + cm, ld,
-                          Xp + (int64_t)cm * ld + cm, ld, 0.0, C, ldc, bstride, pX, pC, 1, 0, 0, 0, nullptr, 0, 0, 0, -1.0,
-                          h->d_kst, nullptr, nullptr));
+                GCHK(gemm(h, GemmCall(false, false, rm, W, W, 1.0, 0.0).a(h->d_B + cm, ld, bstride).b(Xp + (int64_t)cm * ld + cm, ld, pX)
+                                 .c(C, ldc, pC).triangular(TRI_B_UPPER).k_begin(h->d_kst, nullptr)));
             }
-            // S = D - C C^T             (src/tridiagonal_cholesky.jl:77): the product part.  Tile (R, R') sums over
-            // the columns from max(kst[R], kst[R']) on -- the rest of the two row tiles is structurally zero.
-            // (forward solve: its tail row, y_{i-1}'s window against C^T, gives t = b_i - C y_{i-1} for the rows below rmax)
-            const GemmTail tg{h->d_fy + (i - 1) * bsp + cm, h->n_pad, h->d_ft, bsp, nullptr, 0, 1.0};
-            GCHK(gemm(h, false, false, rm, rm, W, 0, 1, -1.0, C, ldc, C, ldc, scatter_in_bxt ? 1.0 : 0.0, h->d_S, ld, pC, pC,
-                      bstride, 1, 0, 0, 0, nullptr, 0, 0, 0, 2.0 * 64.0 * 64.0 * h->g2_tile_k * (double)h->B,
-                      h->d_kst, h->d_kst, nullptr, false, h->fwd_run ? &tg : nullptr));
+            // S = D - C C^T: the product part (with the forward solve's tail row)
+            GCHK(gemm(h, g2_product(h, i, scatter_in_bxt, h->fwd_run)));
         }
         if (h->diag_count[i] > 0 && !scatter_in_bxt) {
             hipLaunchKernelGGL(scatter_block, dim3((unsigned)((h->diag_count[i] + 255) / 256), nb), dim3(256), 0,
@@ -1805,7 +1830,7 @@ static gmrf_status factor_blocks_range(gmrf_handle* h, int64_t i0, int64_t i1) {
             HIPCHK(hipGetLastError());
         }
         if (i == h->tw_blk && h->tw_hj)      // twisted order, meeting block: S -= H_m H_m^T = HJ HJ^T (J is an orthogonal flip)
-            GCHK(gemm(h, false, false, bsp, bsp, bsp, 0, 1, -1.0, h->tw_hj, ld, h->tw_hj, ld, 1.0, h->d_S, ld, 0, 0, 0));
+            GCHK(gemm(h, GemmCall(false, false, bsp, bsp, bsp, -1.0, 1.0).a(h->tw_hj, ld, 0).b(h->tw_hj, ld, 0).c(h->d_S, ld, 0).lower()));
         if (h->bsp > h->bs) {
             hipLaunchKernelGGL(pad_identity, dim3((unsigned)((h->bsp - h->bs + 255) / 256), nb), dim3(256), 0,
                                h->stream, h->d_S, ld, (int)h->bs, bsp, bstride);
@@ -1813,7 +1838,7 @@ static gmrf_status factor_blocks_range(gmrf_handle* h, int64_t i0, int64_t i1) {
         }
         GCHK(potrf_block(h, h->d_S, L, X, h->d_T, (int)(i + 1), h->fwd_run ? h->d_fy + i * bsp : nullptr));
         if (i == h->tw_blk && h->tw_w)       // W = L_m^-1 HJ: the coupling of the twisted sweeps' meeting corrections
-            GCHK(gemm(h, false, true, bsp, bsp, bsp, 0, 0, 1.0, X, ld, h->tw_hj, ld, 0.0, h->tw_w, ld, 0, 0, 0));
+            GCHK(gemm(h, GemmCall(false, true, bsp, bsp, bsp, 1.0, 0.0).a(X, ld, 0).b(h->tw_hj, ld, 0).c(h->tw_w, ld, 0)));
         if (!h->keep_l) {
             // L_i lives in a work buffer that the next block overwrites: its log-determinant part is taken now
             hipLaunchKernelGGL(logdet_blocks, dim3(1, nb), dim3(256), 0, h->stream, L, bstride, ld, (int)h->bs,
@@ -1829,13 +1854,10 @@ static gmrf_status factor_blocks_range(gmrf_handle* h, int64_t i0, int64_t i1) {
 // coupling products never are.  The factor stays full until the next factorisation.
 static gmrf_status ensure_full_inverse(gmrf_handle* h) {
     if (h->xsplit <= 0) return GMRF_OK;
-    const int bsp = (int)h->bsp, p = h->xsplit, q = bsp - p;
-    const int64_t ld = bsp, bstride = (int64_t)bsp * bsp, pX = stride_pX(h), pW = bstride;
+    const int bsp = (int)h->bsp, p = h->xsplit;
     for (int64_t i = 0; i < h->N; ++i) {
-        double* X = h->d_Linv + i * bstride;
-        double* T = h->d_T + (int64_t)p * ld;
-        GCHK(gemm(h, false, true, q, p, p, TRI_B_LOWER, 0, 1.0, X + (int64_t)p * ld, ld, X, ld, 0.0, T, ld, pX, pX, pW));
-        GCHK(gemm(h, false, true, q, p, q, TRI_A_LOWER, 0, -1.0, X + (int64_t)p * ld + p, ld, T, ld, 0.0, X + (int64_t)p * ld, ld, pX, pW, pX));
+        double* X = h->d_Linv + i * blk_elems(h);
+        GCHK(doubling_pair(h, X, stride_pX(h), X, h->d_T, p, 0, bsp - p, p, 1, 0));
     }
     h->xsplit = 0;
     return GMRF_OK;
@@ -1865,29 +1887,15 @@ static gmrf_status factor_fwd_ok(gmrf_handle* h, bool* ok) {
         HIPCHK(hipMalloc(&h->d_ft, sizeof(double) * (size_t)(h->B * h->bsp)));
         h->fy_elems = elems;
     }
-    const int64_t ld = bsp, bstride = (int64_t)bsp * bsp, pX = stride_pX(h), pL = stride_pL(h), pC = stride_pC(h);
-    const int cm = (int)h->cmin, rm = (int)h->rmax, W = bsp - cm;
-    double* S = h->d_S; double* X = h->d_Linv; double* L = h->d_L;
     h->tail_probe = true; h->tail_refused = false;
     gmrf_status st = GMRF_OK;
-    if (h->N > 1) {
-        const GemmTail tg{h->d_fy + cm, h->n_pad, h->d_ft, bsp, nullptr, 0, 1.0};
-        st = gemm(h, false, false, rm, rm, W, 0, 1, -1.0, h->d_C, c_ld(h), h->d_C, c_ld(h), 0.0, S, ld, pC, pC, bstride, 1, 0, 0, 0,
-                  nullptr, 0, 0, 0, -1.0, h->d_kst, h->d_kst, nullptr, false, &tg);
-    }
-    for (int j = 0; j + 4 < nt && st == GMRF_OK; j += 4) {
-        const int64_t oa = (int64_t)j * 64, oc = oa + 256;
-        const int m3 = nt - j - 4;
-        const GemmTail tp{h->d_ft + oa, bsp, h->d_fy + oa, h->n_pad, nullptr, 0, 0.0};
-        const GemmTail tu{h->d_fy + oa, h->n_pad, h->d_ft + oc, bsp, nullptr, 0, 1.0};
+    if (h->N > 1) st = gemm(h, g2_product(h, 1, false, true));
+    for (int j = 0; j + 4 < nt && st == GMRF_OK; j += 4) {         // (the panels with rows below them)
         // (the envelope bounds potrf_block passes -- those of a block behind the first, as good as any: what qualifies does not
-        // depend on their values)
+        // depend on their values, nor on where L[below, P] lies)
         const EnvPanel ev = env_panel(h, std::min<int64_t>(1, h->N - 1), j / 4, true);
-        st = gemm(h, false, false, 64 * m3, 256, 256, TRI_B_UPPER, 0, 1.0, S + oc * ld + oa, ld, X + oa * ld + oa, ld, 0.0, L + oc * ld + oa, ld,
-                  bstride, pX, pL, 1, 0, 0, 0, nullptr, 0, 0, 0, -1.0, ev.pp_kb, nullptr, nullptr, false, &tp, ev.pp_ke, true);
-        if (st == GMRF_OK)
-            st = gemm(h, false, false, m3 * 64, m3 * 64, 256, 0, 1, -1.0, L + oc * ld + oa, ld, L + oc * ld + oa, ld, 1.0, S + oc * ld + oc, ld,
-                      pL, pL, bstride, 1, 0, 0, 0, nullptr, 0, 0, 0, -1.0, ev.upd_kb, ev.upd_kb, nullptr, false, &tu, nullptr, true);
+        st = gemm(h, panel_product(h, h->d_S, h->d_L, h->d_Linv, j, ev, h->d_fy));
+        if (st == GMRF_OK) st = gemm(h, panel_update(h, h->d_S, h->d_L, h->d_Linv, j, ev, h->d_fy));
     }
     h->tail_probe = false;
     *ok = st == GMRF_OK && !h->tail_refused;
@@ -2226,9 +2234,9 @@ static gmrf_status sweep_launches(gmrf_handle* h, bool backward, int kp, double*
             const int rows = backward ? wc : rm, kdim = backward ? rm : wc;
             if (via_gemm) {
                 // T[r][m] = P[r][m] - sum_k y[r][k] c(k,m): the panel is the [m][k] operand, the block the other
-                GCHK(gemm(h, false, backward, kp, rows, kdim, 0, 0, -1.0, xin, npad, Cs, ldc, 1.0, out, npad, pPanel, pCm,
-                          pPanel, 1, 0, 0, 0, nullptr, 0, 0, 0, 2.0 * h->c_streamed * kp * nprob,
-                          nullptr, backward ? nullptr : h->d_kst, backward ? h->d_mend : nullptr, tail));
+                GCHK(gemm(h, GemmCall(false, backward, kp, rows, kdim, -1.0, 1.0).a(xin, npad, pPanel).b(Cs, ldc, pCm).c(out, npad, pPanel)
+                                 .work(2.0 * h->c_streamed * kp * nprob).k_begin(nullptr, backward ? nullptr : h->d_kst)
+                                 .k_end(nullptr, backward ? h->d_mend : nullptr).tail_row(tail)));
             } else {
                 s.Mat = Cs; s.ld = ldc; s.Xin = xin; s.ldx = npad; s.Bin = out; s.ldb = npad; s.Out = out; s.ldo = npad;
                 s.rows = rows; s.kdim = kdim; s.sub = 1;
@@ -2241,8 +2249,14 @@ static gmrf_status sweep_launches(gmrf_handle* h, bool backward, int kp, double*
         // y_i = Linv_i T   /   x_i = Linv_i^T T
         const double* X = h->d_Linv + i * bstride;
         double* yout = Yout + i * bsp;
-        // (dout) columns c of a product that starts at column `first` of the block are the dofs i bs + first + c, real while first + c < bs
-        auto direct = [&](int first) { return GemmTail{nullptr, 0, nullptr, 0, nullptr, 0, 0.0, dout, i * h->bs + first, (int)h->bs - first}; };
+        // On the GEMM, for the n columns from `first` on with the diagonal block Xd of the inverse -- forward: Linv stored [m][k], zero
+        // for k > m; backward: Linv^T, stored [k][m], zero for k < m.  (dout) column c of the product is the dof i bs + first + c, real
+        // while first + c < bs
+        auto tri_product = [&](int first, int n, const double* Xd) {
+            const GemmTail d{nullptr, 0, nullptr, 0, nullptr, 0, 0.0, dout, i * h->bs + first, (int)h->bs - first};
+            return gemm(h, GemmCall(false, backward, kp, n, n, 1.0, 0.0).a(rhs + first, npad, pPanel).b(Xd, ld, pX).c(yout + first, npad, pPanel)
+                               .triangular(backward ? TRI_B_LOWER : TRI_B_UPPER).tail_row(tail).tail_ops(dout ? &d : nullptr));
+        };
         if (h->xsplit > 0) {
             // split representation: [X_aa 0; L_ba X_bb] in the block's storage.  forward: y_a = X_aa t_a, t_b -= L_ba y_a,
             // y_b = X_bb t_b;  backward: x_b = X_bb^T t_b, t_a -= L_ba^T x_b, x_a = X_aa^T t_a.  Same bytes, same flops.
@@ -2252,27 +2266,18 @@ static gmrf_status sweep_launches(gmrf_handle* h, bool backward, int kp, double*
             for (int part = 0; part < 3; ++part) {
                 const int which = backward ? 2 - part : part;          // 0: aa, 1: ba, 2: bb
                 if (via_gemm) {
-                    // (the defaults up to the tail flag)
-                    constexpr int64_t z0 = 0;
-                    const GemmTail da = direct(0), db = direct(p);
-                    if (which == 0)
-                        GCHK(gemm(h, false, backward, kp, p, p, backward ? TRI_B_LOWER : TRI_B_UPPER, 0, 1.0, rhs, npad, X, ld, 0.0, yout, npad,
-                                  pPanel, pX, pPanel, 1, z0, z0, z0, nullptr, z0, z0, 0, -1.0, nullptr, nullptr, nullptr, tail,
-                                  dout ? &da : nullptr));
-                    else if (which == 2)
-                        GCHK(gemm(h, false, backward, kp, q, q, backward ? TRI_B_LOWER : TRI_B_UPPER, 0, 1.0, rhs + p, npad, Xbb, ld, 0.0,
-                                  yout + p, npad, pPanel, pX, pPanel, 1, z0, z0, z0, nullptr, z0, z0, 0, -1.0, nullptr, nullptr, nullptr, tail,
-                                  dout ? &db : nullptr));
+                    if (which == 0) GCHK(tri_product(0, p, X));
+                    else if (which == 2) GCHK(tri_product(p, q, Xbb));
                     else if (!backward)
-                        GCHK(gemm(h, false, false, kp, q, p, 0, 0, -1.0, yout, npad, Lba, ld, 1.0, rhs + p, npad, pPanel, pX, pPanel));
+                        GCHK(gemm(h, GemmCall(false, false, kp, q, p, -1.0, 1.0).a(yout, npad, pPanel).b(Lba, ld, pX).c(rhs + p, npad, pPanel)));
                     else {
                         // (round 19) envelope: column tile bn of L_ba = L[256:, 0:256] is zero below row env_ken[bn] (gmrf_handle)
                         const bool env = p == 256 && h->env_ok && !h->no_env && !h->tw && !h->tw_half && h->tw_blk < 0 && h->env_ken_has[(size_t)i];
                         double units = 0.0;
                         for (int bn = 0; env && bn < 4; ++bn) units += h->env_ken[(size_t)(i * 4 + bn)] / 64;
-                        GCHK(gemm(h, false, true, kp, p, q, 0, 0, -1.0, yout + p, npad, Lba, ld, 1.0, rhs, npad, pPanel, pX, pPanel,
-                                  1, z0, z0, z0, nullptr, z0, z0, 0, env ? 2.0 * kp * 64.0 * 64.0 * units * nprob : -1.0, nullptr, nullptr,
-                                  env ? h->d_env_ken + i * 4 : nullptr, tail, nullptr, nullptr, env));
+                        GCHK(gemm(h, GemmCall(false, true, kp, p, q, -1.0, 1.0).a(yout + p, npad, pPanel).b(Lba, ld, pX).c(rhs, npad, pPanel)
+                                         .work(env ? 2.0 * kp * 64.0 * 64.0 * units * nprob : -1.0)
+                                         .k_end(nullptr, env ? h->d_env_ken + i * 4 : nullptr).k_hints(env).tail_row(tail)));
                     }
                 } else {
                     s.ld = ld; s.ldx = npad; s.ldo = npad; s.pMat = pX; s.pXin = pPanel; s.pOut = pPanel; s.kst = nullptr; s.mend = nullptr;
@@ -2286,10 +2291,7 @@ static gmrf_status sweep_launches(gmrf_handle* h, bool backward, int kp, double*
                 }
             }
         } else if (via_gemm) {
-            // forward: Linv stored [m][k], zero for k > m; backward: Linv^T, stored [k][m], zero for k < m
-            const GemmTail da = direct(0);
-            GCHK(gemm(h, false, backward, kp, bsp, bsp, backward ? TRI_B_LOWER : TRI_B_UPPER, 0, 1.0, rhs, npad, X, ld, 0.0,
-                      yout, npad, pPanel, pX, pPanel, 1, 0, 0, 0, nullptr, 0, 0, 0, -1.0, nullptr, nullptr, nullptr, tail, dout ? &da : nullptr));
+            GCHK(tri_product(0, bsp, X));
         } else {
             s.Mat = X; s.ld = ld; s.Xin = rhs; s.ldx = npad; s.Bin = nullptr; s.ldb = 0; s.Out = yout; s.ldo = npad;
             s.rows = bsp; s.kdim = bsp; s.sub = 0;
@@ -5831,6 +5833,52 @@ static gmrf_status need_single(gmrf_handle* h) {
     return GMRF_OK;
 }
 
+// The Takahashi block step that var_exact and selinv_pattern share (see var_exact for the recurrence).  Its work block d_V holds
+// T1 (tk_t1) and behind it M (tk_m), one bsp x bsp block per problem each; Y is d_T.
+static double* tk_t1(const gmrf_handle* h) { return h->d_V; }
+static double* tk_m(const gmrf_handle* h) { return h->d_V + blk_elems(h) * h->B; }
+static gmrf_status tk_alloc(gmrf_handle* h) {
+    const int64_t bstride = blk_elems(h);
+    if (!h->d_V || h->v_elems < 2 * bstride * h->B) {
+        HIPCHK(hipStreamSynchronize(h->stream));
+        free_dev(h->d_V); h->d_V = nullptr; h->v_elems = 0;
+        HIPCHK(hipMalloc(&h->d_V, sizeof(double) * 2 * (size_t)bstride * (size_t)h->B));
+        h->v_elems = 2 * bstride * h->B;
+    }
+    return GMRF_OK;
+}
+// Block i < N - 1, Sg = the leading block of Sigma_{i+1,i+1} (full, mirrored):  T1 = S' C_w,  M = T1^T C_w,  Y[cmin:] = (I + M) X[cmin:]
+static gmrf_status tk_coupled_y(gmrf_handle* h, int64_t i, const double* Sg) {
+    const int bsp = (int)h->bsp, cm = (int)h->cmin, rm = (int)h->rmax, wc = bsp - cm, twc = wc / 64;
+    const int64_t ld = bsp, pX = stride_pX(h), pCm = stride_pC(h), pW = blk_elems(h);
+    const double* Xw = h->d_Linv + i * pW + (int64_t)cm * ld;      // X[cmin:, :]
+    const double* C = h->d_C + i * c_blk(h);
+    double* V1 = tk_t1(h); double* V2 = tk_m(h); double* Yw = h->d_T + (int64_t)cm * ld;
+    // T1 = S' C_w
+    GCHK(gemm(h, GemmCall(false, true, rm, wc, rm, 1.0, 0.0).a(Sg, ld, pW).b(C, c_ld(h), pCm).c(V1, ld, pW)
+                     .work(2.0 * rm * h->c_streamed * (double)h->B).k_end(nullptr, h->d_mend)));
+    // M = T1^T C_w (lower tiles; T1 taken as it lies, [k][m]), mirrored
+    GCHK(gemm(h, GemmCall(true, true, wc, wc, rm, 1.0, 0.0).a(V1, ld, pW).b(C, c_ld(h), pCm).c(V2, ld, pW).lower().k_end(nullptr, h->d_mend)));
+    hipLaunchKernelGGL(transpose_tiles, dim3((unsigned)(twc * (twc + 1) / 2), (unsigned)h->B), dim3(256), 0, h->stream, V2, ld, V2, ld, pW, pW, twc, twc, 2);
+    HIPCHK(hipGetLastError());
+    // Y[cmin:, :] = M X[cmin:, :] + X[cmin:, :]   (column tile u of X[cmin:, :] starts at row max(0, 64 u - cmin))
+    return gemm(h, GemmCall(false, true, wc, bsp, wc, 1.0, 1.0).a(V2, ld, pW).b(Xw, ld, pX).c(Yw, ld, pW).addend(Xw, ld, pX)
+                       .k_begin(nullptr, h->d_kbx));
+}
+// S_ii[0:ms, 0:ms] = X^T Y on its lower tiles into Sn (X taken as it lies, [k][m]; the rows below cmin of Y are X's; uncoupled: Y = X)
+static gmrf_status tk_xty(gmrf_handle* h, int64_t i, bool coupled, int ms, double* Sn) {
+    const int bsp = (int)h->bsp, cm = (int)h->cmin;
+    const int64_t ld = bsp, pX = stride_pX(h), pW = blk_elems(h);
+    const double* X = h->d_Linv + i * pW;
+    if (!coupled || cm > 0)
+        GCHK(gemm(h, GemmCall(true, true, ms, ms, coupled ? cm : bsp, 1.0, 0.0).a(X, ld, pX).b(X, ld, pX).c(Sn, ld, pW)
+                         .triangular(TRI_A_UPPER | TRI_B_LOWER).lower()));
+    if (coupled)
+        GCHK(gemm(h, GemmCall(true, true, ms, ms, bsp - cm, 1.0, cm > 0 ? 1.0 : 0.0).a(X + (int64_t)cm * ld, ld, pX)
+                         .b(h->d_T + (int64_t)cm * ld, ld, pW).c(Sn, ld, pW).lower().k_begin(h->d_kbx, nullptr)));
+    return GMRF_OK;
+}
+
 // seeded: the twisted order's bottom half -- the caller has put the whole Sigma of the last block (its start, seeded by the
 // meeting block) into d_S; the recurrence goes on from there.
 static gmrf_status var_exact(gmrf_handle* h, double* d_out, bool seeded = false) {
@@ -5848,22 +5896,15 @@ static gmrf_status var_exact(gmrf_handle* h, double* d_out, bool seeded = false)
     // [k][m] operand forced), every product on gemm_f64_dma.
     const int bsp = (int)h->bsp;
     const int64_t ld = bsp, bstride = (int64_t)bsp * bsp;
-    const int64_t pX = stride_pX(h), pCm = stride_pC(h), pW = bstride;
-    const int cm = (int)h->cmin, rm = (int)h->rmax, wc = bsp - cm;
+    const int64_t pX = stride_pX(h), pW = bstride;
+    const int cm = (int)h->cmin, rm = (int)h->rmax;
     const unsigned nb = (unsigned)h->B;
     GCHK(ensure_full_inverse(h));
-    if (!h->d_V || h->v_elems < 2 * bstride * h->B) {
-        HIPCHK(hipStreamSynchronize(h->stream));
-        free_dev(h->d_V); h->d_V = nullptr; h->v_elems = 0;
-        HIPCHK(hipMalloc(&h->d_V, sizeof(double) * 2 * (size_t)bstride * (size_t)h->B));
-        h->v_elems = 2 * bstride * h->B;
-    }
+    GCHK(tk_alloc(h));
     double* Sg = h->d_S;     // leading block of Sigma_{i+1,i+1} (full, mirrored)
     double* Sn = h->d_W;
     double* Y = h->d_T;
-    double* V1 = h->d_V;                                 // T1
-    double* V2 = h->d_V + bstride * h->B;                // M
-    const int nt = bsp / 64, trm = rm / 64, twc = wc / 64;
+    const int nt = bsp / 64, trm = rm / 64;
     for (int64_t i = h->N - 1; i >= 0; --i) {
         if (seeded && i == h->N - 1) {
             hipLaunchKernelGGL(extract_diag_dense, dim3((unsigned)((h->bs + 255) / 256), nb), dim3(256), 0, h->stream, Sg, ld, (int)h->bs,
@@ -5873,20 +5914,7 @@ static gmrf_status var_exact(gmrf_handle* h, double* d_out, bool seeded = false)
         }
         const double* X = h->d_Linv + i * bstride;
         const bool coupled = i < h->N - 1;
-        if (coupled) {
-            const double* C = h->d_C + i * c_blk(h);
-            // T1 = S' C_w
-            GCHK(gemm(h, false, true, rm, wc, rm, 0, 0, 1.0, Sg, ld, C, c_ld(h), 0.0, V1, ld, pW, pCm, pW,
-                      1, 0, 0, 0, nullptr, 0, 0, 0, 2.0 * rm * h->c_streamed * (double)h->B, nullptr, nullptr, h->d_mend));
-            // M = T1^T C_w (lower tiles; T1 taken as it lies, [k][m]), mirrored
-            GCHK(gemm(h, true, true, wc, wc, rm, 0, 1, 1.0, V1, ld, C, c_ld(h), 0.0, V2, ld, pW, pCm, pW,
-                      1, 0, 0, 0, nullptr, 0, 0, 0, -1.0, nullptr, nullptr, h->d_mend));
-            hipLaunchKernelGGL(transpose_tiles, dim3((unsigned)(twc * (twc + 1) / 2), nb), dim3(256), 0, h->stream, V2, ld, V2, ld, pW, pW, twc, twc, 2);
-            HIPCHK(hipGetLastError());
-            // Y[cmin:, :] = M X[cmin:, :] + X[cmin:, :]   (column tile u of X[cmin:, :] starts at row max(0, 64 u - cmin))
-            GCHK(gemm(h, false, true, wc, bsp, wc, 0, 0, 1.0, V2, ld, X + (int64_t)cm * ld, ld, 1.0, Y + (int64_t)cm * ld, ld, pW, pX, pW,
-                      1, 0, 0, 0, X + (int64_t)cm * ld, ld, pX, 0, -1.0, nullptr, h->d_kbx, nullptr));
-        }
+        if (coupled) GCHK(tk_coupled_y(h, i, Sg));
         // diag(S_ii): of the last block processed (i = 0) and of the columns >= rmax by column dot products; the columns below
         // rmax of the other blocks are the diagonal of the leading block formed below (saves reading X and Y once more)
         const int u0 = (i == 0) ? 0 : trm;
@@ -5897,14 +5925,7 @@ static gmrf_status var_exact(gmrf_handle* h, double* d_out, bool seeded = false)
         }
         if (i == 0) break;                               // nobody needs the leading block of S_00
         // leading block of S_ii for the next step: the product X^T Y on its lower tiles (X taken as it lies, [k][m]), mirrored
-        if (coupled) {
-            if (cm > 0)
-                GCHK(gemm(h, true, true, rm, rm, cm, TRI_A_UPPER | TRI_B_LOWER, 1, 1.0, X, ld, X, ld, 0.0, Sn, ld, pX, pX, pW));
-            GCHK(gemm(h, true, true, rm, rm, wc, 0, 1, 1.0, X + (int64_t)cm * ld, ld, Y + (int64_t)cm * ld, ld, cm > 0 ? 1.0 : 0.0, Sn, ld, pX, pW, pW,
-                      1, 0, 0, 0, nullptr, 0, 0, 0, -1.0, h->d_kbx, nullptr, nullptr));
-        } else {
-            GCHK(gemm(h, true, true, rm, rm, bsp, TRI_A_UPPER | TRI_B_LOWER, 1, 1.0, X, ld, X, ld, 0.0, Sn, ld, pX, pX, pW));
-        }
+        GCHK(tk_xty(h, i, coupled, rm, Sn));
         hipLaunchKernelGGL(transpose_tiles, dim3((unsigned)(trm * (trm + 1) / 2), nb), dim3(256), 0, h->stream, Sn, ld, Sn, ld, pW, pW, trm, trm, 2);
         HIPCHK(hipGetLastError());
         {
@@ -5996,53 +6017,28 @@ static gmrf_status selinv_plan(gmrf_handle* h, const gmrf_csr* S, const char* wh
 static gmrf_status selinv_pattern(gmrf_handle* h, double* d_out) {
     const int bsp = (int)h->bsp;
     const int64_t ld = bsp, bstride = (int64_t)bsp * bsp;
-    const int64_t pX = stride_pX(h), pCm = stride_pC(h), pW = bstride;
+    const int64_t pX = stride_pX(h), pW = bstride;
     const int cm = (int)h->cmin, rm = (int)h->rmax, wc = bsp - cm;
     const unsigned nb = (unsigned)h->B;
     GCHK(ensure_full_inverse(h));
-    if (!h->d_V || h->v_elems < 2 * bstride * h->B) {
-        HIPCHK(hipStreamSynchronize(h->stream));
-        free_dev(h->d_V); h->d_V = nullptr; h->v_elems = 0;
-        HIPCHK(hipMalloc(&h->d_V, sizeof(double) * 2 * (size_t)bstride * (size_t)h->B));
-        h->v_elems = 2 * bstride * h->B;
-    }
+    GCHK(tk_alloc(h));
     double* Sg = h->d_S;
     double* Sn = h->d_W;
-    double* Y = h->d_T;
-    double* V1 = h->d_V;                                 // T1
-    double* V2 = h->d_V + bstride * h->B;                // M, then Sigma_{i+1,i}[0:rmax, :]
-    const int trm = rm / 64, twc = wc / 64;
+    double* V2 = tk_m(h);                                // M, then Sigma_{i+1,i}[0:rmax, :]
+    const int trm = rm / 64;
     const int64_t* slot2 = h->d_sel_slot + h->sel_cap;
     for (int64_t i = h->N - 1; i >= 0; --i) {
         const double* X = h->d_Linv + i * bstride;
         const bool coupled = i < h->N - 1;
         const int64_t e0 = h->sel_off[(size_t)i], ne = h->sel_off[(size_t)i + 1] - e0, nd = h->sel_nd[(size_t)i];
         if (coupled) {
-            const double* C = h->d_C + i * c_blk(h);
-            GCHK(gemm(h, false, true, rm, wc, rm, 0, 0, 1.0, Sg, ld, C, c_ld(h), 0.0, V1, ld, pW, pCm, pW,
-                      1, 0, 0, 0, nullptr, 0, 0, 0, 2.0 * rm * h->c_streamed * (double)h->B, nullptr, nullptr, h->d_mend));
-            GCHK(gemm(h, true, true, wc, wc, rm, 0, 1, 1.0, V1, ld, C, c_ld(h), 0.0, V2, ld, pW, pCm, pW,
-                      1, 0, 0, 0, nullptr, 0, 0, 0, -1.0, nullptr, nullptr, h->d_mend));
-            hipLaunchKernelGGL(transpose_tiles, dim3((unsigned)(twc * (twc + 1) / 2), nb), dim3(256), 0, h->stream, V2, ld, V2, ld, pW, pW, twc, twc, 2);
-            HIPCHK(hipGetLastError());
-            GCHK(gemm(h, false, true, wc, bsp, wc, 0, 0, 1.0, V2, ld, X + (int64_t)cm * ld, ld, 1.0, Y + (int64_t)cm * ld, ld, pW, pX, pW,
-                      1, 0, 0, 0, X + (int64_t)cm * ld, ld, pX, 0, -1.0, nullptr, h->d_kbx, nullptr));
+            GCHK(tk_coupled_y(h, i, Sg));
             if (ne > nd)
-                GCHK(gemm(h, false, true, rm, bsp, wc, 0, 0, -1.0, V1, ld, X + (int64_t)cm * ld, ld, 0.0, V2, ld, pW, pX, pW,
-                          1, 0, 0, 0, nullptr, 0, 0, 0, -1.0, nullptr, h->d_kbx, nullptr));
+                GCHK(gemm(h, GemmCall(false, true, rm, bsp, wc, -1.0, 0.0).a(tk_t1(h), ld, pW).b(X + (int64_t)cm * ld, ld, pX).c(V2, ld, pW)
+                                 .k_begin(nullptr, h->d_kbx)));
         }
         // S_ii on its lower tiles: the whole block if this step has entries there, else its leading block for the next step
-        const int ms = nd > 0 ? bsp : rm;
-        if (nd > 0 || i > 0) {
-            if (coupled) {
-                if (cm > 0)
-                    GCHK(gemm(h, true, true, ms, ms, cm, TRI_A_UPPER | TRI_B_LOWER, 1, 1.0, X, ld, X, ld, 0.0, Sn, ld, pX, pX, pW));
-                GCHK(gemm(h, true, true, ms, ms, wc, 0, 1, 1.0, X + (int64_t)cm * ld, ld, Y + (int64_t)cm * ld, ld, cm > 0 ? 1.0 : 0.0, Sn, ld,
-                          pX, pW, pW, 1, 0, 0, 0, nullptr, 0, 0, 0, -1.0, h->d_kbx, nullptr, nullptr));
-            } else {
-                GCHK(gemm(h, true, true, ms, ms, bsp, TRI_A_UPPER | TRI_B_LOWER, 1, 1.0, X, ld, X, ld, 0.0, Sn, ld, pX, pX, pW));
-            }
-        }
+        if (nd > 0 || i > 0) GCHK(tk_xty(h, i, coupled, nd > 0 ? bsp : rm, Sn));
         if (ne > 0) {
             hipLaunchKernelGGL(selinv_scatter, dim3((unsigned)((ne + 255) / 256), nb), dim3(256), 0, h->stream, Sn, V2, pW,
                                h->d_sel_src, h->d_sel_slot, slot2, e0, nd, ne, d_out, h->sel_nnz);
@@ -6511,7 +6507,7 @@ static gmrf_status tw_meeting_coupling(gmrf_handle* h) {
         HIPCHK(hipGetLastError());
     }
     const double* X = bot->d_Linv + (bot->N - 1) * (int64_t)bsp * bsp;
-    GCHK(gemm(bot, false, false, bsp, bsp, bsp, 0, 0, 1.0, t->d_Bm, bsp, X, bsp, 0.0, t->d_HJ, bsp, 0, 0, 0));
+    GCHK(gemm(bot, GemmCall(false, false, bsp, bsp, bsp, 1.0, 0.0).a(t->d_Bm, bsp, 0).b(X, bsp, 0).c(t->d_HJ, bsp, 0)));
     return GMRF_OK;
 }
 
@@ -6735,13 +6731,13 @@ static gmrf_status tw_var_exact(gmrf_handle* h, double* d_out) {
     {
         const double* Xm = top->d_Linv + t->m * bstride;
         const double* Xl = bot->d_Linv + (bot->N - 1) * bstride;
-        GCHK(gemm(bot, true, true, bsp, bsp, bsp, 0, 0, 1.0, Xm, bsp, Xm, bsp, 0.0, t->d_Smm, bsp, 0, 0, 0));           // Sigma_mm
-        GCHK(gemm(bot, false, true, bsp, bsp, bsp, 0, 0, 1.0, t->d_Smm, bsp, t->d_HJ, bsp, 0.0, bot->d_W, bsp, 0, 0, 0));  // Sigma_mm HJ
-        GCHK(gemm(bot, true, true, bsp, bsp, bsp, 0, 0, 1.0, t->d_HJ, bsp, bot->d_W, bsp, 0.0, bot->d_B, bsp, 0, 0, 0));  // HJ^T Sigma_mm HJ
+        GCHK(gemm(bot, GemmCall(true, true, bsp, bsp, bsp, 1.0, 0.0).a(Xm, bsp, 0).b(Xm, bsp, 0).c(t->d_Smm, bsp, 0)));           // Sigma_mm
+        GCHK(gemm(bot, GemmCall(false, true, bsp, bsp, bsp, 1.0, 0.0).a(t->d_Smm, bsp, 0).b(t->d_HJ, bsp, 0).c(bot->d_W, bsp, 0)));  // Sigma_mm HJ
+        GCHK(gemm(bot, GemmCall(true, true, bsp, bsp, bsp, 1.0, 0.0).a(t->d_HJ, bsp, 0).b(bot->d_W, bsp, 0).c(bot->d_B, bsp, 0)));  // HJ^T Sigma_mm HJ
         hipLaunchKernelGGL(add_identity, dim3((unsigned)((bsp + 255) / 256)), dim3(256), 0, bot->stream, bot->d_B, (int64_t)bsp, bsp);
         HIPCHK(hipGetLastError());
-        GCHK(gemm(bot, false, true, bsp, bsp, bsp, 0, 0, 1.0, bot->d_B, bsp, Xl, bsp, 0.0, bot->d_T, bsp, 0, 0, 0));       // (I + M) L'^-1
-        GCHK(gemm(bot, true, true, bsp, bsp, bsp, 0, 0, 1.0, Xl, bsp, bot->d_T, bsp, 0.0, bot->d_S, bsp, 0, 0, 0));        // Sigma'
+        GCHK(gemm(bot, GemmCall(false, true, bsp, bsp, bsp, 1.0, 0.0).a(bot->d_B, bsp, 0).b(Xl, bsp, 0).c(bot->d_T, bsp, 0)));       // (I + M) L'^-1
+        GCHK(gemm(bot, GemmCall(true, true, bsp, bsp, bsp, 1.0, 0.0).a(Xl, bsp, 0).b(bot->d_T, bsp, 0).c(bot->d_S, bsp, 0)));        // Sigma'
         GCHK(var_exact(bot, t->d_var, true));
         const int64_t cnt = bot->N * t->bs;
         hipLaunchKernelGGL(tw_reverse, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, bot->stream, t->d_var, d_out + (t->m + 1) * t->bs, cnt);

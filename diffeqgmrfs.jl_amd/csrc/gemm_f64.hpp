@@ -686,10 +686,7 @@ inline hipError_t gemm_init() {
 // Kernel choice.  0 (default): whichever kernel the makespan model below predicts faster;
 // 1: always the 128 x 128 kernel where it applies; 2: never (tests and tools move it).
 inline int& gemm_big_policy() {
-    static int v = [] {
-        const char* e = getenv("GMRF_GEMM_BIG_POLICY");   // tuning aid
-        return e ? atoi(e) : 0;
-    }();
+    static int v = 0;
     return v;
 }
 
@@ -777,8 +774,6 @@ inline bool gemm_uses_ll(const GemmArgs& g, int batch) {
     if (gemm_ll_policy() == 2 || g.K % 32 || (g.tri & ~15) || g.stamps) return false;
     const int64_t sx = g.N / GEMM_BN, sy = g.M / GEMM_BM;
     const int64_t tiles = ((g.lower_only && g.M == g.N) ? sx * (sx + 1) / 2 : sx * sy) * batch;
-    static const int64_t ll_env = [] { const char* e = getenv("GMRF_GEMM_LL_MAX_TILES"); return (int64_t)(e ? atoi(e) : -1); }();   // tuning aid
-    if (ll_env >= 0) return tiles <= ll_env;
     // The 32 x 32-tile kernel is for the latency of ONE problem's small products (or a handful of problems).  A launch of a
     // real batch is better served by 64 x 64 tiles even when they fill few CUs: with several handles in flight what counts is
     // what a launch takes from the chip, not how soon it ends (darcy256, 4 x 32: the 128-tile launches on gemm_f64_dma are
@@ -820,14 +815,12 @@ inline hipError_t launch_gemm(hipStream_t st, bool a_t, bool b_n, const GemmArgs
         hipError_t derr = hipSuccess;
         if (gemm_try_dma(st, a_t, b_n, g, batch, ev_start, ev_stop, &derr)) return derr;
     }
-    static const bool force_bk16 = getenv("GMRF_GEMM_BK16") != nullptr;     // tuning aid
     // One LDS stage instead of two (two barriers per K step, half the LDS): four workgroups per CU instead of
     // two.  Launches of more than ~1.5 rounds of tiles gain (the fixed part of a tile -- first operand loads,
     // epilogue -- hides behind three neighbours instead of one: 1024^2 x 32 outputs, K = 64 / 128 / 256 / 1024:
     // 26 -> 32, 38 -> 44, 47.6 -> 49.5, 53.7 -> 55.5 TF/s); single-round launches lose 2-8 % to the second barrier.
-    static const int single_env = [] { const char* e = getenv("GMRF_GEMM_SINGLE_STAGE"); return e ? atoi(e) : -1; }();   // tuning aid
-    const bool single_stage = single_env >= 0 ? single_env != 0 : grid.x > 768;
-    const bool wide = (g.K % 32 == 0) && !force_bk16;
+    const bool single_stage = grid.x > 768;
+    const bool wide = g.K % 32 == 0;
     if (gemm_uses_ll(g, batch)) {
         const int64_t lx = g.N / GEMM_LL, ly = g.M / GEMM_LL;
         dim3 lgrid((unsigned)((tri_grid ? lx * (lx + 1) / 2 : lx * ly) * batch));

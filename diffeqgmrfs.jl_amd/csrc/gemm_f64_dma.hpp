@@ -10,15 +10,15 @@
 // parameter: 128 x 64 / 64 x 128 (a wave owns 64 x 32 / 32 x 64 = 8 MFMA tiles: 6 fragment reads per 16 MFMAs instead of
 // 4 per 8) for launches whose M / N allow it, 64 x 64 otherwise.
 //
-// LDS images (K step BK = 16, STAGES buffers of (BM + BN) * 128 bytes):
+// LDS images (K step BK = 16, DMA_STAGES buffers of (BM + BN) * 128 bytes):
 //   [row][16] for an operand stored [row][k]: a row is 128 bytes = 8 chunks of 16 bytes; chunk c of row r sits at
 //       chunk position c ^ ((r >> 1) & 7).  A wave's ds_read_b128 of one k pair from 16 consecutive rows then touches
 //       every bank once (unswizzled, rows 128 bytes apart put every second row on the same banks: 4-way conflicts).
 //       global_load_lds writes LDS linearly (wave-uniform base + lane * 16), so the swizzle is applied on the SOURCE
 //       side: lane l of the instruction that fills rows 8q .. 8q+7 fetches chunk (l & 7) ^ ((row >> 1) & 7) of row 8q + (l >> 3).
 //   [16][BN] as it lies in memory for B stored [k][n] (a 16-lane group reads 256 contiguous bytes: conflict free).
-// Pipeline: STAGES - 1 tiles are in flight (LDS-DMA) while one is multiplied; a wave waits for ITS OWN requests of tile
-// kt with a counted s_waitcnt vmcnt(n) that leaves the later tiles in flight, and ONE raw s_barrier per K step both makes
+// Pipeline: DMA_STAGES - 1 = one tile is in flight (LDS-DMA) while one is multiplied; a wave waits for ITS OWN requests of tile
+// kt with s_waitcnt vmcnt(0), and ONE raw s_barrier per K step both makes
 // every wave's part of tile kt visible and frees the buffer of tile kt - 1 for the next request (no __syncthreads: its
 // fence would drain the DMA queue).  All LDS is ONE dynamic array (cdna_hip_programming.md: a second __shared__ object makes hipcc
 // wait vmcnt(0) before every fragment read).
@@ -30,13 +30,11 @@
 namespace gmrf {
 
 constexpr int DMA_BK = 16;
+constexpr int DMA_STAGES = 2;                // LDS ring: one tile in flight while one is multiplied
 constexpr int DMA_ROWS_ASCENDING = 1024;     // GemmArgs::tri bit set by the launcher: triangular grid walked from row tile 0 on
-#ifndef GMRF_DMA_READS_FIRST
-#define GMRF_DMA_READS_FIRST 0      // 1: a K step issues its fragment reads before the next tile's LDS-DMA requests (measured: see DESIGN.md)
-#endif
 
 template <int BM, int BN>
-constexpr size_t gemm_dma_lds_bytes(int stages) { return (size_t)stages * (BM + BN) * DMA_BK * sizeof(double); }
+constexpr size_t gemm_dma_lds_bytes() { return (size_t)DMA_STAGES * (BM + BN) * DMA_BK * sizeof(double); }
 
 #define GMRF_LDS_PTR(p) ((__attribute__((address_space(3))) void*)(p))
 #define GMRF_GLB_PTR(p) ((const __attribute__((address_space(1))) void*)(p))
@@ -111,9 +109,9 @@ __device__ __forceinline__ void gemm_dma_tile_order(const GemmArgs& g, int bid, 
 //
 // The body is a function of (descriptor, workgroup index, workgroups of the descriptor) so that one launch can run two
 // descriptors (gemm_f64_dma_grouped below); gemm_f64_dma itself is the body at (g, blockIdx.x, gridDim.x).
-template <int BM, int BN, bool B_N, int STAGES, bool A_T, bool TAIL, bool DOUT>
+template <int BM, int BN, bool B_N, bool A_T, bool TAIL, bool DOUT>
 __device__ __forceinline__ void gemm_dma_body(const GemmArgs& g, const int bid, const int gdim) {
-    constexpr int BK = DMA_BK;
+    constexpr int BK = DMA_BK, STAGES = DMA_STAGES;
     constexpr int MI = BM / 32, NJ = BN / 32;                    // 16 x 16 MFMA tiles of a wave: MI x NJ
     constexpr int NA = BM / 32, NB = BN / 32;                    // LDS-DMA instructions per wave and K step (A, B)
     constexpr int A_ST = BM * BK, B_ST = BN * BK, T_ST = TAIL ? BK : 0, ST = A_ST + B_ST + T_ST;   // doubles per stage
@@ -192,8 +190,7 @@ __device__ __forceinline__ void gemm_dma_body(const GemmArgs& g, const int bid, 
         const char* bbase = reinterpret_cast<const char*>(B_N ? B + (int64_t)k0 * g.ldb : B + k0);
         double* as = gsm + stage * ST;
         double* bs = as + A_ST;
-        // (a wave's requests of a tile are waited for by a count that assumes NA + NB of them: the one more of wave 0 only makes
-        // its count wait for one request of the next tile too -- with 2 stages every wait is vmcnt(0) anyway)
+        // (the one more request of wave 0 needs no count of its own: every wait is vmcnt(0))
         if constexpr (TAIL)
             if (tail && w == 0 && lane < 8)
                 __builtin_amdgcn_global_load_lds(GMRF_GLB_PTR(arow + k0 + 2 * lane), GMRF_LDS_PTR(bs + B_ST), 16, 0, 0);
@@ -241,22 +238,20 @@ __device__ __forceinline__ void gemm_dma_body(const GemmArgs& g, const int bid, 
         // fb[2 jp + p]: row k = kg * 8 + 2 lq + p, columns (2 li, 2 li + 1) of column group jp
     }
 
-    // Pipeline: DEPTH = STAGES - 1 tiles are in flight while one is multiplied.  Per K step: wait for this wave's own
-    // requests of tile kt (counted: the tiles after it stay in flight), barrier (every wave's part of tile kt has landed,
-    // and every wave has finished reading tile kt - 1), request tile kt + DEPTH into the buffer tile kt - 1 occupied,
+    // Pipeline: DEPTH = STAGES - 1 = 1 tile is in flight while one is multiplied.  Per K step: wait for this wave's own
+    // requests of tile kt (all it has made: nothing is requested behind tile kt), barrier (every wave's part of tile kt has
+    // landed, and every wave has finished reading tile kt - 1), request tile kt + DEPTH into the buffer tile kt - 1 occupied,
     // multiply tile kt.  ONE barrier per step.
     constexpr int DEPTH = STAGES - 1;
 #pragma unroll
     for (int s = 0; s < DEPTH; ++s)
         if (s < nkt) issue(s, s);
     for (int kt = 0; kt < nkt; ++kt) {
-        const int ahead = min(DEPTH - 1, nkt - 1 - kt);          // requested tiles behind tile kt
-        if (ahead <= 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        else if (ahead == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NA + NB) : "memory");
-        else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * (NA + NB)) : "memory");
+        static_assert(DEPTH == 1, "no tile is requested behind tile kt: the wait is for all of the wave's requests");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
-        if (!GMRF_DMA_READS_FIRST && kt + DEPTH < nkt) issue(kt + DEPTH, (kt + DEPTH) % STAGES);
+        if (kt + DEPTH < nkt) issue(kt + DEPTH, (kt + DEPTH) % STAGES);
         if (!idle) {
             const double* sm = gsm + (kt % STAGES) * ST;
             v2d a[BK / 8][MI], b[BK / 8][NJ];
@@ -271,8 +266,6 @@ __device__ __forceinline__ void gemm_dma_body(const GemmArgs& g, const int bid, 
             v2d ta = (v2d){0.0, 0.0};
             if constexpr (TAIL)
                 if (tail) ta = *reinterpret_cast<const v2d*>(sm + A_ST + B_ST + tkg * 8 + 2 * lq);     // a(k), a(k + 1), k = 8 tkg + 2 lq
-            __builtin_amdgcn_sched_barrier(0);
-            if (GMRF_DMA_READS_FIRST && kt + DEPTH < nkt) issue(kt + DEPTH, (kt + DEPTH) % STAGES);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int kg = 0; kg < BK / 8; ++kg)
@@ -307,7 +300,7 @@ __device__ __forceinline__ void gemm_dma_body(const GemmArgs& g, const int bid, 
                 }
             }
             __builtin_amdgcn_sched_barrier(0);
-        } else if (GMRF_DMA_READS_FIRST && kt + DEPTH < nkt) issue(kt + DEPTH, (kt + DEPTH) % STAGES);
+        }
     }
     if (idle) return;
 
@@ -427,9 +420,9 @@ __global__ void set_direct_out(GemmDirectOut* o, double* samples, double* mean, 
     o->samples = samples; o->mean = mean; o->ld = ld; o->k = k;
 }
 
-template <int BM, int BN, bool B_N, int STAGES, bool A_T = false, bool TAIL = false, bool DOUT = false>
+template <int BM, int BN, bool B_N, bool A_T = false, bool TAIL = false, bool DOUT = false>
 __global__ __launch_bounds__(256, (BM + BN > 128) ? 3 : 4) void gemm_f64_dma(GemmArgs g) {
-    gemm_dma_body<BM, BN, B_N, STAGES, A_T, TAIL, DOUT>(g, (int)blockIdx.x, (int)gridDim.x);
+    gemm_dma_body<BM, BN, B_N, A_T, TAIL, DOUT>(g, (int)blockIdx.x, (int)gridDim.x);
 }
 
 // Two independent products in ONE launch (round 13, 64 x 64 tiles): workgroups [0, wg0) run descriptor g0, [wg0, wg0 + wg1) run g1,
@@ -437,28 +430,23 @@ __global__ __launch_bounds__(256, (BM + BN > 128) ? 3 : 4) void gemm_f64_dma(Gem
 // same bits).  The descriptor and its B layout (bit 0 / bit 1 of b_n: g0 / g1 stored [k][n]) are chosen once per workgroup from
 // blockIdx.x -- wave-uniform -- in front of the K loop; the K loops themselves are the two bodies unchanged.  A multiple of 8 for
 // wg0 keeps g1's problems on the XCDs a launch of its own would put them on (a matter of locality only).
-template <int STAGES>
 __global__ __launch_bounds__(256, 4) void gemm_f64_dma_grouped(GemmArgs g0, GemmArgs g1, int wg0, int wg1, int b_n) {
     const bool second = (int)blockIdx.x >= wg0;
     const GemmArgs g = second ? g1 : g0;
     const int bid = second ? (int)blockIdx.x - wg0 : (int)blockIdx.x, gdim = second ? wg1 : wg0;
-    if ((b_n >> (second ? 1 : 0)) & 1) gemm_dma_body<64, 64, true, STAGES, false, false, false>(g, bid, gdim);
-    else gemm_dma_body<64, 64, false, STAGES, false, false, false>(g, bid, gdim);
+    if ((b_n >> (second ? 1 : 0)) & 1) gemm_dma_body<64, 64, true, false, false, false>(g, bid, gdim);
+    else gemm_dma_body<64, 64, false, false, false, false>(g, bid, gdim);
 }
 
 // ---------------------------------------------------------------------------------------------
-// Kernel choice.  GMRF_GEMM_DMA (tuning aid): 0 = never, 1 = only the 64 x 64 tile, 2 (default) = 128 x 64 / 64 x 128 where
-// the shape allows and the launch keeps >= 2 workgroups per CU, 64 x 64 otherwise.  GMRF_GEMM_DMA_STAGES: 2 (default) or 3.
+// Kernel choice.  The policy (moved by the test hooks only): 0 = never, 1 = only the 64 x 64 tile, 2 (default) = 128 x 64 /
+// 64 x 128 on full products of many tiles, 64 x 64 otherwise.
 inline int& gemm_dma_policy() {
-    static int v = [] { const char* e = getenv("GMRF_GEMM_DMA"); return e ? atoi(e) : 2; }();
+    static int v = 2;
     return v;
 }
 inline int& gemm_dma_force() {          // tests: 0 = by policy, 1 / 2 / 3 = this tile shape wherever the sizes divide
     static int v = 0;
-    return v;
-}
-inline int gemm_dma_stages() {
-    static const int v = [] { const char* e = getenv("GMRF_GEMM_DMA_STAGES"); const int s = e ? atoi(e) : 2; return s == 3 ? 3 : 2; }();
     return v;
 }
 
@@ -484,7 +472,7 @@ inline int gemm_dma_shape(bool a_t, const GemmArgs& g, int batch) {
     // (tools/gemm_dma_rate.py: G2 304 us against 280 us, rank-256 update of 768^2 101 against 88 us).
     const bool plain = !g.lower_only && !g.tri && !g.kb_m && !g.kb_n && !g.ke_n && !g.ke_m;
     const int64_t t64 = (int64_t)(g.M / 64) * (g.N / 64) * batch;
-    if (policy >= 3 || (plain && t64 >= 2048)) {
+    if (plain && t64 >= 2048) {
         if (g.M % 128 == 0) return 2;
         if (g.N % 128 == 0 && !g.lower_only) return 3;
     }
@@ -494,15 +482,21 @@ inline bool gemm_uses_dma(bool a_t, const GemmArgs& g, int batch) { return gemm_
 
 inline hipError_t gemm_dma_init() {
     hipError_t e = hipSuccess;
-#define GMRF_DMA_ATTR(BM, BN, BNAT, ST)                                                                          \
+#define GMRF_DMA_ATTR(BM, BN, BNAT)                                                                              \
     if (e == hipSuccess)                                                                                          \
-        e = hipFuncSetAttribute((const void*)gemm_f64_dma<BM, BN, BNAT, ST>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                (int)gemm_dma_lds_bytes<BM, BN>(ST) + 64 * 1024);
-    GMRF_DMA_ATTR(64, 64, false, 2) GMRF_DMA_ATTR(64, 64, true, 2) GMRF_DMA_ATTR(64, 64, false, 3) GMRF_DMA_ATTR(64, 64, true, 3)
-    GMRF_DMA_ATTR(128, 64, false, 2) GMRF_DMA_ATTR(128, 64, true, 2) GMRF_DMA_ATTR(128, 64, false, 3) GMRF_DMA_ATTR(128, 64, true, 3)
-    GMRF_DMA_ATTR(64, 128, false, 2) GMRF_DMA_ATTR(64, 128, true, 2) GMRF_DMA_ATTR(64, 128, false, 3) GMRF_DMA_ATTR(64, 128, true, 3)
+        e = hipFuncSetAttribute((const void*)gemm_f64_dma<BM, BN, BNAT>, hipFuncAttributeMaxDynamicSharedMemorySize, \
+                                (int)gemm_dma_lds_bytes<BM, BN>() + 64 * 1024);
+    GMRF_DMA_ATTR(64, 64, false) GMRF_DMA_ATTR(64, 64, true)
+    GMRF_DMA_ATTR(128, 64, false) GMRF_DMA_ATTR(128, 64, true)
+    GMRF_DMA_ATTR(64, 128, false) GMRF_DMA_ATTR(64, 128, true)
 #undef GMRF_DMA_ATTR
     return e;
+}
+
+// A triangular grid whose tiles have K begins of their own (kb_m / kb_n: staircase or envelope bounds) walks its rows ascending --
+// longest tiles first (see gemm_dma_tile_order).  Returns the GemmArgs::tri bit to set, for the descriptor as the caller gave it.
+inline int gemm_dma_row_order(const GemmArgs& g) {
+    return (g.lower_only && g.M == g.N && (g.kb_m || g.kb_n)) ? DMA_ROWS_ASCENDING : 0;
 }
 
 // The product plus its tail row M (see TAIL above) on the 64 x 64 tile -- the kernel launch_gemm picks for the M rows when
@@ -531,29 +525,18 @@ inline bool gemm_try_dma_tail(hipStream_t st, bool a_t, bool b_n, const GemmArgs
     const bool tri_grid = g.lower_only && g.M == g.N;
     GemmArgs gs = g;
     gs.lower_only = tri_grid ? 1 : 0;
-    static const bool asc_off = [] { const char* e = getenv("GMRF_GEMM_G2_ORDER"); return e && atoi(e) == 0; }();   // tuning aid
-    if (tri_grid && (g.kb_m || g.kb_n) && !asc_off) gs.tri |= DMA_ROWS_ASCENDING;
+    gs.tri |= gemm_dma_row_order(g);
     const int64_t nx = g.N / 64, ny = g.M / 64;
     const dim3 grid((unsigned)((tri_grid ? ny * (ny + 1) / 2 : nx * ny) * batch)), block(256);
-    const size_t lds = (size_t)gemm_dma_stages() * (64 + 64 + DMA_BK) * DMA_BK * sizeof(double);
-#define GMRF_DMA_TK(BNAT, ST)                                                                                              \
+    const size_t lds = (size_t)DMA_STAGES * (64 + 64 + DMA_BK) * DMA_BK * sizeof(double);
+#define GMRF_DMA_TK(...)                                                                                                   \
     do {                                                                                                                   \
-        if (ev_start) hipExtLaunchKernelGGL((gemm_f64_dma<64, 64, BNAT, ST, false, true>), grid, block, lds, st, ev_start, ev_stop, 0, gs); \
-        else hipLaunchKernelGGL((gemm_f64_dma<64, 64, BNAT, ST, false, true>), grid, block, lds, st, gs);                \
+        if (ev_start) hipExtLaunchKernelGGL((gemm_f64_dma<64, 64, __VA_ARGS__>), grid, block, lds, st, ev_start, ev_stop, 0, gs); \
+        else hipLaunchKernelGGL((gemm_f64_dma<64, 64, __VA_ARGS__>), grid, block, lds, st, gs);                          \
     } while (0)
-#define GMRF_DMA_TKO(ST)                                                                                                   \
-    do {                                                                                                                   \
-        if (ev_start) hipExtLaunchKernelGGL((gemm_f64_dma<64, 64, true, ST, false, true, true>), grid, block, lds, st, ev_start, ev_stop, 0, gs); \
-        else hipLaunchKernelGGL((gemm_f64_dma<64, 64, true, ST, false, true, true>), grid, block, lds, st, gs);          \
-    } while (0)
-    if (g.dout) {
-        if (gemm_dma_stages() == 3) GMRF_DMA_TKO(3); else GMRF_DMA_TKO(2);
-    } else if (gemm_dma_stages() == 3) {
-        if (b_n) GMRF_DMA_TK(true, 3); else GMRF_DMA_TK(false, 3);
-    } else {
-        if (b_n) GMRF_DMA_TK(true, 2); else GMRF_DMA_TK(false, 2);
-    }
-#undef GMRF_DMA_TKO
+    if (g.dout) GMRF_DMA_TK(true, false, true, true);
+    else if (b_n) GMRF_DMA_TK(true, false, true);
+    else GMRF_DMA_TK(false, false, true);
 #undef GMRF_DMA_TK
     *err = hipGetLastError();
     return true;
@@ -567,23 +550,18 @@ inline bool gemm_try_dma(hipStream_t st, bool a_t, bool b_n, const GemmArgs& g, 
     const bool tri_grid = g.lower_only && g.M == g.N;
     GemmArgs gs = g;
     gs.lower_only = tri_grid ? 1 : (g.lower_only ? 2 : 0);
-    static const bool asc_off = [] { const char* e = getenv("GMRF_GEMM_G2_ORDER"); return e && atoi(e) == 0; }();   // tuning aid
-    if (tri_grid && (g.kb_m || g.kb_n) && !asc_off) gs.tri |= DMA_ROWS_ASCENDING;
-    const int stages = gemm_dma_stages();
+    gs.tri |= gemm_dma_row_order(g);
     const dim3 block(256);
 #define GMRF_DMA_GO(BM, BN)                                                                                       \
     do {                                                                                                          \
         const int64_t nx = g.N / BN, ny = g.M / BM;                                                               \
         const int64_t tiles = tri_grid ? (int64_t)(BM / BN > 0 ? BM / BN : 1) * ny * (ny + 1) / 2 : nx * ny;      \
         const dim3 grid((unsigned)(tiles * batch));                                                               \
-        static const size_t lds_pad = [] { const char* e = getenv("GMRF_GEMM_DMA_LDS_PAD_KB"); return (size_t)(e ? atoi(e) : 0) * 1024; }();   /* tuning aid */ \
-        const size_t lds = gemm_dma_lds_bytes<BM, BN>(stages) + lds_pad;                                          \
+        const size_t lds = gemm_dma_lds_bytes<BM, BN>();                                                          \
         if (a_t && BM == 64 && BN == 64) {                                                                        \
-            if (b_n) GMRF_DMA_K((gemm_f64_dma<64, 64, true, 2, true>)); else GMRF_DMA_K((gemm_f64_dma<64, 64, false, 2, true>)); \
-        } else if (stages == 3) {                                                                                 \
-            if (b_n) GMRF_DMA_K((gemm_f64_dma<BM, BN, true, 3>)); else GMRF_DMA_K((gemm_f64_dma<BM, BN, false, 3>)); \
+            if (b_n) GMRF_DMA_K((gemm_f64_dma<64, 64, true, true>)); else GMRF_DMA_K((gemm_f64_dma<64, 64, false, true>)); \
         } else {                                                                                                  \
-            if (b_n) GMRF_DMA_K((gemm_f64_dma<BM, BN, true, 2>)); else GMRF_DMA_K((gemm_f64_dma<BM, BN, false, 2>)); \
+            if (b_n) GMRF_DMA_K((gemm_f64_dma<BM, BN, true>)); else GMRF_DMA_K((gemm_f64_dma<BM, BN, false>));    \
         }                                                                                                         \
     } while (0)
 #define GMRF_DMA_K(KERNEL)                                                                                        \
@@ -616,25 +594,17 @@ inline int64_t gemm_dma_grid64(const GemmArgs& g, int batch) {
 inline bool gemm_try_dma_grouped(hipStream_t st, bool b_n0, const GemmArgs& g0, bool b_n1, const GemmArgs& g1, int batch,
                                  hipEvent_t ev_start, hipEvent_t ev_stop, hipError_t* err) {
     if (!gemm_grouped_ok(g0, g1, batch)) return false;
-    static const bool asc_off = [] { const char* e = getenv("GMRF_GEMM_G2_ORDER"); return e && atoi(e) == 0; }();   // tuning aid
     GemmArgs gs[2] = {g0, g1};
     for (GemmArgs& g : gs) {                                     // (as gemm_try_dma sets a launch of its own up)
-        const bool tri_grid = g.lower_only && g.M == g.N;
-        g.lower_only = tri_grid ? 1 : 0;
-        if (tri_grid && (g.kb_m || g.kb_n) && !asc_off) g.tri |= DMA_ROWS_ASCENDING;
+        g.tri |= gemm_dma_row_order(g);
+        g.lower_only = (g.lower_only && g.M == g.N) ? 1 : 0;
     }
     const int wg0 = (int)gemm_dma_grid64(g0, batch), wg1 = (int)gemm_dma_grid64(g1, batch);
     const int bn = (b_n0 ? 1 : 0) | (b_n1 ? 2 : 0);
     const dim3 grid((unsigned)(wg0 + wg1)), block(256);
-    const int stages = gemm_dma_stages();
-    const size_t lds = gemm_dma_lds_bytes<64, 64>(stages);
-#define GMRF_DMA_GK(ST)                                                                                                   \
-    do {                                                                                                                  \
-        if (ev_start) hipExtLaunchKernelGGL((gemm_f64_dma_grouped<ST>), grid, block, lds, st, ev_start, ev_stop, 0, gs[0], gs[1], wg0, wg1, bn); \
-        else hipLaunchKernelGGL((gemm_f64_dma_grouped<ST>), grid, block, lds, st, gs[0], gs[1], wg0, wg1, bn);           \
-    } while (0)
-    if (stages == 3) GMRF_DMA_GK(3); else GMRF_DMA_GK(2);
-#undef GMRF_DMA_GK
+    const size_t lds = gemm_dma_lds_bytes<64, 64>();
+    if (ev_start) hipExtLaunchKernelGGL(gemm_f64_dma_grouped, grid, block, lds, st, ev_start, ev_stop, 0, gs[0], gs[1], wg0, wg1, bn);
+    else hipLaunchKernelGGL(gemm_f64_dma_grouped, grid, block, lds, st, gs[0], gs[1], wg0, wg1, bn);
     *err = hipGetLastError();
     return true;
 }

@@ -117,7 +117,6 @@ struct gmrf_csr : DevCtx {
     double* d_vals = nullptr;
     float* d_vals32 = nullptr;
     double* d_diag = nullptr;
-    bool tiles128_ok = false;          // the same for 128-row tiles and 2 * SPMV_CAP
     bool tiles_ok = false;             // every SPMV_ROWS-row tile has at most SPMV_CAP entries (csr_spmv_tiles)
     DevBuf stage_x, stage_y;           // host operands of gmrf_spmm / gmrf_spmm_rows
     // tile plan of csr_spmm_tiles (node-major right-hand sides), built on first use
@@ -271,7 +270,7 @@ struct gmrf_handle {
     // One problem: the in-block Cholesky as ONE persistent launch per block / per 256-column panel (potrf_persist.hpp) instead of a
     // launch per 64-column step.  Needs every workgroup resident (1 + tiles <= CUs); a wait that gives up sets d_info[1], and
     // factor_finish then repeats the factorisation with the launch-per-step form and keeps it for this handle.
-    bool no_persist = false;           // set_eager bit 13 / GMRF_PERSIST=0
+    bool no_persist = false;           // set_eager bit 13
     bool persist_gave_up = false;      // a bounded wait inside a persistent launch gave up: this handle keeps the launch-per-step forms for good (set_eager cannot clear it)
     bool persist_launched = false;     // a persistent launch was enqueued since the abort word was last looked at
     int persist_cus = 0;               // CUs held of the device's budget (persist_plan); 0: no persistent launches
@@ -284,7 +283,7 @@ struct gmrf_handle {
     // One problem: a whole sweep as ONE persistent launch (sweep_persist.hpp) instead of two dependent launches per block.  Every
     // workgroup must be resident: the handle then claims the whole chip (persist_plan).  A wait that gives up sets the mapped host
     // word; gmrf_bt_solve / gmrf_bt_sample see it at their synchronisation and repeat the call with the launch-per-product form.
-    bool no_sweep_persist = false;     // set_eager bit 16 / GMRF_SWEEP_PERSIST=0
+    bool no_sweep_persist = false;     // set_eager bit 16
     bool no_scatter_fold = false;      // set_eager bit 17: one problem keeps scatter_block as a launch of its own behind S = -C C^T (comparison)
     bool sweep_persist_planned = false;   // the claim covers the whole chip (persist_plan)
     bool sweep_persist_launched = false;  // such a launch was enqueued since the abort word was last looked at
@@ -892,7 +891,7 @@ static void build_symbolic(int64_t N, int64_t bsp, const std::vector<std::vector
         // tiles of mesh rows 2 and 3 of a block meet subsets of the columns the tile of mesh row 1 above them meets -- darcy256:
         // 195 + 129 + 64 gathered columns become 195).  Greedy: a tile joins the group of an earlier tile when at least half of
         // its columns are already there and the union still fits one thread per column.
-        static const bool no_groups = [] { const char* e = getenv("GMRF_BXT_GROUPS"); return e && atoi(e) == 0; }();   // tuning aid: every tile alone
+        static const bool no_groups = env_int("GMRF_BXT_GROUPS", 1) == 0;   // every tile alone (the tests' bitwise reference)
         const int nrt = (int)(sp.rmax / 64);
         sp.uptr.assign((size_t)(N * (nrt + 1)), 0);
         sp.gtiles.assign((size_t)(N * nrt * 3), -1);
@@ -1234,19 +1233,15 @@ static std::mutex g_persist_mu;
 static std::map<int, std::map<const void*, int>> g_persist_claims;     // device -> handle -> CUs
 
 // `who` asks for `want` CUs of a device with `cus`: true and recorded when it fits beside the others' claims (want = 0 releases)
-static bool persist_budget_claim(std::map<const void*, int>& claims, const void* who, int want, int cus, int margin) {
+static bool persist_budget_claim(std::map<const void*, int>& claims, const void* who, int want, int cus) {
     int others = 0;
     for (const auto& kv : claims) if (kv.first != who) others += kv.second;
-    if (want <= 0 || others + want + margin > cus) { claims.erase(who); return false; }
+    if (want <= 0 || others + want > cus) { claims.erase(who); return false; }
     claims[who] = want;
     return true;
 }
 
 static int potrf_route(const gmrf_handle* h);
-static const int& persist_margin() {
-    static const int margin = [] { const char* e = getenv("GMRF_PERSIST_CU_MARGIN"); return e ? atoi(e) : 0; }();   // tuning aid
-    return margin;
-}
 // CUs the widest persistent launch of this handle's next factorisation needs at once (0: its route launches none)
 static int persist_demand(const gmrf_handle* h) {
     if (h->no_persist || h->persist_gave_up || h->cu_count <= 0 || h->bsp < 128 || h->fork_graph) return 0;
@@ -1255,11 +1250,7 @@ static int persist_demand(const gmrf_handle* h) {
     switch (potrf_route(h)) {
         case 1 /* ROUTE_FUSED */: if (!h->no_lookahead && !h->doubling_x) wgs = 1 + persist_tiles(nt, 0, nt, 1); break;
         case 2 /* ROUTE_BIG_ONE */: if (!h->no_lookahead) wgs = 1 + persist_tiles(nt, 0, std::min(nt, 4), 0); break;      // (the first panel is the widest)
-        case 3 /* ROUTE_PANELS256 */: {
-            static const bool no_small = [] { const char* e = getenv("GMRF_PERSIST_PANELS"); return e && atoi(e) == 0; }();   // tuning aid
-            if (!no_small && !h->no_persist_panels) wgs = 1 + persist_tiles(4, 0, 4, 2);
-            break;
-        }
+        case 3 /* ROUTE_PANELS256 */: if (!h->no_persist_panels) wgs = 1 + persist_tiles(4, 0, 4, 2); break;
         default: break;
     }
     wgs *= h->B;
@@ -1280,10 +1271,10 @@ static void persist_plan(gmrf_handle* h) {
     bool ok;
     {
         std::lock_guard<std::mutex> lock(g_persist_mu);
-        ok = persist_budget_claim(g_persist_claims[h->device], h, want, h->cu_count, want == h->cu_count ? 0 : persist_margin());
+        ok = persist_budget_claim(g_persist_claims[h->device], h, want, h->cu_count);
         if (!ok && want_f > 0 && want_f < want) {          // (the whole chip is not free: the factorisation's launches alone)
             want = want_f;
-            ok = persist_budget_claim(g_persist_claims[h->device], h, want, h->cu_count, persist_margin());
+            ok = persist_budget_claim(g_persist_claims[h->device], h, want, h->cu_count);
         }
     }
     h->sweep_persist_planned = ok && want_s > 0 && want >= want_s;
@@ -1336,7 +1327,7 @@ static gmrf_status launch_persist(gmrf_handle* h, double* S, double* L, double* 
     // can ask for more workgroups than the chip has CUs (each must be resident as a whole), and if they ever hold each other's
     // CUs the handles should learn it soon, drain, and go on with the other route (a launch lasts 60 us; a wait that is
     // honest ends within a few GEMM launches of another stream).
-    static const int limit_ms = [] { const char* e = getenv("GMRF_PERSIST_SPIN_MS"); return e ? atoi(e) : -1; }();
+    static const int limit_ms = env_int("GMRF_PERSIST_SPIN_MS", -1);
     pa.spin_limit = (unsigned)(limit_ms >= 0 ? limit_ms : (h->B > 1 ? 200 : 2000)) * 100000u;
     pa.stamps = h->dbg_stamps;
     h->persist_launched = true;
@@ -1442,7 +1433,7 @@ static gmrf_status potrf_block(gmrf_handle* h, double* S, double* L, double* X, 
     const int route = potrf_route(h);
     const bool fused = route == ROUTE_FUSED;
     if (h->xsplit > 0 && route != ROUTE_PANELS256) return bad_shape("internal: split inverse planned off the 256-column panel route");
-    static const int pw_env = [] { const char* e = getenv("GMRF_PANEL_TILES"); return e ? atoi(e) : 4; }();   // tuning aid
+    static const int pw_env = env_int("GMRF_PANEL_TILES", 4);      // (tests pin the widths 2 and 8)
     const int pw = (!fused && nt >= 8) ? ((pw_env == 2 || pw_env == 8) ? pw_env : 4) : nt;           // panel width in tiles
     // a lone problem with larger blocks: two-level, with the fused kernel restricted to the panel's
     // own columns as the in-panel step (one launch instead of three where the panel has columns left)
@@ -1520,10 +1511,9 @@ static gmrf_status potrf_block(gmrf_handle* h, double* S, double* L, double* X, 
             sa.j = j;
             // two tile Choleskys + four triangular 64^3 products (L10, S11 update, L10 X00, X11 W)
             ProfScope ps(h, 16, (2.0 * t3 / 3.0 + 4.0 * 2.0 * t3 * 0.625) * nb);
-            static const size_t lds_pad = [] { const char* e = getenv("GMRF_DIAG128_LDS_PAD_KB"); return (size_t)(e ? atoi(e) : 0) * 1024; }();   // tuning aid
-            static const bool fat = [] { const char* e = getenv("GMRF_DIAG128_FAT"); return e && atoi(e) != 0; }();      // tuning aid: the three-tile form
-            if (fat) hipLaunchKernelGGL(potrf_diag128, dim3(1, (unsigned)h->B), dim3(256), POTRF_DIAG128_LDS + lds_pad, h->stream, sa);
-            else hipLaunchKernelGGL(potrf_diag128_slim, dim3(1, (unsigned)h->B), dim3(256), POTRF_DIAG128_SLIM_LDS + lds_pad, h->stream, sa);
+            static const bool fat = env_int("GMRF_DIAG128_FAT", 0) != 0;      // the three-tile form (tests: bitwise the slim one)
+            if (fat) hipLaunchKernelGGL(potrf_diag128, dim3(1, (unsigned)h->B), dim3(256), POTRF_DIAG128_LDS, h->stream, sa);
+            else hipLaunchKernelGGL(potrf_diag128_slim, dim3(1, (unsigned)h->B), dim3(256), POTRF_DIAG128_SLIM_LDS, h->stream, sa);
             HIPCHK(hipGetLastError());
             return GMRF_OK;
         };
@@ -1532,8 +1522,7 @@ static gmrf_status potrf_block(gmrf_handle* h, double* S, double* L, double* X, 
         // (potrf_persist on the 4 x 4 tiles of the block, inverse rows included): 62 us instead of ~100 us per panel, on
         // 7 B CUs instead of B (C4 elliptic512 at batch 8: 8 of 256 CUs were busy in the diagonal chain).  Larger batches keep
         // the one-workgroup kernels: their chain hides behind the other problems, and 7 B workgroups of 140 KB would not fit.
-        static const bool no_small = [] { const char* e = getenv("GMRF_PERSIST_PANELS"); return e && atoi(e) == 0; }();   // tuning aid
-        const bool persist_panels = !no_small && !h->no_persist_panels && persist_fits(h, 4, 0, 4, 2);
+        const bool persist_panels = !h->no_persist_panels && persist_fits(h, 4, 0, 4, 2);
         for (int j = 0; j < nt; j += 4) {
             const int64_t oa = (int64_t)j * 64, ob = oa + 128;
             if (persist_panels) {
@@ -1728,7 +1717,7 @@ static gmrf_status factor_blocks_range(gmrf_handle* h, int64_t i0, int64_t i1) {
             HIPCHK(hipGetLastError());
         }
         // (round 5: where the coupling product of this block runs on spmm_bxt_tiles, that launch zeroes the rows as well)
-        static const bool no_tiles_z = [] { const char* e = getenv("GMRF_BXT_TILES"); return e && atoi(e) == 0; }();
+        static const bool no_tiles_z = env_int("GMRF_BXT_TILES", 1) == 0;
         const bool scatter_in_bxt = i > 0 && nb == 1 && h->sparse_b && !h->dense_g1 && h->bxt_plan_ok && !no_tiles_z && h->bxt_nrt == (int)h->rmax / 64
                                     && h->d_dg_rowptr && h->bsp == h->bs && !h->no_scatter_fold;
         const bool zero_in_bxt = scatter_in_bxt || (i > 0 && h->sparse_b && !h->dense_g1 && h->bxt_plan_ok && !no_tiles_z && h->bxt_nrt == (int)h->rmax / 64
@@ -1769,7 +1758,7 @@ static gmrf_status factor_blocks_range(gmrf_handle* h, int64_t i0, int64_t i1) {
                 const dim3 grid((unsigned)((W / ba.cw) * rch * (int)nb));
                 // streamed bytes: C inside the staircase (written) + the rows of Linv from the first gathered column on (read)
                 ProfScope ps(h, 10, 8.0 * (h->c_streamed + 0.5 * (double)W * W) * (double)h->B);
-                static const bool no_tiles = [] { const char* e = getenv("GMRF_BXT_TILES"); return e && atoi(e) == 0; }();   // tuning aid
+                static const bool no_tiles = env_int("GMRF_BXT_TILES", 1) == 0;      // (the tests' bitwise reference: spmm_bxt)
                 if (h->bxt_plan_ok && !no_tiles && h->bxt_nrt == rm / 64) {
                     BxtTileArgs ta;
                     ta.rowptr = ba.rowptr; ta.lidx = h->d_bxt_lidx; ta.vals = h->d_vals; ta.n_entries = h->n_entries;
@@ -1777,13 +1766,12 @@ static gmrf_status factor_blocks_range(gmrf_handle* h, int64_t i0, int64_t i1) {
                     ta.gtiles = h->d_bxt_gtiles + i * h->bxt_nrt * 3; ta.ng = h->bxt_ng[(size_t)i];
                     ta.X = Xp; ta.C = C; ta.ld = ld; ta.ldc = ldc; ta.pX = pX; ta.pC = pC; ta.kst = h->d_kst;
                     ta.cm = cm; ta.rm = rm; ta.bsp = bsp; ta.ecap = h->bxt_ecap;
-                    static const bool live_skip = [] { const char* e = getenv("GMRF_BXT_LIVE"); return e && atoi(e) != 0; }();   // tuning aid (measured: 4.1 vs 3.9 ms per step, off)
+                    static const bool live_skip = env_int("GMRF_BXT_LIVE", 0) != 0;      // tuning aid (measured: 4.1 vs 3.9 ms per step, off)
                     ta.skip_dead = live_skip ? 1 : 0;
                     const int chunks = W / 16, ng = ta.ng;
                     // 16-column chunks per workgroup: the launch should be a whole number of rounds over the 3 workgroups a CU
                     // holds (measured, darcy256 x 64, 4 groups x 48 chunks: 16 chunks = 768 workgroups = one round 85 us; 8 =
                     // two rounds 96 us; 12 = 1.33 rounds 108 us; 24 = 2/3 round 99 us): rounds x (chunks + ~2 for the prologue)
-                    static const int nch_env = [] { const char* e = getenv("GMRF_BXT_NCH"); return e ? atoi(e) : 0; }();   // tuning aid
                     {
                         const int64_t slots = 3 * (int64_t)std::max(h->cu_count, 1);
                         int best = 1; int64_t best_cost = INT64_MAX;
@@ -1793,7 +1781,7 @@ static gmrf_status factor_blocks_range(gmrf_handle* h, int64_t i0, int64_t i1) {
                             const int64_t cost = ((wgs + slots - 1) / slots) * (c + 2);
                             if (cost < best_cost || (cost == best_cost && c < best)) { best = c; best_cost = cost; }
                         }
-                        ta.nch = nch_env > 0 ? std::min(nch_env, chunks) : best;
+                        ta.nch = best;
                     }
                     const int ncg = (chunks + ta.nch - 1) / ta.nch;
                     ta.nprob = (int)nb;
@@ -2125,20 +2113,16 @@ static gmrf_status launch_sweep_persist(gmrf_handle* h, bool backward, int kp, d
     void* dev_abort = nullptr;
     HIPCHK(hipHostGetDevicePointer(&dev_abort, h->h_sweep_abort, 0));
     a.host_abort = reinterpret_cast<unsigned*>(dev_abort);
-    static const int limit_ms = [] {
-        const char* e = getenv("GMRF_SWEEP_SPIN_MS");              // (tests: the sweeps' own bound, so that the factorisation's launches pass)
-        if (!e) e = getenv("GMRF_PERSIST_SPIN_MS");
-        return e ? atoi(e) : -1;
-    }();
+    // (tests: the sweeps' own bound, so that the factorisation's launches pass)
+    static const int limit_ms = env_int("GMRF_SWEEP_SPIN_MS", env_int("GMRF_PERSIST_SPIN_MS", -1));
     a.spin_limit = (unsigned)(limit_ms >= 0 ? limit_ms : 2000) * 100000u;
-    static const int dbg = [] { const char* e = getenv("GMRF_SWEEP_DBG"); return e ? atoi(e) : 0; }();      // tuning aid
+    static const int dbg = env_int("GMRF_SWEEP_DBG", 0);      // tuning aid
     a.dbg = dbg;
     // Pause between two looks at an input that has not arrived: k = 1 looks again at once (8 units = 0.2 us; a longer pause only
     // adds to every product: +0.28 us per 0.43 us measured).  The k >= 16 bodies look with 4 waves x 16 KB per workgroup, and
     // their looks load the fabric the OTHER workgroups' stores and looks travel on: 64 units (1.7 us) -- darcy256's 64-sample
     // sweep 0.96 -> 0.91 ms, and beside the mean's two sweeps (gmrf_bt_posterior) 1.52 -> 1.39 ms for the three; 128 units: 1.05 / 1.35.
-    static const int pause_env = [] { const char* e = getenv("GMRF_SWEEP_PAUSE"); return e ? atoi(e) : -1; }();      // tuning aid
-    a.pause = (kp == 1) ? 8 : (pause_env >= 0 ? pause_env : 64);
+    a.pause = (kp == 1) ? 8 : 64;
     const double N = (double)h->N, bsp = (double)h->bsp;
     const double work = (kp == 1) ? 8.0 * ((N - 1) * h->c_streamed + N * 0.5 * bsp * (bsp + 1))
                                   : kp * (2.0 * (N - 1) * h->c_streamed + N * bsp * (bsp + 1));
@@ -2430,8 +2414,6 @@ gmrf_status gmrf_bt_create(int32_t device, void* stream, gmrf_handle** out) {
     HIPCHK(hipFuncSetAttribute((const void*)potrf_diag128, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     HIPCHK(hipFuncSetAttribute((const void*)potrf_persist<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)POTRF_PERSIST_LDS));
     HIPCHK(hipDeviceGetAttribute(&h->cu_count, hipDeviceAttributeMultiprocessorCount, device));
-    { const char* e = getenv("GMRF_PERSIST"); if (e && atoi(e) == 0) h->no_persist = true; }      // tuning aid
-    { const char* e = getenv("GMRF_SWEEP_PERSIST"); if (e && atoi(e) == 0) h->no_sweep_persist = true; }      // tuning aid
     HIPCHK(hipFuncSetAttribute((const void*)potrf_diag128_slim, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     HIPCHK(gemm_init());
     HIPCHK(gemm_dma_init());
@@ -3652,9 +3634,6 @@ gmrf_status gmrf_csr_create(int32_t device, void* stream, int64_t n_rows, int64_
     m->tiles_ok = true;
     for (int64_t r = 0; r < n_rows; r += SPMV_ROWS)
         if (rp[std::min(n_rows, r + SPMV_ROWS)] - rp[r] > SPMV_CAP) { m->tiles_ok = false; break; }
-    m->tiles128_ok = true;
-    for (int64_t r = 0; r < n_rows; r += 128)
-        if (rp[std::min<int64_t>(n_rows, r + 128)] - rp[r] > 2 * SPMV_CAP) { m->tiles128_ok = false; break; }
     m->n_rows = n_rows; m->n_cols = n_cols; m->nnz = nnz;
     HIPCHK(hipMalloc(&m->d_rowptr, sizeof(int64_t) * (n_rows + 1)));
     HIPCHK(hipMalloc(&m->d_colidx, sizeof(int32_t) * std::max<int64_t>(nnz, 1)));
@@ -3702,16 +3681,10 @@ static gmrf_status spmm_device(const gmrf_csr* S, hipStream_t st, const double* 
     if (k == 1 && S->tiles_ok) {
         // SpMV: LDS-staged row tiles (with 3+ right-hand sides the lane-group kernel, which reuses the
         // entries for four of them, is faster than one pass per right-hand side)
-        static const int rows_env = [] { const char* e = getenv("GMRF_SPMV_ROWS"); return e ? atoi(e) : SPMV_ROWS; }();   // tuning aid: 64 / 128
-        const bool tall = rows_env == 128 && S->tiles128_ok;
-        const int rows = tall ? 128 : SPMV_ROWS;
-        static const int wg_cap = [] { const char* e = getenv("GMRF_SPMV_WGS"); return e ? atoi(e) : 256 * 8; }();   // tuning aid: resident workgroups
-        const dim3 grid((unsigned)std::min<int64_t>((S->n_rows + rows - 1) / rows, wg_cap > 0 ? wg_cap : (1 << 30)));
+        // (at most 256 * 8 workgroups -- what the chip holds at once -- each walking several tiles)
+        const dim3 grid((unsigned)std::min<int64_t>((S->n_rows + SPMV_ROWS - 1) / SPMV_ROWS, 256 * 8));
 #define GMRF_SPMV(VT, VP)                                                                                                   \
-        do {                                                                                                                \
-            if (tall) hipLaunchKernelGGL((csr_spmv_tiles<VT, 128>), grid, dim3(bl), 0, st, S->d_rowptr, S->d_colidx, VP, S->n_rows, d_X + r * ldx, d_Y + r * ldy); \
-            else hipLaunchKernelGGL((csr_spmv_tiles<VT, SPMV_ROWS>), grid, dim3(bl), 0, st, S->d_rowptr, S->d_colidx, VP, S->n_rows, d_X + r * ldx, d_Y + r * ldy); \
-        } while (0)
+        hipLaunchKernelGGL(csr_spmv_tiles<VT>, grid, dim3(bl), 0, st, S->d_rowptr, S->d_colidx, VP, S->n_rows, d_X + r * ldx, d_Y + r * ldy)
         for (int r = 0; r < k; ++r) {
             if (vals_override) GMRF_SPMV(double, vals_override);
             else if (S->d_vals32) GMRF_SPMV(float, S->d_vals32);
@@ -3762,7 +3735,7 @@ static gmrf_status spmm_plan(gmrf_csr* m) {
     std::vector<int32_t> tmp;
     // the tallest tile whose LDS image (distinct rows of X for 16 right-hand sides + the entries) lets three
     // workgroups share a CU; a matrix whose 16-row tiles do not fit keeps the plain kernel
-    static const size_t lds_budget = [] { const char* e = getenv("GMRF_SPMM_LDS_KB"); return (size_t)(e ? atoi(e) : 52) * 1024; }();   // tuning aid
+    constexpr size_t lds_budget = 52 * 1024;
     m->plan_state = -1;
     for (int R : {64, 32, 16}) {
         const int64_t T = (m->n_rows + R - 1) / R;
@@ -3822,8 +3795,7 @@ static gmrf_status spmm_rows_device(const gmrf_csr* S, hipStream_t st, const dou
     if (m->plan_state == 1 && aligned) {
         const int R = m->plan_rows, uc = m->plan_ucap, ec = m->plan_ecap;
         const dim3 grid((unsigned)((S->n_rows + R - 1) / R));
-        static const bool no_pad = [] { const char* e = getenv("GMRF_SPMM_PAD"); return e && atoi(e) == 0; }();   // tuning aid
-        const bool pad = m->plan_ecap_pad > 0 && !no_pad;
+        const bool pad = m->plan_ecap_pad > 0;
         const int ecl = pad ? m->plan_ecap_pad : ec;
         const int ucl = pad ? (m->plan_umax + 7) / 8 * 8 : uc;          // LDS rows of the staged X image
         const size_t lds = pad ? spmm_tile_pad_lds_bytes(R, ucl, ecl) : spmm_tile_lds_bytes(R, uc, ec);
@@ -3865,8 +3837,7 @@ static gmrf_status spmm_rows_device_batch(const gmrf_csr* S, hipStream_t st, int
     if (m->plan_state == 1 && aligned) {
         const int R = m->plan_rows, uc = m->plan_ucap, ec = m->plan_ecap;
         const dim3 grid((unsigned)((S->n_rows + R - 1) / R), (unsigned)batch);
-        static const bool no_pad = [] { const char* e = getenv("GMRF_SPMM_PAD"); return e && atoi(e) == 0; }();   // tuning aid
-        const bool pad = m->plan_ecap_pad > 0 && !no_pad;
+        const bool pad = m->plan_ecap_pad > 0;
         const int ecl = pad ? m->plan_ecap_pad : ec;
         const int ucl = pad ? (m->plan_umax + 7) / 8 * 8 : uc;
         const size_t lds = pad ? spmm_tile_pad_lds_bytes(R, ucl, ecl) : spmm_tile_lds_bytes(R, uc, ec);
@@ -6320,15 +6291,12 @@ gmrf_status gmrf_bt_marginal_var_batch(gmrf_handle* h, int32_t method, int64_t k
 }
 
 // the meeting block when the two halves' forms cost a and b per block: m a = (N - 1 - m) b.  Launch-per-step over persistent
-// in-block form, per block: 1.51 measured on MI355X (darcy256 reference order: 20.22 ms with GMRF_PERSIST=0 against 13.38 ms,
-// tools/twisted_latency.py), used as 1.5; GMRF_TWIST_RATIO overrides it (tuning aid).
-static double tw_step_ratio() {
-    static const double r = [] { const char* e = getenv("GMRF_TWIST_RATIO"); const double v = e ? atof(e) : 0.0; return v > 0.0 ? v : 1.5; }();
-    return r;
-}
+// in-block form, per block: 1.51 measured on MI355X (darcy256 reference order: 20.22 ms with set_eager bit 13 -- persistent
+// launches off -- against 13.38 ms, tools/twisted_latency.py), used as 1.5.
+constexpr double TW_STEP_RATIO = 1.5;
 static int64_t tw_auto_meet(int64_t N, bool top_persist, bool bot_persist) {
     if (N < 3) return N - 1;
-    const double a = top_persist ? 1.0 : tw_step_ratio(), b = bot_persist ? 1.0 : tw_step_ratio();
+    const double a = top_persist ? 1.0 : TW_STEP_RATIO, b = bot_persist ? 1.0 : TW_STEP_RATIO;
     const int64_t m = (int64_t)std::llround((double)(N - 1) * b / (a + b));
     return std::min<int64_t>(std::max<int64_t>(m, 1), N - 2);
 }
@@ -6959,8 +6927,7 @@ gmrf_status gmrf_test_gemm_pair(int32_t device, int32_t batch, int32_t grouped, 
 // own choice with every policy at its default.  *family: 1 / 2 register-staged at BK 16 / 32 (+ 256: single stage), 3 the
 // 128 x 128 kernel, 4 the 32 x 32 one, 5 / 6 / 7 LDS-DMA by tile shape, 8 tail row, 9 tail row with direct output.  A forced
 // route the descriptor does not qualify for is GMRF_ERR_BAD_SHAPE and launches nothing.  The family is this hook's statement of
-// launch_gemm's order of questions (gemm_uses_big, gemm_dma_shape, gemm_uses_ll, K % 32, grid.x > 768): it holds with the
-// launcher's tuning variables GMRF_GEMM_SINGLE_STAGE, GMRF_GEMM_BK16 and GMRF_GEMM_LL_MAX_TILES unset, as the tests run.
+// launch_gemm's order of questions (gemm_uses_big, gemm_dma_shape, gemm_uses_ll, K % 32, grid.x > 768).
 // (ke_m, grouped: gmrf_test_gemm_env below)
 static gmrf_status gemm_desc_run(int32_t device, int32_t route, const int64_t* desc, const double* abt,
                                  const double* A, int64_t nA, const double* B, int64_t nB, double* C, int64_t nC,
@@ -7377,7 +7344,7 @@ gmrf_status gmrf_test_persist_aborts(gmrf_handle* h, int32_t* n) {
 gmrf_status gmrf_test_persist_budget(int32_t cus, int32_t n, const int32_t* demands, int32_t* granted) {
     if (n < 0 || (n > 0 && (!demands || !granted))) return bad_shape("null argument");
     std::map<const void*, int> claims;
-    for (int i = 0; i < n; ++i) granted[i] = persist_budget_claim(claims, (const void*)(demands + i), demands[i], cus, 0) ? 1 : 0;
+    for (int i = 0; i < n; ++i) granted[i] = persist_budget_claim(claims, (const void*)(demands + i), demands[i], cus) ? 1 : 0;
     return GMRF_OK;
 }
 

@@ -1,7 +1,13 @@
 // Host-side plumbing shared by the handles of gmrf_hip.hip: a grow-only device buffer and its carving into pieces, a device
 // context (device + stream) and the staging of host-resident arguments.  Included by gmrf_hip.hip after g_last_error, HIPCHK / GCHK,
-// bad_shape and is_device_ptr; no kernels here.
+// bad_shape and is_device_ptr; no kernels here.  Also env_int, the one reader of the integer GMRF_* environment switches.
 #pragma once
+
+// An integer switch from the environment.  Callers keep the value in a function-local static: read once per process.
+static int env_int(const char* name, int dflt) {
+    const char* e = getenv(name);
+    return e ? atoi(e) : dflt;
+}
 
 static void free_dev(void* p) {
     if (p) (void)hipFree(p);

@@ -53,41 +53,11 @@
 
 using namespace gmrf;
 
-static thread_local std::string g_last_error;
+#include "host_util.hpp"      // g_last_error, HIPCHK / GCHK, bad_shape, is_device_ptr, DevBuf / DevArr, DevCtx, Staging, Carve
+
 static double g_tile_us = 0.0;
 static unsigned long long g_tile_stamps[64];
 static unsigned long long g_persist_stamps[128];    // chain workgroup of the last gmrf_test_potrf_block (potrf_persist.hpp)
-
-#define HIPCHK(expr)                                                                        \
-    do {                                                                                    \
-        hipError_t _e = (expr);                                                             \
-        if (_e != hipSuccess) {                                                             \
-            g_last_error = std::string(#expr) + ": " + hipGetErrorString(_e);               \
-            return GMRF_ERR_HIP;                                                            \
-        }                                                                                   \
-    } while (0)
-
-#define GCHK(expr)                                                                          \
-    do {                                                                                    \
-        gmrf_status _s = (expr);                                                            \
-        if (_s != GMRF_OK) return _s;                                                       \
-    } while (0)
-
-static gmrf_status bad_shape(const char* msg) {
-    g_last_error = msg;
-    return GMRF_ERR_BAD_SHAPE;
-}
-
-static bool is_device_ptr(const void* p) {
-    if (!p) return false;
-    hipPointerAttribute_t attr;
-    hipError_t e = hipPointerGetAttributes(&attr, p);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();   // unregistered host memory: clear the sticky error
-        return false;
-    }
-    return attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged;
-}
 
 // Do the byte ranges [p, p + pb) and [q, q + qb) meet?  Addresses only: host and device pointers alike.
 static bool ranges_overlap(const void* p, int64_t pb, const void* q, int64_t qb) {
@@ -107,23 +77,21 @@ static int64_t next_pow2(int64_t v) {
     return p;
 }
 
-#include "host_util.hpp"      // free_dev, DevBuf, DevCtx, Staging, Carve
-
 // ------------------------------------------------------------------------------------ csr
 struct gmrf_csr : DevCtx {
     int64_t n_rows = 0, n_cols = 0, nnz = 0;
-    int64_t* d_rowptr = nullptr;
-    int32_t* d_colidx = nullptr;
-    double* d_vals = nullptr;
-    float* d_vals32 = nullptr;
-    double* d_diag = nullptr;
+    DevArr<int64_t> d_rowptr;
+    DevArr<int32_t> d_colidx;
+    DevArr<double> d_vals;
+    DevArr<float> d_vals32;
+    DevArr<double> d_diag;
     bool tiles_ok = false;             // every SPMV_ROWS-row tile has at most SPMV_CAP entries (csr_spmv_tiles)
     DevBuf stage_x, stage_y;           // host operands of gmrf_spmm / gmrf_spmm_rows
     // tile plan of csr_spmm_tiles (node-major right-hand sides), built on first use
     int plan_state = 0;                // 0: not built, 1: usable, -1: a tile exceeds the LDS image
-    int64_t* d_tile_uptr = nullptr;    // [tiles + 1] ranges into d_ucols
-    int32_t* d_ucols = nullptr;        // distinct columns of every tile, ascending
-    uint16_t* d_lidx = nullptr;        // per entry: index of its column in the tile's list
+    DevArr<int64_t> d_tile_uptr;       // [tiles + 1] ranges into d_ucols
+    DevArr<int32_t> d_ucols;           // distinct columns of every tile, ascending
+    DevArr<uint16_t> d_lidx;           // per entry: index of its column in the tile's list
     int64_t n_ucols = 0;
     int plan_rows = 0, plan_ucap = 0, plan_ecap = 0, plan_ecap_pad = 0, plan_umax = 0;   // rows per tile, LDS capacities (distinct columns, entries)
     uint64_t id = 0;                   // unique per created matrix (the selected-inverse plan of a handle is keyed by it)
@@ -146,20 +114,17 @@ struct GemmShapeStat {
 
 struct TwistState;
 
-struct gmrf_handle {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
+struct gmrf_handle : DevCtx {
     int64_t n = 0, N = 0, bs = 0, bsp = 0, n_pad = 0;
     int64_t B = 1;                     // independent problems factored / solved in lock step
     int64_t sel = 0;                   // problem the accessors (get_block, logdet, ...) address
     int64_t alloc_B = 0, vals_B = 0;
     // symbolic
     int64_t nnz_in = 0, n_entries = 0;
-    uint64_t* d_keys = nullptr;
-    double* d_vals = nullptr;
-    int64_t* d_src = nullptr;          // entry -> index into the caller's nzval
-    double* d_nz_stage = nullptr;      // staging for host nzval
+    DevArr<uint64_t> d_keys;
+    DevArr<double> d_vals;
+    DevArr<int64_t> d_src;             // entry -> index into the caller's nzval
+    DevArr<double> d_nz_stage;         // staging for host nzval
     std::vector<int64_t> diag_first, diag_count, low_first, low_count;
     bool analyzed = false;
     // Layout of the coupling blocks C_i of the CURRENT factor (set by the symbolic phase, by
@@ -169,10 +134,9 @@ struct gmrf_handle {
     // (kst: monotone envelope over all blocks).  C is STORED as the window only: [rmax][bsp - cmin].
     int64_t cmin = 0, rmax = 0;
     std::vector<int> kst, mend;        // mend[u]: column tile u (64 columns from cmin) is zero below row mend[u]
-    int* d_kst = nullptr;              // device copies: [bsp / 64] each
-    int* d_mend = nullptr;
-    int* d_kbx = nullptr;              // [bsp / 64]: max(0, 64 u - cmin): first non-zero row of column tile u of Linv_i[cmin:, :] (selected inversion)
-    int kst_cap = 0;
+    DevArr<int> d_kst;                 // device copies: [bsp / 64] each
+    DevArr<int> d_mend;
+    DevArr<int> d_kbx;                 // [bsp / 64]: max(0, 64 u - cmin): first non-zero row of column tile u of Linv_i[cmin:, :] (selected inversion)
     double c_streamed = 0.0;           // doubles of one C_i inside the staircase (what a k = 1 sweep reads)
     double g2_tile_k = 0.0;            // sum over lower tiles of the K extent of S = -C C^T (flop accounting)
     bool c_dirty = false;              // C must be re-zeroed (new pattern)
@@ -184,22 +148,22 @@ struct gmrf_handle {
     // d_env_ken[4 i + bn]: row tiles of L[256:, 0:256] that column tile bn meets, as a K end (the backward sweep's L_ba^T product).
     std::vector<int> env_lo, env_hi, env_host, env_ken;
     std::vector<unsigned char> env_has, env_ken_has;
-    int* d_env = nullptr;
-    int* d_env_ken = nullptr;
+    DevArr<int> d_env;
+    DevArr<int> d_env_ken;
     bool env_ok = false;               // the arrays above describe the analysed pattern and the current layout
     bool no_env = false;               // set_eager bit 21: no envelope bounds (comparison)
     bool tw_half = false;              // a half of a twisted handle: never takes them
-    int* d_lo_rowptr = nullptr;
-    int* d_dg_rowptr = nullptr;       // [N][bsp + 1]: the diagonal blocks' entries row by row (absolute positions in d_keys)
+    DevArr<int> d_lo_rowptr;
+    DevArr<int> d_dg_rowptr;          // [N][bsp + 1]: the diagonal blocks' entries row by row (absolute positions in d_keys)
     // tile plan of the sparse C = B X^T (spmm_bxt_tiles): per lower block and 64-row tile the distinct columns, per entry its index into them
-    int* d_bxt_uptr = nullptr; int* d_bxt_ucols = nullptr; uint16_t* d_bxt_lidx = nullptr; int* d_bxt_gtiles = nullptr;
+    DevArr<int> d_bxt_uptr, d_bxt_ucols; DevArr<uint16_t> d_bxt_lidx; DevArr<int> d_bxt_gtiles;
     std::vector<int> bxt_ng;           // groups of row tiles per lower block (host copy: the launch's grid)
     int bxt_ecap = 0; int bxt_nrt = 0; bool bxt_plan_ok = false;        // [N][bsp + 1] row-wise view of the lower blocks' entry lists
     int64_t lo_row_max = 0;            // most entries in one row of a lower block
     bool sparse_b = false;             // lower blocks are sparse enough for C = B X^T by spmm_bxt
     bool dense_g1 = false;             // force the dense GEMM for C = B X^T (comparison)
     // factor storage
-    double *d_L = nullptr, *d_C = nullptr, *d_Linv = nullptr;
+    DevArr<double> d_L, d_C, d_Linv;   // ours, or the caller's (gmrf_bt_set_storage: borrowed, never freed)
     bool external_storage = false;
     bool keep_l = true;                // false: L_i lives in a one-block work buffer (sweeps need Linv and C only)
     bool l_valid = false;              // d_L holds the blocks of the current factor (get_block / export / logdet from L)
@@ -207,34 +171,28 @@ struct gmrf_handle {
     std::vector<char> got_block;       // blocks received through gmrf_bt_unpack_blocks_async since the last adopt / commit
     int64_t alloc_rm = 0, alloc_wc = 0;
     bool alloc_keep_l = true;
-    double *d_S = nullptr, *d_B = nullptr, *d_T = nullptr, *d_W = nullptr;
-    double* d_V = nullptr;             // two more work blocks per problem, allocated by the first exact-variance call (var_exact)
-    int64_t v_elems = 0;
+    DevArr<double> d_S, d_B, d_T, d_W;
+    DevArr<double> d_V;                // two more work blocks per problem, allocated by the first exact-variance call (var_exact)
     // selected inverse on a pattern (gmrf_bt_selinv / gmrf_bt_trace_inv): the plan of the last pattern, built on the host once per
     // (layout, pattern); a new layout or shape (layout_gen) drops it, new values of the same pattern keep it
     uint64_t layout_gen = 0;
     uint64_t sel_csr = 0, sel_gen = ~0ull;            // plan of matrix id sel_csr under layout_gen sel_gen
     int64_t sel_nnz = 0;
     std::vector<int64_t> sel_off, sel_nd;             // [N + 1] block step i's entries; [N] how many of them read S_ii
-    int64_t* d_sel_src = nullptr;                     // [entries] element offset inside the block (row * bsp + col)
-    int64_t* d_sel_slot = nullptr;                    // [2][entries] output slot, mirrored slot (-1: none)
-    int64_t sel_cap = 0;
-    double* d_sig = nullptr;                          // [B][nnz] Sigma on the pattern (gmrf_bt_trace_inv, host output)
-    int64_t sig_elems = 0;
-    double* d_dv = nullptr;                           // staged host dvals / trace output
-    int64_t dv_elems = 0;
-    int* d_info = nullptr;
-    double* d_logdet = nullptr;
+    DevArr<int64_t> d_sel_src;                        // [entries] element offset inside the block (row * bsp + col)
+    DevArr<int64_t> d_sel_slot;                       // [2][sel_cap] output slot, mirrored slot (-1: none)
+    int64_t sel_cap = 0;                              // stride between the two halves of d_sel_slot
+    DevArr<double> d_sig;                             // [B][nnz] Sigma on the pattern (gmrf_bt_trace_inv, host output)
+    DevArr<double> d_dv;                              // staged host dvals / trace output
+    DevArr<int> d_info;
+    DevArr<double> d_logdet;
     int64_t alloc_N = 0, alloc_bsp = 0;
     bool factored = false;
     // right-hand-side panels
-    double *d_P = nullptr, *d_Y = nullptr, *d_Tp = nullptr;
-    int64_t kp_cap = 0;
-    double* d_stage = nullptr;
-    int64_t stage_cap = 0;
+    DevArr<double> d_P, d_Y, d_Tp;
+    DevArr<double> d_stage;
     DevBuf mean_arena;                 // a host `mean` of gmrf_bt_sample, a host `out` of gmrf_bt_logdet_batch (Staging)
-    double* d_acc = nullptr;           // variance accumulator / output ([acc_B][n])
-    int64_t acc_B = 0;
+    DevArr<double> d_acc;              // variance accumulator / output ([problems][n])
     int32_t var_group = 0, var_groups = 0;   // the last batched sampled estimator: problems per group of the stage, groups per chunk (gmrf_test_var_groups)
     // graphs
     bool eager = false;
@@ -250,10 +208,9 @@ struct gmrf_handle {
     bool fwd_run = false;              // the factorisation being enqueued carries the forward solve (factor_fwd_ok)
     bool no_factor_fwd = false;        // set_eager bit 19: never (comparison)
     bool no_grouped_gemm = false;      // set_eager bit 20: the panel chain's two independent 128^3 products stay two launches (comparison)
-    GemmDirectOut* d_dout = nullptr;   // where the fused posterior's last products write the caller's mean / samples (posterior_fused_ok allocates)
-    double* d_ft = nullptr;            // [B][bsp]: t = b_i - C_i y_{i-1} of the block being factored, updated panel by panel
-    double* d_fy = nullptr;            // [B][n_pad]: y, laid out as a k = 1 panel (what fill_normals_panel reads row kp from)
-    int64_t fy_elems = 0;
+    DevArr<GemmDirectOut> d_dout;      // where the fused posterior's last products write the caller's mean / samples (posterior_fused_ok allocates)
+    DevArr<double> d_ft;               // [B][bsp]: t = b_i - C_i y_{i-1} of the block being factored, updated panel by panel
+    DevArr<double> d_fy;               // [B][n_pad]: y, laid out as a k = 1 panel (what fill_normals_panel reads row kp from)
     const double* factor_graph_rhs = nullptr;   // b the captured factor graph reads (nullptr: it does not solve)
     unsigned long long* dbg_stamps = nullptr;   // test hook: phase stamps of the fused panel step
     bool fork_graph = false;           // second branch in the captured factor graph (experiment, see potrf_block)
@@ -278,8 +235,7 @@ struct gmrf_handle {
     int factor_graph_route = 0;        // stats.persist_route of the captured factor graph
     int persist_aborts = 0;
     int cu_count = 0;
-    unsigned* d_pflags = nullptr;      // flag words of the persistent launches (zero between launches: potrf_persist cleans up after itself)
-    int64_t pflags_words = 0;
+    DevArr<unsigned> d_pflags;         // flag words of the persistent launches (zero between launches: potrf_persist cleans up after itself)
     // One problem: a whole sweep as ONE persistent launch (sweep_persist.hpp) instead of two dependent launches per block.  Every
     // workgroup must be resident: the handle then claims the whole chip (persist_plan).  A wait that gives up sets the mapped host
     // word; gmrf_bt_solve / gmrf_bt_sample see it at their synchronisation and repeat the call with the launch-per-product form.
@@ -287,13 +243,11 @@ struct gmrf_handle {
     bool no_scatter_fold = false;      // set_eager bit 17: one problem keeps scatter_block as a launch of its own behind S = -C C^T (comparison)
     bool sweep_persist_planned = false;   // the claim covers the whole chip (persist_plan)
     bool sweep_persist_launched = false;  // such a launch was enqueued since the abort word was last looked at
-    unsigned* d_sweep_flags = nullptr;    // [0] the device's abort word
-    double* d_Tsw = nullptr;              // intermediate panel of the persistent sweeps (right-hand side minus coupling product)
-    int64_t t_elems = 0;
-    unsigned* h_sweep_abort = nullptr;    // mapped host word
+    DevArr<unsigned> d_sweep_flags;       // [0] the device's abort word
+    DevArr<double> d_Tsw;                 // intermediate panel of the persistent sweeps (right-hand side minus coupling product)
+    HostWord h_sweep_abort;               // mapped host word
     int sweep_nw = 0;
-    double *d_P2 = nullptr, *d_Y2 = nullptr, *d_T2 = nullptr;     // gmrf_bt_posterior: the samples' panels (their sweep runs beside the mean's)
-    int64_t p2_elems = 0;
+    DevArr<double> d_P2, d_Y2, d_T2;      // gmrf_bt_posterior: the samples' panels (their sweep runs beside the mean's)
     bool sweep_persist_hold = false;      // this call must not use it (an input overlaps an output: a launch that gave up could not be repeated)
     bool no_persist_panels = false;    // batches small enough for it keep potrf_diag128 + the 128^3 products instead of one persistent launch per panel (set_eager bit 15)
     // second branch of the captured factor graph: the inverse assembly of a block's first half runs
@@ -343,16 +297,15 @@ struct TwistState {
     gmrf_handle* top = nullptr;
     gmrf_handle* bot = nullptr;
     int64_t m = -1, N = 0, n = 0, bs = 0, bsp = 0, nnz = 0;
-    uint64_t* d_mkeys = nullptr;       // entries of Q[m+1, m] as entries of B-hat: (row gamma, column bs-1-rho) for Q[rho, gamma]
-    int64_t* d_msrc = nullptr;
-    double* d_mvals = nullptr;
+    DevArr<uint64_t> d_mkeys;          // entries of Q[m+1, m] as entries of B-hat: (row gamma, column bs-1-rho) for Q[rho, gamma]
+    DevArr<int64_t> d_msrc;
+    DevArr<double> d_mvals;
     int64_t m_count = 0;
-    double *d_Bm = nullptr, *d_HJ = nullptr, *d_W = nullptr, *d_Smm = nullptr;     // bsp x bsp, row-major
-    int64_t dense_bsp = 0;
-    double* d_nz = nullptr;            // staged host nzval (both halves gather from it)
+    DevArr<double> d_Bm, d_HJ, d_W, d_Smm;       // bsp x bsp, row-major
+    DevArr<double> d_nz;               // staged host nzval (both halves gather from it)
     const double* d_nz_cur = nullptr;  // the nzval of the current factorisation (device)
-    double* d_z = nullptr;             // column-major n x 64 samples (sampled variances)
-    double* d_var = nullptr;           // the bottom half's variances in its own (reversed) order
+    DevArr<double> d_z;                // column-major n x 64 samples (sampled variances)
+    DevArr<double> d_var;              // the bottom half's variances in its own (reversed) order
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
 };
 
@@ -624,13 +577,7 @@ static gmrf_status set_layout(gmrf_handle* h, int64_t cmin, int64_t rmax, const 
         h->c_streamed += 64.0 * (double)(bsp - cmin - h->kst[t]);
         h->g2_tile_k += (double)(t + 1) * (double)(bsp - cmin - h->kst[t]);    // tiles (t, 0..t) start at kst[t]
     }
-    if (!h->d_kst || !h->d_mend || h->kst_cap < ntile) {
-        free_dev(h->d_kst); free_dev(h->d_mend); free_dev(h->d_kbx); h->d_kst = h->d_mend = h->d_kbx = nullptr; h->kst_cap = 0;
-        HIPCHK(hipMalloc(&h->d_kst, sizeof(int) * ntile));
-        HIPCHK(hipMalloc(&h->d_mend, sizeof(int) * ntile));
-        HIPCHK(hipMalloc(&h->d_kbx, sizeof(int) * ntile));
-        h->kst_cap = ntile;
-    }
+    GCHK(reserve_group(h->stream, {h->d_kst.want((size_t)ntile), h->d_mend.want((size_t)ntile), h->d_kbx.want((size_t)ntile)}));
     {
         std::vector<int> kbx((size_t)ntile);
         for (int u = 0; u < ntile; ++u) kbx[(size_t)u] = (int)std::max<int64_t>(0, 64 * (int64_t)u - cmin);
@@ -649,9 +596,14 @@ static gmrf_status set_layout_dense(gmrf_handle* h) {
 }
 
 static gmrf_status alloc_work(gmrf_handle* h);
+// The factor and the work blocks that follow its shape.  Caller-owned storage is let go of, not freed.
+static void release_factor(gmrf_handle* h) {
+    for (auto* a : {&h->d_L, &h->d_C, &h->d_Linv, &h->d_S, &h->d_B, &h->d_T, &h->d_W, &h->d_logdet}) a->release();
+}
 static gmrf_status alloc_factor(gmrf_handle* h) {
     if (h->alloc_N == h->N && h->alloc_bsp == h->bsp && h->alloc_B == h->B && h->alloc_rm == h->rmax &&
-        h->alloc_wc == c_ld(h) && h->alloc_keep_l == h->keep_l && h->d_Linv)
+        h->alloc_wc == c_ld(h) && h->alloc_keep_l == h->keep_l && h->d_L && h->d_C && h->d_Linv && h->d_S && h->d_B && h->d_T &&
+        h->d_W && h->d_logdet && h->d_pflags)
         return GMRF_OK;
     destroy_graphs(h);
     h->logdet_valid = false;
@@ -666,15 +618,11 @@ static gmrf_status alloc_factor(gmrf_handle* h) {
         h->l_valid = false;
         return GMRF_OK;
     }
-    free_dev(h->d_L); free_dev(h->d_C); free_dev(h->d_Linv);
-    free_dev(h->d_S); free_dev(h->d_B); free_dev(h->d_T); free_dev(h->d_W);
-    free_dev(h->d_logdet);
-    h->d_L = h->d_C = h->d_Linv = h->d_S = h->d_B = h->d_T = h->d_W = h->d_logdet = nullptr;
+    release_factor(h);
     h->l_valid = false;
     const size_t blk = (size_t)blk_elems(h) * sizeof(double) * (size_t)h->B;
-    HIPCHK(hipMalloc(&h->d_L, blk * (h->keep_l ? h->N : 1)));
-    HIPCHK(hipMalloc(&h->d_Linv, blk * h->N));
-    HIPCHK(hipMalloc(&h->d_C, (size_t)stride_pC(h) * sizeof(double) * (size_t)h->B));
+    GCHK(reserve_group(h->stream, {h->d_L.want((size_t)blk_elems(h) * (size_t)h->B * (size_t)(h->keep_l ? h->N : 1)),
+                                   h->d_Linv.want((size_t)stride_pX(h) * (size_t)h->B), h->d_C.want((size_t)stride_pC(h) * (size_t)h->B)}));
     // tiles strictly above the block diagonal of L / Linv are never written: keep them zero
     HIPCHK(hipMemsetAsync(h->d_L, 0, blk * (h->keep_l ? h->N : 1), h->stream));
     HIPCHK(hipMemsetAsync(h->d_Linv, 0, blk * h->N, h->stream));
@@ -687,19 +635,14 @@ static gmrf_status alloc_factor(gmrf_handle* h) {
 
 static gmrf_status alloc_work(gmrf_handle* h) {
     const size_t blk = (size_t)blk_elems(h) * sizeof(double) * (size_t)h->B;
-    HIPCHK(hipMalloc(&h->d_S, blk));
-    HIPCHK(hipMalloc(&h->d_B, blk));
-    HIPCHK(hipMalloc(&h->d_T, blk));
-    HIPCHK(hipMalloc(&h->d_W, blk));
-    HIPCHK(hipMalloc(&h->d_logdet, sizeof(double) * h->N * h->B));
+    const size_t be = (size_t)blk_elems(h) * (size_t)h->B;
+    GCHK(reserve_group(h->stream, {h->d_S.want(be), h->d_B.want(be), h->d_T.want(be), h->d_W.want(be), h->d_logdet.want((size_t)(h->N * h->B))}));
     {   // flag words of the persistent in-block launches (potrf_persist.hpp), one set per problem
-        const int64_t words = (int64_t)persist_flag_words((int)(h->bsp / 64)) * h->B;
-        if (!h->d_pflags || h->pflags_words < words) {
-            free_dev(h->d_pflags); h->d_pflags = nullptr; h->pflags_words = 0;
-            HIPCHK(hipMalloc(&h->d_pflags, sizeof(unsigned) * (size_t)words));
-            HIPCHK(hipMemsetAsync(h->d_pflags, 0, sizeof(unsigned) * (size_t)words, h->stream));
+        const size_t words = (size_t)persist_flag_words((int)(h->bsp / 64)) * (size_t)h->B;
+        if (!h->d_pflags.fits(words)) {
+            GCHK(h->d_pflags.reserve(h->stream, words));
+            HIPCHK(hipMemsetAsync(h->d_pflags, 0, sizeof(unsigned) * words, h->stream));
             HIPCHK(hipStreamSynchronize(h->stream));     // (whatever stream the first launch is on later sees the zeros)
-            h->pflags_words = words;
         }
     }
     h->alloc_N = h->N; h->alloc_bsp = h->bsp; h->alloc_B = h->B;
@@ -712,12 +655,9 @@ static gmrf_status alloc_work(gmrf_handle* h) {
 static void release_shape_buffers(gmrf_handle* h) {
     for (auto& kv : h->sweep_graphs) (void)hipGraphExecDestroy(kv.second);
     h->sweep_graphs.clear();
-    free_dev(h->d_P); free_dev(h->d_Y); free_dev(h->d_Tp);
-    h->d_P = h->d_Y = h->d_Tp = nullptr; h->kp_cap = 0;
+    for (auto* a : {&h->d_P, &h->d_Y, &h->d_Tp, &h->d_acc, &h->d_stage, &h->d_ft, &h->d_fy}) a->release();
     h->mean_arena.release();
-    free_dev(h->d_acc); h->d_acc = nullptr; h->acc_B = 0;
-    free_dev(h->d_stage); h->d_stage = nullptr; h->stage_cap = 0;
-    free_dev(h->d_ft); free_dev(h->d_fy); h->d_ft = h->d_fy = nullptr; h->fy_elems = 0; h->fy_for = nullptr;
+    h->fy_for = nullptr;
 }
 
 static gmrf_status set_shape(gmrf_handle* h, int64_t n, int64_t N) {
@@ -741,25 +681,15 @@ static gmrf_status set_shape(gmrf_handle* h, int64_t n, int64_t N) {
 }
 
 static gmrf_status ensure_panels(gmrf_handle* h, int64_t kp) {
-    if (kp <= h->kp_cap && h->d_P) return GMRF_OK;
+    const size_t pe = (size_t)(kp * h->n_pad * h->B), te = (size_t)(kp * h->bsp * h->B);
+    if (h->d_P.fits(pe) && h->d_Y.fits(pe) && h->d_Tp.fits(te)) return GMRF_OK;
     for (auto& kv : h->sweep_graphs) (void)hipGraphExecDestroy(kv.second);
     h->sweep_graphs.clear();
-    free_dev(h->d_P); free_dev(h->d_Y); free_dev(h->d_Tp);
-    h->d_P = h->d_Y = h->d_Tp = nullptr;
-    HIPCHK(hipMalloc(&h->d_P, sizeof(double) * kp * h->n_pad * h->B));
-    HIPCHK(hipMalloc(&h->d_Y, sizeof(double) * kp * h->n_pad * h->B));
-    HIPCHK(hipMalloc(&h->d_Tp, sizeof(double) * kp * h->bsp * h->B));
-    h->kp_cap = kp;
-    return GMRF_OK;
+    return reserve_group(h->stream, {h->d_P.want(pe), h->d_Y.want(pe), h->d_Tp.want(te)});
 }
 
 static gmrf_status ensure_stage(gmrf_handle* h, int64_t elems) {
-    if (elems <= h->stage_cap && h->d_stage) return GMRF_OK;
-    free_dev(h->d_stage);
-    h->d_stage = nullptr;
-    HIPCHK(hipMalloc(&h->d_stage, sizeof(double) * elems));
-    h->stage_cap = elems;
-    return GMRF_OK;
+    return h->d_stage.reserve(h->stream, (size_t)elems);
 }
 
 // ------------------------------------------------------------------------------------ symbolic
@@ -1004,13 +934,11 @@ static gmrf_status upload_envelope(gmrf_handle* h, const SymbolicPlan& sp) {
     derive_envelope(N, bsp, sp, eh);
     h->env_host.swap(eh.host); h->env_has.swap(eh.has); h->env_ken.swap(eh.ken); h->env_ken_has.swap(eh.ken_has);
     const bool any = eh.any;
-    free_dev(h->d_env); free_dev(h->d_env_ken);
-    h->d_env = nullptr; h->d_env_ken = nullptr;
+    h->d_env.release(); h->d_env_ken.release();
     if (!any) return GMRF_OK;                                  // (no such structure: every launch as without the bounds)
-    HIPCHK(hipMalloc(&h->d_env, h->env_host.size() * sizeof(int)));
-    HIPCHK(hipMalloc(&h->d_env_ken, h->env_ken.size() * sizeof(int)));
-    HIPCHK(hipMemcpyAsync(h->d_env, h->env_host.data(), h->env_host.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->d_env_ken, h->env_ken.data(), h->env_ken.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    GCHK(reserve_group(h->stream, {h->d_env.want(h->env_host.size()), h->d_env_ken.want(h->env_ken.size())}));
+    GCHK(h->d_env.upload(h->stream, h->env_host));
+    GCHK(h->d_env_ken.upload(h->stream, h->env_ken));
     HIPCHK(hipStreamSynchronize(h->stream));
     h->env_ok = true;
     return GMRF_OK;
@@ -1027,46 +955,32 @@ static gmrf_status upload_entries(gmrf_handle* h, const std::vector<std::vector<
     const auto& keys = sp.keys; const auto& src = sp.src;
     GCHK(set_layout(h, sp.cmin, sp.rmax, sp.first));
     GCHK(upload_envelope(h, sp));
-    free_dev(h->d_keys); free_dev(h->d_vals); free_dev(h->d_src); free_dev(h->d_nz_stage);
-    h->d_keys = nullptr; h->d_vals = nullptr; h->d_src = nullptr; h->d_nz_stage = nullptr;
     h->n_entries = (int64_t)keys.size();
     h->nnz_in = nnz_in;
-    const size_t ne = std::max<size_t>(keys.size(), 1);
-    HIPCHK(hipMalloc(&h->d_keys, ne * sizeof(uint64_t)));
-    HIPCHK(hipMalloc(&h->d_vals, ne * sizeof(double) * h->B));
-    HIPCHK(hipMalloc(&h->d_src, ne * sizeof(int64_t)));
-    HIPCHK(hipMalloc(&h->d_nz_stage, std::max<int64_t>(nnz_in, 1) * sizeof(double) * h->B));
+    GCHK(reserve_group(h->stream, {h->d_keys.want(keys.size()), h->d_vals.want(keys.size() * (size_t)h->B), h->d_src.want(keys.size()),
+                                   h->d_nz_stage.want((size_t)nnz_in * (size_t)h->B)}));
     h->vals_B = h->B;
     if (!keys.empty()) {
         // (stream-ordered copies + a stream wait: a synchronous hipMemcpy goes through the legacy stream,
         //  which HIP refuses while another host thread is capturing a graph)
-        HIPCHK(hipMemcpyAsync(h->d_keys, keys.data(), keys.size() * sizeof(uint64_t), hipMemcpyHostToDevice, h->stream));
-        HIPCHK(hipMemcpyAsync(h->d_src, src.data(), src.size() * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+        GCHK(h->d_keys.upload(h->stream, keys));
+        GCHK(h->d_src.upload(h->stream, src));
         HIPCHK(hipStreamSynchronize(h->stream));
     }
-    free_dev(h->d_lo_rowptr);
-    h->d_lo_rowptr = nullptr;
-    HIPCHK(hipMalloc(&h->d_lo_rowptr, sp.rowptr.size() * sizeof(int)));
-    HIPCHK(hipMemcpyAsync(h->d_lo_rowptr, sp.rowptr.data(), sp.rowptr.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    free_dev(h->d_dg_rowptr);
-    h->d_dg_rowptr = nullptr;
-    HIPCHK(hipMalloc(&h->d_dg_rowptr, sp.drowptr.size() * sizeof(int)));
-    HIPCHK(hipMemcpyAsync(h->d_dg_rowptr, sp.drowptr.data(), sp.drowptr.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    GCHK(h->d_lo_rowptr.upload(h->stream, sp.rowptr));
+    GCHK(h->d_dg_rowptr.upload(h->stream, sp.drowptr));
     HIPCHK(hipStreamSynchronize(h->stream));
     h->lo_row_max = sp.max_row;
     h->sparse_b = sp.sparse_b;
-    free_dev(h->d_bxt_uptr); free_dev(h->d_bxt_ucols); free_dev(h->d_bxt_lidx); free_dev(h->d_bxt_gtiles);
-    h->d_bxt_uptr = nullptr; h->d_bxt_ucols = nullptr; h->d_bxt_lidx = nullptr; h->d_bxt_gtiles = nullptr; h->bxt_plan_ok = false;
+    h->bxt_plan_ok = false;
     if (sp.bxt_ok) {
-        HIPCHK(hipMalloc(&h->d_bxt_gtiles, sp.gtiles.size() * sizeof(int)));
-        HIPCHK(hipMemcpyAsync(h->d_bxt_gtiles, sp.gtiles.data(), sp.gtiles.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+        GCHK(reserve_group(h->stream, {h->d_bxt_gtiles.want(sp.gtiles.size()), h->d_bxt_uptr.want(sp.uptr.size()),
+                                       h->d_bxt_ucols.want(sp.ucols.size()), h->d_bxt_lidx.want(sp.lidx.size())}));
+        GCHK(h->d_bxt_gtiles.upload(h->stream, sp.gtiles));
         h->bxt_ng = sp.ng;
-        HIPCHK(hipMalloc(&h->d_bxt_uptr, sp.uptr.size() * sizeof(int)));
-        HIPCHK(hipMalloc(&h->d_bxt_ucols, std::max<size_t>(sp.ucols.size(), 1) * sizeof(int)));
-        HIPCHK(hipMalloc(&h->d_bxt_lidx, sp.lidx.size() * sizeof(uint16_t)));
-        HIPCHK(hipMemcpyAsync(h->d_bxt_uptr, sp.uptr.data(), sp.uptr.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
-        if (!sp.ucols.empty()) HIPCHK(hipMemcpyAsync(h->d_bxt_ucols, sp.ucols.data(), sp.ucols.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
-        HIPCHK(hipMemcpyAsync(h->d_bxt_lidx, sp.lidx.data(), sp.lidx.size() * sizeof(uint16_t), hipMemcpyHostToDevice, h->stream));
+        GCHK(h->d_bxt_uptr.upload(h->stream, sp.uptr));
+        GCHK(h->d_bxt_ucols.upload(h->stream, sp.ucols));
+        GCHK(h->d_bxt_lidx.upload(h->stream, sp.lidx));
         HIPCHK(hipStreamSynchronize(h->stream));
         h->bxt_ecap = sp.ecap; h->bxt_nrt = sp.nrt; h->bxt_plan_ok = true;
     }
@@ -1122,10 +1036,7 @@ static gmrf_status load_values(gmrf_handle* h, const double* nzval) {
     if (!nzval) return bad_shape("null nzval");
     const double* d_nz = nzval;
     if (h->vals_B != h->B) {            // batch size changed after the analysis: resize the value buffers
-        free_dev(h->d_vals); free_dev(h->d_nz_stage);
-        h->d_vals = nullptr; h->d_nz_stage = nullptr;
-        HIPCHK(hipMalloc(&h->d_vals, std::max<int64_t>(h->n_entries, 1) * sizeof(double) * h->B));
-        HIPCHK(hipMalloc(&h->d_nz_stage, std::max<int64_t>(h->nnz_in, 1) * sizeof(double) * h->B));
+        GCHK(reserve_group(h->stream, {h->d_vals.want((size_t)(h->n_entries * h->B)), h->d_nz_stage.want((size_t)(h->nnz_in * h->B))}));
         h->vals_B = h->B;
     }
     if (!is_device_ptr(nzval)) {
@@ -1314,7 +1225,7 @@ static bool persist_fits(const gmrf_handle* h, int nt, int j0, int j1, int xrows
 static gmrf_status launch_persist(gmrf_handle* h, double* S, double* L, double* X, int nt, int j0, int j1, int xrows, int blk_id,
                                   double flops) {
     const int words = persist_flag_words(nt);
-    if (!h->d_pflags || h->pflags_words < (int64_t)words * h->B) return bad_shape("internal: flag words of the persistent launches not allocated");
+    if (!h->d_pflags.fits((size_t)((int64_t)words * h->B))) return bad_shape("internal: flag words of the persistent launches not allocated");
     // (no memset node: the words are zero -- zeroed when allocated, left zero by the last workgroup out of every launch)
     PersistArgs pa;
     pa.S = S; pa.L = L; pa.X = X; pa.ld = h->bsp; pa.nt = nt; pa.j0 = j0; pa.j1 = j1; pa.xrows = xrows;
@@ -1867,13 +1778,10 @@ static gmrf_status factor_fwd_ok(gmrf_handle* h, bool* ok) {
     if (!h->frhs || h->no_factor_fwd || h->B <= 1 || tw_on(h) || h->tw_blk >= 0 || h->fork_graph || h->rmax <= 0) return GMRF_OK;
     const int bsp = (int)h->bsp, nt = bsp / 64;
     if (potrf_route(h) != ROUTE_PANELS256 || bsp % 256 != 0) return GMRF_OK;
-    const int64_t elems = h->B * h->n_pad + h->B * h->bsp;
-    if (!h->d_fy || h->fy_elems < elems) {
-        HIPCHK(hipStreamSynchronize(h->stream));
-        free_dev(h->d_ft); free_dev(h->d_fy); h->d_ft = h->d_fy = nullptr; h->fy_elems = 0; h->fy_for = nullptr;
-        HIPCHK(hipMalloc(&h->d_fy, sizeof(double) * (size_t)(h->B * h->n_pad)));
-        HIPCHK(hipMalloc(&h->d_ft, sizeof(double) * (size_t)(h->B * h->bsp)));
-        h->fy_elems = elems;
+    const size_t ye = (size_t)(h->B * h->n_pad), te = (size_t)(h->B * h->bsp);
+    if (!h->d_fy.fits(ye) || !h->d_ft.fits(te)) {
+        h->fy_for = nullptr;
+        GCHK(reserve_group(h->stream, {h->d_fy.want(ye), h->d_ft.want(te)}));
     }
     h->tail_probe = true; h->tail_refused = false;
     gmrf_status st = GMRF_OK;
@@ -1932,7 +1840,7 @@ static gmrf_status persist_check_range(gmrf_handle* h, int64_t i0, int64_t i1, i
         persist_give_up(h);
         const int restore[4] = {h->info_checked, 0, 0, 0};     // (what the aborted range wrote into the info word means nothing)
         HIPCHK(hipMemcpyAsync(h->d_info, restore, 4 * sizeof(int), hipMemcpyHostToDevice, h->stream));
-        if (h->d_pflags) HIPCHK(hipMemsetAsync(h->d_pflags, 0, sizeof(unsigned) * (size_t)h->pflags_words, h->stream));   // (belt and braces: the drained launches cleaned up themselves)
+        if (h->d_pflags) HIPCHK(hipMemsetAsync(h->d_pflags, 0, sizeof(unsigned) * h->d_pflags.size(), h->stream));   // (belt and braces: the drained launches cleaned up themselves)
         h->stats.persist_route = 0;
         GCHK(factor_blocks_range(h, i0, i1));
         HIPCHK(hipMemcpyAsync(hinfo2, h->d_info, 2 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
@@ -2076,21 +1984,16 @@ static bool sweep_persist_ok(const gmrf_handle* h, int kp) {
 // the words and the intermediate panel of the persistent sweeps (before any capture: allocations are not allowed inside one)
 static gmrf_status sweep_persist_prepare(gmrf_handle* h, int kp) {
     if (!h->d_sweep_flags) {
-        HIPCHK(hipMalloc(&h->d_sweep_flags, sizeof(unsigned) * 16));
+        GCHK(h->d_sweep_flags.reserve(h->stream, 16));
         HIPCHK(hipMemsetAsync(h->d_sweep_flags, 0, sizeof(unsigned) * 16, h->stream));
     }
     h->sweep_nw = std::min(256, h->cu_count);
-    if (!h->h_sweep_abort) {
-        HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&h->h_sweep_abort), 64, hipHostMallocMapped));
-        *h->h_sweep_abort = 0u;
-    }
-    const int64_t need = (int64_t)kp * h->n_pad;
-    if (!h->d_Tsw || h->t_elems < need) {
+    HIPCHK(h->h_sweep_abort.open());
+    const size_t need = (size_t)((int64_t)kp * h->n_pad);
+    if (!h->d_Tsw.fits(need)) {
         HIPCHK(hipStreamSynchronize(h->stream));
-        free_dev(h->d_Tsw); h->d_Tsw = nullptr; h->t_elems = 0;
         destroy_graphs(h);                                  // (captured sweeps hold the old pointer)
-        HIPCHK(hipMalloc(&h->d_Tsw, sizeof(double) * (size_t)need));
-        h->t_elems = need;
+        GCHK(h->d_Tsw.reserve(h->stream, need));
     }
     return GMRF_OK;
 }
@@ -2101,7 +2004,7 @@ static gmrf_status launch_sweep_persist(gmrf_handle* h, bool backward, int kp, d
     const int64_t elems = (int64_t)kp * h->n_pad;
     hipStream_t st = st_over ? st_over : h->stream;
     double* Tp = T_over ? T_over : h->d_Tsw;
-    if (!h->d_sweep_flags || !h->h_sweep_abort || nw <= 0 || !Tp || (!T_over && h->t_elems < elems))
+    if (!h->d_sweep_flags || !h->h_sweep_abort || nw <= 0 || !Tp || (!T_over && !h->d_Tsw.fits((size_t)elems)))
         return bad_shape("internal: words / panel of the persistent sweeps not allocated");
     if (elems % 2 != 0) return bad_shape("internal: the persistent sweeps' panels need an even element count (sweep_fill_sentinel)");
     SweepPersistArgs a;
@@ -2145,7 +2048,7 @@ static gmrf_status sweep_persist_check(gmrf_handle* h, bool* repeat) {
     *repeat = false;
     if (!h->sweep_persist_launched) return GMRF_OK;
     h->sweep_persist_launched = false;
-    if (!h->h_sweep_abort || *reinterpret_cast<volatile unsigned*>(h->h_sweep_abort) == 0u) return GMRF_OK;
+    if (!h->h_sweep_abort || *static_cast<volatile unsigned*>(h->h_sweep_abort.p) == 0u) return GMRF_OK;
     *h->h_sweep_abort = 0u;
     persist_give_up(h);
     HIPCHK(hipMemsetAsync(h->d_sweep_flags, 0, sizeof(unsigned) * 16, h->stream));
@@ -2400,12 +2303,13 @@ gmrf_status gmrf_bt_create(int32_t device, void* stream, gmrf_handle** out) {
         return GMRF_ERR_NO_DEVICE;
     }
     HIPCHK(hipSetDevice(device));
-    gmrf_handle* h = new gmrf_handle();
+    std::unique_ptr<gmrf_handle, gmrf_status (*)(gmrf_handle*)> guard(new gmrf_handle(), gmrf_bt_destroy);
+    gmrf_handle* h = guard.get();
     memset(&h->stats, 0, sizeof(h->stats));
     h->device = device;
     if (stream) { h->stream = (hipStream_t)stream; h->own_stream = false; }
     else { HIPCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking)); h->own_stream = true; }
-    HIPCHK(hipMalloc(&h->d_info, 4 * sizeof(int)));           // [0] info, [1] abort word of the persistent kernel
+    GCHK(h->d_info.reserve(h->stream, 4));                    // [0] info, [1] abort word of the persistent kernel
     HIPCHK(hipMemsetAsync(h->d_info, 0, 4 * sizeof(int), h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     HIPCHK(hipEventCreate(&h->ev0));
@@ -2417,7 +2321,7 @@ gmrf_status gmrf_bt_create(int32_t device, void* stream, gmrf_handle** out) {
     HIPCHK(hipFuncSetAttribute((const void*)potrf_diag128_slim, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     HIPCHK(gemm_init());
     HIPCHK(gemm_dma_init());
-    *out = h;
+    *out = guard.release();
     return GMRF_OK;
 }
 
@@ -2428,25 +2332,12 @@ gmrf_status gmrf_bt_destroy(gmrf_handle* h) {
     (void)hipStreamSynchronize(h->stream);
     persist_release(h);
     destroy_graphs(h);
-    free_dev(h->d_keys); free_dev(h->d_vals); free_dev(h->d_src); free_dev(h->d_nz_stage);
-    free_dev(h->d_lo_rowptr); free_dev(h->d_dg_rowptr); free_dev(h->d_kst); free_dev(h->d_mend); free_dev(h->d_env); free_dev(h->d_env_ken);
-    free_dev(h->d_bxt_uptr); free_dev(h->d_bxt_ucols); free_dev(h->d_bxt_lidx); free_dev(h->d_bxt_gtiles);
-    if (!h->external_storage) { free_dev(h->d_L); free_dev(h->d_C); free_dev(h->d_Linv); }
-    else if (!h->keep_l) free_dev(h->d_L);               // the one-block work buffer is ours
-    free_dev(h->d_S); free_dev(h->d_B); free_dev(h->d_T); free_dev(h->d_W);
-    free_dev(h->d_sweep_flags); free_dev(h->d_Tsw); free_dev(h->d_P2); free_dev(h->d_Y2); free_dev(h->d_T2);
-    if (h->h_sweep_abort) { (void)hipHostFree(h->h_sweep_abort); h->h_sweep_abort = nullptr; }
-    free_dev(h->d_dout); free_dev(h->d_info); free_dev(h->d_logdet); free_dev(h->d_pflags); free_dev(h->d_kbx); free_dev(h->d_V);
-    free_dev(h->d_P); free_dev(h->d_Y); free_dev(h->d_Tp);
-    free_dev(h->d_stage); h->mean_arena.release(); free_dev(h->d_acc);
-    free_dev(h->d_ft); free_dev(h->d_fy);
-    free_dev(h->d_sel_src); free_dev(h->d_sel_slot); free_dev(h->d_sig); free_dev(h->d_dv);
     for (auto e : h->ev_pool) (void)hipEventDestroy(e);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
     for (auto e : h->fork_events) (void)hipEventDestroy(e);
     if (h->aux) (void)hipStreamDestroy(h->aux);
-    if (h->own_stream) (void)hipStreamDestroy(h->stream);
+    h->close();
     delete h;
     return GMRF_OK;
 }
@@ -2655,15 +2546,15 @@ gmrf_status gmrf_bt_set_storage(gmrf_handle* h, int64_t n, int64_t n_blocks, int
     GCHK(set_shape(h, n, n_blocks));
     HIPCHK(hipStreamSynchronize(h->stream));
     destroy_graphs(h);
-    if (!h->external_storage) { free_dev(h->d_L); free_dev(h->d_C); free_dev(h->d_Linv); }
-    else if (!h->keep_l) free_dev(h->d_L);             // our one-block work buffer of an earlier set_storage
-    free_dev(h->d_S); free_dev(h->d_B); free_dev(h->d_T); free_dev(h->d_W); free_dev(h->d_logdet);
-    h->d_S = h->d_B = h->d_T = h->d_W = h->d_logdet = nullptr;
-    h->d_L = (double*)dev_L; h->d_C = (double*)dev_C; h->d_Linv = (double*)dev_Linv;
+    release_factor(h);                                 // (frees what is ours: an earlier call's storage stays the caller's)
+    const size_t be = (size_t)blk_elems(h) * (size_t)h->B;
+    h->d_C.borrow((double*)dev_C, be * (size_t)std::max<int64_t>(h->N - 1, 1));
+    h->d_Linv.borrow((double*)dev_Linv, be * (size_t)h->N);
     h->external_storage = true;
     h->factored = false; h->l_valid = false; h->logdet_valid = false;   // whatever was factored lived in the old buffers
-    if (!h->keep_l) {                                  // one-block work buffer for L_i
-        HIPCHK(hipMalloc(&h->d_L, (size_t)blk_elems(h) * sizeof(double) * (size_t)h->B));
+    if (h->keep_l) h->d_L.borrow((double*)dev_L, be * (size_t)h->N);
+    else {                                             // one-block work buffer for L_i: ours
+        GCHK(h->d_L.reserve(h->stream, be));
         HIPCHK(hipMemsetAsync(h->d_L, 0, (size_t)blk_elems(h) * sizeof(double) * (size_t)h->B, h->stream));
     }
     if (!h->analyzed) GCHK(set_layout_dense(h));      // until a pattern is analysed / a layout adopted
@@ -3109,16 +3000,17 @@ gmrf_status gmrf_comm_create(int32_t device, int32_t rank, int32_t world, const 
     }
     GCHK(rccl_load());
     HIPCHK(hipSetDevice(device));
-    gmrf_comm* c = new gmrf_comm();
+    std::unique_ptr<gmrf_comm, gmrf_status (*)(gmrf_comm*)> guard(new gmrf_comm(), gmrf_comm_destroy);
+    gmrf_comm* c = guard.get();
     c->device = device; c->rank = rank; c->world = world;
     NcclUid u;
     memcpy(u.b, id128, 128);
     int r = g_rccl.CommInitRank(&c->comm, world, u, rank);
-    if (r != 0) { g_last_error = std::string("ncclCommInitRank: ") + g_rccl.GetErrorString(r); delete c; return GMRF_ERR_RCCL; }
+    if (r != 0) { g_last_error = std::string("ncclCommInitRank: ") + g_rccl.GetErrorString(r); return GMRF_ERR_RCCL; }
     HIPCHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     HIPCHK(hipEventCreateWithFlags(&c->ev_in, hipEventDisableTiming));
     HIPCHK(hipEventCreateWithFlags(&c->ev_out, hipEventDisableTiming));
-    *out = c;
+    *out = guard.release();
     return GMRF_OK;
 }
 
@@ -3127,7 +3019,6 @@ gmrf_status gmrf_comm_destroy(gmrf_comm* c) {
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->comm) (void)g_rccl.CommDestroy(c->comm);
-    c->small.release(); c->pack.release();
     if (c->ev_in) (void)hipEventDestroy(c->ev_in);
     if (c->ev_out) (void)hipEventDestroy(c->ev_out);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -3389,16 +3280,8 @@ static gmrf_status posterior_beside(gmrf_handle* h, const double* b, uint64_t se
     const int kp = pad_k(k);
     GCHK(ensure_panels(h, 1));
     GCHK(sweep_persist_prepare(h, 1));
-    const int64_t elems = (int64_t)kp * h->n_pad;
-    if (!h->d_P2 || h->p2_elems < elems) {
-        HIPCHK(hipStreamSynchronize(h->stream));
-        free_dev(h->d_P2); free_dev(h->d_Y2); free_dev(h->d_T2);
-        h->d_P2 = h->d_Y2 = h->d_T2 = nullptr; h->p2_elems = 0;
-        HIPCHK(hipMalloc(&h->d_P2, sizeof(double) * (size_t)elems));
-        HIPCHK(hipMalloc(&h->d_Y2, sizeof(double) * (size_t)elems));
-        HIPCHK(hipMalloc(&h->d_T2, sizeof(double) * (size_t)elems));
-        h->p2_elems = elems;
-    }
+    const size_t elems = (size_t)((int64_t)kp * h->n_pad);
+    GCHK(reserve_group(h->stream, {h->d_P2.want(elems), h->d_Y2.want(elems), h->d_T2.want(elems)}));
     GCHK(ensure_aux(h));
     h->fork_next = 0;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
@@ -3440,7 +3323,7 @@ static bool posterior_fused_ok(gmrf_handle* h, int64_t k, bool dev_all) {
     if (kp % 64 != 0 || (int64_t)h->B * (h->bsp / 64) * (kp / 64) < 128) return false;
     if ((int64_t)(kp + 1) * h->n_pad * 8 >= ((int64_t)1 << 32)) return false;
     if (ensure_panels(h, kp + 1) != GMRF_OK) return false;
-    if (!h->d_dout && hipMalloc(&h->d_dout, sizeof(GemmDirectOut)) != hipSuccess) { (void)hipGetLastError(); return false; }
+    if (!h->d_dout && h->d_dout.reserve(h->stream, 1) != GMRF_OK) { (void)hipGetLastError(); return false; }
     h->tail_probe = true; h->tail_refused = false;
     const gmrf_status st = sweep_launches(h, true, kp, h->d_P, h->d_Y, true, h->d_dout);
     h->tail_probe = false;
@@ -3635,24 +3518,20 @@ gmrf_status gmrf_csr_create(int32_t device, void* stream, int64_t n_rows, int64_
     for (int64_t r = 0; r < n_rows; r += SPMV_ROWS)
         if (rp[std::min(n_rows, r + SPMV_ROWS)] - rp[r] > SPMV_CAP) { m->tiles_ok = false; break; }
     m->n_rows = n_rows; m->n_cols = n_cols; m->nnz = nnz;
-    HIPCHK(hipMalloc(&m->d_rowptr, sizeof(int64_t) * (n_rows + 1)));
-    HIPCHK(hipMalloc(&m->d_colidx, sizeof(int32_t) * std::max<int64_t>(nnz, 1)));
-    HIPCHK(hipMemcpyAsync(m->d_rowptr, rp.data(), sizeof(int64_t) * (n_rows + 1), hipMemcpyHostToDevice, m->stream));
-    HIPCHK(hipMemcpyAsync(m->d_colidx, ci.data(), sizeof(int32_t) * nnz, hipMemcpyHostToDevice, m->stream));
+    GCHK(m->d_rowptr.upload(m->stream, rp));
+    GCHK(m->d_colidx.upload(m->stream, ci));
     HIPCHK(hipStreamSynchronize(m->stream));
     if (values_f32) {
         std::vector<float> vf((size_t)nnz);
         for (int64_t p = 0; p < nnz; ++p) vf[p] = (float)vals[p];
-        HIPCHK(hipMalloc(&m->d_vals32, sizeof(float) * std::max<int64_t>(nnz, 1)));
-        HIPCHK(hipMemcpyAsync(m->d_vals32, vf.data(), sizeof(float) * nnz, hipMemcpyHostToDevice, m->stream));
+        GCHK(m->d_vals32.upload(m->stream, vf));
         HIPCHK(hipStreamSynchronize(m->stream));
     } else {
-        HIPCHK(hipMalloc(&m->d_vals, sizeof(double) * std::max<int64_t>(nnz, 1)));
-        HIPCHK(hipMemcpyAsync(m->d_vals, vals, sizeof(double) * nnz, hipMemcpyHostToDevice, m->stream));
+        GCHK(m->d_vals.upload(m->stream, vals, (size_t)nnz));
         HIPCHK(hipStreamSynchronize(m->stream));
     }
     if (n_rows == n_cols) {
-        HIPCHK(hipMalloc(&m->d_diag, sizeof(double) * n_rows));
+        GCHK(m->d_diag.reserve(m->stream, (size_t)n_rows));
         hipLaunchKernelGGL(csr_extract_diag, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, m->stream,
                            m->d_rowptr, m->d_colidx, m->d_vals, m->d_vals32, n_rows, m->d_diag);
         HIPCHK(hipGetLastError());
@@ -3665,11 +3544,6 @@ gmrf_status gmrf_csr_create(int32_t device, void* stream, int64_t n_rows, int64_
 gmrf_status gmrf_csr_destroy(gmrf_csr* m) {
     if (!m) return GMRF_OK;
     m->close();
-    if (m->has_device()) {
-        free_dev(m->d_rowptr); free_dev(m->d_colidx); free_dev(m->d_vals); free_dev(m->d_vals32);
-        free_dev(m->d_diag); m->stage_x.release(); m->stage_y.release();
-        free_dev(m->d_tile_uptr); free_dev(m->d_ucols); free_dev(m->d_lidx);
-    }
     delete m;
     return GMRF_OK;
 }
@@ -3771,12 +3645,9 @@ static gmrf_status spmm_plan(gmrf_csr* m) {
         m->plan_ecap_pad = (spmm_tile_pad_lds_bytes(R, (int)((umax + 7) / 8 * 8), ecap_pad64) <= lds_budget + 1024) ? ecap_pad64 : 0;
         (void)ecap_pad;
         m->n_ucols = (int64_t)ucols.size();
-        HIPCHK(hipMalloc(&m->d_tile_uptr, sizeof(int64_t) * (T + 1)));
-        HIPCHK(hipMalloc(&m->d_ucols, sizeof(int32_t) * std::max<size_t>(ucols.size(), 1)));
-        HIPCHK(hipMalloc(&m->d_lidx, sizeof(uint16_t) * std::max<int64_t>(m->nnz, 1)));
-        HIPCHK(hipMemcpyAsync(m->d_tile_uptr, uptr.data(), sizeof(int64_t) * (T + 1), hipMemcpyHostToDevice, m->stream));
-        if (!ucols.empty()) HIPCHK(hipMemcpyAsync(m->d_ucols, ucols.data(), sizeof(int32_t) * ucols.size(), hipMemcpyHostToDevice, m->stream));
-        if (m->nnz > 0) HIPCHK(hipMemcpyAsync(m->d_lidx, lidx.data(), sizeof(uint16_t) * m->nnz, hipMemcpyHostToDevice, m->stream));
+        GCHK(m->d_tile_uptr.upload(m->stream, uptr.data(), (size_t)(T + 1)));
+        GCHK(m->d_ucols.upload(m->stream, ucols));
+        GCHK(m->d_lidx.upload(m->stream, lidx.data(), (size_t)m->nnz));
         HIPCHK(hipStreamSynchronize(m->stream));
         m->plan_state = 1;
         break;
@@ -3939,17 +3810,17 @@ gmrf_status gmrf_spmm_rows_async(const gmrf_csr* S, const double* X, double* Y, 
 struct gmrf_assembler : DevCtx {        // device -1: symbolic only (pattern queries; no numeric phase)
     int64_t n = 0, m = 0, nnz_q = 0, nnz_j = 0, nnz_out = 0, n_pairs = 0;
     std::vector<int64_t> colptr, rowval;            // result pattern (CSC, 0-based, rows ascending)
-    int64_t *d_pptr = nullptr, *d_qmap = nullptr, *d_jt_ptr = nullptr, *d_j_rptr = nullptr;
-    int32_t *d_pa = nullptr, *d_pb = nullptr, *d_jt_row = nullptr, *d_jt_src = nullptr, *d_j_col = nullptr;
+    DevArr<int64_t> d_pptr, d_qmap, d_jt_ptr, d_j_rptr;
+    DevArr<int32_t> d_pa, d_pb, d_jt_row, d_jt_src, d_j_col;
     DevBuf arena;                       // host arguments of the current call (Staging)
     // the batch calls: Q's own pattern (0-based; symmetric, so its CSC arrays are read by rows), uploaded by the first objective
     std::vector<int64_t> q_ptr;
     std::vector<int32_t> q_row;
-    int64_t* d_q_ptr = nullptr;
-    int32_t* d_q_row = nullptr;
+    DevArr<int64_t> d_q_ptr;
+    DevArr<int32_t> d_q_row;
     // ... and the result pattern the same way (colptr / rowval with 32-bit rows), uploaded by the first quadratic form
-    int64_t* d_o_ptr = nullptr;
-    int32_t* d_o_row = nullptr;
+    DevArr<int64_t> d_o_ptr;
+    DevArr<int32_t> d_o_row;
     DevBuf bpart;                       // work arrays: [batch][m] (J x + obs_diff) of the rhs, the partial sums of the objective / quadratic form
 };
 
@@ -4022,18 +3893,16 @@ gmrf_status gmrf_assemble_create(int32_t device, void* stream, int64_t n, const 
     }
     GCHK(as->open(device, stream, hipStreamDefault, "gmrf_assemble_create"));      // (a blocking stream: inherited, not chosen)
     if (as->device >= 0) {
-        auto up = [&](auto** d, const auto& v) -> hipError_t {
-            using T = typename std::remove_reference<decltype(v[0])>::type;
-            hipError_t e = hipMalloc((void**)d, std::max<size_t>(v.size(), 1) * sizeof(T));
-            if (e == hipSuccess && !v.empty()) e = hipMemcpyAsync(*d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, as->stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(as->stream);
-            return e;
+        auto up = [&](auto& d, const auto& v) -> gmrf_status {
+            GCHK(d.upload(as->stream, v));
+            HIPCHK(hipStreamSynchronize(as->stream));
+            return GMRF_OK;
         };
         std::vector<int64_t> j_rptr((size_t)m + 1);
         for (int64_t k = 0; k <= m; ++k) j_rptr[k] = j_rowptr[k] - b;
-        HIPCHK(up(&as->d_pptr, pptr)); HIPCHK(up(&as->d_qmap, qmap)); HIPCHK(up(&as->d_pa, pa)); HIPCHK(up(&as->d_pb, pb));
-        HIPCHK(up(&as->d_jt_ptr, jt_ptr)); HIPCHK(up(&as->d_jt_row, jt_row)); HIPCHK(up(&as->d_jt_src, jt_src));
-        HIPCHK(up(&as->d_j_rptr, j_rptr)); HIPCHK(up(&as->d_j_col, j_col));
+        GCHK(up(as->d_pptr, pptr)); GCHK(up(as->d_qmap, qmap)); GCHK(up(as->d_pa, pa)); GCHK(up(as->d_pb, pb));
+        GCHK(up(as->d_jt_ptr, jt_ptr)); GCHK(up(as->d_jt_row, jt_row)); GCHK(up(as->d_jt_src, jt_src));
+        GCHK(up(as->d_j_rptr, j_rptr)); GCHK(up(as->d_j_col, j_col));
     }
     *out = guard.release();
     return GMRF_OK;
@@ -4042,12 +3911,6 @@ gmrf_status gmrf_assemble_create(int32_t device, void* stream, int64_t n, const 
 gmrf_status gmrf_assemble_destroy(gmrf_assembler* as) {
     if (!as) return GMRF_OK;
     as->close();
-    if (as->has_device()) {
-        free_dev(as->d_pptr); free_dev(as->d_qmap); free_dev(as->d_pa); free_dev(as->d_pb);
-        free_dev(as->d_jt_ptr); free_dev(as->d_jt_row); free_dev(as->d_jt_src); free_dev(as->d_j_rptr); free_dev(as->d_j_col);
-        free_dev(as->d_q_ptr); free_dev(as->d_q_row); free_dev(as->d_o_ptr); free_dev(as->d_o_row);
-        as->arena.release(); as->bpart.release();
-    }
     delete as;
     return GMRF_OK;
 }
@@ -4091,9 +3954,9 @@ struct gmrf_darcy_p1 : DevCtx {         // device -1: pattern only
     int64_t nx = 0, ny = 0, n = 0, nnz = 0;
     int order = 1;                      // 1: P1 triangles on the nx x ny nodes; 2: quadratic triangles, dofs = the (2 nx - 1) x (2 ny - 1) lattice
     std::vector<int64_t> rowptr, colidx;            // 0-based
-    int64_t* d_rowptr = nullptr;
-    int32_t* d_colidx = nullptr;        // order 2: the pattern's columns and the Dirichlet mask for darcy_p2_constrain_batch
-    uint8_t* d_pres = nullptr;
+    DevArr<int64_t> d_rowptr;
+    DevArr<int32_t> d_colidx;           // order 2: the pattern's columns and the Dirichlet mask for darcy_p2_constrain_batch
+    DevArr<uint8_t> d_pres;
     DevBuf arena;                       // host arguments of the current call (Staging)
     DevBuf bwork;                       // work of an assembly: [batch][n] |diagonal|, [batch] means
 };
@@ -4166,8 +4029,7 @@ static gmrf_status darcy_create(int32_t device, void* stream, int64_t nx, int64_
     d->nnz = (int64_t)d->colidx.size();
     GCHK(d->open(device, stream, hipStreamNonBlocking, "gmrf_darcy_p1_create"));
     if (d->device >= 0) {
-        HIPCHK(hipMalloc(&d->d_rowptr, sizeof(int64_t) * (d->n + 1)));
-        HIPCHK(hipMemcpyAsync(d->d_rowptr, d->rowptr.data(), sizeof(int64_t) * (d->n + 1), hipMemcpyHostToDevice, d->stream));
+        GCHK(d->d_rowptr.upload(d->stream, d->rowptr.data(), (size_t)(d->n + 1)));
         std::vector<int32_t> col32;
         std::vector<uint8_t> pres;
         if (order == 2) {
@@ -4175,10 +4037,8 @@ static gmrf_status darcy_create(int32_t device, void* stream, int64_t nx, int64_
             col32.assign(d->colidx.begin(), d->colidx.end());
             pres.resize((size_t)d->n);
             for (int64_t r = 0; r < d->n; ++r) { const int64_t I = r % W, J = r / W; pres[(size_t)r] = (I == 0 || J == 0 || I == W - 1 || J == H - 1) ? 1 : 0; }
-            HIPCHK(hipMalloc(&d->d_colidx, sizeof(int32_t) * d->nnz));
-            HIPCHK(hipMalloc(&d->d_pres, (size_t)d->n));
-            HIPCHK(hipMemcpyAsync(d->d_colidx, col32.data(), sizeof(int32_t) * d->nnz, hipMemcpyHostToDevice, d->stream));
-            HIPCHK(hipMemcpyAsync(d->d_pres, pres.data(), (size_t)d->n, hipMemcpyHostToDevice, d->stream));
+            GCHK(d->d_colidx.upload(d->stream, col32));
+            GCHK(d->d_pres.upload(d->stream, pres));
         }
         HIPCHK(hipStreamSynchronize(d->stream));
     }
@@ -4197,10 +4057,6 @@ gmrf_status gmrf_darcy_p2_create(int32_t device, void* stream, int64_t nx, int64
 gmrf_status gmrf_darcy_p1_destroy(gmrf_darcy_p1* d) {
     if (!d) return GMRF_OK;
     d->close();
-    if (d->has_device()) {
-        free_dev(d->d_rowptr); free_dev(d->d_colidx); free_dev(d->d_pres);
-        d->arena.release(); d->bwork.release();
-    }
     delete d;
     return GMRF_OK;
 }
@@ -4231,11 +4087,11 @@ struct gmrf_burgers_p1 : DevCtx {       // device -1: pattern only
     int scheme = GMRF_BURGERS_EULER, bc = GMRF_BURGERS_PERIODIC;
     double dt = 0.0, nu = 0.0, h = 0.0; // h: cell length
     std::vector<int64_t> rowptr;        // 0-based row pointer of J
-    int64_t* d_rowptr = nullptr;        // dirichlet only: the periodic rows have a closed form
+    DevArr<int64_t> d_rowptr;           // dirichlet only: the periodic rows have a closed form
     int64_t npts = 0;                   // GMRF_BURGERS_COLLOCATION (gmrf_burgers_colloc_create): the points of a slice, their
     std::vector<int32_t> cell;          // cells, and the device table of burgers_colloc.hpp: cells, then a and d as [3][npts]
-    int32_t* d_cell = nullptr;
-    double* d_shape = nullptr;          // a at 0, d at 3 npts
+    DevArr<int32_t> d_cell;
+    DevArr<double> d_shape;             // a at 0, d at 3 npts
     DevBuf arena;                       // host arguments of the current call (Staging)
 };
 
@@ -4274,8 +4130,7 @@ gmrf_status gmrf_burgers_line_create(int32_t device, void* stream, int64_t nc, i
     b->nnz = b->rowptr[(size_t)b->rows];
     GCHK(b->open(device, stream, hipStreamNonBlocking, "gmrf_burgers_line_create"));
     if (b->device >= 0 && dirichlet) {
-        HIPCHK(hipMalloc(&b->d_rowptr, sizeof(int64_t) * (b->rows + 1)));
-        HIPCHK(hipMemcpyAsync(b->d_rowptr, b->rowptr.data(), sizeof(int64_t) * (b->rows + 1), hipMemcpyHostToDevice, b->stream));
+        GCHK(b->d_rowptr.upload(b->stream, b->rowptr.data(), (size_t)(b->rows + 1)));
         HIPCHK(hipStreamSynchronize(b->stream));
     }
     *out = guard.release();
@@ -4323,10 +4178,8 @@ gmrf_status gmrf_burgers_colloc_create(int32_t device, void* stream, int64_t nc,
     for (int64_t r = 0; r <= b->rows; ++r) b->rowptr[(size_t)r] = 6 * r;
     GCHK(b->open(device, stream, hipStreamNonBlocking, "gmrf_burgers_colloc_create"));
     if (b->device >= 0) {
-        HIPCHK(hipMalloc(&b->d_cell, sizeof(int32_t) * npts));
-        HIPCHK(hipMalloc(&b->d_shape, sizeof(double) * 6 * npts));
-        HIPCHK(hipMemcpyAsync(b->d_cell, b->cell.data(), sizeof(int32_t) * npts, hipMemcpyHostToDevice, b->stream));
-        HIPCHK(hipMemcpyAsync(b->d_shape, shape.data(), sizeof(double) * 6 * npts, hipMemcpyHostToDevice, b->stream));
+        GCHK(b->d_cell.upload(b->stream, b->cell.data(), (size_t)npts));
+        GCHK(b->d_shape.upload(b->stream, shape.data(), 6 * (size_t)npts));
         HIPCHK(hipStreamSynchronize(b->stream));
     }
     *out = guard.release();
@@ -4336,7 +4189,6 @@ gmrf_status gmrf_burgers_colloc_create(int32_t device, void* stream, int64_t nc,
 gmrf_status gmrf_burgers_p1_destroy(gmrf_burgers_p1* b) {
     if (!b) return GMRF_OK;
     b->close();
-    if (b->has_device()) { free_dev(b->d_rowptr); free_dev(b->d_cell); free_dev(b->d_shape); b->arena.release(); }
     delete b;
     return GMRF_OK;
 }
@@ -4501,7 +4353,6 @@ gmrf_status gmrf_burgers_line_prior_create(int32_t device, void* stream, int64_t
 gmrf_status gmrf_burgers_prior_destroy(gmrf_burgers_prior* p) {
     if (!p) return GMRF_OK;
     p->close();
-    if (p->has_device()) { p->arena.release(); p->bulk.release(); }
     delete p;
     return GMRF_OK;
 }
@@ -4584,7 +4435,7 @@ struct gmrf_elliptic_p1 : DevCtx {      // device -1: pattern and quadrature poi
     int64_t nx = 0, ny = 0, n = 0, nnz = 0, cells = 0;
     int order = 1, nq = 3;              // element order and quadrature points per cell (order 2: the lattice of gmrf_darcy_p2_create, 4)
     std::vector<int64_t> rowptr, colidx;            // 0-based: the pattern of gmrf_darcy_p1_create / _p2_create(nx, ny)
-    int64_t* d_rowptr = nullptr;
+    DevArr<int64_t> d_rowptr;
     DevBuf arena;                       // host arguments of the current call (Staging)
 };
 
@@ -4598,8 +4449,7 @@ static gmrf_status elliptic_create(int32_t device, void* stream, int64_t nx, int
     e->nnz = (int64_t)e->colidx.size();
     GCHK(e->open(device, stream, hipStreamNonBlocking, "gmrf_elliptic_p1_create"));
     if (e->device >= 0) {
-        HIPCHK(hipMalloc(&e->d_rowptr, sizeof(int64_t) * (e->n + 1)));
-        HIPCHK(hipMemcpyAsync(e->d_rowptr, e->rowptr.data(), sizeof(int64_t) * (e->n + 1), hipMemcpyHostToDevice, e->stream));
+        GCHK(e->d_rowptr.upload(e->stream, e->rowptr.data(), (size_t)(e->n + 1)));
         HIPCHK(hipStreamSynchronize(e->stream));
     }
     *out = guard.release();
@@ -4617,7 +4467,6 @@ gmrf_status gmrf_elliptic_p2_create(int32_t device, void* stream, int64_t nx, in
 gmrf_status gmrf_elliptic_p1_destroy(gmrf_elliptic_p1* e) {
     if (!e) return GMRF_OK;
     e->close();
-    if (e->has_device()) { free_dev(e->d_rowptr); e->arena.release(); }
     delete e;
     return GMRF_OK;
 }
@@ -4818,13 +4667,11 @@ static int64_t objective_chunks(const gmrf_assembler* as) {
 }
 
 static gmrf_status objective_ready(gmrf_assembler* as) {
-    if (as->d_q_ptr) return GMRF_OK;
+    if (as->d_q_ptr && as->d_q_row) return GMRF_OK;
     if (as->q_ptr.empty()) return bad_shape("the objective needs n < 2^31");
-    HIPCHK(hipMalloc(&as->d_q_ptr, sizeof(int64_t) * as->q_ptr.size()));
-    HIPCHK(hipMalloc(&as->d_q_row, sizeof(int32_t) * std::max<size_t>(as->q_row.size(), 1)));
-    HIPCHK(hipMemcpyAsync(as->d_q_ptr, as->q_ptr.data(), sizeof(int64_t) * as->q_ptr.size(), hipMemcpyHostToDevice, as->stream));
-    if (!as->q_row.empty())
-        HIPCHK(hipMemcpyAsync(as->d_q_row, as->q_row.data(), sizeof(int32_t) * as->q_row.size(), hipMemcpyHostToDevice, as->stream));
+    GCHK(reserve_group(as->stream, {as->d_q_ptr.want(as->q_ptr.size()), as->d_q_row.want(as->q_row.size())}));
+    GCHK(as->d_q_ptr.upload(as->stream, as->q_ptr));
+    GCHK(as->d_q_row.upload(as->stream, as->q_row));
     HIPCHK(hipStreamSynchronize(as->stream));
     return GMRF_OK;
 }
@@ -4922,13 +4769,12 @@ gmrf_status gmrf_assemble_objective_batch(gmrf_assembler* as, int64_t batch, con
 static int64_t std_norm_chunks(int64_t n) { return std::min<int64_t>(1024, std::max<int64_t>(1, (n + 2047) / 2048)); }
 
 static gmrf_status quadform_ready(gmrf_assembler* as) {
-    if (as->d_o_ptr) return GMRF_OK;
+    if (as->d_o_ptr && as->d_o_row) return GMRF_OK;
     if (as->n >= ((int64_t)1 << 31)) return bad_shape("the quadratic form needs n < 2^31");
     const std::vector<int32_t> row(as->rowval.begin(), as->rowval.end());
-    HIPCHK(hipMalloc(&as->d_o_ptr, sizeof(int64_t) * as->colptr.size()));
-    HIPCHK(hipMalloc(&as->d_o_row, sizeof(int32_t) * std::max<size_t>(row.size(), 1)));
-    HIPCHK(hipMemcpyAsync(as->d_o_ptr, as->colptr.data(), sizeof(int64_t) * as->colptr.size(), hipMemcpyHostToDevice, as->stream));
-    if (!row.empty()) HIPCHK(hipMemcpyAsync(as->d_o_row, row.data(), sizeof(int32_t) * row.size(), hipMemcpyHostToDevice, as->stream));
+    GCHK(reserve_group(as->stream, {as->d_o_ptr.want(as->colptr.size()), as->d_o_row.want(row.size())}));
+    GCHK(as->d_o_ptr.upload(as->stream, as->colptr));
+    GCHK(as->d_o_row.upload(as->stream, row));
     HIPCHK(hipStreamSynchronize(as->stream));        // (`row` goes with this scope)
     return GMRF_OK;
 }
@@ -4982,7 +4828,6 @@ struct DriverBase {
     void close() {
         (void)hipSetDevice(device);
         (void)hipStreamSynchronize(stream);
-        in.release(); work.release();
         if (Qp) (void)gmrf_csr_destroy(Qp);
         Qp = nullptr;
     }
@@ -5071,7 +4916,7 @@ struct gmrf_gn : DriverBase {
     double *d_a = nullptr, *d_rhs = nullptr, *d_q = nullptr, *d_part = nullptr, *d_obj = nullptr;
     double *d_last = nullptr, *d_cur = nullptr, *d_hist = nullptr;
     int32_t *d_steps = nullptr, *d_active = nullptr, *d_take = nullptr;
-    unsigned* h_active = nullptr;        // mapped host word the stop rule writes
+    HostWord h_active;                   // mapped host word the stop rule writes
     unsigned* dev_active = nullptr;      // ... as the device addresses it
     int64_t q_stride = 0;
     double noise = 0.0;
@@ -5107,18 +4952,16 @@ static gmrf_status gn_bound_ok(const gmrf_gn* g) {
 static gmrf_status gn_create(gmrf_handle* h, gmrf_assembler* as, gmrf_burgers_p1* b, gmrf_elliptic_p1* el, gmrf_gn** out) {
     if (!h || !as || (!b && !el) || !out) return bad_shape("null pointer");
     if (as->device < 0 || (b ? b->device : el->device) < 0) return bad_shape("the Gauss-Newton driver needs an assembler and a tangent with a device");
-    gmrf_gn tmp; tmp.bind(h, as); tmp.b = b; tmp.e = el;
-    GCHK(gn_bound_ok(&tmp));
+    auto g = std::make_unique<gmrf_gn>();
+    g->bind(h, as); g->b = b; g->e = el;
+    GCHK(gn_bound_ok(g.get()));
     HIPCHK(hipSetDevice(h->device));
-    auto* g = new gmrf_gn(tmp);
-    hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&g->h_active), 64, hipHostMallocMapped);
-    if (e != hipSuccess) { delete g; g_last_error = std::string("gmrf_gn_create: ") + hipGetErrorString(e); return GMRF_ERR_HIP; }
-    *g->h_active = 0u;
     void* dev_word = nullptr;
-    e = hipHostGetDevicePointer(&dev_word, g->h_active, 0);
-    if (e != hipSuccess) { (void)hipHostFree(g->h_active); delete g; g_last_error = std::string("gmrf_gn_create: ") + hipGetErrorString(e); return GMRF_ERR_HIP; }
+    hipError_t e = g->h_active.open();
+    if (e == hipSuccess) e = hipHostGetDevicePointer(&dev_word, g->h_active, 0);
+    if (e != hipSuccess) { g_last_error = std::string("gmrf_gn_create: ") + hipGetErrorString(e); return GMRF_ERR_HIP; }
     g->dev_active = static_cast<unsigned*>(dev_word);
-    *out = g;
+    *out = g.release();
     return GMRF_OK;
 }
 
@@ -5132,8 +4975,6 @@ gmrf_status gmrf_gn_create_elliptic(gmrf_handle* h, gmrf_assembler* as, gmrf_ell
 gmrf_status gmrf_gn_destroy(gmrf_gn* g) {
     if (!g) return GMRF_OK;
     g->close();
-    g->post.release();
-    if (g->h_active) (void)hipHostFree(g->h_active);
     delete g;
     return GMRF_OK;
 }
@@ -5256,7 +5097,7 @@ gmrf_status gmrf_gn_run(gmrf_gn* g, const double* q_nzval, int64_t q_stride, con
         return GMRF_OK;
     };
     for (int32_t it = 0; it < max_steps && status == GMRF_OK; ++it) {
-        if (*reinterpret_cast<volatile unsigned*>(g->h_active) == 0u) break;
+        if (*static_cast<volatile unsigned*>(g->h_active.p) == 0u) break;
         status = iteration();
         if (status == GMRF_OK) g->iterations += 1;
     }
@@ -5316,9 +5157,10 @@ gmrf_status gmrf_dc_create(gmrf_handle* h, gmrf_assembler* as, gmrf_darcy_p1* d,
         return GMRF_ERR_NO_DEVICE;
     }
     if (!h) return bad_shape("null handle");
-    gmrf_dc tmp; tmp.bind(h, as); tmp.d = d;
-    GCHK(dc_bound_ok(&tmp));
-    *out = new gmrf_dc(tmp);
+    auto g = std::make_unique<gmrf_dc>();
+    g->bind(h, as); g->d = d;
+    GCHK(dc_bound_ok(g.get()));
+    *out = g.release();
     return GMRF_OK;
 }
 
@@ -5434,8 +5276,9 @@ gmrf_status gmrf_bic_create(gmrf_handle* h, gmrf_assembler* as, gmrf_burgers_pri
         return GMRF_ERR_NO_DEVICE;
     }
     if (!h) return bad_shape("null handle");
-    gmrf_bic tmp; tmp.bind(h, as); tmp.pr = prior;
-    GCHK(bic_bound_ok(&tmp));
+    auto g = std::make_unique<gmrf_bic>();
+    g->bind(h, as); g->pr = prior;
+    GCHK(bic_bound_ok(g.get()));
     // the same sizes are not yet the same pattern: entry by entry against the prior's statement of it
     if (as->q_ptr.empty()) return bad_shape("the Burgers initial-condition driver needs n < 2^31");
     for (int64_t j = 0; j <= as->n; ++j) {
@@ -5447,7 +5290,7 @@ gmrf_status gmrf_bic_create(gmrf_handle* h, gmrf_assembler* as, gmrf_burgers_pri
         prior_entry(prior, e, &row, &col);
         if (as->q_row[(size_t)e] != row) return bad_shape("the assembler's Q is not the Burgers prior's pattern");
     }
-    *out = new gmrf_bic(tmp);
+    *out = g.release();
     return GMRF_OK;
 }
 
@@ -5643,20 +5486,15 @@ gmrf_status gmrf_gn_posterior(gmrf_gn* g, const double* z, int64_t first, int64_
 struct gmrf_swe_p1 : DevCtx {           // device -1: patterns / quadrature points only
     int64_t nx = 0, ny = 0, nn = 0, n = 0, cells = 0, nnz_k = 0, nnz_s = 0;
     std::vector<int64_t> rowptr_k, col_k, rowptr_s, col_s;     // 0-based
-    int64_t *d_rowptr_k = nullptr, *d_rowptr_s = nullptr;
-    int32_t *d_col_k = nullptr, *d_col_s = nullptr;
-    double *d_dk = nullptr, *d_ds = nullptr, *d_mean = nullptr;   // |diagonals|, three meandiag scalars
+    DevArr<int64_t> d_rowptr_k, d_rowptr_s;
+    DevArr<int32_t> d_col_k, d_col_s;
+    DevArr<double> d_dk, d_ds, d_mean;                            // |diagonals|, three meandiag scalars
     DevBuf arena;                       // host arguments of the current call (Staging)
 };
 
 gmrf_status gmrf_shallow_water_p1_destroy(gmrf_swe_p1* w) {
     if (!w) return GMRF_OK;
     w->close();
-    if (w->has_device()) {
-        free_dev(w->d_rowptr_k); free_dev(w->d_rowptr_s); free_dev(w->d_col_k); free_dev(w->d_col_s);
-        free_dev(w->d_dk); free_dev(w->d_ds); free_dev(w->d_mean);
-        w->arena.release();
-    }
     delete w;
     return GMRF_OK;
 }
@@ -5688,17 +5526,11 @@ gmrf_status gmrf_shallow_water_p1_create(int32_t device, void* stream, int64_t n
     GCHK(w->open(device, stream, hipStreamNonBlocking, "gmrf_shallow_water_p1_create"));
     if (w->device >= 0) {
         std::vector<int32_t> ck(w->col_k.begin(), w->col_k.end()), cs(w->col_s.begin(), w->col_s.end());
-        HIPCHK(hipMalloc(&w->d_rowptr_k, sizeof(int64_t) * (w->n + 1)));
-        HIPCHK(hipMalloc(&w->d_rowptr_s, sizeof(int64_t) * (w->n + 1)));
-        HIPCHK(hipMalloc(&w->d_col_k, sizeof(int32_t) * w->nnz_k));
-        HIPCHK(hipMalloc(&w->d_col_s, sizeof(int32_t) * w->nnz_s));
-        HIPCHK(hipMalloc(&w->d_dk, sizeof(double) * w->n));
-        HIPCHK(hipMalloc(&w->d_ds, sizeof(double) * w->n));
-        HIPCHK(hipMalloc(&w->d_mean, sizeof(double) * 4));
-        HIPCHK(hipMemcpyAsync(w->d_rowptr_k, w->rowptr_k.data(), sizeof(int64_t) * (w->n + 1), hipMemcpyHostToDevice, w->stream));
-        HIPCHK(hipMemcpyAsync(w->d_rowptr_s, w->rowptr_s.data(), sizeof(int64_t) * (w->n + 1), hipMemcpyHostToDevice, w->stream));
-        HIPCHK(hipMemcpyAsync(w->d_col_k, ck.data(), sizeof(int32_t) * w->nnz_k, hipMemcpyHostToDevice, w->stream));
-        HIPCHK(hipMemcpyAsync(w->d_col_s, cs.data(), sizeof(int32_t) * w->nnz_s, hipMemcpyHostToDevice, w->stream));
+        GCHK(reserve_group(w->stream, {w->d_dk.want((size_t)w->n), w->d_ds.want((size_t)w->n), w->d_mean.want(4)}));
+        GCHK(w->d_rowptr_k.upload(w->stream, w->rowptr_k));
+        GCHK(w->d_rowptr_s.upload(w->stream, w->rowptr_s));
+        GCHK(w->d_col_k.upload(w->stream, ck));
+        GCHK(w->d_col_s.upload(w->stream, cs));
         HIPCHK(hipStreamSynchronize(w->stream));
     }
     *out = guard.release();
@@ -5809,14 +5641,7 @@ static gmrf_status need_single(gmrf_handle* h) {
 static double* tk_t1(const gmrf_handle* h) { return h->d_V; }
 static double* tk_m(const gmrf_handle* h) { return h->d_V + blk_elems(h) * h->B; }
 static gmrf_status tk_alloc(gmrf_handle* h) {
-    const int64_t bstride = blk_elems(h);
-    if (!h->d_V || h->v_elems < 2 * bstride * h->B) {
-        HIPCHK(hipStreamSynchronize(h->stream));
-        free_dev(h->d_V); h->d_V = nullptr; h->v_elems = 0;
-        HIPCHK(hipMalloc(&h->d_V, sizeof(double) * 2 * (size_t)bstride * (size_t)h->B));
-        h->v_elems = 2 * bstride * h->B;
-    }
-    return GMRF_OK;
+    return h->d_V.reserve(h->stream, 2 * (size_t)blk_elems(h) * (size_t)h->B);
 }
 // Block i < N - 1, Sg = the leading block of Sigma_{i+1,i+1} (full, mirrored):  T1 = S' C_w,  M = T1^T C_w,  Y[cmin:] = (I + M) X[cmin:]
 static gmrf_status tk_coupled_y(gmrf_handle* h, int64_t i, const double* Sg) {
@@ -5962,11 +5787,9 @@ static gmrf_status selinv_plan(gmrf_handle* h, const gmrf_csr* S, const char* wh
     for (int64_t i = 0; i < N; ++i) off[(size_t)i + 1] += off[(size_t)i];
     const int64_t cnt = (int64_t)src.size();
     HIPCHK(hipStreamSynchronize(h->stream));
-    if (!h->d_sel_src || h->sel_cap < cnt) {
-        free_dev(h->d_sel_src); free_dev(h->d_sel_slot); h->d_sel_src = nullptr; h->d_sel_slot = nullptr; h->sel_cap = 0;
-        HIPCHK(hipMalloc(&h->d_sel_src, sizeof(int64_t) * (size_t)std::max<int64_t>(cnt, 1)));
-        HIPCHK(hipMalloc(&h->d_sel_slot, sizeof(int64_t) * 2 * (size_t)std::max<int64_t>(cnt, 1)));
-        h->sel_cap = std::max<int64_t>(cnt, 1);
+    if (!h->d_sel_src || !h->d_sel_slot || h->sel_cap < cnt) {
+        h->sel_cap = std::max<int64_t>(cnt, 1);           // (the stride between the two halves of d_sel_slot)
+        GCHK(reserve_group(h->stream, {h->d_sel_src.want((size_t)h->sel_cap), h->d_sel_slot.want(2 * (size_t)h->sel_cap)}));
     }
     if (cnt > 0) {
         HIPCHK(hipMemcpyAsync(h->d_sel_src, src.data(), sizeof(int64_t) * cnt, hipMemcpyHostToDevice, h->stream));
@@ -6034,13 +5857,7 @@ static gmrf_status selinv_ready(gmrf_handle* h, const gmrf_csr* S, const char* w
 }
 
 static gmrf_status ensure_sig(gmrf_handle* h) {
-    const int64_t need = std::max<int64_t>(h->sel_nnz, 1) * h->B;
-    if (h->d_sig && h->sig_elems >= need) return GMRF_OK;
-    HIPCHK(hipStreamSynchronize(h->stream));
-    free_dev(h->d_sig); h->d_sig = nullptr; h->sig_elems = 0;
-    HIPCHK(hipMalloc(&h->d_sig, sizeof(double) * (size_t)need));
-    h->sig_elems = need;
-    return GMRF_OK;
+    return h->d_sig.reserve(h->stream, (size_t)(std::max<int64_t>(h->sel_nnz, 1) * h->B));
 }
 
 gmrf_status gmrf_bt_selinv(gmrf_handle* h, const gmrf_csr* S, double* vals_out) {
@@ -6065,12 +5882,7 @@ gmrf_status gmrf_bt_trace_inv(gmrf_handle* h, const gmrf_csr* S, const double* d
     const int64_t nch = std::min<int64_t>(256, std::max<int64_t>(1, (nnz + 8191) / 8192)), len = (nnz + nch - 1) / nch;
     const bool dv_dev = is_device_ptr(dvals), out_dev = is_device_ptr(out);
     const int64_t need = (dv_dev ? 0 : dv_count) + h->B * m * nch + (out_dev ? 0 : h->B * m);
-    if (need > 0 && (!h->d_dv || h->dv_elems < need)) {
-        HIPCHK(hipStreamSynchronize(h->stream));
-        free_dev(h->d_dv); h->d_dv = nullptr; h->dv_elems = 0;
-        HIPCHK(hipMalloc(&h->d_dv, sizeof(double) * (size_t)need));
-        h->dv_elems = need;
-    }
+    if (need > 0) GCHK(h->d_dv.reserve(h->stream, (size_t)need));
     const double* d_dv = dvals;
     if (!dv_dev) {
         HIPCHK(hipMemcpyAsync(h->d_dv, dvals, sizeof(double) * dv_count, hipMemcpyHostToDevice, h->stream));
@@ -6181,11 +5993,7 @@ static gmrf_status var_accumulate_dev(gmrf_handle* h, int method, int64_t first_
 
 // h->d_acc: room for the variances of B problems
 static gmrf_status ensure_acc(gmrf_handle* h, int64_t B) {
-    if (h->d_acc && h->acc_B >= B) return GMRF_OK;
-    free_dev(h->d_acc); h->d_acc = nullptr;
-    HIPCHK(hipMalloc(&h->d_acc, sizeof(double) * h->n * B));
-    h->acc_B = B;
-    return GMRF_OK;
+    return h->d_acc.reserve(h->stream, (size_t)(h->n * B));
 }
 
 gmrf_status gmrf_bt_var_accumulate(gmrf_handle* h, int32_t method, int64_t first_id, int64_t k, uint64_t seed,
@@ -6268,18 +6076,14 @@ gmrf_status gmrf_bt_marginal_var_batch(gmrf_handle* h, int32_t method, int64_t k
     const int64_t n = h->n, B = h->B;
     GCHK(ensure_acc(h, B));
     GCHK(sweep_guarded(h, {}, [&]() -> gmrf_status {     // (a batch of one: its sweeps may be persistent launches)
-        std::unique_ptr<double, void (*)(void*)> d_qv(nullptr, free_dev), d_diag(nullptr, free_dev);     // (freed on every way out)
+        DevArr<double> d_qv, d_diag;                     // (freed on every way out)
         const double* qv = q_vals;
         if (method == GMRF_VAR_RBMC) {
-            double* buf = nullptr;
             if (!is_device_ptr(q_vals)) {
-                HIPCHK(hipMalloc(&buf, sizeof(double) * Q->nnz * B));
-                d_qv.reset(buf);
-                HIPCHK(hipMemcpyAsync(d_qv.get(), q_vals, sizeof(double) * Q->nnz * B, hipMemcpyHostToDevice, h->stream));
-                qv = d_qv.get();
+                GCHK(d_qv.upload(h->stream, q_vals, (size_t)(Q->nnz * B)));
+                qv = d_qv;
             }
-            HIPCHK(hipMalloc(&buf, sizeof(double) * n * B));
-            d_diag.reset(buf);
+            GCHK(d_diag.reserve(h->stream, (size_t)(n * B)));
         }
         GCHK(var_batch_enqueue(h, method, k, seed, Q, qv, d_diag.get(), h->d_acc));
         const hipMemcpyKind kind = is_device_ptr(var_out) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
@@ -6313,10 +6117,8 @@ static void tw_drop_own_factor(gmrf_handle* h) {
     h->xsplit = 0;
     h->l_valid = h->logdet_valid = false;
     if (h->external_storage) return;
-    free_dev(h->d_L); free_dev(h->d_C); free_dev(h->d_Linv);
-    free_dev(h->d_S); free_dev(h->d_B); free_dev(h->d_T); free_dev(h->d_W); free_dev(h->d_logdet); free_dev(h->d_V);
-    h->d_L = h->d_C = h->d_Linv = h->d_S = h->d_B = h->d_T = h->d_W = h->d_logdet = h->d_V = nullptr;
-    h->v_elems = 0;
+    release_factor(h);
+    h->d_V.release();
     h->alloc_N = h->alloc_bsp = h->alloc_B = 0;
     h->stats.factor_bytes = 0;
 }
@@ -6328,9 +6130,6 @@ static void tw_free(gmrf_handle* h) {
     (void)hipStreamSynchronize(h->stream);
     if (t->top) (void)gmrf_bt_destroy(t->top);
     if (t->bot) (void)gmrf_bt_destroy(t->bot);
-    free_dev(t->d_mkeys); free_dev(t->d_msrc); free_dev(t->d_mvals);
-    free_dev(t->d_Bm); free_dev(t->d_HJ); free_dev(t->d_W); free_dev(t->d_Smm);
-    free_dev(t->d_nz); free_dev(t->d_z); free_dev(t->d_var);
     if (t->ev_fork) (void)hipEventDestroy(t->ev_fork);
     if (t->ev_join) (void)hipEventDestroy(t->ev_join);
     delete t;
@@ -6432,32 +6231,17 @@ static gmrf_status tw_analyze(gmrf_handle* h, int64_t n, int64_t N, const int64_
             keys.push_back((gam << 32) | (uint64_t)(bs - 1 - rho));
             src.push_back(e.src);
         }
-        free_dev(t->d_mkeys); free_dev(t->d_msrc); free_dev(t->d_mvals);
-        t->d_mkeys = nullptr; t->d_msrc = nullptr; t->d_mvals = nullptr;
         t->m_count = (int64_t)keys.size();
-        const size_t ne = std::max<size_t>(keys.size(), 1);
-        HIPCHK(hipMalloc(&t->d_mkeys, ne * sizeof(uint64_t)));
-        HIPCHK(hipMalloc(&t->d_msrc, ne * sizeof(int64_t)));
-        HIPCHK(hipMalloc(&t->d_mvals, ne * sizeof(double)));
+        GCHK(reserve_group(h->stream, {t->d_mkeys.want(keys.size()), t->d_msrc.want(keys.size()), t->d_mvals.want(keys.size())}));
         if (!keys.empty()) {
-            HIPCHK(hipMemcpyAsync(t->d_mkeys, keys.data(), keys.size() * sizeof(uint64_t), hipMemcpyHostToDevice, h->stream));
-            HIPCHK(hipMemcpyAsync(t->d_msrc, src.data(), src.size() * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+            GCHK(t->d_mkeys.upload(h->stream, keys));
+            GCHK(t->d_msrc.upload(h->stream, src));
             HIPCHK(hipStreamSynchronize(h->stream));
         }
     }
-    if (t->dense_bsp != t->bsp) {
-        free_dev(t->d_Bm); free_dev(t->d_HJ); free_dev(t->d_W); free_dev(t->d_Smm);
-        t->d_Bm = t->d_HJ = t->d_W = t->d_Smm = nullptr; t->dense_bsp = 0;
-        const size_t bytes = sizeof(double) * (size_t)(t->bsp * t->bsp);
-        HIPCHK(hipMalloc(&t->d_Bm, bytes)); HIPCHK(hipMalloc(&t->d_HJ, bytes));
-        HIPCHK(hipMalloc(&t->d_W, bytes)); HIPCHK(hipMalloc(&t->d_Smm, bytes));
-        t->dense_bsp = t->bsp;
-    }
-    free_dev(t->d_var); t->d_var = nullptr;
-    HIPCHK(hipMalloc(&t->d_var, sizeof(double) * (size_t)(Nb * bs)));
-    free_dev(t->d_z); t->d_z = nullptr;
-    free_dev(t->d_nz); t->d_nz = nullptr;
-    return GMRF_OK;
+    const size_t be = (size_t)(t->bsp * t->bsp);
+    GCHK(reserve_group(h->stream, {t->d_Bm.want(be), t->d_HJ.want(be), t->d_W.want(be), t->d_Smm.want(be)}));
+    return t->d_var.reserve(h->stream, (size_t)(Nb * bs));        // (d_z and d_nz follow n / nnz at their first use)
 }
 
 // HJ = B-hat L'^-T of the bottom half's last block (= J C'), on the bottom half's stream
@@ -6496,8 +6280,7 @@ static gmrf_status tw_numeric(gmrf_handle* h, const double* nzval, int32_t* info
     const int64_t m = t->m, Nb = bot->N, N = t->N;
     const double* d_nz = nzval;
     if (!is_device_ptr(nzval)) {
-        if (!t->d_nz) HIPCHK(hipMalloc(&t->d_nz, sizeof(double) * (size_t)std::max<int64_t>(t->nnz, 1)));
-        HIPCHK(hipMemcpyAsync(t->d_nz, nzval, sizeof(double) * t->nnz, hipMemcpyHostToDevice, h->stream));
+        GCHK(t->d_nz.upload(h->stream, nzval, (size_t)t->nnz));
         d_nz = t->d_nz;
     }
     t->d_nz_cur = d_nz;
@@ -6719,7 +6502,7 @@ static gmrf_status tw_var_exact(gmrf_handle* h, double* d_out) {
 static gmrf_status tw_var_accumulate_dev(gmrf_handle* h, int method, int64_t first_id, int64_t k, uint64_t seed, const gmrf_csr* Q,
                                          double* d_acc) {
     TwistState* t = h->tw;
-    if (!t->d_z) HIPCHK(hipMalloc(&t->d_z, sizeof(double) * (size_t)(64 * t->n)));
+    GCHK(t->d_z.reserve(h->stream, (size_t)(64 * t->n)));
     for (int64_t c0 = 0; c0 < k; c0 += 64) {
         const int kc = (int)std::min<int64_t>(64, k - c0);
         GCHK(tw_sample_chunk(h, seed, first_id + c0, kc, nullptr, 0));
@@ -6880,7 +6663,7 @@ gmrf_status gmrf_test_gemm_pair(int32_t device, int32_t batch, int32_t grouped, 
     double *dA[2] = {nullptr, nullptr}, *dB[2] = {nullptr, nullptr}, *dC[2] = {nullptr, nullptr};
     GemmArgs g[2];
     bool b_n[2];
-    auto drop = [&]() { for (int i = 0; i < 2; ++i) { free_dev(dA[i]); free_dev(dB[i]); free_dev(dC[i]); } };
+    auto drop = [&]() { for (int i = 0; i < 2; ++i) { (void)hipFree(dA[i]); (void)hipFree(dB[i]); (void)hipFree(dC[i]); } };
     for (int i = 0; i < 2; ++i) {
         const int64_t M = desc[6 * i], N = desc[6 * i + 1], K = desc[6 * i + 2];
         b_n[i] = desc[6 * i + 3] != 0;
@@ -6990,7 +6773,7 @@ static gmrf_status gemm_desc_run(int32_t device, int32_t route, const int64_t* d
     HIPCHK(gemm_dma_init());
 
     std::vector<void*> owned;
-    auto drop = [&]() { for (void* p : owned) free_dev(p); owned.clear(); };
+    auto drop = [&]() { for (void* p : owned) (void)hipFree(p); owned.clear(); };
     hipError_t e = hipSuccess;
     auto up = [&](const void* host, int64_t count, size_t elem) -> void* {
         if (!host || e != hipSuccess) return nullptr;

@@ -1,7 +1,63 @@
-// Host-side plumbing shared by the handles of gmrf_hip.hip: a grow-only device buffer and its carving into pieces, a device
-// context (device + stream) and the staging of host-resident arguments.  Included by gmrf_hip.hip after g_last_error, HIPCHK / GCHK,
-// bad_shape and is_device_ptr; no kernels here.  Also env_int, the one reader of the integer GMRF_* environment switches.
+// Host-side plumbing shared by every handle of gmrf_hip.hip: the error state and its macros, device memory as objects that know
+// their size and free themselves (DevBuf, DevArr<T>, reserve_group, HostWord), the carving of one allocation into pieces, a device
+// context (device + stream) and the staging of host-resident arguments.  Self-contained; no kernels here.  Also env_int, the one
+// reader of the integer GMRF_* environment switches.
+//
+// Ownership: a handle's device memory is a member of one of these types, so `delete` of the handle is the only free list.  A buffer
+// is either OWNED (reserve: grow-only; freed on growth, release() and destruction) or BORROWED (borrow: the caller's memory, never
+// freed).  Buffers that must never be half-present grow through reserve_group: all members or none.
 #pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <stdlib.h>
+
+#include <algorithm>
+#include <initializer_list>
+#include <string>
+#include <vector>
+
+#include "../../include/gmrf_hip.h"
+
+static thread_local std::string g_last_error;
+
+#define HIPCHK(expr)                                                                        \
+    do {                                                                                    \
+        hipError_t _e = (expr);                                                             \
+        if (_e != hipSuccess) {                                                             \
+            g_last_error = std::string(#expr) + ": " + hipGetErrorString(_e);               \
+            return GMRF_ERR_HIP;                                                            \
+        }                                                                                   \
+    } while (0)
+
+#define GCHK(expr)                                                                          \
+    do {                                                                                    \
+        gmrf_status _s = (expr);                                                            \
+        if (_s != GMRF_OK) return _s;                                                       \
+    } while (0)
+
+static gmrf_status bad_shape(const char* msg) {
+    g_last_error = msg;
+    return GMRF_ERR_BAD_SHAPE;
+}
+
+static bool is_device_ptr(const void* p) {
+    if (!p) return false;
+    hipPointerAttribute_t attr;
+    hipError_t e = hipPointerGetAttributes(&attr, p);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();   // unregistered host memory: clear the sticky error
+        return false;
+    }
+    return attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged;
+}
+
+// Where DevBuf meets the device.  A stand-alone check of the ownership rules defines GMRF_HOST_UTIL_FAKE_DEVICE and its own three.
+#ifndef GMRF_HOST_UTIL_FAKE_DEVICE
+static hipError_t dev_alloc(void** p, size_t bytes) { return hipMalloc(p, bytes); }
+static void dev_free(void* p) { (void)hipFree(p); }
+static hipError_t dev_drain(hipStream_t stream) { return hipStreamSynchronize(stream); }
+#endif
 
 // An integer switch from the environment.  Callers keep the value in a function-local static: read once per process.
 static int env_int(const char* name, int dflt) {
@@ -9,22 +65,25 @@ static int env_int(const char* name, int dflt) {
     return e ? atoi(e) : dflt;
 }
 
-static void free_dev(void* p) {
-    if (p) (void)hipFree(p);
-}
-
-// Grow-only device buffer.  What was enqueued on `stream` may still use the old allocation, so the stream is drained
-// before it is freed.
+// Grow-only device buffer that frees itself.  What was enqueued on `stream` may still use the old allocation, so the stream is
+// drained before it is freed.  A failed reserve leaves the buffer empty: the next call retries.
 struct DevBuf {
     void* p = nullptr;
     size_t cap = 0;                     // bytes
+    bool owned = true;                  // false: p is the caller's (borrow), never freed
 
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { release(); }
+
+    bool fits(size_t bytes) const { return p && owned && bytes <= cap; }
     gmrf_status reserve(hipStream_t stream, size_t bytes) {
-        if (p && bytes <= cap) return GMRF_OK;
-        if (p) HIPCHK(hipStreamSynchronize(stream));
+        if (fits(bytes)) return GMRF_OK;
+        if (p && owned) HIPCHK(dev_drain(stream));
         release();
         bytes = std::max<size_t>(bytes, 16);
-        if (hipError_t e = hipMalloc(&p, bytes); e != hipSuccess) {
+        if (hipError_t e = dev_alloc(&p, bytes); e != hipSuccess) {
             p = nullptr;
             g_last_error = std::string("hipMalloc (DevBuf::reserve): ") + hipGetErrorString(e);
             return GMRF_ERR_HIP;
@@ -32,8 +91,62 @@ struct DevBuf {
         cap = bytes;
         return GMRF_OK;
     }
-    void release() { free_dev(p); p = nullptr; cap = 0; }
+    void borrow(void* q, size_t bytes) { release(); p = q; cap = bytes; owned = false; }
+    void release() { if (p && owned) dev_free(p); p = nullptr; cap = 0; owned = true; }
     template <class T> T* as() const { return static_cast<T*>(p); }
+};
+
+// A member of a reserve_group: the buffer and the bytes it must hold.
+struct Want { DevBuf* buf; size_t bytes; };
+
+// Buffers that are used together grow together or not at all: if any member fails, every member is released.
+static gmrf_status reserve_group(hipStream_t stream, std::initializer_list<Want> group) {
+    gmrf_status s = GMRF_OK;
+    for (const Want& w : group)
+        if ((s = w.buf->reserve(stream, w.bytes)) != GMRF_OK) break;
+    if (s != GMRF_OK)
+        for (const Want& w : group) w.buf->release();
+    return s;
+}
+
+// Typed DevBuf.  Converts to T*, so it stands wherever the raw pointer stood (arithmetic, null tests, kernel arguments).
+template <class T> struct DevArr {
+    DevBuf buf;
+
+    operator T*() const { return static_cast<T*>(buf.p); }
+    T* get() const { return static_cast<T*>(buf.p); }
+    size_t size() const { return buf.cap / sizeof(T); }             // elements
+    bool fits(size_t elems) const { return buf.fits(elems * sizeof(T)); }
+    bool owned() const { return buf.owned; }
+    gmrf_status reserve(hipStream_t stream, size_t elems) { return buf.reserve(stream, elems * sizeof(T)); }
+    Want want(size_t elems) { return {&buf, elems * sizeof(T)}; }
+    void borrow(T* q, size_t elems) { buf.borrow(q, elems * sizeof(T)); }
+    void release() { buf.release(); }
+    // Reserves and enqueues the copy of `elems` host elements; the caller keeps `src` alive until it has synchronised.
+    gmrf_status upload(hipStream_t stream, const T* src, size_t elems) {
+        GCHK(reserve(stream, elems));
+        if (elems) HIPCHK(hipMemcpyAsync(buf.p, src, elems * sizeof(T), hipMemcpyHostToDevice, stream));
+        return GMRF_OK;
+    }
+    gmrf_status upload(hipStream_t stream, const std::vector<T>& v) { return upload(stream, v.data(), v.size()); }
+};
+
+// One mapped host word (64 bytes) that a kernel writes and the host polls.
+struct HostWord {
+    unsigned* p = nullptr;
+
+    HostWord() = default;
+    HostWord(const HostWord&) = delete;
+    HostWord& operator=(const HostWord&) = delete;
+    ~HostWord() { if (p) (void)hipHostFree(p); }
+
+    operator unsigned*() const { return p; }
+    hipError_t open() {
+        if (p) return hipSuccess;
+        hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&p), 64, hipHostMallocMapped);
+        if (e == hipSuccess) *p = 0u; else p = nullptr;
+        return e;
+    }
 };
 
 // Device and stream of a handle.  device -1: the handle was created for its host side only (patterns); nothing of the

@@ -95,6 +95,9 @@ struct gmrf_csr : DevCtx {
     int64_t n_ucols = 0;
     int plan_rows = 0, plan_ucap = 0, plan_ecap = 0, plan_ecap_pad = 0, plan_umax = 0;   // rows per tile, LDS capacities (distinct columns, entries)
     uint64_t id = 0;                   // unique per created matrix (the selected-inverse plan of a handle is keyed by it)
+    // the routes of the last products launched on this matrix (gmrf_test_spmm_route): node-major kind (SpmmRowsRoute) and NG,
+    // column-major lane group (0: csr_spmv_tiles); -1: none yet
+    int last_rows_kind = -1, last_rows_ng = -1, last_cols_g = -1;
 };
 static std::atomic<uint64_t> g_csr_ids{0};
 
@@ -3492,6 +3495,97 @@ gmrf_status gmrf_bt_logdet_batch(gmrf_handle* h, double* out) {
 }
 
 // --------------------------------------------------------------------------------- CSR / SpMM
+// The routes of Y = S X as values: what the launchers below branch on, and what gmrf_test_spmm_plan / gmrf_test_spmm_route report
+// (host only, no device state).
+
+// csr_spmv_tiles can take the matrix: no SPMV_ROWS-row tile has more than SPMV_CAP entries (rp: 0-based row pointers)
+static bool spmv_tiles_ok(int64_t n_rows, const int64_t* rp) {
+    for (int64_t r = 0; r < n_rows; r += SPMV_ROWS)
+        if (rp[std::min(n_rows, r + SPMV_ROWS)] - rp[r] > SPMV_CAP) return false;
+    return true;
+}
+
+// Column-major operands: 0 = csr_spmv_tiles (one right-hand side, tiles_ok), else the lane group G of csr_spmm<VT, G>, by entries per row
+static int spmm_cols_route(int64_t nnz, int64_t n_rows, int k, bool tiles_ok) {
+    if (k == 1 && tiles_ok) return 0;
+    const double avg = (double)nnz / (double)n_rows;
+    return avg > 40 ? 64 : avg > 20 ? 32 : avg > 10 ? 16 : 8;
+}
+
+// Tile plan of csr_spmm_tiles: per R-row tile the ascending list of distinct columns and, per entry, the 16-bit index of its
+// column in that list; the LDS capacities of the two tiled kernels.
+struct SpmmPlan {
+    int state = -1;                    // 1: usable, -1: no tile height fits the LDS image
+    int R = 0, ucap = 0, ecap = 0;     // rows per tile; distinct columns (rounded to 32) and entries (rounded to 256) of the largest tile
+    int ecap_pad = 0;                  // entries of the largest tile with rows padded to 8, rounded to 64; 0: the padded image does not fit
+    int umax = 0;                      // most distinct columns of a tile
+    std::vector<int64_t> tile_uptr;    // [tiles + 1] ranges into ucols
+    std::vector<int32_t> ucols;
+    std::vector<uint16_t> lidx;        // [nnz]
+};
+
+static void spmm_plan_host(int64_t n_rows, const int64_t* rp, const int32_t* ci, SpmmPlan& pl) {
+    const int64_t nnz = rp[n_rows];
+    std::vector<int64_t>& uptr = pl.tile_uptr;
+    std::vector<int32_t>& ucols = pl.ucols;
+    std::vector<uint16_t>& lidx = pl.lidx;
+    lidx.assign((size_t)std::max<int64_t>(nnz, 1), 0);
+    std::vector<int32_t> tmp;
+    // the tallest tile whose LDS image (distinct rows of X for 16 right-hand sides + the entries) lets three
+    // workgroups share a CU; a matrix whose 16-row tiles do not fit keeps the plain kernel
+    constexpr size_t lds_budget = 52 * 1024;
+    pl.state = -1;
+    for (int R : {64, 32, 16}) {
+        const int64_t T = (n_rows + R - 1) / R;
+        uptr.assign((size_t)T + 1, 0);
+        ucols.clear();
+        ucols.reserve((size_t)(nnz / 3 + 16));
+        int64_t umax = 0, emax = 0, pmax = 0;
+        bool ok = true;
+        for (int64_t tix = 0; tix < T && ok; ++tix) {
+            const int64_t r0 = tix * R, r1 = std::min(n_rows, r0 + R);
+            const int64_t a = rp[r0], b = rp[r1];
+            tmp.assign(ci + a, ci + b);
+            std::sort(tmp.begin(), tmp.end());
+            tmp.erase(std::unique(tmp.begin(), tmp.end()), tmp.end());
+            umax = std::max<int64_t>(umax, (int64_t)tmp.size()); emax = std::max(emax, b - a);
+            int64_t padded = 0;                                  // rows padded to multiples of 8 entries (csr_spmm_tiles_pad)
+            for (int64_t r = r0; r < r1; ++r) padded += (rp[r + 1] - rp[r] + 7) / 8 * 8;
+            pmax = std::max(pmax, padded);
+            if ((int64_t)tmp.size() > 32 * SPMM_NG || b - a > 8192) { ok = false; break; }
+            for (int64_t e = a; e < b; ++e)
+                lidx[(size_t)e] = (uint16_t)(std::lower_bound(tmp.begin(), tmp.end(), ci[e]) - tmp.begin());
+            ucols.insert(ucols.end(), tmp.begin(), tmp.end());
+            uptr[(size_t)tix + 1] = (int64_t)ucols.size();
+        }
+        if (!ok) continue;
+        const int ucap = (int)std::max<int64_t>(32, (umax + 31) / 32 * 32), ecap = (int)std::max<int64_t>(256, (emax + 255) / 256 * 256);
+        if (spmm_tile_lds_bytes(R, ucap, ecap) > lds_budget) continue;
+        pl.R = R; pl.ucap = ucap; pl.ecap = ecap; pl.umax = (int)umax;
+        // (the padded kernel sizes its LDS image by the distinct columns rounded to 8, the entries to 64: 39.3 KB on the
+        //  burgers4096x512 matrix -- four workgroups per CU)
+        const int ecap_pad64 = (int)std::max<int64_t>(64, (pmax + 63) / 64 * 64);
+        pl.ecap_pad = (spmm_tile_pad_lds_bytes(R, (int)((umax + 7) / 8 * 8), ecap_pad64) <= lds_budget + 1024) ? ecap_pad64 : 0;
+        pl.state = 1;
+        return;
+    }
+    uptr.clear(); ucols.clear();
+}
+
+// Node-major operands: which kernel takes one call.  The tiled kernels read X and write Y as 16-byte pieces and keep a gathered row's
+// offset in 32 bits of 16-byte units: even k, ld and batch strides, 16-byte aligned bases, n_cols * ldx < 2^32 -- else the plain kernel.
+enum { SPMM_ROWS_PLAIN = 0, SPMM_ROWS_TILES = 1, SPMM_ROWS_PAD = 2 };
+struct SpmmRowsRoute { int kind, ng; };                  // ng: gather loads per thread and chunk (7: up to 224 distinct columns, else SPMM_NG)
+static SpmmRowsRoute spmm_rows_route(int plan_state, int ucap, int ecap_pad, int64_t n_cols, int k, int64_t ldx, int64_t ldy,
+                                     bool x_aligned, bool y_aligned, int64_t x_stride, int64_t y_stride, bool no_pad) {
+    const bool aligned = (k % 2 == 0) && (ldx % 2 == 0) && (ldy % 2 == 0) && x_aligned && y_aligned && (x_stride % 2 == 0) &&
+                         (y_stride % 2 == 0) && (n_cols * ldx < ((int64_t)1 << 32));
+    if (plan_state != 1 || !aligned) return {SPMM_ROWS_PLAIN, 0};
+    // 7 gather loads per thread and chunk serve up to 224 distinct columns per tile, 10 up to 320
+    return {ecap_pad > 0 && !no_pad ? SPMM_ROWS_PAD : SPMM_ROWS_TILES, ucap <= 224 ? 7 : SPMM_NG};
+}
+static bool ptr_aligned16(const void* p) { return ((uintptr_t)p) % 16 == 0; }
+
 gmrf_status gmrf_csr_create(int32_t device, void* stream, int64_t n_rows, int64_t n_cols, const int64_t* rowptr,
                             const int64_t* colidx, const double* vals, int32_t index_base, int32_t values_f32,
                             gmrf_csr** out) {
@@ -3514,9 +3608,7 @@ gmrf_status gmrf_csr_create(int32_t device, void* stream, int64_t n_rows, int64_
         ci[p] = (int32_t)c;
     }
     m->id = ++g_csr_ids;
-    m->tiles_ok = true;
-    for (int64_t r = 0; r < n_rows; r += SPMV_ROWS)
-        if (rp[std::min(n_rows, r + SPMV_ROWS)] - rp[r] > SPMV_CAP) { m->tiles_ok = false; break; }
+    m->tiles_ok = spmv_tiles_ok(n_rows, rp.data());
     m->n_rows = n_rows; m->n_cols = n_cols; m->nnz = nnz;
     GCHK(m->d_rowptr.upload(m->stream, rp));
     GCHK(m->d_colidx.upload(m->stream, ci));
@@ -3550,9 +3642,10 @@ gmrf_status gmrf_csr_destroy(gmrf_csr* m) {
 
 static gmrf_status spmm_device(const gmrf_csr* S, hipStream_t st, const double* d_X, int64_t ldx, double* d_Y,
                                int64_t ldy, int k, const double* vals_override = nullptr) {
-    const double avg = (double)S->nnz / (double)S->n_rows;
+    const int lg = spmm_cols_route(S->nnz, S->n_rows, k, S->tiles_ok);      // 0: csr_spmv_tiles, else the lane group
+    const_cast<gmrf_csr*>(S)->last_cols_g = lg;
     const int bl = 256;
-    if (k == 1 && S->tiles_ok) {
+    if (lg == 0) {
         // SpMV: LDS-staged row tiles (with 3+ right-hand sides the lane-group kernel, which reuses the
         // entries for four of them, is faster than one pass per right-hand side)
         // (at most 256 * 8 workgroups -- what the chip holds at once -- each walking several tiles)
@@ -3572,30 +3665,24 @@ static gmrf_status spmm_device(const gmrf_csr* S, hipStream_t st, const double* 
 #define SPMM_LAUNCH(VT, G, VP)                                                                               \
     hipLaunchKernelGGL((csr_spmm<VT, G>), grid_for(G), dim3(bl), 0, st, S->d_rowptr, S->d_colidx, VP,        \
                        S->n_rows, d_X, ldx, d_Y, ldy, k)
-    if (vals_override) {                      // same pattern, another problem's values (fp64)
-        if (avg > 40) SPMM_LAUNCH(double, 64, vals_override);
-        else if (avg > 20) SPMM_LAUNCH(double, 32, vals_override);
-        else if (avg > 10) SPMM_LAUNCH(double, 16, vals_override);
-        else SPMM_LAUNCH(double, 8, vals_override);
-    } else if (S->d_vals32) {
-        if (avg > 40) SPMM_LAUNCH(float, 64, S->d_vals32);
-        else if (avg > 20) SPMM_LAUNCH(float, 32, S->d_vals32);
-        else if (avg > 10) SPMM_LAUNCH(float, 16, S->d_vals32);
-        else SPMM_LAUNCH(float, 8, S->d_vals32);
-    } else {
-        if (avg > 40) SPMM_LAUNCH(double, 64, S->d_vals);
-        else if (avg > 20) SPMM_LAUNCH(double, 32, S->d_vals);
-        else if (avg > 10) SPMM_LAUNCH(double, 16, S->d_vals);
-        else SPMM_LAUNCH(double, 8, S->d_vals);
-    }
+#define SPMM_LAUNCH_G(VT, VP)                                                                                \
+    do {                                                                                                     \
+        if (lg == 64) SPMM_LAUNCH(VT, 64, VP);                                                               \
+        else if (lg == 32) SPMM_LAUNCH(VT, 32, VP);                                                          \
+        else if (lg == 16) SPMM_LAUNCH(VT, 16, VP);                                                          \
+        else SPMM_LAUNCH(VT, 8, VP);                                                                         \
+    } while (0)
+    if (vals_override) SPMM_LAUNCH_G(double, vals_override);      // same pattern, another problem's values (fp64)
+    else if (S->d_vals32) SPMM_LAUNCH_G(float, S->d_vals32);
+    else SPMM_LAUNCH_G(double, S->d_vals);
+#undef SPMM_LAUNCH_G
 #undef SPMM_LAUNCH
     HIPCHK(hipGetLastError());
     return GMRF_OK;
 }
 
-// Tile plan of csr_spmm_tiles: per SPMM_ROWS-row tile the ascending list of distinct columns and, per
-// entry, the 16-bit index of its column in that list.  Built once per matrix (host; the device
-// arrays of the matrix are read back), like the symbolic phase of the factor.
+// The tile plan of a matrix, built once (spmm_plan_host over the pattern read back from the device, like the symbolic phase
+// of the factor) and uploaded.
 static gmrf_status spmm_plan(gmrf_csr* m) {
     if (m->plan_state != 0) return GMRF_OK;
     std::vector<int64_t> rp((size_t)m->n_rows + 1);
@@ -3603,56 +3690,29 @@ static gmrf_status spmm_plan(gmrf_csr* m) {
     HIPCHK(hipMemcpyAsync(rp.data(), m->d_rowptr, sizeof(int64_t) * (m->n_rows + 1), hipMemcpyDeviceToHost, m->stream));
     if (m->nnz > 0) HIPCHK(hipMemcpyAsync(ci.data(), m->d_colidx, sizeof(int32_t) * m->nnz, hipMemcpyDeviceToHost, m->stream));
     HIPCHK(hipStreamSynchronize(m->stream));
-    std::vector<int64_t> uptr;
-    std::vector<int32_t> ucols;
-    std::vector<uint16_t> lidx((size_t)std::max<int64_t>(m->nnz, 1));
-    std::vector<int32_t> tmp;
-    // the tallest tile whose LDS image (distinct rows of X for 16 right-hand sides + the entries) lets three
-    // workgroups share a CU; a matrix whose 16-row tiles do not fit keeps the plain kernel
-    constexpr size_t lds_budget = 52 * 1024;
+    SpmmPlan pl;
+    spmm_plan_host(m->n_rows, rp.data(), ci.data(), pl);
     m->plan_state = -1;
-    for (int R : {64, 32, 16}) {
-        const int64_t T = (m->n_rows + R - 1) / R;
-        uptr.assign((size_t)T + 1, 0);
-        ucols.clear();
-        ucols.reserve((size_t)(m->nnz / 3 + 16));
-        int64_t umax = 0, emax = 0, pmax = 0;
-        bool ok = true;
-        for (int64_t tix = 0; tix < T && ok; ++tix) {
-            const int64_t r0 = tix * R, r1 = std::min(m->n_rows, r0 + R);
-            const int64_t a = rp[r0], b = rp[r1];
-            tmp.assign(ci.begin() + a, ci.begin() + b);
-            std::sort(tmp.begin(), tmp.end());
-            tmp.erase(std::unique(tmp.begin(), tmp.end()), tmp.end());
-            umax = std::max<int64_t>(umax, (int64_t)tmp.size()); emax = std::max(emax, b - a);
-            int64_t padded = 0;                                  // rows padded to multiples of 8 entries (csr_spmm_tiles_pad)
-            for (int64_t r = r0; r < r1; ++r) padded += (rp[r + 1] - rp[r] + 7) / 8 * 8;
-            pmax = std::max(pmax, padded);
-            if ((int64_t)tmp.size() > 32 * SPMM_NG || b - a > 8192) { ok = false; break; }
-            for (int64_t e = a; e < b; ++e)
-                lidx[(size_t)e] = (uint16_t)(std::lower_bound(tmp.begin(), tmp.end(), ci[(size_t)e]) - tmp.begin());
-            ucols.insert(ucols.end(), tmp.begin(), tmp.end());
-            uptr[(size_t)tix + 1] = (int64_t)ucols.size();
-        }
-        if (!ok) continue;
-        const int ucap = (int)std::max<int64_t>(32, (umax + 31) / 32 * 32), ecap = (int)std::max<int64_t>(256, (emax + 255) / 256 * 256);
-        const int ecap_pad = (int)std::max<int64_t>(256, (pmax + 255) / 256 * 256);
-        if (spmm_tile_lds_bytes(R, ucap, ecap) > lds_budget) continue;
-        m->plan_rows = R; m->plan_ucap = ucap; m->plan_ecap = ecap; m->plan_umax = (int)umax;
-        // (the padded kernel sizes its LDS image by the distinct columns rounded to 8, the entries to 64: 39.3 KB on the
-        //  burgers4096x512 matrix -- four workgroups per CU)
-        const int ecap_pad64 = (int)std::max<int64_t>(64, (pmax + 63) / 64 * 64);
-        m->plan_ecap_pad = (spmm_tile_pad_lds_bytes(R, (int)((umax + 7) / 8 * 8), ecap_pad64) <= lds_budget + 1024) ? ecap_pad64 : 0;
-        (void)ecap_pad;
-        m->n_ucols = (int64_t)ucols.size();
-        GCHK(m->d_tile_uptr.upload(m->stream, uptr.data(), (size_t)(T + 1)));
-        GCHK(m->d_ucols.upload(m->stream, ucols));
-        GCHK(m->d_lidx.upload(m->stream, lidx.data(), (size_t)m->nnz));
-        HIPCHK(hipStreamSynchronize(m->stream));
-        m->plan_state = 1;
-        break;
-    }
+    if (pl.state != 1) return GMRF_OK;
+    m->plan_rows = pl.R; m->plan_ucap = pl.ucap; m->plan_ecap = pl.ecap; m->plan_umax = pl.umax; m->plan_ecap_pad = pl.ecap_pad;
+    m->n_ucols = (int64_t)pl.ucols.size();
+    GCHK(m->d_tile_uptr.upload(m->stream, pl.tile_uptr));
+    GCHK(m->d_ucols.upload(m->stream, pl.ucols));
+    GCHK(m->d_lidx.upload(m->stream, pl.lidx.data(), (size_t)m->nnz));
+    HIPCHK(hipStreamSynchronize(m->stream));
+    m->plan_state = 1;
     return GMRF_OK;
+}
+
+// Launch geometry of the tiled kernels on S's plan: the padded kernel sizes its LDS image by the distinct columns rounded to 8
+struct SpmmTileGeom { int R, uc, ec; size_t lds; };
+static SpmmTileGeom spmm_tile_geom(const gmrf_csr* m, bool pad) {
+    SpmmTileGeom g;
+    g.R = m->plan_rows;
+    g.uc = pad ? (m->plan_umax + 7) / 8 * 8 : m->plan_ucap;            // LDS rows of the staged X image
+    g.ec = pad ? m->plan_ecap_pad : m->plan_ecap;
+    g.lds = pad ? spmm_tile_pad_lds_bytes(g.R, g.uc, g.ec) : spmm_tile_lds_bytes(g.R, g.uc, g.ec);
+    return g;
 }
 
 // Y = S X with node-major device operands (X[col][rhs], Y[row][rhs]); vals_override: same pattern,
@@ -3661,31 +3721,28 @@ static gmrf_status spmm_rows_device(const gmrf_csr* S, hipStream_t st, const dou
                                     int64_t ldy, int k, const double* vals_override = nullptr) {
     gmrf_csr* m = const_cast<gmrf_csr*>(S);
     GCHK(spmm_plan(m));
-    const bool aligned = (k % 2 == 0) && (ldx % 2 == 0) && (ldy % 2 == 0) && (((uintptr_t)d_X) % 16 == 0) && (((uintptr_t)d_Y) % 16 == 0) &&
-                         (S->n_cols * ldx < ((int64_t)1 << 32));
-    if (m->plan_state == 1 && aligned) {
-        const int R = m->plan_rows, uc = m->plan_ucap, ec = m->plan_ecap;
-        const dim3 grid((unsigned)((S->n_rows + R - 1) / R));
-        const bool pad = m->plan_ecap_pad > 0;
-        const int ecl = pad ? m->plan_ecap_pad : ec;
-        const int ucl = pad ? (m->plan_umax + 7) / 8 * 8 : uc;          // LDS rows of the staged X image
-        const size_t lds = pad ? spmm_tile_pad_lds_bytes(R, ucl, ecl) : spmm_tile_lds_bytes(R, uc, ec);
-        // 7 gather loads per thread and chunk serve up to 224 distinct columns per tile, 10 up to 320
+    const SpmmRowsRoute rt = spmm_rows_route(m->plan_state, m->plan_ucap, m->plan_ecap_pad, S->n_cols, k, ldx, ldy, ptr_aligned16(d_X),
+                                             ptr_aligned16(d_Y), 0, 0, false);
+    m->last_rows_kind = rt.kind; m->last_rows_ng = rt.ng;
+    if (rt.kind != SPMM_ROWS_PLAIN) {
+        const bool pad = rt.kind == SPMM_ROWS_PAD;
+        const SpmmTileGeom tg = spmm_tile_geom(m, pad);
+        const dim3 grid((unsigned)((S->n_rows + tg.R - 1) / tg.R));
+#define GMRF_SPMM_TILES_K(KERNEL, VT, NGV, VP)                                                                           \
+        hipLaunchKernelGGL((KERNEL<VT, NGV>), grid, dim3(SPMM_THREADS), tg.lds, st, S->d_rowptr, S->d_lidx, VP, S->d_tile_uptr, \
+                           S->d_ucols, S->n_rows, d_X, ldx, d_Y, ldy, k, tg.R, tg.uc, tg.ec, SpmmBatch())
 #define GMRF_SPMM_TILES(VT, VP)                                                                                          \
         do {                                                                                                             \
-            if (pad && uc <= 224) hipLaunchKernelGGL((csr_spmm_tiles_pad<VT, 7>), grid, dim3(SPMM_THREADS), lds, st, S->d_rowptr, S->d_lidx, VP, \
-                                              S->d_tile_uptr, S->d_ucols, S->n_rows, d_X, ldx, d_Y, ldy, k, R, ucl, ecl, SpmmBatch());  \
-            else if (pad) hipLaunchKernelGGL((csr_spmm_tiles_pad<VT, SPMM_NG>), grid, dim3(SPMM_THREADS), lds, st, S->d_rowptr, S->d_lidx, VP,    \
-                                    S->d_tile_uptr, S->d_ucols, S->n_rows, d_X, ldx, d_Y, ldy, k, R, ucl, ecl, SpmmBatch());            \
-            else if (uc <= 224) hipLaunchKernelGGL((csr_spmm_tiles<VT, 7>), grid, dim3(SPMM_THREADS), lds, st, S->d_rowptr, S->d_lidx, VP, \
-                                              S->d_tile_uptr, S->d_ucols, S->n_rows, d_X, ldx, d_Y, ldy, k, R, uc, ec, SpmmBatch());  \
-            else hipLaunchKernelGGL((csr_spmm_tiles<VT, SPMM_NG>), grid, dim3(SPMM_THREADS), lds, st, S->d_rowptr, S->d_lidx, VP,    \
-                                    S->d_tile_uptr, S->d_ucols, S->n_rows, d_X, ldx, d_Y, ldy, k, R, uc, ec, SpmmBatch());            \
+            if (pad && rt.ng == 7) GMRF_SPMM_TILES_K(csr_spmm_tiles_pad, VT, 7, VP);                                     \
+            else if (pad) GMRF_SPMM_TILES_K(csr_spmm_tiles_pad, VT, SPMM_NG, VP);                                        \
+            else if (rt.ng == 7) GMRF_SPMM_TILES_K(csr_spmm_tiles, VT, 7, VP);                                           \
+            else GMRF_SPMM_TILES_K(csr_spmm_tiles, VT, SPMM_NG, VP);                                                     \
         } while (0)
         if (vals_override) GMRF_SPMM_TILES(double, vals_override);
         else if (S->d_vals32) GMRF_SPMM_TILES(float, S->d_vals32);
         else GMRF_SPMM_TILES(double, S->d_vals);
 #undef GMRF_SPMM_TILES
+#undef GMRF_SPMM_TILES_K
     } else {
         const dim3 grid((unsigned)((S->n_rows + 15) / 16));
         if (vals_override) hipLaunchKernelGGL(csr_spmm_rows<double>, grid, dim3(256), 0, st, S->d_rowptr, S->d_colidx, vals_override, S->n_rows, d_X, ldx, d_Y, ldy, k);
@@ -3697,29 +3754,29 @@ static gmrf_status spmm_rows_device(const gmrf_csr* S, hipStream_t st, const dou
 }
 
 // The same product for `batch` problems on S's pattern in one launch: problem p has the fp64 values vals + p nnz and the
-// node-major operands d_X + p x_stride, d_Y + p y_stride.  The route (tiled, padded, plain) is chosen exactly as
-// spmm_rows_device chooses it for one problem -- the strides keep the operands 16-byte aligned or the plain kernel runs.
+// node-major operands d_X + p x_stride, d_Y + p y_stride.  The route (tiled, padded, plain) is the one spmm_rows_route gives
+// one problem -- the strides keep the operands 16-byte aligned or the plain kernel runs.  no_pad withholds the padded plan
+// for this call (gmrf_test_spmm_rows_batch: the unpadded kernels on a matrix whose padded image fits).
 static gmrf_status spmm_rows_device_batch(const gmrf_csr* S, hipStream_t st, int64_t batch, const double* vals, const double* d_X,
-                                          int64_t ldx, int64_t x_stride, double* d_Y, int64_t ldy, int64_t y_stride, int k) {
+                                          int64_t ldx, int64_t x_stride, double* d_Y, int64_t ldy, int64_t y_stride, int k,
+                                          bool no_pad = false) {
     gmrf_csr* m = const_cast<gmrf_csr*>(S);
     GCHK(spmm_plan(m));
-    const bool aligned = (k % 2 == 0) && (ldx % 2 == 0) && (ldy % 2 == 0) && (((uintptr_t)d_X) % 16 == 0) && (((uintptr_t)d_Y) % 16 == 0) &&
-                         (x_stride % 2 == 0) && (y_stride % 2 == 0) && (S->n_cols * ldx < ((int64_t)1 << 32));
-    if (m->plan_state == 1 && aligned) {
-        const int R = m->plan_rows, uc = m->plan_ucap, ec = m->plan_ecap;
-        const dim3 grid((unsigned)((S->n_rows + R - 1) / R), (unsigned)batch);
-        const bool pad = m->plan_ecap_pad > 0;
-        const int ecl = pad ? m->plan_ecap_pad : ec;
-        const int ucl = pad ? (m->plan_umax + 7) / 8 * 8 : uc;
-        const size_t lds = pad ? spmm_tile_pad_lds_bytes(R, ucl, ecl) : spmm_tile_lds_bytes(R, uc, ec);
-#define GMRF_SPMM_TILES_B(KERNEL, NGV, UC, EC)                                                                                \
-        hipLaunchKernelGGL((KERNEL<double, NGV, true>), grid, dim3(SPMM_THREADS), lds, st, S->d_rowptr, S->d_lidx, vals, S->d_tile_uptr, \
-                           S->d_ucols, S->n_rows, d_X, ldx, d_Y, ldy, k, R, UC, EC, sb)
+    const SpmmRowsRoute rt = spmm_rows_route(m->plan_state, m->plan_ucap, m->plan_ecap_pad, S->n_cols, k, ldx, ldy, ptr_aligned16(d_X),
+                                             ptr_aligned16(d_Y), x_stride, y_stride, no_pad);
+    m->last_rows_kind = rt.kind; m->last_rows_ng = rt.ng;
+    if (rt.kind != SPMM_ROWS_PLAIN) {
+        const bool pad = rt.kind == SPMM_ROWS_PAD;
+        const SpmmTileGeom tg = spmm_tile_geom(m, pad);
+        const dim3 grid((unsigned)((S->n_rows + tg.R - 1) / tg.R), (unsigned)batch);
+#define GMRF_SPMM_TILES_B(KERNEL, NGV)                                                                                        \
+        hipLaunchKernelGGL((KERNEL<double, NGV, true>), grid, dim3(SPMM_THREADS), tg.lds, st, S->d_rowptr, S->d_lidx, vals, S->d_tile_uptr, \
+                           S->d_ucols, S->n_rows, d_X, ldx, d_Y, ldy, k, tg.R, tg.uc, tg.ec, sb)
         const SpmmBatch sb{S->nnz, x_stride, y_stride};
-        if (pad && uc <= 224) GMRF_SPMM_TILES_B(csr_spmm_tiles_pad, 7, ucl, ecl);
-        else if (pad) GMRF_SPMM_TILES_B(csr_spmm_tiles_pad, SPMM_NG, ucl, ecl);
-        else if (uc <= 224) GMRF_SPMM_TILES_B(csr_spmm_tiles, 7, uc, ec);
-        else GMRF_SPMM_TILES_B(csr_spmm_tiles, SPMM_NG, uc, ec);
+        if (pad && rt.ng == 7) GMRF_SPMM_TILES_B(csr_spmm_tiles_pad, 7);
+        else if (pad) GMRF_SPMM_TILES_B(csr_spmm_tiles_pad, SPMM_NG);
+        else if (rt.ng == 7) GMRF_SPMM_TILES_B(csr_spmm_tiles, 7);
+        else GMRF_SPMM_TILES_B(csr_spmm_tiles, SPMM_NG);
 #undef GMRF_SPMM_TILES_B
     } else {
         hipLaunchKernelGGL(csr_spmm_rows_batch<double>, dim3((unsigned)((S->n_rows + 15) / 16), (unsigned)batch), dim3(256), 0, st,
@@ -7284,6 +7341,78 @@ gmrf_status gmrf_test_envelope_csc(int64_t n, int64_t n_blocks, const int64_t* c
                 u[0] = env_units_pp(host, nt, m3, 0); u[1] = env_units_pp(host, nt, m3, 2); u[2] = env_units_upd(host, m3);
             }
     }
+    return GMRF_OK;
+}
+
+// The tile plan and the routes of Y = S X for a CSR pattern, without a device (spmm_plan_host, spmm_rows_route, spmm_cols_route).
+// geom[8] = {k, ldx, ldy, X base 16-byte aligned?, Y base 16-byte aligned?, x_stride, y_stride, padded plan withheld?} (the leading
+// dimensions are the node-major call's).  out[12] = {plan state, R, ucap, ecap, ecap_pad, umax, tiles, distinct columns listed,
+// node-major kind (0 plain, 1 tiled, 2 padded), NG, column-major route at this k (0: csr_spmv_tiles, else G), tiles_ok}.
+// tile_uptr [tiles + 1], ucols, lidx [nnz]: filled where all three are given and cap_uptr / cap_ucols suffice.
+gmrf_status gmrf_test_spmm_plan(int64_t n_rows, int64_t n_cols, const int64_t* rowptr, const int64_t* colidx, int32_t index_base,
+                                const int64_t* geom, int64_t* out, int64_t* tile_uptr, int32_t* ucols, uint16_t* lidx,
+                                int64_t cap_uptr, int64_t cap_ucols) {
+    if (!rowptr || !colidx || !geom || !out) return bad_shape("null pointer");
+    if (n_rows <= 0 || n_cols <= 0 || geom[0] <= 0 || geom[0] > (1 << 20)) return bad_shape("bad CSR arguments");
+    std::vector<int64_t> rp((size_t)n_rows + 1);
+    for (int64_t i = 0; i <= n_rows; ++i) {
+        rp[i] = rowptr[i] - index_base;
+        if (i == 0 ? rp[0] != 0 : rp[i] < rp[i - 1]) return bad_shape("bad CSR row pointers");
+    }
+    const int64_t nnz = rp[n_rows];
+    std::vector<int32_t> ci((size_t)std::max<int64_t>(nnz, 1));
+    for (int64_t p = 0; p < nnz; ++p) {
+        const int64_t c = colidx[p] - index_base;
+        if (c < 0 || c >= n_cols) return bad_shape("column index out of range");
+        ci[p] = (int32_t)c;
+    }
+    SpmmPlan pl;
+    spmm_plan_host(n_rows, rp.data(), ci.data(), pl);
+    const bool tiles_ok = spmv_tiles_ok(n_rows, rp.data());
+    const SpmmRowsRoute rt = spmm_rows_route(pl.state, pl.ucap, pl.ecap_pad, n_cols, (int)geom[0], geom[1], geom[2], geom[3] != 0,
+                                             geom[4] != 0, geom[5], geom[6], geom[7] != 0);
+    out[0] = pl.state; out[1] = pl.R; out[2] = pl.ucap; out[3] = pl.ecap; out[4] = pl.ecap_pad; out[5] = pl.umax;
+    out[6] = pl.state == 1 ? (int64_t)pl.tile_uptr.size() - 1 : 0; out[7] = (int64_t)pl.ucols.size();
+    out[8] = rt.kind; out[9] = rt.ng; out[10] = spmm_cols_route(nnz, n_rows, (int)geom[0], tiles_ok); out[11] = tiles_ok;
+    if (pl.state == 1 && tile_uptr && ucols && lidx && cap_uptr >= (int64_t)pl.tile_uptr.size() && cap_ucols >= (int64_t)pl.ucols.size()) {
+        std::copy(pl.tile_uptr.begin(), pl.tile_uptr.end(), tile_uptr);
+        std::copy(pl.ucols.begin(), pl.ucols.end(), ucols);
+        std::copy(pl.lidx.begin(), pl.lidx.begin() + nnz, lidx);
+    }
+    return GMRF_OK;
+}
+
+// The routes of a live matrix for one call geometry: geom[8] as gmrf_test_spmm_plan with the two alignment flags taken from the
+// addresses X and Y (only their values are read; device or host).  out[12] = {plan state, R, ucap, ecap, ecap_pad, umax, node-major
+// kind, NG, column-major route, and the routes of the LAST products launched on S: node-major kind, NG, column-major route (-1: none)}.
+gmrf_status gmrf_test_spmm_route(const gmrf_csr* S, const int64_t* geom, const void* X, const void* Y, int64_t* out) {
+    if (!S || !geom || !out) return bad_shape("null pointer");
+    if (geom[0] <= 0 || geom[0] > (1 << 20)) return bad_shape("bad k");
+    HIPCHK(hipSetDevice(S->device));
+    gmrf_csr* m = const_cast<gmrf_csr*>(S);
+    GCHK(spmm_plan(m));
+    const SpmmRowsRoute rt = spmm_rows_route(m->plan_state, m->plan_ucap, m->plan_ecap_pad, S->n_cols, (int)geom[0], geom[1], geom[2],
+                                             ptr_aligned16(X), ptr_aligned16(Y), geom[5], geom[6], geom[7] != 0);
+    const bool planned = m->plan_state == 1;
+    out[0] = m->plan_state; out[1] = planned ? m->plan_rows : 0; out[2] = planned ? m->plan_ucap : 0; out[3] = planned ? m->plan_ecap : 0;
+    out[4] = planned ? m->plan_ecap_pad : 0; out[5] = planned ? m->plan_umax : 0;
+    out[6] = rt.kind; out[7] = rt.ng; out[8] = spmm_cols_route(S->nnz, S->n_rows, (int)geom[0], S->tiles_ok);
+    out[9] = S->last_rows_kind; out[10] = S->last_rows_ng; out[11] = S->last_cols_g;
+    return GMRF_OK;
+}
+
+// spmm_rows_device_batch with explicit device pointers: B problems on S's pattern, values vals[B][nnz] (fp64), node-major operands
+// X + p x_stride (row stride ldx) and Y + p y_stride (ldy), k right-hand sides; no_pad withholds the padded plan for this call.
+// B = 1 is the product with another problem's values.  Synchronises S's stream.
+gmrf_status gmrf_test_spmm_rows_batch(const gmrf_csr* S, int64_t B, const double* vals, const double* X, int64_t ldx, int64_t x_stride,
+                                      double* Y, int64_t ldy, int64_t y_stride, int64_t k, int32_t no_pad) {
+    if (!S || !vals || !X || !Y) return bad_shape("null pointer");
+    if (B <= 0 || B > 65535 || k <= 0 || k > (1 << 20) || ldx < k || ldy < k) return bad_shape("bad B / k / ld");
+    if (B > 1 && (x_stride < (S->n_cols - 1) * ldx + k || y_stride < (S->n_rows - 1) * ldy + k)) return bad_shape("problems overlap");
+    HIPCHK(hipSetDevice(S->device));
+    if (!is_device_ptr(vals) || !is_device_ptr(X) || !is_device_ptr(Y)) return bad_shape("gmrf_test_spmm_rows_batch takes device pointers");
+    GCHK(spmm_rows_device_batch(S, S->stream, B, vals, X, ldx, x_stride, Y, ldy, y_stride, (int)k, no_pad != 0));
+    HIPCHK(hipStreamSynchronize(S->stream));
     return GMRF_OK;
 }
 

@@ -912,6 +912,27 @@ gmrf_status gmrf_test_symbolic_csc(int64_t n, int64_t n_blocks, const int64_t* c
 gmrf_status gmrf_test_envelope_csc(int64_t n, int64_t n_blocks, const int64_t* colptr, const int64_t* rowval, int32_t index_base,
                                    int32_t* lo, int32_t* hi, double* units, int64_t cap, int64_t* n_vals);
 
+/* The sparse products' routes as values.  geom[8] = {k, ldx, ldy, X base 16-byte aligned?, Y base 16-byte aligned?, x_stride,
+ * y_stride, padded plan withheld?} describes one node-major call (one problem: strides 0); node-major kinds: 0 csr_spmm_rows /
+ * csr_spmm_rows_batch, 1 csr_spmm_tiles, 2 csr_spmm_tiles_pad, with NG gather loads per thread (7 or 10); column-major route at
+ * the same k: 0 csr_spmv_tiles, else the lane group G of csr_spmm.
+ * gmrf_test_spmm_plan: host only (no device), the tile plan of a CSR pattern and its routes.  out[12] = {plan state (1 usable, -1
+ * none), R, ucap, ecap, ecap_pad, umax, tiles, listed distinct columns, node-major kind, NG, column-major route, every 64-row tile
+ * within csr_spmv_tiles' capacity?}; tile_uptr[tiles + 1], ucols, lidx[nnz] are filled where all three are given and the two
+ * capacities suffice.
+ * gmrf_test_spmm_route: the same for a live matrix, the alignment flags taken from the addresses X and Y.  out[12] = {plan state,
+ * R, ucap, ecap, ecap_pad, umax, node-major kind, NG, column-major route, and of the LAST products launched on S: node-major kind,
+ * NG, column-major route (-1: none yet)}.
+ * gmrf_test_spmm_rows_batch: the batched node-major product on explicit DEVICE pointers -- B problems on S's pattern with the fp64
+ * values vals[B][nnz], operands X + p x_stride, Y + p y_stride; no_pad withholds the padded plan for this call, so the unpadded
+ * tiled kernels run on a matrix whose padded image fits.  B = 1: the product with another problem's values.  Synchronises. */
+gmrf_status gmrf_test_spmm_plan(int64_t n_rows, int64_t n_cols, const int64_t* rowptr, const int64_t* colidx, int32_t index_base,
+                                const int64_t* geom, int64_t* out, int64_t* tile_uptr, int32_t* ucols, uint16_t* lidx,
+                                int64_t cap_uptr, int64_t cap_ucols);
+gmrf_status gmrf_test_spmm_route(const gmrf_csr* S, const int64_t* geom, const void* X, const void* Y, int64_t* out);
+gmrf_status gmrf_test_spmm_rows_batch(const gmrf_csr* S, int64_t B, const double* vals, const double* X, int64_t ldx,
+                                      int64_t x_stride, double* Y, int64_t ldy, int64_t y_stride, int64_t k, int32_t no_pad);
+
 #ifdef __cplusplus
 }
 #endif

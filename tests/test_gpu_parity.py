@@ -1049,16 +1049,26 @@ def test_spmm_node_major_lds_tiles(pkg):
     Y = S64 @ X
     assert np.array_equal(Y[:, 3], (S64 @ np.ascontiguousarray(X[:, 2:6]))[:, 1])
     assert rel(Y[:, 3], S64 @ np.ascontiguousarray(X[:, 3])) < 1e-15
-    # ragged: empty rows, a row count that is no multiple of the tile, rectangular, a tile with too many
-    # distinct columns (falls back to the plain node-major kernel), a dense-ish matrix beyond the entry cap
+    # ragged: empty rows, a row count that is no multiple of the tile, rectangular, 64-row tiles with too many distinct
+    # columns (the plan settles for 32-row tiles of up to 224: the padded kernel with 7 gather loads, NOT the plain kernel);
+    # a dense-ish matrix whose 16-row tiles are beyond the LDS image (no plan: the plain node-major kernel)
+    def last_rows_route(S):
+        out = np.zeros(12, np.int64)
+        pkg._cabi.check(pkg._cabi.load().gmrf_test_spmm_route(S._h, pkg._cabi.ptr(np.array([2, 2, 2, 0, 0, 0, 0, 0], np.int64)), None, None,
+                                                              pkg._cabi.ptr(out)))
+        return tuple(int(v) for v in (out[9], out[10], out[1]))          # kind (0 plain, 1 tiled, 2 padded), NG, tile height
     A = sp.random(1000, 700, density=0.01, random_state=rng, data_rvs=rng.standard_normal).tolil()
     A[5, :] = 0.0; A[999, :] = 0.0
     A = A.tocsr(); A.eliminate_zeros()
     Xa = rng.standard_normal((700, 8))
-    assert rel(pkg.CsrMatrix(A) @ Xa, A @ Xa) < 1e-14
+    Sa = pkg.CsrMatrix(A)
+    assert rel(Sa @ Xa, A @ Xa) < 1e-14
+    assert last_rows_route(Sa) == (2, 7, 32)
     D = sp.random(200, 300, density=0.5, random_state=rng, data_rvs=rng.standard_normal).tocsr()
     Xd2 = rng.standard_normal((300, 4))
-    assert rel(pkg.CsrMatrix(D) @ Xd2, D @ Xd2) < 1e-13
+    Sd = pkg.CsrMatrix(D)
+    assert rel(Sd @ Xd2, D @ Xd2) < 1e-13
+    assert last_rows_route(Sd) == (0, 0, 0)
     # the banded FEM case keeps the plan: a 1-D chain with 3 couplings per row
     T = sp.diags([1.0, -2.5, 1.0], [-1, 0, 1], shape=(5000, 5000)).tocsr()
     Xt = rng.standard_normal((5000, 32))

@@ -51,6 +51,7 @@ EXPORTS = [
     "gmrf_test_gemm", "gmrf_test_gemm_desc", "gmrf_test_gemm_env", "gmrf_test_envelope", "gmrf_test_gemm_pair", "gmrf_test_gemm_rate", "gmrf_test_gemm_shapes", "gmrf_test_potrf_tile", "gmrf_test_potrf_block", "gmrf_test_potrf_route", "gmrf_test_tile_timing", "gmrf_test_persist_stamps", "gmrf_test_persist_aborts", "gmrf_test_factor_fwd", "gmrf_test_gn_route", "gmrf_test_dc_route", "gmrf_test_bic_route", "gmrf_test_var_groups", "gmrf_test_persist_budget", "gmrf_test_clock_probe_start", "gmrf_test_clock_probe_finish",
     "gmrf_test_mfma_f64_rate", "gmrf_test_hbm_rate", "gmrf_test_microbench", "gmrf_test_symbolic_csc", "gmrf_test_envelope_csc",
     "gmrf_test_spmm_plan", "gmrf_test_spmm_route", "gmrf_test_spmm_rows_batch",
+    "gmrf_test_sweep_route", "gmrf_test_sweep_product",
 ]
 
 
@@ -253,6 +254,8 @@ def load() -> C.CDLL:
         "gmrf_test_spmm_plan": [i64, i64, vp, vp, i32, vp, vp, vp, vp, vp, i64, i64],
         "gmrf_test_spmm_route": [vp, vp, vp, vp, vp],
         "gmrf_test_spmm_rows_batch": [vp, i64, vp, vp, i64, i64, vp, i64, i64, i64, i32],
+        "gmrf_test_sweep_route": [vp, vp],
+        "gmrf_test_sweep_product": [i32, i32, vp, vp, i64, vp, i64, i64, i64, i64, vp, i64, vp, i64, P(i32)],
     }
     for name, args in sigs.items():
         fn = getattr(lib, name)

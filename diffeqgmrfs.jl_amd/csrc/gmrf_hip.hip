@@ -7416,6 +7416,141 @@ gmrf_status gmrf_test_spmm_rows_batch(const gmrf_csr* S, int64_t B, const double
     return GMRF_OK;
 }
 
+// ---- the block sweep products (sweep.hpp) as a route value and as one product on explicit operands ---------------------------
+// desc[17] = {trans, tri, kp, rows, kdim, nprob, narrow, kst set?, mend set?, ld, ldx, ldb, ldo, pMat, pXin, pBin, pOut}
+struct SweepDesc {
+    bool trans, tri, has_kst, has_mend;
+    int kp, rows, kdim, nprob, narrow;
+    int64_t ld, ldx, ldb, ldo, pMat, pXin, pBin, pOut;
+};
+static gmrf_status sweep_desc_read(const int64_t* desc, SweepDesc* d) {
+    for (int i = 2; i < 7; ++i)
+        if (desc[i] < -(1 << 24) || desc[i] > (1 << 24)) return bad_shape("sweep test: a size is beyond 2^24");
+    for (int i = 9; i < 17; ++i)
+        if (desc[i] < 0 || desc[i] > ((int64_t)1 << 40)) return bad_shape("sweep test: a leading dimension or stride is negative");
+    d->trans = desc[0] != 0; d->tri = desc[1] != 0; d->kp = (int)desc[2]; d->rows = (int)desc[3]; d->kdim = (int)desc[4];
+    d->nprob = (int)desc[5]; d->narrow = (int)desc[6]; d->has_kst = desc[7] != 0; d->has_mend = desc[8] != 0;
+    d->ld = desc[9]; d->ldx = desc[10]; d->ldb = desc[11]; d->ldo = desc[12];
+    d->pMat = desc[13]; d->pXin = desc[14]; d->pBin = desc[15]; d->pOut = desc[16];
+    return GMRF_OK;
+}
+
+// Host only, no device: the kernel launch_sweep takes for the description and its grid.  out[4] = {id (0: refused), gx, gy, gz};
+// the reason of a refusal is left in gmrf_last_error.
+gmrf_status gmrf_test_sweep_route(const int64_t* desc, int64_t* out) {
+    if (!desc || !out) return bad_shape("null pointer");
+    SweepDesc d;
+    GCHK(sweep_desc_read(desc, &d));
+    const SweepRoute r = sweep_route(d.trans, d.tri, d.kp, d.rows, d.kdim, d.nprob, d.narrow, d.has_kst, d.has_mend);
+    if (r.id == SWEEP_REFUSED) g_last_error = r.why;
+    out[0] = r.id; out[1] = r.gx; out[2] = r.gy; out[3] = r.gz;
+    return GMRF_OK;
+}
+
+// One sweep product on explicit operands.  Mat (nMat doubles) and the panel P (nP doubles) are host arrays, uploaded whole; P is
+// read back whole, so the caller sees what was written and what was left.  Xin = P + x_off, Bin = P + b_off (b_off < 0: no addend,
+// sub = 0; b_off == o_off: in place), Out = P + o_off.  force = 0: launch_sweep's own choice; force = id: that instantiation, if the
+// shape meets the kernel's own preconditions (sweep_kernel_route).  *route_out = the id that ran.  Everything a kernel could read
+// or write out of bounds with -- or read misaligned, or race on -- is refused before anything is uploaded:
+//   * the route refuses, or kst / mend are given to a product that has no staircase, or disagree with desc[7], desc[8];
+//   * kst / mend shorter than one entry per 64 rows, an entry odd or outside [0, kdim], or one that leaves a sweep_mm range that
+//     is not a multiple of 8;
+//   * ld (pMat) odd where the kernel loads 16-byte row pieces (all but the transposed sweep_mm, which loads single elements of the
+//     block); x_off, ldx, pXin odd where it loads 16-byte pieces of the input (sweep_mm and the non-transposed gemv kernels);
+//   * ld below the row length, or the furthest element of the block beyond nMat: (rows - 1) ld + kdim, transposed (kdim - 1) ld +
+//     rows, per problem -- the triangular kernels' pieces right of the diagonal end at the next even column (four-row gemv) or at
+//     the end of the diagonal 16-row / CW-column block, all of them inside the first `rows` columns of their rows;
+//   * an input, addend or output cell beyond nP; an output cell that is also an input cell, another output's cell, or an addend
+//     cell other than its own (cell by cell over the whole batch).
+gmrf_status gmrf_test_sweep_product(int32_t device, int32_t force, const int64_t* desc, const double* Mat, int64_t nMat, double* P, int64_t nP,
+                                    int64_t x_off, int64_t b_off, int64_t o_off, const int32_t* kst, int64_t n_kst,
+                                    const int32_t* mend, int64_t n_mend, int32_t* route_out) {
+    if (!desc || !Mat || !P || !route_out) return bad_shape("sweep test: null pointer");
+    *route_out = 0;
+    SweepDesc d;
+    GCHK(sweep_desc_read(desc, &d));
+    if (nMat <= 0 || nP <= 0 || nMat > ((int64_t)1 << 28) || nP > ((int64_t)1 << 28)) return bad_shape("sweep test: buffer sizes");
+    if ((kst != nullptr) != d.has_kst || (mend != nullptr) != d.has_mend) return bad_shape("sweep test: kst / mend disagree with the description");
+    if (kst && (d.trans || d.tri)) return bad_shape("sweep test: kst belongs to the non-transposed, non-triangular product");
+    if (mend && (!d.trans || d.tri)) return bad_shape("sweep test: mend belongs to the transposed, non-triangular product");
+    if (force < 0 || force > SWEEP_KERNELS) return bad_shape("sweep test: no such kernel");
+    const SweepRoute r = force ? sweep_kernel_route(force, d.trans, d.tri, d.kp, d.rows, d.kdim, d.nprob, d.has_kst, d.has_mend)
+                               : sweep_route(d.trans, d.tri, d.kp, d.rows, d.kdim, d.nprob, d.narrow, d.has_kst, d.has_mend);
+    if (r.id == SWEEP_REFUSED) return bad_shape(r.why);
+    const bool mm = r.id <= SWEEP_MM_T_TRI;
+    const int ntile = (d.rows + 63) / 64;
+    for (const int32_t* a : {kst, mend}) {
+        if (!a) continue;
+        if ((a == kst ? n_kst : n_mend) < ntile) return bad_shape("sweep test: kst / mend shorter than one entry per 64 rows");
+        for (int t = 0; t < ntile; ++t) {
+            if (a[t] < 0 || a[t] > d.kdim || a[t] % 2) return bad_shape("sweep test: a kst / mend entry is odd or out of range");
+            if (mm && (a == kst ? d.kdim - a[t] : a[t]) % 8) return bad_shape("sweep test: a kst / mend entry leaves a K range that is not a multiple of 8");
+        }
+    }
+    const bool mat16 = r.id != SWEEP_MM_T && r.id != SWEEP_MM_T_TRI, x16 = r.id <= SWEEP_GEMV_N4_TRI;
+    if (mat16 && (d.ld % 2 || d.pMat % 2)) return bad_shape("sweep test: odd ld or pMat under 16-byte loads of the block");
+    if (x16 && (x_off % 2 || d.pXin % 2 || (mm && d.ldx % 2))) return bad_shape("sweep test: odd x_off, ldx or pXin under 16-byte loads of the input");
+    if (d.ld < (d.trans ? d.rows : d.kdim)) return bad_shape("sweep test: ld below the row length");
+    const bool sub = b_off >= 0;
+    if (mm && (d.ldx < d.kdim || d.ldo < d.rows || (sub && d.ldb < d.rows))) return bad_shape("sweep test: a panel's leading dimension is below its extent");
+    const int64_t needMat = (int64_t)(d.nprob - 1) * d.pMat + (d.trans ? (int64_t)(d.kdim - 1) * d.ld + d.rows : (int64_t)(d.rows - 1) * d.ld + d.kdim);
+    if (needMat > nMat) return bad_shape("sweep test: the block does not fit its buffer");
+    if (x_off < 0 || o_off < 0) return bad_shape("sweep test: negative offset");
+    const bool in_place = sub && b_off == o_off;
+    if (in_place && (d.pBin != d.pOut || (mm && d.ldb != d.ldo))) return bad_shape("sweep test: in place needs the addend's strides to be the output's");
+    {
+        // cell by cell: 1 = input, 2 = output, 4 = addend
+        std::vector<uint8_t> mark((size_t)nP, 0);
+        auto runs = [&](int64_t off, int64_t ldr, int64_t pstride, int len, uint8_t bit, uint8_t clash) -> const char* {
+            for (int p = 0; p < d.nprob; ++p)
+                for (int q = 0; q < d.kp; ++q) {
+                    const int64_t a = off + (int64_t)p * pstride + (int64_t)q * ldr;
+                    if (a < 0 || a + len > nP) return "sweep test: a panel operand does not fit its buffer";
+                    for (int64_t c = a; c < a + len; ++c) {
+                        if (mark[(size_t)c] & clash) return "sweep test: operands overlap";
+                        mark[(size_t)c] |= bit;
+                    }
+                }
+            return nullptr;
+        };
+        const char* bad = runs(x_off, d.ldx, d.pXin, d.kdim, 1, 0);
+        if (!bad) bad = runs(o_off, d.ldo, d.pOut, d.rows, 2, 1 | 2);
+        if (!bad && sub && !in_place) bad = runs(b_off, d.ldb, d.pBin, d.rows, 4, 2);
+        if (bad) return bad_shape(bad);
+    }
+
+    HIPCHK(hipSetDevice(device));
+    std::vector<void*> owned;
+    auto drop = [&]() { for (void* p : owned) (void)hipFree(p); owned.clear(); };
+    hipError_t e = hipSuccess;
+    auto up = [&](const void* host, int64_t count, size_t elem) -> void* {
+        if (!host || e != hipSuccess) return nullptr;
+        void* dv = nullptr;
+        e = hipMalloc(&dv, std::max<size_t>((size_t)count * elem, 16));
+        if (e != hipSuccess) return nullptr;
+        owned.push_back(dv);
+        e = hipMemcpy(dv, host, (size_t)count * elem, hipMemcpyHostToDevice);
+        return dv;
+    };
+    const double* dMat = (const double*)up(Mat, nMat, 8);
+    double* dP = (double*)up(P, nP, 8);
+    SweepArgs s;
+    s.kst = (const int*)up(kst, ntile, 4);
+    s.mend = (const int*)up(mend, ntile, 4);
+    if (e != hipSuccess) { drop(); HIPCHK(e); }
+    s.Mat = dMat; s.ld = d.ld; s.Xin = dP + x_off; s.ldx = d.ldx; s.Bin = sub ? dP + b_off : nullptr; s.ldb = sub ? d.ldb : 0;
+    s.Out = dP + o_off; s.ldo = d.ldo; s.rows = d.rows; s.kdim = d.kdim; s.sub = sub ? 1 : 0;
+    s.pMat = d.pMat; s.pXin = d.pXin; s.pBin = sub ? d.pBin : 0; s.pOut = d.pOut;
+    s.narrow = d.narrow;
+    e = force ? launch_sweep_kernel(nullptr, r, s) : launch_sweep(nullptr, d.trans, d.tri, d.kp, s, d.nprob);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(P, dP, sizeof(double) * (size_t)nP, hipMemcpyDeviceToHost);
+    drop();
+    HIPCHK(e);
+    *route_out = r.id;
+    return GMRF_OK;
+}
+
 gmrf_status gmrf_test_microbench(int32_t device, double* out, int32_t n) {
     if (!out || n < 16) return bad_shape("need 16 outputs");
     HIPCHK(hipSetDevice(device));

@@ -347,7 +347,10 @@ __global__ __launch_bounds__(256) void sweep_gemv_n_short(SweepArgs s) {
     double sum[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-        // the order of sweep_gemv_n: even elements into one sum, odd into the other, ascending k, then the wave reduction
+        // even elements into one sum, odd into the other, ascending k, then the wave reduction.  Non-TRI: the order of
+        // sweep_gemv_n, the same bits.  TRI: the same bits on the odd rows and on the rows that are multiples of 128; on the
+        // other even rows sweep_gemv_n adds the last element (the row's odd tail) to lane 0's sum while here it stays in the
+        // piece of lane (row / 2) % 64 -- another order of the same sum (tests/test_gpu_sweep_routes.py asserts all of this)
         double a0 = fma(m[r][0].x, x0.x, 0.0), a1 = fma(m[r][0].y, x0.y, 0.0);
         a0 = fma(m[r][1].x, x1.x, a0); a1 = fma(m[r][1].y, x1.y, a1);
         sum[r] = a0 + a1;
@@ -367,7 +370,8 @@ __global__ __launch_bounds__(256) void sweep_gemv_n_short(SweepArgs s) {
 // One right-hand side, non-transposed, rows of moderate length (a batch's coupling window inside its staircase, the parts of
 // a split block inverse: 256 .. 768 elements): a wave owns FOUR consecutive rows (rows % 4 == 0; they share the staircase
 // start, 4 | 64), reads the vector piece once per 128 elements and keeps eight 16-byte row pieces in flight -- one row per
-// wave (sweep_gemv_n) gets there only for rows of 1024 elements and more.  Per row the summation order of sweep_gemv_n.
+// wave (sweep_gemv_n) gets there only for rows of 1024 elements and more.  Per row the summation order of sweep_gemv_n_short
+// (the same bits, TRI or not), hence of sweep_gemv_n for the non-triangular form and, TRI, on the rows named there.
 template <bool TRI>
 __global__ __launch_bounds__(256) void sweep_gemv_n4(SweepArgs s) {
     sweep_select_problem(s, blockIdx.z);
@@ -481,51 +485,152 @@ __global__ __launch_bounds__(256) void sweep_gemv_t(SweepArgs s) {
     }
 }
 
-inline hipError_t launch_sweep(hipStream_t st, bool trans, bool tri, int kp, const SweepArgs& s, int nprob) {
-    if (kp == 1) {
-        if (!trans) {
-            if (s.kdim <= 256 && s.rows % 16 == 0 && s.kdim % 2 == 0 && !s.kst) {
-                dim3 grid(s.rows / 16, 1, nprob), block(256);
-                if (tri) hipLaunchKernelGGL((sweep_gemv_n_short<true>), grid, block, 0, st, s);
-                else hipLaunchKernelGGL((sweep_gemv_n_short<false>), grid, block, 0, st, s);
-                return hipGetLastError();
-            }
-            if (nprob >= 8 && s.rows % 16 == 0 && s.kdim <= 768 && s.kdim % 2 == 0) {
-                dim3 grid(s.rows / 16, 1, nprob), block(256);
-                if (tri) hipLaunchKernelGGL((sweep_gemv_n4<true>), grid, block, 0, st, s);
-                else hipLaunchKernelGGL((sweep_gemv_n4<false>), grid, block, 0, st, s);
-                return hipGetLastError();
-            }
-            dim3 grid((s.rows + 3) / 4, 1, nprob), block(256);
-            if (tri) hipLaunchKernelGGL((sweep_gemv_n<true>), grid, block, 0, st, s);
-            else hipLaunchKernelGGL((sweep_gemv_n<false>), grid, block, 0, st, s);
-        } else {
-            // wide column blocks (256-byte row pieces) when the batch supplies enough workgroups that way (two per CU),
-            // narrow ones otherwise (the short products of a split block inverse); one problem (or a few) with blocks of 512 and more:
-            // 8 columns (64-byte row pieces, 64 row groups) -- its chain of dependent products is bound by what ONE CU pulls in,
-            // and twice the workgroups pull twice as much (round 5; sweep_persist's k = 1 bodies do the same sums)
-            const int ncb32 = s.rows / 32;
-            const bool wide = nprob >= 8 && s.rows % 32 == 0 && (int64_t)(tri ? (ncb32 + 1) / 2 : ncb32) * nprob >= 512;
-            // (a few problems: the same sums as one alone.  Up to 1024 rows: darcy256's backward sweep 1.10 -> 0.91 ms; blocks of 4096
-            //  have the workgroups anyway and lose on the 64-byte row pieces -- burgers4096x512: 26 -> 46 us per coupling product)
-            const bool narrow = s.narrow != 0 && s.rows % 8 == 0;      // (the host decides by the BLOCK size: sweep_launches)
-            const int cw = wide ? 32 : (narrow ? 8 : 16), ncb = s.rows / cw;
-            dim3 grid(tri ? (ncb + 1) / 2 : ncb, 1, nprob), block(256);
-            if (tri && wide) hipLaunchKernelGGL((sweep_gemv_t<true, 32>), grid, block, 0, st, s);
-            else if (tri && narrow) hipLaunchKernelGGL((sweep_gemv_t<true, 8>), grid, block, 0, st, s);
-            else if (tri) hipLaunchKernelGGL((sweep_gemv_t<true, 16>), grid, block, 0, st, s);
-            else if (wide) hipLaunchKernelGGL((sweep_gemv_t<false, 32>), grid, block, 0, st, s);
-            else if (narrow) hipLaunchKernelGGL((sweep_gemv_t<false, 8>), grid, block, 0, st, s);
-            else hipLaunchKernelGGL((sweep_gemv_t<false, 16>), grid, block, 0, st, s);
+// What the TRI kernels read of a block beyond its lower triangle (stored zeros, which they multiply with finite inputs):
+//   sweep_gemv_n<true>                      nothing (a row ends at its diagonal element, the odd tail is a single load)
+//   sweep_gemv_n_short / sweep_gemv_n4      an even row r: the element (r, r + 1), the other half of its last 16-byte piece
+//   sweep_mm<false,true>                    the strict upper triangle of every diagonal 16 x 16 block
+//   sweep_mm<true,true>, sweep_gemv_t<true,CW>   the strict upper triangle of every diagonal 16 x 16 / CW x CW block
+// All of it lies in the strict upper triangles of the diagonal 64 x 64 tiles (2, 8, 16 and 32 divide 64), which the factor's
+// contract makes zero (tests/potrf_ref.py).  The 64 x 64 tiles ABOVE the diagonal are read by nobody: the factor leaves them
+// untouched, and the split inverse [X_aa 0; L_ba X_bb] has no "0" in storage.  tests/test_gpu_sweep_routes.py plants NaN there.
+
+// ---- the route as a value ------------------------------------------------------------------------------------------------
+// The sixteen instantiations, with stable ids (0 = refused).  tests/sweep_ref.py restates the table; gmrf_test_sweep_route reports it.
+//   id  kernel                      reached by launch_sweep when                                     grid
+//    1  sweep_mm<false,false>       kp != 1, not transposed, dense / staircase                       (rows / 16, kp / 16, nprob)
+//    2  sweep_mm<false,true>        kp != 1, not transposed, triangular
+//    3  sweep_mm<true,false>        kp != 1, transposed, dense / staircase
+//    4  sweep_mm<true,true>         kp != 1, transposed, triangular
+//    5  sweep_gemv_n<false>         kp == 1, not transposed: what neither of the two four-row forms takes  ((rows + 3) / 4, 1, nprob)
+//    6  sweep_gemv_n<true>
+//    7  sweep_gemv_n_short<false>   ... kdim <= 256, rows % 16 == 0, kdim even, no kst                (rows / 16, 1, nprob)
+//    8  sweep_gemv_n_short<true>
+//    9  sweep_gemv_n4<false>        ... else nprob >= 8, rows % 16 == 0, kdim <= 768, kdim even        (rows / 16, 1, nprob)
+//   10  sweep_gemv_n4<true>
+//   11  sweep_gemv_t<false,8>       kp == 1, transposed, not wide, narrow and rows % 8 == 0           (ncb, 1, nprob), ncb = rows / CW;
+//   12  sweep_gemv_t<true,8>                                                                            triangular: ((ncb + 1) / 2, 1, nprob)
+//   13  sweep_gemv_t<false,16>      kp == 1, transposed, neither wide nor narrow
+//   14  sweep_gemv_t<true,16>
+//   15  sweep_gemv_t<false,32>      kp == 1, transposed, wide: nprob >= 8, rows % 32 == 0 and 512 workgroups or more that way
+//   16  sweep_gemv_t<true,32>
+enum SweepKernel : int {
+    SWEEP_REFUSED = 0,
+    SWEEP_MM_N = 1, SWEEP_MM_N_TRI = 2, SWEEP_MM_T = 3, SWEEP_MM_T_TRI = 4,
+    SWEEP_GEMV_N = 5, SWEEP_GEMV_N_TRI = 6, SWEEP_GEMV_N_SHORT = 7, SWEEP_GEMV_N_SHORT_TRI = 8, SWEEP_GEMV_N4 = 9, SWEEP_GEMV_N4_TRI = 10,
+    SWEEP_GEMV_T8 = 11, SWEEP_GEMV_T8_TRI = 12, SWEEP_GEMV_T16 = 13, SWEEP_GEMV_T16_TRI = 14, SWEEP_GEMV_T32 = 15, SWEEP_GEMV_T32_TRI = 16,
+    SWEEP_KERNELS = 16
+};
+
+struct SweepRoute {
+    int id;                 // SweepKernel; SWEEP_REFUSED: nothing may be launched
+    int gx, gy, gz;         // the grid (256 threads per workgroup)
+    const char* why;        // refused: what the kernel cannot do with the shape
+};
+
+// What kernel `id` itself needs of a shape, from its code (not from who calls it), and the grid it is launched on.  A kernel
+// computes nothing for what its grid does not cover and its loops do not reach, so those shapes are refused:
+//   * sweep_mm: rows / 16 by kp / 16 tiles, the K range of a tile split over four waves in groups of 8 -- kp % 16, rows % 16 and
+//     the length of every K range % 8.  A dense range is [0, kdim), a triangular one [0, m0 + 16) or [m0, kdim): kdim % 8 covers
+//     them.  With a staircase the range of a tile is [kst[t], kdim) or [0, mend[u]): the entries are device memory the launcher
+//     cannot see.  The hot path trusts set_layout, which rounds every entry (and cmin, rmax) to 64; gmrf_test_sweep_product
+//     checks its host copies.
+//   * sweep_gemv_n_short / sweep_gemv_n4: four rows per wave, sixteen per workgroup, 16-byte pieces (kdim even); the short form
+//     holds a row in two pieces per lane (kdim <= 256) and knows no staircase.
+//   * sweep_gemv_t<*, CW>: rows / CW column blocks.
+//   * triangular: rows == kdim.
+inline SweepRoute sweep_kernel_route(int id, bool trans, bool tri, int kp, int rows, int kdim, int nprob, bool has_kst, bool has_mend) {
+    (void)has_mend;         // (every transposed non-triangular kernel takes a staircase end; no precondition hangs on it)
+    auto no = [](const char* why) { return SweepRoute{SWEEP_REFUSED, 0, 0, 0, why}; };
+    if (id < 1 || id > SWEEP_KERNELS) return no("no such sweep kernel");
+    if (rows <= 0 || kdim <= 0) return no("rows and kdim must be positive");
+    if (kp <= 0 || nprob <= 0 || nprob > 65535) return no("kp and nprob must be positive (nprob is a grid dimension)");
+    if (tri && rows != kdim) return no("a triangular product is square");
+    const bool id_tri = id % 2 == 0;                         // (the even ids are the triangular forms)
+    if (id_tri != tri) return no("the kernel is of the other triangularity");
+    if (id <= SWEEP_MM_T_TRI) {
+        if ((id >= SWEEP_MM_T) != trans) return no("the kernel is of the other orientation");
+        if (kp == 1) return no("sweep_mm takes multiples of 16 right-hand sides");
+        if (kp % 16 != 0 || kp / 16 > 65535) return no("sweep_mm: kp is not a multiple of 16");
+        if (rows % 16 != 0) return no("sweep_mm: rows is not a multiple of 16");
+        if (kdim % 8 != 0) return no("sweep_mm: a K range is not a multiple of 8");
+        return SweepRoute{id, rows / 16, kp / 16, nprob, nullptr};
+    }
+    if (kp != 1) return no("the gemv kernels take one right-hand side");
+    if (id <= SWEEP_GEMV_N4_TRI) {
+        if (trans) return no("the kernel is of the other orientation");
+        if (id <= SWEEP_GEMV_N_TRI) return SweepRoute{id, (rows + 3) / 4, 1, nprob, nullptr};
+        if (rows % 16 != 0) return no("four-row gemv: rows is not a multiple of 16");
+        if (kdim % 2 != 0) return no("four-row gemv: kdim is odd");
+        if (id <= SWEEP_GEMV_N_SHORT_TRI) {
+            if (kdim > 256) return no("sweep_gemv_n_short: rows longer than 256");
+            if (has_kst) return no("sweep_gemv_n_short knows no staircase");
         }
+        return SweepRoute{id, rows / 16, 1, nprob, nullptr};
+    }
+    if (!trans) return no("the kernel is of the other orientation");
+    const int cw = id <= SWEEP_GEMV_T8_TRI ? 8 : (id <= SWEEP_GEMV_T16_TRI ? 16 : 32);
+    if (rows < cw || rows % cw != 0) return no("sweep_gemv_t: rows is not a multiple of the column block");
+    const int ncb = rows / cw;
+    return SweepRoute{id, tri ? (ncb + 1) / 2 : ncb, 1, nprob, nullptr};
+}
+
+// Which kernel one product takes: THE choice (launch_sweep has no other), then that kernel's own preconditions -- a shape its
+// kernel cannot compute is refused, not truncated.  narrow: SweepArgs::narrow; has_kst / has_mend: whether the pointers are set
+// (as today a set kst keeps a product off the short form whether or not its kernel would look at it).
+inline SweepRoute sweep_route(bool trans, bool tri, int kp, int rows, int kdim, int nprob, int narrow, bool has_kst, bool has_mend) {
+    int id;
+    if (kp != 1) {
+        id = trans ? (tri ? SWEEP_MM_T_TRI : SWEEP_MM_T) : (tri ? SWEEP_MM_N_TRI : SWEEP_MM_N);
+    } else if (!trans) {
+        if (kdim <= 256 && rows % 16 == 0 && kdim % 2 == 0 && !has_kst) id = tri ? SWEEP_GEMV_N_SHORT_TRI : SWEEP_GEMV_N_SHORT;
+        else if (nprob >= 8 && rows % 16 == 0 && kdim <= 768 && kdim % 2 == 0) id = tri ? SWEEP_GEMV_N4_TRI : SWEEP_GEMV_N4;
+        else id = tri ? SWEEP_GEMV_N_TRI : SWEEP_GEMV_N;
     } else {
-        dim3 grid(s.rows / 16, kp / 16, nprob), block(256);
-        if (!trans && !tri) hipLaunchKernelGGL((sweep_mm<false, false>), grid, block, 0, st, s);
-        else if (!trans && tri) hipLaunchKernelGGL((sweep_mm<false, true>), grid, block, 0, st, s);
-        else if (trans && !tri) hipLaunchKernelGGL((sweep_mm<true, false>), grid, block, 0, st, s);
-        else hipLaunchKernelGGL((sweep_mm<true, true>), grid, block, 0, st, s);
+        // wide column blocks (256-byte row pieces) when the batch supplies enough workgroups that way (two per CU),
+        // narrow ones otherwise (the short products of a split block inverse); one problem (or a few) with blocks of 512 and more:
+        // 8 columns (64-byte row pieces, 64 row groups) -- its chain of dependent products is bound by what ONE CU pulls in,
+        // and twice the workgroups pull twice as much (round 5; sweep_persist's k = 1 bodies do the same sums)
+        const int ncb32 = rows / 32;
+        const bool wide = nprob >= 8 && rows % 32 == 0 && (int64_t)(tri ? (ncb32 + 1) / 2 : ncb32) * nprob >= 512;
+        // (a few problems take the kernel one problem takes: a problem's sums do not depend on the batch it comes in --
+        //  tests/test_gpu_sweep_routes.py.  Up to 1024 rows: darcy256's backward sweep 1.10 -> 0.91 ms; blocks of 4096
+        //  have the workgroups anyway and lose on the 64-byte row pieces -- burgers4096x512: 26 -> 46 us per coupling product)
+        const bool nar = narrow != 0 && rows % 8 == 0;      // (the host decides by the BLOCK size: sweep_launches)
+        id = wide ? (tri ? SWEEP_GEMV_T32_TRI : SWEEP_GEMV_T32) : (nar ? (tri ? SWEEP_GEMV_T8_TRI : SWEEP_GEMV_T8) : (tri ? SWEEP_GEMV_T16_TRI : SWEEP_GEMV_T16));
+    }
+    return sweep_kernel_route(id, trans, tri, kp, rows, kdim, nprob, has_kst, has_mend);
+}
+
+// Launches the kernel of a route that was NOT refused, on its grid.
+inline hipError_t launch_sweep_kernel(hipStream_t st, const SweepRoute& r, const SweepArgs& s) {
+    const dim3 grid((unsigned)r.gx, (unsigned)r.gy, (unsigned)r.gz), block(256);
+    switch (r.id) {
+        // (in the order the compiler has always met the instantiations: the device code is emitted in it)
+        case SWEEP_GEMV_N_SHORT_TRI: hipLaunchKernelGGL((sweep_gemv_n_short<true>), grid, block, 0, st, s); break;
+        case SWEEP_GEMV_N_SHORT: hipLaunchKernelGGL((sweep_gemv_n_short<false>), grid, block, 0, st, s); break;
+        case SWEEP_GEMV_N4_TRI: hipLaunchKernelGGL((sweep_gemv_n4<true>), grid, block, 0, st, s); break;
+        case SWEEP_GEMV_N4: hipLaunchKernelGGL((sweep_gemv_n4<false>), grid, block, 0, st, s); break;
+        case SWEEP_GEMV_N_TRI: hipLaunchKernelGGL((sweep_gemv_n<true>), grid, block, 0, st, s); break;
+        case SWEEP_GEMV_N: hipLaunchKernelGGL((sweep_gemv_n<false>), grid, block, 0, st, s); break;
+        case SWEEP_GEMV_T32_TRI: hipLaunchKernelGGL((sweep_gemv_t<true, 32>), grid, block, 0, st, s); break;
+        case SWEEP_GEMV_T8_TRI: hipLaunchKernelGGL((sweep_gemv_t<true, 8>), grid, block, 0, st, s); break;
+        case SWEEP_GEMV_T16_TRI: hipLaunchKernelGGL((sweep_gemv_t<true, 16>), grid, block, 0, st, s); break;
+        case SWEEP_GEMV_T32: hipLaunchKernelGGL((sweep_gemv_t<false, 32>), grid, block, 0, st, s); break;
+        case SWEEP_GEMV_T8: hipLaunchKernelGGL((sweep_gemv_t<false, 8>), grid, block, 0, st, s); break;
+        case SWEEP_GEMV_T16: hipLaunchKernelGGL((sweep_gemv_t<false, 16>), grid, block, 0, st, s); break;
+        case SWEEP_MM_N: hipLaunchKernelGGL((sweep_mm<false, false>), grid, block, 0, st, s); break;
+        case SWEEP_MM_N_TRI: hipLaunchKernelGGL((sweep_mm<false, true>), grid, block, 0, st, s); break;
+        case SWEEP_MM_T: hipLaunchKernelGGL((sweep_mm<true, false>), grid, block, 0, st, s); break;
+        case SWEEP_MM_T_TRI: hipLaunchKernelGGL((sweep_mm<true, true>), grid, block, 0, st, s); break;
+        default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
+}
+
+inline hipError_t launch_sweep(hipStream_t st, bool trans, bool tri, int kp, const SweepArgs& s, int nprob) {
+    const SweepRoute r = sweep_route(trans, tri, kp, s.rows, s.kdim, nprob, s.narrow, s.kst != nullptr, s.mend != nullptr);
+    if (r.id == SWEEP_REFUSED) return hipErrorInvalidValue;      // (nothing launched: no rows or right-hand sides are dropped silently)
+    return launch_sweep_kernel(st, r, s);
 }
 
 }  // namespace gmrf

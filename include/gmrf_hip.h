@@ -933,6 +933,25 @@ gmrf_status gmrf_test_spmm_route(const gmrf_csr* S, const int64_t* geom, const v
 gmrf_status gmrf_test_spmm_rows_batch(const gmrf_csr* S, int64_t B, const double* vals, const double* X, int64_t ldx,
                                       int64_t x_stride, double* Y, int64_t ldy, int64_t y_stride, int64_t k, int32_t no_pad);
 
+/* The block sweep products (csrc/sweep.hpp: out = [b -] Mat x or Mat^T x, the step of every forward and backward sweep) as values.
+ * desc[17] = {trans, tri, kp, rows, kdim, nprob, narrow, kst set?, mend set?, ld, ldx, ldb, ldo, pMat, pXin, pBin, pOut}: the
+ * arguments of sweep_route, then the leading dimensions of the block, the input, the addend and the output, then the per-problem
+ * strides.  Kernel ids: 1 .. 4 sweep_mm<trans, tri> = <0,0>, <0,1>, <1,0>, <1,1>; 5 / 6 sweep_gemv_n<0 / 1>; 7 / 8
+ * sweep_gemv_n_short; 9 / 10 sweep_gemv_n4; 11 / 12 sweep_gemv_t<0 / 1, 8>; 13 / 14 sweep_gemv_t<., 16>; 15 / 16 sweep_gemv_t<., 32>;
+ * 0 = refused (the kernel cannot compute the shape; gmrf_last_error says why).
+ * gmrf_test_sweep_route: host only (no device).  out[4] = {id, grid x, y, z} of the kernel launch_sweep takes.
+ * gmrf_test_sweep_product: one product on host arrays.  Mat[nMat] and the panel P[nP] are uploaded whole and P is read back whole,
+ * so the caller sees what was written and what was left.  Xin = P + x_off, Bin = P + b_off (b_off < 0: no addend; b_off == o_off:
+ * in place), Out = P + o_off; kst / mend (or NULL): one entry per 64 rows.  force = 0: launch_sweep's own choice; force = id: that
+ * kernel, if the shape meets its own preconditions.  *route_out = the id that ran.  GMRF_ERR_BAD_SHAPE with nothing uploaded or
+ * launched: a refused route, an operand that does not fit its buffer, an odd ld / offset / stride under 16-byte loads, a kst / mend
+ * entry that is odd, out of range or leaves a sweep_mm K range that is no multiple of 8, outputs that overlap inputs, each other or
+ * another output's addend. */
+gmrf_status gmrf_test_sweep_route(const int64_t* desc, int64_t* out);
+gmrf_status gmrf_test_sweep_product(int32_t device, int32_t force, const int64_t* desc, const double* Mat, int64_t nMat, double* P,
+                                    int64_t nP, int64_t x_off, int64_t b_off, int64_t o_off, const int32_t* kst, int64_t n_kst,
+                                    const int32_t* mend, int64_t n_mend, int32_t* route_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,6 +16,7 @@ layout): pass `np.asfortranarray(B)` or a torch tensor of shape (k, n) via `.T`.
 from __future__ import annotations
 
 import ctypes as C
+import enum
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -23,6 +24,28 @@ import scipy.sparse as sp
 
 from . import _cabi
 from ._cabi import GmrfError, NotPositiveDefinite  # noqa: F401  (re-exported)
+
+
+class Switch(enum.IntFlag):
+    """The route switches of a factor handle (`TridiagonalCholeskyFactor.set_eager`): the GMRF_SW_* constants of
+    include/gmrf_hip.h one for one, where each is described.  The values are ABI."""
+    EAGER = 1 << 0
+    BATCH_ROUTES = 1 << 1
+    SWEEP_NO_GEMM = 1 << 2
+    DENSE_COUPLING = 1 << 3
+    FORK_GRAPH = 1 << 4
+    NO_STAIRCASE = 1 << 5
+    DOUBLING_INVERSE = 1 << 7
+    NO_LOOKAHEAD = 1 << 8
+    NO_XSPLIT = 1 << 12
+    NO_PERSIST = 1 << 13
+    NO_PERSIST_PANELS = 1 << 15
+    NO_SWEEP_PERSIST = 1 << 16
+    NO_SCATTER_FOLD = 1 << 17
+    TWO_CALL_POSTERIOR = 1 << 18
+    NO_FACTOR_FWD = 1 << 19
+    NO_GROUPED_GEMM = 1 << 20
+    NO_ENVELOPE = 1 << 21
 
 
 def _is_torch(x) -> bool:
@@ -1381,7 +1404,7 @@ class TridiagonalCholeskyFactor:
         samples (B, k, n) with the sample ids of `sample_batch` (problem p, sample s: first_id + p*k + s).  Where the samples'
         sweep runs on the GEMM (k <= 128, padded to a multiple of 64, enough tiles) and no output overlaps an input, the mean's
         backward sweep is the tail row of the samples' (one pass over the factor; samples' L^-T z bitwise `sample_batch`, the mean
-        at rounding level of `solve_batch`); else the call is `solve_batch` + `sample_batch`.  set_eager bit 18 keeps the latter."""
+        at rounding level of `solve_batch`); else the call is `solve_batch` + `sample_batch`.  `set_eager(Switch.TWO_CALL_POSTERIOR)` keeps the latter."""
         import torch
         B, n = self.batch, self.N
         b = b.reshape(B, n).contiguous()
@@ -1516,8 +1539,9 @@ class TridiagonalCholeskyFactor:
     def set_profiling(self, level: int):
         _cabi.check(self._lib.gmrf_bt_set_profiling(self._h, level))
 
-    def set_eager(self, eager: bool):
-        _cabi.check(self._lib.gmrf_bt_set_eager(self._h, int(eager)))
+    def set_eager(self, switches: int = 0):
+        """Select the handle's routes: the OR of any `Switch` members (0: every default route; True is `Switch.EAGER`)."""
+        _cabi.check(self._lib.gmrf_bt_set_eager(self._h, int(switches)))
 
     def synchronize(self):
         _cabi.check(self._lib.gmrf_bt_synchronize(self._h))

@@ -154,8 +154,7 @@ struct gmrf_handle : DevCtx {
     DevArr<int> d_env;
     DevArr<int> d_env_ken;
     bool env_ok = false;               // the arrays above describe the analysed pattern and the current layout
-    bool no_env = false;               // set_eager bit 21: no envelope bounds (comparison)
-    bool tw_half = false;              // a half of a twisted handle: never takes them
+    bool tw_half = false;              // a half of a twisted handle: never takes the envelope bounds
     DevArr<int> d_lo_rowptr;
     DevArr<int> d_dg_rowptr;          // [N][bsp + 1]: the diagonal blocks' entries row by row (absolute positions in d_keys)
     // tile plan of the sparse C = B X^T (spmm_bxt_tiles): per lower block and 64-row tile the distinct columns, per entry its index into them
@@ -164,7 +163,6 @@ struct gmrf_handle : DevCtx {
     int bxt_ecap = 0; int bxt_nrt = 0; bool bxt_plan_ok = false;        // [N][bsp + 1] row-wise view of the lower blocks' entry lists
     int64_t lo_row_max = 0;            // most entries in one row of a lower block
     bool sparse_b = false;             // lower blocks are sparse enough for C = B X^T by spmm_bxt
-    bool dense_g1 = false;             // force the dense GEMM for C = B X^T (comparison)
     // factor storage
     DevArr<double> d_L, d_C, d_Linv;   // ours, or the caller's (gmrf_bt_set_storage: borrowed, never freed)
     bool external_storage = false;
@@ -197,11 +195,11 @@ struct gmrf_handle : DevCtx {
     DevBuf mean_arena;                 // a host `mean` of gmrf_bt_sample, a host `out` of gmrf_bt_logdet_batch (Staging)
     DevArr<double> d_acc;              // variance accumulator / output ([problems][n])
     int32_t var_group = 0, var_groups = 0;   // the last batched sampled estimator: problems per group of the stage, groups per chunk (gmrf_test_var_groups)
+    // route switches: the last gmrf_bt_set_eager word, GMRF_SW_* of gmrf_hip.h (a half of a twisted handle beside another half
+    // also carries GMRF_SW_NO_SWEEP_PERSIST)
+    int32_t switches = 0;
+    bool sw(int32_t bit) const { return (switches & bit) != 0; }
     // graphs
-    bool eager = false;
-    bool split_step = false;           // use the three-launch panel step also for batch 1 (experiment)
-    bool sweep_no_gemm = false;        // keep 64-multiples of right-hand sides on sweep_mm (comparison)
-    bool no_fused_posterior = false;   // a batch's gmrf_bt_posterior = gmrf_bt_solve + gmrf_bt_sample (eager bit 18; comparison)
     bool tail_probe = false;           // gemm(tail): only check whether the product qualifies (posterior_fused_ok)
     bool tail_refused = false;         // ... one did not
     // The forward solve inside a batch's factorisation (round 7, gmrf_bt_set_factor_rhs): with the registered right-hand side b the
@@ -209,28 +207,20 @@ struct gmrf_handle : DevCtx {
     const double* frhs = nullptr;      // registered b (device, n x B, read at factor time)
     const double* fy_for = nullptr;    // the current factor left y = L^-1 fy_for in d_fy (nullptr: none)
     bool fwd_run = false;              // the factorisation being enqueued carries the forward solve (factor_fwd_ok)
-    bool no_factor_fwd = false;        // set_eager bit 19: never (comparison)
-    bool no_grouped_gemm = false;      // set_eager bit 20: the panel chain's two independent 128^3 products stay two launches (comparison)
     DevArr<GemmDirectOut> d_dout;      // where the fused posterior's last products write the caller's mean / samples (posterior_fused_ok allocates)
     DevArr<double> d_ft;               // [B][bsp]: t = b_i - C_i y_{i-1} of the block being factored, updated panel by panel
     DevArr<double> d_fy;               // [B][n_pad]: y, laid out as a k = 1 panel (what fill_normals_panel reads row kp from)
     const double* factor_graph_rhs = nullptr;   // b the captured factor graph reads (nullptr: it does not solve)
     unsigned long long* dbg_stamps = nullptr;   // test hook: phase stamps of the fused panel step
-    bool fork_graph = false;           // second branch in the captured factor graph (experiment, see potrf_block)
-    bool no_staircase = false;         // treat the coupling window as dense (comparison; takes effect at the next analysis)
-    bool doubling_x = false;           // one problem: assemble Linv by recursive doubling after the steps (comparison) instead of row by row inside them
     // Split representation of the block inverses (batches whose coupling blocks are zero left of column cmin >= 256):
     // with p = xsplit, a = [0, p), b = [p, bsp), the storage of Linv_i holds X_aa, X_bb and -- in the place of
     // X_ba = -X_bb L_ba X_aa -- the factor's own L_ba.  C_i = B_i Linv_{i-1}^T reads X_bb only; the sweeps apply
     // y_a = X_aa t_a, y_b = X_bb (t_b - L_ba y_a) (and the transposed order backward).  0: the full inverse.
     int xsplit = 0;                    // state of the stored factor
     int adopt_xsplit = 0;              // what the layout record of an adopted factor said (committed by gmrf_bt_adopt_commit)
-    bool no_xsplit = false;            // set_eager bit 12: always assemble the full inverse (comparison)
-    bool no_lookahead = false;         // one problem: every fused step re-factors its diagonal tile (comparison) instead of the look-ahead chain
     // One problem: the in-block Cholesky as ONE persistent launch per block / per 256-column panel (potrf_persist.hpp) instead of a
     // launch per 64-column step.  Needs every workgroup resident (1 + tiles <= CUs); a wait that gives up sets d_info[1], and
     // factor_finish then repeats the factorisation with the launch-per-step form and keeps it for this handle.
-    bool no_persist = false;           // set_eager bit 13
     bool persist_gave_up = false;      // a bounded wait inside a persistent launch gave up: this handle keeps the launch-per-step forms for good (set_eager cannot clear it)
     bool persist_launched = false;     // a persistent launch was enqueued since the abort word was last looked at
     int persist_cus = 0;               // CUs held of the device's budget (persist_plan); 0: no persistent launches
@@ -242,8 +232,6 @@ struct gmrf_handle : DevCtx {
     // One problem: a whole sweep as ONE persistent launch (sweep_persist.hpp) instead of two dependent launches per block.  Every
     // workgroup must be resident: the handle then claims the whole chip (persist_plan).  A wait that gives up sets the mapped host
     // word; gmrf_bt_solve / gmrf_bt_sample see it at their synchronisation and repeat the call with the launch-per-product form.
-    bool no_sweep_persist = false;     // set_eager bit 16
-    bool no_scatter_fold = false;      // set_eager bit 17: one problem keeps scatter_block as a launch of its own behind S = -C C^T (comparison)
     bool sweep_persist_planned = false;   // the claim covers the whole chip (persist_plan)
     bool sweep_persist_launched = false;  // such a launch was enqueued since the abort word was last looked at
     DevArr<unsigned> d_sweep_flags;       // [0] the device's abort word
@@ -252,7 +240,6 @@ struct gmrf_handle : DevCtx {
     int sweep_nw = 0;
     DevArr<double> d_P2, d_Y2, d_T2;      // gmrf_bt_posterior: the samples' panels (their sweep runs beside the mean's)
     bool sweep_persist_hold = false;      // this call must not use it (an input overlaps an output: a launch that gave up could not be repeated)
-    bool no_persist_panels = false;    // batches small enough for it keep potrf_diag128 + the 128^3 products instead of one persistent launch per panel (set_eager bit 15)
     // second branch of the captured factor graph: the inverse assembly of a block's first half runs
     // beside the panel chain of its second half (see potrf_block)
     hipStream_t aux = nullptr;
@@ -275,7 +262,6 @@ struct gmrf_handle : DevCtx {
     // one-problem sub-handles (TwistState); meet_req = -1: automatic
     int order = GMRF_ORDER_REFERENCE;
     int64_t meet_req = -1;
-    int32_t eager_bits = 0;            // last gmrf_bt_set_eager (handed on to the halves of a twisted handle)
     TwistState* tw = nullptr;
     // the top half of a twisted handle: block tw_blk is the meeting block, its Schur block also takes -HJ HJ^T (HJ = H_m J) and
     // its factorisation leaves W = L_m^-1 HJ (the meeting corrections of the sweeps).  -1: a plain handle.
@@ -526,7 +512,7 @@ static gmrf_status gemm_pair(gmrf_handle* h, const GemmCall& q0, const GemmCall&
         gemm_fill(h, c, g[i]);
         work[i] = c.pwork >= 0.0 ? c.pwork : gemm_flops(c.M, c.N, c.K, c.tri, c.lower_only, (double)h->B);
     }
-    if (h->no_grouped_gemm || !gemm_grouped_ok(g[0], g[1], (int)h->B)) {
+    if (h->sw(GMRF_SW_NO_GROUPED_GEMM) || !gemm_grouped_ok(g[0], g[1], (int)h->B)) {
         GCHK(gemm(h, q0));
         return gemm(h, q1);
     }
@@ -953,7 +939,7 @@ static gmrf_status upload_entries(gmrf_handle* h, const std::vector<std::vector<
     SymbolicPlan sp;
     // (tile groups for batches: one problem alone has too few workgroups as it is -- 48 chunks x 12 tiles = 576 of 768 slots -- and
     //  a third of them doing three tiles' rows each is slower: 7.1 -> 9.7 us per block on darcy256)
-    build_symbolic(N, h->bsp, dg, lo, h->no_staircase, sp, h->B >= 8);
+    build_symbolic(N, h->bsp, dg, lo, h->sw(GMRF_SW_NO_STAIRCASE), sp, h->B >= 8);
     h->diag_first = sp.diag_first; h->diag_count = sp.diag_count; h->low_first = sp.low_first; h->low_count = sp.low_count;
     const auto& keys = sp.keys; const auto& src = sp.src;
     GCHK(set_layout(h, sp.cmin, sp.rmax, sp.first));
@@ -1119,8 +1105,8 @@ enum PotrfRoute {
 };
 static int potrf_route(const gmrf_handle* h) {
     const int nt = (int)(h->bsp / 64);
-    if (h->B == 1 && !h->split_step) return nt <= 16 ? ROUTE_FUSED : ROUTE_BIG_ONE;
-    if (h->fork_graph && nt >= 8) return ROUTE_STEPS;
+    if (h->B == 1 && !h->sw(GMRF_SW_BATCH_ROUTES)) return nt <= 16 ? ROUTE_FUSED : ROUTE_BIG_ONE;
+    if (h->sw(GMRF_SW_FORK_GRAPH) && nt >= 8) return ROUTE_STEPS;
     return (nt >= 4 && nt % 4 == 0) ? ROUTE_PANELS256 : ROUTE_STEPS;
 }
 
@@ -1129,7 +1115,7 @@ static int potrf_route(const gmrf_handle* h) {
 // column nobody multiplies with.  p = the largest power of two <= cmin (the doubling tree splits at powers of two).
 static int planned_xsplit(const gmrf_handle* h) {
     const int bsp = (int)h->bsp, nt = bsp / 64;
-    if (h->no_xsplit || h->N <= 0 || nt < 8 || potrf_route(h) != ROUTE_PANELS256) return 0;
+    if (h->sw(GMRF_SW_NO_XSPLIT) || h->N <= 0 || nt < 8 || potrf_route(h) != ROUTE_PANELS256) return 0;
     int p = 256;
     while (2 * p <= (int)h->cmin) p *= 2;
     return (h->cmin >= 256 && p < bsp) ? p : 0;
@@ -1155,16 +1141,17 @@ static bool persist_budget_claim(std::map<const void*, int>& claims, const void*
     return true;
 }
 
-static int potrf_route(const gmrf_handle* h);
+// persistent launches are open to this handle: not switched off, and no launch of its own has given up
+static bool persist_allowed(const gmrf_handle* h) { return !h->sw(GMRF_SW_NO_PERSIST) && !h->persist_gave_up; }
 // CUs the widest persistent launch of this handle's next factorisation needs at once (0: its route launches none)
 static int persist_demand(const gmrf_handle* h) {
-    if (h->no_persist || h->persist_gave_up || h->cu_count <= 0 || h->bsp < 128 || h->fork_graph) return 0;
+    if (!persist_allowed(h) || h->cu_count <= 0 || h->bsp < 128 || h->sw(GMRF_SW_FORK_GRAPH)) return 0;
     const int nt = (int)(h->bsp / 64);
     int64_t wgs = 0;
     switch (potrf_route(h)) {
-        case 1 /* ROUTE_FUSED */: if (!h->no_lookahead && !h->doubling_x) wgs = 1 + persist_tiles(nt, 0, nt, 1); break;
-        case 2 /* ROUTE_BIG_ONE */: if (!h->no_lookahead) wgs = 1 + persist_tiles(nt, 0, std::min(nt, 4), 0); break;      // (the first panel is the widest)
-        case 3 /* ROUTE_PANELS256 */: if (!h->no_persist_panels) wgs = 1 + persist_tiles(4, 0, 4, 2); break;
+        case ROUTE_FUSED: if (!h->sw(GMRF_SW_NO_LOOKAHEAD) && !h->sw(GMRF_SW_DOUBLING_INVERSE)) wgs = 1 + persist_tiles(nt, 0, nt, 1); break;
+        case ROUTE_BIG_ONE: if (!h->sw(GMRF_SW_NO_LOOKAHEAD)) wgs = 1 + persist_tiles(nt, 0, std::min(nt, 4), 0); break;      // (the first panel is the widest)
+        case ROUTE_PANELS256: if (!h->sw(GMRF_SW_NO_PERSIST_PANELS)) wgs = 1 + persist_tiles(4, 0, 4, 2); break;
         default: break;
     }
     wgs *= h->B;
@@ -1173,7 +1160,7 @@ static int persist_demand(const gmrf_handle* h) {
 // One problem with blocks of 512 .. 1024: its sweeps run as one persistent launch each (sweep_persist.hpp), whose workgroups --
 // one per CU, up to 256 -- must all be resident: the handle then asks for the whole chip.  0: the sweeps keep a launch per product.
 static int sweep_persist_demand(const gmrf_handle* h) {
-    if (h->no_persist || h->no_sweep_persist || h->persist_gave_up || h->cu_count < 64 || h->B != 1) return 0;
+    if (!persist_allowed(h) || h->sw(GMRF_SW_NO_SWEEP_PERSIST) || h->cu_count < 64 || h->B != 1) return 0;
     if (!h->d_kst || !h->d_mend) return 0;             // (a handle that adopted a factor without analysing a pattern)
     if (h->bsp < 512 || h->bsp > SWEEP_PERSIST_XMAX || h->bsp % 64 != 0 || h->cmin % 16 != 0 || h->rmax % 16 != 0) return 0;      // (the bodies' tilings: 16 rows, 8 / 16 columns)
     return h->cu_count;
@@ -1220,7 +1207,7 @@ static void persist_give_up(gmrf_handle* h) {
 // between launches: the last workgroup out of a launch leaves them so).  false: the handle holds no claim that covers this
 // shape (it does not fit the chip beside the other handles' launches, or the form is switched off).
 static bool persist_fits(const gmrf_handle* h, int nt, int j0, int j1, int xrows) {
-    if (h->no_persist || h->persist_gave_up || h->persist_cus <= 0) return false;
+    if (!persist_allowed(h) || h->persist_cus <= 0) return false;
     // (a batch: every problem brings its own set of workgroups and flag words; all of them must fit the claim at once)
     return (int64_t)(1 + persist_tiles(nt, j0, j1, xrows)) * h->B <= h->persist_cus;
 }
@@ -1273,7 +1260,7 @@ static double env_units_upd(const int* host, int m3) {
 static EnvPanel env_panel(const gmrf_handle* h, int64_t i, int p, bool tail_rides) {
     const int nt = (int)(h->bsp / 64), np = nt / 4, m3 = nt - 4 * p - 4;
     EnvPanel e{nullptr, nullptr, nullptr, 10.0 * m3, 4.0 * (m3 * (m3 + 1) / 2)};
-    if (!h->env_ok || h->no_env || h->B <= 1 || h->tw || h->tw_half || h->tw_blk >= 0 || i < 0 || i >= h->N || p < 0 || p >= np || m3 <= 0) return e;
+    if (!h->env_ok || h->sw(GMRF_SW_NO_ENVELOPE) || h->B <= 1 || h->tw || h->tw_half || h->tw_blk >= 0 || i < 0 || i >= h->N || p < 0 || p >= np || m3 <= 0) return e;
     const size_t at = (size_t)((i * np + p) * 4) * nt;
     const unsigned char has = h->env_has[(size_t)(i * np + p)];
     const int* host = h->env_host.data() + at;
@@ -1358,11 +1345,11 @@ static gmrf_status potrf_block(gmrf_handle* h, double* S, double* L, double* X, 
     // chain of the second half.  Measured on darcy256: the branches do overlap (3.4 ms of a 42 ms
     // factor) but the two cross-queue dependencies per block cost as much, and with several handles
     // the extra streams share hardware queues (3 x 32: 22.6 k -> 19.3 k solves/s).  Off by default.
-    const bool overlap = h->capturing && h->fork_graph && nt >= 8;
+    const bool overlap = h->capturing && h->sw(GMRF_SW_FORK_GRAPH) && nt >= 8;
     if (overlap && !h->aux) HIPCHK(hipStreamCreateWithFlags(&h->aux, hipStreamNonBlocking));
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     if (overlap) { GCHK(fork_event(h, &ev_fork)); GCHK(fork_event(h, &ev_join)); }
-    if (fused && !h->no_lookahead && !h->doubling_x && !overlap && nt >= 2 && persist_fits(h, nt, 0, nt, 1)) {
+    if (fused && !h->sw(GMRF_SW_NO_LOOKAHEAD) && !h->sw(GMRF_SW_DOUBLING_INVERSE) && !overlap && nt >= 2 && persist_fits(h, nt, 0, nt, 1)) {
         // One problem, ONE launch per block: the look-ahead chain below with flags in place of its launch boundaries
         // (potrf_persist.hpp)
         const double t3 = 64.0 * 64.0 * 64.0;
@@ -1373,7 +1360,7 @@ static gmrf_status potrf_block(gmrf_handle* h, double* S, double* L, double* X, 
         }
         return launch_persist(h, S, L, X, nt, 0, nt, 1, blk_id, fl);
     }
-    if (fused && !h->no_lookahead && !h->doubling_x && !overlap && nt >= 2) {
+    if (fused && !h->sw(GMRF_SW_NO_LOOKAHEAD) && !h->sw(GMRF_SW_DOUBLING_INVERSE) && !overlap && nt >= 2) {
         // One problem, look-ahead chain (potrf_step, `lookahead`): tile 0 alone, then per step j ONE launch in which
         // workgroup 0 forms L[j+1,j], updates tile (j+1,j+1) in LDS and factors it for the next launch while the other
         // workgroups do panel + update of their tiles with the X_jj the previous launch left; the tiles of row j of
@@ -1436,7 +1423,7 @@ static gmrf_status potrf_block(gmrf_handle* h, double* S, double* L, double* X, 
         // (potrf_persist on the 4 x 4 tiles of the block, inverse rows included): 62 us instead of ~100 us per panel, on
         // 7 B CUs instead of B (C4 elliptic512 at batch 8: 8 of 256 CUs were busy in the diagonal chain).  Larger batches keep
         // the one-workgroup kernels: their chain hides behind the other problems, and 7 B workgroups of 140 KB would not fit.
-        const bool persist_panels = !h->no_persist_panels && persist_fits(h, 4, 0, 4, 2);
+        const bool persist_panels = !h->sw(GMRF_SW_NO_PERSIST_PANELS) && persist_fits(h, 4, 0, 4, 2);
         for (int j = 0; j < nt; j += 4) {
             const int64_t oa = (int64_t)j * 64, ob = oa + 128;
             if (persist_panels) {
@@ -1516,7 +1503,7 @@ static gmrf_status potrf_block(gmrf_handle* h, double* S, double* L, double* X, 
         const double rem = 64.0 * m, nb = (double)h->B;
         const double f_tile = 64.0 * 64.0 * 64.0 / 3.0 * nb, f_panel = rem * 64.0 * 64.0 * nb;
         const double f_upd = 2.0 * 64.0 * 64.0 * 64.0 * utiles * nb;
-        if (fused_in_panel && !h->no_lookahead && !overlap && j % pw == 0 && cend - j >= 2 && persist_fits(h, nt, j, cend, 0)) {
+        if (fused_in_panel && !h->sw(GMRF_SW_NO_LOOKAHEAD) && !overlap && j % pw == 0 && cend - j >= 2 && persist_fits(h, nt, j, cend, 0)) {
             // One problem, larger blocks: the panel's column tiles [j, cend) as ONE persistent launch (potrf_persist.hpp): the
             // look-ahead chain over the panel's own columns, the last column's rows below included (the launch's last-column
             // workgroups form them: `tail_panel`); the rank-256 update of the rest of the block (GEMM) follows as before
@@ -1534,7 +1521,7 @@ static gmrf_status potrf_block(gmrf_handle* h, double* S, double* L, double* X, 
         } else if (fused || m == 0) {
             // one problem, fused steps: the tiles of row j - 1 of the inverse ride in the launch of step j (4 workgroups
             // per tile on CUs the step leaves idle; see xrow_strip), the last row gets a launch of its own below
-            const bool xrows = fused && !h->doubling_x && !overlap && j >= 2;
+            const bool xrows = fused && !h->sw(GMRF_SW_DOUBLING_INVERSE) && !overlap && j >= 2;
             const int ntile_wg = 1 + m * (m + 1) / 2;
             sa.xrow = xrows ? j - 1 : -1; sa.xrow_first = ntile_wg;
             const int nx_wg = xrows ? 4 * (j - 1) : 0;
@@ -1581,7 +1568,7 @@ static gmrf_status potrf_block(gmrf_handle* h, double* S, double* L, double* X, 
             GCHK(st);
         }
     }
-    if (fused && !h->doubling_x && !overlap) {
+    if (fused && !h->sw(GMRF_SW_DOUBLING_INVERSE) && !overlap) {
         // the inverse was assembled row by row inside the step launches; its last row is what is left
         if (nt >= 2) {
             StepArgs sa;
@@ -1608,8 +1595,16 @@ static gmrf_status potrf_block(gmrf_handle* h, double* S, double* L, double* X, 
     return GMRF_OK;
 }
 
+// The coupling products C = B X^T of this handle's blocks run on spmm_bxt_tiles: sparse lower blocks, not forced onto the dense GEMM,
+// and a tile plan that covers the coupling rows.  (GMRF_BXT_TILES=0 keeps spmm_bxt: the tests' bitwise reference.)
+static bool coupling_on_tiles(const gmrf_handle* h) {
+    static const bool no_tiles = env_int("GMRF_BXT_TILES", 1) == 0;
+    return h->sparse_b && !h->sw(GMRF_SW_DENSE_COUPLING) && h->bxt_plan_ok && !no_tiles && h->bxt_nrt == (int)h->rmax / 64;
+}
+
 static gmrf_status factor_blocks_range(gmrf_handle* h, int64_t i0, int64_t i1) {
     const int bsp = (int)h->bsp;
+    const bool bxt_tiles = coupling_on_tiles(h);
     h->xsplit = planned_xsplit(h);                     // representation of the inverses this factorisation leaves
     const int64_t ld = bsp;
     const size_t blk_bytes = (size_t)bsp * bsp * sizeof(double) * (size_t)h->B;
@@ -1631,11 +1626,8 @@ static gmrf_status factor_blocks_range(gmrf_handle* h, int64_t i0, int64_t i1) {
             HIPCHK(hipGetLastError());
         }
         // (round 5: where the coupling product of this block runs on spmm_bxt_tiles, that launch zeroes the rows as well)
-        static const bool no_tiles_z = env_int("GMRF_BXT_TILES", 1) == 0;
-        const bool scatter_in_bxt = i > 0 && nb == 1 && h->sparse_b && !h->dense_g1 && h->bxt_plan_ok && !no_tiles_z && h->bxt_nrt == (int)h->rmax / 64
-                                    && h->d_dg_rowptr && h->bsp == h->bs && !h->no_scatter_fold;
-        const bool zero_in_bxt = scatter_in_bxt || (i > 0 && h->sparse_b && !h->dense_g1 && h->bxt_plan_ok && !no_tiles_z && h->bxt_nrt == (int)h->rmax / 64
-                                                    && ((int64_t)(bsp - rm_s) * bsp) % 2 == 0);
+        const bool scatter_in_bxt = i > 0 && nb == 1 && bxt_tiles && h->d_dg_rowptr && h->bsp == h->bs && !h->sw(GMRF_SW_NO_SCATTER_FOLD);
+        const bool zero_in_bxt = scatter_in_bxt || (i > 0 && bxt_tiles && ((int64_t)(bsp - rm_s) * bsp) % 2 == 0);
         if (rm_s < bsp && !zero_in_bxt) {
             const int64_t cnt = (int64_t)(bsp - rm_s) * bsp;
             hipLaunchKernelGGL(zero_rows, dim3((unsigned)((cnt / 2 + 255) / 256), nb), dim3(256), 0, h->stream,
@@ -1645,7 +1637,7 @@ static gmrf_status factor_blocks_range(gmrf_handle* h, int64_t i0, int64_t i1) {
         if (i > 0) {
             double* C = h->d_C + (i - 1) * cstride;              // stored window: rows 0 .. rm, columns cm ..
             const double* Xp = h->d_Linv + (i - 1) * bstride;
-            const bool sparse_g1 = h->sparse_b && !h->dense_g1;
+            const bool sparse_g1 = h->sparse_b && !h->sw(GMRF_SW_DENSE_COUPLING);
             if (!sparse_g1) {          // dense image of B for the GEMM route
                 HIPCHK(hipMemsetAsync(h->d_B, 0, blk_bytes, h->stream));
                 if (h->low_count[i] > 0) {
@@ -1672,8 +1664,7 @@ static gmrf_status factor_blocks_range(gmrf_handle* h, int64_t i0, int64_t i1) {
                 const dim3 grid((unsigned)((W / ba.cw) * rch * (int)nb));
                 // streamed bytes: C inside the staircase (written) + the rows of Linv from the first gathered column on (read)
                 ProfScope ps(h, 10, 8.0 * (h->c_streamed + 0.5 * (double)W * W) * (double)h->B);
-                static const bool no_tiles = env_int("GMRF_BXT_TILES", 1) == 0;      // (the tests' bitwise reference: spmm_bxt)
-                if (h->bxt_plan_ok && !no_tiles && h->bxt_nrt == rm / 64) {
+                if (bxt_tiles) {
                     BxtTileArgs ta;
                     ta.rowptr = ba.rowptr; ta.lidx = h->d_bxt_lidx; ta.vals = h->d_vals; ta.n_entries = h->n_entries;
                     ta.uptr = h->d_bxt_uptr + i * (h->bxt_nrt + 1); ta.ucols = h->d_bxt_ucols;
@@ -1778,7 +1769,7 @@ static std::mutex g_capture_mu;
 // handle leaves no y, and gmrf_bt_posterior runs its forward sweep.  Allocates d_ft / d_fy.
 static gmrf_status factor_fwd_ok(gmrf_handle* h, bool* ok) {
     *ok = false;
-    if (!h->frhs || h->no_factor_fwd || h->B <= 1 || tw_on(h) || h->tw_blk >= 0 || h->fork_graph || h->rmax <= 0) return GMRF_OK;
+    if (!h->frhs || h->sw(GMRF_SW_NO_FACTOR_FWD) || h->B <= 1 || tw_on(h) || h->tw_blk >= 0 || h->sw(GMRF_SW_FORK_GRAPH) || h->rmax <= 0) return GMRF_OK;
     const int bsp = (int)h->bsp, nt = bsp / 64;
     if (potrf_route(h) != ROUTE_PANELS256 || bsp % 256 != 0) return GMRF_OK;
     const size_t ye = (size_t)(h->B * h->n_pad), te = (size_t)(h->B * h->bsp);
@@ -1802,7 +1793,7 @@ static gmrf_status factor_fwd_ok(gmrf_handle* h, bool* ok) {
 }
 
 static gmrf_status run_factor(gmrf_handle* h, int64_t i0, int64_t i1) {
-    if (h->eager || h->profiling) { h->stats.persist_route = 0; return factor_blocks_range(h, i0, i1); }
+    if (h->sw(GMRF_SW_EAGER) || h->profiling) { h->stats.persist_route = 0; return factor_blocks_range(h, i0, i1); }
     const double* grhs = h->fwd_run ? h->frhs : nullptr;          // (the graph reads b, and the choice of launches depends on it)
     if (!h->factor_graph || h->factor_graph_i0 != i0 || h->factor_graph_i1 != i1 || h->factor_graph_rhs != grhs) {
         std::lock_guard<std::mutex> capture_lock(g_capture_mu);
@@ -1976,11 +1967,11 @@ static double sweep_bytes(const gmrf_handle* h, int64_t k) {
 
 // One problem: may this sweep run as one persistent launch?  (the claim is planned with the factorisation: persist_plan)
 static bool sweep_persist_ok(const gmrf_handle* h, int kp) {
-    if (!h->sweep_persist_planned || h->sweep_persist_hold || h->no_sweep_persist || h->no_persist || h->persist_gave_up || h->B != 1 || h->xsplit != 0) return false;
+    if (!h->sweep_persist_planned || h->sweep_persist_hold || h->sw(GMRF_SW_NO_SWEEP_PERSIST) || !persist_allowed(h) || h->B != 1 || h->xsplit != 0) return false;
     if (h->persist_cus < h->cu_count || sweep_persist_demand(h) <= 0) return false;
     if (kp != 1 && (kp % 16 != 0 || (int64_t)kp * h->n_pad * 8 >= ((int64_t)1 << 31))) return false;
     if (h->n_pad * 8 >= ((int64_t)1 << 31)) return false;
-    const bool via_gemm = (kp % 64 == 0) && !h->sweep_no_gemm && (int64_t)(h->bsp / 64) * (kp / 64) >= 128;
+    const bool via_gemm = (kp % 64 == 0) && !h->sw(GMRF_SW_SWEEP_NO_GEMM) && (int64_t)(h->bsp / 64) * (kp / 64) >= 128;
     return !via_gemm;
 }
 
@@ -2108,7 +2099,7 @@ static gmrf_status sweep_launches(gmrf_handle* h, bool backward, int kp, double*
     const double blk_work_t = ((kp == 1) ? 4.0 * bsp * (double)(bsp + 1) : 1.0 * bsp * (double)(bsp + 1) * kp) * nprob;
     // 64-multiples of right-hand sides go through the GEMM kernel (panel = the [m][k] operand) when
     // the batch gives it enough 64 x 64 tiles; a lone problem stays on sweep_mm (256 workgroups)
-    const bool via_gemm = (kp % 64 == 0) && !h->sweep_no_gemm && (int64_t)nprob * (bsp / 64) * (kp / 64) >= 128;
+    const bool via_gemm = (kp % 64 == 0) && !h->sw(GMRF_SW_SWEEP_NO_GEMM) && (int64_t)nprob * (bsp / 64) * (kp / 64) >= 128;
     if (tail && (!via_gemm || !backward)) return bad_shape("internal: the tail row needs the backward sweep on the GEMM");
     if (dout && !tail) return bad_shape("internal: direct output needs the tail-row sweep");
     for (int64_t step = 0; step < N; ++step) {
@@ -2162,7 +2153,7 @@ static gmrf_status sweep_launches(gmrf_handle* h, bool backward, int kp, double*
                         GCHK(gemm(h, GemmCall(false, false, kp, q, p, -1.0, 1.0).a(yout, npad, pPanel).b(Lba, ld, pX).c(rhs + p, npad, pPanel)));
                     else {
                         // (round 19) envelope: column tile bn of L_ba = L[256:, 0:256] is zero below row env_ken[bn] (gmrf_handle)
-                        const bool env = p == 256 && h->env_ok && !h->no_env && !h->tw && !h->tw_half && h->tw_blk < 0 && h->env_ken_has[(size_t)i];
+                        const bool env = p == 256 && h->env_ok && !h->sw(GMRF_SW_NO_ENVELOPE) && !h->tw && !h->tw_half && h->tw_blk < 0 && h->env_ken_has[(size_t)i];
                         double units = 0.0;
                         for (int bn = 0; env && bn < 4; ++bn) units += h->env_ken[(size_t)(i * 4 + bn)] / 64;
                         GCHK(gemm(h, GemmCall(false, true, kp, p, q, -1.0, 1.0).a(yout + p, npad, pPanel).b(Lba, ld, pX).c(rhs, npad, pPanel)
@@ -2213,7 +2204,7 @@ static gmrf_status run_sweeps(gmrf_handle* h, int mode, int kp) {
         h->stats.sweep_persist = 1;
         h->stats.sweep_persist_launches += (mode == GMRF_SOLVE_FULL) ? 2 : 1;
     }
-    if (h->eager || h->profiling) return body();
+    if (h->sw(GMRF_SW_EAGER) || h->profiling) return body();
     const int64_t key = ((int64_t)h->xsplit << 32) | ((int64_t)mode * 4096 + kp) |       // (the representation decides the launches)
                         (persistent ? ((int64_t)1 << 60) : 0);
     auto it = h->sweep_graphs.find(key);
@@ -2377,32 +2368,25 @@ gmrf_status gmrf_bt_set_profiling(gmrf_handle* h, int32_t level) {
     return GMRF_OK;
 }
 
+// The switches whose change leaves the captured graphs holding other launches than the next capture would record: every live one
+// but GMRF_SW_EAGER (the graphs stay good, they are just not replayed), GMRF_SW_NO_STAIRCASE (takes effect at the next analysis,
+// which drops them itself), GMRF_SW_TWO_CALL_POSTERIOR (chooses which calls a posterior makes, outside any graph) and
+// GMRF_SW_NO_FACTOR_FWD (the factor graph is kept per right-hand side: factor_graph_rhs).
+static const int32_t SW_DROP_GRAPHS =
+    GMRF_SW_BATCH_ROUTES | GMRF_SW_SWEEP_NO_GEMM | GMRF_SW_DENSE_COUPLING | GMRF_SW_FORK_GRAPH | GMRF_SW_DOUBLING_INVERSE | GMRF_SW_NO_LOOKAHEAD
+    | GMRF_SW_NO_XSPLIT | GMRF_SW_NO_PERSIST | GMRF_SW_NO_PERSIST_PANELS | GMRF_SW_NO_SWEEP_PERSIST | GMRF_SW_NO_SCATTER_FOLD
+    | GMRF_SW_NO_GROUPED_GEMM | GMRF_SW_NO_ENVELOPE;
+
 gmrf_status gmrf_bt_set_eager(gmrf_handle* h, int32_t eager) {
     if (!h) return bad_shape("null handle");
-    if (((eager & 2) != 0) != h->split_step) { destroy_graphs(h); h->split_step = (eager & 2) != 0; }
-    if (((eager & 4) != 0) != h->sweep_no_gemm) { destroy_graphs(h); h->sweep_no_gemm = (eager & 4) != 0; }
-    if (((eager & 8) != 0) != h->dense_g1) { destroy_graphs(h); h->dense_g1 = (eager & 8) != 0; }
-    if (((eager & 16) != 0) != h->fork_graph) { destroy_graphs(h); h->fork_graph = (eager & 16) != 0; }
-    h->no_staircase = (eager & 32) != 0;
-    if (((eager & 128) != 0) != h->doubling_x) { destroy_graphs(h); h->doubling_x = (eager & 128) != 0; }
-    if (((eager & 256) != 0) != h->no_lookahead) { destroy_graphs(h); h->no_lookahead = (eager & 256) != 0; }
-    if (((eager & 4096) != 0) != h->no_xsplit) { destroy_graphs(h); h->no_xsplit = (eager & 4096) != 0; }
-    if (((eager & 8192) != 0) != h->no_persist) { destroy_graphs(h); h->no_persist = (eager & 8192) != 0; }
-    if (((eager & 32768) != 0) != h->no_persist_panels) { destroy_graphs(h); h->no_persist_panels = (eager & 32768) != 0; }
-    if (((eager & 65536) != 0) != h->no_sweep_persist) { destroy_graphs(h); h->no_sweep_persist = (eager & 65536) != 0; }
-    if (((eager & 131072) != 0) != h->no_scatter_fold) { destroy_graphs(h); h->no_scatter_fold = (eager & 131072) != 0; }
-    h->no_fused_posterior = (eager & 262144) != 0;
-    h->no_factor_fwd = (eager & 524288) != 0;
-    if (((eager & 1048576) != 0) != h->no_grouped_gemm) { destroy_graphs(h); h->no_grouped_gemm = (eager & 1048576) != 0; }
-    if (((eager & 2097152) != 0) != h->no_env) { destroy_graphs(h); h->no_env = (eager & 2097152) != 0; }
-    if (eager != h->eager_bits) h->fy_for = nullptr;         // (a factor of other settings: no y taken for granted)
-    h->eager = (eager & 1) != 0;
-    h->eager_bits = eager;
+    if ((eager ^ h->switches) & SW_DROP_GRAPHS) destroy_graphs(h);
+    if (eager != h->switches) h->fy_for = nullptr;         // (a factor of other settings: no y taken for granted)
+    h->switches = eager;
     if (h->tw)
         for (gmrf_handle* s : {h->tw->top, h->tw->bot})
             if (s) {
                 GCHK(gmrf_bt_set_eager(s, eager));
-                if (h->tw->bot) s->no_sweep_persist = true;       // (the halves of a twisted handle never take the persistent sweep)
+                if (h->tw->bot) s->switches |= GMRF_SW_NO_SWEEP_PERSIST;       // (two halves never take the persistent sweep)
             }
     return GMRF_OK;
 }
@@ -3317,11 +3301,11 @@ static gmrf_status posterior_beside(gmrf_handle* h, const double* b, uint64_t se
 }
 
 // A batch's posterior with the mean's backward sweep carried in the samples' (round 6): may it run fused?  Batches only (B > 1),
-// k <= 128 with kp = pad_k(k) a multiple of 64 on the GEMM route of the sweeps, device pointers, not switched off (eager bit 18),
+// k <= 128 with kp = pad_k(k) a multiple of 64 on the GEMM route of the sweeps, device pointers, not switched off (GMRF_SW_TWO_CALL_POSTERIOR),
 // and every product of the backward sweep on the 64 x 64 LDS-DMA tile that takes the tail row (a dry run of the sweep asks).
 // Needs the panels of kp + 1 rows (ensure_panels).
 static bool posterior_fused_ok(gmrf_handle* h, int64_t k, bool dev_all) {
-    if (tw_on(h) || h->B <= 1 || !dev_all || h->no_fused_posterior || h->sweep_no_gemm || k <= 0 || k > KP_CHUNK) return false;
+    if (tw_on(h) || h->B <= 1 || !dev_all || h->sw(GMRF_SW_TWO_CALL_POSTERIOR) || h->sw(GMRF_SW_SWEEP_NO_GEMM) || k <= 0 || k > KP_CHUNK) return false;
     const int kp = pad_k(k);
     if (kp % 64 != 0 || (int64_t)h->B * (h->bsp / 64) * (kp / 64) < 128) return false;
     if ((int64_t)(kp + 1) * h->n_pad * 8 >= ((int64_t)1 << 32)) return false;
@@ -6195,7 +6179,7 @@ static void tw_free(gmrf_handle* h) {
 
 static gmrf_status tw_new_half(gmrf_handle* h, hipStream_t st, gmrf_handle** out) {
     GCHK(gmrf_bt_create(h->device, (void*)st, out));
-    GCHK(gmrf_bt_set_eager(*out, h->eager_bits));
+    GCHK(gmrf_bt_set_eager(*out, h->switches));
     (*out)->profiling = h->profiling;
     (*out)->tw_half = true;
     return GMRF_OK;
@@ -6235,7 +6219,7 @@ static gmrf_status tw_analyze(gmrf_handle* h, int64_t n, int64_t N, const int64_
     if (m < 0 || m < N - 1) {
         if (!t->bot) { GCHK(ensure_aux(h)); GCHK(tw_new_half(h, h->aux, &t->bot)); }
         // the halves never take the persistent sweep: it needs every CU while the other half runs
-        t->top->no_sweep_persist = t->bot->no_sweep_persist = true;
+        for (gmrf_handle* s : {t->top, t->bot}) s->switches |= GMRF_SW_NO_SWEEP_PERSIST;
     }
     if (m < 0) {
         // automatic: which half's in-block Cholesky is the persistent form decides the balance (the CU budget holds one
@@ -6251,7 +6235,7 @@ static gmrf_status tw_analyze(gmrf_handle* h, int64_t n, int64_t N, const int64_
         m = tw_auto_meet(N, t->top->persist_cus > 0, t->bot->persist_cus > 0);
     }
     if (m == N - 1 && t->bot) { (void)gmrf_bt_destroy(t->bot); t->bot = nullptr; }
-    if (!t->bot) t->top->no_sweep_persist = h->no_sweep_persist;
+    if (!t->bot) t->top->switches = h->switches;       // (the handle IS its top half: its own GMRF_SW_NO_SWEEP_PERSIST again)
     t->m = m; t->N = N; t->n = n; t->bs = bs; t->nnz = colptr[n] - base;
     const int64_t nnz = t->nnz;
     {   // top: blocks 0 .. m as they are
@@ -7220,12 +7204,12 @@ gmrf_status gmrf_test_potrf_block(int32_t device, int64_t bs, double* S, double*
     return s;
 }
 
-// potrf_block once, on whichever route a handle of this shape takes: N = 1, `batch` problems, set_eager(eager_bits), keep_l, a
+// potrf_block once, on whichever route a handle of this shape takes: N = 1, `batch` problems, set_eager(switches), keep_l, a
 // coupling window that starts at cmin (what planned_xsplit looks at).  S, L, Linv: host, [batch][bs][bs]; all three are uploaded
 // whole (so the caller decides what the kernels find where they do not write) and L, Linv are read back whole.  info: the info
 // word as the kernels left it (0, or 1 + problem).  route[4] = {potrf_route, stats.persist_route, xsplit, persistent waits that
 // gave up}.  Launches what the factorisation launches and nothing else; no stamps, no forward solve.
-gmrf_status gmrf_test_potrf_route(int32_t device, int64_t bs, int32_t batch, int32_t eager_bits, int64_t cmin, int32_t keep_l,
+gmrf_status gmrf_test_potrf_route(int32_t device, int64_t bs, int32_t batch, int32_t switches, int64_t cmin, int32_t keep_l,
                                   double* S, double* L, double* Linv, int32_t* info, int32_t* route) {
     if (!S || !L || !Linv || !info || !route) return bad_shape("null pointer");
     if (bs < 64 || bs % 64 || next_pow2(bs / 64) != bs / 64) return bad_shape("bs must be 64 * 2^p");
@@ -7235,7 +7219,7 @@ gmrf_status gmrf_test_potrf_route(int32_t device, int64_t bs, int32_t batch, int
     GCHK(gmrf_bt_create(device, nullptr, &h));
     h->N = 1; h->n = bs; h->bs = bs; h->bsp = bs; h->n_pad = bs; h->B = batch;
     h->keep_l = keep_l != 0;
-    gmrf_status s = gmrf_bt_set_eager(h, eager_bits);
+    gmrf_status s = gmrf_bt_set_eager(h, switches);
     if (s == GMRF_OK) s = set_layout(h, cmin, bs, std::vector<int64_t>((size_t)(bs / 64), cmin));
     if (s == GMRF_OK) s = alloc_factor(h);
     if (s == GMRF_OK) {

@@ -172,7 +172,7 @@ gmrf_status gmrf_bt_sample(gmrf_handle* h, uint64_t seed, int64_t first_id, int6
  * them) whose samples' sweep runs on the GEMM (k <= 128 padded to a multiple of 64, B * bsp / 64 * kp / 64 >= 128, device
  * pointers) makes ONE backward pass over the factor for both: the mean's backward sweep is the tail row of every product of the
  * samples' (kp + 1 panel rows); its samples' L^-T z are the same bits as gmrf_bt_sample's, its mean agrees with gmrf_bt_solve's to
- * rounding (summed by another kernel), stats.solve_ms = the whole call, stats.sample_ms = 0.  set_eager bit 18 keeps the two calls.
+ * rounding (summed by another kernel), stats.solve_ms = the whole call, stats.sample_ms = 0.  set_eager bit 18 (GMRF_SW_TWO_CALL_POSTERIOR) keeps the two calls.
  * If two of b, mean, samples overlap the call IS the two calls (each with its own guard against overlap). */
 gmrf_status gmrf_bt_posterior(gmrf_handle* h, const double* b, uint64_t seed, int64_t first_id, int64_t k,
                               double* mean, double* samples, int64_t ld);
@@ -183,7 +183,7 @@ gmrf_status gmrf_bt_posterior(gmrf_handle* h, const double* b, uint64_t seed, in
  * the factor; a fused gmrf_bt_posterior with this same pointer then skips its forward sweep (the mean agrees with the swept one
  * to rounding).  Whatever b holds when gmrf_bt_posterior runs, the mean is that of b as the factorisation read it.  Any other way
  * to a factor (ranges, adopt, import), a set_eager change, another b or b == NULL leaves no y: the forward sweep runs as before.
- * set_eager bit 19 switches the forward solve inside the factorisation off. */
+ * set_eager bit 19 (GMRF_SW_NO_FACTOR_FWD) switches the forward solve inside the factorisation off. */
 gmrf_status gmrf_bt_set_factor_rhs(gmrf_handle* h, const double* b);
 
 /* The N(0,1) draws gmrf_bt_sample would use (for tests and for callers that need z). */
@@ -411,28 +411,27 @@ gmrf_status gmrf_bt_half_stats(gmrf_handle* h, int32_t half, gmrf_stats* out);
 
 gmrf_status gmrf_bt_stats(gmrf_handle* h, gmrf_stats* out);
 gmrf_status gmrf_bt_set_profiling(gmrf_handle* h, int32_t level);
-/* bit 0: plain stream launches instead of replaying captured HIP graphs; bit 1: three-launch
- * panel step also for batch 1; bit 2: keep 64-multiples of right-hand sides on sweep_mm;
- * bit 3: C = B X^T by the dense GEMM even when the lower blocks are sparse; bit 4: second
- * branch in the captured factor graph (inverse assembly beside the panel chain; experiment); bit 5:
- * ignore the staircase of the coupling blocks (dense window; takes effect at the next factor_csc); bit 7:
- * one problem assembles Linv by recursive doubling after the panel steps instead of row by row inside them; bit 8:
- * one problem re-factors the diagonal tile in every workgroup of a step instead of the look-ahead chain;
- * bit 12: batches always assemble the full block inverses (no split representation; comparison); bit 13: no persistent
- * launches (potrf_persist) -- the launch-per-step forms; bit 15: small batches keep potrf_diag128 + the 128^3 products
- * instead of one persistent launch per panel diagonal block; bit 16: one problem's sweeps keep one launch per product
- * instead of ONE persistent launch per sweep (sweep_persist; comparison -- bit 13 switches both persistent forms off); bit 17: one problem
- * keeps scatter_block (S += D_i) as a launch of its own behind S = -C C^T instead of zero + scatter inside the spmm_bxt_tiles launch and an
- * accumulating product (comparison; same bits); bit 18: a batch's gmrf_bt_posterior is gmrf_bt_solve + gmrf_bt_sample (the mean's
- * backward sweep a pass of its own) instead of the fused pass that sweeps the mean as the tail row of the samples' GEMMs
- * (comparison; the samples' L^-T z rows are the same bits, the mean agrees to rounding); bit 19: factorisations do not solve for the
- * right-hand side of gmrf_bt_set_factor_rhs (comparison: the posterior's forward sweep runs); bit 20: the two independent 128^3
- * products of a 256-column panel's diagonal chain (S_BB -= L_BA L_BA^T and T = L_BA X_A) stay two launches instead of ONE launch of
- * gemm_f64_dma_grouped (comparison; same bits); bit 21: the batched factorisation's panel products and rank-256 updates, and the
- * backward sweep's L_ba^T product, run over their whole K ranges instead of skipping the 64-wide K units outside the blocks'
- * envelope (comparison; same bits).
- * (Bits 6, 9, 10, 11, 14 selected comparison routes that lost twice -- left-looking panels, in-panel updates on the GEMM kernel,
- * rank-64 panel steps of batches, 128-column panels, potrf_panel256 -- and were removed with them in round 5; they are ignored.) */
+/* The route switches of a handle: gmrf_bt_set_eager takes the OR of any of them (0: every default route).  The values are ABI. */
+enum {
+    GMRF_SW_EAGER              = 1 << 0,    /* plain stream launches instead of replaying captured HIP graphs */
+    GMRF_SW_BATCH_ROUTES       = 1 << 1,    /* the three-launch panel step (the batches' in-block routes) also for batch 1 (experiment) */
+    GMRF_SW_SWEEP_NO_GEMM      = 1 << 2,    /* keep 64-multiples of right-hand sides on sweep_mm */
+    GMRF_SW_DENSE_COUPLING     = 1 << 3,    /* C = B X^T by the dense GEMM even when the lower blocks are sparse */
+    GMRF_SW_FORK_GRAPH         = 1 << 4,    /* second branch in the captured factor graph: inverse assembly beside the panel chain (experiment) */
+    GMRF_SW_NO_STAIRCASE       = 1 << 5,    /* ignore the staircase of the coupling blocks: dense window; takes effect at the next factor_csc */
+    GMRF_SW_DOUBLING_INVERSE   = 1 << 7,    /* one problem assembles Linv by recursive doubling after the panel steps, not row by row inside them */
+    GMRF_SW_NO_LOOKAHEAD       = 1 << 8,    /* one problem re-factors the diagonal tile in every workgroup of a step instead of the look-ahead chain */
+    GMRF_SW_NO_XSPLIT          = 1 << 12,   /* batches always assemble the full block inverses: no split representation (comparison) */
+    GMRF_SW_NO_PERSIST         = 1 << 13,   /* no persistent launches (potrf_persist, sweep_persist): the launch-per-step / per-product forms */
+    GMRF_SW_NO_PERSIST_PANELS  = 1 << 15,   /* small batches keep potrf_diag128 + the 128^3 products instead of one persistent launch per panel diagonal block */
+    GMRF_SW_NO_SWEEP_PERSIST   = 1 << 16,   /* one problem's sweeps keep one launch per product instead of ONE persistent launch per sweep (comparison) */
+    GMRF_SW_NO_SCATTER_FOLD    = 1 << 17,   /* one problem keeps scatter_block (S += D_i) a launch of its own behind S = -C C^T, not folded into spmm_bxt_tiles (comparison; same bits) */
+    GMRF_SW_TWO_CALL_POSTERIOR = 1 << 18,   /* a batch's gmrf_bt_posterior is gmrf_bt_solve + gmrf_bt_sample, not the fused pass (comparison; samples the same bits, mean to rounding) */
+    GMRF_SW_NO_FACTOR_FWD      = 1 << 19,   /* factorisations do not solve for the right-hand side of gmrf_bt_set_factor_rhs: the posterior's forward sweep runs (comparison) */
+    GMRF_SW_NO_GROUPED_GEMM    = 1 << 20,   /* a 256-column panel's two independent 128^3 products stay two launches, not ONE of gemm_f64_dma_grouped (comparison; same bits) */
+    GMRF_SW_NO_ENVELOPE        = 1 << 21    /* batched panel products, rank-256 updates and the backward L_ba^T product run their whole K ranges, no envelope skip (comparison; same bits) */
+};
+/* (Bits 6, 9, 10, 11 and 14 selected comparison routes that were removed in round 5; they are retired and ignored.) */
 gmrf_status gmrf_bt_set_eager(gmrf_handle* h, int32_t eager);
 gmrf_status gmrf_bt_synchronize(gmrf_handle* h);
 
@@ -653,7 +652,7 @@ gmrf_status gmrf_assemble_quadform_batch(gmrf_assembler* as, int64_t batch, cons
  * observations (NULL = 0); steps_out [B]; obj_hist_out [B][max_steps + 1] (slot 0: the start point; slots no step reached: NaN).
  * GMRF_ERR_NOT_SPD in any problem ends the run (`info`: the failing block, as gmrf_bt_refactor_values reports it); x then holds
  * the last complete iterate of every problem and steps_out says which.  The run's right-hand sides are registered with
- * gmrf_bt_set_factor_rhs for its duration (the caller's registration is put back); set_eager bit 19 switches that route off.
+ * gmrf_bt_set_factor_rhs for its duration (the caller's registration is put back); GMRF_SW_NO_FACTOR_FWD switches that route off.
  * gmrf_gn_finalize: tangent at the final x, assemble, re-factor -- the handle then holds the factor of
  * Q + noise J(x)' J(x) of every problem (x_final of solve_burgers_gmrf-fem.jl:184-193) for posterior / sample / variance calls. */
 typedef struct gmrf_gn gmrf_gn;
@@ -694,7 +693,7 @@ gmrf_status gmrf_gn_posterior(gmrf_gn* g, const double* z, int64_t first, int64_
  * factored the assembler's pattern once (GMRF_ERR_NO_FACTOR before).  One call, on the handle's stream:
  *     ic [B][ns] -> bulk, Q_ic's values, Qx_prior -> Q_ic on the assembler's pattern (its J'J entries 0) -> Qx_prior registered with
  *     gmrf_bt_set_factor_rhs for the run (the caller's registration is put back) -> gmrf_bt_refactor_values -> x_ic = Q_ic^-1 Qx_prior
- *     (the backward sweep alone where the factorisation carried the forward one; set_eager bit 19 switches that off).
+ *     (the backward sweep alone where the factorisation carried the forward one; GMRF_SW_NO_FACTOR_FWD switches that off).
  * x_ic [B][n] is mean(x_ic) of :172-179: prior mean and start point of gmrf_gn_run, with q_values_out as its q_nzval and qx_out
  * (= Q_ic x_ic) as its qx_prior.  ic, x_ic_out: host or device; q_values_out [B][nnz(Q)], qx_out [B][n], bulk_out [B]: NULL (not
  * wanted), host or device.  GMRF_ERR_NOT_SPD ends the call with `info` as gmrf_bt_refactor_values sets it and leaves the outputs
@@ -863,14 +862,14 @@ gmrf_status gmrf_test_tile_timing(double* out, int32_t n);
 gmrf_status gmrf_test_potrf_block(int32_t device, int64_t bs, double* S /* in/out: L */,
                                   double* Linv, int32_t* info);
 /* The in-block Cholesky (potrf_block) once, on the route a handle of this shape takes: one block per problem, `batch` problems,
- * gmrf_bt_set_eager(eager_bits), gmrf_bt_set_keep_l(keep_l), a coupling window that starts at column cmin (a multiple of 64 in
+ * gmrf_bt_set_eager(switches), gmrf_bt_set_keep_l(keep_l), a coupling window that starts at column cmin (a multiple of 64 in
  * [0, bs): what decides the split inverse).  bs = 64 * 2^p.  S, L, Linv: host, [batch][bs][bs] row-major; all three are uploaded
  * whole and L, Linv read back whole, so the caller sees what the kernels wrote and what they left.  *info: 0, or 1 + the index of a
  * problem with a non-positive pivot.  route[4]: the route (1 fused, 2 big one-problem, 3 256-column panels, 4 steps),
  * gmrf_stats.persist_route of the launches (0 none, 1 block, 2 panel, 3 diagonal block of a batch), the split p of the inverse
  * (0: full), and the number of persistent waits that gave up.  Bad arguments: GMRF_ERR_BAD_SHAPE, nothing launched.
  * tests/potrf_ref.py states the contract of the three buffers. */
-gmrf_status gmrf_test_potrf_route(int32_t device, int64_t bs, int32_t batch, int32_t eager_bits, int64_t cmin, int32_t keep_l,
+gmrf_status gmrf_test_potrf_route(int32_t device, int64_t bs, int32_t batch, int32_t switches, int64_t cmin, int32_t keep_l,
                                   double* S, double* L, double* Linv, int32_t* info, int32_t* route);
 /* s_memtime stamps of the chain workgroup of the last gmrf_test_potrf_block that took the persistent form
  * (csrc/potrf_persist.hpp): out[0] = tile 0 done, then eight per step (tools/persist_stamps.py names them); cycles relative to out[0], -1 = not written. */

@@ -31,7 +31,7 @@ F.refactor(w.Q.data)                       # the handle keeps the launch-per-ste
 out["single_aborts_after_second"] = aborts(F)
 mu2 = pkg.ldiv(F, w.rhs)
 Fs = pkg.TridiagonalCholeskyFactor()
-Fs.set_eager(8192)                         # the launch-per-step form up front
+Fs.set_eager(pkg.Switch.NO_PERSIST)                         # the launch-per-step form up front
 Fs.factor(w.Q, w.n_blocks)
 out["single_aborts_of_the_step_form"] = aborts(Fs)
 out["single_equal"] = bool(np.array_equal(mu, pkg.ldiv(Fs, w.rhs)) and np.array_equal(mu, mu2)
@@ -39,13 +39,13 @@ out["single_equal"] = bool(np.array_equal(mu, pkg.ldiv(Fs, w.rhs)) and np.array_
 out["single_logdet_equal"] = bool(F.logdet() == Fs.logdet())
 keys = ("persist_aborts", "persist_route", "persist_cus", "persist_refused")
 out["single_stats"] = {k: F.stats()[k] for k in keys}
-F.set_eager(0); F.refactor(w.Q.data)       # (bit 13 clear: a handle that gave a persistent launch up does not get the form back)
+F.set_eager(0); F.refactor(w.Q.data)       # (NO_PERSIST clear: a handle that gave a persistent launch up does not get the form back)
 out["single_after_set_eager_0"] = {k: F.stats()[k] for k in keys}
 # stepwise (the shared-factor job): every range is packed right after its step, as HipEngine.share_range does
 import torch
 Fp = pkg.TridiagonalCholeskyFactor()
 Fp.factor_begin(w.Q, w.n_blocks)
-Fq = pkg.TridiagonalCholeskyFactor(); Fq.set_eager(8192)
+Fq = pkg.TridiagonalCholeskyFactor(); Fq.set_eager(pkg.Switch.NO_PERSIST)
 Fq.factor_begin(w.Q, w.n_blocks)
 same = True
 for i0 in range(0, w.n_blocks, 4):
@@ -69,7 +69,7 @@ Fb = pkg.TridiagonalCholeskyFactor(batch=2).factor(w.Q, w.n_blocks, values=vals)
 out["batch_aborts"] = aborts(Fb)
 xb = Fb.solve_batch(rhs[:, None, :])
 Fd = pkg.TridiagonalCholeskyFactor(batch=2)
-Fd.set_eager(8192)                         # persistent launches off: potrf_diag128 + GEMM
+Fd.set_eager(pkg.Switch.NO_PERSIST)                         # persistent launches off: potrf_diag128 + GEMM
 Fd.factor(w.Q, w.n_blocks, values=vals)
 out["batch_equal"] = bool(np.array_equal(xb, Fd.solve_batch(rhs[:, None, :])))
 Fb.select_problem(1); Fd.select_problem(1)

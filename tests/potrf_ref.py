@@ -64,6 +64,8 @@ from dataclasses import dataclass
 
 import numpy as np
 
+import __graft_entry__
+
 U = 2.0 ** -53
 LD = np.longdouble
 LONGDOUBLE_OK = bool(np.finfo(np.longdouble).eps <= 2.0 ** -63)
@@ -71,8 +73,9 @@ SLACK = 1.0 + 2.0 ** -20
 
 ROUTE_FUSED, ROUTE_BIG_ONE, ROUTE_PANELS256, ROUTE_STEPS = 1, 2, 3, 4
 ROUTE_NAMES = {1: "fused", 2: "big_one", 3: "panels256", 4: "steps"}
-BIT_BATCH_ROUTES, BIT_FORK, BIT_DOUBLING, BIT_NO_LOOKAHEAD = 2, 16, 128, 256
-BIT_NO_XSPLIT, BIT_NO_PERSIST, BIT_NO_PERSIST_PANELS = 4096, 8192, 32768
+_SW = __graft_entry__.load_package().Switch         # (plain ints: the cases' ids and records carry numbers)
+BIT_BATCH_ROUTES, BIT_FORK, BIT_DOUBLING, BIT_NO_LOOKAHEAD = int(_SW.BATCH_ROUTES), int(_SW.FORK_GRAPH), int(_SW.DOUBLING_INVERSE), int(_SW.NO_LOOKAHEAD)
+BIT_NO_XSPLIT, BIT_NO_PERSIST, BIT_NO_PERSIST_PANELS = int(_SW.NO_XSPLIT), int(_SW.NO_PERSIST), int(_SW.NO_PERSIST_PANELS)
 FAMILIES = ("dominant", "graded", "lattice", "spectrum")
 SCALES = (1.0, 1e-3, 1e6, 1e-5, 1e2)
 CUS = 256                         # compute units of the device the routes are planned for

@@ -26,7 +26,7 @@ F.refactor(w.Q.data)                                    # ... and its factorisat
 out["route_after_refactor"] = int(F.stats()["persist_route"])
 mu2 = pkg.ldiv(F, rhs)
 G = pkg.TridiagonalCholeskyFactor()
-G.set_eager(65536)                                      # a launch per product up front
+G.set_eager(pkg.Switch.NO_SWEEP_PERSIST)                                      # a launch per product up front
 G.factor(w.Q, w.n_blocks)
 mu_g = pkg.ldiv(G, rhs)
 X_g = G.sample(16, mean=mu_g, seed=11, like=rhs)
@@ -93,7 +93,7 @@ cases = {
     "posterior_b_in_samples": posterior_b_in_samples,
 }
 G = pkg.TridiagonalCholeskyFactor()
-G.set_eager(65536)
+G.set_eager(pkg.Switch.NO_SWEEP_PERSIST)
 G.factor(w.Q, w.n_blocks)
 refs = {name: f(G) for name, f in cases.items()}
 out["aborts_of_the_per_product_form"] += int(G.stats()["persist_aborts"])

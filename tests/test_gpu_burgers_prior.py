@@ -10,7 +10,7 @@ import scipy.sparse.linalg as spla
 
 from tests import burgers_prior_checks as BP
 from tests import gn_batch_oracle as GO
-from tests.test_gpu_gn_batch import NO_FACTOR_FWD, single_device_loop
+from tests.test_gpu_gn_batch import Switch, single_device_loop
 from tests.test_gpu_parity import rel, solve_tol
 
 pytestmark = pytest.mark.gpu
@@ -112,7 +112,7 @@ def _check_ic_stage(pkg, s, r, problems):
     ic_stage = pkg.BurgersInitialConditionBatch(s.F, s.asm, s.prior)
     out_on = ic_stage.run(s.dev(s.ics))
     route_on = _route(pkg, ic_stage)
-    s.F.set_eager(NO_FACTOR_FWD)
+    s.F.set_eager(Switch.NO_FACTOR_FWD)
     out_off = ic_stage.run(s.dev(s.ics))
     assert _route(pkg, ic_stage) == 0
     s.F.set_eager(0)

@@ -37,7 +37,7 @@ def prior(pkg, n_xy):
 
 def setup(pkg, n_xy, B, stream=None, eager=0):
     """Darcy assembler, posterior assembler and a batch-B handle factored once on the posterior pattern, on one stream.
-    eager = 2: a one-problem handle runs the launch sequence of a batch (the bits of a batch's problem)."""
+    eager = Switch.BATCH_ROUTES: a one-problem handle runs the launch sequence of a batch (the bits of a batch's problem)."""
     import torch
     Q0, N = prior(pkg, n_xy)
     st = stream if stream is not None else torch.cuda.Stream()
@@ -221,7 +221,7 @@ def test_batched_variances_are_the_one_problem_accumulation_bitwise(pkg, env5, m
         Pp = e.P.copy()
         Pp.data = nz[p].copy()
         F1 = pkg.TridiagonalCholeskyFactor()
-        F1.set_eager(2)                                    # the launch sequence of a batch: its bits (test_batch_of_problems_matches_one_by_one)
+        F1.set_eager(pkg.Switch.BATCH_ROUTES)                                    # the launch sequence of a batch: its bits (test_batch_of_problems_matches_one_by_one)
         F1.factor(Pp, e.N)
         Q1 = pkg.CsrMatrix(Pp)
         acc = F1.var_accumulate(np.zeros(e.n), method, p * k, k, seed=77, Q=Q1 if method == "rbmc" else None)
@@ -244,7 +244,7 @@ def test_driver_is_the_composition_of_the_public_calls_bitwise(pkg):
     got3d, _ = _run_vs_composed(pkg, e3, True)
     for a, b in zip(got3, got3d):
         assert np.array_equal(a, b)
-    e1 = setup(pkg, 64, 1, eager=2)
+    e1 = setup(pkg, 64, 1, eager=pkg.Switch.BATCH_ROUTES)
     got1, stats = _run_vs_composed(pkg, e1, True)
     assert stats["persist_aborts"] == 0, stats
     # problem 0 alone through a batch's launch sequence (set_eager bit 1): the same factor, so the same std, and the same norm

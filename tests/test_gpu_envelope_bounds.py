@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 import scipy.sparse as sp
 
+import __graft_entry__
 from oracle import bt_oracle as O
 from tests import envelope_ref as E
 from tests import gemm_desc_ref as R
@@ -22,7 +23,7 @@ from tests.test_gpu_parity import TOL_FACTOR
 
 pytestmark = pytest.mark.gpu
 
-NO_ENV = 1 << 21             # set_eager bit 21: no envelope bounds
+Switch = __graft_entry__.load_package().Switch
 T3 = 2.0 * 64.0 ** 3
 
 
@@ -157,7 +158,7 @@ def fcase(request, pkg):
     env = F.envelope()
     for with_rhs in (False, True):
         F.set_factor_rhs(b if with_rhs else None)
-        for bits in (0, NO_ENV):
+        for bits in (0, Switch.NO_ENVELOPE):
             F.set_eager(bits)
             F.refactor(vals)
             st, y = _fwd_state(pkg, F)
@@ -180,7 +181,7 @@ def test_factor_and_forward_solve_bitwise_with_and_without_the_bounds(fcase):
     w, Q, nb, B, idx, tails, vals, env, got, probs = fcase
     for with_rhs in (False, True):
         blocks_on, st_on, y_on, ld_on = got[(with_rhs, 0)]
-        blocks_off, st_off, y_off, ld_off = got[(with_rhs, NO_ENV)]
+        blocks_off, st_off, y_off, ld_off = got[(with_rhs, Switch.NO_ENVELOPE)]
         assert st_on == st_off == (1 if (with_rhs and tails) else st_on)
         if not with_rhs:
             assert st_on == 0
@@ -235,15 +236,15 @@ def test_fused_posterior_bitwise(pkg, name, nb, B):
     F.set_factor_rhs(b)
     out = {}
     F.factor(Q, nb, values=vals)
-    for bits in (0, NO_ENV):
+    for bits in (0, Switch.NO_ENVELOPE):
         F.set_eager(bits)
         F.refactor(vals)
         mu, X = F.posterior_batch(b, 64, seed=19, first_id=7)
         assert F.stats()["sample_ms"] == 0.0               # the fused pass
         out[bits] = (mu.cpu().numpy().copy(), X.cpu().numpy().copy())
     F.close()
-    assert np.array_equal(out[0][0].view(np.uint64), out[NO_ENV][0].view(np.uint64))
-    assert np.array_equal(out[0][1].view(np.uint64), out[NO_ENV][1].view(np.uint64))
+    assert np.array_equal(out[0][0].view(np.uint64), out[Switch.NO_ENVELOPE][0].view(np.uint64))
+    assert np.array_equal(out[0][1].view(np.uint64), out[Switch.NO_ENVELOPE][1].view(np.uint64))
     assert np.isfinite(out[0][0]).all() and np.isfinite(out[0][1]).all()
 
 
@@ -276,7 +277,7 @@ def test_k_units_booked(pkg, with_rhs):
         F.set_factor_rhs(torch.from_numpy(np.stack([rhs] * B)).cuda())
     F.factor(Q, nb, values=vals)
     on = _profiled(F, vals)
-    F.set_eager(NO_ENV)
+    F.set_eager(Switch.NO_ENVELOPE)
     off = _profiled(F, vals)
     F.close()
     lo, hi = E.envelope(Q, nb)
@@ -309,7 +310,7 @@ def test_trivial_bounds_launch_as_before(pkg):
     assert state == 1 and np.array_equal(lo.reshape(lo_py.shape), lo_py) and np.array_equal(hi.reshape(hi_py.shape), hi_py)
     on_blocks = _blocks(F, range(nb), (0, B - 1))
     on = _profiled(F, vals)
-    F.set_eager(NO_ENV)
+    F.set_eager(Switch.NO_ENVELOPE)
     F.refactor(vals)
     off_blocks = _blocks(F, range(nb), (0, B - 1))
     off = _profiled(F, vals)

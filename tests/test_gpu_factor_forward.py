@@ -13,13 +13,13 @@ import numpy as np
 import pytest
 import scipy.sparse as sp
 
+import __graft_entry__
 from oracle import bt_oracle as O
 from tests.test_gpu_parity import rel, solve_tol
 
 pytestmark = pytest.mark.gpu
 
-TWO_CALLS = 1 << 18          # set_eager bit 18: a batch's posterior = solve + sample
-NO_FWD = 1 << 19             # set_eager bit 19: factorisations do not solve for the registered right-hand side
+Switch = __graft_entry__.load_package().Switch
 FORWARD = 1                  # gmrf_bt_solve mode: y = L^-1 b
 
 
@@ -87,7 +87,7 @@ def test_factor_bitwise_unchanged_and_y_is_the_forward_sweep(pkg, fcase):
     for p in range(B):
         assert rel(y[p], ysweep[p]) <= 1e-13
     # the same values without the forward solve: the same bits
-    F.set_eager(NO_FWD)
+    F.set_eager(Switch.NO_FACTOR_FWD)
     try:
         F.refactor(vals)
         assert _fwd_state(pkg, F) == 0
@@ -110,7 +110,7 @@ def test_posterior_with_the_factor_forward_solve(pkg, fcase):
     X_s = F.sample_batch(k, mean=mu_f, seed=seed, first_id=first, like=b)
     assert bool((X_s == X_f).all())
     # the two-call route (eager bit 18) to rounding
-    F.set_eager(TWO_CALLS)
+    F.set_eager(Switch.TWO_CALL_POSTERIOR)
     try:
         mu_u, X_u = F.posterior_batch(b, k, seed=seed, first_id=first)
     finally:

@@ -5,12 +5,13 @@ import numpy as np
 import pytest
 import scipy.sparse as sp
 
+import __graft_entry__
 from oracle import bt_oracle as O
 from tests.test_gpu_parity import rel, solve_tol
 
 pytestmark = pytest.mark.gpu
 
-TWO_CALLS = 1 << 18          # set_eager bit 18: a batch's posterior = solve + sample
+Switch = __graft_entry__.load_package().Switch
 TAIL = 65536                 # gmrf_test_gemm: the 64 x 64 LDS-DMA kernel with the tail row
 
 
@@ -59,7 +60,7 @@ def test_fused_posterior_against_two_calls_and_oracle(pkg, batch_case):
     X_s = F.sample_batch(k, mean=mu_f, seed=seed, first_id=first, like=b)
     assert bool((X_s == X_f).all())
     # the two-call route (eager bit 18): the mean to rounding, the samples around their own mean
-    F.set_eager(TWO_CALLS)
+    F.set_eager(Switch.TWO_CALL_POSTERIOR)
     try:
         mu_u, X_u = F.posterior_batch(b, k, seed=seed, first_id=first)
         assert not _fused(F)
@@ -123,7 +124,7 @@ def test_fused_posterior_aliased_input_takes_two_calls(pkg, lib):
     w = pkg.workloads.make("burgers512x64")
     B, k = 16, 64
     F, vals, b = _batch(pkg, w.Q, w.rhs, w.n_blocks, B)
-    F.set_eager(TWO_CALLS)
+    F.set_eager(Switch.TWO_CALL_POSTERIOR)
     mu_ref, X_ref = F.posterior_batch(b, k, seed=3, first_id=0)
     F.set_eager(0)
     bm = b.clone()

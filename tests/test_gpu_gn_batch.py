@@ -6,13 +6,14 @@ import types
 import numpy as np
 import pytest
 
+import __graft_entry__
 from oracle import bt_oracle as O
 from tests import gn_batch_oracle as GO
 from tests.test_gpu_parity import rel, solve_tol
 
 pytestmark = pytest.mark.gpu
 
-NO_FACTOR_FWD = 524288          # set_eager bit 19
+Switch = __graft_entry__.load_package().Switch
 
 
 class Setup:
@@ -250,7 +251,7 @@ def test_forward_in_factor_route(pkg, lib, ns, nt, B, expected):
     assert _route(pkg, gn) == (1, 1 if qualifies else 0)
     pkg._cabi.check(lib.gmrf_test_factor_fwd(s.F._h, C.byref(state), None))
     assert state.value == 0                               # (the run's registration does not outlive it)
-    s.F.set_eager(NO_FACTOR_FWD)
+    s.F.set_eager(Switch.NO_FACTOR_FWD)
     x_off, _, h_off = s.run(gn, 1, 1e-4)
     assert _route(pkg, gn) == (1, 0)
     s.F.set_eager(0)

@@ -8,13 +8,13 @@ import numpy as np
 import pytest
 import scipy.sparse as sp
 
+import __graft_entry__
 from oracle import bt_oracle as O
 from tests.test_gpu_parity import TOL_FACTOR
 
 pytestmark = pytest.mark.gpu
 
-NO_PERSIST_PANELS = 1 << 15  # set_eager bit 15: potrf_diag128 + the 128^3 products instead of one persistent launch per panel
-NO_GROUPED = 1 << 20         # set_eager bit 20: the two independent 128^3 products stay two launches
+Switch = __graft_entry__.load_package().Switch
 TRI_B_LOWER = 4
 GEMM_CLASSES = (0, 6, 7, 11, 12, 13, 14, 15, 18)
 
@@ -70,12 +70,12 @@ def factored(pkg):
     Q = chain(BS, NB)
     vals = np.stack([Q.data * (1.0 + 0.05 * p) for p in range(B)])
     F = pkg.TridiagonalCholeskyFactor(batch=B)
-    F.set_eager(NO_PERSIST_PANELS)
+    F.set_eager(Switch.NO_PERSIST_PANELS)
     F.factor(Q, NB, values=vals)
     probs = tuple(range(B))
     grouped = _blocks(F, NB, probs)
     st_g, shapes_g = _profiled_refactor(F, vals)
-    F.set_eager(NO_PERSIST_PANELS | NO_GROUPED)
+    F.set_eager(Switch.NO_PERSIST_PANELS | Switch.NO_GROUPED_GEMM)
     F.refactor(vals)
     plain = _blocks(F, NB, probs)
     st_p, shapes_p = _profiled_refactor(F, vals)

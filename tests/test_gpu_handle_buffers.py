@@ -255,3 +255,32 @@ def test_handles_that_come_and_go_leave_no_device_memory(pkg):
         free_b, total_b = torch.cuda.mem_get_info(0)
         used.append(total_b - free_b)
     assert max(used[2:]) - min(used[2:]) < 64 << 20
+
+
+@pytest.mark.parametrize("batch,bs,route,switch", [(1, 128, 1, "NO_PERSIST"), (2, 256, 3, "NO_PERSIST_PANELS")])
+def test_a_changed_switch_reaches_a_handle_with_captured_graphs(pkg, batch, bs, route, switch):
+    """Graphs on: a handle that has captured its factor graph on the persistent route (stats persist_route: 1 the fused block
+    launch of one problem at block size 128, 3 a batch's launch per panel diagonal block at 256 -- the smallest shapes that take
+    them) drops it when the switch comes, takes the launch-per-step form (0), and takes the persistent one again when the switch
+    goes.  Each factor solves to the first one's solution within the bound of solves across routes (test_gpu_parity.solve_tol)."""
+    from tests.test_gpu_parity import rel, solve_tol
+    w = pkg.workloads.random_block_tridiagonal(3, bs, seed=5)
+    vals = np.stack([w.Q.data * (1.0 + 0.25 * p) for p in range(batch)]) if batch > 1 else w.Q.data
+    rhs = np.stack([w.rhs * (p + 1.0) for p in range(batch)])
+    F = pkg.TridiagonalCholeskyFactor(batch=batch)         # (the only handle alive: the CU budget is its alone)
+    try:
+        def solve():
+            return F.solve_batch(rhs[:, None, :])[:, 0, :] if batch > 1 else pkg.ldiv(F, rhs[0])[None, :]
+
+        F.factor(w.Q, w.n_blocks, values=vals if batch > 1 else None)
+        assert F.stats()["persist_route"] == route
+        x0 = solve()
+        for switches, want in ((getattr(pkg.Switch, switch), 0), (0, route)):
+            F.set_eager(switches)
+            F.refactor(vals)
+            assert F.stats()["persist_route"] == want, (switches, F.stats()["persist_route"])
+            x = solve()
+            for p in range(batch):
+                assert rel(x[p], x0[p]) < solve_tol(w), (switches, p)
+    finally:
+        F.close()

@@ -5,9 +5,11 @@ import numpy as np
 import pytest
 import scipy.sparse as sp
 
+import __graft_entry__
 from oracle import bt_oracle as O
 
 pytestmark = pytest.mark.gpu
+Switch = __graft_entry__.load_package().Switch
 
 TOL_FACTOR = 1e-11     # max-abs / max-abs on factor blocks
 EPS = 2.220446049250313e-16
@@ -166,7 +168,7 @@ def test_eager_and_graph_paths_agree_bitwise(pkg):
     w = pkg.workloads.make("darcy32")
     F = pkg.tridiagonal_cholesky(w.Q, w.n_blocks)
     a = pkg.ldiv(F, w.rhs)
-    F.set_eager(True)
+    F.set_eager(Switch.EAGER)
     F.refactor(w.Q.data)
     b = pkg.ldiv(F, w.rhs)
     assert np.array_equal(a, b)
@@ -180,7 +182,7 @@ def test_panel_sweeps_through_gemm_match_sweep_kernel(pkg):
     F = pkg.TridiagonalCholeskyFactor(batch=nb).factor(w.Q, w.n_blocks, values=np.tile(w.Q.data, (nb, 1)))
     B = np.random.default_rng(5).standard_normal((nb, 64, w.n))
     a = [F.solve_batch(B, m) for m in (pkg._cabi.SOLVE_FULL, pkg._cabi.SOLVE_FORWARD, pkg._cabi.SOLVE_BACKWARD)]
-    F.set_eager(4)
+    F.set_eager(Switch.SWEEP_NO_GEMM)
     b = [F.solve_batch(B, m) for m in (pkg._cabi.SOLVE_FULL, pkg._cabi.SOLVE_FORWARD, pkg._cabi.SOLVE_BACKWARD)]
     for x, y in zip(a, b):
         assert rel(x, y) < 1e-12 and not np.array_equal(x, y)
@@ -194,10 +196,10 @@ def test_forked_factor_graph_matches_single_branch(pkg):
     kernels on the same data: bitwise equal to the single-branch graph and to plain stream launches."""
     w = pkg.workloads.make("burgers512x64")
     F = pkg.TridiagonalCholeskyFactor()
-    F.set_eager(128)                         # the inverse by recursive doubling: what the forked branch overlaps
+    F.set_eager(Switch.DOUBLING_INVERSE)                         # the inverse by recursive doubling: what the forked branch overlaps
     F.factor(w.Q, w.n_blocks)
     a = pkg.ldiv(F, w.rhs); la = F.chos[40].copy(); xa = F.get_block(pkg._cabi.BLOCK_LINV, 40)
-    for flags in (16 | 128, 1 | 128, 16 | 128):
+    for flags in (Switch.FORK_GRAPH | Switch.DOUBLING_INVERSE, Switch.EAGER | Switch.DOUBLING_INVERSE, Switch.FORK_GRAPH | Switch.DOUBLING_INVERSE):
         F.set_eager(flags)
         for _ in range(2):                   # capture, then a replay of the forked graph
             F.refactor(w.Q.data)
@@ -383,7 +385,7 @@ def test_sparse_and_dense_coupling_product_agree(pkg, name):
     Fo = O.tridiagonal_cholesky(w.Q, w.n_blocks)
     Fs = pkg.tridiagonal_cholesky(w.Q, w.n_blocks)
     Fd = pkg.TridiagonalCholeskyFactor()
-    Fd.set_eager(8)
+    Fd.set_eager(Switch.DENSE_COUPLING)
     Fd.factor(w.Q, w.n_blocks)
     for i in (0, w.n_blocks // 2, w.n_blocks - 2):
         scale = np.max(np.abs(Fo.Cs[i]))
@@ -393,7 +395,7 @@ def test_sparse_and_dense_coupling_product_agree(pkg, name):
     assert rel(pkg.ldiv(Fs, w.rhs), pkg.ldiv(Fd, w.rhs)) < solve_tol(w)
     # the GEMM route with a batch (dense image of B per problem)
     Fb = pkg.TridiagonalCholeskyFactor(batch=2)
-    Fb.set_eager(8)
+    Fb.set_eager(Switch.DENSE_COUPLING)
     Fb.factor(w.Q, w.n_blocks, values=np.stack([w.Q.data, 2.0 * w.Q.data]))
     xb = Fb.solve_batch(np.stack([w.rhs, w.rhs])[:, None, :])[:, 0, :]
     # (a batch assembles the inverses by recursive doubling, one problem row by row inside the fused steps: equal to rounding)
@@ -576,7 +578,7 @@ def test_batch_of_problems_matches_one_by_one(pkg):
     for p in range(B):
         Qp = w.Q.copy(); Qp.data = vals[p]
         F1 = pkg.TridiagonalCholeskyFactor()
-        F1.set_eager(2)
+        F1.set_eager(Switch.BATCH_ROUTES)
         F1.factor(Qp, w.n_blocks)
         mu1 = pkg.ldiv(F1, rhs[p])
         assert np.array_equal(mu_b[p], mu1)
@@ -601,7 +603,7 @@ def test_batch_of_problems_matches_one_by_one(pkg):
     vm = Fb.marginal_var("mc", k=64, seed=9)
     Q0 = w.Q.copy(); Q0.data = vals[0]
     F0 = pkg.TridiagonalCholeskyFactor()
-    F0.set_eager(2)
+    F0.set_eager(Switch.BATCH_ROUTES)
     F0.factor(Q0, w.n_blocks)
     assert np.array_equal(vr[0], F0.marginal_var("rbmc", k=64, seed=9, Q=pkg.CsrMatrix(Q0)))
     assert np.array_equal(vm[0], F0.marginal_var("mc", k=64, seed=9))
@@ -651,7 +653,7 @@ def test_two_level_panel_factor_of_batches(pkg):
     assert np.max(np.abs(np.tril(Fb.chos[63]) - Fo.chos[63])) / np.max(np.abs(Fo.chos[63])) < TOL_FACTOR
     assert abs(Fb.logdet() - O.logdet(Fo)) < 1e-10 * abs(O.logdet(Fo))
     F1 = pkg.TridiagonalCholeskyFactor()
-    F1.set_eager(2)
+    F1.set_eager(Switch.BATCH_ROUTES)
     F1.factor(w.Q, w.n_blocks)
     assert np.array_equal(F1.chos[63], Fb.chos[63]) and np.array_equal(pkg.ldiv(F1, w.rhs), mu_b[0])
     F1.set_eager(0)                      # fused one-launch step: same factor up to rounding
@@ -667,7 +669,7 @@ def test_two_level_panel_factor_of_batches(pkg):
     assert st["kernel_launches"][16] == 0 and st["kernel_launches"][17] == (w.block_size // 256) * w.n_blocks and not is128(Fb)
     assert st["persist_route"] == 3 and st["persist_cus"] == 14 and st["persist_refused"] == 0 and st["persist_aborts"] == 0
     Fd = pkg.TridiagonalCholeskyFactor(batch=2)
-    Fd.set_eager(32768)
+    Fd.set_eager(Switch.NO_PERSIST_PANELS)
     Fd.factor(w.Q, w.n_blocks, values=vals)
     Fd.select_problem(0)
     assert 0 < np.max(np.abs(Fd.chos[63] - Fb.chos[63])) / np.max(np.abs(Fo.chos[63])) < 1e-12
@@ -899,7 +901,7 @@ def test_staircase_of_the_coupling_blocks_is_exact(pkg):
         w = pkg.workloads.make(name)
         Fs = pkg.tridiagonal_cholesky(w.Q, w.n_blocks)
         Fd = pkg.TridiagonalCholeskyFactor()
-        Fd.set_eager(32)
+        Fd.set_eager(Switch.NO_STAIRCASE)
         Fd.factor(w.Q, w.n_blocks)
         lay_s, lay_d = Fs.get_layout(), Fd.get_layout()
         # record = [cmin, rmax, row tiles, kst..., split of the inverses (0 here: one problem)]
@@ -1160,7 +1162,7 @@ def test_schur_block_assembled_inside_the_coupling_launch(pkg):
         w = pkg.workloads.make(name)
         F = pkg.tridiagonal_cholesky(w.Q, w.n_blocks)
         G = pkg.TridiagonalCholeskyFactor()
-        G.set_eager(131072)
+        G.set_eager(Switch.NO_SCATTER_FOLD)
         G.factor(w.Q, w.n_blocks)
         for i in (0, 1, w.n_blocks // 2, w.n_blocks - 1):
             assert np.array_equal(F.chos[i], G.chos[i]), (name, i)
@@ -1179,7 +1181,7 @@ def F_ref16(F, res, rhs):
     """16 samples with seed 6 by the launch-per-product form (computed once per handle and kept in that handle's `res`:
     a cache keyed by id(F) handed a freed handle's samples to the next handle allocated at the same address)."""
     if "ref16" not in res:
-        F.set_eager(65536)
+        F.set_eager(Switch.NO_SWEEP_PERSIST)
         res["ref16"] = F.sample(16, mean=res["per_product"][0], seed=6, like=rhs)
         F.set_eager(0)
     return res["ref16"]
@@ -1201,7 +1203,7 @@ def test_persistent_sweeps_of_one_problem_are_the_per_product_sweeps_bitwise(pkg
         st = F.stats()
         assert st["persist_cus"] == 256 and st["persist_refused"] == 0, st        # (the handle holds the whole chip)
         res = {}
-        for label, bits in (("persist", 0), ("persist_eager", 1), ("per_product", 65536)):
+        for label, bits in (("persist", 0), ("persist_eager", Switch.EAGER), ("per_product", Switch.NO_SWEEP_PERSIST)):
             F.set_eager(bits)
             mu = pkg.ldiv(F, rhs); s_mu = F.stats()["sweep_persist"]
             yf = pkg.forward_solve(F, rhs)
@@ -1209,7 +1211,7 @@ def test_persistent_sweeps_of_one_problem_are_the_per_product_sweeps_bitwise(pkg
             X64 = F.sample(64, mean=mu, seed=3, like=rhs); s_x = F.stats()["sweep_persist"]
             X16 = F.sample(16, mean=mu, seed=5, like=rhs)
             res[label] = (mu, yf, xb, X64, X16)
-            assert s_mu == s_x == (0 if bits == 65536 else 1), (name, label, s_mu, s_x)
+            assert s_mu == s_x == (0 if bits == Switch.NO_SWEEP_PERSIST else 1), (name, label, s_mu, s_x)
         for label in ("persist", "persist_eager"):
             for a, b in zip(res[label], res["per_product"]):
                 assert torch.equal(a, b), (name, label)
@@ -1217,7 +1219,7 @@ def test_persistent_sweeps_of_one_problem_are_the_per_product_sweeps_bitwise(pkg
         # consecutive solves with DIFFERENT right-hand sides through the same panels: a value left over from the previous call
         # (in a cache of another XCD, or in a panel the sentinel fill did not cover) would be taken for this call's data
         rhs2 = torch.flip(rhs, dims=[0]) * 0.37 + 1.0
-        F.set_eager(65536); mu2_ref = pkg.ldiv(F, rhs2); xb2_ref = pkg.backward_solve(F, rhs2); F.set_eager(0)
+        F.set_eager(Switch.NO_SWEEP_PERSIST); mu2_ref = pkg.ldiv(F, rhs2); xb2_ref = pkg.backward_solve(F, rhs2); F.set_eager(0)
         for it in range(6):
             if it % 2 == 0:
                 assert torch.equal(pkg.ldiv(F, rhs), res["per_product"][0]), (name, it)
@@ -1260,13 +1262,13 @@ def test_posterior_in_one_call_is_mean_then_samples_bitwise(pkg):
         mu_ref = pkg.ldiv(F, rhs)
         for k, seed in ((64, 3), (16, 5), (48, 7)):
             X_ref = F.sample(k, mean=mu_ref, seed=seed, like=rhs)
-            for bits in (0, 65536, 1):
+            for bits in (0, Switch.NO_SWEEP_PERSIST, Switch.EAGER):
                 F.set_eager(bits)
                 mu, X = F.posterior(rhs, k, seed=seed)
                 assert torch.equal(mu, mu_ref) and torch.equal(X, X_ref), (name, k, bits)
                 st = F.stats()
                 assert st["persist_aborts"] == 0
-                assert st["sweep_persist"] == (1 if bits != 65536 and name != "darcy64" else 0), (name, bits, st["sweep_persist"])
+                assert st["sweep_persist"] == (1 if bits != Switch.NO_SWEEP_PERSIST and name != "darcy64" else 0), (name, bits, st["sweep_persist"])
             F.set_eager(0)
         # twice in a row with another right-hand side (the panels of the two streams are reused), then host arrays
         rhs2 = torch.flip(rhs, dims=[0]) * 0.5 - 2.0
@@ -1292,7 +1294,7 @@ def test_persistent_sweeps_under_uneven_load(pkg):
     w = pkg.workloads.make("burgers512x64")
     rhs = torch.from_numpy(w.rhs).cuda()
     F = pkg.tridiagonal_cholesky(w.Q, w.n_blocks)
-    F.set_eager(65536)
+    F.set_eager(Switch.NO_SWEEP_PERSIST)
     mu0 = pkg.ldiv(F, rhs); X0 = F.sample(16, mean=mu0, seed=9, like=rhs)
     F.set_eager(0)
     streams = pkg.StreamSet(1)
@@ -1416,7 +1418,7 @@ def test_persistent_sampled_variances_against_float64_reference(pkg, name):
                 den = ref if method == "rbmc" else np.maximum(ref, scale)
                 err = float(np.max(np.abs(v - ref) / den))
                 assert err < 4.0 * tol, (name, method, k, err, tol)             # squares of samples that agree to tol
-                F.set_eager(65536)
+                F.set_eager(Switch.NO_SWEEP_PERSIST)
                 v_pp = F.marginal_var(method, **kw)
                 st_pp = F.stats()
                 F.set_eager(0)
@@ -1473,7 +1475,7 @@ def test_persistent_sweeps_c_abi_leading_dimensions_and_mixed_k(pkg, lib, name):
         def both_forms(call, dev, k):
             """call(out) on the persistent form and on the launch-per-product form; the first result (host array)"""
             res = []
-            for bits in (0, 65536):
+            for bits in (0, Switch.NO_SWEEP_PERSIST):
                 F.set_eager(bits)
                 out = padded(np.full((n, k), np.nan), dev)
                 n0 = F.stats()["sweep_persist_launches"]
@@ -1529,7 +1531,7 @@ def test_persistent_sweeps_with_aliased_arguments(pkg, lib, name):
 
         def both_forms(run):
             res = [None, None]
-            for i, bits in enumerate((0, 65536)):
+            for i, bits in enumerate((0, Switch.NO_SWEEP_PERSIST)):
                 F.set_eager(bits)
                 res[i] = run()
             F.set_eager(0)
@@ -1598,7 +1600,7 @@ def test_persistent_route_does_not_depend_on_the_previous_call(pkg, name):
     w, Fo, tol, F = _persist_case(pkg, name)
     try:
         rhs = torch.from_numpy(w.rhs).cuda()
-        F.set_eager(65536)
+        F.set_eager(Switch.NO_SWEEP_PERSIST)
         mu_ref = pkg.ldiv(F, rhs)
         X_ref = F.sample(16, mean=mu_ref, seed=7, like=rhs)
         v_ref = F.marginal_var("mc", k=64, seed=5)
@@ -1634,7 +1636,7 @@ def test_inverse_rows_inside_the_fused_steps(pkg):
             w.meta.setdefault("cond", 3.4e9)
         Fr = pkg.tridiagonal_cholesky(w.Q, w.n_blocks)
         Fd = pkg.TridiagonalCholeskyFactor()
-        Fd.set_eager(128)
+        Fd.set_eager(Switch.DOUBLING_INVERSE)
         Fd.factor(w.Q, w.n_blocks)
         i = w.n_blocks // 2
         assert np.array_equal(Fr.chos[0], Fd.chos[0])
@@ -1656,7 +1658,7 @@ def test_inverse_rows_inside_the_fused_steps(pkg):
         # the look-ahead chain (tile j+1 factored inside the launch of step j) does the same arithmetic as the form in
         # which every workgroup of a step re-factors the diagonal tile (set_eager bit 8): bitwise equal factor
         Fn = pkg.TridiagonalCholeskyFactor()
-        Fn.set_eager(256)
+        Fn.set_eager(Switch.NO_LOOKAHEAD)
         Fn.factor(w.Q, w.n_blocks)
         for b in (0, i, w.n_blocks - 1):
             assert np.array_equal(Fr.chos[b], Fn.chos[b])
@@ -2057,7 +2059,7 @@ def test_split_inverse_representation_of_batches(pkg):
     vals, rhs = np.stack(vals), np.stack(rhs)
     rhs_t = torch.from_numpy(rhs[:, None, :]).cuda()
     Fs = pkg.TridiagonalCholeskyFactor(batch=8); Fs.set_keep_l(False)
-    Ff = pkg.TridiagonalCholeskyFactor(batch=8); Ff.set_keep_l(False); Ff.set_eager(4096)
+    Ff = pkg.TridiagonalCholeskyFactor(batch=8); Ff.set_keep_l(False); Ff.set_eager(Switch.NO_XSPLIT)
     for F in (Fs, Ff):
         F.set_profiling(1)
         F.factor(Q0, nb, values=vals)

@@ -1,5 +1,5 @@
 """Development aid (round 5): one problem's sweeps as ONE persistent launch each (sweep_persist) against a launch per product
-(set_eager bit 16) -- bitwise comparison of mean / samples / forward-only / backward-only solves, and the times of both."""
+(set_eager bit 16, Switch.NO_SWEEP_PERSIST) -- bitwise comparison of mean / samples / forward-only / backward-only solves, and the times of both."""
 import sys, time, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -15,7 +15,7 @@ for name in (sys.argv[1:] or ["burgers512x64", "darcy256"]):
     F = pkg.tridiagonal_cholesky(w.Q, w.n_blocks)
     rhs = torch.from_numpy(w.rhs).cuda()
     res = {}
-    for label, bits in (("persist", 0), ("per_product", 65536)):
+    for label, bits in (("persist", 0), ("per_product", pkg.Switch.NO_SWEEP_PERSIST)):
         F.set_eager(bits)
         times = []
         for it in range(4):

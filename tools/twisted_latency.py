@@ -3,7 +3,7 @@
 For darcy256, elliptic512 and burgers512x64: factor (gmrf_bt_refactor_values), mean (ldiv), 64 samples and the one-call
 posterior (mean + 64 samples), device-resident right-hand sides, median of --reps after --warmup; the twisted order with the
 automatic meeting block, its resolved m and each half's persist_route / persist_aborts.  darcy256 is also factored in the
-reference order with set_eager(8192) (bit 13, the launch-per-step in-block form: the ratio behind the automatic meeting block).
+reference order with set_eager(Switch.NO_PERSIST) (bit 13, the launch-per-step in-block form: the ratio behind the automatic meeting block).
 Handles are closed before the next one is made (a one-problem handle with persistent sweeps claims the whole chip).
 Prints one JSON line."""
 import argparse
@@ -33,11 +33,11 @@ def _median_ms(fn, reps, warmup, dev_ms=None):
     return out
 
 
-def measure(pkg, w, order, reps, warmup, legs=("factor", "mean", "samples", "posterior"), eager_bits=0):
+def measure(pkg, w, order, reps, warmup, legs=("factor", "mean", "samples", "posterior"), switches=0):
     import torch
     F = pkg.TridiagonalCholeskyFactor(order=order)
-    if eager_bits:
-        F.set_eager(eager_bits)
+    if switches:
+        F.set_eager(switches)
     F.factor(w.Q, w.n_blocks)
     nz = w.Q.tocsc()
     nz.sort_indices()
@@ -84,7 +84,7 @@ def main():
         c["reference"] = measure(pkg, w, "reference", args.reps, args.warmup)
         c["twisted"] = measure(pkg, w, "twisted", args.reps, args.warmup)
         if name == "darcy256":
-            c["reference_launch_per_step"] = measure(pkg, w, "reference", args.reps, args.warmup, legs=("factor",), eager_bits=8192)
+            c["reference_launch_per_step"] = measure(pkg, w, "reference", args.reps, args.warmup, legs=("factor",), switches=pkg.Switch.NO_PERSIST)
             c["step_over_persist_per_block"] = (c["reference_launch_per_step"]["factor"]["device_ms"] /
                                                 c["reference"]["factor"]["device_ms"])
         c["twisted_over_reference_factor"] = c["twisted"]["factor"]["device_ms"] / c["reference"]["factor"]["device_ms"]

@@ -1046,6 +1046,124 @@ def solution_errors_batch(pred, soln, first: int = 0, device: int = 0) -> np.nda
     return out
 
 
+class FieldEvaluator:
+    """FEM fields at the points of a data grid, on the device: `E = evaluation_matrix(disc, pred_coords)` of the data-set loops
+    (scripts/darcy/solve_darcy_gmrf-fem.jl:82-89, scripts/burgers/solve_burgers_gmrf-fem.jl:75-83), `pred = E * mean` and its
+    `rel_err`, `rmse`, `max_err` against the data set's solution -- the last line of those loops:
+
+        ev = FieldEvaluator.triangles(nx, ny, workloads.darcy_pred_coords(xs, ys), order=2)
+        errors = ev.errors(DarcyConditioningBatch(F, asm, darcy).run(tables, q).mean, truth)              # (B, 3)
+        ev = FieldEvaluator.line(nc, workloads.burgers_pred_coords(xs))
+        errors = ev.errors(gn.posterior().x, truth, nt=nt, first_slice=1)                                # the scripts' [2:end, :]
+
+    The rows of E are computed once at creation, on the host, in double precision (include/gmrf_hip.h states the rules); `points`
+    are host coordinates in any order.  Every value is ONE rounding sequence, w0 f[i0] then fma(wk, f[ik], .) in ascending dof
+    index: the same bits in every batch and on every call.  The calls run on the handle's stream (`stream`, or one of its own)
+    and return synchronised; a tensor that torch is still writing on another stream must be complete before it is passed, as for
+    the other handles.  device = -1: `rows()` and `matrix()` only (no GPU needed)."""
+
+    def __init__(self, handle: C.c_void_p, npts: int):
+        self._h, self.npts = handle, int(npts)
+        ns, width = C.c_int64(0), C.c_int64(0)
+        _cabi.check(_cabi.load().gmrf_eval_rows(self._h, C.byref(ns), C.byref(width), None, None))
+        self.ns, self.width = int(ns.value), int(width.value)
+
+    @classmethod
+    def line(cls, nc: int, points, order: int = 2, bc: str = "periodic", length: float = 1.0, device: int = 0, stream: int = 0):
+        """The lines of `BurgersP1Tangent`: nc cells of length / nc, order 1 or 2, bc "periodic" (points in [0, length)) or
+        "dirichlet" (points in [0, length])."""
+        if bc not in BurgersP1Tangent.BCS:
+            raise GmrfError(_cabi.ERR_BAD_SHAPE, f"FieldEvaluator.line: bc {bc!r} {tuple(BurgersP1Tangent.BCS)}")
+        pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1)
+        h = C.c_void_p()
+        _cabi.check(_cabi.load().gmrf_eval_line_create(int(device), C.c_void_p(stream), int(nc), int(order), BurgersP1Tangent.BCS[bc],
+                                                       float(length), pts.shape[0], _cabi.ptr(pts), C.byref(h)))
+        return cls(h, pts.shape[0])
+
+    @classmethod
+    def triangles(cls, nx: int, ny: int, xy, order: int = 1, device: int = 0, stream: int = 0):
+        """The triangle meshes of `DarcyP1Assembler` / `EllipticP1Tangent` / `ShallowWaterP1`: nx x ny vertices on the unit
+        square, order 1 (vertex dofs) or 2 (the (2 nx - 1) x (2 ny - 1) lattice); xy (npts, 2) in [0, 1]^2."""
+        pts = np.ascontiguousarray(xy, dtype=np.float64)
+        if pts.ndim != 2 or pts.shape[1] != 2:
+            raise ValueError("xy must have shape (npts, 2)")
+        h = C.c_void_p()
+        _cabi.check(_cabi.load().gmrf_eval_tri_create(int(device), C.c_void_p(stream), int(nx), int(ny), int(order), pts.shape[0],
+                                                      _cabi.ptr(pts), C.byref(h)))
+        return cls(h, pts.shape[0])
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            _cabi.load().gmrf_eval_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def rows(self) -> Tuple[np.ndarray, np.ndarray]:
+        """(idx (npts, width) int64, w (npts, width)): the dofs of every point, ascending, and their weights (zeros stored)."""
+        idx, w = np.empty((self.npts, self.width), dtype=np.int64), np.empty((self.npts, self.width))
+        _cabi.check(_cabi.load().gmrf_eval_rows(self._h, None, None, _cabi.ptr(idx), _cabi.ptr(w)))
+        return idx, w
+
+    def matrix(self, nt: int = 1, slice: Optional[int] = None) -> sp.csr_matrix:
+        """E as a SciPy CSR matrix built on the host from `rows()`, explicit zeros kept.  nt = 1: (npts, ns), the reference's
+        `evaluation_matrix`; nt > 1: the space-time form (nt npts, nt ns) of `spatial_to_spatiotemporal`, slice t's points on slice
+        t's dofs; slice = t: those npts rows alone, (npts, nt ns) -- slice = 0 is `A_ic`."""
+        nt = int(nt)
+        if nt < 1 or (slice is not None and not 0 <= int(slice) < nt):
+            raise ValueError("nt >= 1 and 0 <= slice < nt")
+        idx, w = self.rows()
+        slices = np.arange(nt) if slice is None else np.array([int(slice)])
+        cols = (idx[None, :, :] + self.ns * slices[:, None, None]).reshape(-1)
+        rp = self.width * np.arange(slices.size * self.npts + 1, dtype=np.int64)
+        return sp.csr_matrix((np.tile(w.reshape(-1), slices.size), cols, rp), shape=(slices.size * self.npts, nt * self.ns))
+
+    @staticmethod
+    def _prep(a, name: str):
+        if _is_torch(a):
+            import torch
+            if a.dtype != torch.float64:
+                raise TypeError("float64 required")
+            if not a.is_cuda:
+                raise TypeError(f"{name}: a torch tensor must live on the device (pass NumPy for host data)")
+            return a.contiguous()
+        return np.ascontiguousarray(a, dtype=np.float64)
+
+    def apply(self, fields):
+        """fields (..., ns) -> (..., npts) of the same kind (NumPy array or torch CUDA tensor): every leading index is one spatial
+        field -- means, samples, or the slices of space-time fields given as (..., nt, ns)."""
+        f = self._prep(fields, "fields")
+        if f.ndim < 1 or f.shape[-1] != self.ns:
+            raise ValueError(f"fields must have a last axis of {self.ns} dofs")
+        lead = tuple(f.shape[:-1])
+        rows = int(np.prod(lead, dtype=np.int64))
+        pred = PosteriorAssembler._like2(f, lead + (self.npts,))
+        _cabi.check(_cabi.load().gmrf_eval_apply_batch(self._h, rows, _cabi.ptr(f), _cabi.ptr(pred)))
+        return pred
+
+    def errors(self, fields, truth, nt: int = 1, first_slice: int = 0, return_pred: bool = False):
+        """(B, 3) NumPy array of (rel_err, rmse, max_err) per problem of E fields against truth over the slices [first_slice, nt):
+        fields (B, nt ns) or (B, nt, ns), truth (B, nt npts) or (B, nt, npts), NumPy arrays or torch CUDA tensors.  Bitwise
+        `solution_errors_batch(apply(fields), truth, first=first_slice * npts)`, in one pass that does not write pred.
+        return_pred: also pred (B, nt npts), of the kind of `fields`, the bits of `apply`."""
+        nt = int(nt)
+        f, t = self._prep(fields, "fields"), self._prep(truth, "truth")
+        if f.ndim < 2 or int(np.prod(f.shape[1:], dtype=np.int64)) != nt * self.ns:
+            raise ValueError(f"fields must have shape (B, {nt} * {self.ns})")
+        B = f.shape[0]
+        if t.shape[0] != B or int(np.prod(t.shape[1:], dtype=np.int64)) != nt * self.npts:
+            raise ValueError(f"truth must have shape ({B}, {nt} * {self.npts})")
+        out = np.empty((B, 3), dtype=np.float64)
+        pred = PosteriorAssembler._like2(f, (B, nt * self.npts)) if return_pred else None
+        _cabi.check(_cabi.load().gmrf_eval_errors_batch(self._h, B, nt, int(first_slice), _cabi.ptr(f), _cabi.ptr(t), _cabi.ptr(out),
+                                                        _cabi.ptr(pred)))
+        return (out, pred) if return_pred else out
+
+
 class ConditionedGMRF:
     """What `condition_on_observations(x, A, Q_eps, y; solver_blueprint)` returns in the reference's
     problem loop (scripts/darcy/solve_darcy_gmrf-fem.jl:176-192), served by the block-tridiagonal

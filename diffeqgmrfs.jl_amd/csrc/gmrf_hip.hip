@@ -50,6 +50,7 @@
 #include "gn_posterior.hpp"
 #include "burgers_prior.hpp"
 #include "burgers_line_prior.hpp"
+#include "field_eval.hpp"
 
 using namespace gmrf;
 
@@ -5439,6 +5440,182 @@ gmrf_status gmrf_field_errors_batch(int32_t device, void* stream, int64_t batch,
     ctx.close();                        // (drains the stream before the buffers go)
     arena.release(); part.release();
     return status;
+}
+
+// --------------------------------------------------------------------------------- fields at data-grid points (field_eval.hpp)
+// E = evaluation_matrix(disc, pred_coords) of the data-set loops (solve_darcy_gmrf-fem.jl:82-89, solve_burgers_gmrf-fem.jl:75-83) as
+// a table of `width` (dof, weight) pairs per point, built here once in double precision; `pred = E f` and the metrics against a
+// truth on the device.
+struct gmrf_eval : DevCtx {             // device -1: the rows only
+    int64_t ns = 0, npts = 0;
+    int width = 0;
+    std::vector<int64_t> idx;           // [npts][width], ascending within a row
+    std::vector<double> w;
+    DevArr<int32_t> d_idx;              // [width][npts]
+    DevArr<double> d_w;
+    DevBuf arena, part;                 // host arguments of the current call (Staging); the chunk sums of the metrics
+};
+
+gmrf_status gmrf_eval_destroy(gmrf_eval* e) {
+    if (!e) return GMRF_OK;
+    e->close();
+    delete e;
+    return GMRF_OK;
+}
+
+static gmrf_status eval_bad_point(int64_t c, const std::string& what, const char* domain) {
+    g_last_error = "evaluation point " + std::to_string(c) + " = " + what + " is not in " + domain;
+    return GMRF_ERR_BAD_SHAPE;
+}
+
+// Opens the device side of a handle whose rows are complete and uploads the table point-minor.
+static gmrf_status eval_finish(std::unique_ptr<gmrf_eval, gmrf_status (*)(gmrf_eval*)>& guard, int32_t device, void* stream,
+                               const char* who, gmrf_eval** out) {
+    gmrf_eval* e = guard.get();
+    GCHK(e->open(device, stream, hipStreamNonBlocking, who));
+    if (e->device >= 0) {
+        const int64_t W = e->width, np = e->npts;
+        std::vector<int32_t> ti((size_t)(W * np));
+        std::vector<double> tw((size_t)(W * np));
+        for (int64_t c = 0; c < np; ++c)
+            for (int64_t k = 0; k < W; ++k) {
+                ti[(size_t)(k * np + c)] = (int32_t)e->idx[(size_t)(c * W + k)];
+                tw[(size_t)(k * np + c)] = e->w[(size_t)(c * W + k)];
+            }
+        GCHK(e->d_idx.upload(e->stream, ti));
+        GCHK(e->d_w.upload(e->stream, tw));
+        HIPCHK(hipStreamSynchronize(e->stream));
+    }
+    *out = guard.release();
+    return GMRF_OK;
+}
+
+static bool eval_npts_ok(int64_t npts) { return npts >= 1 && npts <= (1 << 28); }
+
+gmrf_status gmrf_eval_line_create(int32_t device, void* stream, int64_t nc, int32_t order, int32_t bc, double length, int64_t npts,
+                                  const double* points, gmrf_eval** out) {
+    const bool dirichlet = bc == GMRF_BURGERS_DIRICHLET;
+    if (!out) return bad_shape("null pointer");
+    if (order != 1 && order != 2) return bad_shape("order must be 1 or 2");
+    if (bc != GMRF_BURGERS_PERIODIC && !dirichlet) return bad_shape("bc must be periodic or dirichlet");
+    if (!(length > 0.0) || !std::isfinite(length)) return bad_shape("length must be positive");
+    if (nc < (dirichlet ? 2 : 3) || nc > (1 << 24)) return bad_shape("nc: >= 3 cells, >= 2 on the Dirichlet interval (<= 2^24)");
+    if (!eval_npts_ok(npts)) return bad_shape("npts must lie in [1, 2^28]");
+    if (!points) return bad_shape("null pointer");
+    for (int64_t c = 0; c < npts; ++c) {
+        const double x = points[c];
+        if (!std::isfinite(x) || x < 0.0 || !(dirichlet ? x <= length : x < length))
+            return eval_bad_point(c, std::to_string(x), dirichlet ? "[0, length]" : "[0, length)");
+    }
+    std::unique_ptr<gmrf_eval, gmrf_status (*)(gmrf_eval*)> guard(new gmrf_eval(), gmrf_eval_destroy);
+    gmrf_eval* e = guard.get();
+    e->ns = order * nc + (dirichlet ? 1 : 0); e->npts = npts; e->width = order + 1;
+    e->idx.resize((size_t)(npts * e->width)); e->w.resize((size_t)(npts * e->width));
+    const double h = length / (double)nc;
+    for (int64_t c = 0; c < npts; ++c)
+        field_eval_line_row(order, nc, e->ns, h, points[c], &e->idx[(size_t)(c * e->width)], &e->w[(size_t)(c * e->width)]);
+    return eval_finish(guard, device, stream, "gmrf_eval_line_create", out);
+}
+
+gmrf_status gmrf_eval_tri_create(int32_t device, void* stream, int64_t nx, int64_t ny, int32_t order, int64_t npts, const double* xy,
+                                 gmrf_eval** out) {
+    if (!out) return bad_shape("null pointer");
+    if (order != 1 && order != 2) return bad_shape("order must be 1 or 2");
+    if (nx < 2 || ny < 2 || nx > 16384 || ny > 16384) return bad_shape("nx, ny must lie in [2, 16384]");
+    if (!eval_npts_ok(npts)) return bad_shape("npts must lie in [1, 2^28]");
+    if (!xy) return bad_shape("null pointer");
+    for (int64_t c = 0; c < npts; ++c) {
+        const double x = xy[2 * c], y = xy[2 * c + 1];
+        if (!std::isfinite(x) || !std::isfinite(y) || x < 0.0 || x > 1.0 || y < 0.0 || y > 1.0)
+            return eval_bad_point(c, "(" + std::to_string(x) + ", " + std::to_string(y) + ")", "[0, 1]^2");
+    }
+    std::unique_ptr<gmrf_eval, gmrf_status (*)(gmrf_eval*)> guard(new gmrf_eval(), gmrf_eval_destroy);
+    gmrf_eval* e = guard.get();
+    e->ns = order == 1 ? nx * ny : (2 * nx - 1) * (2 * ny - 1); e->npts = npts; e->width = order == 1 ? 3 : 6;
+    e->idx.resize((size_t)(npts * e->width)); e->w.resize((size_t)(npts * e->width));
+    for (int64_t c = 0; c < npts; ++c)
+        field_eval_tri_row(order, nx, ny, xy[2 * c], xy[2 * c + 1], &e->idx[(size_t)(c * e->width)], &e->w[(size_t)(c * e->width)]);
+    return eval_finish(guard, device, stream, "gmrf_eval_tri_create", out);
+}
+
+gmrf_status gmrf_eval_rows(const gmrf_eval* e, int64_t* ns_out, int64_t* width_out, int64_t* idx, double* w) {
+    if (!e) return bad_shape("null handle");
+    if (ns_out) *ns_out = e->ns;
+    if (width_out) *width_out = e->width;
+    if (idx) std::copy(e->idx.begin(), e->idx.end(), idx);
+    if (w) std::copy(e->w.begin(), e->w.end(), w);
+    return GMRF_OK;
+}
+
+// rows is looped over inside the kernel: grid.y stays under its cap of 65 535
+static gmrf_status launch_eval_apply(const gmrf_eval* e, int64_t rows, const double* d_fields, double* d_pred) {
+    const dim3 grid((unsigned)((e->npts + 255) / 256), (unsigned)std::min<int64_t>(rows, 65535));
+    auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, e->stream, e->d_idx.get(), e->d_w.get(), e->npts, e->ns, rows, d_fields, d_pred);
+    };
+    if (e->width == 2) go(field_eval_apply<2>);
+    else if (e->width == 3) go(field_eval_apply<3>);
+    else go(field_eval_apply<6>);
+    HIPCHK(hipGetLastError());
+    return GMRF_OK;
+}
+
+gmrf_status gmrf_eval_apply_batch(gmrf_eval* e, int64_t rows, const double* fields, double* pred_out) {
+    if (!e) return bad_shape("null handle");
+    if (!fields || !pred_out) return bad_shape("null pointer");
+    if (rows < 1 || rows > (1 << 24)) return bad_shape("rows outside [1, 2^24]");
+    GCHK(e->ready("gmrf_eval_apply_batch needs the device"));
+    const double* d_fields;
+    double* d_pred;
+    Staging args(e->arena);
+    args.in(fields, sizeof(double) * rows * e->ns, &d_fields);
+    args.out(pred_out, sizeof(double) * rows * e->npts, &d_pred);
+    GCHK(args.commit(e->stream));
+    GCHK(launch_eval_apply(e, rows, d_fields, d_pred));
+    GCHK(args.flush(e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return GMRF_OK;
+}
+
+gmrf_status gmrf_eval_errors_batch(gmrf_eval* e, int64_t batch, int64_t nt, int64_t first_slice, const double* fields,
+                                   const double* truth, double* errors_out, double* pred_out) {
+    if (!e) return bad_shape("null handle");
+    if (!fields || !truth || !errors_out) return bad_shape("null pointer");
+    if (!batch_ok(batch)) return bad_shape("batch outside [1, 4096]");
+    if (nt < 1 || first_slice < 0 || first_slice >= nt || nt > (int64_t)0x7fffffff / e->npts)
+        return bad_shape("the slices [first_slice, nt) must not be empty (nt npts < 2^31)");
+    GCHK(e->ready("gmrf_eval_errors_batch needs the device"));
+    const hipStream_t st = e->stream;
+    const int64_t n = nt * e->npts, first = first_slice * e->npts, count = n - first, nch = field_errors_chunks(count),
+                  len = (count + nch - 1) / nch;
+    const double *d_fields, *d_truth;
+    double *d_err, *d_pred;
+    Staging args(e->arena);
+    args.in(fields, sizeof(double) * batch * nt * e->ns, &d_fields);
+    args.in(truth, sizeof(double) * batch * n, &d_truth);
+    args.out(errors_out, sizeof(double) * batch * 3, &d_err);
+    args.out(pred_out, sizeof(double) * batch * n, &d_pred);
+    GCHK(args.commit(st));
+    GCHK(e->part.reserve(st, sizeof(double) * (size_t)(batch * nch * 3)));
+    if (d_pred) {
+        // the caller wants pred: it is written once by the apply kernel and the metrics read it
+        GCHK(launch_eval_apply(e, batch * nt, d_fields, d_pred));
+        GCHK(launch_field_errors_batch(st, batch, n, first, d_pred, d_truth, e->part.as<double>(), d_err));
+    } else {
+        const dim3 grid((unsigned)nch, (unsigned)batch);
+        auto go = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, e->d_idx.get(), e->d_w.get(), e->npts, e->ns, nt, d_fields, d_truth, first,
+                               len, e->part.as<double>());
+        };
+        if (e->width == 2) go(field_eval_errors_part<2>);
+        else if (e->width == 3) go(field_eval_errors_part<3>);
+        else go(field_eval_errors_part<6>);
+        hipLaunchKernelGGL(field_errors_finish, dim3(1, (unsigned)batch), dim3(256), 0, st, e->part.as<double>(), nch, count, d_err);
+        HIPCHK(hipGetLastError());
+    }
+    GCHK(args.flush(st));
+    HIPCHK(hipStreamSynchronize(st));
+    return GMRF_OK;
 }
 
 // --------------------------------------------------------------------------------- the posterior stage of the Gauss-Newton driver

@@ -415,6 +415,19 @@ def solution_errors(pred, soln) -> dict:
             "rel_err": float(np.linalg.norm(d) / np.linalg.norm(soln))}
 
 
+def darcy_pred_coords(x_coords, y_coords) -> np.ndarray:
+    """(len(x) len(y), 2) points of a data grid in the order of the Darcy script's `pred_coords`
+    (scripts/darcy/solve_darcy_gmrf-fem.jl:82): x outer, y inner -- the `xy` of `FieldEvaluator.triangles`."""
+    x, y = np.asarray(x_coords, dtype=np.float64).reshape(-1), np.asarray(y_coords, dtype=np.float64).reshape(-1)
+    return np.stack([np.repeat(x, y.size), np.tile(y, x.size)], axis=1)
+
+
+def burgers_pred_coords(x_coords) -> np.ndarray:
+    """(len(x),) points of a data grid as the Burgers scripts' `pred_coords` (scripts/burgers/solve_burgers_gmrf-fem.jl:75) -- the
+    `points` of `FieldEvaluator.line`."""
+    return np.ascontiguousarray(x_coords, dtype=np.float64).reshape(-1).copy()
+
+
 # --------------------------------------------------------------------------- 1-D space-time
 
 def p1_periodic_line(ns: int):

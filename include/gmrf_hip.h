@@ -711,6 +711,48 @@ gmrf_status gmrf_bic_run(gmrf_bic* g, const double* ic, double* x_ic_out, double
 gmrf_status gmrf_field_errors_batch(int32_t device, void* stream, int64_t batch, int64_t n, int64_t first, const double* pred,
                                     const double* soln, double* out);
 
+/* FEM fields at the points of a data grid: E = evaluation_matrix(disc, pred_coords) of the data-set loops
+ * (scripts/darcy/solve_darcy_gmrf-fem.jl:82-89, scripts/burgers/solve_burgers_gmrf-fem.jl:75-83; A_ic of :114-115 is the same operator at
+ * the initial condition's coordinates), pred = E f on the device, and the metrics of pred against a truth in the same pass.
+ * The rows of E are computed once at creation, on the host, in double precision; points / xy are HOST arrays in any order
+ * (duplicates, several points in a cell and cells without a point are fine).  device -1: a handle for gmrf_eval_rows only.
+ *   Line (the meshes of gmrf_burgers_line_create): nc cells of h = length / nc, order 1 or 2, bc GMRF_BURGERS_PERIODIC (ns = order nc
+ *     dofs, points in [0, length)) or GMRF_BURGERS_DIRICHLET (ns = order nc + 1, points in [0, length]), dofs numbered by position.
+ *     e = min(floor(x / h), nc - 1), xi = 2 (x - e h) / h - 1 clamped to [-1, 1].  Order 1: ((1 - xi) / 2, (1 + xi) / 2) on the dofs
+ *     (e, (e + 1) mod ns); order 2: (xi (xi - 1) / 2, xi (xi + 1) / 2, 1 - xi^2) on (2e, (2e + 2) mod ns, 2e + 1), the shape functions
+ *     of gmrf_burgers_colloc_create.
+ *   Triangles (the meshes of gmrf_darcy_p1_create / _p2_create, the elliptic and the shallow-water handles): nx x ny vertices on the
+ *     unit square, x fastest, quads cut by the diagonal n00 - n11; points in [0, 1]^2 as xy [npts][2].  hx = 1 / (nx - 1),
+ *     qx = min(floor(x / hx), nx - 2), s = (x - qx hx) / hx clamped to [0, 1]; qy and t likewise.  t <= s: the lower triangle
+ *     (n00, n10, n11) with barycentrics (1 - s, s - t, t); otherwise the upper one (n00, n11, n01) with (1 - t, s, t - s).  Order 1:
+ *     the barycentrics on the vertices i + nx j.  Order 2 (dofs: the (2 nx - 1) x (2 ny - 1) lattice, x fastest): l (2 l - 1) at the
+ *     lattice point 2 V of vertex V and 4 la lb at Va + Vb of the edge between Va and Vb.
+ * A row holds width = 2, 3, 3 or 6 entries in ASCENDING dof index; a weight that is exactly 0.0 (a point on a vertex or an edge) is
+ * stored.  gmrf_eval_rows: ns, width, idx [npts][width] (0-based) and w [npts][width], each NULL (not wanted) or HOST memory.
+ * GMRF_ERR_BAD_SHAPE for another order or bc, length <= 0, nc < 3 (periodic) / < 2 (dirichlet), nx or ny < 2, npts < 1, and for a
+ * point that is not finite or outside the domain -- gmrf_last_error names its index.  Upper limits (32-bit dof indices on the
+ * device): nc <= 2^24, nx, ny <= 16384, npts <= 2^28.
+ * gmrf_eval_apply_batch: pred_out [rows][npts] = E fields [rows][ns], rows in [1, 2^24] spatial fields (means, samples, or the
+ * slices of space-time fields: spatial_to_spatiotemporal without the nt times larger matrix).  ONE rounding sequence,
+ *     pred = w0 f[idx0], then pred = fma(wk, f[idxk], pred) for k = 1 .. width - 1 in the stored order,
+ * so a result is the same bits in every batch, for every `rows` and on every call.
+ * gmrf_eval_errors_batch: fields [batch][nt][ns] against truth [batch][nt][npts] -> errors_out [batch][3] = (rel_err, rmse, max_err)
+ * over the slices [first_slice, nt) (first_slice = 1: the scripts' [2:end, :]), bitwise what gmrf_eval_apply_batch followed by
+ * gmrf_field_errors_batch(batch, n = nt npts, first = first_slice npts) gives; pred_out NULL or [batch][nt][npts], the bits of
+ * gmrf_eval_apply_batch -- without it nothing of that size is written.  batch in [1, 4096], nt >= 1, 0 <= first_slice < nt,
+ * nt npts < 2^31.  fields, truth, pred_out, errors_out: host or device.  Both calls run on the handle's stream and synchronise
+ * before they return; GMRF_ERR_NO_DEVICE on a device -1 handle. */
+typedef struct gmrf_eval gmrf_eval;
+gmrf_status gmrf_eval_line_create(int32_t device, void* stream, int64_t nc, int32_t order, int32_t bc, double length, int64_t npts,
+                                  const double* points, gmrf_eval** out);
+gmrf_status gmrf_eval_tri_create(int32_t device, void* stream, int64_t nx, int64_t ny, int32_t order, int64_t npts, const double* xy,
+                                 gmrf_eval** out);
+gmrf_status gmrf_eval_destroy(gmrf_eval* e);
+gmrf_status gmrf_eval_rows(const gmrf_eval* e, int64_t* ns_out, int64_t* width_out, int64_t* idx, double* w);
+gmrf_status gmrf_eval_apply_batch(gmrf_eval* e, int64_t rows, const double* fields, double* pred_out);
+gmrf_status gmrf_eval_errors_batch(gmrf_eval* e, int64_t batch, int64_t nt, int64_t first_slice, const double* fields,
+                                   const double* truth, double* errors_out, double* pred_out);
+
 /* Tangent, residual and load of the nonlinear elliptic benchmark -Lap u + u^3 = f_src (FEM block assembly, fourth piece;
  * /root/reference/_research/elliptic_chen24.jl) as its Gauss-Newton loop evaluates them per iteration (f_and_J, :280-285):
  *     J(w) = J_static + J_cube(w),  J_static[i][j] = int grad(phi_i).grad(phi_j)   (assemble_J_diff_and_f, :179-228)

@@ -32,7 +32,8 @@ using SparseArrays, LinearAlgebra
 export TridiagonalCholeskyFactor, tridiagonal_cholesky, forward_solve, backward_solve, ldiv, PosteriorAssembler, GmrfCsr,
        GmrfComm, DarcyP1Assembler, BurgersP1Tangent, BurgersCollocationTangent, EllipticP1Tangent, elliptic_load!, GaussNewtonBatch, gauss_newton_batch!, DarcyConditioningBatch,
        BurgersP1Prior, BurgersLinePrior, prior_values_batch!, BurgersInitialConditionBatch, initial_condition_batch, solution_errors_batch,
-       condition_on_observations_batch, assemble_batch!, logdet_batch, quadform_batch!, posterior!
+       condition_on_observations_batch, assemble_batch!, logdet_batch, quadform_batch!, posterior!,
+       FieldEvaluator, FieldEvaluatorLine, FieldEvaluatorTriangles, evaluation_rows, evaluation_matrix, evaluate_fields, evaluation_errors
 
 const libgmrf = get(ENV, "LIBGMRF_HIP", joinpath(@__DIR__, "..", "diffeqgmrfs.jl_amd", "csrc", "libgmrf_hip.so"))
 
@@ -929,6 +930,88 @@ function solution_errors_batch(pred::Matrix{Float64}, soln::Matrix{Float64}; fir
         (Int32, Ptr{Cvoid}, Int64, Int64, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
         device, C_NULL, size(pred, 2), size(pred, 1), first, pred, soln, out))
     return out
+end
+
+# FEM fields at the points of a data grid: E = evaluation_matrix(disc, pred_coords) of the data-set loops
+# (scripts/darcy/solve_darcy_gmrf-fem.jl:82-89, scripts/burgers/solve_burgers_gmrf-fem.jl:75-83) as `width` (dof, weight) pairs per
+# point, computed once at creation on the host; `apply` and `errors` run on the device.  device = -1: `evaluation_rows` only.
+mutable struct FieldEvaluator
+    handle::Ptr{Cvoid}
+    ns::Int
+    npts::Int
+    width::Int
+end
+
+function _field_evaluator(h::Ptr{Cvoid}, npts::Integer)
+    ns = Ref{Int64}(0); width = Ref{Int64}(0)
+    check(ccall((:gmrf_eval_rows, libgmrf), Int32, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}, Ptr{Int64}, Ptr{Float64}), h, ns, width, C_NULL, C_NULL))
+    e = FieldEvaluator(h, ns[], npts, width[])
+    finalizer(x -> ccall((:gmrf_eval_destroy, libgmrf), Int32, (Ptr{Cvoid},), x.handle), e)
+    return e
+end
+
+"the lines of `BurgersP1Tangent`: `nc` cells of `length / nc`; `points` in [0, length) (`:periodic`) or [0, length] (`:dirichlet`)"
+function FieldEvaluatorLine(nc::Integer, points::Vector{Float64}; order::Integer = 2, bc::Symbol = :periodic, length::Real = 1.0,
+                            device::Integer = 0, stream::Ptr{Cvoid} = C_NULL)
+    bcs = Dict(:periodic => 0, :dirichlet => 1)
+    haskey(bcs, bc) || throw(ArgumentError("bc :periodic or :dirichlet"))
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve points check(ccall((:gmrf_eval_line_create, libgmrf), Int32,
+        (Int32, Ptr{Cvoid}, Int64, Int32, Int32, Float64, Int64, Ptr{Float64}, Ref{Ptr{Cvoid}}),
+        device, stream, nc, Int32(order), Int32(bcs[bc]), Float64(length), Base.length(points), points, h))
+    return _field_evaluator(h[], Base.length(points))
+end
+
+"the triangle meshes of `DarcyP1Assembler` / `EllipticP1Tangent`: `nx x ny` vertices on the unit square; `xy` (2 x npts) in [0, 1]^2"
+function FieldEvaluatorTriangles(nx::Integer, ny::Integer, xy::Matrix{Float64}; order::Integer = 1, device::Integer = 0,
+                                 stream::Ptr{Cvoid} = C_NULL)
+    size(xy, 1) == 2 || throw(ArgumentError("xy must be 2 x npts"))
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve xy check(ccall((:gmrf_eval_tri_create, libgmrf), Int32,
+        (Int32, Ptr{Cvoid}, Int64, Int64, Int32, Int64, Ptr{Float64}, Ref{Ptr{Cvoid}}),
+        device, stream, nx, ny, Int32(order), size(xy, 2), xy, h))
+    return _field_evaluator(h[], size(xy, 2))
+end
+
+"`(idx (width x npts, 1-based dofs, ascending), w (width x npts))`: the rows of E, zeros stored"
+function evaluation_rows(e::FieldEvaluator)
+    idx = Matrix{Int64}(undef, e.width, e.npts); w = Matrix{Float64}(undef, e.width, e.npts)
+    ns = Ref{Int64}(0); width = Ref{Int64}(0)
+    check(ccall((:gmrf_eval_rows, libgmrf), Int32, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}, Ptr{Int64}, Ptr{Float64}), e.handle, ns, width, idx, w))
+    return idx .+ 1, w
+end
+
+"`E` as a sparse matrix (npts x ns), the reference's `evaluation_matrix`"
+function evaluation_matrix(e::FieldEvaluator)
+    idx, w = evaluation_rows(e)
+    return sparse(repeat(1:e.npts, inner = e.width), vec(idx), vec(w), e.npts, e.ns)
+end
+
+"`fields` (ns x rows) -> `pred` (npts x rows): every column one spatial field (a mean, a sample, a slice of a space-time field)"
+function evaluate_fields(e::FieldEvaluator, fields::Matrix{Float64})
+    size(fields, 1) == e.ns || throw(DimensionMismatch("fields must be ns x rows"))
+    pred = Matrix{Float64}(undef, e.npts, size(fields, 2))
+    GC.@preserve fields pred check(ccall((:gmrf_eval_apply_batch, libgmrf), Int32, (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}),
+        e.handle, size(fields, 2), fields, pred))
+    return pred
+end
+
+"""
+    evaluation_errors(e, fields, truth; nt = 1, first_slice = 0, return_pred = false)
+
+`fields` (nt ns x B) against `truth` (nt npts x B): `(rel_err, rmse, max_err)` per problem (3 x B) over the slices
+`first_slice + 1 : nt` (`first_slice = 1` is the scripts' `[2:end, :]`), bitwise `solution_errors_batch` of `evaluate_fields`.
+"""
+function evaluation_errors(e::FieldEvaluator, fields::Matrix{Float64}, truth::Matrix{Float64}; nt::Integer = 1,
+                           first_slice::Integer = 0, return_pred::Bool = false)
+    B = size(fields, 2)
+    (size(fields, 1) == nt * e.ns && size(truth) == (nt * e.npts, B)) || throw(DimensionMismatch("fields nt ns x B, truth nt npts x B"))
+    out = Matrix{Float64}(undef, 3, B)
+    pred = return_pred ? Matrix{Float64}(undef, nt * e.npts, B) : nothing
+    GC.@preserve fields truth out pred check(ccall((:gmrf_eval_errors_batch, libgmrf), Int32,
+        (Ptr{Cvoid}, Int64, Int64, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+        e.handle, B, nt, first_slice, fields, truth, out, return_pred ? pointer(pred) : Ptr{Float64}(C_NULL)))
+    return return_pred ? (out, pred) : out
 end
 
 # Linear shallow-water SPDE (src/spdes/shallow_water.jl): element kernels of assemble_system! (:17-122) and the per-step

@@ -53,6 +53,7 @@ EXPORTS = [
     "gmrf_test_mfma_f64_rate", "gmrf_test_hbm_rate", "gmrf_test_microbench", "gmrf_test_symbolic_csc", "gmrf_test_envelope_csc",
     "gmrf_test_spmm_plan", "gmrf_test_spmm_route", "gmrf_test_spmm_rows_batch",
     "gmrf_test_sweep_route", "gmrf_test_sweep_product",
+    "gmrf_test_coupling_plan", "gmrf_test_coupling_group_tiles", "gmrf_test_coupling_product",
 ]
 
 
@@ -263,6 +264,9 @@ def load() -> C.CDLL:
         "gmrf_test_spmm_rows_batch": [vp, i64, vp, vp, i64, i64, vp, i64, i64, i64, i32],
         "gmrf_test_sweep_route": [vp, vp],
         "gmrf_test_sweep_product": [i32, i32, vp, vp, i64, vp, i64, i64, i64, i64, vp, i64, vp, i64, P(i32)],
+        "gmrf_test_coupling_plan": [i64, i64, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+        "gmrf_test_coupling_group_tiles": [vp, i32],
+        "gmrf_test_coupling_product": [vp, i64, i32, vp, vp, i64, vp, i64, vp, i64, vp],
     }
     for name, args in sigs.items():
         fn = getattr(lib, name)

@@ -161,6 +161,7 @@ struct gmrf_handle : DevCtx {
     // tile plan of the sparse C = B X^T (spmm_bxt_tiles): per lower block and 64-row tile the distinct columns, per entry its index into them
     DevArr<int> d_bxt_uptr, d_bxt_ucols; DevArr<uint16_t> d_bxt_lidx; DevArr<int> d_bxt_gtiles;
     std::vector<int> bxt_ng;           // groups of row tiles per lower block (host copy: the launch's grid)
+    int group_tiles_force = -1;        // test hook (gmrf_test_coupling_group_tiles): the next analysis groups tiles (1) / keeps every tile alone (0); -1: by the batch
     int bxt_ecap = 0; int bxt_nrt = 0; bool bxt_plan_ok = false;        // [N][bsp + 1] row-wise view of the lower blocks' entry lists
     int64_t lo_row_max = 0;            // most entries in one row of a lower block
     bool sparse_b = false;             // lower blocks are sparse enough for C = B X^T by spmm_bxt
@@ -537,6 +538,19 @@ static inline double* l_block(const gmrf_handle* h, int64_t i) { return h->d_L +
 // Layout of the coupling blocks (see gmrf_handle): validates, derives mend / the accounting sums and
 // uploads the per-tile bounds.  kst_abs[t]: first non-zero column of row tile t (absolute, any value;
 // it is rounded down to 64 and replaced by its monotone envelope).  Needs set_shape first.
+// (host only: gmrf_test_coupling_plan reaches it without a device)
+static void layout_kst(int64_t bsp, int64_t cmin, int64_t rmax, const std::vector<int64_t>& kst_abs, std::vector<int>& kst) {
+    const int nrt = (int)(rmax / 64), ntile = (int)(bsp / 64);
+    kst.assign((size_t)ntile, 0);
+    int64_t run = bsp - 64;                                   // envelope from the bottom: kst[t] = min over t' >= t
+    for (int t = nrt - 1; t >= 0; --t) {
+        int64_t v = std::min(std::max(kst_abs[t], cmin), bsp - 64);
+        run = std::min(run, (v / 64) * 64);
+        kst[t] = (int)(run - cmin);
+    }
+    if (nrt > 0) kst[0] = 0;                                  // cmin is the smallest start by definition
+    for (int t = nrt; t < ntile; ++t) kst[t] = (int)(bsp - cmin);         // rows below rmax: empty
+}
 static gmrf_status set_layout(gmrf_handle* h, int64_t cmin, int64_t rmax, const std::vector<int64_t>& kst_abs) {
     const int64_t bsp = h->bsp;
     if (cmin < 0 || cmin >= bsp || cmin % 64 || rmax <= 0 || rmax > bsp || rmax % 64) return bad_shape("bad coupling-block layout");
@@ -547,15 +561,7 @@ static gmrf_status set_layout(gmrf_handle* h, int64_t cmin, int64_t rmax, const 
     h->cmin = cmin; h->rmax = rmax;
     h->layout_gen++;
     h->env_ok = false;                                        // (the envelope bounds belong to the analysed pattern's layout: upload_envelope)
-    h->kst.assign((size_t)ntile, 0);
-    int64_t run = bsp - 64;                                   // envelope from the bottom: kst[t] = min over t' >= t
-    for (int t = nrt - 1; t >= 0; --t) {
-        int64_t v = std::min(std::max(kst_abs[t], cmin), bsp - 64);
-        run = std::min(run, (v / 64) * 64);
-        h->kst[t] = (int)(run - cmin);
-    }
-    if (nrt > 0) h->kst[0] = 0;                               // cmin is the smallest start by definition
-    for (int t = nrt; t < ntile; ++t) h->kst[t] = (int)(bsp - cmin);      // rows below rmax: empty
+    layout_kst(bsp, cmin, rmax, kst_abs, h->kst);
     h->mend.assign((size_t)ntile, (int)rmax);
     for (int u = 0; u < nct; ++u) {
         int m = 0;
@@ -940,7 +946,7 @@ static gmrf_status upload_entries(gmrf_handle* h, const std::vector<std::vector<
     SymbolicPlan sp;
     // (tile groups for batches: one problem alone has too few workgroups as it is -- 48 chunks x 12 tiles = 576 of 768 slots -- and
     //  a third of them doing three tiles' rows each is slower: 7.1 -> 9.7 us per block on darcy256)
-    build_symbolic(N, h->bsp, dg, lo, h->sw(GMRF_SW_NO_STAIRCASE), sp, h->B >= 8);
+    build_symbolic(N, h->bsp, dg, lo, h->sw(GMRF_SW_NO_STAIRCASE), sp, h->group_tiles_force >= 0 ? h->group_tiles_force != 0 : h->B >= 8);
     h->diag_first = sp.diag_first; h->diag_count = sp.diag_count; h->low_first = sp.low_first; h->low_count = sp.low_count;
     const auto& keys = sp.keys; const auto& src = sp.src;
     GCHK(set_layout(h, sp.cmin, sp.rmax, sp.first));
@@ -1596,22 +1602,178 @@ static gmrf_status potrf_block(gmrf_handle* h, double* S, double* L, double* X, 
     return GMRF_OK;
 }
 
-// The coupling products C = B X^T of this handle's blocks run on spmm_bxt_tiles: sparse lower blocks, not forced onto the dense GEMM,
-// and a tile plan that covers the coupling rows.  (GMRF_BXT_TILES=0 keeps spmm_bxt: the tests' bitwise reference.)
-static bool coupling_on_tiles(const gmrf_handle* h) {
-    static const bool no_tiles = env_int("GMRF_BXT_TILES", 1) == 0;
-    return h->sparse_b && !h->sw(GMRF_SW_DENSE_COUPLING) && h->bxt_plan_ok && !no_tiles && h->bxt_nrt == (int)h->rmax / 64;
-}
+// ---- The coupling step of block i > 0 as a value: C_i = B_i Linv_{i-1}^T and whoever clears the Schur block S before S = D_i - C C^T.
+// coupling_route decides (host only: gmrf_test_coupling_plan asks it without a device), launch_coupling issues what it says and
+// nothing else; factor_blocks_range calls the two, gmrf_test_coupling_product the second with a forced or overridden route.
+enum CouplingKind { COUPLING_DENSE = 0, COUPLING_BXT = 1, COUPLING_TILES = 2 };
+// who clears S: nobody (rm == bsp: the product writes every row), zero_rows (a launch of its own, rows >= rm), the zero role of
+// spmm_bxt_tiles (rows >= rm), its scatter role (one problem: the whole block, then D_i's entries)
+enum CouplingFill { FILL_NONE = 0, FILL_ZERO_ROWS = 1, FILL_ZERO_ROLE = 2, FILL_SCATTER_ROLE = 3 };
+struct CouplingShape {
+    int bsp = 0, bs = 0, cm = 0, rm = 0, nb = 1, cus = 0;
+    bool sparse_b = false;      // rows of at most 32 entries (build_symbolic)
+    bool plan_ok = false;       // a tile plan that covers the coupling rows
+    bool has_drow = false;      // D_i's entries row by row are on the device (the scatter role reads them)
+    int max_row = 0, ng = 0;    // longest row of a lower block; groups of row tiles of THIS block
+    int32_t switches = 0;
+};
+struct CouplingRoute {
+    int kind = COUPLING_DENSE;
+    int km = 0, cw = 0;                     // spmm_bxt<km>, columns per workgroup
+    int nch = 0, ncg = 0, ng = 0;           // spmm_bxt_tiles: 16-column chunks per workgroup, column groups, tile groups
+    int grid = 0;                           // workgroups of the product's launch (0: the GEMM's own)
+    int fill = FILL_NONE, zwgs = 0;
+    int skip_dead = 0;
+};
+static const int kBxtNch[] = {1, 2, 3, 4, 6, 8, 12, 16, 24, 48};
 
-static gmrf_status factor_blocks_range(gmrf_handle* h, int64_t i0, int64_t i1) {
+// workgroups of the product's launch for the fields as they stand
+static void coupling_grid(const CouplingShape& s, CouplingRoute& r) {
+    const int W = s.bsp - s.cm, rch = (s.rm + 255) / 256;
+    if (r.kind == COUPLING_BXT) r.grid = (W / r.cw) * rch * s.nb;
+    else if (r.kind == COUPLING_TILES) { r.ncg = (W / 16 + r.nch - 1) / r.nch; r.grid = (r.ncg * r.ng + r.zwgs) * s.nb; }
+    else r.grid = 0;
+}
+static int coupling_zero_wgs(const CouplingShape& s) {        // the zero role: >= 128 KB per workgroup
+    const int64_t zcount = (int64_t)(s.bsp - s.rm) * s.bsp;
+    return (int)std::min<int64_t>(32, std::max<int64_t>(1, zcount / 16384));
+}
+// every field of the route once the kernel family is chosen (its preconditions are the caller's to check)
+static CouplingRoute coupling_route_of(const CouplingShape& s, int kind) {
+    CouplingRoute r;
+    r.kind = kind;
+    const int W = s.bsp - s.cm, rch = (s.rm + 255) / 256, nb = s.nb;
+    if (kind == COUPLING_TILES) {
+        static const bool live_skip = env_int("GMRF_BXT_LIVE", 0) != 0;      // tuning aid (measured: 4.1 vs 3.9 ms per step, off)
+        r.skip_dead = live_skip ? 1 : 0;
+        const int chunks = W / 16;
+        r.ng = s.ng;
+        // 16-column chunks per workgroup: the launch should be a whole number of rounds over the 3 workgroups a CU
+        // holds (measured, darcy256 x 64, 4 groups x 48 chunks: 16 chunks = 768 workgroups = one round 85 us; 8 =
+        // two rounds 96 us; 12 = 1.33 rounds 108 us; 24 = 2/3 round 99 us): rounds x (chunks + ~2 for the prologue)
+        const int64_t slots = 3 * (int64_t)std::max(s.cus, 1);
+        int best = 1; int64_t best_cost = INT64_MAX;
+        for (int c : kBxtNch) {
+            if (c > chunks) break;
+            const int64_t wgs = (int64_t)((chunks + c - 1) / c) * r.ng * nb;
+            const int64_t cost = ((wgs + slots - 1) / slots) * (c + 2);
+            if (cost < best_cost || (cost == best_cost && c < best)) { best = c; best_cost = cost; }
+        }
+        r.nch = best;
+        // (round 5: the launch clears the Schur block as well) one problem: the WHOLE block, and D_i scattered into it
+        if (nb == 1 && s.has_drow && s.bsp == s.bs && !(s.switches & GMRF_SW_NO_SCATTER_FOLD)) { r.fill = FILL_SCATTER_ROLE; r.zwgs = 64; }
+        else if (s.rm < s.bsp && ((int64_t)(s.bsp - s.rm) * s.bsp) % 2 == 0) { r.fill = FILL_ZERO_ROLE; r.zwgs = coupling_zero_wgs(s); }
+        else if (s.rm < s.bsp) r.fill = FILL_ZERO_ROWS;
+    } else {
+        if (kind == COUPLING_BXT) {
+            r.km = s.max_row <= 8 ? 8 : (s.max_row <= 16 ? 16 : 32);
+            r.cw = ((int64_t)(W / 64) * rch * nb >= 512) ? 64 : (((int64_t)(W / 32) * rch * nb >= 512) ? 32 : 16);
+        }
+        if (s.rm < s.bsp) r.fill = FILL_ZERO_ROWS;
+    }
+    coupling_grid(s, r);
+    return r;
+}
+// The route rule: sparse lower blocks, not forced onto the dense GEMM, go to spmm_bxt_tiles where a tile plan covers the coupling
+// rows, else to spmm_bxt.  (GMRF_BXT_TILES=0 keeps spmm_bxt: the tests' bitwise reference.)
+static CouplingRoute coupling_route(const CouplingShape& s) {
+    static const bool no_tiles = env_int("GMRF_BXT_TILES", 1) == 0;
+    const bool sparse_g1 = s.sparse_b && !(s.switches & GMRF_SW_DENSE_COUPLING);
+    return coupling_route_of(s, !sparse_g1 ? COUPLING_DENSE : (s.plan_ok && !no_tiles ? COUPLING_TILES : COUPLING_BXT));
+}
+static CouplingShape coupling_shape(const gmrf_handle* h, int64_t i) {
+    CouplingShape s;
+    s.bsp = (int)h->bsp; s.bs = (int)h->bs; s.cm = (int)h->cmin; s.rm = (int)h->rmax; s.nb = (int)h->B; s.cus = h->cu_count;
+    s.sparse_b = h->sparse_b;
+    s.plan_ok = h->bxt_plan_ok && h->bxt_nrt == (int)h->rmax / 64;
+    s.has_drow = (bool)h->d_dg_rowptr;
+    s.max_row = (int)h->lo_row_max;
+    s.ng = (s.plan_ok && i >= 0 && (size_t)i < h->bxt_ng.size()) ? h->bxt_ng[(size_t)i] : 0;
+    s.switches = h->switches;
+    return s;
+}
+static CouplingRoute coupling_route(const gmrf_handle* h, int64_t i) { return coupling_route(coupling_shape(h, i)); }
+
+// Block i > 0, everything up to (not including) S = -C C^T: the Schur block's zero fill, whoever does it; the dense image of B_i
+// for the GEMM route; the product C_i = B_i Linv_{i-1}^T into the stored window of d_C.
+static gmrf_status launch_coupling(gmrf_handle* h, int64_t i, const CouplingRoute& r) {
     const int bsp = (int)h->bsp;
-    const bool bxt_tiles = coupling_on_tiles(h);
-    h->xsplit = planned_xsplit(h);                     // representation of the inverses this factorisation leaves
     const int64_t ld = bsp;
     const size_t blk_bytes = (size_t)bsp * bsp * sizeof(double) * (size_t)h->B;
     const int64_t bstride = (int64_t)bsp * bsp;
     const int64_t pX = stride_pX(h), pC = stride_pC(h);
     const int64_t ldc = c_ld(h), cstride = c_blk(h);
+    const unsigned nb = (unsigned)h->B;
+    const int cm = (int)h->cmin, rm = (int)h->rmax;
+    const int W = bsp - cm;
+    if (r.fill == FILL_ZERO_ROWS) {
+        const int64_t cnt = (int64_t)(bsp - rm) * bsp;
+        hipLaunchKernelGGL(zero_rows, dim3((unsigned)((cnt / 2 + 255) / 256), nb), dim3(256), 0, h->stream,
+                           h->d_S + (int64_t)rm * ld, cnt, bstride);
+        HIPCHK(hipGetLastError());
+    }
+    double* C = h->d_C + (i - 1) * cstride;              // stored window: rows 0 .. rm, columns cm ..
+    const double* Xp = h->d_Linv + (i - 1) * bstride;
+    if (r.kind == COUPLING_DENSE) {          // dense image of B for the GEMM route
+        HIPCHK(hipMemsetAsync(h->d_B, 0, blk_bytes, h->stream));
+        if (h->low_count[i] > 0) {
+            hipLaunchKernelGGL(scatter_block, dim3((unsigned)((h->low_count[i] + 255) / 256), nb), dim3(256), 0,
+                               h->stream, h->d_keys, h->d_vals, h->low_first[i], h->low_count[i], h->d_B, ld,
+                               h->n_entries, bstride, 0);
+            HIPCHK(hipGetLastError());
+        }
+        // C = B * Linv_{i-1}^T      (src/tridiagonal_cholesky.jl:74).  B is zero left of column
+        // cmin and below row rmax, hence C is zero there too and only the rest is computed; inside that
+        // window row tile t of B -- and of C, Linv being lower triangular -- is zero left of kst[t].
+        return gemm(h, GemmCall(false, false, rm, W, W, 1.0, 0.0).a(h->d_B + cm, ld, bstride).b(Xp + (int64_t)cm * ld + cm, ld, pX)
+                           .c(C, ldc, pC).triangular(TRI_B_UPPER).k_begin(h->d_kst, nullptr));
+    }
+    // streamed bytes: C inside the staircase (written) + the rows of Linv from the first gathered column on (read)
+    ProfScope ps(h, 10, 8.0 * (h->c_streamed + 0.5 * (double)W * W) * (double)h->B);
+    if (r.kind == COUPLING_TILES) {
+        BxtTileArgs ta;
+        ta.rowptr = h->d_lo_rowptr + i * (h->bsp + 1); ta.lidx = h->d_bxt_lidx; ta.vals = h->d_vals; ta.n_entries = h->n_entries;
+        ta.uptr = h->d_bxt_uptr + i * (h->bxt_nrt + 1); ta.ucols = h->d_bxt_ucols;
+        ta.gtiles = h->d_bxt_gtiles + i * h->bxt_nrt * 3; ta.ng = r.ng;
+        ta.X = Xp; ta.C = C; ta.ld = ld; ta.ldc = ldc; ta.pX = pX; ta.pC = pC; ta.kst = h->d_kst;
+        ta.cm = cm; ta.rm = rm; ta.bsp = bsp; ta.ecap = h->bxt_ecap;
+        ta.skip_dead = r.skip_dead;
+        ta.nch = r.nch;
+        ta.nprob = (int)nb;
+        ta.zdst = nullptr; ta.zcount = 0; ta.zpdst = 0; ta.zwgs = 0;
+        ta.srowptr = nullptr; ta.skeys = nullptr; ta.svals = nullptr;
+        if (r.fill == FILL_SCATTER_ROLE) {
+            // one problem: the launch zeroes the WHOLE Schur block and scatters D_i into it row range by row range; the
+            // product then accumulates, S = 1.0 * S - C C^T -- the same single rounding fl(D - acc) as "S := -C C^T, then
+            // S += D_i", without the scatter launch (4.9 us + a boundary) between the product and the block's Cholesky
+            ta.zdst = h->d_S; ta.zcount = (int64_t)bsp * bsp; ta.zpdst = bstride; ta.zwgs = r.zwgs;
+            ta.srowptr = h->d_dg_rowptr + i * (h->bsp + 1); ta.skeys = h->d_keys; ta.svals = h->d_vals;
+        } else if (r.fill == FILL_ZERO_ROLE) {
+            ta.zdst = h->d_S + (int64_t)rm * ld; ta.zcount = (int64_t)(bsp - rm) * bsp; ta.zpdst = bstride; ta.zwgs = r.zwgs;
+        }
+        hipLaunchKernelGGL(spmm_bxt_tiles, dim3((unsigned)r.grid), dim3(256), bxt_tile_lds_bytes(h->bxt_ecap), h->stream, ta);
+    } else {
+        BxtArgs ba;
+        ba.rowptr = h->d_lo_rowptr + i * (h->bsp + 1); ba.keys = h->d_keys;
+        ba.vals = h->d_vals; ba.n_entries = h->n_entries;
+        ba.X = Xp; ba.C = C; ba.ld = ld; ba.ldc = ldc; ba.pX = pX; ba.pC = pC; ba.cm = cm; ba.rm = rm;
+        ba.kst = h->d_kst;
+        ba.cw = r.cw;
+        ba.bsp = bsp;
+        const dim3 grid((unsigned)r.grid);
+        if (r.km == 8) hipLaunchKernelGGL(spmm_bxt<8>, grid, dim3(256), 0, h->stream, ba);
+        else if (r.km == 16) hipLaunchKernelGGL(spmm_bxt<16>, grid, dim3(256), 0, h->stream, ba);
+        else hipLaunchKernelGGL(spmm_bxt<32>, grid, dim3(256), 0, h->stream, ba);
+    }
+    HIPCHK(hipGetLastError());
+    return GMRF_OK;
+}
+
+static gmrf_status factor_blocks_range(gmrf_handle* h, int64_t i0, int64_t i1) {
+    const int bsp = (int)h->bsp;
+    h->xsplit = planned_xsplit(h);                     // representation of the inverses this factorisation leaves
+    const int64_t ld = bsp;
+    const int64_t bstride = (int64_t)bsp * bsp;
     const unsigned nb = (unsigned)h->B;
     for (int64_t i = i0; i < i1; ++i) {
         double* L = l_block(h, i);
@@ -1619,7 +1781,6 @@ static gmrf_status factor_blocks_range(gmrf_handle* h, int64_t i0, int64_t i1) {
         // S = D_i - C C^T is built as  S := -C C^T (GEMM, beta = 0)  then  S += D_i (scatter): same
         // single rounding as D - acc, and only the rows the product does not write (>= rmax) need
         // zeroing -- a quarter of the block on darcy instead of all of it.  The first block has no product.
-        const int rm_s = (i > 0) ? (int)h->rmax : 0;
         if (h->fwd_run) {
             // t = b_i (the rows G2's tail does not write stay so)
             hipLaunchKernelGGL(factor_rhs_block, dim3((unsigned)((bsp + 255) / 256), nb), dim3(256), 0, h->stream, h->frhs, h->n, (int)h->bs,
@@ -1627,93 +1788,14 @@ static gmrf_status factor_blocks_range(gmrf_handle* h, int64_t i0, int64_t i1) {
             HIPCHK(hipGetLastError());
         }
         // (round 5: where the coupling product of this block runs on spmm_bxt_tiles, that launch zeroes the rows as well)
-        const bool scatter_in_bxt = i > 0 && nb == 1 && bxt_tiles && h->d_dg_rowptr && h->bsp == h->bs && !h->sw(GMRF_SW_NO_SCATTER_FOLD);
-        const bool zero_in_bxt = scatter_in_bxt || (i > 0 && bxt_tiles && ((int64_t)(bsp - rm_s) * bsp) % 2 == 0);
-        if (rm_s < bsp && !zero_in_bxt) {
-            const int64_t cnt = (int64_t)(bsp - rm_s) * bsp;
-            hipLaunchKernelGGL(zero_rows, dim3((unsigned)((cnt / 2 + 255) / 256), nb), dim3(256), 0, h->stream,
-                               h->d_S + (int64_t)rm_s * ld, cnt, bstride);
+        const CouplingRoute route = i > 0 ? coupling_route(h, i) : CouplingRoute();
+        const bool scatter_in_bxt = i > 0 && route.fill == FILL_SCATTER_ROLE;
+        if (i == 0) {
+            const int64_t cnt = (int64_t)bsp * bsp;
+            hipLaunchKernelGGL(zero_rows, dim3((unsigned)((cnt / 2 + 255) / 256), nb), dim3(256), 0, h->stream, h->d_S, cnt, bstride);
             HIPCHK(hipGetLastError());
-        }
-        if (i > 0) {
-            double* C = h->d_C + (i - 1) * cstride;              // stored window: rows 0 .. rm, columns cm ..
-            const double* Xp = h->d_Linv + (i - 1) * bstride;
-            const bool sparse_g1 = h->sparse_b && !h->sw(GMRF_SW_DENSE_COUPLING);
-            if (!sparse_g1) {          // dense image of B for the GEMM route
-                HIPCHK(hipMemsetAsync(h->d_B, 0, blk_bytes, h->stream));
-                if (h->low_count[i] > 0) {
-                    hipLaunchKernelGGL(scatter_block, dim3((unsigned)((h->low_count[i] + 255) / 256), nb), dim3(256), 0,
-                                       h->stream, h->d_keys, h->d_vals, h->low_first[i], h->low_count[i], h->d_B, ld,
-                                       h->n_entries, bstride, 0);
-                    HIPCHK(hipGetLastError());
-                }
-            }
-            // C = B * Linv_{i-1}^T      (src/tridiagonal_cholesky.jl:74).  B is zero left of column
-            // cmin and below row rmax, hence C is zero there too and only the rest is computed; inside that
-            // window row tile t of B -- and of C, Linv being lower triangular -- is zero left of kst[t].
-            const int cm = (int)h->cmin, rm = (int)h->rmax;
-            const int W = bsp - cm;
-            if (sparse_g1) {
-                BxtArgs ba;
-                ba.rowptr = h->d_lo_rowptr + i * (h->bsp + 1); ba.keys = h->d_keys;
-                ba.vals = h->d_vals; ba.n_entries = h->n_entries;
-                ba.X = Xp; ba.C = C; ba.ld = ld; ba.ldc = ldc; ba.pX = pX; ba.pC = pC; ba.cm = cm; ba.rm = rm;
-                ba.kst = h->d_kst;
-                const int rch = (rm + 255) / 256;
-                ba.cw = ((int64_t)(W / 64) * rch * nb >= 512) ? 64 : (((int64_t)(W / 32) * rch * nb >= 512) ? 32 : 16);
-                ba.bsp = bsp;
-                const dim3 grid((unsigned)((W / ba.cw) * rch * (int)nb));
-                // streamed bytes: C inside the staircase (written) + the rows of Linv from the first gathered column on (read)
-                ProfScope ps(h, 10, 8.0 * (h->c_streamed + 0.5 * (double)W * W) * (double)h->B);
-                if (bxt_tiles) {
-                    BxtTileArgs ta;
-                    ta.rowptr = ba.rowptr; ta.lidx = h->d_bxt_lidx; ta.vals = h->d_vals; ta.n_entries = h->n_entries;
-                    ta.uptr = h->d_bxt_uptr + i * (h->bxt_nrt + 1); ta.ucols = h->d_bxt_ucols;
-                    ta.gtiles = h->d_bxt_gtiles + i * h->bxt_nrt * 3; ta.ng = h->bxt_ng[(size_t)i];
-                    ta.X = Xp; ta.C = C; ta.ld = ld; ta.ldc = ldc; ta.pX = pX; ta.pC = pC; ta.kst = h->d_kst;
-                    ta.cm = cm; ta.rm = rm; ta.bsp = bsp; ta.ecap = h->bxt_ecap;
-                    static const bool live_skip = env_int("GMRF_BXT_LIVE", 0) != 0;      // tuning aid (measured: 4.1 vs 3.9 ms per step, off)
-                    ta.skip_dead = live_skip ? 1 : 0;
-                    const int chunks = W / 16, ng = ta.ng;
-                    // 16-column chunks per workgroup: the launch should be a whole number of rounds over the 3 workgroups a CU
-                    // holds (measured, darcy256 x 64, 4 groups x 48 chunks: 16 chunks = 768 workgroups = one round 85 us; 8 =
-                    // two rounds 96 us; 12 = 1.33 rounds 108 us; 24 = 2/3 round 99 us): rounds x (chunks + ~2 for the prologue)
-                    {
-                        const int64_t slots = 3 * (int64_t)std::max(h->cu_count, 1);
-                        int best = 1; int64_t best_cost = INT64_MAX;
-                        for (int c : {1, 2, 3, 4, 6, 8, 12, 16, 24, 48}) {
-                            if (c > chunks) break;
-                            const int64_t wgs = (int64_t)((chunks + c - 1) / c) * ng * nb;
-                            const int64_t cost = ((wgs + slots - 1) / slots) * (c + 2);
-                            if (cost < best_cost || (cost == best_cost && c < best)) { best = c; best_cost = cost; }
-                        }
-                        ta.nch = best;
-                    }
-                    const int ncg = (chunks + ta.nch - 1) / ta.nch;
-                    ta.nprob = (int)nb;
-                    ta.zdst = nullptr; ta.zcount = 0; ta.zpdst = 0; ta.zwgs = 0;
-                    ta.srowptr = nullptr; ta.skeys = nullptr; ta.svals = nullptr;
-                    if (scatter_in_bxt) {
-                        // one problem: the launch zeroes the WHOLE Schur block and scatters D_i into it row range by row range; the
-                        // product then accumulates, S = 1.0 * S - C C^T -- the same single rounding fl(D - acc) as "S := -C C^T, then
-                        // S += D_i", without the scatter launch (4.9 us + a boundary) between the product and the block's Cholesky
-                        ta.zdst = h->d_S; ta.zcount = (int64_t)bsp * bsp; ta.zpdst = bstride; ta.zwgs = 64;
-                        ta.srowptr = h->d_dg_rowptr + i * (h->bsp + 1); ta.skeys = h->d_keys; ta.svals = h->d_vals;
-                    } else if (zero_in_bxt && rm_s < bsp) {
-                        ta.zdst = h->d_S + (int64_t)rm_s * ld; ta.zcount = (int64_t)(bsp - rm_s) * bsp; ta.zpdst = bstride;
-                        ta.zwgs = (int)std::min<int64_t>(32, std::max<int64_t>(1, ta.zcount / 16384));      // >= 128 KB per workgroup
-                    }
-                    hipLaunchKernelGGL(spmm_bxt_tiles, dim3((unsigned)((ncg * ng + ta.zwgs) * (int)nb)), dim3(256), bxt_tile_lds_bytes(h->bxt_ecap),
-                                       h->stream, ta);
-                }
-                else if (h->lo_row_max <= 8) hipLaunchKernelGGL(spmm_bxt<8>, grid, dim3(256), 0, h->stream, ba);
-                else if (h->lo_row_max <= 16) hipLaunchKernelGGL(spmm_bxt<16>, grid, dim3(256), 0, h->stream, ba);
-                else hipLaunchKernelGGL(spmm_bxt<32>, grid, dim3(256), 0, h->stream, ba);
-                HIPCHK(hipGetLastError());
-            } else {
-                GCHK(gemm(h, GemmCall(false, false, rm, W, W, 1.0, 0.0).a(h->d_B + cm, ld, bstride).b(Xp + (int64_t)cm * ld + cm, ld, pX)
-                                 .c(C, ldc, pC).triangular(TRI_B_UPPER).k_begin(h->d_kst, nullptr)));
-            }
+        } else {
+            GCHK(launch_coupling(h, i, route));
             // S = D - C C^T: the product part (with the forward solve's tail row)
             GCHK(gemm(h, g2_product(h, i, scatter_in_bxt, h->fwd_run)));
         }
@@ -7709,6 +7791,133 @@ gmrf_status gmrf_test_sweep_product(int32_t device, int32_t force, const int64_t
     drop();
     HIPCHK(e);
     *route_out = r.id;
+    return GMRF_OK;
+}
+
+static void coupling_route_write(const CouplingRoute& r, int64_t* out) {
+    out[0] = r.kind; out[1] = r.km; out[2] = r.cw; out[3] = r.nch; out[4] = r.ncg; out[5] = r.ng; out[6] = r.grid; out[7] = r.fill;
+    out[8] = r.zwgs; out[9] = r.skip_dead;
+}
+
+// Host only, no device: what the symbolic phase plans for the coupling products of a CSC pattern, array by array, and the route
+// coupling_route takes on it.  group_tiles: build_symbolic's parameter (a handle passes B >= 8).  scal[12] = {cmin, rmax, most
+// entries in a row of a lower block, sparse_b, bxt_ok, ecap, nrt, then the lengths of kst, rowptr, gtiles, ucols, lidx}.  The arrays
+// (each may be NULL) are filled where cap[7] -- capacities of kst, rowptr, ng, gtiles, uptr, ucols, lidx in elements -- suffices:
+// kst [bsp / 64] as set_layout leaves it, rowptr [N][bsp + 1], and of a usable plan ng [N], gtiles [N][nrt][3], uptr [N][nrt + 1],
+// ucols, lidx [entries].  query (or NULL) = {B, CUs, block i, switches}: route[10] = {kind, KM, cw, nch, ncg, ng, grid, fill, zwgs,
+// skip_dead} of block i of a handle of B problems on a device of that many CUs.
+gmrf_status gmrf_test_coupling_plan(int64_t n, int64_t n_blocks, const int64_t* colptr, const int64_t* rowval, int32_t index_base,
+                                    int32_t group_tiles, int64_t* scal, int32_t* kst, int32_t* rowptr, int32_t* ng, int32_t* gtiles,
+                                    int32_t* uptr, int32_t* ucols, uint16_t* lidx, const int64_t* cap, const int64_t* query, int64_t* route) {
+    if (!colptr || !rowval || !scal || !cap) return bad_shape("null pointer");
+    if (n <= 0 || n_blocks <= 0 || n % n_blocks != 0) return bad_shape("n must be a positive multiple of N_blocks");
+    if (query && !route) return bad_shape("null pointer");
+    const int64_t bs = n / n_blocks, bsp = 64 * next_pow2((bs + 63) / 64);
+    if (query && (query[0] < 1 || query[0] > (1 << 20) || query[1] < 0 || query[2] < 1 || query[2] >= n_blocks))
+        return bad_shape("coupling plan: bad query");
+    std::vector<std::vector<HostEntry>> dg, lo;
+    GCHK(split_csc(n, n_blocks, bs, colptr, rowval, index_base, dg, lo));
+    SymbolicPlan sp;
+    build_symbolic(n_blocks, bsp, dg, lo, false, sp, group_tiles != 0);
+    std::vector<int> k;
+    layout_kst(bsp, sp.cmin, sp.rmax, sp.first, k);
+    scal[0] = sp.cmin; scal[1] = sp.rmax; scal[2] = sp.max_row; scal[3] = sp.sparse_b; scal[4] = sp.bxt_ok; scal[5] = sp.ecap;
+    scal[6] = sp.nrt; scal[7] = (int64_t)k.size(); scal[8] = (int64_t)sp.rowptr.size();
+    scal[9] = sp.bxt_ok ? (int64_t)sp.gtiles.size() : 0; scal[10] = sp.bxt_ok ? (int64_t)sp.ucols.size() : 0;
+    scal[11] = sp.bxt_ok ? (int64_t)sp.lidx.size() : 0;
+    auto put = [](auto* dst, int64_t capn, const auto& v) {
+        if (dst && capn >= (int64_t)v.size()) for (size_t q = 0; q < v.size(); ++q) dst[q] = v[q];
+    };
+    put(kst, cap[0], k);
+    put(rowptr, cap[1], sp.rowptr);
+    if (sp.bxt_ok) {
+        put(ng, cap[2], sp.ng); put(gtiles, cap[3], sp.gtiles); put(uptr, cap[4], sp.uptr); put(ucols, cap[5], sp.ucols);
+        put(lidx, cap[6], sp.lidx);
+    }
+    if (query) {
+        CouplingShape s;
+        s.bsp = (int)bsp; s.bs = (int)bs; s.cm = (int)sp.cmin; s.rm = (int)sp.rmax; s.nb = (int)query[0]; s.cus = (int)query[1];
+        s.sparse_b = sp.sparse_b; s.plan_ok = sp.bxt_ok && sp.nrt == (int)(sp.rmax / 64); s.has_drow = sp.keys.size() < ((size_t)1 << 31);
+        s.max_row = (int)sp.max_row; s.ng = s.plan_ok ? sp.ng[(size_t)query[2]] : 0; s.switches = (int32_t)query[3];
+        coupling_route_write(coupling_route(s), route);
+    }
+    return GMRF_OK;
+}
+
+// The next analysis of this handle plans the tile groups of spmm_bxt_tiles with group_tiles = mode (0: every tile alone, 1: grouped)
+// instead of by its batch (-1: by the batch again).
+gmrf_status gmrf_test_coupling_group_tiles(gmrf_handle* h, int32_t mode) {
+    if (!h || mode < -1 || mode > 1) return bad_shape("coupling test: bad arguments");
+    h->group_tiles_force = mode;
+    return GMRF_OK;
+}
+
+// One coupling step (launch_coupling, once, then a synchronisation) of block i on a handle that gmrf_bt_factor_begin_csc has
+// prepared: pattern analysed, values resident, factor storage allocated.  force = 0: coupling_route's own choice; 1: spmm_bxt;
+// 2: spmm_bxt_tiles on the handle's plan; 3: the dense GEMM.  over[4] (or NULL), 0 = own choice: cw in {16, 32, 64}; nch, one of the
+// launcher's list; skip_dead 1 = off, 2 = on; Schur fill 1 = nobody, 2 = the zero role, 3 = the scatter role.  X[B][bsp bsp] is
+// uploaded as Linv_{i-1} of every problem, C[nC] as the handle's whole d_C (every problem, every block), S[B][bsp bsp] as the
+// Schur work block; C and S are read back whole.  route_out[10] as gmrf_test_coupling_plan.  Refused with GMRF_ERR_BAD_SHAPE,
+// nothing uploaded or launched: a buffer of the wrong size, a route or override that the shape's own preconditions do not admit.
+gmrf_status gmrf_test_coupling_product(gmrf_handle* h, int64_t i, int32_t force, const int32_t* over, const double* X, int64_t nX,
+                                       double* C, int64_t nC, double* S, int64_t nS, int64_t* route_out) {
+    if (!h || !X || !C || !S || !route_out) return bad_shape("coupling test: null pointer");
+    GCHK(tw_refuse(h, "gmrf_test_coupling_product"));
+    if (!h->analyzed || !h->d_C || !h->d_S || !h->d_Linv || !h->d_B || h->alloc_B != h->B || h->vals_B != h->B || h->alloc_rm != h->rmax ||
+        h->alloc_wc != c_ld(h) || h->alloc_N != h->N || h->alloc_bsp != h->bsp)
+        return bad_shape("coupling test: the handle has not been through gmrf_bt_factor_begin_csc");
+    if (i < 1 || i >= h->N) return bad_shape("coupling test: block out of range");
+    if (force < 0 || force > 3) return bad_shape("coupling test: no such route");
+    const int64_t bsp = h->bsp, be = bsp * bsp * h->B;
+    if (nX != be || nS != be || nC != stride_pC(h) * h->B) return bad_shape("coupling test: a buffer has the wrong size");
+    const CouplingShape s = coupling_shape(h, i);
+    CouplingRoute r;
+    if (force == 0) r = coupling_route(s);
+    else {
+        if (force == 1 && !s.sparse_b) return bad_shape("coupling test: spmm_bxt holds rows of at most 32 entries");
+        if (force == 2 && !s.plan_ok) return bad_shape("coupling test: the handle has no usable tile plan");
+        r = coupling_route_of(s, force == 1 ? COUPLING_BXT : (force == 2 ? COUPLING_TILES : COUPLING_DENSE));
+    }
+    const int W = s.bsp - s.cm;
+    if (over) {
+        if (over[0]) {
+            if (r.kind != COUPLING_BXT || (over[0] != 16 && over[0] != 32 && over[0] != 64) || W % over[0]) return bad_shape("coupling test: bad cw");
+            r.cw = over[0];
+        }
+        if (over[1]) {
+            if (r.kind != COUPLING_TILES || std::find(std::begin(kBxtNch), std::end(kBxtNch), over[1]) == std::end(kBxtNch) || over[1] > W / 16)
+                return bad_shape("coupling test: bad nch");
+            r.nch = over[1];
+        }
+        if (over[2]) {
+            if (r.kind != COUPLING_TILES || over[2] < 0 || over[2] > 2) return bad_shape("coupling test: bad skip_dead");
+            r.skip_dead = over[2] - 1;
+        }
+        if (over[3] == 1) { r.fill = FILL_NONE; r.zwgs = 0; }
+        else if (over[3] == 2) {
+            if (r.kind != COUPLING_TILES || s.rm >= s.bsp) return bad_shape("coupling test: the zero role needs the tile route and rows below rmax");
+            r.fill = FILL_ZERO_ROLE; r.zwgs = coupling_zero_wgs(s);
+        } else if (over[3] == 3) {
+            if (r.kind != COUPLING_TILES || s.nb != 1 || s.bsp != s.bs || !s.has_drow)
+                return bad_shape("coupling test: the scatter role needs the tile route, one problem and unpadded blocks");
+            r.fill = FILL_SCATTER_ROLE; r.zwgs = 64;
+        } else if (over[3] != 0) return bad_shape("coupling test: bad fill");
+        coupling_grid(s, r);
+    }
+    HIPCHK(hipSetDevice(h->device));
+    const int64_t bstride = bsp * bsp;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    for (int64_t p = 0; p < h->B; ++p)
+        HIPCHK(hipMemcpyAsync(h->d_Linv + p * stride_pX(h) + (i - 1) * bstride, X + p * bstride, sizeof(double) * (size_t)bstride, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->d_C, C, sizeof(double) * (size_t)nC, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->d_S, S, sizeof(double) * (size_t)nS, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->factored = false; h->l_valid = false;
+    GCHK(launch_coupling(h, i, r));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpy(C, h->d_C, sizeof(double) * (size_t)nC, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(S, h->d_S, sizeof(double) * (size_t)nS, hipMemcpyDeviceToHost));
+    coupling_route_write(r, route_out);
     return GMRF_OK;
 }
 

@@ -211,18 +211,22 @@ __global__ __launch_bounds__(256) void spmm_bxt(BxtArgs a) {
     const double* __restrict__ vals = a.vals + (int64_t)prob * a.n_entries;
     int k0 = 0, len = 0;
     if (r < a.rm) { k0 = a.rowptr[r]; len = a.rowptr[r + 1] - k0; }
+    int lm = len;                                  // longest row of the wave bounds the entry loop
+    // a row shorter than that pads with (value 0, a column some row of the wave does hold): the product adds exact zeros and
+    // reads no column of X that B does not reference (column 0 need not be one: a window with cm > 0)
+    int jpad = len > 0 ? (int)(a.keys[k0] & 0xffffffffu) : -1;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) { lm = max(lm, __shfl_xor(lm, off)); jpad = max(jpad, __shfl_xor(jpad, off)); }
+    lm = __builtin_amdgcn_readfirstlane(lm);
+    jpad = max(__builtin_amdgcn_readfirstlane(jpad), 0);
     int jt[KM];
     double vt[KM];
 #pragma unroll
     for (int t = 0; t < KM; ++t) {
         const bool ok = t < len;
-        jt[t] = ok ? (int)(a.keys[k0 + t] & 0xffffffffu) : 0;
+        jt[t] = ok ? (int)(a.keys[k0 + t] & 0xffffffffu) : jpad;
         vt[t] = ok ? vals[k0 + t] : 0.0;
     }
-    int lm = len;                                  // longest row of the wave bounds the entry loop
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) lm = max(lm, __shfl_xor(lm, off));
-    lm = __builtin_amdgcn_readfirstlane(lm);
     // 16 columns at a time; the 256 x 16 results turn through LDS so that they leave as full
     // 128-byte lines (stores of 8 or 16 bytes a line apart cost one L2 transaction each and made
     // this kernel slower than the dense GEMM it replaces)

@@ -993,6 +993,34 @@ gmrf_status gmrf_test_sweep_product(int32_t device, int32_t force, const int64_t
                                     int64_t nP, int64_t x_off, int64_t b_off, int64_t o_off, const int32_t* kst, int64_t n_kst,
                                     const int32_t* mend, int64_t n_mend, int32_t* route_out);
 
+/* The coupling step of block i > 0 of a factorisation (C_i = B_i Linv_{i-1}^T into the stored window of C, and whoever clears the
+ * Schur block before S = D_i - C_i C_i^T) as a value.  route[10] = {kind (0 dense GEMM, 1 spmm_bxt, 2 spmm_bxt_tiles), KM of
+ * spmm_bxt, cw, nch, ncg, ng, workgroups of the product's launch (0: the GEMM's own), Schur fill (0 nobody, 1 zero_rows, 2 the zero
+ * role of spmm_bxt_tiles, 3 its scatter role), zwgs, skip_dead}.
+ * gmrf_test_coupling_plan: host only (no device).  The plan of the symbolic phase for a CSC pattern with build_symbolic's
+ * group_tiles flag (a handle passes batch >= 8): scal[12] = {cmin, rmax, most entries in a row of a lower block, sparse_b, bxt_ok,
+ * ecap, nrt, and the lengths of kst, rowptr, gtiles, ucols, lidx}; the arrays (each may be NULL) are filled where cap[7] = the
+ * capacities of {kst, rowptr, ng, gtiles, uptr, ucols, lidx} suffice: kst[bsp / 64] as the layout keeps it (monotone envelope,
+ * relative to cmin), rowptr[N][bsp + 1], and of a usable plan ng[N], gtiles[N][nrt][3], uptr[N][nrt + 1], ucols, lidx[entries].
+ * query (or NULL) = {batch, CUs of the device, block i, switches}: route[10] of that block.
+ * gmrf_test_coupling_group_tiles: the next analysis of the handle plans with group_tiles = mode (0 / 1; -1: by its batch again).
+ * gmrf_test_coupling_product: one coupling step of block i on a handle that gmrf_bt_factor_begin_csc has prepared (no step taken).
+ * force = 0: the library's own route; 1 spmm_bxt, 2 spmm_bxt_tiles on the handle's plan, 3 the dense GEMM.  over[4] (or NULL), 0 =
+ * own choice: {cw in 16 / 32 / 64, nch of the launcher's list, skip_dead 1 off / 2 on, Schur fill 1 nobody / 2 zero role / 3 scatter
+ * role}.  X[batch][bsp bsp] is uploaded as Linv_{i-1} of every problem, C[nC] as the handle's whole image of the coupling blocks
+ * (every problem, every block), S[batch][bsp bsp] as the Schur work block; C and S are read back whole.  One launch_coupling and
+ * a synchronisation, nothing else.  GMRF_ERR_BAD_SHAPE with nothing uploaded or launched: a buffer of the wrong size; a forced
+ * route or override the shape does not admit (tiles without a usable plan, spmm_bxt with rows of more than 32 entries, cw that does
+ * not divide the window, nch above its 16-column chunks, the zero role without rows below rmax, the scatter role with a batch or
+ * padded blocks). */
+gmrf_status gmrf_test_coupling_plan(int64_t n, int64_t n_blocks, const int64_t* colptr, const int64_t* rowval, int32_t index_base,
+                                    int32_t group_tiles, int64_t* scal, int32_t* kst, int32_t* rowptr, int32_t* ng, int32_t* gtiles,
+                                    int32_t* uptr, int32_t* ucols, uint16_t* lidx, const int64_t* cap, const int64_t* query,
+                                    int64_t* route);
+gmrf_status gmrf_test_coupling_group_tiles(gmrf_handle* h, int32_t mode);
+gmrf_status gmrf_test_coupling_product(gmrf_handle* h, int64_t i, int32_t force, const int32_t* over, const double* X, int64_t nX,
+                                       double* C, int64_t nC, double* S, int64_t nS, int64_t* route_out);
+
 #ifdef __cplusplus
 }
 #endif

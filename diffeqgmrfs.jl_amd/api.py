@@ -1055,6 +1055,7 @@ class FieldEvaluator:
         errors = ev.errors(DarcyConditioningBatch(F, asm, darcy).run(tables, q).mean, truth)              # (B, 3)
         ev = FieldEvaluator.line(nc, workloads.burgers_pred_coords(xs))
         errors = ev.errors(gn.posterior().x, truth, nt=nt, first_slice=1)                                # the scripts' [2:end, :]
+        std = ev.variance(F, nt, std=True); cal = ev.calibration(F, mean, truth, nt)     # error bars and calibration at the points
 
     The rows of E are computed once at creation, on the host, in double precision (include/gmrf_hip.h states the rules); `points`
     are host coordinates in any order.  Every value is ONE rounding sequence, w0 f[i0] then fma(wk, f[ik], .) in ascending dof
@@ -1162,6 +1163,67 @@ class FieldEvaluator:
         _cabi.check(_cabi.load().gmrf_eval_errors_batch(self._h, B, nt, int(first_slice), _cabi.ptr(f), _cabi.ptr(t), _cabi.ptr(out),
                                                         _cabi.ptr(pred)))
         return (out, pred) if return_pred else out
+
+    def pairs(self) -> Tuple[sp.csr_matrix, np.ndarray]:
+        """(P, pos): the pair table of the pointwise variance (gmrf_eval_pairs; no GPU needed).  P (ns, ns) is the pattern --
+        symmetric, both triangles, sorted, values 1.0 -- of exactly the dof pairs some point uses, with the diagonal of every dof
+        used; pos (width (width + 1) / 2, npts) int32 holds for point c and the pair a >= b of its row, at a (a + 1) / 2 + b, the
+        place of the entry (idx[c, a], idx[c, b]) in P's CSR order."""
+        lib, nnz = _cabi.load(), C.c_int64(0)
+        _cabi.check(lib.gmrf_eval_pairs(self._h, C.byref(nnz), None, None, None))
+        rp, ci = np.empty(self.ns + 1, dtype=np.int64), np.empty(int(nnz.value), dtype=np.int64)
+        pos = np.empty((self.width * (self.width + 1) // 2, self.npts), dtype=np.int32)
+        _cabi.check(lib.gmrf_eval_pairs(self._h, None, _cabi.ptr(rp), _cabi.ptr(ci), _cabi.ptr(pos)))
+        return sp.csr_matrix((np.ones(ci.size), ci, rp), shape=(self.ns, self.ns)), pos
+
+    def pair_pattern(self, nt: int = 1) -> sp.csr_matrix:
+        """I_nt (x) P as a sorted SciPy CSR matrix (nt ns, nt ns): the entries of Sigma that `variance` reads for a field of nt
+        slices, slice t on the dofs t ns .. (t + 1) ns - 1 as in `matrix(nt)`; the entry of `pairs()`'s pos sits at t nnz(P) + pos."""
+        if int(nt) < 1:
+            raise ValueError("nt >= 1")
+        K = sp.kron(sp.identity(int(nt), format="csr"), self.pairs()[0], format="csr")
+        K.sort_indices()
+        return K
+
+    def variance(self, F, nt: int = 1, out=None, std: bool = False):
+        """The pointwise predictive variance diag(E Sigma E^T) at the points, (batch, nt, npts), for the batch that the
+        `TridiagonalCholeskyFactor` F holds factored (F.N == nt * ns), exactly: the selected inverse on `pair_pattern(nt)` never
+        leaves the device and every value is ONE rounding sequence (gmrf_eval_var_batch), the same bits in every batch and on
+        every call.  `out`: a contiguous float64 array of that shape to fill -- NumPy, or a torch tensor on the device; default a
+        new NumPy array.  std=True: sqrt(max(v, 0)) in place of v.  F's pattern rule applies to the pairs (`selected_inverse`):
+        same or neighbouring block, the later index below rmax -- true for the pairs of the mesh F's matrix was assembled on."""
+        out = TridiagonalCholeskyFactor._out_array(out, (F.batch, int(nt), self.npts))
+        _cabi.check(_cabi.load().gmrf_eval_var_batch(self._h, F._h, int(nt), _cabi.ptr(out)))
+        if std:
+            if _is_torch(out):
+                out.clamp_(min=0.0).sqrt_()
+            else:
+                np.sqrt(np.maximum(out, 0.0, out=out), out=out)
+        return out
+
+    def calibration(self, F, fields, truth, nt: int = 1, first_slice: int = 0, zcrit: float = 1.96, return_pred: bool = False,
+                    return_var: bool = False):
+        """(B, 4) NumPy array of (mean z^2, coverage, mean log predictive density, min variance) per problem over the slices
+        [first_slice, nt): z = (E fields - truth) / sqrt(v) with v of `variance(F, nt)`, coverage the share of points with
+        |z| <= zcrit, the density's term -(log(2 pi v) + z^2) / 2.  fields (B, nt ns) or (B, nt, ns) -- the prediction's dofs, e.g.
+        the posterior means of the batch F factors -- and truth (B, nt npts) or (B, nt, npts): NumPy arrays or torch CUDA
+        tensors.  The same bits on every call.  A point with v <= 0 makes the first three inf or nan and shows in the fourth: look
+        at it first.  return_pred / return_var: also pred / the variances (B, nt npts), of the kind of `fields`, the bits of
+        `apply` / `variance`."""
+        nt = int(nt)
+        f, t = self._prep(fields, "fields"), self._prep(truth, "truth")
+        if f.ndim < 2 or int(np.prod(f.shape[1:], dtype=np.int64)) != nt * self.ns:
+            raise ValueError(f"fields must have shape (B, {nt} * {self.ns})")
+        B = f.shape[0]
+        if t.shape[0] != B or int(np.prod(t.shape[1:], dtype=np.int64)) != nt * self.npts:
+            raise ValueError(f"truth must have shape ({B}, {nt} * {self.npts})")
+        out = np.empty((B, 4), dtype=np.float64)
+        pred = PosteriorAssembler._like2(f, (B, nt * self.npts)) if return_pred else None
+        var = PosteriorAssembler._like2(f, (B, nt * self.npts)) if return_var else None
+        _cabi.check(_cabi.load().gmrf_eval_calibration_batch(self._h, F._h, B, nt, int(first_slice), float(zcrit), _cabi.ptr(f),
+                                                             _cabi.ptr(t), _cabi.ptr(out), _cabi.ptr(pred), _cabi.ptr(var)))
+        extra = tuple(a for a, want in ((pred, return_pred), (var, return_var)) if want)
+        return (out,) + extra if extra else out
 
 
 class ConditionedGMRF:

@@ -6,12 +6,15 @@
 // coalesce, the W reads of the field row are the only irregular access.  ONE rounding sequence for every result,
 //     pred = w0 f[idx0];  pred = fma(wk, f[idxk], pred), k = 1 .. W - 1,
 // so a point's value is the same bits in every batch, for every number of rows and on every call.  No atomics, no scratch.
+// The pointwise predictive variance diag(E Sigma E^T) and the calibration of pred under it follow the same scheme over the selected
+// inverse on the pair pattern (field_eval_pairs, field_eval_var, field_eval_calibration_part at the end of this file).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <algorithm>
 #include <cmath>
+#include <vector>
 
 #include "burgers_prior.hpp"        // block_sum_256 (selinv.hpp), block_max_256
 
@@ -63,6 +66,36 @@ inline void field_eval_tri_row(int order, int64_t nx, int64_t ny, double x, doub
         }
     }
     field_eval_sort_row(order == 1 ? 3 : 6, idx, w);
+}
+
+// Pair table of the rows idx [npts][W] (ascending within a row) over ns dofs: the pattern P (ns x ns, symmetric, both triangles,
+// sorted CSR) of exactly the dof pairs that some point uses -- the diagonal of every dof used among them -- and, for point c and
+// pair (a >= b) at k = a (a + 1) / 2 + b, the position pos[k npts + c] of the entry (idx_a, idx_b) of the lower triangle in P's CSR
+// order.  False if P has 2^31 entries or more (positions are 32-bit).
+inline bool field_eval_pairs(int W, int64_t npts, int64_t ns, const int64_t* idx, std::vector<int64_t>& rowptr,
+                             std::vector<int64_t>& colidx, std::vector<int32_t>& pos) {
+    std::vector<int64_t> keys;                          // row ns + column, both triangles
+    keys.reserve((size_t)(npts * W * W));
+    for (int64_t c = 0; c < npts; ++c) {
+        const int64_t* r = idx + c * W;
+        for (int a = 0; a < W; ++a)
+            for (int b = 0; b < W; ++b) keys.push_back(r[a] * ns + r[b]);
+    }
+    std::sort(keys.begin(), keys.end());
+    keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
+    if (keys.size() >= ((size_t)1 << 31)) return false;
+    rowptr.assign((size_t)ns + 1, 0);
+    colidx.resize(keys.size());
+    for (size_t e = 0; e < keys.size(); ++e) { rowptr[(size_t)(keys[e] / ns) + 1]++; colidx[e] = keys[e] % ns; }
+    for (int64_t r = 0; r < ns; ++r) rowptr[(size_t)r + 1] += rowptr[(size_t)r];
+    pos.resize((size_t)(npts * (W * (W + 1) / 2)));
+    for (int64_t c = 0; c < npts; ++c) {
+        const int64_t* r = idx + c * W;
+        for (int a = 0, k = 0; a < W; ++a)
+            for (int b = 0; b <= a; ++b, ++k)
+                pos[(size_t)(k * npts + c)] = (int32_t)(std::lower_bound(keys.begin(), keys.end(), r[a] * ns + r[b]) - keys.begin());
+    }
+    return true;
 }
 
 // ------------------------------------------------------------------------------------------------ kernels
@@ -129,6 +162,115 @@ __global__ __launch_bounds__(256) void field_eval_errors_part(const int32_t* __r
     if (threadIdx.x == 0) {
         double* o = part + (p * nch + c) * 3;
         o[0] = sd; o[1] = ss; o[2] = m;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ pointwise predictive variance
+// var = diag(E Sigma E^T) at the points: row c of E has W dofs i_0 < ... < i_{W-1} in one element, so
+//     v_c = sum_ab w_a w_b Sigma[i_a, i_b]
+// over W (W + 1) / 2 distinct entries of Sigma.  The pair table (field_eval_pairs below, built on the host at creation) holds the
+// spatial pattern P of those entries and, per point and pair (a >= b) at k = a (a + 1) / 2 + b, the position pos[k][c] of
+// (i_a, i_b) in P's CSR order; slice t of a space-time field reads I_nt (x) P at t nnz(P) + pos.  sig is the selected inverse on
+// that pattern (gmrf_bt_selinv), [problems][nt nnz(P)].  ONE rounding sequence,
+//     s_a = w_0 Sigma[a,0];  s_a = fma(w_b, Sigma[a,b], s_a), b = 1 .. W - 1;   v = w_0 s_0;  v = fma(w_a, s_a, v), a = 1 .. W - 1,
+// so a point's variance is the same bits in every batch and on every call.  No atomics, no scratch.
+__host__ __device__ constexpr int field_eval_pair(int a, int b) { return a >= b ? a * (a + 1) / 2 + b : b * (b + 1) / 2 + a; }
+
+// var[r][c] for the rows r = (problem, slice) = blockIdx.y, blockIdx.y + gridDim.y, ... < problems nt: grid as field_eval_apply.  A
+// thread keeps its point's weights and positions in registers over its rows; the W (W + 1) / 2 reads of sig are the only
+// irregular access.
+template <int W>
+__global__ __launch_bounds__(256) void field_eval_var(const int32_t* __restrict__ pos, const double* __restrict__ w, int64_t npts,
+                                                      int64_t nnzp, int64_t rows, const double* __restrict__ sig,
+                                                      double* __restrict__ var) {
+    constexpr int NP = W * (W + 1) / 2;
+    const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (c >= npts) return;
+    int32_t q[NP];
+    double a[W];
+#pragma unroll
+    for (int k = 0; k < NP; ++k) q[k] = pos[k * npts + c];
+#pragma unroll
+    for (int k = 0; k < W; ++k) a[k] = w[k * npts + c];
+    for (int64_t r = blockIdx.y; r < rows; r += gridDim.y) {
+        const double* s = sig + r * nnzp;       // row r = p nt + t: problem p's slice t starts at p (nt nnzp) + t nnzp
+        double e[NP];
+#pragma unroll
+        for (int k = 0; k < NP; ++k) e[k] = s[q[k]];
+        double v = 0.0;
+#pragma unroll
+        for (int i = 0; i < W; ++i) {
+            double si = a[0] * e[field_eval_pair(i, 0)];
+#pragma unroll
+            for (int j = 1; j < W; ++j) si = fma(a[j], e[field_eval_pair(i, j)], si);
+            v = i == 0 ? a[0] * si : fma(a[i], si, v);
+        }
+        var[r * npts + c] = v;
+    }
+}
+
+// Calibration of a prediction against a truth under those variances, problem p's nt field rows [nt][ns], truth and var
+// [nt npts], elements [first, nt npts): z = (pred - truth) / sqrt(v), pred formed as field_eval_errors_part forms it.  The
+// partition and the LDS trees are field_eval_errors_part's: part[p][c][4] = (sum z^2, #{|z| <= zcrit}, sum -(log(2 pi v) + z^2) / 2,
+// min v).  The count is an integer per thread and is summed as a double, which is exact below 2^53.  grid = (nch, batch).
+template <int W>
+__global__ __launch_bounds__(256) void field_eval_calibration_part(const int32_t* __restrict__ idx, const double* __restrict__ w,
+                                                                   int64_t npts, int64_t ns, int64_t nt,
+                                                                   const double* __restrict__ fields,
+                                                                   const double* __restrict__ truth, const double* __restrict__ var,
+                                                                   double zcrit, int64_t first, int64_t len,
+                                                                   double* __restrict__ part) {
+    __shared__ double red[256];
+    const int64_t c = blockIdx.x, p = blockIdx.y, nch = gridDim.x, n = nt * npts;
+    fields += p * nt * ns; truth += p * n; var += p * n;
+    double acc_z = 0.0, acc_l = 0.0, mn = __builtin_huge_val();
+    int cnt = 0;
+    const int64_t i0 = first + c * len + threadIdx.x, i1 = min(n, first + (c + 1) * len);
+    const int64_t dq = 256 / npts, dr = 256 % npts;
+    int64_t slice = i0 / npts, pt = i0 % npts;
+    for (int64_t i = i0; i < i1; i += 256) {
+        const double v = var[i], z = (field_eval_point<W>(idx, w, npts, pt, fields + slice * ns) - truth[i]) / sqrt(v);
+        acc_z = fma(z, z, acc_z);
+        cnt += fabs(z) <= zcrit ? 1 : 0;
+        acc_l += -0.5 * fma(z, z, log(6.283185307179586 * v));
+        mn = fmin(mn, v);
+        slice += dq; pt += dr;
+        if (pt >= npts) { pt -= npts; ++slice; }
+    }
+    const double sz = block_sum_256(acc_z, red);
+    __syncthreads();
+    const double sc = block_sum_256((double)cnt, red);
+    __syncthreads();
+    const double sl = block_sum_256(acc_l, red);
+    const double m = -block_max_256(-mn, red);
+    if (threadIdx.x == 0) {
+        double* o = part + (p * nch + c) * 4;
+        o[0] = sz; o[1] = sc; o[2] = sl; o[3] = m;
+    }
+}
+
+// out[p] = (mean z^2, coverage, mean log predictive density, min variance) from a problem's nch chunks, summed as
+// field_errors_finish sums its own.
+__global__ __launch_bounds__(256) void field_eval_calibration_finish(const double* __restrict__ part, int64_t nch, int64_t count,
+                                                                     double* __restrict__ out) {
+    __shared__ double red[256];
+    const int64_t p = blockIdx.y;
+    const double* q = part + p * nch * 4;
+    double acc_z = 0.0, acc_c = 0.0, acc_l = 0.0, mn = __builtin_huge_val();
+    for (int64_t c = threadIdx.x; c < nch; c += 256) {
+        acc_z += q[4 * c]; acc_c += q[4 * c + 1]; acc_l += q[4 * c + 2]; mn = fmin(mn, q[4 * c + 3]);
+    }
+    const double sz = block_sum_256(acc_z, red);
+    __syncthreads();
+    const double sc = block_sum_256(acc_c, red);
+    __syncthreads();
+    const double sl = block_sum_256(acc_l, red);
+    const double m = -block_max_256(-mn, red);
+    if (threadIdx.x == 0) {
+        out[4 * p] = sz / (double)count;
+        out[4 * p + 1] = sc / (double)count;
+        out[4 * p + 2] = sl / (double)count;
+        out[4 * p + 3] = m;
     }
 }
 

@@ -5536,10 +5536,18 @@ struct gmrf_eval : DevCtx {             // device -1: the rows only
     DevArr<int32_t> d_idx;              // [width][npts]
     DevArr<double> d_w;
     DevBuf arena, part;                 // host arguments of the current call (Staging); the chunk sums of the metrics
+    // pair table of the pointwise variance (field_eval_pairs): the spatial pattern P and the pairs' positions in it
+    std::vector<int64_t> p_rowptr, p_colidx;
+    std::vector<int32_t> pos;           // [width (width + 1) / 2][npts]
+    DevArr<int32_t> d_pos;
+    gmrf_csr* var_csr = nullptr;        // I_nt (x) P on the device, the pattern gmrf_bt_selinv is asked for; rebuilt when nt changes
+    int64_t var_nt = 0;
+    DevArr<double> d_var;               // [batch][nt][npts] of a calibration call that does not return the variances
 };
 
 gmrf_status gmrf_eval_destroy(gmrf_eval* e) {
     if (!e) return GMRF_OK;
+    if (e->var_csr) (void)gmrf_csr_destroy(e->var_csr);
     e->close();
     delete e;
     return GMRF_OK;
@@ -5554,8 +5562,11 @@ static gmrf_status eval_bad_point(int64_t c, const std::string& what, const char
 static gmrf_status eval_finish(std::unique_ptr<gmrf_eval, gmrf_status (*)(gmrf_eval*)>& guard, int32_t device, void* stream,
                                const char* who, gmrf_eval** out) {
     gmrf_eval* e = guard.get();
+    if (!field_eval_pairs(e->width, e->npts, e->ns, e->idx.data(), e->p_rowptr, e->p_colidx, e->pos))
+        return bad_shape((std::string(who) + ": the pair pattern of the points has 2^31 entries or more").c_str());
     GCHK(e->open(device, stream, hipStreamNonBlocking, who));
     if (e->device >= 0) {
+        GCHK(e->d_pos.upload(e->stream, e->pos));
         const int64_t W = e->width, np = e->npts;
         std::vector<int32_t> ti((size_t)(W * np));
         std::vector<double> tw((size_t)(W * np));
@@ -5626,6 +5637,15 @@ gmrf_status gmrf_eval_rows(const gmrf_eval* e, int64_t* ns_out, int64_t* width_o
     if (width_out) *width_out = e->width;
     if (idx) std::copy(e->idx.begin(), e->idx.end(), idx);
     if (w) std::copy(e->w.begin(), e->w.end(), w);
+    return GMRF_OK;
+}
+
+gmrf_status gmrf_eval_pairs(const gmrf_eval* e, int64_t* nnz_out, int64_t* rowptr, int64_t* colidx, int32_t* pos) {
+    if (!e) return bad_shape("null handle");
+    if (nnz_out) *nnz_out = (int64_t)e->p_colidx.size();
+    if (rowptr) std::copy(e->p_rowptr.begin(), e->p_rowptr.end(), rowptr);
+    if (colidx) std::copy(e->p_colidx.begin(), e->p_colidx.end(), colidx);
+    if (pos) std::copy(e->pos.begin(), e->pos.end(), pos);
     return GMRF_OK;
 }
 
@@ -6199,6 +6219,115 @@ gmrf_status gmrf_bt_trace_inv(gmrf_handle* h, const gmrf_csr* S, const double* d
     if (!out_dev) HIPCHK(hipMemcpyAsync(out, d_res, sizeof(double) * h->B * m, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     if (h->profiling) prof_collect(h);
+    return GMRF_OK;
+}
+
+// ------------------------------------------------------------- pointwise predictive variance at data-grid points (field_eval.hpp)
+// var = diag(E Sigma E^T): the selected inverse of the handle's factor on I_nt (x) P, P the evaluator's pair pattern, into the
+// handle's own Sigma buffer, then one quadratic form per (problem, slice, point) on the evaluator's stream.  The pattern matrix is
+// the evaluator's, so the handle's plan (keyed by the matrix id) holds across refactor_values and is rebuilt only after another
+// pattern was asked of the handle in between.
+static gmrf_status eval_var_sigma(gmrf_eval* e, gmrf_handle* h, int64_t nt, int64_t batch, const char* who) {
+    GCHK(tw_refuse(h, who));
+    if (!h->factored) { g_last_error = std::string(who) + " before factor"; return GMRF_ERR_NO_FACTOR; }
+    const int64_t nnzp = (int64_t)e->p_colidx.size(), ns = e->ns;
+    if (nt < 1 || h->n != nt * ns)
+        return bad_shape((std::string(who) + ": the factored n = " + std::to_string(h->n) + " is not nt * ns = " + std::to_string(nt) + " * " +
+                          std::to_string(ns)).c_str());
+    if (nt > (int64_t)0x7fffffff / std::max(nnzp, e->npts))
+        return bad_shape((std::string(who) + ": nt npts and nt nnz(P) must stay below 2^31").c_str());
+    if (h->device != e->device) return bad_shape((std::string(who) + ": the factor handle and the evaluator live on different devices").c_str());
+    if (batch >= 0 && batch != h->B)
+        return bad_shape((std::string(who) + ": batch = " + std::to_string(batch) + " but the handle factors " + std::to_string(h->B) +
+                          " problems").c_str());
+    if (!e->var_csr || e->var_nt != nt) {
+        std::vector<int64_t> rp((size_t)(nt * ns) + 1), ci((size_t)(nt * nnzp));
+        for (int64_t t = 0; t < nt; ++t) {
+            for (int64_t r = 0; r < ns; ++r) rp[(size_t)(t * ns + r)] = t * nnzp + e->p_rowptr[(size_t)r];
+            for (int64_t k = 0; k < nnzp; ++k) ci[(size_t)(t * nnzp + k)] = t * ns + e->p_colidx[(size_t)k];
+        }
+        rp[(size_t)(nt * ns)] = nt * nnzp;
+        const std::vector<double> zeros((size_t)(nt * nnzp), 0.0);          // (the values of a pattern matrix are never read)
+        if (e->var_csr) { (void)gmrf_csr_destroy(e->var_csr); e->var_csr = nullptr; }
+        GCHK(gmrf_csr_create(e->device, e->stream, nt * ns, nt * ns, rp.data(), ci.data(), zeros.data(), 0, 0, &e->var_csr));
+        e->var_nt = nt;
+    }
+    GCHK(selinv_ready(h, e->var_csr, who));
+    GCHK(ensure_sig(h));
+    GCHK(selinv_pattern(h, h->d_sig));
+    HIPCHK(hipStreamSynchronize(h->stream));            // (the evaluator's stream reads Sigma after this)
+    if (h->profiling) prof_collect(h);
+    return GMRF_OK;
+}
+
+static gmrf_status launch_eval_var(const gmrf_eval* e, const gmrf_handle* h, int64_t nt, double* d_var) {
+    const int64_t rows = h->B * nt, nnzp = (int64_t)e->p_colidx.size();
+    const dim3 grid((unsigned)((e->npts + 255) / 256), (unsigned)std::min<int64_t>(rows, 65535));
+    auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, e->stream, e->d_pos.get(), e->d_w.get(), e->npts, nnzp, rows, h->d_sig.get(), d_var);
+    };
+    if (e->width == 2) go(field_eval_var<2>);
+    else if (e->width == 3) go(field_eval_var<3>);
+    else go(field_eval_var<6>);
+    HIPCHK(hipGetLastError());
+    return GMRF_OK;
+}
+
+gmrf_status gmrf_eval_var_batch(gmrf_eval* e, gmrf_handle* h, int64_t nt, double* var_out) {
+    if (!e || !h) return bad_shape("null handle");
+    if (!var_out) return bad_shape("null pointer");
+    GCHK(e->ready("gmrf_eval_var_batch needs the device"));
+    GCHK(eval_var_sigma(e, h, nt, -1, "gmrf_eval_var_batch"));
+    double* d_var;
+    Staging args(e->arena);
+    args.out(var_out, sizeof(double) * h->B * nt * e->npts, &d_var);
+    GCHK(args.commit(e->stream));
+    GCHK(launch_eval_var(e, h, nt, d_var));
+    GCHK(args.flush(e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return GMRF_OK;
+}
+
+gmrf_status gmrf_eval_calibration_batch(gmrf_eval* e, gmrf_handle* h, int64_t batch, int64_t nt, int64_t first_slice, double zcrit,
+                                        const double* fields, const double* truth, double* out, double* pred_out, double* var_out) {
+    if (!e || !h) return bad_shape("null handle");
+    if (!fields || !truth || !out) return bad_shape("null pointer");
+    if (!batch_ok(batch)) return bad_shape("batch outside [1, 4096]");
+    if (nt < 1 || first_slice < 0 || first_slice >= nt || nt > (int64_t)0x7fffffff / e->npts)
+        return bad_shape("the slices [first_slice, nt) must not be empty (nt npts < 2^31)");
+    if (!(zcrit >= 0.0)) return bad_shape("zcrit must not be negative");
+    GCHK(e->ready("gmrf_eval_calibration_batch needs the device"));
+    GCHK(eval_var_sigma(e, h, nt, batch, "gmrf_eval_calibration_batch"));
+    const hipStream_t st = e->stream;
+    const int64_t n = nt * e->npts, first = first_slice * e->npts, count = n - first, nch = field_errors_chunks(count),
+                  len = (count + nch - 1) / nch;
+    const double *d_fields, *d_truth;
+    double *d_out, *d_pred, *d_var;
+    Staging args(e->arena);
+    args.in(fields, sizeof(double) * batch * nt * e->ns, &d_fields);
+    args.in(truth, sizeof(double) * batch * n, &d_truth);
+    args.out(out, sizeof(double) * batch * 4, &d_out);
+    args.out(pred_out, sizeof(double) * batch * n, &d_pred);
+    args.out(var_out, sizeof(double) * batch * n, &d_var);
+    GCHK(args.commit(st));
+    GCHK(e->part.reserve(st, sizeof(double) * (size_t)(batch * nch * 4)));
+    if (!d_var) {
+        GCHK(e->d_var.reserve(st, (size_t)(batch * n)));
+        d_var = e->d_var;
+    }
+    GCHK(launch_eval_var(e, h, nt, d_var));
+    if (d_pred) GCHK(launch_eval_apply(e, batch * nt, d_fields, d_pred));       // (the caller's copy; the sums form pred themselves)
+    auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)nch, (unsigned)batch), dim3(256), 0, st, e->d_idx.get(), e->d_w.get(), e->npts, e->ns, nt,
+                           d_fields, d_truth, (const double*)d_var, zcrit, first, len, e->part.as<double>());
+    };
+    if (e->width == 2) go(field_eval_calibration_part<2>);
+    else if (e->width == 3) go(field_eval_calibration_part<3>);
+    else go(field_eval_calibration_part<6>);
+    hipLaunchKernelGGL(field_eval_calibration_finish, dim3(1, (unsigned)batch), dim3(256), 0, st, e->part.as<double>(), nch, count, d_out);
+    HIPCHK(hipGetLastError());
+    GCHK(args.flush(st));
+    HIPCHK(hipStreamSynchronize(st));
     return GMRF_OK;
 }
 

@@ -753,6 +753,40 @@ gmrf_status gmrf_eval_apply_batch(gmrf_eval* e, int64_t rows, const double* fiel
 gmrf_status gmrf_eval_errors_batch(gmrf_eval* e, int64_t batch, int64_t nt, int64_t first_slice, const double* fields,
                                    const double* truth, double* errors_out, double* pred_out);
 
+/* Pointwise predictive variance and calibration at the points: var = diag(E Sigma E^T) with Sigma = A^-1 of a factored handle,
+ * exactly (no sampling).  Row c of E has width dofs i_0 < ... < i_{width-1} of one element, so
+ *     v_c = sum_ab w_a w_b Sigma[i_a, i_b]
+ * over width (width + 1) / 2 distinct entries of Sigma, which gmrf_bt_selinv gives on the device.
+ * gmrf_eval_pairs (works on a device -1 handle): the pair table, built at creation.  P is the ns x ns pattern -- symmetric, both
+ *   triangles stored, sorted CSR -- of exactly the dof pairs some point uses, the diagonal of every dof used among them.  nnz_out,
+ *   rowptr [ns + 1], colidx [nnz] (0-based) and pos [width (width + 1) / 2][npts] (32-bit), each NULL (not wanted) or HOST memory:
+ *   pos[a (a + 1) / 2 + b][c], a >= b, is the place of the entry (i_a, i_b) of the lower triangle in P's CSR order.  The variance of
+ *   a space-time field of nt slices needs Sigma on I_nt (x) P (slice t on the dofs t ns .. (t + 1) ns - 1), where that entry sits at
+ *   t nnz(P) + pos.
+ * gmrf_eval_var_batch: var_out [batch][nt][npts], host or device, for the batch of h, whose n must be nt ns.  The evaluator keeps one
+ *   gmrf_csr of I_nt (x) P (rebuilt only when nt changes); the call runs h's selected-inverse path on it into h's own Sigma buffer --
+ *   the plan is keyed by that matrix, so it holds across refactor_values -- and then ONE rounding sequence per (problem, slice, point):
+ *       s_a = w_0 Sigma[a,0], then s_a = fma(w_b, Sigma[a,b], s_a) for b = 1 .. width - 1;
+ *       v = w_0 s_0, then v = fma(w_a, s_a, v) for a = 1 .. width - 1,
+ *   the same bits in every batch and on every call, no atomics.  |v - exact form of the Sigma read| <= (2 width + 2) eps
+ *   sum_ab |w_a w_b Sigma_ab|; a variance that small against that sum can come out <= 0.
+ * gmrf_eval_calibration_batch: fields [batch][nt][ns] (the prediction's dofs, e.g. the posterior means of the batch h factors)
+ *   against truth [batch][nt][npts] under those variances -> out [batch][4] = (mean z^2, coverage, mean log predictive density,
+ *   min variance) over the slices [first_slice, nt): z = (pred - truth) / sqrt(v), coverage the share of points with |z| <= zcrit
+ *   (counted in integers), the density's term -(log(2 pi v) + z^2) / 2.  Fixed-shape sums on the partition of gmrf_eval_errors_batch:
+ *   the same bits on every call.  pred_out / var_out: NULL or [batch][nt][npts], the bits of gmrf_eval_apply_batch /
+ *   gmrf_eval_var_batch.  A point with v <= 0 makes the first three outputs inf or nan and shows in the fourth: look at it first.
+ *   batch must be h's; zcrit >= 0; fields, truth, out, pred_out, var_out: host or device.
+ * Errors: the selected inverse's own, with its message -- a twisted handle GMRF_ERR_BAD_SHAPE, no factor GMRF_ERR_NO_FACTOR, a pair
+ *   across two blocks whose later index is not below rmax (or across more than neighbouring blocks) GMRF_ERR_BAD_SHAPE naming the
+ *   entry -- and n != nt ns, nt npts or nt nnz(P) >= 2^31, another batch or a handle on another device: GMRF_ERR_BAD_SHAPE; a
+ *   device -1 evaluator: GMRF_ERR_NO_DEVICE.  Both calls wait for h's stream, run on the evaluator's and synchronise before they
+ *   return. */
+gmrf_status gmrf_eval_pairs(const gmrf_eval* e, int64_t* nnz_out, int64_t* rowptr, int64_t* colidx, int32_t* pos);
+gmrf_status gmrf_eval_var_batch(gmrf_eval* e, gmrf_handle* h, int64_t nt, double* var_out);
+gmrf_status gmrf_eval_calibration_batch(gmrf_eval* e, gmrf_handle* h, int64_t batch, int64_t nt, int64_t first_slice, double zcrit,
+                                        const double* fields, const double* truth, double* out, double* pred_out, double* var_out);
+
 /* Tangent, residual and load of the nonlinear elliptic benchmark -Lap u + u^3 = f_src (FEM block assembly, fourth piece;
  * /root/reference/_research/elliptic_chen24.jl) as its Gauss-Newton loop evaluates them per iteration (f_and_J, :280-285):
  *     J(w) = J_static + J_cube(w),  J_static[i][j] = int grad(phi_i).grad(phi_j)   (assemble_J_diff_and_f, :179-228)

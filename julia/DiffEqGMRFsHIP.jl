@@ -33,7 +33,8 @@ export TridiagonalCholeskyFactor, tridiagonal_cholesky, forward_solve, backward_
        GmrfComm, DarcyP1Assembler, BurgersP1Tangent, BurgersCollocationTangent, EllipticP1Tangent, elliptic_load!, GaussNewtonBatch, gauss_newton_batch!, DarcyConditioningBatch,
        BurgersP1Prior, BurgersLinePrior, prior_values_batch!, BurgersInitialConditionBatch, initial_condition_batch, solution_errors_batch,
        condition_on_observations_batch, assemble_batch!, logdet_batch, quadform_batch!, posterior!,
-       FieldEvaluator, FieldEvaluatorLine, FieldEvaluatorTriangles, evaluation_rows, evaluation_matrix, evaluate_fields, evaluation_errors
+       FieldEvaluator, FieldEvaluatorLine, FieldEvaluatorTriangles, evaluation_rows, evaluation_matrix, evaluate_fields, evaluation_errors,
+       evaluation_pairs, pair_pattern, evaluation_variance, evaluation_calibration
 
 const libgmrf = get(ENV, "LIBGMRF_HIP", joinpath(@__DIR__, "..", "diffeqgmrfs.jl_amd", "csrc", "libgmrf_hip.so"))
 
@@ -1012,6 +1013,55 @@ function evaluation_errors(e::FieldEvaluator, fields::Matrix{Float64}, truth::Ma
         (Ptr{Cvoid}, Int64, Int64, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
         e.handle, B, nt, first_slice, fields, truth, out, return_pred ? pointer(pred) : Ptr{Float64}(C_NULL)))
     return return_pred ? (out, pred) : out
+end
+
+# Pointwise predictive variance diag(E Sigma E') at the points and the calibration of a prediction under it: the selected inverse
+# of a factored handle on the evaluator's pair pattern, on the device (include/gmrf_hip.h, gmrf_eval_pairs and the two calls below).
+
+"`(P, pos)`: the pair pattern (ns x ns, symmetric, values 1.0) and, per pair `a >= b` of a point's row, the 1-based place of its entry in P's row-wise order"
+function evaluation_pairs(e::FieldEvaluator)
+    nnz_out = Ref{Int64}(0)
+    check(ccall((:gmrf_eval_pairs, libgmrf), Int32, (Ptr{Cvoid}, Ref{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int32}),
+        e.handle, nnz_out, C_NULL, C_NULL, C_NULL))
+    rowptr = Vector{Int64}(undef, e.ns + 1); colidx = Vector{Int64}(undef, nnz_out[])
+    pos = Matrix{Int32}(undef, e.npts, div(e.width * (e.width + 1), 2))
+    check(ccall((:gmrf_eval_pairs, libgmrf), Int32, (Ptr{Cvoid}, Ref{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int32}),
+        e.handle, nnz_out, rowptr, colidx, pos))
+    # (the CSR arrays of a symmetric pattern are its CSC arrays)
+    return SparseMatrixCSC(e.ns, e.ns, rowptr .+ 1, colidx .+ 1, ones(nnz_out[])), pos .+ Int32(1)
+end
+
+"`kron(I_nt, P)`: the entries of Sigma the variance of a field of `nt` slices reads"
+pair_pattern(e::FieldEvaluator; nt::Integer = 1) = kron(sparse(I, nt, nt), evaluation_pairs(e)[1])
+
+"the variances (nt npts x B) of the batch `F` holds factored (`F.N == nt * e.ns`); `std = true`: `sqrt(max(v, 0))`"
+function evaluation_variance(e::FieldEvaluator, F::TridiagonalCholeskyFactor; nt::Integer = 1, std::Bool = false)
+    var = Matrix{Float64}(undef, nt * e.npts, F.batch)
+    GC.@preserve var check(ccall((:gmrf_eval_var_batch, libgmrf), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Float64}),
+        e.handle, F.handle, nt, var))
+    return std ? sqrt.(max.(var, 0.0)) : var
+end
+
+"""
+    evaluation_calibration(e, F, fields, truth; nt = 1, first_slice = 0, zcrit = 1.96, return_pred = false, return_var = false)
+
+`(mean z^2, coverage, mean log predictive density, min variance)` per problem (4 x B) of `fields` (nt ns x B) against `truth`
+(nt npts x B) over the slices `first_slice + 1 : nt`, `z = (E fields - truth) / sqrt(v)` with `v` of `evaluation_variance`.  A point
+with `v <= 0` makes the first three inf or nan and shows in the fourth.
+"""
+function evaluation_calibration(e::FieldEvaluator, F::TridiagonalCholeskyFactor, fields::Matrix{Float64}, truth::Matrix{Float64};
+                                nt::Integer = 1, first_slice::Integer = 0, zcrit::Real = 1.96, return_pred::Bool = false,
+                                return_var::Bool = false)
+    B = size(fields, 2)
+    (size(fields, 1) == nt * e.ns && size(truth) == (nt * e.npts, B)) || throw(DimensionMismatch("fields nt ns x B, truth nt npts x B"))
+    out = Matrix{Float64}(undef, 4, B)
+    pred = return_pred ? Matrix{Float64}(undef, nt * e.npts, B) : nothing
+    var = return_var ? Matrix{Float64}(undef, nt * e.npts, B) : nothing
+    GC.@preserve fields truth out pred var check(ccall((:gmrf_eval_calibration_batch, libgmrf), Int32,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Int64, Float64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+        e.handle, F.handle, B, nt, first_slice, Float64(zcrit), fields, truth, out,
+        return_pred ? pointer(pred) : Ptr{Float64}(C_NULL), return_var ? pointer(var) : Ptr{Float64}(C_NULL)))
+    return (out, (return_pred ? (pred,) : ())..., (return_var ? (var,) : ())...)
 end
 
 # Linear shallow-water SPDE (src/spdes/shallow_water.jl): element kernels of assemble_system! (:17-122) and the per-step

@@ -50,7 +50,7 @@ EXPORTS = [
     "gmrf_bt_logdet_batch", "gmrf_assemble_quadform_batch", "gmrf_gn_posterior",
     "gmrf_eval_line_create", "gmrf_eval_tri_create", "gmrf_eval_destroy", "gmrf_eval_rows", "gmrf_eval_apply_batch", "gmrf_eval_errors_batch",
     "gmrf_eval_pairs", "gmrf_eval_var_batch", "gmrf_eval_calibration_batch",
-    "gmrf_test_gemm", "gmrf_test_gemm_desc", "gmrf_test_gemm_env", "gmrf_test_envelope", "gmrf_test_gemm_pair", "gmrf_test_gemm_rate", "gmrf_test_gemm_shapes", "gmrf_test_potrf_tile", "gmrf_test_potrf_block", "gmrf_test_potrf_route", "gmrf_test_tile_timing", "gmrf_test_persist_stamps", "gmrf_test_persist_aborts", "gmrf_test_factor_fwd", "gmrf_test_gn_route", "gmrf_test_dc_route", "gmrf_test_bic_route", "gmrf_test_var_groups", "gmrf_test_persist_budget", "gmrf_test_clock_probe_start", "gmrf_test_clock_probe_finish",
+    "gmrf_test_gemm", "gmrf_test_gemm_desc", "gmrf_test_gemm_env", "gmrf_test_gemm_sym", "gmrf_test_strict_lower", "gmrf_test_envelope", "gmrf_test_gemm_pair", "gmrf_test_gemm_rate", "gmrf_test_gemm_shapes", "gmrf_test_potrf_tile", "gmrf_test_potrf_block", "gmrf_test_potrf_route", "gmrf_test_tile_timing", "gmrf_test_persist_stamps", "gmrf_test_persist_aborts", "gmrf_test_factor_fwd", "gmrf_test_gn_route", "gmrf_test_dc_route", "gmrf_test_bic_route", "gmrf_test_var_groups", "gmrf_test_persist_budget", "gmrf_test_clock_probe_start", "gmrf_test_clock_probe_finish",
     "gmrf_test_mfma_f64_rate", "gmrf_test_hbm_rate", "gmrf_test_microbench", "gmrf_test_symbolic_csc", "gmrf_test_envelope_csc",
     "gmrf_test_spmm_plan", "gmrf_test_spmm_route", "gmrf_test_spmm_rows_batch",
     "gmrf_test_sweep_route", "gmrf_test_sweep_product",
@@ -241,6 +241,8 @@ def load() -> C.CDLL:
         "gmrf_test_gemm_shapes": [vp, P(dbl), i64, P(i64)],
         "gmrf_test_gemm_desc": [i32, i32, vp, vp] + [vp, i64] * 12 + [P(i32)],
         "gmrf_test_gemm_env": [i32, i32, vp, vp] + [vp, i64] * 11 + [i32, P(i32)],
+        "gmrf_test_gemm_sym": [i32, i32, vp, vp] + [vp, i64] * 11 + [i32, i32, P(i32)],
+        "gmrf_test_strict_lower": [i32],
         "gmrf_test_envelope": [vp, vp, vp, i64, P(i64), P(i32)],
         "gmrf_test_gemm_pair": [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp],
         "gmrf_test_gemm_rate": [i32, i64, i64, i64, i32, i32, i32, i32, i32, i32, P(dbl)],

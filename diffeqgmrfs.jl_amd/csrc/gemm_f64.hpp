@@ -84,6 +84,12 @@ struct GemmArgs {
     const GemmDirectOut* dout = nullptr;
     int64_t o_j0 = 0, o_n = 0;
     int o_cols = 0;
+    // (round 29) Strict-lower mode of a square lower-only product (lower_only with M == N): nothing strictly above the ELEMENT
+    // diagonal is needed, so a kernel MAY leave such elements of a diagonal tile as they are.  The 64 x 64 LDS-DMA kernels
+    // (gemm_f64_dma.hpp) then skip, in every diagonal tile, the six 16 x 16 MFMA blocks above its block diagonal (B stored
+    // [n][k]) or the 32 x 32 quadrant rows 0 .. 31 x columns 32 .. 63 (B stored [k][n]); every other kernel ignores the field
+    // and writes whole tiles.  Every element with row >= col keeps its bits either way.
+    int strict_lower = 0;
 };
 
 constexpr int GEMM_BM = 64;

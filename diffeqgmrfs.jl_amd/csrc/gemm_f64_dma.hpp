@@ -25,6 +25,7 @@
 // Summation order per output element = gemm_f64_mfma's (k ascending in steps of 8, even k then odd k inside a step
 // pair ... identical MFMA k-slot assignment), so results are bitwise those of the register-staged kernel.
 #pragma once
+#include <type_traits>
 #include "gemm_f64.hpp"
 
 namespace gmrf {
@@ -154,7 +155,28 @@ __device__ __forceinline__ void gemm_dma_body(const GemmArgs& g, const int bid, 
     const int li = lane & 15, lq = lane >> 4;
     // waves whose whole quadrant lies strictly above the block diagonal of a lower-only product only help with staging
     // (inside a 64 x 64 tile on the diagonal everything is computed, as gemm_f64_mfma does)
-    const bool idle = g.lower_only != 0 && ((n0 + wn) / 64 > (m0 + wm + BM / 2 - 1) / 64);
+    bool idle = g.lower_only != 0 && ((n0 + wn) / 64 > (m0 + wm + BM / 2 - 1) / 64);
+    // (round 29) GemmArgs::strict_lower, 64 x 64 tiles, on a diagonal tile of a triangular grid (workgroup-uniform; per wave
+    // everything below is wave-uniform: scalar branches).
+    //   B stored [k][n]: wave 1 (rows 0 .. 31, columns 32 .. 63) owns only elements strictly above the ELEMENT diagonal.  It is
+    //   idle as above -- its share of the requests, the waits and the barrier of every K step, nothing else -- unless the tile
+    //   carries the tail row (TAIL: the diagonal tiles are the tail's owners): then it still reads the two B fragments of its k
+    //   pair group and the tail row and does its four FMAs per step.
+    //   B stored [n][k] (the symmetric products of the factor): 16 x 16 granularity.  Six of the tile's sixteen MFMA blocks are
+    //   strictly upper; the ten others are dealt 3 / 2 / 2 / 3 over the waves -- an idle wave 1 alone would leave the tile as
+    //   long as it was, its three sisters' SIMDs as loaded as before -- by giving wave 1 the lower half of wave 2's quadrant:
+    //       wave 0: (0,0) (1,0) (1,1)    wave 1: (3,0) (3,1)    wave 2: (2,0) (2,1)    wave 3: (2,2) (3,2) (3,3)
+    //   A block's sum is the same MFMA sequence whichever wave runs it (k ascending, the same k slots): the same bits.  The
+    //   tail's partial sums stay with their waves (wave 1: columns 32 .. 63 of k pair group 0, from two fragment reads of its own).
+    bool strict_diag = false;
+    if constexpr (BM == 64 && BN == 64 && !A_T && !DOUT) strict_diag = g.strict_lower != 0 && g.lower_only == 1 && bm == bn;
+    const bool skipq = B_N && strict_diag && w == 1;
+    const bool diag16 = !B_N && strict_diag;
+    const bool tail_only = TAIL && skipq;
+    if (!TAIL) idle = idle || skipq;
+    // the wave's MFMA blocks (bit 2 i + j) and where they lie: wave 1's at rows 32 .., columns 0 .. instead of its quadrant's
+    const int omask = !diag16 ? 15 : (w == 1 ? 12 : (w == 2 ? 3 : 13));
+    const int dwm = (diag16 && w == 1) ? BM / 2 : wm, dwn = (diag16 && w == 1) ? 0 : wn;
 
     // ---- staging plan: per-lane byte offsets (relative to the operand's k0 column / row), one per DMA instruction
     uint32_t offa[NA], offb[NB];
@@ -246,7 +268,97 @@ __device__ __forceinline__ void gemm_dma_body(const GemmArgs& g, const int bid, 
 #pragma unroll
     for (int s = 0; s < DEPTH; ++s)
         if (s < nkt) issue(s, s);
-    for (int kt = 0; kt < nkt; ++kt) {
+    int kt_first = 0;
+    if constexpr (TAIL) {
+        if (tail_only) {
+            // (round 29) the wave of the skipped quadrant of a diagonal tile that carries the tail: a K loop of its own with the
+            // same requests, waits and barrier per step, the tail's operands and its four FMAs as in the loop below, no A
+            // fragments and no MFMA
+            for (int kt = 0; kt < nkt; ++kt) {
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                __builtin_amdgcn_s_barrier();
+                __builtin_amdgcn_sched_barrier(0);
+                if (kt + DEPTH < nkt) issue(kt + DEPTH, (kt + DEPTH) % STAGES);
+                const double* sm = gsm + (kt % STAGES) * ST;
+                const v2d b0 = *reinterpret_cast<const v2d*>(sm + fb[0] + (B_N ? tkg * 8 * BN : ((tkg * 8) ^ sb2[0])));
+                const v2d b1 = *reinterpret_cast<const v2d*>(sm + fb[1] + (B_N ? tkg * 8 * BN : ((tkg * 8) ^ sb2[1])));
+                const v2d ta = *reinterpret_cast<const v2d*>(sm + A_ST + B_ST + tkg * 8 + 2 * lq);
+                if (B_N) {
+                    tacc.x = fma(ta.x, b0.x, tacc.x); tacc.x = fma(ta.y, b1.x, tacc.x);
+                    tacc.y = fma(ta.x, b0.y, tacc.y); tacc.y = fma(ta.y, b1.y, tacc.y);
+                } else {
+                    tacc.x = fma(ta.x, b0.x, tacc.x); tacc.x = fma(ta.y, b0.y, tacc.x);
+                    tacc.y = fma(ta.x, b1.x, tacc.y); tacc.y = fma(ta.y, b1.y, tacc.y);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            kt_first = nkt;
+        }
+    }
+    if constexpr (BM == 64 && BN == 64 && !B_N && !A_T && !DOUT) {
+        if (diag16) {
+            // (round 29) the K loop of a strict-lower diagonal tile: the loop below with the wave's blocks (MASK, bit 2 i + j)
+            // chosen at compile time -- the same requests, waits and barrier per step, the fragments its blocks need, their
+            // MFMAs in the order of the loop below, the tail as there (TX: wave 1, whose tail columns are not its blocks')
+            auto run = [&](auto mask_c, auto tx_c) {
+                constexpr int MASK = decltype(mask_c)::value;
+                constexpr bool TX = decltype(tx_c)::value;
+                // (TX: wave 1) its blocks' rows lie 32 rows of the A image behind its quadrant's, their columns 32 rows of the B
+                // image in front of it: the same swizzle (it depends on the row's low four bits), 32 * 16 doubles away.  The
+                // tail's columns are the quadrant's.
+                constexpr int ash = TX ? 32 * 16 : 0, bsh = TX ? -32 * 16 : 0;
+                for (int kt = 0; kt < nkt; ++kt) {
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                    __builtin_amdgcn_s_barrier();
+                    __builtin_amdgcn_sched_barrier(0);
+                    if (kt + DEPTH < nkt) issue(kt + DEPTH, (kt + DEPTH) % STAGES);
+                    const double* sm = gsm + (kt % STAGES) * ST;
+                    v2d a[BK / 8][2], b[BK / 8][2];
+#pragma unroll
+                    for (int kg = 0; kg < BK / 8; ++kg) {
+#pragma unroll
+                        for (int i = 0; i < 2; ++i) {
+                            a[kg][i] = (v2d){0.0, 0.0};
+                            if ((MASK >> (2 * i)) & 3) a[kg][i] = *reinterpret_cast<const v2d*>(sm + ash + fa[i] + ((kg * 8) ^ sa2[i]));
+                        }
+#pragma unroll
+                        for (int j = 0; j < 2; ++j) b[kg][j] = *reinterpret_cast<const v2d*>(sm + bsh + fb[j] + ((kg * 8) ^ sb2[j]));
+                    }
+                    v2d ta = (v2d){0.0, 0.0}, tb0 = ta, tb1 = ta;
+                    if constexpr (TAIL) {
+                        ta = *reinterpret_cast<const v2d*>(sm + A_ST + B_ST + tkg * 8 + 2 * lq);
+                        if constexpr (TX) {
+                            tb0 = *reinterpret_cast<const v2d*>(sm + fb[0] + ((tkg * 8) ^ sb2[0]));
+                            tb1 = *reinterpret_cast<const v2d*>(sm + fb[1] + ((tkg * 8) ^ sb2[1]));
+                        }
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                    for (int kg = 0; kg < BK / 8; ++kg)
+#pragma unroll
+                        for (int p = 0; p < 2; ++p)
+#pragma unroll
+                            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                                for (int j = 0; j < 2; ++j)
+                                    if ((MASK >> (2 * i + j)) & 1)
+                                        acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(p ? a[kg][i].y : a[kg][i].x, p ? b[kg][j].y : b[kg][j].x,
+                                                                                         acc[i][j], 0, 0, 0);
+                    if constexpr (TAIL) {
+                        if constexpr (!TX) { tb0 = tkg ? b[1][0] : b[0][0]; tb1 = tkg ? b[1][1] : b[0][1]; }
+                        tacc.x = fma(ta.x, tb0.x, tacc.x); tacc.x = fma(ta.y, tb0.y, tacc.x);
+                        tacc.y = fma(ta.x, tb1.x, tacc.y); tacc.y = fma(ta.y, tb1.y, tacc.y);
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            };
+            if (w == 1) run(std::integral_constant<int, 12>{}, std::true_type{});
+            else if (w == 2) run(std::integral_constant<int, 3>{}, std::false_type{});
+            else run(std::integral_constant<int, 13>{}, std::false_type{});
+            kt_first = nkt;
+        }
+    }
+    for (int kt = kt_first; kt < nkt; ++kt) {
         static_assert(DEPTH == 1, "no tile is requested behind tile kt: the wait is for all of the wave's requests");
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
@@ -338,7 +450,28 @@ __device__ __forceinline__ void gemm_dma_body(const GemmArgs& g, const int bid, 
 #pragma unroll
         for (int jp = 0; jp < NJ / 2; ++jp) mu[jp] = *reinterpret_cast<const v2d*>(gsm + 8 * BN + wn + jp * 32 + 2 * li);
     }
-    if (B_N) {
+    if (tail_only) {
+        // (the skipped quadrant: no addend loads, no stores -- C keeps what it held there; the tail's sums follow below)
+    } else if (diag16) {
+        // the wave's blocks of a strict-lower diagonal tile; the six blocks strictly above the diagonal keep what C held
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+                if (omask & (1 << (2 * i + j))) {
+                    double d[4] = {0.0, 0.0, 0.0, 0.0};
+                    if (beta != 0.0) {
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) d[r] = Dm[(int64_t)(m0 + dwm + i * 16 + lq + 4 * r) * ldd + n0 + dwn + j * 16 + li];
+                    }
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        double v = alpha * acc[i][j][r];
+                        if (beta != 0.0) v += beta * d[r];
+                        C[(int64_t)(m0 + dwm + i * 16 + lq + 4 * r) * g.ldc + n0 + dwn + j * 16 + li] = v;
+                    }
+                }
+    } else if (B_N) {
         v2d d[MI][4][NJ / 2 > 0 ? NJ / 2 : 1];
         if (beta != 0.0) {
 #pragma unroll
@@ -450,6 +583,14 @@ inline int& gemm_dma_force() {          // tests: 0 = by policy, 1 / 2 / 3 = thi
     return v;
 }
 
+// (round 29, moved by a test hook only) non-zero: the launchers below drop GemmArgs::strict_lower -- every diagonal tile is
+// computed whole, as before round 29.  Read when a launch is issued, so when a factor graph is CAPTURED: a graph replays what
+// it was captured with.
+inline int& gemm_strict_lower_off() {
+    static int v = 0;
+    return v;
+}
+
 // 0: not a DMA launch; 1: 64 x 64; 2: 128 x 64; 3: 64 x 128
 inline int gemm_dma_shape(bool a_t, const GemmArgs& g, int batch) {
     const int policy = gemm_dma_force() ? 2 : gemm_dma_policy();
@@ -526,6 +667,7 @@ inline bool gemm_try_dma_tail(hipStream_t st, bool a_t, bool b_n, const GemmArgs
     GemmArgs gs = g;
     gs.lower_only = tri_grid ? 1 : 0;
     gs.tri |= gemm_dma_row_order(g);
+    if (gemm_strict_lower_off()) gs.strict_lower = 0;
     const int64_t nx = g.N / 64, ny = g.M / 64;
     const dim3 grid((unsigned)((tri_grid ? ny * (ny + 1) / 2 : nx * ny) * batch)), block(256);
     const size_t lds = (size_t)DMA_STAGES * (64 + 64 + DMA_BK) * DMA_BK * sizeof(double);
@@ -551,6 +693,7 @@ inline bool gemm_try_dma(hipStream_t st, bool a_t, bool b_n, const GemmArgs& g, 
     GemmArgs gs = g;
     gs.lower_only = tri_grid ? 1 : (g.lower_only ? 2 : 0);
     gs.tri |= gemm_dma_row_order(g);
+    if (gemm_strict_lower_off()) gs.strict_lower = 0;
     const dim3 block(256);
 #define GMRF_DMA_GO(BM, BN)                                                                                       \
     do {                                                                                                          \
@@ -598,6 +741,7 @@ inline bool gemm_try_dma_grouped(hipStream_t st, bool b_n0, const GemmArgs& g0, 
     for (GemmArgs& g : gs) {                                     // (as gemm_try_dma sets a launch of its own up)
         g.tri |= gemm_dma_row_order(g);
         g.lower_only = (g.lower_only && g.M == g.N) ? 1 : 0;
+        if (gemm_strict_lower_off()) g.strict_lower = 0;
     }
     const int wg0 = (int)gemm_dma_grid64(g0, batch), wg1 = (int)gemm_dma_grid64(g1, batch);
     const int bn = (b_n0 ? 1 : 0) | (b_n1 ? 2 : 0);

@@ -401,6 +401,7 @@ struct GemmCall {
     const double* B = nullptr; int64_t ldb = 0, pB = 0;
     double* C = nullptr; int64_t ldc = 0, pC = 0;
     int tri = 0, lower_only = 0;       // TRI_* of the operands; only the tiles on and below the block diagonal
+    bool strict = false;               // with lower(): nothing strictly above the ELEMENT diagonal is needed (GemmArgs::strict_lower)
     int batch = 1; int64_t sA = 0, sB = 0, sC = 0;                 // products per problem, and their strides
     const double* D = nullptr; int64_t ldd = 0, pD = 0;            // addend (null: C, in place)
     int pclass = 0; double pwork = -1.0;                           // statistics class (0: by kernel) and work (< 0: the product's flops)
@@ -419,6 +420,7 @@ struct GemmCall {
     GemmCall& c(double* p, int64_t ld, int64_t pp) { C = p; ldc = ld; pC = pp; return *this; }
     GemmCall& triangular(int flags) { tri = flags; return *this; }
     GemmCall& lower() { lower_only = 1; return *this; }
+    GemmCall& strict_lower(bool on = true) { strict = on; return *this; }
     GemmCall& batched(int n, int64_t sa, int64_t sb, int64_t sc) { batch = n; sA = sa; sB = sb; sC = sc; return *this; }
     GemmCall& addend(const double* p, int64_t ld, int64_t pp) { D = p; ldd = ld; pD = pp; return *this; }
     GemmCall& work(double w, int cls = 0) { pwork = w; pclass = cls; return *this; }
@@ -440,6 +442,7 @@ static void gemm_fill(const gmrf_handle* h, const GemmCall& c, GemmArgs& g) {
     g.D = c.D; g.ldd = c.ldd; g.pD = c.pD;
     g.M = c.M; g.N = c.N; g.K = c.K; g.tri = c.tri; g.lower_only = c.lower_only; g.alpha = c.alpha; g.beta = c.beta; g.stamps = nullptr;
     g.kb_m = c.kb_m; g.kb_n = c.kb_n; g.ke_n = c.ke_n; g.ke_m = c.ke_m;
+    g.strict_lower = (c.strict && c.lower_only && c.M == c.N) ? 1 : 0;
 }
 
 // Runs one GEMM launch on the handle's GEMM stream -- run(stream, begin, end) -> hipError_t; when profiling, with an event pair
@@ -1117,6 +1120,15 @@ static int potrf_route(const gmrf_handle* h) {
     return (nt >= 4 && nt % 4 == 0) ? ROUTE_PANELS256 : ROUTE_STEPS;
 }
 
+// (round 29) May the symmetric products into the Schur block S -- G2, the rank-256 updates, the 128^2 S_BB update -- leave the
+// 16 x 16 blocks strictly above the diagonal of S's diagonal tiles unwritten (GemmCall::strict_lower)?  Only where every reader
+// of a diagonal tile of S has been read for it ([r29]: the 256-column panel route of batches, whose readers are
+// potrf_diag128 / potrf_diag128_slim and the persistent diagonal-block launch); one problem, the twisted order and the
+// launch-per-step route keep whole tiles.
+static bool strict_lower_route(const gmrf_handle* h) {
+    return h->B > 1 && potrf_route(h) == ROUTE_PANELS256 && !h->tw && !h->tw_half && h->tw_blk < 0;
+}
+
 // The split the next factorisation of this handle will use (0: none): only the 256-column panel route of batches
 // assembles the inverse level by level, and only a coupling window that starts at cmin >= 256 leaves a first block
 // column nobody multiplies with.  p = the largest power of two <= cmin (the doubling tree splits at powers of two).
@@ -1293,7 +1305,7 @@ static GemmCall g2_product(const gmrf_handle* h, int64_t i, bool accumulate, boo
     const double* C = h->d_C + (i - 1) * c_blk(h);
     const GemmTail tg{h->d_fy + (i - 1) * bsp + cm, h->n_pad, h->d_ft, bsp, nullptr, 0, 1.0};
     return GemmCall(false, false, rm, rm, bsp - cm, -1.0, accumulate ? 1.0 : 0.0).a(C, c_ld(h), stride_pC(h)).b(C, c_ld(h), stride_pC(h))
-        .c(h->d_S, bsp, (int64_t)bsp * bsp).lower().work(2.0 * 64.0 * 64.0 * h->g2_tile_k * (double)h->B)
+        .c(h->d_S, bsp, (int64_t)bsp * bsp).lower().strict_lower(strict_lower_route(h)).work(2.0 * 64.0 * 64.0 * h->g2_tile_k * (double)h->B)
         .k_begin(h->d_kst, h->d_kst).tail_ops(tail ? &tg : nullptr);
 }
 // The 256-column panel at column tile j of a block (S, L, X) with rows below it, and the bounds `ev` of its envelope (env_panel):
@@ -1323,7 +1335,7 @@ static GemmCall panel_update(const gmrf_handle* h, double* S, double* L, double*
     const PanelBelow lb = panel_below(h, L, X, j);
     const GemmTail tu{fy + oa, h->n_pad, h->d_ft + oc, ld, nullptr, 0, 1.0};
     return GemmCall(false, false, m3 * 64, m3 * 64, 256, -1.0, 1.0).a(lb.Lb, ld, lb.pLb).b(lb.Lb, ld, lb.pLb).c(S + oc * ld + oc, ld, ld * ld)
-        .lower().work(2.0 * 64.0 * 64.0 * 64.0 * ev.units_upd * (double)h->B).k_begin(ev.upd_kb, ev.upd_kb).k_hints()
+        .lower().strict_lower(strict_lower_route(h)).work(2.0 * 64.0 * 64.0 * 64.0 * ev.units_upd * (double)h->B).k_begin(ev.upd_kb, ev.upd_kb).k_hints()
         .tail_ops(fy ? &tu : nullptr);
 }
 
@@ -1453,7 +1465,7 @@ static gmrf_status potrf_block(gmrf_handle* h, double* S, double* L, double* X, 
                 // 192 + 256 workgroups per 64 problems in front of the second diagonal block instead of a launch on either side of it
                 GCHK(gemm_pair(h,
                                GemmCall(false, false, 128, 128, 128, -1.0, 1.0).a(L + ob * ld + oa, ld, sa.pL).b(L + ob * ld + oa, ld, sa.pL)
-                                   .c(S + ob * ld + ob, ld, sa.pS).lower().work(2.0 * t3 * 2.0 * 3.0 * nb),
+                                   .c(S + ob * ld + ob, ld, sa.pS).lower().strict_lower(strict_lower_route(h)).work(2.0 * t3 * 2.0 * 3.0 * nb),
                                GemmCall(false, true, 128, 128, 128, 1.0, 0.0).a(L + ob * ld + oa, ld, sa.pL).b(X + oa * ld + oa, ld, sa.pX)
                                    .c(T + ob * ld + oa, ld, pW).triangular(TRI_B_LOWER)));
                 GCHK(diag128(j + 2));
@@ -7146,8 +7158,11 @@ static gmrf_status gemm_desc_run(int32_t device, int32_t route, const int64_t* d
                                  const double* D, int64_t nD, const double* tA, int64_t ntA, double* tC, int64_t ntC,
                                  const double* tD, int64_t ntD, const int32_t* kb_m, int64_t n_kb_m, const int32_t* kb_n,
                                  int64_t n_kb_n, const int32_t* ke_n, int64_t n_ke_n, double* samples, int64_t n_samples,
-                                 double* mean, int64_t n_mean, int32_t* family, const int32_t* ke_m, int64_t n_ke_m, int32_t grouped) {
+                                 double* mean, int64_t n_mean, int32_t* family, const int32_t* ke_m, int64_t n_ke_m, int32_t grouped,
+                                 int32_t strict_lower = 0) {
     if (!desc || !abt || !A || !B || !C || !family) return bad_shape("gemm desc test: null pointer");
+    if (strict_lower != 0 && strict_lower != 1) return bad_shape("gemm desc test: strict_lower is 0 or 1");
+    if (strict_lower && (desc[6] != 1 || desc[0] != desc[1])) return bad_shape("gemm desc test: strict_lower needs a square lower-only product");
     *family = 0;
     const int64_t M = desc[0], N = desc[1], K = desc[2];
     const bool a_t = desc[3] != 0, b_n = desc[4] != 0;
@@ -7238,6 +7253,7 @@ static gmrf_status gemm_desc_run(int32_t device, int32_t route, const int64_t* d
     g.ptA = ptA; g.ptC = ptC; g.ptD = ptD;
     g.stamps = nullptr;
     g.dout = d_out; g.o_j0 = o_j0; g.o_n = o_n; g.o_cols = (int)o_cols;
+    g.strict_lower = strict_lower;
 
     const int saved_big = gemm_big_policy(), saved_ll = gemm_ll_policy(), saved_dma = gemm_dma_policy(), saved_force = gemm_dma_force();
     auto restore = [&]() { gemm_big_policy() = saved_big; gemm_ll_policy() = saved_ll; gemm_dma_policy() = saved_dma; gemm_dma_force() = saved_force; };
@@ -7304,6 +7320,26 @@ gmrf_status gmrf_test_gemm_env(int32_t device, int32_t route, const int64_t* des
                                int32_t grouped, int32_t* family) {
     return gemm_desc_run(device, route, desc, abt, A, nA, B, nB, C, nC, D, nD, tA, ntA, tC, ntC, tD, ntD, kb_m, n_kb_m, kb_n, n_kb_n,
                          ke_n, n_ke_n, nullptr, 0, nullptr, 0, family, ke_m, n_ke_m, grouped);
+}
+// gmrf_test_gemm_env with GemmArgs::strict_lower (0 / 1; 1 needs lower_only = 1 and M == N).  The 64 x 64 LDS-DMA launches --
+// route 3, its grouped forms and the tail route 6 -- then leave, in every diagonal tile, the six 16 x 16 blocks above its block
+// diagonal (B stored [n][k]) or the quadrant rows 0 .. 31 x columns 32 .. 63 (B stored [k][n]) as C held them; the other routes
+// take the field and write whole tiles.
+gmrf_status gmrf_test_gemm_sym(int32_t device, int32_t route, const int64_t* desc, const double* abt,
+                               const double* A, int64_t nA, const double* B, int64_t nB, double* C, int64_t nC,
+                               const double* D, int64_t nD, const double* tA, int64_t ntA, double* tC, int64_t ntC,
+                               const double* tD, int64_t ntD, const int32_t* kb_m, int64_t n_kb_m, const int32_t* kb_n,
+                               int64_t n_kb_n, const int32_t* ke_n, int64_t n_ke_n, const int32_t* ke_m, int64_t n_ke_m,
+                               int32_t grouped, int32_t strict_lower, int32_t* family) {
+    return gemm_desc_run(device, route, desc, abt, A, nA, B, nB, C, nC, D, nD, tA, ntA, tC, ntC, tD, ntD, kb_m, n_kb_m, kb_n, n_kb_n,
+                         ke_n, n_ke_n, nullptr, 0, nullptr, 0, family, ke_m, n_ke_m, grouped, strict_lower);
+}
+// Process-wide: enabled = 0 makes every launcher drop GemmArgs::strict_lower (whole diagonal tiles, the launches of before round
+// 29), 1 (the default) honours it.  Read when a launch is issued -- for a handle, when its factor graph is captured.
+gmrf_status gmrf_test_strict_lower(int32_t enabled) {
+    if (enabled != 0 && enabled != 1) return bad_shape("gmrf_test_strict_lower: 0 or 1");
+    gemm_strict_lower_off() = enabled ? 0 : 1;
+    return GMRF_OK;
 }
 // The envelope bounds of the analysed pattern (gmrf_handle::env_lo / env_hi: [n_blocks][bsp / 64], in-block columns) and what the
 // factorisation does with them: *state = 0 none computed (blocks not a multiple of 256), 1 computed but trivial for every panel

@@ -919,6 +919,20 @@ gmrf_status gmrf_test_gemm_env(int32_t device, int32_t route, const int64_t* des
                                const double* tD, int64_t ntD, const int32_t* kb_m, int64_t n_kb_m, const int32_t* kb_n,
                                int64_t n_kb_n, const int32_t* ke_n, int64_t n_ke_n, const int32_t* ke_m, int64_t n_ke_m,
                                int32_t grouped, int32_t* family);
+/* gmrf_test_gemm_env with GemmArgs::strict_lower (0 / 1; 1 needs lower_only = 1 and M == N): nothing strictly above the element
+ * diagonal is needed.  The 64 x 64 LDS-DMA launches (route 3, grouped or not, and the tail route 6) then leave, in every diagonal
+ * tile, the six 16 x 16 blocks above its block diagonal (B stored [n][k]) or the quadrant rows 0 .. 31 x columns 32 .. 63 (B stored
+ * [k][n]) as C held them; the other routes take the field and write whole tiles. */
+gmrf_status gmrf_test_gemm_sym(int32_t device, int32_t route, const int64_t* desc, const double* abt,
+                               const double* A, int64_t nA, const double* B, int64_t nB, double* C, int64_t nC,
+                               const double* D, int64_t nD, const double* tA, int64_t ntA, double* tC, int64_t ntC,
+                               const double* tD, int64_t ntD, const int32_t* kb_m, int64_t n_kb_m, const int32_t* kb_n,
+                               int64_t n_kb_n, const int32_t* ke_n, int64_t n_ke_n, const int32_t* ke_m, int64_t n_ke_m,
+                               int32_t grouped, int32_t strict_lower, int32_t* family);
+/* Process-wide switch for comparisons: enabled = 0 makes every GEMM launcher drop the strict-lower mode (whole diagonal tiles),
+ * 1 (the default) honours it.  It is read when a launch is issued, which for a handle is when its factor graph is CAPTURED: set
+ * it before the handle's first factorisation (or use a fresh handle) -- a captured graph replays the launches it was taken with. */
+gmrf_status gmrf_test_strict_lower(int32_t enabled);
 /* The envelope bounds the symbolic phase derived per block and 64-row tile ([n_blocks][bsp / 64] each, in-block columns; blocks that
  * are a multiple of 256): lo = first column of D_i in the rows S = D_i - C C^T leaves untouched, rounded down to 64 (0 elsewhere),
  * hi = end of D_i's columns inside lo's 256-column panel, rounded up to 64 (the panel's end for a tile inside that panel, bsp
